@@ -1,8 +1,18 @@
 """bench.py -- headline benchmark of the MI355X HGEMM hot path (driver contract: one JSON line).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload M_N_K[:fp16|fp32]]
+                    [--dump-outputs DIR] [--full [--no-shapes] [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs the W warm-up and K timed steps, writes the outputs if --dump-outputs is given, and prints the
+JSON line (headline + `roofline`, whose clock rides on the timed launches themselves).  --full adds everything that takes
+runs of its own: `shapes` (hipBLASLt / rocBLAS on BASELINE's shapes, incl. the hipBLASLt autotune) and `cpu_baseline`.
+
+--dump-outputs DIR writes, after the timed steps, the C matrices the last timed step computed: one DIR/c_set<i>.npy (float32)
+per rotating operand set written in that step, rank 0's when N > 1 (the operands are seeded, so the same arguments give the
+same inputs).  When all of them exceed DUMP_BUDGET_BYTES together, each file holds the same fixed sample of C's elements
+instead: flat row-major indices drawn once by numpy.random.default_rng(0) without replacement, sorted, a 1-D array.
 
 Workload (config.workload): BASELINE.json configs[2], the 4096x4096x4096 fp16-accumulate HGEMM -- the single-GPU
 configuration whose MFMA utilisation BASELINE.json asks for (configs[1], 64x4096x64, is a 7-microsecond
@@ -28,10 +38,10 @@ Extra objects on the JSON line:
                 `traffic` (HBM + Infinity-Cache bytes per launch) is NOT measured in this run: it is read from the
                 committed rocprofv3 PMC summary named in `traffic_source` (profiles/), collected as
                 MI355X_MICROARCH.md prescribes (separate --pmc passes, FETCH_SIZE doubled on gfx950)
-  cpu_baseline  the reference's CPU oracle expression (fp32 torch.matmul on the host, rounded to fp16) timed on
+  cpu_baseline  (--full) the reference's CPU oracle expression (fp32 torch.matmul on the host, rounded to fp16) timed on
                 rank 0 (any N: after the timed region, while the other ranks wait in the closing barrier) over a bounded
                 sample of the same shape
-  shapes        BASELINE.json's three single-GPU shapes: device-timed TFLOP/s of ours, hipBLASLt heuristic AND
+  shapes        (--full) BASELINE.json's three single-GPU shapes: device-timed TFLOP/s of ours, hipBLASLt heuristic AND
                 autotune (tn, nn), rocBLAS; the reference-style host wall-clock (sync either side of each call);
                 our per-call time inside a 32-launch hipGraph replay; a roofline entry per shape
 """
@@ -59,6 +69,7 @@ HBM_PEAK_TBPS = 8.0            # HBM3E spec, MI355X_MICROARCH.md
 BASELINE3 = [("64_4096_64", "fp32"), ("512_4096_4096", "fp32"), ("4096_4096_4096", "fp16")]
 WORKLOAD = ("4096_4096_4096", "fp16")
 EVENT_STRIDE = 16              # every 16th launch of the timed region carries dispatch-attached timing events
+DUMP_BUDGET_BYTES = 32 << 20   # --dump-outputs: float32 bytes written in all
 
 
 PLAN_FLAGS = (("fused_split_k", 0x10000), ("nt_store", 0x20000), ("streamk", 0x40000), ("xcd_stagger", 0x80000), ("nt_loads", 0x100000),
@@ -136,6 +147,25 @@ class Problem:
         s = self.sets[self.i % len(self.sets)]
         self.i += 1
         return s
+
+
+def dump_outputs(prob: Problem, last_step_sets: list[int], out_dir: Path) -> dict:
+    """Write the C of every operand set the last timed step wrote (each set always gets the same product, so its C is what
+    that step's launches on it returned) as float32 .npy files; a fixed seeded element sample when over DUMP_BUDGET_BYTES."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    numel = prob.m * prob.n
+    per_set = min(numel, DUMP_BUDGET_BYTES // 4 // len(last_step_sets))
+    idx = None
+    if per_set < numel:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(numel, per_set, replace=False))).to(prob.sets[0][3].device)
+    for s in last_step_sets:
+        c = prob.sets[s][3]
+        out = (c.float() if idx is None else c.reshape(-1)[idx].float()).cpu().numpy()
+        np.save(out_dir / f"c_set{s}.npy", out)
+    return {"dir": str(out_dir), "files": [f"c_set{s}.npy" for s in last_step_sets], "dtype": "float32",
+            "elements_per_file": per_set, "sampled": idx is not None}
 
 
 def launch_ours(lib, prob: Problem, stream: int):
@@ -367,9 +397,14 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1024, help="GEMM problems per step (one C-ABI call each)")
     ap.add_argument("--workload", type=str, default=":".join(WORKLOAD), help="M_N_K[:fp16|fp32] (default: BASELINE.json configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-shapes", action="store_true", help="skip the per-shape report (ours / hipBLASLt / rocBLAS on BASELINE's shapes)")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/c_set<i>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the per-shape report and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-shapes", action="store_true", help="with --full: skip the per-shape report (ours / hipBLASLt / rocBLAS on BASELINE's shapes)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0 or args.batch < 1:
+        ap.error("--steps and --batch must be >= 1, --warmup >= 0")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a MI355X (torch.cuda.is_available() is False); there is no CPU fallback")
@@ -425,6 +460,8 @@ def main(argv=None):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    last_step_sets = sorted({(prob.i - 1 - j) % len(prob.sets) for j in range(min(args.batch, len(prob.sets)))})
+    dumped = dump_outputs(prob, last_step_sets, args.dump_outputs) if args.dump_outputs is not None and rank == 0 else None
 
     wall_per_call_us = elapsed / (args.steps * args.batch) * 1e6     # this rank's clock, before the reduction over ranks
     elapsed, total_flops = reduce_over_ranks(elapsed, prob.flops * args.batch * args.steps, device)
@@ -462,8 +499,10 @@ def main(argv=None):
                    "plan": plan_dict(cname, sp.value, gm.value)},
         "roofline": roof,
     }
+    if dumped is not None:
+        result["outputs"] = dumped
     if rank == 0:
-        if not args.no_shapes:
+        if args.full and not args.no_shapes:
             others = [Problem(m_, a_, device) for m_, a_ in BASELINE3 if (m_, a_) != (mnk, acc)]
             result["shapes"] = per_shape_report(lib, others + [prob], stream)
             sp_h = [v["speedup_vs_hipblaslt_heur_max"] for v in result["shapes"].values()]
@@ -478,7 +517,7 @@ def main(argv=None):
                 lt_us = w["ours_us"] * w["speedup_vs_hipblaslt_auto_max"]     # speedup = hipBLASLt time / our time
                 result["vs_hipblaslt_autotune_max"] = {"ratio": round(w["speedup_vs_hipblaslt_auto_max"], 4), "ours_tflops": round(w["ours_tflops"], 1),
                                                        "hipblaslt_tflops": round(prob.flops / lt_us * 1e-6, 1), "clock": "HIP events, back-to-back launches, same run"}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0, any N (north_star: the 2 / 4 / 8-GPU figures stand "next to torch.matmul on the box's host CPU cores ... in
             # the same run").  The other ranks wait in the closing barrier meanwhile: their timed regions are over.
             result["cpu_baseline"] = cpu_baseline([(mnk, acc)], seconds=12.0 if world == 1 else 6.0)

@@ -13,7 +13,7 @@ timeout 200 $T check --configs $Q --shapes 1000_516_192,960_388_320,584_1004_448
 LD_LIBRARY_PATH=$P/lib_q192 timeout 100 $T check --configs q192x192_w2x2 --shapes 1000_516_192,1000_520_192,960_388_320,192_192_64,3072_3072_448 > $O/check_q192x192_after_fix.log 2>&1; tail -1 $O/check_q192x192_after_fix.log
 timeout 1200 python -m pytest tests -m gpu -x -q 2>&1 | tail -4
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-timeout 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 300 $O/bench.json; echo
+timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 300 $O/bench.json; echo
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --no-shapes --no-cpu-baseline > $O/bench_profiled.json 2> $O/prof.err; echo "rocprof rc=$?"
 timeout 300 python tests/tools/verify_plans.py --out $O/parity_1000.jsonl 2>&1 | tail -1
 find $O -name "*.db" -delete 2>/dev/null; find $O -name "*agent_info.csv" -delete; find $O/prof -name "*kernel_trace.csv" -size +20M -delete; du -sh $O

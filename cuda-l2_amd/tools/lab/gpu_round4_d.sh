@@ -11,7 +11,7 @@ T=cuda-l2_amd/bin/hgemm_tune
 timeout 400 $T check > $O/check_final.log 2>&1; echo "check rc=$?"; tail -1 $O/check_final.log
 HGEMM_RECORD_DIR=$O/records timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -6
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-timeout 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 600 $O/bench.json; echo
+timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 600 $O/bench.json; echo
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --no-shapes --no-cpu-baseline > $O/bench_profiled.json 2> $O/prof.err; echo "rocprof rc=$?"
 python cuda-l2_amd/tools/pmc_table.py shapes > $O/pmc_shapes.txt
 sed -i 's/timeout 240 rocprofv3/timeout 80 rocprofv3/' cuda-l2_amd/tools/pmc_table.sh

@@ -38,7 +38,7 @@ done
 find $O -name "*_agent_info.csv" -delete; find $O -name "*kernel_trace.csv" -delete
 # (3) bench.py again (its `vs_hipblaslt_autotune_max.hipblaslt_tflops` field had the ratio inverted in call D's record), with the
 # rocprofv3 kernel stats of the same command, so that the committed bench line, profiled line and CSV come from one tree
-timeout 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 300 $O/bench.json; echo
+timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 300 $O/bench.json; echo
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --no-shapes --no-cpu-baseline > $O/bench_profiled.json 2> $O/prof.err; echo "rocprof rc=$?"
 find $O -name "*.db" -delete 2>/dev/null; find $O -name "*agent_info.csv" -delete; find $O -name "*kernel_trace.csv" -size +2M -delete
 du -sh $O

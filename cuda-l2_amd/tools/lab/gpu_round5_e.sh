@@ -16,5 +16,5 @@ for f in check_all check_q_walk; do grep -q " 0 failures" $O/$f.log || { echo "C
 timeout 900 $T tune --shape-file cuda-l2_amd/tuning/r05_retune_pass3_shapes.txt --cand-file cuda-l2_amd/tuning/r05_retune_pass3_candidates.txt --rank both --baselines --stream --out $O/retune3.jsonl > $O/retune3.log 2>&1; echo "retune3 rc=$? lines=$(wc -l < $O/retune3.jsonl)"
 timeout 900 python tests/tools/verify_plans.py --plans $O/retune3.jsonl --top 3 --out $O/retune3_parity.jsonl 2>&1 | tail -1
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$? $(tail -1 $O/pytest_gpu.log)"
-timeout 300 python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['roofline']['frac'], d['roofline']['launch_us'], d['roofline']['wall_per_call_us'], d.get('vs_hipblaslt_autotune_max'))"
+timeout 300 python bench.py --steps 10 --warmup 3 --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['roofline']['frac'], d['roofline']['launch_us'], d['roofline']['wall_per_call_us'], d.get('vs_hipblaslt_autotune_max'))"
 du -sh $O

@@ -19,7 +19,7 @@ timeout 400 $T check --shapes 64_64_4096,128_64_8192,80_48_2080,256_256_2048,33_
 HGEMM_RECORD_DIR=$O/records timeout 1800 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$? $(tail -1 $O/pytest_gpu.log)"
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
 timeout 300 $T tune --plan-only --baselines --stream --shape-file cuda-l2_amd/tools/offgrid_shapes.txt --out $O/offgrid_plan_report.jsonl > $O/offgrid_plan_report.log 2>&1; echo "offgrid report lines=$(wc -l < $O/offgrid_plan_report.jsonl)"
-timeout 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 400 $O/bench.json; echo
+timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 400 $O/bench.json; echo
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --no-shapes --no-cpu-baseline > $O/bench_profiled.json 2> $O/prof.err; echo "rocprof rc=$?"
 python cuda-l2_amd/tools/pmc_table.py shapes > $O/pmc_shapes.txt; wc -l $O/pmc_shapes.txt
 sed -i 's/timeout 240 rocprofv3/timeout 100 rocprofv3/' cuda-l2_amd/tools/pmc_table.sh

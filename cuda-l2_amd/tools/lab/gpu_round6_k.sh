@@ -20,7 +20,7 @@ HGEMM_RECORD_DIR=$O/records timeout 2700 python -m pytest tests -m gpu -q > $O/p
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
 export HGEMM_AUTOTUNE_CACHE=$PWD/cuda-l2_amd/tuning/r06_hipblaslt_autotune_cache.txt
 timeout 400 $T tune --plan-only --baselines --stream --interleave --shape-file cuda-l2_amd/tools/offgrid_shapes.txt --out $O/offgrid_plan_report.jsonl > $O/offgrid_plan_report.log 2>&1; echo "offgrid report lines=$(wc -l < $O/offgrid_plan_report.jsonl)"
-timeout 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 400 $O/bench.json; echo
+timeout 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; head -c 400 $O/bench.json; echo
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --no-shapes --no-cpu-baseline > $O/bench_profiled.json 2> $O/prof.err; echo "rocprof rc=$?"
 python cuda-l2_amd/tools/pmc_table.py shapes > $O/pmc_shapes.txt; wc -l $O/pmc_shapes.txt
 sed -i 's/timeout 240 rocprofv3/timeout 150 rocprofv3/' cuda-l2_amd/tools/pmc_table.sh

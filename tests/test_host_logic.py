@@ -797,3 +797,33 @@ def test_autotune_cache_file_is_read_and_counts_records(lib, tmp_path):
     assert lib.hgemm_hipblaslt_autotune_cache_stats(None, None) == 0
     assert lib.hgemm_hipblaslt_autotune_from_cache(1) == 0
     assert lib.hgemm_hipblaslt_autotune_find_best_tn(64, 4096, 64, 0) == -5     # HGEMM_ERR_NOT_READY: no init, no GPU
+
+
+def test_bench_dump_outputs_writes_the_c_of_each_set_as_float32(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 file per operand set, the whole C while it fits the budget, else the same seeded
+    sample of flat indices in every file; --steps / --batch below 1 are refused before anything touches a device."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    torch.manual_seed(0)
+    p = bench.Problem("96_80_64", "fp16", "cpu")
+    for a, b, _, c in p.sets:
+        c.copy_((a.float() @ b.float()).half())
+    info = bench.dump_outputs(p, [0, 2], tmp_path / "whole")
+    assert info["files"] == ["c_set0.npy", "c_set2.npy"] and not info["sampled"]
+    for s in (0, 2):
+        got = np.load(tmp_path / "whole" / f"c_set{s}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, p.sets[s][3].float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 4 * 1000)
+    info = bench.dump_outputs(p, [1, 3], tmp_path / "sample")
+    assert info["sampled"] and info["elements_per_file"] == 1000
+    idx = np.sort(np.random.default_rng(0).choice(96 * 80, 1000, replace=False))
+    for s in (1, 3):
+        got = np.load(tmp_path / "sample" / f"c_set{s}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, p.sets[s][3].float().numpy().reshape(-1)[idx])
+    for bad in (["--steps", "0"], ["--batch", "0"]):
+        with pytest.raises(SystemExit) as e:
+            bench.main(bad)
+        assert e.value.code == 2
