@@ -57,6 +57,14 @@ char*  g_lent_ptr = nullptr;
 size_t g_lent_bytes = 0;
 int    g_lent_device = -1;
 
+// the calling thread's stream-capture mode is relaxed while one of these lives (see its uses)
+struct RelaxedCapture {
+  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+  bool ok;
+  RelaxedCapture() { ok = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess; if (!ok) (void)hipGetLastError(); }
+  ~RelaxedCapture() { if (ok && hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) (void)hipGetLastError(); }
+};
+
 // slab_bytes of fp32 slab space (+ counters) for a launch on `stream`; HGEMM_ERR_NO_WORKSPACE when a lent
 // buffer is too small or the allocation fails -- the caller then degrades to a plan that needs none.
 constexpr int HGEMM_ERR_NO_WORKSPACE_INTERNAL = -100;
@@ -90,12 +98,7 @@ int ensure_workspace(size_t slab_bytes, hipStream_t stream, float** slabs, unsig
     // global mode (this call's own stream does not, see above; the legacy stream cannot even be asked) they would
     // invalidate that capture.  The thread's capture mode is switched to relaxed around them, which is the documented
     // way for a library to allocate next to somebody else's capture.
-    struct RelaxedCapture {
-      hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-      bool ok;
-      RelaxedCapture() { ok = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess; if (!ok) (void)hipGetLastError(); }
-      ~RelaxedCapture() { if (ok && hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) (void)hipGetLastError(); }
-    } relaxed;
+    RelaxedCapture relaxed;
     const size_t old = w->bytes;   // (read before the buffer is let go: the growth below is geometric in the OLD size)
     if (w->ptr && w->captured) {
       g_ws_retired.push_back(w->ptr);
@@ -355,8 +358,14 @@ const TunedPlan* find_tuned(int M, int N, int K) {
 // model ranks q128x256 first, q256x256 at two splits measures 11 % faster)
 struct RankedPlan { double us; int cfg, splits, group_m; };
 bool neighbour_plan(int M, int N, int K, int* cfg, int* splits, int* group_m, RankedPlan* ranked = nullptr, int* n_ranked = nullptr) {
-  auto record = [&](double us, int c, int sp, int g) {
-    if (ranked && n_ranked && *n_ranked < 8) ranked[(*n_ranked)++] = RankedPlan{us, c, sp, g};
+  double best = 1e30;
+  bool found = false;
+  // a candidate plan: listed for the first-use selection when `rank`, kept when it is the fastest so far
+  auto take = [&](double us, int c, int sp, bool rank) {
+    const KernelEntry& e = g_kernel_table[c];
+    const int g = default_group_m(e, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn);
+    if (rank && ranked && n_ranked && *n_ranked < 8) ranked[(*n_ranked)++] = RankedPlan{us, c, sp, g};
+    if (us < best) { best = us; found = true; *cfg = c; *splits = sp; *group_m = g; }
   };
   int br[3][2];
   const int dims[3] = {M, N, K};
@@ -368,8 +377,6 @@ bool neighbour_plan(int M, int N, int K, int* cfg, int* splits, int* group_m, Ra
     }
     br[d][0] = lo; br[d][1] = hi;
   }
-  double best = 1e30;
-  bool found = false;
   for (int c = 0; c < 8; ++c) {
     const TunedPlan* p = find_tuned(br[0][c & 1], br[1][(c >> 1) & 1], br[2][(c >> 2) & 1]);
     if (!p || p->cfg < 0) continue;
@@ -380,14 +387,8 @@ bool neighbour_plan(int M, int N, int K, int* cfg, int* splits, int* group_m, Ra
     // a stream-K corner plan keeps its form (the low bits are its workgroup count, not a split count) and is priced as such
     const bool sk_usable = streamk_really_runs(e, M, N, K);   // (direct K tail, > 65536 tiles: the launch would run data-parallel)
     if ((p->splits & HGEMM_PLAN_STREAMK) && sk_usable) {
-      const double t = model_us_streamk(e, M, N, K, streamk_grid(e, p->splits & HGEMM_SPLITK_MASK));
-      record(t, p->cfg, HGEMM_PLAN_STREAMK | (p->splits & HGEMM_SPLITK_MASK), default_group_m(e, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn));
-      if (t < best) {
-        best = t; found = true;
-        *cfg = p->cfg;
-        *splits = HGEMM_PLAN_STREAMK | (p->splits & HGEMM_SPLITK_MASK);
-        *group_m = default_group_m(e, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn);
-      }
+      take(model_us_streamk(e, M, N, K, streamk_grid(e, p->splits & HGEMM_SPLITK_MASK)), p->cfg,
+           HGEMM_PLAN_STREAMK | (p->splits & HGEMM_SPLITK_MASK), true);
       continue;
     }
     const int s = (p->splits & HGEMM_PLAN_STREAMK) ? 1 : std::max(1, std::min(p->splits & HGEMM_SPLITK_MASK, ksteps));
@@ -405,31 +406,20 @@ bool neighbour_plan(int M, int N, int K, int* cfg, int* splits, int* group_m, Ra
     // another corner win (1332 x 3108 x 4440: 525 tiles of 64 x 128 measured 101 us against 82 us for the 256 x 256 corner plan)
     if (e.name[0] == 't' && e.wm * e.wn == 8 && e.bm * e.bn <= 128 * 64 &&
         (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn) * s > 2L * kCUs) continue;
-    const double t = model_us(e, M, N, K, s);
-    {
-      int sp = s > 1 ? (s | (p->splits & HGEMM_SPLITK_FUSED)) : 1;
-      if (e.name[0] == 'r' && K % 64 == 0) sp |= p->splits & (HGEMM_PLAN_RS_XCD_STAGGER | HGEMM_PLAN_RS_NT_LOADS);
-      if (e.name[0] == 'q') sp |= p->splits & (HGEMM_PLAN_XCD_STAGGER | HGEMM_PLAN_PHASE_OFFSET | HGEMM_PLAN_PHASE_OFFSET4);
-      record(t, p->cfg, sp, default_group_m(e, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn));
-    }
-    if (t < best) {
-      best = t; found = true;
-      *cfg = p->cfg;
-      *splits = s > 1 ? (s | (p->splits & HGEMM_SPLITK_FUSED)) : 1;
-      // family r's load flags travel with the corner plan (they belong to the access pattern of the shape class, not to the shape)
-      // -- while the rows stay 128-byte aligned (K % 64 == 0).  With rows that straddle cache lines a non-temporal load drops the
-      // half line the next K stage of the same row needs again, and the flags cost instead of paying: 64 x 16384 x 9160 (stride
-      // 18320 B) r64x128_k128 split 2 64.0 us plain / 70.6 with both flags, r64x64_k256 66.8 / 70.3, the corner plan itself
-      // (r64x128_k128_d, NT loads) 73.6 -> 67.7 without; with aligned rows off the grid they keep paying (16000 x 128 x 16000
-      // 0.81 -> 0.79 of hipBLASLt without them, 128 x 16000 x 16000 0.99 -> 0.95, 64 x 14928 x 10624 0.77 -> 0.73:
-      // tuning/r04_ktail_candidates_mi355x.jsonl, r04_offgrid_plan_report_call_j3_no_r_flags_mi355x.jsonl)
-      if (e.name[0] == 'r' && K % 64 == 0) *splits |= p->splits & (HGEMM_PLAN_RS_XCD_STAGGER | HGEMM_PLAN_RS_NT_LOADS);
-      // family q's schedule flags (round 5) travel with the corner plan as well: they belong to the shape class (a one-round plan of
-      // long rows wants the K stagger, a walk of many short-K items the phase offset), cannot change a result, and fall away by
-      // themselves where they do not apply (a K tail takes the ktail variant, a single round has nothing to offset)
-      if (e.name[0] == 'q') *splits |= p->splits & (HGEMM_PLAN_XCD_STAGGER | HGEMM_PLAN_PHASE_OFFSET | HGEMM_PLAN_PHASE_OFFSET4);
-      *group_m = default_group_m(e, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn);
-    }
+    int sp = s > 1 ? (s | (p->splits & HGEMM_SPLITK_FUSED)) : 1;
+    // family r's load flags travel with the corner plan (they belong to the access pattern of the shape class, not to the shape)
+    // -- while the rows stay 128-byte aligned (K % 64 == 0).  With rows that straddle cache lines a non-temporal load drops the
+    // half line the next K stage of the same row needs again, and the flags cost instead of paying: 64 x 16384 x 9160 (stride
+    // 18320 B) r64x128_k128 split 2 64.0 us plain / 70.6 with both flags, r64x64_k256 66.8 / 70.3, the corner plan itself
+    // (r64x128_k128_d, NT loads) 73.6 -> 67.7 without; with aligned rows off the grid they keep paying (16000 x 128 x 16000
+    // 0.81 -> 0.79 of hipBLASLt without them, 128 x 16000 x 16000 0.99 -> 0.95, 64 x 14928 x 10624 0.77 -> 0.73:
+    // tuning/r04_ktail_candidates_mi355x.jsonl, r04_offgrid_plan_report_call_j3_no_r_flags_mi355x.jsonl)
+    if (e.name[0] == 'r' && K % 64 == 0) sp |= p->splits & (HGEMM_PLAN_RS_XCD_STAGGER | HGEMM_PLAN_RS_NT_LOADS);
+    // family q's schedule flags (round 5) travel with the corner plan as well: they belong to the shape class (a one-round plan of
+    // long rows wants the K stagger, a walk of many short-K items the phase offset), cannot change a result, and fall away by
+    // themselves where they do not apply (a K tail takes the ktail variant, a single round has nothing to offset)
+    if (e.name[0] == 'q') sp |= p->splits & (HGEMM_PLAN_XCD_STAGGER | HGEMM_PLAN_PHASE_OFFSET | HGEMM_PLAN_PHASE_OFFSET4);
+    take(model_us(e, M, N, K, s), p->cfg, sp, true);
   }
   // The grid's only multiple of 192 is 12288: a shape with another one (3072, 1536, 6144 ...) finds no corner that uses the 192-wide
   // persistent tiles although they may fit it exactly (3072^2: 144 tiles of 256 x 256 on 256 CUs, 192 of 192 x 256).  They join the
@@ -446,16 +436,8 @@ bool neighbour_plan(int M, int N, int K, int* cfg, int* splits, int* group_m, Ra
       const KernelEntry& e = g_kernel_table[c];
       // (only where the 192-wide tiles fill at least half the chip: 1968 x 576 has 24 of them and measured 0.72x of its corner plan)
       if ((long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn) < kCUs / 2 || !k_ok(e, K)) continue;
-      for (int s : {1, best_s}) {
-        if (s > std::max(1, K / e.kgran)) continue;
-        const double t = model_us(e, M, N, K, s);
-        if (t < best) {
-          best = t;
-          *cfg = c;
-          *splits = s > 1 ? (s | best_fused) : 1;
-          *group_m = default_group_m(e, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn);
-        }
-      }
+      for (int s : {1, best_s})
+        if (s <= std::max(1, K / e.kgran)) take(model_us(e, M, N, K, s), c, s > 1 ? (s | best_fused) : 1, false);
     }
   }
   // A corner plan of family q was tuned on a shape whose tiles fill the resident workgroups; off the grid the same tile may leave
@@ -485,14 +467,7 @@ bool neighbour_plan(int M, int N, int K, int* cfg, int* splits, int* group_m, Ra
           // (round 6: a split of a sibling needs >= 2048 of K per slice -- with 1024 the model took 40 tiles of 256 x 128 at four
           // single-launch splits for 1968 x 576 x 4096 when its corner moved to the K = 128 stages: 39.1 us against 26.9 for the corner plan)
           if (s > 1 && K / s < 2048) break;
-          if (fill_of(e, s) < fill0) continue;
-          const double t = model_us(e, M, N, K, s);
-          if (t < best) {
-            best = t;
-            *cfg = c;
-            *splits = s > 1 ? (s | fused0) : 1;
-            *group_m = default_group_m(e, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn);
-          }
+          if (fill_of(e, s) >= fill0) take(model_us(e, M, N, K, s), c, s > 1 ? (s | fused0) : 1, false);
         }
       }
     }
@@ -513,6 +488,154 @@ bool mfma_path_ok(const void* a, const void* bt, const void* c, int M, int N, in
   if (((uintptr_t)a & 15) || ((uintptr_t)bt & 15) || ((uintptr_t)c & 7)) return false;
   (void)M;
   return true;
+}
+
+// ---- launch resolution: the form a hgemm_mi355x_launch call runs as, its workspace and its dispatches -------------------
+// Host logic only (no HIP call, allocation or lock): the launch issues what it returns, hgemm_mi355x_plan_workspace_bytes reports
+// its request, hgemm_mi355x_selfcheck_launch shows it to the CPU tests.
+enum Form { FORM_REFERENCE, FORM_RAGGED, FORM_STREAMK, FORM_SPLITK, FORM_FUSED, FORM_HYBRID, FORM_PLAIN };
+enum Thunk { THUNK_ENTRY, THUNK_SPLITK_REDUCE, THUNK_TAIL_REDUCE, THUNK_RAGGED, THUNK_GENERIC };
+// one dispatch: its arguments (operand pointers, slabs and counters are the launch's to fill in), grid (0: the thunk sizes it),
+// epilogue, and whether it carries the timing hook's start / stop event
+struct Dispatch { int thunk; GemmArgs g; int grid, epi; bool start, stop; };
+struct LaunchPlan {
+  int status = HGEMM_OK, form = FORM_PLAIN, n = 0;
+  size_t slab_bytes = 0;   // fp32 slab space the form asks for behind the arrival counters (0: no workspace)
+  bool counters = false;   // the form uses the arrival counters
+  Dispatch d[3];
+};
+constexpr struct { int plan, arg; } kArgFlags[] = {   // plan flags -> GemmArgs::flags
+    {HGEMM_PLAN_NT_STORE, ARG_NT_STORE}, {HGEMM_PLAN_RS_XCD_STAGGER, ARG_XCD_STAGGER}, {HGEMM_PLAN_RS_NT_LOADS, ARG_NT_LOADS},
+    {HGEMM_PLAN_PHASE_OFFSET, ARG_PHASE_OFFSET}, {HGEMM_PLAN_WAVE_PRIORITY, ARG_WAVE_PRIORITY}, {HGEMM_PLAN_PHASE_OFFSET4, ARG_PHASE_OFFSET4}};
+
+// has_b / has_bt: b / b_col_major given; aligned: the operands pass mfma_path_ok; ruled_out: bits 1 << form of the workspace-backed
+// forms that got no workspace
+LaunchPlan resolve_launch(int config_id, int splits_arg, int group_m, bool has_b, bool has_bt, bool aligned, int M, int N, int K,
+                          int lda, int ldb, int ldc, unsigned ruled_out) {
+  LaunchPlan p;
+  auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
+    if (p.n) p.d[p.n - 1].stop = false;
+    p.d[p.n] = Dispatch{thunk, g, (int)grid, epi, p.n == 0, true};
+    ++p.n;
+  };
+  auto fail = [&p](int status) { p.status = status; return p; };
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
+  for (const auto& f : kArgFlags) g.flags |= (splits_arg & f.plan) ? f.arg : 0;
+  g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
+#ifdef HGEMM_ABLATION
+  g.debug = g_debug_flags;
+#endif
+#ifdef HGEMM_TIMELINE
+  g.timeline = (g_timeline && g_timeline_slots > 0)   // (hgemm_mi355x_launch has counted this call already)
+                   ? g_timeline + (size_t)((g_timeline_count - 1) % (unsigned)g_timeline_slots) * kTimelineWgs * HGEMM_TL_WORDS
+                   : nullptr;
+#endif
+  bool fast = config_id >= 0 && has_bt && aligned;
+  if (fast) {
+    // 32-bit LDS-DMA offsets: (BM-1) rows * ld * 2 B + K * 2 B must stay below 4 GiB; beyond that the
+    // register-staged kernel (64-bit addressing) takes over instead of an error.
+    const KernelEntry& e = g_kernel_table[config_id];
+    // 2 GiB where bit 31 of an offset is the out-of-range mark: the classic family (its descriptors end at 2 GiB), and a launch that
+    // runs a direct K tail (families q / r, K % stage != 0); their whole-stage launches address 4 GiB
+    const bool mark31 = e.name[0] == 't' || (e.ktail && k_ok(e, K) && split_k(e, K, 1).tail_direct);
+    const double reach = mark31 ? 2147483648.0 : 4294967296.0;
+    if ((double)e.bm * lda * 2.0 + K * 2.0 >= reach || (double)e.bn * ldb * 2.0 + K * 2.0 >= reach) fast = false;
+    if (K % BK != 0 && !k_ok(e, K)) fast = false;   // a partial last K-step on a geometry that cannot take it: any-shape kernel
+    // the LDS-staged epilogue addresses a wave tile through one buffer descriptor with 32-bit offsets
+    if ((double)e.bm * ldc * 2.0 + (double)N * 2.0 >= 2147483648.0) fast = false;
+  }
+  if (!fast) {
+    const bool ragged = config_id != HGEMM_CONFIG_GENERIC && has_bt;
+    if (ragged && (long)((M + 63) / 64) * ((N + 63) / 64) > 0x7fffffffL) return fail(HGEMM_ERR_TOO_LARGE);
+    if (!ragged && !has_b) return fail(HGEMM_ERR_BAD_ARG);
+    p.form = ragged ? FORM_RAGGED : FORM_REFERENCE;
+    add(ragged ? THUNK_RAGGED : THUNK_GENERIC, g, 0, EPI_C16);
+    return p;
+  }
+  const KernelEntry& e = g_kernel_table[config_id];
+  g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (N + e.bn - 1) / e.bn;
+  const long tiles = (long)g.tiles_m * g.tiles_n;
+  if (!k_ok(e, K)) return fail(HGEMM_ERR_BAD_ARG);
+  const int ksteps = split_k(e, K, 1).steps;   // pipeline stages along K (direct tail: whole stages; the rest rides on the last split)
+  // Stream-K (HGEMM_PLAN_STREAMK; the low bits of `splits` are then the number of persistent workgroups): one launch, no
+  // combine kernel.  Not available (family without the kernel, too many tiles for the counter block): the plan runs as splits = 1.
+  if ((splits_arg & HGEMM_PLAN_STREAMK) && !(ruled_out & (1u << FORM_STREAMK)) && streamk_really_runs(e, M, N, K)) {
+    const int min_steps = streamk_min_steps(e);
+    const int G = (int)std::max<long>(1, std::min<long>(streamk_grid(e, splits_arg & HGEMM_SPLITK_MASK), std::max<long>(1, tiles * ksteps / min_steps)));
+    if ((size_t)2 * G * e.bm * e.bn * sizeof(float) < 2147483648ull) {
+      p.form = FORM_STREAMK; p.slab_bytes = (size_t)2 * G * e.bm * e.bn * sizeof(float); p.counters = true;
+      g.group_m = std::max(1, std::min(group_m, g.tiles_m)); g.items = (int)tiles;
+      g.sk = make_streamk((int)tiles, ksteps, G, min_steps);
+      set_raster_div(g);
+      add(THUNK_ENTRY, g, G, EPI_STREAMK);
+      return p;
+    }
+  }
+  // at most one split per stage, no empty split
+  int splits = split_k(e, K, (splits_arg & HGEMM_PLAN_STREAMK) ? 1 : splits_arg & HGEMM_SPLITK_MASK).splits;
+  g.group_m = std::max(1, std::min(group_m, g.tiles_m));
+  if (tiles * splits > 0x7fffffffL) return fail(HGEMM_ERR_TOO_LARGE);
+  if (ruled_out & ((1u << FORM_SPLITK) | (1u << FORM_FUSED))) splits = 1;
+  // Split-K: two-pass (slabs + combine kernel) by default; single-launch ("fused") on request, unless the
+  // tile count exceeds the counter block or the kernel family has no fused epilogue.
+  int epi = EPI_C16;
+  if (splits > 1) {
+    const bool fused = (splits_arg & HGEMM_SPLITK_FUSED) && tiles <= (long)kMaxFusedTiles && e.has_fused &&
+                       (double)tiles * splits * e.bm * e.bn * sizeof(float) < 2147483648.0;   // 32-bit slab offsets
+    p.form = fused ? FORM_FUSED : FORM_SPLITK;
+    p.slab_bytes = fused ? (size_t)tiles * splits * e.bm * e.bn * sizeof(float) : (size_t)splits * M * N * sizeof(float);
+    p.counters = fused;
+    epi = fused ? EPI_FUSED : EPI_SLAB;
+  }
+  g.k_chunk = split_k(e, K, splits).k_chunk; g.splits = splits;
+  const long grid = tiles * splits;
+  g.items = (int)grid;
+  // Hybrid schedule for the persistent family (stream-K's data-parallel + tail form): when the tile
+  // count is not a multiple of the resident workgroups, the last partial round would keep most CUs
+  // idle for a whole tile time.  Instead the full rounds run as they are and the `tail` leftover
+  // tiles are cut along K into floor(G / tail) slices each, one slice per workgroup, combined by a
+  // small reduce over compact fp32 slabs.  (7168^3 with 256x256 tiles: 784 = 3 x 256 + 16.)
+  const long G = e.persistent_wgs;
+#ifdef HGEMM_ABLATION
+  if (g_debug_flags & 32) ruled_out |= 1u << FORM_HYBRID;
+#endif
+  if (G > 0 && splits == 1 && tiles > G && tiles % G != 0 && !(ruled_out & (1u << FORM_HYBRID))) {
+    const long tail = tiles % G, full = tiles - tail;
+    int S = (int)std::min<long>(G / tail, ksteps / 4);   // >= 4 K-steps per slice
+    if (S >= 2) {
+      const int per_t = (ksteps + S - 1) / S;
+      S = (ksteps + per_t - 1) / per_t;
+      // Worth it when it beats the partial round it replaces.  Measured on MI355X: a round with few
+      // tiles runs at ~0.6x of a full round's tile time (no contention), and the tail pass costs its
+      // K slice plus ~25 us of prologue / epilogue / two extra launches / combine
+      // (7168^3: 702 -> 661 us, 4352^2 x 4096: 175 -> 149 us; 10000^2 x 1024 would lose 7 %).
+      const double tile_us = model_us(e, e.bm, e.bn, K, 1) - kLaunchUs;
+      if (0.6 * tile_us - tile_us / S > 25.0) {
+        GemmArgs t = g;
+        t.tail_first = (int)full; t.tail_tiles = (int)tail; t.splits = S; t.k_chunk = per_t * e.kgran;
+        t.items = (int)tail * S;
+        g.items = (int)full; set_raster_div(g); set_raster_div(t);
+        p.form = FORM_HYBRID; p.slab_bytes = (size_t)t.items * e.bm * e.bn * sizeof(float);
+        add(THUNK_ENTRY, g, std::min<long>(full, G), EPI_C16);
+        add(THUNK_ENTRY, t, std::min<long>(t.items, G), EPI_SLAB);
+        add(THUNK_TAIL_REDUCE, t, 0, EPI_SLAB);
+        return p;
+      }
+    }
+  }
+  // persistent families walk their work items themselves: one resident wave of workgroups
+  long launch_grid = (e.persistent_wgs > 0) ? std::min<long>(grid, e.persistent_wgs) : grid;
+  // A two-resident member (persistent_wgs = 512) whose single-launch split-K variant no longer fits twice into a CU's 160 KiB
+  // -- the fused epilogue adds the 64-byte vote word to the stage area: q192x128 / q128x192 with 80 KiB of stages -- is resident
+  // once per CU: 512 workgroups would run as two sequential waves of 256, each paying its own prologue.  One wave of 256 walks
+  // the same items.
+  if (epi == EPI_FUSED && e.persistent_wgs > kCUs && 2L * (e.lds_bytes + 64) > 160L * 1024) launch_grid = std::min<long>(launch_grid, kCUs);
+  set_raster_div(g);
+  add(THUNK_ENTRY, g, launch_grid, epi);
+  if (epi == EPI_SLAB) add(THUNK_SPLITK_REDUCE, g, 0, EPI_SLAB);
+  return p;
 }
 
 // ---- first-use plan selection on the box the library runs on (opt-in) ---------------------------------------------------------
@@ -620,12 +743,7 @@ bool insitu_select(int dev, const void* a, const void* b, const void* bt, void* 
   // ensure_workspace's hipMalloc does.
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return false;
-  struct RelaxedCapture {
-    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-    bool ok;
-    RelaxedCapture() { ok = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess; if (!ok) (void)hipGetLastError(); }
-    ~RelaxedCapture() { if (ok && hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) (void)hipGetLastError(); }
-  } relaxed;
+  RelaxedCapture relaxed;
   PlanTriple cand[3];
   const int n = insitu_candidates(M, N, K, cand);
   if (n == 0) return false;
@@ -775,22 +893,11 @@ size_t hgemm_mi355x_workspace_bytes(int M, int N, int splits) {
 }
 
 size_t hgemm_mi355x_plan_workspace_bytes(int config_id, int splits, int M, int N, int K) {
-  // exactly what hgemm_mi355x_launch will ask ensure_workspace for with this plan (0: the plan needs none)
+  // what hgemm_mi355x_launch asks ensure_workspace for with this plan on the operands run() passes (0: the plan needs none)
   if (config_id < 0 || config_id >= g_num_kernels || M <= 0 || N <= 0 || K <= 0) return 0;
-  const KernelEntry& e = g_kernel_table[config_id];
-  if (!k_ok(e, K)) return 0;
-  const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
-  if (splits & HGEMM_PLAN_STREAMK) {
-    if (!streamk_really_runs(e, M, N, K)) return 0;
-    const long total = tiles * split_k(e, K, 1).steps;
-    const long G = std::max<long>(1, std::min<long>(streamk_grid(e, splits & HGEMM_SPLITK_MASK), std::max<long>(1, total / streamk_min_steps(e))));
-    return kCounterBytes + (size_t)2 * G * e.bm * e.bn * sizeof(float);
-  }
-  const int sp = split_k(e, K, std::max(1, splits & HGEMM_SPLITK_MASK)).splits;
-  if (sp <= 1) return 0;
-  const bool fused = (splits & HGEMM_SPLITK_FUSED) && tiles <= (long)kMaxFusedTiles && e.has_fused &&
-                     (double)tiles * sp * e.bm * e.bn * sizeof(float) < 2147483648.0;
-  return kCounterBytes + (fused ? (size_t)tiles * sp * e.bm * e.bn : (size_t)sp * M * N) * sizeof(float);
+  const bool aligned = mfma_path_ok(nullptr, nullptr, nullptr, M, N, K, K, K, N);   // (null pointers are aligned ones)
+  const LaunchPlan p = resolve_launch(config_id, splits, 1, true, true, aligned, M, N, K, K, K, N, 0);
+  return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
 }
 
 int hgemm_mi355x_set_workspace(void* device_ptr, size_t bytes) {
@@ -841,11 +948,10 @@ int hgemm_mi355x_reserve_workspace(int M, int N, int K, void* stream) {
   int cfg = 0, splits = 1, group = 1;
   const int st = hgemm_mi355x_plan(M, N, K, &cfg, &splits, &group);
   if (st != HGEMM_OK) return st;
-  // split-K slabs of the plan, or the hybrid tail's compact slabs (one 256x256 fp32 tile per resident workgroup at most)
-  size_t slab = cfg >= 0 ? hgemm_mi355x_plan_workspace_bytes(cfg, splits, M, N, K) : 0;   // exactly what the launch will ask for
-  slab = std::max(slab, kCounterBytes + (size_t)256 * 256 * 256 * sizeof(float)) - kCounterBytes;
+  // what the launch will ask for, and no less than what a hybrid tail can ask for (one 256x256 fp32 tile per resident workgroup)
+  const size_t ws = std::max(hgemm_mi355x_plan_workspace_bytes(cfg, splits, M, N, K), kCounterBytes + (size_t)256 * 256 * 256 * sizeof(float));
   float* slabs = nullptr; unsigned* counters = nullptr;
-  const int rc = ensure_workspace(slab, (hipStream_t)stream, &slabs, &counters);
+  const int rc = ensure_workspace(ws - kCounterBytes, (hipStream_t)stream, &slabs, &counters);
   return rc == HGEMM_ERR_NO_WORKSPACE_INTERNAL ? HGEMM_ERR_NO_WORKSPACE : rc;
 }
 
@@ -857,166 +963,42 @@ int hgemm_mi355x_launch(int config_id, int splits_arg, int group_m, const void* 
   } disarm_timing;
   if (!a || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   if (config_id >= g_num_kernels || config_id < HGEMM_CONFIG_RAGGED) return HGEMM_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool want_fused = (splits_arg & HGEMM_SPLITK_FUSED) != 0;
-  const bool want_streamk = (splits_arg & HGEMM_PLAN_STREAMK) != 0;
-  int splits = splits_arg & HGEMM_SPLITK_MASK;
-
-  GemmArgs g;
-  g.A = (const f16*)a; g.Bt = (const f16*)b_col_major; g.C = (f16*)c; g.partial = nullptr; g.counters = nullptr;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.k_chunk = K; g.splits = 1; g.tiles_m = g.tiles_n = 1; g.group_m = 1; g.items = 1;
-  g.tail_first = 0; g.tail_tiles = 0;
-  g.flags = ((splits_arg & HGEMM_PLAN_NT_STORE) ? 1 : 0) | ((splits_arg & HGEMM_PLAN_RS_XCD_STAGGER) ? 2 : 0) | ((splits_arg & HGEMM_PLAN_RS_NT_LOADS) ? 4 : 0) |
-            ((splits_arg & HGEMM_PLAN_PHASE_OFFSET) ? 8 : 0) | ((splits_arg & HGEMM_PLAN_WAVE_PRIORITY) ? 16 : 0) | ((splits_arg & HGEMM_PLAN_PHASE_OFFSET4) ? 32 : 0);
-  g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
-#ifdef HGEMM_ABLATION
-  g.debug = g_debug_flags;
-#endif
 #ifdef HGEMM_TIMELINE
-  g.timeline = (g_timeline && g_timeline_slots > 0)
-                   ? g_timeline + (size_t)(g_timeline_count++ % (unsigned)g_timeline_slots) * kTimelineWgs * HGEMM_TL_WORDS
-                   : nullptr;
+  ++g_timeline_count;
 #endif
-
-  bool fast = config_id >= 0 && b_col_major && mfma_path_ok(a, b_col_major, c, M, N, K, lda, ldb, ldc);
-  if (fast) {
-    // 32-bit LDS-DMA offsets: (BM-1) rows * ld * 2 B + K * 2 B must stay below 4 GiB; beyond that the
-    // register-staged kernel (64-bit addressing) takes over instead of an error.
-    const KernelEntry& e = g_kernel_table[config_id];
-    // 2 GiB where bit 31 of an offset is the out-of-range mark: the classic family (its descriptors end at 2 GiB), and a launch that
-    // runs a direct K tail (families q / r, K % stage != 0); their whole-stage launches address 4 GiB
-    const bool mark31 = e.name[0] == 't' || (e.ktail && k_ok(e, K) && split_k(e, K, 1).tail_direct);
-    const double reach = mark31 ? 2147483648.0 : 4294967296.0;
-    if ((double)e.bm * lda * 2.0 + K * 2.0 >= reach || (double)e.bn * ldb * 2.0 + K * 2.0 >= reach) fast = false;
-    if (K % BK != 0 && !k_ok(e, K)) fast = false;   // a partial last K-step on a geometry that cannot take it: any-shape kernel
-    // the LDS-staged epilogue addresses a wave tile through one buffer descriptor with 32-bit offsets
-    if ((double)e.bm * ldc * 2.0 + (double)N * 2.0 >= 2147483648.0) fast = false;
+  hipStream_t s = (hipStream_t)stream;
+  const bool aligned = mfma_path_ok(a, b_col_major, c, M, N, K, lda, ldb, ldc);
+  unsigned ruled_out = 0;
+  auto resolve = [&] {
+    return resolve_launch(config_id, splits_arg, group_m, b != nullptr, b_col_major != nullptr, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  };
+  LaunchPlan p = resolve();
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  // No workspace (lent buffer too small, allocation failed, capturing stream) runs the plan without the form that needed it;
+  // stream-K and split-K return any other error, the hybrid tail runs its plain launch whatever went wrong.
+  while (p.status == HGEMM_OK && p.slab_bytes) {
+    const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
+    if (st == HGEMM_OK) break;
+    if (st != HGEMM_ERR_NO_WORKSPACE_INTERNAL && p.form != FORM_HYBRID) return st;
+    ruled_out |= 1u << p.form;
+    p = resolve();
   }
-  if (!fast) {
-    if (config_id != HGEMM_CONFIG_GENERIC && b_col_major) {
-      if ((long)((M + 63) / 64) * ((N + 63) / 64) > 0x7fffffffL) return HGEMM_ERR_TOO_LARGE;
-      launch_ragged(g, s, timing_slot(true, true));
-    } else {
-      if (!b) return HGEMM_ERR_BAD_ARG;
-      launch_generic((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, N, ldc, s, timing_slot(true, true));
+  if (p.status != HGEMM_OK) return p.status;
+  for (int i = 0; i < p.n; ++i) {
+    GemmArgs& g = p.d[i].g;
+    g.A = (const f16*)a; g.Bt = (const f16*)b_col_major; g.C = (f16*)c;
+    if (p.d[i].epi != EPI_C16) {
+      g.partial = slabs;
+      if (p.counters) g.counters = counters;
     }
-  } else {
-    const KernelEntry& e = g_kernel_table[config_id];
-    g.tiles_m = (M + e.bm - 1) / e.bm;
-    g.tiles_n = (N + e.bn - 1) / e.bn;
-    const long tiles = (long)g.tiles_m * g.tiles_n;
-    // pipeline stages of this geometry along K (BK = 64, or 128 for the "_k128" members)
-    if (!k_ok(e, K)) return HGEMM_ERR_BAD_ARG;
-    const int kgran = e.kgran;
-    const KSplit ks0 = split_k(e, K, 1);
-    const bool tail_direct = ks0.tail_direct;
-    const int ksteps = ks0.steps;   // (direct tail: whole stages; the rest rides on the last split)
-    // Stream-K (HGEMM_PLAN_STREAMK; the low bits of `splits` are then the number of persistent workgroups): one launch, no
-    // combine kernel.  Not available (family without the kernel, too many tiles for the counter block, no workspace): the
-    // plan degrades to the geometry's plain data-parallel launch, like a split-K plan without workspace.
-    if (want_streamk) {
-      const long total = tiles * ksteps;
-      if (streamk_really_runs(e, M, N, K)) {   // (else: the plain launch below; hgemm_mi355x_streamk_runs tells a caller beforehand)
-        const int min_steps = streamk_min_steps(e);
-        const int G = (int)std::max<long>(1, std::min<long>(streamk_grid(e, splits), std::max<long>(1, total / min_steps)));
-        const size_t slab_bytes = (size_t)2 * G * e.bm * e.bn * sizeof(float);
-        unsigned* counters = nullptr;
-        const int st = slab_bytes < 2147483648ull ? ensure_workspace(slab_bytes, s, &g.partial, &counters) : HGEMM_ERR_NO_WORKSPACE_INTERNAL;
-        if (st == HGEMM_OK) {
-          g.counters = counters;
-          g.group_m = std::max(1, std::min(group_m, g.tiles_m));
-          g.items = (int)tiles;
-          g.sk = make_streamk((int)tiles, ksteps, G, min_steps);
-          set_raster_div(g);
-          e.launch(g, G, s, EPI_STREAMK, timing_slot(true, true));
-          hipError_t err2 = hipGetLastError();
-          if (err2 != hipSuccess) { g_last_hip_error = (int)err2; return HGEMM_ERR_HIP; }
-          return HGEMM_OK;
-        }
-        if (st != HGEMM_ERR_NO_WORKSPACE_INTERNAL) return st;
-        g.partial = nullptr;
-      }
-      splits = 1;
+    const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
+    switch (p.d[i].thunk) {
+      case THUNK_ENTRY: g_kernel_table[config_id].launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
+      case THUNK_SPLITK_REDUCE: launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts); break;
+      case THUNK_TAIL_REDUCE: launch_tail_reduce(g, g_kernel_table[config_id].bm, g_kernel_table[config_id].bn, s, ts); break;
+      case THUNK_RAGGED: launch_ragged(g, s, ts); break;
+      case THUNK_GENERIC: launch_generic((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, N, ldc, s, ts); break;
     }
-    splits = split_k(e, K, splits).splits;   // at most one per stage, no empty split
-    g.group_m = std::max(1, std::min(group_m, g.tiles_m));
-    if (tiles * splits > 0x7fffffffL) return HGEMM_ERR_TOO_LARGE;
-    // Split-K: two-pass (slabs + combine kernel) by default; single-launch ("fused") on request, unless the
-    // tile count exceeds the counter block or the kernel family has no fused epilogue.  No workspace (lent buffer too small, allocation failed) means
-    // no split-K: the plan degrades to splits = 1 instead of failing.
-    int epi = EPI_C16;
-    if (splits > 1) {
-      const bool fused = want_fused && tiles <= (long)kMaxFusedTiles && e.has_fused &&
-                         (double)tiles * splits * e.bm * e.bn * sizeof(float) < 2147483648.0;   // 32-bit slab offsets
-      const size_t slab_bytes = fused ? (size_t)tiles * splits * e.bm * e.bn * sizeof(float)
-                                      : (size_t)splits * M * N * sizeof(float);
-      unsigned* counters = nullptr;
-      const int st = ensure_workspace(slab_bytes, s, &g.partial, &counters);
-      if (st == HGEMM_OK) {
-        epi = fused ? EPI_FUSED : EPI_SLAB;
-        if (fused) g.counters = counters;
-      } else if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
-        splits = 1; g.partial = nullptr;
-      } else {
-        return st;
-      }
-    }
-    g.k_chunk = split_k(e, K, splits).k_chunk;   // (splits may have dropped to 1 above: no workspace)
-    g.splits = splits;
-    const long grid = tiles * splits;
-    g.items = (int)grid;
-    // Hybrid schedule for the persistent family (stream-K's data-parallel + tail form): when the tile
-    // count is not a multiple of the resident workgroups, the last partial round would keep most CUs
-    // idle for a whole tile time.  Instead the full rounds run as they are and the `tail` leftover
-    // tiles are cut along K into floor(G / tail) slices each, one slice per workgroup, combined by a
-    // small reduce over compact fp32 slabs.  (7168^3 with 256x256 tiles: 784 = 3 x 256 + 16.)
-    const long G = e.persistent_wgs;
-#ifdef HGEMM_ABLATION
-    const bool hybrid_ok = !(g_debug_flags & 32);
-#else
-    const bool hybrid_ok = true;
-#endif
-    if (G > 0 && splits == 1 && tiles > G && tiles % G != 0 && hybrid_ok) {
-      const long tail = tiles % G, full = tiles - tail;
-      int S = (int)std::min<long>(G / tail, ksteps / 4);   // >= 4 K-steps per slice
-      if (S >= 2) {
-        const int per_t = (ksteps + S - 1) / S;
-        S = (ksteps + per_t - 1) / per_t;
-        // Worth it when it beats the partial round it replaces.  Measured on MI355X: a round with few
-        // tiles runs at ~0.6x of a full round's tile time (no contention), and the tail pass costs its
-        // K slice plus ~25 us of prologue / epilogue / two extra launches / combine
-        // (7168^3: 702 -> 661 us, 4352^2 x 4096: 175 -> 149 us; 10000^2 x 1024 would lose 7 %).
-        const double tile_us = model_us(e, e.bm, e.bn, K, 1) - kLaunchUs;
-        if (0.6 * tile_us - tile_us / S > 25.0) {
-          GemmArgs t = g;
-          t.tail_first = (int)full; t.tail_tiles = (int)tail; t.splits = S; t.k_chunk = per_t * kgran;
-          t.items = (int)tail * S;
-          unsigned* unused = nullptr;
-          // (no workspace just means: no hybrid schedule)
-          if (ensure_workspace((size_t)t.items * e.bm * e.bn * sizeof(float), s, &t.partial, &unused) == HGEMM_OK) {
-            g.items = (int)full;
-            set_raster_div(g); set_raster_div(t);
-            e.launch(g, (int)std::min<long>(full, G), s, EPI_C16, timing_slot(true, false));
-            e.launch(t, (int)std::min<long>(t.items, G), s, EPI_SLAB, timing_slot(false, false));
-            launch_tail_reduce(t, e.bm, e.bn, s, timing_slot(false, true));
-            hipError_t err2 = hipGetLastError();
-            if (err2 != hipSuccess) { g_last_hip_error = (int)err2; return HGEMM_ERR_HIP; }
-            return HGEMM_OK;
-          }
-        }
-      }
-    }
-    // persistent families walk their work items themselves: one resident wave of workgroups
-    long launch_grid = (e.persistent_wgs > 0) ? std::min<long>(grid, e.persistent_wgs) : grid;
-    // A two-resident member (persistent_wgs = 512) whose single-launch split-K variant no longer fits twice into a CU's 160 KiB
-    // -- the fused epilogue adds the 64-byte vote word to the stage area: q192x128 / q128x192 with 80 KiB of stages -- is resident
-    // once per CU: 512 workgroups would run as two sequential waves of 256, each paying its own prologue.  One wave of 256 walks
-    // the same items.
-    if (epi == EPI_FUSED && e.persistent_wgs > kCUs && 2L * (e.lds_bytes + 64) > 160L * 1024) launch_grid = std::min<long>(launch_grid, kCUs);
-    set_raster_div(g);
-    e.launch(g, (int)launch_grid, s, epi, timing_slot(true, epi != EPI_SLAB));
-    if (epi == EPI_SLAB) launch_splitk_reduce(g.partial, g.C, M, N, ldc, splits, s, timing_slot(false, true));
   }
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
@@ -1090,6 +1072,23 @@ int hgemm_mi355x_selfcheck_ksplit(int config_id, int K, int splits, int out[4]) 
   const KSplit r = split_k(g_kernel_table[config_id], K, splits);
   out[0] = r.steps; out[1] = r.splits; out[2] = r.k_chunk; out[3] = r.tail_direct ? 1 : 0;
   return HGEMM_OK;
+}
+// what hgemm_mi355x_launch decides for a call, nothing launched: operands = 1 (b given) | 2 (b_col_major given) | 4 (pointers
+// 16-byte aligned; dimensions and strides are checked as the launch checks them), ruled_out = 1 << form of the workspace-backed forms
+// that got no workspace.  Returns the call's status; out = {form, dispatches, slab bytes, counters (0 / 1)}, then for each dispatch
+// {thunk, grid, epi, splits, k_chunk, items, start, stop}.
+int hgemm_mi355x_selfcheck_launch(int config_id, int splits, int group_m, int operands, int M, int N, int K, int lda, int ldb, int ldc,
+                                  int ruled_out, long long out[28]) {
+  if (M <= 0 || N <= 0 || K <= 0 || config_id >= g_num_kernels || config_id < HGEMM_CONFIG_RAGGED || !out) return HGEMM_ERR_BAD_ARG;
+  const bool aligned = (operands & 4) && mfma_path_ok(nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc);
+  const LaunchPlan p = resolve_launch(config_id, splits, group_m, operands & 1, operands & 2, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  out[0] = p.form; out[1] = p.n; out[2] = (long long)p.slab_bytes; out[3] = p.counters;
+  for (int i = 0; i < p.n; ++i) {
+    const Dispatch& d = p.d[i];
+    const long long v[8] = {d.thunk, d.grid, d.epi, d.g.splits, d.g.k_chunk, d.g.items, d.start, d.stop};
+    std::copy(v, v + 8, out + 4 + 8 * i);
+  }
+  return p.status;
 }
 unsigned hgemm_mi355x_selfcheck_fastdiv(unsigned n, unsigned d) { return d ? fast_div(n, make_fast_div(d)) : 0xFFFFFFFFu; }
 

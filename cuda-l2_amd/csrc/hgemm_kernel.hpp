@@ -44,6 +44,14 @@ constexpr int BK        = 64;       // K elements per pipeline stage
 constexpr int ROW_BYTES = BK * 2;   // one tile row in LDS = 128 B
 constexpr int NUM_XCD   = 8;
 
+// GemmArgs::flags: the plan flags of include/hgemm_mi355x.h that reach the kernels (hgemm_api.hip maps them; all wave-uniform)
+constexpr int ARG_NT_STORE      = 1;    // HGEMM_PLAN_NT_STORE: non-temporal fp16 C stores
+constexpr int ARG_XCD_STAGGER   = 2;    // HGEMM_PLAN_(RS_)XCD_STAGGER: family r K stagger per XCD instead of per tile, family q the kstagger variant
+constexpr int ARG_NT_LOADS      = 4;    // HGEMM_PLAN_RS_NT_LOADS: non-temporal loads of family r's streamed operand
+constexpr int ARG_PHASE_OFFSET  = 8;    // HGEMM_PLAN_PHASE_OFFSET: family q's phase groups of the persistent walk
+constexpr int ARG_WAVE_PRIORITY = 16;   // HGEMM_PLAN_WAVE_PRIORITY: family q's two-resident members
+constexpr int ARG_PHASE_OFFSET4 = 32;   // HGEMM_PLAN_PHASE_OFFSET4: four phase groups instead of two (both bits: eight)
+
 // cache-policy bits of the LDS-DMA loads (buffer_load ... lds aux operand: 1 = sc0, 2 = nt, 16 = sc1).
 // 0 = default policy; other values are build-time experiments (build.py HGEMM_EXTRA_HIPFLAGS).
 // C stores: each C element is written once and never re-read by the kernel.  HGEMM_NT_STORE=1 marks the
@@ -52,12 +60,12 @@ constexpr int NUM_XCD   = 8;
 #define HGEMM_NT_STORE 0
 #endif
 // (HGEMM_NT_STORE=1 forces them for every plan: experiment builds.  Shipping builds take the plan's HGEMM_PLAN_NT_STORE bit,
-// GemmArgs::flags bit 0 -- a wave-uniform branch around the store.)
+// GemmArgs::flags ARG_NT_STORE -- a wave-uniform branch around the store.)
 #if HGEMM_NT_STORE
 #define HGEMM_STORE_C(g, ptr, val) __builtin_nontemporal_store((val), (ptr))
 #else
 #define HGEMM_STORE_C(g, ptr, val) \
-  do { if ((g).flags & 1) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
+  do { if ((g).flags & ARG_NT_STORE) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
 #endif
 
 #ifndef HGEMM_DMA_AUX
@@ -198,8 +206,7 @@ struct GemmArgs {
   // Single-launch split-K (EPI_FUSED): one arrival counter per output tile (zero before the launch, reset
   // by the last arriver) and compact per-item slabs partial[item][BM*BN] in the kernel's own lane order.
   unsigned* counters;
-  int flags;       // bit 0: non-temporal fp16 C stores (HGEMM_PLAN_NT_STORE); bit 1 (HGEMM_PLAN_XCD_STAGGER) family r: K stagger per XCD instead of per tile, family q: the kstagger variant
-                   // (HGEMM_PLAN_RS_XCD_STAGGER), bit 2 non-temporal loads of the streamed operand (HGEMM_PLAN_RS_NT_LOADS)
+  int flags;       // ARG_* bits (above)
 #if HGEMM_FASTDIV
   RasterDiv rd;    // multipliers for the raster map's divisions (set_raster_div on the host, after the fields above are final)
 #endif

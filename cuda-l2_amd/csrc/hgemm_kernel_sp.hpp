@@ -378,7 +378,7 @@ __device__ __forceinline__ void sp_epilogue_staged(const GemmArgs& g, int m_wave
   for (int gg = 0; gg < NG; ++gg)
     voff[gg] = (n_wave + gg * 64 + rch * 8 < g.N) ? (unsigned)(rrow * g.ldc + gg * 64 + rch * 8) * 2u : 0x80000000u;
   const unsigned row8 = (unsigned)g.ldc * 16u;                                          // 8 rows further, in bytes
-  const bool nt = (g.flags & 1) != 0;                                                   // plan flag HGEMM_PLAN_NT_STORE (uniform)
+  const bool nt = (g.flags & ARG_NT_STORE) != 0;                                        // plan flag HGEMM_PLAN_NT_STORE (uniform)
   u4 rb[2][2];   // read-back data of the group in flight [buffer][row half]
   auto write_group = [&](int k) {      // accumulators of group k -> buffer k & 1
     const int i = k / NG, gg = k % NG;

@@ -515,15 +515,16 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_sq_kernel(const GemmArg
   // in its L2 -- so all 32 CUs of the XCD reach their epilogues together and 32 x BM x BN x 2 B of C meet the XCD's one path into
   // the fabric at once (16384^2 x 256: ~11k cycles per epilogue of a 256 x 256 tile = 0.7 TB/s per XCD), while that path idles
   // during the K loops: the time of the small-K / large-MN class is the SUM of a store phase and an MFMA phase.
-  //   flags bit 3 (HGEMM_PLAN_PHASE_OFFSET): every second workgroup of an XCD enters its walk half an item period late, so half of
+  //   ARG_PHASE_OFFSET (HGEMM_PLAN_PHASE_OFFSET): every second workgroup of an XCD enters its walk half an item period late, so half of
   //     the XCD's CUs store while the other half multiplies.  The wait is a sleep in front of the first LDS-DMA piece, once per launch.
-  //     Bit 5 (HGEMM_PLAN_PHASE_OFFSET4): four groups a quarter period apart; both bits: eight groups an eighth apart.
-  //   flags bit 4 (HGEMM_PLAN_WAVE_PRIORITY), two-resident members: the wave in the odd hardware slot of its SIMD raises its
+  //     ARG_PHASE_OFFSET4 (HGEMM_PLAN_PHASE_OFFSET4): four groups a quarter period apart; both bits: eight groups an eighth apart.
+  //   ARG_WAVE_PRIORITY (HGEMM_PLAN_WAVE_PRIORITY), two-resident members: the wave in the odd hardware slot of its SIMD raises its
   //     priority for good, so the two workgroups of a CU stop sharing the matrix pipe evenly (and reaching their epilogues
   //     together): one's K loop runs at full rate and its epilogue under the other's K loop.
-  if (g.flags & (8 | 32)) {   // (bit 5, HGEMM_PLAN_PHASE_OFFSET4: four phase groups a quarter period apart instead of two; both bits: eight)
+  if (g.flags & (ARG_PHASE_OFFSET | ARG_PHASE_OFFSET4)) {
     const int j = (int)(blockIdx.x >> 3);   // index of the workgroup inside its XCD
-    const int groups = (g.flags & (8 | 32)) == (8 | 32) ? 8 : (g.flags & 32) ? 4 : 2, grp = j & (groups - 1);
+    constexpr int both = ARG_PHASE_OFFSET | ARG_PHASE_OFFSET4;
+    const int groups = (g.flags & both) == both ? 8 : (g.flags & ARG_PHASE_OFFSET4) ? 4 : 2, grp = j & (groups - 1);
     if (grp != 0 && walk.count > 1) {
       // spacing of two neighbouring groups: an equal share of the item period, but no more than an epilogue that has the XCD's
       // fabric path to itself takes anyway (~BM x BN / 6 cycles when all 32 CUs store at once): with a long K the point is only
@@ -536,7 +537,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_sq_kernel(const GemmArg
     }
   }
   if constexpr (CFG::WGS == 2) {
-    if (g.flags & 16) {
+    if (g.flags & ARG_WAVE_PRIORITY) {
       unsigned hw;
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
       if (hw & 1u) __builtin_amdgcn_s_setprio(2);

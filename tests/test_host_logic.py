@@ -722,6 +722,157 @@ def test_stream_k_query_says_whether_a_plan_really_runs_and_what_workspace_it_ta
     assert "hgemm_mi355x_streamk_runs" in text
 
 
+FORMS = ["reference", "ragged", "stream-K", "split-K", "fused", "hybrid", "plain"]
+THUNKS = ["entry", "splitk_reduce", "tail_reduce", "ragged", "generic"]
+COUNTERS = 256 << 10          # arrival counters in front of the slabs
+
+
+def _resolve(lib, cfg, splits, m, n, k, lds=None, operands=7, ruled_out=0, group=4):
+    """hgemm_mi355x_launch's decision for one call, nothing launched (hgemm_mi355x_selfcheck_launch): operands = b | b_col_major << 1 |
+    aligned pointers << 2, ruled_out = 1 << form of the workspace-backed forms that got no workspace.  Returns (status, form, slab
+    bytes, counters, [(thunk, grid, epi, splits, k_chunk, items, start, stop)])."""
+    if isinstance(cfg, str):
+        lib.hgemm_mi355x_config_by_name.argtypes = [ctypes.c_char_p]
+        cfg = lib.hgemm_mi355x_config_by_name(cfg.encode())
+        assert cfg >= 0
+    lda, ldb, ldc = lds or (k, k, n)
+    out = (ctypes.c_longlong * 28)()
+    st = lib.hgemm_mi355x_selfcheck_launch(cfg, splits, group, operands, m, n, k, lda, ldb, ldc, ruled_out, out)
+    disp = [(THUNKS[out[4 + 8 * i]],) + tuple(out[5 + 8 * i:12 + 8 * i]) for i in range(out[1])]
+    return st, FORMS[out[0]], out[2], out[3], disp
+
+
+def test_workspace_query_is_what_the_launch_asks_for(lib):
+    """hgemm_mi355x_plan_workspace_bytes promises exactly the launch's request (counters + slabs, 0 for none) on the operands
+    hgemm_mi355x_fp32 / _fp16 pass.  It used to size the plan by a copy of the launch's logic, which missed the hybrid tail's
+    slabs (0 reported, up to 64 MiB asked).  Every tuned row, every alternate, the planner's plan of every off-grid shape and
+    of a seeded fuzz, and random explicit plans; every form issues 1-3 dispatches, the first carrying the timing start event and
+    the last the stop event."""
+    import random
+
+    lib.hgemm_mi355x_plan_workspace_bytes.restype = ctypes.c_size_t
+    plans = []
+    for inc in ("hgemm_tuned_table.inc", "hgemm_tuned_alternates.inc"):
+        for ln in (PKG / "csrc" / inc).read_text().splitlines():
+            mm = re.match(r'\s*\{(\d+), (\d+), (\d+), "([^"]+)", (\d+), (\d+)\}', ln)
+            if mm:
+                plans.append((lib.hgemm_mi355x_config_by_name(mm[4].encode()), int(mm[5]), int(mm[1]), int(mm[2]), int(mm[3])))
+    assert len(plans) == 1000 + 1791
+    shapes = [tuple(map(int, ln.split("_"))) for ln in (PKG / "tools" / "offgrid_shapes.txt").read_text().split()
+              if not ln.startswith("#") and "_" in ln]
+    assert len(shapes) == 80
+    rnd = random.Random(23)
+    shapes += [(rnd.randrange(1, 20000), rnd.randrange(1, 5000) * 4, rnd.randrange(1, 2500) * 8) for _ in range(400)]
+    c, s, g = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    for (m, n, k) in shapes:
+        assert lib.hgemm_mi355x_plan(m, n, k, ctypes.byref(c), ctypes.byref(s), ctypes.byref(g)) == 0
+        if c.value >= 0:
+            plans.append((c.value, s.value, m, n, k))
+    n_cfg = lib.hgemm_mi355x_num_configs()
+    for _ in range(1500):
+        sp = rnd.choice([1, 2, 3, 4, 8, 2 | 0x10000, 4 | 0x10000, 0x40000, 0x40000 | 300, 0x40000 | 5000]) | rnd.choice([0, 0x20000, 0x80000])
+        plans.append((rnd.randrange(n_cfg), sp, rnd.choice([64, 200, 1000, 4096, 4352, 7168]), rnd.choice([64, 128, 1000, 4096, 4352]),
+                      rnd.choice([64, 128, 520, 1024, 4096, 4440, 8192])))
+    forms = set()
+    for (cfg, sp, m, n, k) in plans:
+        st, form, slab, _, disp = _resolve(lib, cfg, sp, m, n, k)
+        want = (COUNTERS + slab) if st == 0 and slab else 0
+        assert lib.hgemm_mi355x_plan_workspace_bytes(cfg, sp, m, n, k) == want, (cfg, hex(sp), m, n, k, form)
+        if st == 0:
+            forms.add(form)
+            assert 1 <= len(disp) <= 3 and [d[6] for d in disp] == [1] + [0] * (len(disp) - 1), (cfg, sp, m, n, k)
+            assert [d[7] for d in disp] == [0] * (len(disp) - 1) + [1], (cfg, sp, m, n, k)
+    assert forms >= {"stream-K", "split-K", "fused", "hybrid", "plain", "ragged"}
+
+
+def test_launch_decisions_of_the_persistent_families_are_pinned(lib):
+    """The combined decision of hgemm_mi355x_launch, worked out by hand from its rules: which form a call takes, with which grids,
+    splits and K chunks, and what it falls back to without workspace.  A silent change of form would still pass every exactness
+    test on the GPU (one launch instead of three shows up as a timing shift only)."""
+    lib.hgemm_mi355x_model_us.restype = ctypes.c_double
+    # 4352^2 x 4096 (test_hybrid_tail_schedule_is_exact_on_zero_one_inputs), splits = 1: K = 64 stages of 64.  The hybrid tail runs
+    # when the tile count is not a multiple of the resident workgroups G, S = min(G // tail, stages // 4) >= 2, and
+    # 0.6 tile_us - tile_us / S > 25 (tile_us: the model's time of one tile without the launch)
+    m = n = 4352
+    k = 4096
+
+    def tile_us(name):
+        return lib.hgemm_mi355x_model_us(lib.hgemm_mi355x_config_by_name(name.encode()), 1, *{"s256x256_w2x2": (256, 256),
+                                         "q256x256_w2x2": (256, 256), "s128x256_w2x2": (128, 256), "q256x128_w2x2": (256, 128)}[name], k) - 2.0
+
+    for name in ("s256x256_w2x2", "q256x256_w2x2"):
+        # 17 x 17 = 289 tiles, G = 256 (one 128 KiB workgroup per CU): 256 full + 33 tail tiles, S = min(256 // 33, 64 // 4) = 7,
+        # per slice ceil(64 / 7) = 10 stages (S stays ceil(64 / 10) = 7), 33 x 7 = 231 tail items of one 256 x 256 fp32 slab each
+        assert 0.6 * tile_us(name) - tile_us(name) / 7 > 25.0
+        assert _resolve(lib, name, 1, m, n, k) == (0, "hybrid", 231 * 256 * 256 * 4, 0, [
+            ("entry", 256, 0, 1, k, 256, 1, 0), ("entry", 231, 1, 7, 10 * 64, 231, 0, 0), ("tail_reduce", 0, 1, 7, 10 * 64, 231, 0, 1)])
+    for name in ("s128x256_w2x2", "q256x128_w2x2"):
+        # 34 x 17 = 578 tiles, G = 256 (96 KiB + 64 B per workgroup: one per CU): 66 tail tiles, S = min(256 // 66, 16) = 3, and a
+        # third of a ~44 us tile does not pay for the tail pass
+        assert 0.6 * tile_us(name) - tile_us(name) / 3 < 25.0
+        assert _resolve(lib, name, 1, m, n, k) == (0, "plain", 0, 0, [("entry", 256, 0, 1, k, 578, 1, 1)])
+    # fallbacks: split-K without workspace runs as splits = 1 -- and then takes the hybrid form; a hybrid tail without workspace runs
+    # the plain launch (one resident wave walking all 289 tiles)
+    q = "q256x256_w2x2"
+    hybrid = _resolve(lib, q, 1, m, n, k)
+    assert _resolve(lib, q, 2, m, n, k) == (0, "split-K", 2 * m * n * 4, 0, [("entry", 256, 1, 2, 32 * 64, 578, 1, 0),
+                                                                            ("splitk_reduce", 0, 1, 2, 32 * 64, 578, 0, 1)])
+    assert _resolve(lib, q, 2 | 0x10000, m, n, k) == (0, "fused", 289 * 2 * 256 * 256 * 4, 1, [("entry", 256, 2, 2, 32 * 64, 578, 1, 1)])
+    assert _resolve(lib, q, 2, m, n, k, ruled_out=1 << 3) == hybrid
+    assert _resolve(lib, q, 2 | 0x10000, m, n, k, ruled_out=1 << 4) == hybrid
+    assert _resolve(lib, q, 1, m, n, k, ruled_out=1 << 5) == (0, "plain", 0, 0, [("entry", 256, 0, 1, k, 289, 1, 1)])
+    assert _resolve(lib, q, 2, m, n, k, ruled_out=(1 << 3) | (1 << 5)) == (0, "plain", 0, 0, [("entry", 256, 0, 1, k, 289, 1, 1)])
+    # stream-K asked of a family without the kernel: splits = 1, which may again be the hybrid form
+    assert _resolve(lib, q, 0x40000 | 256, m, n, k) == hybrid
+
+    # fused split-K on the two-resident members: G = 512, but 80 KiB of stages + the 64-byte vote word fit once per CU -> 256
+    # workgroups.  4096^3: 22 x 32 = 704 tiles of 192 x 128 (32 x 22 of 128 x 192), two splits of 32 stages.
+    for name, tiles in (("q192x128_w2x2", 22 * 32), ("q128x192_w2x2", 32 * 22)):
+        assert _resolve(lib, name, 2 | 0x10000, 4096, 4096, 4096) == (0, "fused", tiles * 2 * 192 * 128 * 4, 1, [
+            ("entry", 256, 2, 2, 32 * 64, 2 * tiles, 1, 1)])
+        assert _resolve(lib, name, 2, 4096, 4096, 4096)[4][0] == ("entry", 512, 1, 2, 32 * 64, 2 * tiles, 1, 0)   # two-pass: 512
+    # (64 KiB of stages fit twice even with the vote word: no clamp)
+    assert _resolve(lib, "q128x128_w2x2", 2 | 0x10000, 4096, 4096, 4096)[4] == [("entry", 512, 2, 2, 32 * 64, 2 * 32 * 32, 1, 1)]
+
+    # stream-K: G = min(the plan's workgroups (<= 4096; 0 / 1: 256 x workgroups per CU), tiles x stages // min stages per run), with
+    # r128x128_k128 (stages of 128, at least 3 per run) on 12288 x 128 x 8192: 96 tiles x 64 stages = 6144 -> at most 2048 runs
+    r = "r128x128_k128"
+    sk_per_cu = lib.hgemm_mi355x_config_streamk(lib.hgemm_mi355x_config_by_name(r.encode()))
+    for g_plan, G in ((256, 256), (5000, 6144 // 3), (0, 256 * sk_per_cu), (3000, 6144 // 3)):
+        assert _resolve(lib, r, 0x40000 | g_plan, 12288, 128, 8192) == (0, "stream-K", 2 * G * 128 * 128 * 4, 1, [
+            ("entry", G, 3, 1, 8192, 96, 1, 1)]), g_plan
+    # 256 x 128 x 512: 2 tiles x 4 stages -> 8 // 3 = 2 workgroups
+    assert _resolve(lib, r, 0x40000 | 256, 256, 128, 512)[1:3] == ("stream-K", 2 * 2 * 128 * 128 * 4)
+    # no workspace, or a direct K tail (family r has no stream-K kernel with one): the plain launch, one workgroup per tile
+    plain = (0, "plain", 0, 0, [("entry", 96, 0, 1, 8192, 96, 1, 1)])
+    assert _resolve(lib, r, 0x40000 | 256, 12288, 128, 8192, ruled_out=1 << 2) == plain
+    assert _resolve(lib, r, 0x40000 | 256, 12288, 128, 8192 + 64)[1:3] == ("plain", 0)
+
+
+def test_launch_decisions_off_the_lds_dma_path_are_pinned(lib):
+    """Calls the LDS-DMA kernels cannot take: unaligned operands, strides beyond the 32-bit reach, K the geometry does not accept
+    -> the ragged kernel (HGEMM_ERR_TOO_LARGE past 2^31 tiles of 64 x 64); HGEMM_CONFIG_GENERIC or no b_col_major -> the
+    reference kernel (HGEMM_ERR_BAD_ARG without b); a K that is whole 64-steps but not the geometry's stages -> HGEMM_ERR_BAD_ARG."""
+    q = "q256x256_w2x2"
+    ragged = (0, "ragged", 0, 0, [("ragged", 0, 0, 1, 4096, 1, 1, 1)])
+    reference = (0, "reference", 0, 0, [("generic", 0, 0, 1, 4096, 1, 1, 1)])
+    assert _resolve(lib, q, 2, 4096, 4096, 4096, operands=3) == ragged                             # pointers not 16-byte aligned
+    assert _resolve(lib, q, 2, 4096, 4096, 4096, lds=(4100, 4096, 4096)) == ragged                # lda % 8 != 0
+    assert _resolve(lib, q, 1, 4096, 4096, 4096, lds=(1 << 23, 4096, 4096)) == ragged            # 256 rows x 16 MiB >= 4 GiB
+    assert _resolve(lib, "q128x128_w2x2", 1, 4096, 4096, 4096, lds=(1 << 23, 4096, 4096))[1] == "plain"   # 128 rows: < 4 GiB
+    assert _resolve(lib, "t128x128_w2x2_m16_s3", 1, 4096, 4096, 4096, lds=(1 << 23, 4096, 4096)) == ragged   # classic: 2 GiB
+    assert _resolve(lib, q, 1, 4096, 4096, 100)[1] == "ragged"                                     # K % 8 != 0
+    assert _resolve(lib, -2, 1, 4096, 4096, 4096) == ragged
+    assert _resolve(lib, -1, 1, 4096, 4096, 4096) == reference
+    assert _resolve(lib, q, 1, 4096, 4096, 4096, operands=1 | 4) == reference                     # no b_col_major
+    assert _resolve(lib, -1, 1, 4096, 4096, 4096, operands=2 | 4)[0] == -1                        # no b
+    assert _resolve(lib, q, 1, 4096, 4096, 4096, operands=4)[0] == -1
+    assert _resolve(lib, "q128x128_w2x2_k128", 1, 4096, 4096, 64)[0] == -1                        # 64 < one stage of 128
+    big = 1 << 30                                                                                  # 2^24 x 2^24 tiles of 64 x 64
+    assert _resolve(lib, -2, 1, big, big, 64, operands=3)[0] == -2
+    assert _resolve(lib, q, 1, big, big, 64, operands=3)[0] == -2
+
+
 def test_plan_flags_of_round_5_are_flags_not_split_counts(lib):
     """HGEMM_PLAN_XCD_STAGGER (family q's kstagger variant), HGEMM_PLAN_PHASE_OFFSET(4), HGEMM_PLAN_WAVE_PRIORITY ride in `splits`
     like the older flags: the model prices the plan, never the flag bits; the two-resident members report two workgroups per
