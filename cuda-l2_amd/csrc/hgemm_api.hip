@@ -519,6 +519,9 @@ LaunchPlan resolve_launch(int config_id, int splits_arg, int group_m, bool has_b
     ++p.n;
   };
   auto fail = [&p](int status) { p.status = status; return p; };
+  // rows must not overlap: lda >= K, ldc >= N, ldb >= K where b_col_major is given (the row-major b is read at stride N).  K, N >= 1,
+  // so a stride of 0 or below is rejected as well (ldc = 0 would pass mfma_path_ok and write every row over row 0)
+  if (lda < K || ldc < N || (has_bt && ldb < K)) return fail(HGEMM_ERR_BAD_ARG);
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;

@@ -32,6 +32,11 @@
     throw std::runtime_error("Tensor size mismatch!");          \
   }
 
+#define CHECK_TORCH_TENSOR_CONTIGUOUS(T)                        \
+  if (!(T).is_contiguous()) {                                   \
+    throw std::runtime_error(#T " must be contiguous");         \
+  }
+
 namespace hgemm_shim {
 
 inline void* current_stream() { return (void*)c10::hip::getCurrentHIPStream().stream(); }
@@ -41,18 +46,26 @@ inline void check_status(int st, const char* what) {
     throw std::runtime_error(std::string(what) + ": " + hgemm_mi355x_strerror(st));
 }
 
-// a: [M,K], second operand: [K,N]-shaped tensor (b or b_col_major), c: [M,N]; all fp16.
+// a: [M,K], b: [K,N], b_col_major: B^T's storage -- [N,K], or [K,N] as the harness's as_col_major shapes it --, c: [M,N];
+// all fp16 and contiguous (the C ABI takes the operands without strides: a view would be read and written as if it were dense).
 struct Problem {
   int M, N, K;
 };
-inline Problem check(const torch::Tensor& a, const torch::Tensor& b2, const torch::Tensor& c) {
+inline Problem check(const torch::Tensor& a, const torch::Tensor& b, const torch::Tensor& b_col_major, const torch::Tensor& c) {
   CHECK_TORCH_TENSOR_DTYPE(a, torch::kHalf)
-  CHECK_TORCH_TENSOR_DTYPE(b2, torch::kHalf)
+  CHECK_TORCH_TENSOR_DTYPE(b, torch::kHalf)
+  CHECK_TORCH_TENSOR_DTYPE(b_col_major, torch::kHalf)
   CHECK_TORCH_TENSOR_DTYPE(c, torch::kHalf)
-  const int M = a.size(0), K = a.size(1), N = b2.size(1);
-  CHECK_TORCH_TENSOR_SHAPE(a, M, K)
-  CHECK_TORCH_TENSOR_SHAPE(b2, K, N)
+  if (a.dim() != 2 || b.dim() != 2 || b_col_major.dim() != 2 || c.dim() != 2) throw std::runtime_error("Tensor size mismatch!");
+  const int M = a.size(0), K = a.size(1), N = b.size(1);
+  CHECK_TORCH_TENSOR_SHAPE(b, K, N)
+  if (!((b_col_major.size(0) == N && b_col_major.size(1) == K) || (b_col_major.size(0) == K && b_col_major.size(1) == N)))
+    throw std::runtime_error("Tensor size mismatch!");
   CHECK_TORCH_TENSOR_SHAPE(c, M, N)
+  CHECK_TORCH_TENSOR_CONTIGUOUS(a)
+  CHECK_TORCH_TENSOR_CONTIGUOUS(b)
+  CHECK_TORCH_TENSOR_CONTIGUOUS(b_col_major)
+  CHECK_TORCH_TENSOR_CONTIGUOUS(c)
   return {M, N, K};
 }
 
@@ -62,12 +75,12 @@ inline Problem check(const torch::Tensor& a, const torch::Tensor& b2, const torc
 void init_cublas_handle() { hgemm_shim::check_status(hgemm_rocblas_init(), "rocblas init"); }
 void destroy_cublas_handle() { hgemm_rocblas_destroy(); }
 void hgemm_cublas_nn(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major, torch::Tensor c) {
-  auto p = hgemm_shim::check(a, b, c);
+  auto p = hgemm_shim::check(a, b, b_col_major, c);
   hgemm_shim::check_status(hgemm_rocblas_nn(a.data_ptr(), b.data_ptr(), c.data_ptr(), p.M, p.N, p.K, HGEMM_ACC_MODE,
                                             hgemm_shim::current_stream()), "rocblas nn");
 }
 void hgemm_cublas_tn(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major, torch::Tensor c) {
-  auto p = hgemm_shim::check(a, b_col_major, c);
+  auto p = hgemm_shim::check(a, b, b_col_major, c);
   hgemm_shim::check_status(hgemm_rocblas_tn(a.data_ptr(), b_col_major.data_ptr(), c.data_ptr(), p.M, p.N, p.K,
                                             HGEMM_ACC_MODE, hgemm_shim::current_stream()), "rocblas tn");
 }
@@ -76,13 +89,13 @@ void hgemm_cublas_tn(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major
 void init_cublaslt_handle_v1() { hgemm_shim::check_status(hgemm_hipblaslt_heuristic_init(), "hipblaslt init"); }
 void destroy_cublaslt_handle_v1() { hgemm_hipblaslt_heuristic_destroy(); }
 void hgemm_cublaslt_heuristic_nn(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major, torch::Tensor c) {
-  auto p = hgemm_shim::check(a, b, c);
+  auto p = hgemm_shim::check(a, b, b_col_major, c);
   hgemm_shim::check_status(hgemm_hipblaslt_heuristic_nn(a.data_ptr(), b.data_ptr(), c.data_ptr(), p.M, p.N, p.K,
                                                         HGEMM_ACC_MODE, hgemm_shim::current_stream()),
                            "hipblaslt heuristic nn");
 }
 void hgemm_cublaslt_heuristic_tn(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major, torch::Tensor c) {
-  auto p = hgemm_shim::check(a, b_col_major, c);
+  auto p = hgemm_shim::check(a, b, b_col_major, c);
   hgemm_shim::check_status(hgemm_hipblaslt_heuristic_tn(a.data_ptr(), b_col_major.data_ptr(), c.data_ptr(), p.M,
                                                         p.N, p.K, HGEMM_ACC_MODE, hgemm_shim::current_stream()),
                            "hipblaslt heuristic tn");
@@ -98,13 +111,13 @@ void find_best_algo_tn_v2_torch(int M, int N, int K) {
   hgemm_shim::check_status(hgemm_hipblaslt_autotune_find_best_tn(M, N, K, HGEMM_ACC_MODE), "[V2] No algorithm found for TN");
 }
 void hgemm_cublaslt_auto_tuning_nn(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major, torch::Tensor c) {
-  auto p = hgemm_shim::check(a, b, c);
+  auto p = hgemm_shim::check(a, b, b_col_major, c);
   hgemm_shim::check_status(hgemm_hipblaslt_autotune_nn(a.data_ptr(), b.data_ptr(), c.data_ptr(), p.M, p.N, p.K,
                                                        HGEMM_ACC_MODE, hgemm_shim::current_stream()),
                            "hipblaslt autotune nn");
 }
 void hgemm_cublaslt_auto_tuning_tn(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major, torch::Tensor c) {
-  auto p = hgemm_shim::check(a, b_col_major, c);
+  auto p = hgemm_shim::check(a, b, b_col_major, c);
   hgemm_shim::check_status(hgemm_hipblaslt_autotune_tn(a.data_ptr(), b_col_major.data_ptr(), c.data_ptr(), p.M,
                                                        p.N, p.K, HGEMM_ACC_MODE, hgemm_shim::current_stream()),
                            "hipblaslt autotune tn");
@@ -116,12 +129,9 @@ extern "C" int cuda_l2_mi355x_shape_launch(const void* a, const void* b, const v
 
 #define HGEMM_DEFINE_CUDA_L2_ENTRY(name)                                                                      \
   void name(torch::Tensor a, torch::Tensor b, torch::Tensor b_col_major, torch::Tensor c) {                   \
-    CHECK_TORCH_TENSOR_DTYPE(a, torch::kHalf)                                                                 \
-    CHECK_TORCH_TENSOR_DTYPE(b, torch::kHalf)                                                                 \
-    CHECK_TORCH_TENSOR_DTYPE(c, torch::kHalf)                                                                 \
-    const int M = a.size(0), K = a.size(1), N = b.size(1);                                                    \
+    const auto p = hgemm_shim::check(a, b, b_col_major, c);                                                    \
     hgemm_shim::check_status(cuda_l2_mi355x_shape_launch(a.data_ptr(), b.data_ptr(), b_col_major.data_ptr(),  \
-                                                         c.data_ptr(), M, N, K, hgemm_shim::current_stream()), \
+                                                         c.data_ptr(), p.M, p.N, p.K, hgemm_shim::current_stream()), \
                              #name);                                                                          \
   }
 

@@ -137,7 +137,9 @@ int hgemm_mi355x_fp16(const void* a, const void* b, const void* b_col_major, voi
  *   splits     split-K factor >= 1, optionally | HGEMM_SPLITK_FUSED (see above); clamped to K / 64;
  *              degrades to 1 when no workspace is available (lent buffer too small, out of memory)
  *   group_m    rasterisation group height in tiles (>= 1)
- * lda/ldb/ldc are row strides in elements (ldb is the row stride of b_col_major, i.e. >= K). */
+ * lda/ldb/ldc are row strides in elements: lda of a (>= K), ldb of b_col_major (>= K; unused without b_col_major), ldc of c
+ * (>= N); a smaller stride (zero and negative ones included) returns HGEMM_ERR_BAD_ARG.  The row-major b is always read at
+ * stride N. */
 int hgemm_mi355x_launch(int config_id, int splits, int group_m,
                         const void* a, const void* b, const void* b_col_major, void* c,
                         int M, int N, int K, int lda, int ldb, int ldc, void* stream);

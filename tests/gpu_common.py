@@ -29,24 +29,35 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def gemm(a_np: np.ndarray, b_np: np.ndarray, entry: str = "fp32", plan=None) -> np.ndarray:
-    """C = A.B on the GPU through the C ABI; plan = (config_id, splits, group_m) for an explicit launch."""
+def gemm(a_np: np.ndarray, b_np: np.ndarray, entry: str = "fp32", plan=None, ld=None) -> np.ndarray:
+    """C = A.B on the GPU through the C ABI; plan = (config_id, splits, group_m) for an explicit launch.  ld = (lda, ldb, ldc)
+    (explicit plans only) places A, b_col_major and C in wider buffers: A's columns K..lda-1 and b_col_major's K..ldb-1 hold NaN
+    (0 x NaN = NaN: a read of them shows in C), C's columns N..ldc-1 hold -3.0 (no 0/1 product is negative), and every padding
+    element must come back bit-unchanged.  The row-major b stays contiguous (the library reads it at stride N)."""
     L = lib()
     m, k = a_np.shape
     n = b_np.shape[1]
-    a = torch.from_numpy(np.ascontiguousarray(a_np)).cuda()
+    assert ld is None or plan is not None, "the entry points take contiguous operands"
+    lda, ldb, ldc = ld or (k, k, n)
     b = torch.from_numpy(np.ascontiguousarray(b_np)).cuda()
-    bt = b.t().contiguous()
-    c = torch.full((m, n), float("nan"), dtype=torch.half, device="cuda")  # unwritten outputs stay NaN
+    a = torch.full((m, lda), float("nan"), dtype=torch.half, device="cuda")
+    a[:, :k] = torch.from_numpy(np.ascontiguousarray(a_np)).cuda()
+    bt = torch.full((n, ldb), float("nan"), dtype=torch.half, device="cuda")
+    bt[:, :k] = b.t()
+    c = torch.full((m, ldc), -3.0, dtype=torch.half, device="cuda")
+    c[:, :n] = float("nan")  # unwritten outputs stay NaN
+    pads = [(x[:, w:], x[:, w:].clone()) for x, w in ((a, k), (bt, k), (c, n))]
     if plan is None:
         fn = L.hgemm_mi355x_fp16 if entry == "fp16" else L.hgemm_mi355x_fp32
         st = fn(a.data_ptr(), b.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, stream())
     else:
         st = L.hgemm_mi355x_launch(plan[0], plan[1], plan[2], a.data_ptr(), b.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n,
-                                   k, k, k, n, stream())
+                                   k, lda, ldb, ldc, stream())
     assert st == 0, L.hgemm_mi355x_strerror(st)
     torch.cuda.synchronize()
-    return c.cpu().numpy()
+    for pad, before in pads:
+        assert torch.equal(pad.view(torch.int16), before.view(torch.int16)), f"padding changed (lda, ldb, ldc = {lda}, {ldb}, {ldc})"
+    return c[:, :n].contiguous().cpu().numpy()
 
 
 def config_names():

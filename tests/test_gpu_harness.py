@@ -53,6 +53,20 @@ def test_entry_point_semantics_and_errors(kernel):
         f(a.float(), b, as_col_major(b), c)
     with pytest.raises(RuntimeError, match="Tensor size mismatch"):
         kernel.module.hgemm_cublas_nn(a, b, as_col_major(b), torch.zeros(64, 64, dtype=torch.half, device="cuda"))
+    # the C ABI takes dense operands: a view or a wrong shape is an error, not a silently wrong C (every input below is chosen so
+    # that an unchecked call would still read and write inside the tensors' storage)
+    wide = torch.randn(64, 96, dtype=torch.half, device="cuda")
+    tall = torch.full((80, 4096), -3.0, dtype=torch.half, device="cuda")
+    for fn in (f, kernel.module.hgemm_cublas_tn):
+        c.fill_(-3.0)
+        with pytest.raises(RuntimeError, match="must be contiguous"):
+            fn(wide[:, :64], b, as_col_major(b), c)                         # a: a [64, 64] view of a wider tensor
+        with pytest.raises(RuntimeError, match="must be contiguous"):
+            fn(a, b, b.t(), c)                                              # b_col_major: the transpose view, not its storage
+        with pytest.raises(RuntimeError, match="Tensor size mismatch"):
+            fn(a, b, as_col_major(b), tall)                                 # c: 16 rows too many
+        torch.cuda.synchronize()
+        assert bool((c == -3.0).all()) and bool((tall == -3.0).all())
     # another shape through the same extension still computes correctly (library planner fall-back)
     a2 = torch.randn(128, 256, dtype=torch.half, device="cuda")
     b2 = torch.randn(256, 192, dtype=torch.half, device="cuda")

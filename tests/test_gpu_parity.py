@@ -109,9 +109,9 @@ def test_stream_k_is_exact_and_deterministic(g, oracle, case):
     rng = np.random.default_rng(m + 3 * n + 7 * k)
     a, b = oracle.zero_one_inputs(m, n, k, rng)
     truth = oracle.truth_numpy(a, b)
-    for _ in range(2):
-        got = g.gemm(a, b, plan=(cid, 0x40000 | wgs, group))
-        assert np.array_equal(got.view(np.uint16), truth.view(np.uint16)), case
+    for ld in (None, None, (k + 8, k + 64, n + 4)):   # twice contiguous (the arrival counters must be back at zero), then padded
+        got = g.gemm(a, b, plan=(cid, 0x40000 | wgs, group), ld=ld)
+        assert np.array_equal(got.view(np.uint16), truth.view(np.uint16)), (case, ld)
     ar = torch.randn((m, k), dtype=torch.half, device="cuda")
     br = torch.randn((k, n), dtype=torch.half, device="cuda")
     btr = br.t().contiguous()
@@ -455,7 +455,8 @@ def test_dispatch_attached_timing_hook_is_one_shot_and_plausible(g):
 def test_hybrid_tail_schedule_is_exact_on_zero_one_inputs(g, shape):
     """Persistent family, tile count not a multiple of the resident workgroups: full rounds + K-split
     tail tiles + compact-slab combine (hgemm_api.hip).  Integer-valued inputs make every fp32 sum exact,
-    so the result must be bit-identical to the CPU product whatever the summation order."""
+    so the result must be bit-identical to the CPU product whatever the summation order.  Contiguous and at
+    padded strides (the tail reduce writes C at ldc; ldc % 8 = 4: narrow epilogue)."""
     m, n, k = shape
     rng = np.random.default_rng(7)
     a = (rng.random((m, k)) < 0.25).astype(np.float16)
@@ -464,8 +465,9 @@ def test_hybrid_tail_schedule_is_exact_on_zero_one_inputs(g, shape):
     assert float(np.abs(truth).max()) <= 2047
     names = g.config_names()
     for cfg in ("s256x256_w2x2", "s128x256_w2x2", "q256x256_w2x2", "q256x128_w2x2"):
-        got = g.gemm(a, b, plan=(names.index(cfg), 1, 4))
-        assert np.array_equal(got.view(np.uint16), truth.view(np.uint16)), cfg
+        for ld in (None, (k + 8, k + 64, n + 4)):
+            got = g.gemm(a, b, plan=(names.index(cfg), 1, 4), ld=ld)
+            assert np.array_equal(got.view(np.uint16), truth.view(np.uint16)), (cfg, ld)
     # the library's own plan for the shape (whatever it picks) agrees as well
     assert np.array_equal(g.gemm(a, b).view(np.uint16), truth.view(np.uint16))
 

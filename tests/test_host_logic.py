@@ -871,6 +871,23 @@ def test_launch_decisions_off_the_lds_dma_path_are_pinned(lib):
     big = 1 << 30                                                                                  # 2^24 x 2^24 tiles of 64 x 64
     assert _resolve(lib, -2, 1, big, big, 64, operands=3)[0] == -2
     assert _resolve(lib, q, 1, big, big, 64, operands=3)[0] == -2
+    # strides below the row length (overlapping rows; ldc = 0 passes the alignment rule and writes every row over row 0; a negative
+    # ldc writes in front of C) -> HGEMM_ERR_BAD_ARG on every path; ldb only where b_col_major is given
+    k = n = 4096
+    for lds in ((k - 8, k, n), (k, k - 8, n), (k, k, n - 4), (0, k, n), (k, 0, n), (k, k, 0), (-k, k, n), (k, -k, n), (k, k, -n)):
+        for cfg, operands in ((q, 7), (q, 3), ("t128x128_w2x2_m16_s3", 7), ("r64x64_k256", 7), (-2, 7), (-1, 7)):
+            for splits in (1, 2, 2 | 0x10000, 0x40000 | 64):
+                assert _resolve(lib, cfg, splits, 4096, n, k, lds=lds, operands=operands)[0] == -1, (cfg, lds, operands, hex(splits))
+    for lds in ((k, k - 8, n), (k, 0, n), (k, -k, n)):                                             # no b_col_major: ldb unused
+        assert _resolve(lib, q, 1, 4096, n, k, lds=lds, operands=1 | 4) == reference
+        assert _resolve(lib, -1, 1, 4096, n, k, lds=lds, operands=1 | 4) == reference
+    # (K, K, N) and wider strides resolve as before
+    for cfg, splits in ((q, 1), (q, 2), (q, 2 | 0x10000), ("r128x128_k128", 0x40000 | 256), ("t128x128_w2x2_m16_s3", 3), (-2, 1), (-1, 1)):
+        want = _resolve(lib, cfg, splits, 4096, n, k)
+        assert want[0] == 0
+        for lds in ((k, k, n), (k + 64, k + 64, n + 64), (k + 8, k + 16, n + 4)):
+            assert _resolve(lib, cfg, splits, 4096, n, k, lds=lds) == want, (cfg, hex(splits), lds)
+        assert _resolve(lib, cfg, splits, 4096, n, k, lds=(k + 4, k, n))[1] == ("reference" if cfg == -1 else "ragged")
 
 
 def test_plan_flags_of_round_5_are_flags_not_split_counts(lib):
