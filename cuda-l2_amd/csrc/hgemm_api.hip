@@ -322,6 +322,7 @@ void model_plan(int M, int N, int K, int* cfg, int* splits, int* group_m) {
     if (e.bn > N * 2 && e.bn > 32) continue;
     if (!k_ok(e, K)) continue;
     if ((e.name[0] == 's' || e.name[0] == 'q') && e.mi == 32) continue;   // experimental 32x32x16 members: explicit plans only
+    if (e.name[0] == 'u') continue;                                       // family u (split inside the workgroup): explicit plans only
     // family "w" inside its domain only: a K of one or two pipeline steps, or a tiny output with a long K
     if (e.name[0] == 'w' && !(K <= 128 || (long)M * N <= 128L * 128L)) continue;
     for (int s = 1; s <= 64; s *= 2) {
@@ -546,6 +547,7 @@ LaunchPlan resolve_launch(int config_id, int splits_arg, int group_m, bool has_b
     const double reach = mark31 ? 2147483648.0 : 4294967296.0;
     if ((double)e.bm * lda * 2.0 + K * 2.0 >= reach || (double)e.bn * ldb * 2.0 + K * 2.0 >= reach) fast = false;
     if (K % BK != 0 && !k_ok(e, K)) fast = false;   // a partial last K-step on a geometry that cannot take it: any-shape kernel
+    if (e.name[0] == 'u' && !k_ok(e, K)) fast = false;   // family u: a K that is not whole stages (128 / 256) likewise
     // the LDS-staged epilogue addresses a wave tile through one buffer descriptor with 32-bit offsets
     if ((double)e.bm * ldc * 2.0 + (double)N * 2.0 >= 2147483648.0) fast = false;
   }
@@ -827,6 +829,11 @@ int hgemm_mi355x_config_k_granularity(int id) {
 int hgemm_mi355x_config_accepts_k(int id, int K) {
   if (id < 0 || id >= g_num_kernels) return K > 0 ? 1 : 0;   // the special ids take any K
   return K > 0 && k_ok(g_kernel_table[id], K) ? 1 : 0;
+}
+
+int hgemm_mi355x_config_local_splits(int id) {
+  if (id < 0 || id >= g_num_kernels) return -1;
+  return g_kernel_table[id].name[0] == 'u' ? LU_KS : 1;
 }
 
 int hgemm_mi355x_config_by_name(const char* name) {

@@ -3,6 +3,7 @@
 #include "hgemm_kernel_rs.hpp"
 #include "hgemm_kernel_sq.hpp"
 #include "hgemm_kernel_wd.hpp"
+#include "hgemm_kernel_lu.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -118,6 +119,15 @@ void launch_wd(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingS
     HGEMM_LAUNCH((hgemm_tn_wd_kernel<CFG, EPI_SLAB>), grid, CFG::THREADS, stream, ts, g);
   else
     HGEMM_LAUNCH((hgemm_tn_wd_kernel<CFG, EPI_C16>), grid, CFG::THREADS, stream, ts, g);
+}
+
+// family u (hgemm_kernel_lu.hpp): plain and two-pass slab epilogues; the host never sends it a single-launch or stream-K plan
+template <class CFG>
+void launch_lu(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB)
+    HGEMM_LAUNCH((hgemm_tn_lu_kernel<CFG, EPI_SLAB>), grid, CFG::THREADS, stream, ts, g);
+  else
+    HGEMM_LAUNCH((hgemm_tn_lu_kernel<CFG, EPI_C16>), grid, CFG::THREADS, stream, ts, g);
 }
 
 struct KernelEntry {

@@ -23,6 +23,10 @@ namespace hgemm_mi355x {
 #undef HGEMM_SQ
 #undef HGEMM_RS
 #undef HGEMM_WD
+#define HGEMM_LU(BM, BN, WM, WN, NIMG, NB) \
+  extern template void launch_lu<CfgLU<BM, BN, WM, WN, NIMG, NB>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#include "hgemm_configs_lu.def"
+#undef HGEMM_LU
 
 // The table holds host function pointers: keep it out of the device pass.
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -98,6 +102,14 @@ const KernelEntry g_kernel_table[] = {
   {wd_name<CfgWD<FM, FN, KW>::BM, CfgWD<FM, FN, KW>::BN, KW>(), CfgWD<FM, FN, KW>::BM, CfgWD<FM, FN, KW>::BN, CfgWD<FM, FN, KW>::WM, \
    CfgWD<FM, FN, KW>::WN, 16, 1, CfgWD<FM, FN, KW>::THREADS, CfgWD<FM, FN, KW>::LDS_BYTES, &launch_wd<CfgWD<FM, FN, KW>>, 0, true, 64, false, 0},
 #include "hgemm_configs.def"
+// family "u" (hgemm_kernel_lu.hpp), behind every other family so that their ids stay put: WM x WN is the wave grid of ONE of the
+// four K-groups ("_k4": threads = WM * WN * 4 * 64); no single-launch split-K, no K tail, no stream-K; K granularity = the stage
+#define HGEMM_LU(BM, BN, WM, WN, NIMG, NB)                                                                        \
+  {"u" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN) "_k4", BM, BN, WM, WN, 16, NB,           \
+   CfgLU<BM, BN, WM, WN, NIMG, NB>::THREADS, CfgLU<BM, BN, WM, WN, NIMG, NB>::LDS_BYTES,                            \
+   &launch_lu<CfgLU<BM, BN, WM, WN, NIMG, NB>>, 0, false, CfgLU<BM, BN, WM, WN, NIMG, NB>::STAGE_K, false, 0},
+#include "hgemm_configs_lu.def"
+#undef HGEMM_LU
 };
 #undef HGEMM_CFG
 #undef HGEMM_SP

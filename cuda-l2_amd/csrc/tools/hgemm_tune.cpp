@@ -5,6 +5,9 @@
 //                                                     (zero_one_correctness_check.py:65-92,263-268)
 //   hgemm_tune tune  --shapes M_N_K,... | --shape-file F  [--out F.jsonl] [--keep R] [--baselines] [--fused] [--streamk] [--nt]
 //                                                     time candidate plans, print one JSON line per shape
+//   hgemm_tune tune  --plan-only --baselines --interleave [--stream] [--autotune] [--also CONFIG:SPLITS:GROUP,...] --shapes ...
+//                                                     the library's plan, the vendor baselines and the named explicit plans in the
+//                                                     same interleaved rounds (family u: a candidate only by name, --configs / --also)
 //   hgemm_tune bench --shape M_N_K [--config NAME --splits S --group G] [--reps N] [--lib]
 //                                                     run one plan N times (for rocprofv3)
 //   hgemm_tune bench --shape M_N_K --baseline X --isolated [--reps N]   a vendor baseline one launch at a time (for rocprofv3 --pmc)
@@ -209,6 +212,11 @@ static bool g_try_nt = false;   // tune --nt: streaming C stores for the winner,
 // (DESIGN.md section 6.7).  Same record keys as the sequential report, plus "protocol".
 static bool g_interleave = false;
 static bool g_reverse = false;
+// tune --plan-only --baselines --interleave --also config:splits:group,...: explicit plans timed as further contenders of the SAME
+// interleaved rounds as the library's plan and the baselines (how a new family is compared with the shipped plan before any table
+// row moves); a plan whose geometry does not take the shape's K is left out.  Recorded under "also".
+struct AlsoPlan { std::string cfg; int splits, group; };
+static std::vector<AlsoPlan> g_also;
 #include <functional>
 struct Contender {
   const char* key;                          // JSON key stem
@@ -305,6 +313,8 @@ static std::vector<Plan> candidates(const Shape& sh, double keep_ratio, int max_
     if (info[0] > sh.M * 2 && info[0] > 32) continue;
     if (info[1] > sh.N * 2 && info[1] > 32) continue;
     if (!hgemm_mi355x_config_accepts_k(c, sh.K)) continue;
+    // family u (K split inside the workgroup) is a candidate only when --configs names it: no plan of the table uses it yet
+    if (hgemm_mi355x_config_local_splits(c) > 1 && g_config_filter.empty()) continue;
     for (int s = 1; s <= 64; s *= 2) {
       if (s > 1 && ksteps / s < 2) break;
       const long wgs = (long)((sh.M + info[0] - 1) / info[0]) * ((sh.N + info[1] - 1) / info[1]) * s;
@@ -414,6 +424,8 @@ static int cmd_check(const std::vector<Shape>& shapes) {
                                    // the walk's phase flags (prologue only: a sleep / a priority): alone, together, with a stagger
                                    1 | HGEMM_PLAN_PHASE_OFFSET, 1 | HGEMM_PLAN_PHASE_OFFSET4, 1 | HGEMM_PLAN_PHASE_OFFSET8, 1 | HGEMM_PLAN_WAVE_PRIORITY | HGEMM_PLAN_NT_STORE,
                                    2 | HGEMM_PLAN_PHASE_OFFSET | HGEMM_PLAN_WAVE_PRIORITY | HGEMM_PLAN_XCD_STAGGER});
+      if (fam == 'u')   // family u (K split inside the workgroup): external splits 5 and 16 on top of 1 / 2 / 3 / 8, non-temporal stores
+        forms.insert(forms.end(), {5, 16, 1 | HGEMM_PLAN_NT_STORE, 2 | HGEMM_PLAN_NT_STORE});
       for (int splits : forms) {
         const bool sk = (splits & HGEMM_PLAN_STREAMK) != 0;
         const int sp = sk ? 2 : (splits & HGEMM_SPLITK_MASK);   // (sp > 1: run twice, one raster group)
@@ -461,7 +473,7 @@ static int cmd_check(const std::vector<Shape>& shapes) {
     if (g_config_filter.empty() || std::find(g_config_filter.begin(), g_config_filter.end(), std::string(cname)) != g_config_filter.end())
       printf(" %s", cname);
   }
-  printf("\ncheck-forms: 1 2 3 8 2|fused 8|fused 3|fused 5|fused 7|fused 13|fused 16|fused 21|fused 32|fused 37|fused 48|fused (3|fused .. 48|fused: K >= 2048) streamk|0 streamk|5 streamk|37 streamk|300 (stream-K on the geometries that have the kernel), family r also 1|xcd-stagger|nt-loads 2|fused|xcd-stagger 3|nt-loads streamk|37|xcd-stagger|nt-loads, family q also 1|xcd-stagger 1|xcd-stagger|nt-store 3|xcd-stagger 4|fused|xcd-stagger 1|phase-offset 1|phase-offset4 1|phase-offset8 1|wave-priority|nt-store 2|phase-offset|wave-priority|xcd-stagger, raster groups 1 4\n");
+  printf("\ncheck-forms: 1 2 3 8 2|fused 8|fused 3|fused 5|fused 7|fused 13|fused 16|fused 21|fused 32|fused 37|fused 48|fused (3|fused .. 48|fused: K >= 2048) streamk|0 streamk|5 streamk|37 streamk|300 (stream-K on the geometries that have the kernel), family r also 1|xcd-stagger|nt-loads 2|fused|xcd-stagger 3|nt-loads streamk|37|xcd-stagger|nt-loads, family q also 1|xcd-stagger 1|xcd-stagger|nt-store 3|xcd-stagger 4|fused|xcd-stagger 1|phase-offset 1|phase-offset4 1|phase-offset8 1|wave-priority|nt-store 2|phase-offset|wave-priority|xcd-stagger, family u also 5 16 1|nt-store 2|nt-store (its fused / stream-K words run as two-pass / plain), raster groups 1 4\n");
   printf("check: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs)\n", runs, failures);
   return failures ? 1 : 0;
 }
@@ -622,6 +634,7 @@ static int cmd_tune(const std::vector<Shape>& shapes, const char* out_path, doub
     int at_cached[2] = {0, 0};
     const bool interleaved = baselines && g_plan_only && g_interleave;
     int il_rounds = 0, il_stream_rounds = 0;
+    std::string also_json;
     if (interleaved) {
       bool have_at_nn = false, have_at_tn = false;
       if (autotune) {   // the search first: nothing of it may sit between two timed samples
@@ -639,6 +652,17 @@ static int cmd_tune(const std::vector<Shape>& shapes, const char* out_path, doub
       cs.push_back({"heur_tn", [&](Buffers& b) { return hgemm_hipblaslt_heuristic_tn(b.a, b.bt, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
       if (have_at_nn) cs.push_back({"auto_nn", [&](Buffers& b) { return hgemm_hipblaslt_autotune_nn(b.a, b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
       if (have_at_tn) cs.push_back({"auto_tn", [&](Buffers& b) { return hgemm_hipblaslt_autotune_tn(b.a, b.bt, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
+      std::vector<std::string> also_keys;
+      also_keys.reserve(g_also.size());
+      std::vector<Plan> also_plans;
+      for (const AlsoPlan& ap : g_also) {
+        const int ac = hgemm_mi355x_config_by_name(ap.cfg.c_str());
+        if (ac < 0 || !hgemm_mi355x_config_accepts_k(ac, sh.K)) continue;
+        const Plan q{ac, ap.splits, ap.group > 0 ? ap.group : default_group(ac, sh), 0.0};
+        also_plans.push_back(q);
+        also_keys.push_back("also:" + ap.cfg + ":" + std::to_string(ap.splits));
+        cs.push_back({also_keys.back().c_str(), [&, q](Buffers& b) { return hgemm_mi355x_launch(q.cfg, q.splits, q.group_m, b.a, b.b, b.bt, b.c, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N, nullptr); }});
+      }
       il_rounds = flops > 1.5e12 ? 3 : std::max(5, (int)std::min(30.0, 20000.0 / std::max(2.0, res[0].us)));
       il_stream_rounds = g_stream_report ? 3 : 0;
       const double box = g_stream_box_s > 0 ? g_stream_box_s : (flops > 1.5e12 ? 0.012 : 0.008);
@@ -653,6 +677,13 @@ static int cmd_tune(const std::vector<Shape>& shapes, const char* out_path, doub
         else if (k == "heur_tn") { lt_tn = iso; st_lt_tn = bx; }
         else if (k == "auto_nn") { at_nn = iso; st_at_nn = bx; }
         else if (k == "auto_tn") { at_tn = iso; st_at_tn = bx; }
+      }
+      for (size_t i = 0; i < also_plans.size(); ++i) {
+        const Contender& c = cs[cs.size() - also_plans.size() + i];
+        char buf[256];
+        snprintf(buf, sizeof buf, "%s{\"config\": \"%s\", \"splits\": %d, \"group_m\": %d, \"us\": %.3f, \"stream_us\": %.3f}", i ? ", " : "",
+                 hgemm_mi355x_config_name(also_plans[i].cfg), also_plans[i].splits, also_plans[i].group_m, c.iso_us(), c.box_us());
+        also_json += buf;
       }
     }
     if (baselines && !interleaved) {
@@ -711,6 +742,7 @@ static int cmd_tune(const std::vector<Shape>& shapes, const char* out_path, doub
     if (nt_iso_us > 0) fprintf(out, ", \"nt_adopted_on\": \"stream\", \"isolated_plain_us\": %.3f, \"isolated_nt_us\": %.3f", nt_plain_iso_us, nt_iso_us);
     if (st_ours > 0)
       fprintf(out, ", \"stream_us\": %.3f, \"hipblaslt_heur_tn_stream_us\": %.3f, \"hipblaslt_heur_nn_stream_us\": %.3f", st_ours, st_lt_tn, st_lt_nn);
+    if (!also_json.empty()) fprintf(out, ", \"also\": [%s]", also_json.c_str());
     fprintf(out, ", \"candidates\": [");
     for (size_t i = 0; i < res.size(); ++i)
     {
@@ -992,6 +1024,14 @@ int main(int argc, char** argv) {
     else if (a == "--stream") g_stream_report = true;
     else if (a == "--interleave") g_interleave = true;
     else if (a == "--reverse") g_reverse = true;
+    else if (a == "--also") {
+      std::stringstream ss(next()); std::string t;
+      while (std::getline(ss, t, ',')) {
+        const size_t x = t.find(':'), y = t.rfind(':');
+        if (x == std::string::npos) g_also.push_back({t, 1, 0});
+        else g_also.push_back({t.substr(0, x), atoi(t.substr(x + 1).c_str()), y != x ? atoi(t.substr(y + 1).c_str()) : 0});
+      }
+    }
     else if (a == "--cand-file") { if (!load_cand_file(next())) { fprintf(stderr, "cannot read --cand-file\n"); return 2; } }
     else if (a == "--configs") { std::stringstream ss(next()); std::string t; while (std::getline(ss, t, ',')) if (!t.empty()) g_config_filter.push_back(t); }
     else if (a == "--plan-only") g_plan_only = true;
@@ -1037,7 +1077,8 @@ int main(int argc, char** argv) {
       // needs more items than resident workgroups: `check --shapes 4352_4352_328 --configs <family q>`, tools/lab/gpu_round4_j.sh)
       shapes = parse_shapes("64_64_64,64_4096_64,128_192_256,200_136_128,256_256_1024,320_448_512,512_1024_2048,1000_520_192,"
                             "1000_520_200,65_30_100,33_17_40,300_260_2048,300_260_2104,520_392_728,"
-                            "96_80_4096");   // (round 6: K / 64 = 64, so that the 37- and 48-way single-launch splits run)
+                            "96_80_4096,"    // (round 6: K / 64 = 64, so that the 37- and 48-way single-launch splits run)
+                            "328_456_384,136_200_896");   // (family u, 128 of K per stage: three and seven stages, ragged M and N)
     return cmd_check(shapes);
   }
   if (mode == "tune") {

@@ -82,6 +82,17 @@ typedef enum { HGEMM_ACC_FP32 = 0, HGEMM_ACC_FP16 = 1 } hgemm_acc_t;
  * waits).  Geometries of the classic ("t") and register-staged ("r") families have the kernel
  * (hgemm_mi355x_config_streamk); elsewhere, or without workspace, the plan runs as the geometry's plain launch. */
 #define HGEMM_PLAN_STREAMK 0x40000
+/* LOCAL split (family "u", names u<BM>x<BN>_w<WM>x<WN>_k4): the one way of putting several wave sets on the K walk of ONE output
+ * tile that does not go through HBM.  The workgroup is WM x WN x 4 waves; a pipeline stage (128 or 256 of K:
+ * hgemm_mi355x_config_k_granularity) is staged into LDS by all sixteen waves, K-group g runs the MFMAs of its quarter of the stage,
+ * and after the walk the four groups' fp32 accumulators are added through LDS in group order 0, 1, 2, 3 (fixed: deterministic per
+ * plan), rounded once to fp16 and stored by all waves.  One launch, no slabs, no counters, no workspace -- so a `splits` = 1 plan of
+ * the family can be captured into a hipGraph without a reserved workspace.  An external `splits` > 1 composes with it (two-pass form:
+ * the slab is written after the LDS reduce); HGEMM_SPLITK_FUSED on such a geometry runs as the two-pass form and HGEMM_PLAN_STREAMK
+ * as its plain launch (it has neither kernel); HGEMM_PLAN_NT_STORE is honoured.  K must be a whole number of stages, any other K is
+ * served by the any-shape kernel (HGEMM_OK, exact).  Explicit plans only: hgemm_mi355x_plan, the off-grid rules and the first-use
+ * candidates never return a family-u geometry.  hgemm_mi355x_config_local_splits tells the factor. */
+
 /* Plan flags of the register-staged streaming family ("r" geometries; ignored elsewhere).  Results are exact either way (0/1
  * inputs) / differ only in the summation order of a tile's K walk (N(0,1) inputs), deterministically per plan.
  * HGEMM_PLAN_RS_XCD_STAGGER: the K stagger of the family (workgroups start their K walk at different stages so that the chip does
@@ -186,13 +197,16 @@ int hgemm_mi355x_config_by_name(const char* name);
  * from fragments loaded straight from global memory (round 4; K must then hold at least one whole stage:
  * hgemm_mi355x_config_accepts_k) -- and the pipeline stage depth for the others (64; the reference pads K in the
  * harness instead, tools/utils.py:8-36).  hgemm_mi355x_launch returns HGEMM_ERR_BAD_ARG for a table geometry when K is a
- * multiple of 64 but not of its stage depth, and serves any other K it cannot take with the any-shape kernel (the planner
- * never picks such a geometry); 1 for the special ids. */
+ * multiple of 64 but not of its stage depth (family u excepted: every K it cannot take goes to the any-shape kernel), and serves
+ * any other K it cannot take with the any-shape kernel (the planner never picks such a geometry); 1 for the special ids. */
 int hgemm_mi355x_config_k_granularity(int config_id);
 /* 1 when hgemm_mi355x_launch runs this geometry's own kernel for a problem with this K (operands aligned), 0 when it
  * would fall back or refuse: K a multiple of the stage depth, or K % 8 == 0 on a geometry with a K tail (families q and
  * r: K >= one stage). */
 int hgemm_mi355x_config_accepts_k(int config_id, int K);
+/* K-groups INSIDE the geometry's workgroup (the local split above): 4 for family u, 1 for every other table geometry, -1 for an
+ * id outside the table. */
+int hgemm_mi355x_config_local_splits(int config_id);
 /* > 0 when the geometry has a stream-K kernel (HGEMM_PLAN_STREAMK): workgroups of it one CU holds. */
 int hgemm_mi355x_config_streamk(int config_id);
 /* 1 when a HGEMM_PLAN_STREAMK plan of this geometry really runs as stream-K on (M, N, K) -- the family has the kernel, K has no
