@@ -1073,12 +1073,16 @@ int main(int argc, char** argv) {
   if (mode == "check") {
     if (shapes.empty())
       // (the last two: K tails -- 2104 = 32 x 64 + 56 = 8 x 256 + 56, 728 = 11 x 64 + 24 = 5 x 128 + 88 = 2 x 256 + 216: odd and even
-      // stage counts, one to seven K = 32 slices of tail, the last one partial.  The tail at the item seams of a persistent walk
-      // needs more items than resident workgroups: `check --shapes 4352_4352_328 --configs <family q>`, tools/lab/gpu_round4_j.sh)
+      // stage counts, one to seven K = 32 slices of tail, the last one partial.  The item seams of a persistent walk need more
+      // items than resident workgroups -- `check --shapes 4352_4352_192,4352_4352_232 --configs <families s, q>`: 289 tiles of
+      // 256 x 256, three K-steps per item, with and without a K tail -- and are left out of this list for their size: the every-run
+      // net is tests/test_gpu_ladders.py (1 ... 5 K-steps per item, items made by tiles and by splits, bit-exact per member).
+      // 1_264_128 / 264_4_128: sliver tiles, one row (whole wave rows out of range) / one 4-column sliver (narrow epilogue))
       shapes = parse_shapes("64_64_64,64_4096_64,128_192_256,200_136_128,256_256_1024,320_448_512,512_1024_2048,1000_520_192,"
                             "1000_520_200,65_30_100,33_17_40,300_260_2048,300_260_2104,520_392_728,"
                             "96_80_4096,"    // (round 6: K / 64 = 64, so that the 37- and 48-way single-launch splits run)
-                            "328_456_384,136_200_896");   // (family u, 128 of K per stage: three and seven stages, ragged M and N)
+                            "328_456_384,136_200_896,"    // (family u, 128 of K per stage: three and seven stages, ragged M and N)
+                            "1_264_128,264_4_128");
     return cmd_check(shapes);
   }
   if (mode == "tune") {

@@ -14,6 +14,8 @@ for p in (str(REPO), str(PKG)):
 
 import bench  # noqa: E402  (bench.load_library: the product's only way in, fails loudly if the .so is missing)
 
+FORMS = ["reference", "ragged", "stream-K", "split-K", "fused", "hybrid", "plain"]   # enum Form of hgemm_api.hip
+
 _lib = None
 
 
@@ -63,3 +65,11 @@ def gemm(a_np: np.ndarray, b_np: np.ndarray, entry: str = "fp32", plan=None, ld=
 def config_names():
     L = lib()
     return [L.hgemm_mi355x_config_name(i).decode() for i in range(L.hgemm_mi355x_num_configs())]
+
+
+def resolve(cfg, splits, m, n, k, lds, group=2):
+    """hgemm_mi355x_launch's decision for a call with b, b_col_major and 16-byte aligned operands, nothing launched
+    (hgemm_mi355x_selfcheck_launch): (status, form, [(thunk, grid, epi, splits, k_chunk, items) per dispatch])."""
+    out = (ctypes.c_longlong * 28)()
+    st = lib().hgemm_mi355x_selfcheck_launch(cfg, splits, group, 7, m, n, k, *lds, 0, out)
+    return st, FORMS[out[0]], [tuple(out[4 + 8 * i:10 + 8 * i]) for i in range(out[1])]

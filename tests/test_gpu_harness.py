@@ -141,9 +141,13 @@ def test_defense_audit_passes_on_the_shipped_op(kernel):
             for _ in range(40):
                 torch.matmul(a, b, out=c)
 
-    big_a = torch.randn((2048, 2048), dtype=torch.half, device="cuda")
-    big_b = torch.randn((2048, 2048), dtype=torch.half, device="cuda")
-    big_c = torch.zeros((2048, 2048), dtype=torch.half, device="cuda")
+    # The hidden work must outlast its own launches, or there is nothing to detect: the audit compares the time the caller's
+    # stream sees (here: the host issuing 40 launches) with the time until the whole device is idle.  40 products of 2048^3 are
+    # ~0.6 ms of MI355X time against 0.2 - 0.8 ms of launches -- under the 1.5x threshold whenever the host was the slower side,
+    # and the test then failed now and then.  4096^3 is eight times the work per launch (~6 ms in all).
+    big_a = torch.randn((4096, 4096), dtype=torch.half, device="cuda")
+    big_b = torch.randn((4096, 4096), dtype=torch.half, device="cuda")
+    big_c = torch.zeros((4096, 4096), dtype=torch.half, device="cuda")
     passed, msg, _ = defense.check_stream_injection(lambda: sneaky(big_a, big_b, None, big_c))
     assert not passed and "Stream injection detected" in msg
 

@@ -11,9 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_common import resolve
+
 pytestmark = pytest.mark.gpu
 
-FORMS = ["reference", "ragged", "stream-K", "split-K", "fused", "hybrid", "plain"]
 RAGGED, GENERIC = -2, -1                        # HGEMM_CONFIG_RAGGED, HGEMM_CONFIG_GENERIC
 FUSED, NT_STORE, STREAMK = 0x10000, 0x20000, 0x40000
 XCD_STAGGER, RS_NT_LOADS = 0x80000, 0x100000
@@ -34,14 +35,6 @@ def oracle():
     from oracle import hgemm_oracle
 
     return hgemm_oracle
-
-
-def resolve(g, cfg, splits, m, n, k, lds, group=2):
-    """hgemm_mi355x_launch's decision for a call with b, b_col_major and 16-byte aligned operands, nothing launched
-    (hgemm_mi355x_selfcheck_launch): (status, form, [(thunk, grid, epi, splits, k_chunk, items) per dispatch])."""
-    out = (ctypes.c_longlong * 28)()
-    st = g.lib().hgemm_mi355x_selfcheck_launch(cfg, splits, group, 7, m, n, k, *lds, 0, out)
-    return st, FORMS[out[0]], [tuple(out[4 + 8 * i:10 + 8 * i]) for i in range(out[1])]
 
 
 def bits(x):
@@ -91,14 +84,14 @@ def test_every_geometry_is_exact_and_stride_blind_at_padded_strides(g, oracle, k
     for cid, name in cases:
         for splits in plan_forms(g, cid, name):
             plan = (cid, splits, 2)
-            base = resolve(g, cid, splits, m, n, k, contiguous)
+            base = resolve(cid, splits, m, n, k, contiguous)
             assert base[0] == 0 and base[1] == {RAGGED: "ragged", GENERIC: "reference"}.get(cid, base[1]), (name, hex(splits), base)
             if cid >= 0:
                 assert base[1] != "ragged", (name, hex(splits), base)
             ref = g.gemm(ar, br, plan=plan)
             for pad in STRIDES:
                 lds = tuple(x + p for x, p in zip(contiguous, pad))
-                got = resolve(g, cid, splits, m, n, k, lds)
+                got = resolve(cid, splits, m, n, k, lds)
                 if pad[0] % 8 and cid != GENERIC:
                     assert got[:2] == (0, "ragged"), (name, hex(splits), lds, got)
                     want = ragged_ref
@@ -120,7 +113,7 @@ def largest_fast_stride(g, cid, m, n, k, side):
     def fast(s):
         lds = [k, k, n]
         lds[side] = s
-        st, form, _ = resolve(g, cid, 1, m, n, k, tuple(lds))
+        st, form, _ = resolve(cid, 1, m, n, k, tuple(lds))
         assert st == 0
         return form != "ragged"
 
@@ -174,7 +167,7 @@ def test_reach_edges_run_exact_on_both_sides(g, oracle, case):
     for stride, form in ((s, "plain"), (s + 8, "ragged")):
         lds = [k, k, n]
         lds[side] = stride
-        assert resolve(g, cid, 1, m, n, k, tuple(lds))[:2] == (0, form), (stride, form)
+        assert resolve(cid, 1, m, n, k, tuple(lds))[:2] == (0, form), (stride, form)
         window = flat.as_strided((rows, cols), (stride, 1))
         c = torch.full((m, n), float("nan"), dtype=torch.half, device="cuda")
         if side == 2:
