@@ -130,20 +130,32 @@ void launch_lu(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingS
     HGEMM_LAUNCH((hgemm_tn_lu_kernel<CFG, EPI_C16>), grid, CFG::THREADS, stream, ts, g);
 }
 
+// A registry row states what the host code needs to know about its kernel: the name is the persisted key of a plan (tuned tables,
+// shape files, hgemm_mi355x_config_by_name) and nothing is derived from it.
+enum class Family : char { T = 't', S = 's', Q = 'q', R = 'r', W = 'w', U = 'u' };
+// A K that is not a multiple of kgran (K % 8 == 0):
+//   NONE    the kernel takes none
+//   PADDED  the classic family zero-fills a partial last LDS-DMA step
+//   DIRECT  families q (MI = 16) and r run their "ktail" variants: whole stages through the pipeline (so K >= kgran), the rest from
+//           fragments loaded straight from global memory (direct_k_tail)
+enum class KTail : char { NONE, PADDED, DIRECT };
+
 struct KernelEntry {
   const char* name;
+  Family family;
   int bm, bn, wm, wn, mi, nbuf;
   int threads, lds_bytes;
   void (*launch)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
   int persistent_wgs;  // > 0: the kernel walks its work items itself, launch at most this many workgroups
   bool has_fused;      // the family has a single-launch split-K epilogue (EPI_FUSED)
   int kgran;           // K granularity of one pipeline stage (64, or 128 / 256 for the deep-stage members): every
-                       // split-K chunk is a multiple, and so is K unless `ktail`
-  bool ktail;          // the kernel takes a K that is not a multiple of kgran (K % 8 == 0): the classic family zero-fills a partial
-                       // last LDS-DMA step; families q (MI = 16) and r run their "ktail" variants: whole stages through the
-                       // pipeline (so K >= kgran), the rest from fragments loaded straight from global memory (direct_k_tail)
+                       // split-K chunk is a multiple, and so is K unless `ktail` says otherwise
+  KTail ktail;
   int sk_wgs_per_cu;   // > 0: the family has a stream-K kernel (EPI_STREAMK); workgroups of it one CU holds (default G = 256 x this)
+  bool explicit_only;  // the planner never returns this member (the MI = 32 members of s and q, family u)
 };
+// a "_k4" member of family w: its four waves share one wave tile and split its K walk
+inline bool w_splits_k(const KernelEntry& e) { return e.family == Family::W && e.wm * e.wn == 1; }
 
 extern const KernelEntry g_kernel_table[];
 extern const int g_num_kernels;

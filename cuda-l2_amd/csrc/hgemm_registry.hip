@@ -7,26 +7,8 @@
 
 namespace hgemm_mi355x {
 
-#define HGEMM_CFG(G, BM, BN, WM, WN, MI, NB) \
-  extern template void launch_cfg<Cfg<BM, BN, WM, WN, MI, NB>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_SP(G, BM, BN, WM, WN, MI) \
-  extern template void launch_sp<CfgSP<BM, BN, WM, WN, MI>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_SQ(G, BM, BN, WM, WN, KT, MI) \
-  extern template void launch_sq<CfgSQ<BM, BN, WM, WN, KT, MI>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_RS(G, BM, BN, BKS, LB) \
-  extern template void launch_rs<CfgRS<BM, BN, BKS, LB>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_WD(G, FM, FN, KW) \
-  extern template void launch_wd<CfgWD<FM, FN, KW>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#include "hgemm_configs.def"
-#undef HGEMM_CFG
-#undef HGEMM_SP
-#undef HGEMM_SQ
-#undef HGEMM_RS
-#undef HGEMM_WD
-#define HGEMM_LU(BM, BN, WM, WN, NIMG, NB) \
-  extern template void launch_lu<CfgLU<BM, BN, WM, WN, NIMG, NB>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#include "hgemm_configs_lu.def"
-#undef HGEMM_LU
+#define HGEMM_THUNK(G, FN, ...) extern template void FN<__VA_ARGS__>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#include "hgemm_thunks.inc"
 
 // The table holds host function pointers: keep it out of the device pass.
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -45,77 +27,75 @@ const char* wd_name() {
   if (!buf[0]) snprintf(buf, sizeof buf, "w%dx%d%s", BM, BN, KW == 4 ? "_k4" : "");
   return buf;
 }
-#define HGEMM_STR2(x) #x
-#define HGEMM_STR(x) HGEMM_STR2(x)
-#define HGEMM_CFG(G, BM, BN, WM, WN, MI, NB)                                                    \
-  {"t" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN) "_m" HGEMM_STR(MI)  \
-   "_s" HGEMM_STR(NB),                                                                         \
-   BM, BN, WM, WN, MI, NB, Cfg<BM, BN, WM, WN, MI, NB>::THREADS,                                \
-   Cfg<BM, BN, WM, WN, MI, NB>::LDS_BYTES, &launch_cfg<Cfg<BM, BN, WM, WN, MI, NB>>, 0, true, 64, true,                      \
-   sk_residency(Cfg<BM, BN, WM, WN, MI, NB>::LDS_BYTES + 64, Cfg<BM, BN, WM, WN, MI, NB>::NW, BM * BN / (64 * Cfg<BM, BN, WM, WN, MI, NB>::NW))},
-#define HGEMM_SP(G, BM, BN, WM, WN, MI)
-#define HGEMM_SQ(G, BM, BN, WM, WN, KT, MI)
-#define HGEMM_RS(G, BM, BN, BKS, LB)
-#define HGEMM_WD(G, FM, FN, KW)
-const KernelEntry g_kernel_table[] = {
-#include "hgemm_configs.def"
-#undef HGEMM_CFG
-#undef HGEMM_SP
-#undef HGEMM_SQ
-#undef HGEMM_RS
-#define HGEMM_RS(G, BM, BN, BKS, LB)
-#define HGEMM_CFG(G, BM, BN, WM, WN, MI, NB)
-// MI = 16 members keep their round-1 names (tuned tables refer to plans by name); MI = 32 members add "_m32"
-#define HGEMM_SP_NAME_16(BM, BN, WM, WN) "s" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN)
-#define HGEMM_SP_NAME_32(BM, BN, WM, WN) "s" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN) "_m32"
-#define HGEMM_SP(G, BM, BN, WM, WN, MI)                                                          \
-  {HGEMM_SP_NAME_##MI(BM, BN, WM, WN), BM, BN, WM, WN, MI, 2,                                      \
-   CfgSP<BM, BN, WM, WN, MI>::THREADS, CfgSP<BM, BN, WM, WN, MI>::LDS_BYTES + 64,                  \
-   &launch_sp<CfgSP<BM, BN, WM, WN, MI>>, 256 * (160 * 1024 / (CfgSP<BM, BN, WM, WN, MI>::LDS_BYTES + 64)), true, 64, false, 0},
-#define HGEMM_SQ_NAME_1_16(BM, BN, WM, WN) "q" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN)
-#define HGEMM_SQ_NAME_2_16(BM, BN, WM, WN) "q" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN) "_k128"
-#define HGEMM_SQ_NAME_1_32(BM, BN, WM, WN) "q" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN) "_m32"
-#define HGEMM_SQ(G, BM, BN, WM, WN, KT, MI)                                                                     \
-  {HGEMM_SQ_NAME_##KT##_##MI(BM, BN, WM, WN), BM, BN, WM, WN, MI, 2, CfgSQ<BM, BN, WM, WN, KT, MI>::THREADS,      \
-   CfgSQ<BM, BN, WM, WN, KT, MI>::LDS_BYTES + (CfgSQ<BM, BN, WM, WN, KT, MI>::WGS == 2 ? 0 : 64), &launch_sq<CfgSQ<BM, BN, WM, WN, KT, MI>>, \
-   256 * CfgSQ<BM, BN, WM, WN, KT, MI>::WGS, true, 64 * KT, MI == 16, 0},
-#include "hgemm_configs.def"
-#undef HGEMM_CFG
-#undef HGEMM_SP
-#undef HGEMM_SQ
-#undef HGEMM_RS
-#define HGEMM_CFG(G, BM, BN, WM, WN, MI, NB)
-#define HGEMM_SP(G, BM, BN, WM, WN, MI)
-#define HGEMM_SQ(G, BM, BN, WM, WN, KT, MI)
-#define HGEMM_RS_SUFFIX_1 ""
-#define HGEMM_RS_SUFFIX_2 "_d"
-#define HGEMM_RS(G, BM, BN, BKS, LB)                                                                                   \
-  {"r" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_k" HGEMM_STR(BKS) HGEMM_RS_SUFFIX_##LB, BM, BN, 2, 2, 16, LB, CfgRS<BM, BN, BKS, LB>::THREADS, \
-   CfgRS<BM, BN, BKS, LB>::LDS_BYTES, &launch_rs<CfgRS<BM, BN, BKS, LB>>, 0, true, BKS, true, CfgRS<BM, BN, BKS, LB>::WGS_PER_CU},
-#include "hgemm_configs.def"
-#undef HGEMM_RS
-#undef HGEMM_WD
-#define HGEMM_RS(G, BM, BN, BKS, LB)
+
+// One row builder per family, C = the member's config type.  Fields in KernelEntry's order: name, family, tile, wave grid, MI, ring
+// depth, threads, LDS bytes, thunk, persistent workgroups, single-launch split-K, K granularity, K-tail rule, stream-K residency,
+// explicit plans only.
+template <class C>
+constexpr KernelEntry row_t(const char* name) {
+  return {name, Family::T, C::BM, C::BN, C::WM, C::WN, C::MI, C::NBUF, C::THREADS, C::LDS_BYTES, &launch_cfg<C>, 0, true, 64, KTail::PADDED,
+          sk_residency(C::LDS_BYTES + 64, C::NW, C::BM * C::BN / (64 * C::NW)), false};
+}
+template <class C>
+constexpr KernelEntry row_s(const char* name) {
+  return {name, Family::S, C::BM, C::BN, C::WM, C::WN, C::MI, 2, C::THREADS, C::LDS_BYTES + 64, &launch_sp<C>,
+          256 * (160 * 1024 / (C::LDS_BYTES + 64)), true, 64, KTail::NONE, 0, C::MI == 32};
+}
+template <class C>
+constexpr KernelEntry row_q(const char* name) {
+  return {name, Family::Q, C::BM, C::BN, C::WM, C::WN, C::MI, 2, C::THREADS, C::LDS_BYTES + (C::WGS == 2 ? 0 : 64), &launch_sq<C>,
+          256 * C::WGS, true, 64 * C::KT, C::MI == 16 ? KTail::DIRECT : KTail::NONE, 0, C::MI == 32};
+}
+template <class C>
+constexpr KernelEntry row_r(const char* name) {
+  return {name, Family::R, C::BM, C::BN, 2, 2, 16, C::LB, C::THREADS, C::LDS_BYTES, &launch_rs<C>, 0, true, C::BKS, KTail::DIRECT,
+          C::WGS_PER_CU, false};
+}
 // family "w": named by its WORKGROUP tile; "_k4" = the four waves split the K walk of one wave tile.  (K granularity 64: a
 // split-K chunk is then a whole number of K = 32 slices whatever the split count.)
-#define HGEMM_WD(G, FM, FN, KW)                                                                                          \
-  {wd_name<CfgWD<FM, FN, KW>::BM, CfgWD<FM, FN, KW>::BN, KW>(), CfgWD<FM, FN, KW>::BM, CfgWD<FM, FN, KW>::BN, CfgWD<FM, FN, KW>::WM, \
-   CfgWD<FM, FN, KW>::WN, 16, 1, CfgWD<FM, FN, KW>::THREADS, CfgWD<FM, FN, KW>::LDS_BYTES, &launch_wd<CfgWD<FM, FN, KW>>, 0, true, 64, false, 0},
-#include "hgemm_configs.def"
+template <class C>
+KernelEntry row_w() {
+  return {wd_name<C::BM, C::BN, C::KW>(), Family::W, C::BM, C::BN, C::WM, C::WN, 16, 1, C::THREADS, C::LDS_BYTES, &launch_wd<C>, 0, true, 64,
+          KTail::NONE, 0, false};
+}
 // family "u" (hgemm_kernel_lu.hpp), behind every other family so that their ids stay put: WM x WN is the wave grid of ONE of the
 // four K-groups ("_k4": threads = WM * WN * 4 * 64); no single-launch split-K, no K tail, no stream-K; K granularity = the stage
-#define HGEMM_LU(BM, BN, WM, WN, NIMG, NB)                                                                        \
-  {"u" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN) "_k4", BM, BN, WM, WN, 16, NB,           \
-   CfgLU<BM, BN, WM, WN, NIMG, NB>::THREADS, CfgLU<BM, BN, WM, WN, NIMG, NB>::LDS_BYTES,                            \
-   &launch_lu<CfgLU<BM, BN, WM, WN, NIMG, NB>>, 0, false, CfgLU<BM, BN, WM, WN, NIMG, NB>::STAGE_K, false, 0},
+template <class C>
+constexpr KernelEntry row_u(const char* name) {
+  return {name, Family::U, C::BM, C::BN, C::WM, C::WN, 16, C::NBUF, C::THREADS, C::LDS_BYTES, &launch_lu<C>, 0, false, C::STAGE_K, KTail::NONE,
+          0, true};
+}
+
+// names are the persisted keys of plans (tuned tables, shape files): literals built from the entry's arguments
+#define HGEMM_STR2(x) #x
+#define HGEMM_STR(x) HGEMM_STR2(x)
+#define HGEMM_TILE_NAME(F, BM, BN, WM, WN) F HGEMM_STR(BM) "x" HGEMM_STR(BN) "_w" HGEMM_STR(WM) "x" HGEMM_STR(WN)
+// MI = 16 members keep their round-1 names (tuned tables refer to plans by name); MI = 32 members add "_m32"
+#define HGEMM_SP_SUFFIX_16 ""
+#define HGEMM_SP_SUFFIX_32 "_m32"
+#define HGEMM_SQ_SUFFIX_1_16 ""
+#define HGEMM_SQ_SUFFIX_2_16 "_k128"
+#define HGEMM_SQ_SUFFIX_1_32 "_m32"
+#define HGEMM_RS_SUFFIX_1 ""
+#define HGEMM_RS_SUFFIX_2 "_d"
+
+// Config ids are positions in this table: every t row, then the s and q rows in list order, then r, w and u
+const KernelEntry g_kernel_table[] = {
+#define HGEMM_CFG(G, BM, BN, WM, WN, MI, NB) \
+  row_t<Cfg<BM, BN, WM, WN, MI, NB>>(HGEMM_TILE_NAME("t", BM, BN, WM, WN) "_m" HGEMM_STR(MI) "_s" HGEMM_STR(NB)),
+#include "hgemm_configs.def"
+#define HGEMM_SP(G, BM, BN, WM, WN, MI) row_s<CfgSP<BM, BN, WM, WN, MI>>(HGEMM_TILE_NAME("s", BM, BN, WM, WN) HGEMM_SP_SUFFIX_##MI),
+#define HGEMM_SQ(G, BM, BN, WM, WN, KT, MI) \
+  row_q<CfgSQ<BM, BN, WM, WN, KT, MI>>(HGEMM_TILE_NAME("q", BM, BN, WM, WN) HGEMM_SQ_SUFFIX_##KT##_##MI),
+#include "hgemm_configs.def"
+#define HGEMM_RS(G, BM, BN, BKS, LB) \
+  row_r<CfgRS<BM, BN, BKS, LB>>("r" HGEMM_STR(BM) "x" HGEMM_STR(BN) "_k" HGEMM_STR(BKS) HGEMM_RS_SUFFIX_##LB),
+#include "hgemm_configs.def"
+#define HGEMM_WD(G, FM, FN, KW) row_w<CfgWD<FM, FN, KW>>(),
+#include "hgemm_configs.def"
+#define HGEMM_LU(BM, BN, WM, WN, NIMG, NB) row_u<CfgLU<BM, BN, WM, WN, NIMG, NB>>(HGEMM_TILE_NAME("u", BM, BN, WM, WN) "_k4"),
 #include "hgemm_configs_lu.def"
-#undef HGEMM_LU
 };
-#undef HGEMM_CFG
-#undef HGEMM_SP
-#undef HGEMM_SQ
-#undef HGEMM_RS
-#undef HGEMM_WD
 const int g_num_kernels = (int)(sizeof(g_kernel_table) / sizeof(g_kernel_table[0]));
 #endif  // !__HIP_DEVICE_COMPILE__
 

@@ -3,7 +3,7 @@
     python tools/eval_planner_loo.py tuning/r02_grid_tune_runA_mi355x.jsonl tuning/r02_grid_tune_runB_mi355x.jsonl ...
 
 Every grid shape is treated as if it were missing from the tuned table and planned (a) by the analytic model among
-all of its measured candidate plans (what hgemm_api.hip model_plan does), (b) from the winning plans of its K nearest
+all of its measured candidate plans (what hgemm_plan.hip model_plan does), (b) from the winning plans of its K nearest
 grid shapes (log2 distance), ranked for this shape by the analytic model's estimate -- what neighbour_plan does with
 the lattice corners around an off-grid shape.  Regret = measured time of the chosen plan / measured time of the
 shape's best plan (geometric mean of the runs that measured it).  A neighbour's plan that was never measured on the

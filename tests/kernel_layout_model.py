@@ -288,7 +288,7 @@ def hybrid_partition(tiles: int, ksteps: int, G: int):
 
 
 def streamk_min_steps(kgran: int) -> int:
-    """hgemm_api.hip: streamk_min_steps -- stages closer than this to a tile boundary are not worth a cut."""
+    """hgemm_plan.hpp: streamk_min_steps -- stages closer than this to a tile boundary are not worth a cut."""
     return 2 if kgran >= 256 else 3 if kgran >= 128 else 4
 
 

@@ -538,7 +538,7 @@ def test_off_grid_rules_of_round_4(lib):
 
 
 def test_k_is_cut_into_splits_that_cover_it_exactly_once(lib):
-    """How hgemm_mi355x_launch cuts K (hgemm_api.hip: split_k; the kernels' side: map_logical / sq_k_items): for every geometry, a
+    """How hgemm_mi355x_launch cuts K (hgemm_plan.hpp: split_k; the kernels' side: map_logical / sq_k_items): for every geometry, a
     sweep of K (tails included) and every requested split count, the splits are non-empty, all but the last are whole stages, the
     last one ends at K, a direct tail (families q and r) sits behind at least one whole stage of the last split and is shorter than
     a stage, and the classic family's partial step is the last step of the last split."""
