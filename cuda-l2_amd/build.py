@@ -26,7 +26,7 @@ CSRC = PKG_DIR / "csrc"
 INCLUDE = REPO_DIR / "include"
 BUILD = PKG_DIR / "build"
 OBJ = BUILD / "obj"
-# experiment builds: HGEMM_LIB_SUFFIX=nt HGEMM_EXTRA_HIPFLAGS="-DHGEMM_DMA_AUX=2" python build.py -> lib_nt/
+# experiment builds: HGEMM_LIB_SUFFIX=slack10 HGEMM_EXTRA_HIPFLAGS="-DHGEMM_SQ_SLACK=10" python build.py -> lib_slack10/
 _SUFFIX = os.environ.get("HGEMM_LIB_SUFFIX", "")
 LIB_DIR = PKG_DIR / ("lib_" + _SUFFIX if _SUFFIX else "lib")
 BIN_DIR = PKG_DIR / "bin"

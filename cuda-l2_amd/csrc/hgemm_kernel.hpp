@@ -52,36 +52,30 @@ constexpr int ARG_PHASE_OFFSET  = 8;    // HGEMM_PLAN_PHASE_OFFSET: family q's p
 constexpr int ARG_WAVE_PRIORITY = 16;   // HGEMM_PLAN_WAVE_PRIORITY: family q's two-resident members
 constexpr int ARG_PHASE_OFFSET4 = 32;   // HGEMM_PLAN_PHASE_OFFSET4: four phase groups instead of two (both bits: eight)
 
-// cache-policy bits of the LDS-DMA loads (buffer_load ... lds aux operand: 1 = sc0, 2 = nt, 16 = sc1).
-// 0 = default policy; other values are build-time experiments (build.py HGEMM_EXTRA_HIPFLAGS).
-// C stores: each C element is written once and never re-read by the kernel.  HGEMM_NT_STORE=1 marks the
-// fp16 output stores non-temporal (streaming), so they do not displace the A/B panels from L2.
-#ifndef HGEMM_NT_STORE
-#define HGEMM_NT_STORE 0
-#endif
-// (HGEMM_NT_STORE=1 forces them for every plan: experiment builds.  Shipping builds take the plan's HGEMM_PLAN_NT_STORE bit,
-// GemmArgs::flags ARG_NT_STORE -- a wave-uniform branch around the store.)
-#if HGEMM_NT_STORE
-#define HGEMM_STORE_C(g, ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define HGEMM_STORE_C(g, ptr, val) \
-  do { if ((g).flags & ARG_NT_STORE) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
+// Build-time switches retired with the experiments they selected: each either forced on what is a plan flag now (ARG_* above),
+// or guarded the "off" path of something every measured library has had on.  A stale -D must not silently measure the shipping
+// kernel (extra compiler flags reach a build through the environment), so naming one of them stops the build.
+#if defined(HGEMM_SQ_SPREAD) || defined(HGEMM_SQ_GAPS) || defined(HGEMM_SQ_QORDER) || defined(HGEMM_NT_STORE) || \
+    defined(HGEMM_DMA_AUX) || defined(HGEMM_FASTDIV) || defined(HGEMM_KERNARG_PREFETCH) || defined(HGEMM_EPI_STAGED) || \
+    defined(HGEMM_RS_NT) || defined(HGEMM_RS_STAGGER) || defined(HGEMM_RS_STAGGER_MODE)
+#error "retired build switch defined (DESIGN.md section 4.7), one of: HGEMM_SQ_SPREAD, HGEMM_SQ_GAPS, HGEMM_SQ_QORDER, " \
+       "HGEMM_NT_STORE, HGEMM_DMA_AUX, HGEMM_FASTDIV, HGEMM_KERNARG_PREFETCH, HGEMM_EPI_STAGED, HGEMM_RS_NT, HGEMM_RS_STAGGER, " \
+       "HGEMM_RS_STAGGER_MODE"
 #endif
 
-#ifndef HGEMM_DMA_AUX
-#define HGEMM_DMA_AUX 0
-#endif
+// C stores: each C element is written once and never re-read by the kernel.  A plan with HGEMM_PLAN_NT_STORE (GemmArgs::flags
+// ARG_NT_STORE -- a wave-uniform branch around the store) marks the fp16 output stores non-temporal (streaming), so they do
+// not displace the A/B panels from L2.
+#define HGEMM_STORE_C(g, ptr, val) \
+  do { if ((g).flags & ARG_NT_STORE) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
 // ---- exact unsigned division by a launch constant (Granlund-Montgomery, 32-bit): the raster map below divides a
 // work-item id by three launch constants; a hardware-less integer division is ~40 instructions with a v_rcp in its
 // dependency chain, five of them are most of a kernel's prologue and ~700 cycles per work item of a persistent
-// kernel.  With HGEMM_FASTDIV the host passes multipliers (GemmArgs::rd) and a division is s_mul_hi + 4 ALU ops.
+// kernel.  The host passes multipliers instead (GemmArgs::rd) and a division is s_mul_hi + 4 ALU ops.
 // tests/test_host_logic.py compares raster_fast with raster_ref on the host for every id of many launch shapes.
-#ifndef HGEMM_FASTDIV
-#define HGEMM_FASTDIV 1
-#endif
 struct FastDiv { uint32_t mul, sh1, sh2; };   // n / d = (t + ((n - t) >> sh1)) >> sh2,  t = mulhi(n, mul)
 __host__ __device__ __forceinline__ uint32_t fast_div(uint32_t n, const FastDiv& f) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -207,9 +201,7 @@ struct GemmArgs {
   // by the last arriver) and compact per-item slabs partial[item][BM*BN] in the kernel's own lane order.
   unsigned* counters;
   int flags;       // ARG_* bits (above)
-#if HGEMM_FASTDIV
   RasterDiv rd;    // multipliers for the raster map's divisions (set_raster_div on the host, after the fields above are final)
-#endif
   StreamK sk;      // stream-K launches (EPI_STREAMK) only: the partition of the tile-major K-stage sequence (appended: the
                    // kernarg offsets of every field above are what the round-3 kernels were validated with)
 #ifdef HGEMM_ABLATION
@@ -252,11 +244,7 @@ __device__ __forceinline__ unsigned long long hgemm_tl_get(const char* slots, in
 #define HGEMM_TL_REALTIME(slots, slot, tid) ((void)0)
 #endif
 inline void set_raster_div(GemmArgs& g) {   // host: after tiles_m / tiles_n / group_m / tail_tiles are final
-#if HGEMM_FASTDIV
   g.rd = make_raster_div(g.tiles_m, g.tiles_n, g.group_m, g.tail_tiles);
-#else
-  (void)g;
-#endif
 }
 
 // Kernel-argument prefetch.  GemmArgs is passed by value: the kernel reads it from the launch's kernarg buffer with scalar
@@ -265,12 +253,9 @@ inline void set_raster_div(GemmArgs& g) {   // host: after tiles_m / tiles_n / g
 // pass between kernel entry and the first LDS-DMA piece with or without the multiplier raster map, i.e. the arithmetic is
 // not what takes the time.  One dword of every line is requested at entry instead, all at once (ONE round trip): the
 // compiler's own loads then hit the scalar cache.  (By-value structs cannot use the CP's kernarg preload.)
-#ifndef HGEMM_KERNARG_PREFETCH
-#define HGEMM_KERNARG_PREFETCH 1
-#endif
 template <int BYTES>
 __device__ __forceinline__ void prefetch_kernargs() {
-#if defined(__HIP_DEVICE_COMPILE__) && HGEMM_KERNARG_PREFETCH
+#if defined(__HIP_DEVICE_COMPILE__)
   // one statement: the loads AND their wait (a scalar load writes its destination when it returns; the compiler would
   // consider an unused destination free again right behind the statement and the late write would corrupt its new value)
   const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -352,7 +337,6 @@ struct TileCoord {
 
 // logical work-item id (after the XCD remap) -> (split, tile origin, K range), grouped raster
 __device__ __forceinline__ TileCoord map_logical(const GemmArgs& g, int bid, int BM, int BN) {
-#if HGEMM_FASTDIV
   const RasterPos rp = raster_fast(bid, g.tiles_m, g.tiles_n, g.group_m, g.tail_first, g.tail_tiles, g.rd);
   const int split = rp.split;
   TileCoord tc;
@@ -361,28 +345,6 @@ __device__ __forceinline__ TileCoord map_logical(const GemmArgs& g, int bid, int
   tc.item = bid;
   tc.m0 = rp.tile_m * BM;
   tc.n0 = rp.tile_n * BN;
-#else   // (the same map as raster_ref, kept in this form: the shipped binaries were validated with it)
-  const int tiles = g.tiles_m * g.tiles_n;
-  int split, t_id;
-  if (g.tail_tiles > 0) {
-    split = bid / g.tail_tiles;
-    t_id  = g.tail_first + (bid - split * g.tail_tiles);
-  } else {
-    split = bid / tiles;
-    t_id  = bid - split * tiles;
-  }
-  const int gsz   = g.group_m * g.tiles_n;
-  const int grp   = t_id / gsz;
-  const int first_m = grp * g.group_m;
-  const int gm    = min(g.tiles_m - first_m, g.group_m);
-  const int tin   = t_id - grp * gsz;
-  TileCoord tc;
-  tc.split = split;
-  tc.tile = t_id;
-  tc.item = bid;
-  tc.m0 = (first_m + tin % gm) * BM;
-  tc.n0 = (tin / gm) * BN;
-#endif
   tc.k_begin = split * g.k_chunk;
   tc.nk = (min(g.K, tc.k_begin + g.k_chunk) - tc.k_begin + BK - 1) / BK;   // the last K-step may be partial (classic family)
   if (HGEMM_DBG(g, 4)) tc.nk = min(tc.nk, 2);
@@ -609,6 +571,7 @@ struct FusedBatch { static constexpr int U = NQ <= 1 ? 32 : NQ <= 2 ? 16 : NQ <=
 // kernel stubs, so device bodies are compiled under __HIP_DEVICE_COMPILE__ only.
 #if defined(__HIP_DEVICE_COMPILE__)
 // Issue the LDS-DMA pieces of one K-step (tile rows x 128 B) owned by this wave.
+// (the last operand of an LDS-DMA load: its cache-policy bits, 1 = sc0, 2 = nt, 16 = sc1; 0 = default policy, here and in every family)
 template <class CFG>
 __device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB,
                                            const uint32_t (&voff)[CFG::NJ], char* lds_stage,
@@ -619,9 +582,9 @@ __device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rsA, __amdgpu_
     if (CFG::NI % CFG::NW == 0 || i < CFG::NI) {
       lds_void_t* dst = (lds_void_t*)(lds_stage + i * 1024);
       if (i < CFG::NI_A)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, voff[j], kbyte, 0, HGEMM_DMA_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, voff[j], kbyte, 0, 0);
       else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, voff[j], kbyte, 0, HGEMM_DMA_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, voff[j], kbyte, 0, 0);
     }
   }
 }
@@ -641,9 +604,9 @@ __device__ __forceinline__ void stage_tile_tail(__amdgpu_buffer_rsrc_t rsA, __am
       lds_void_t* dst = (lds_void_t*)(lds_stage + i * 1024);
       const uint32_t vo = voff[j] | (((tailmask >> j) & 1u) << 31);
       if (i < CFG::NI_A)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, vo, kbyte, 0, HGEMM_DMA_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, vo, kbyte, 0, 0);
       else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, vo, kbyte, 0, HGEMM_DMA_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, vo, kbyte, 0, 0);
     }
   }
 }
@@ -912,11 +875,7 @@ __device__ __forceinline__ SkSegment sk_segment(const GemmArgs& g, int w, int ru
   s.k1 = min(g.sk.steps, s.k0 + (run_end - x));
   s.whole = s.k0 == 0 && s.k1 == g.sk.steps;
   s.slab = 2 * w + (x == run_begin ? 0 : 1);
-#if HGEMM_FASTDIV
   const RasterPos rp = raster_fast(s.tile, g.tiles_m, g.tiles_n, g.group_m, 0, 0, g.rd);
-#else
-  const RasterPos rp = raster_ref(s.tile, g.tiles_m, g.tiles_n, g.group_m, 0, 0);
-#endif
   s.m0 = rp.tile_m * BM;
   s.n0 = rp.tile_n * BN;
   return s;

@@ -115,9 +115,9 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_lu_kernel(const GemmArg
       const int p = wave + j * NW;
       lds_void_t* dst = (lds_void_t*)(lds_stage + p * 1024);   // image-major, rows in piece order: p * 1 KiB
       if (p % CFG::PPI < CFG::NI_A)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, voff[j], kbyte, 0, HGEMM_DMA_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, voff[j], kbyte, 0, 0);
       else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, voff[j], kbyte, 0, HGEMM_DMA_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, voff[j], kbyte, 0, 0);
     }
   };
 
@@ -219,8 +219,8 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_lu_kernel(const GemmArg
           // hint are merged by the optimiser and the hint is lost); the tile's bytes are below 2 GiB from its first row (host check)
           const f16x4 o = {(f16)s[0], (f16)s[1], (f16)s[2], (f16)s[3]};
           const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
-          if (HGEMM_NT_STORE || (g.flags & ARG_NT_STORE)) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsC, off, 0, 2);
-          else                                            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsC, off, 0, 0);
+          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsC, off, 0, 2);
+          else                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), rsC, off, 0, 0);
         }
       }
     }

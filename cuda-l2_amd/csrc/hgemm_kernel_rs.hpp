@@ -92,22 +92,13 @@ __device__ __forceinline__ void classic_epilogue(const GemmArgs& g, const TileCo
 #endif
 }
 
-// cache policy of the operand loads (experiment knob HGEMM_RS_NT: 0 = default, 1 = the STREAMED operand -- the one
-// with more rows, read exactly once -- is loaded non-temporally, 2 = both)
-#ifndef HGEMM_RS_NT
-#define HGEMM_RS_NT 0
-#endif
-// K stagger (Tensile's StaggerU): workgroup w starts its K walk at stage (w * HGEMM_RS_STAGGER) mod nk and wraps
+// K stagger (Tensile's StaggerU): workgroup w starts its K walk at stage (w * kRsStagger) mod nk and wraps
 // around, so the workgroups of a launch do not all read the same K offset of their rows at the same time (row
 // stride = K * 2 B is a large power of two on the grid shapes: identical low address bits = the same few HBM
 // channels; measured: 16384 x 64 x 16384 115 -> 96 us).  The summation order of a tile changes with its
-// coordinates, deterministically.
-#ifndef HGEMM_RS_STAGGER
-#define HGEMM_RS_STAGGER 3
-#endif
-#ifndef HGEMM_RS_STAGGER_MODE
-#define HGEMM_RS_STAGGER_MODE 0   // 0: per work item; 1: per XCD (blockIdx % 8): an XCD's workgroups stay in lock-step; 2: item % 8
-#endif
+// coordinates, deterministically.  (Plan flag ARG_XCD_STAGGER: per XCD, blockIdx % 8, instead -- an XCD's workgroups stay in
+// lock-step.)
+constexpr int kRsStagger = 3;
 
 // Family r's main loop for ONE work item: tile (m0, n0), nk stages of BKS halfs from K offset k_begin, accumulators cleared
 // here; `tile_id` seeds the K stagger (built from the item's COORDINATES, not from its raster position: the summation order
@@ -152,13 +143,14 @@ __device__ __forceinline__ void rs_mainloop(const GemmArgs& g, int m0, int n0, i
 
   f16x8 ra0[CA], rb0[CB], ra1[CA], rb1[CB];      // two stages in flight
   constexpr int kAuxNt = 2;   // buffer aux operand: bit 1 = nt
-  // (plan flags ARG_NT_LOADS / ARG_XCD_STAGGER: wave-uniform; the build-time knobs force them for experiment builds)
-  const bool nt_streamed = HGEMM_RS_NT == 1 || (g.flags & ARG_NT_LOADS) != 0;
-  const bool nt_a = HGEMM_RS_NT == 2 || (nt_streamed && g.M >= g.N);
-  const bool nt_b = HGEMM_RS_NT == 2 || (nt_streamed && g.M < g.N);
-  const unsigned stg_id = (HGEMM_RS_STAGGER_MODE == 1 || (g.flags & ARG_XCD_STAGGER) != 0) ? (blockIdx.x % NUM_XCD) * (unsigned)max(1, nk / NUM_XCD)
-                        : HGEMM_RS_STAGGER_MODE == 2 ? (tile_id % 8u) * (unsigned)max(1, nk / 8) : tile_id * (unsigned)HGEMM_RS_STAGGER;
-  const int stage0 = HGEMM_RS_STAGGER ? (int)(stg_id % (unsigned)nk) : 0;
+  // (plan flags ARG_NT_LOADS / ARG_XCD_STAGGER: wave-uniform.  ARG_NT_LOADS: the STREAMED operand -- the one with more rows,
+  // read exactly once -- is loaded non-temporally)
+  const bool nt_streamed = (g.flags & ARG_NT_LOADS) != 0;
+  const bool nt_a = nt_streamed && g.M >= g.N;
+  const bool nt_b = nt_streamed && g.M < g.N;
+  const unsigned stg_id = (g.flags & ARG_XCD_STAGGER) != 0 ? (blockIdx.x % NUM_XCD) * (unsigned)max(1, nk / NUM_XCD)
+                                                           : tile_id * (unsigned)kRsStagger;
+  const int stage0 = (int)(stg_id % (unsigned)nk);
 #define RS_STAGE(T) ((stage0 + (T)) >= nk ? (stage0 + (T)) - nk : (stage0 + (T)))
 #define RS_LD1(RS, VOFF, SOFF, NT) \
   __builtin_bit_cast(f16x8, (NT) ? __builtin_amdgcn_raw_buffer_load_b128(RS, VOFF, SOFF, kAuxNt) : __builtin_amdgcn_raw_buffer_load_b128(RS, VOFF, SOFF, 0))

@@ -153,7 +153,7 @@ template <class CFG>
 __device__ __forceinline__ void sp_issue_piece(__amdgpu_buffer_rsrc_t rs, const uint32_t (&voff)[CFG::NJ], char* lds_stage,
                                                int wave, int p, uint32_t kbyte) {
   lds_void_t* dst = (lds_void_t*)(lds_stage + (wave + p * CFG::NW) * 1024);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff[p], kbyte, 0, HGEMM_DMA_AUX);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff[p], kbyte, 0, 0);   // (cache-policy bits: default)
 }
 
 __device__ __forceinline__ void sp_sync() {
@@ -333,14 +333,11 @@ __device__ __forceinline__ void sp_store_tile32(const GemmArgs& g, int m, int nb
 // number of store instructions, half the lines per instruction, no lane swaps.  Two 2 KiB buffers per wave alternate; DS
 // instructions of one wave execute in order, so the only wait is for the read-back data.  The region is wave-private: no
 // barrier, and the next work item's LDS-DMA stream (other regions) keeps flowing underneath.
-#ifndef HGEMM_EPI_STAGED
-#define HGEMM_EPI_STAGED 1
-#endif
 constexpr int SP_STAGED_BYTES_PER_WAVE = 4096;
 // (only where the extra 16 KiB do not cost a resident workgroup: the host launches 256 x (160 KiB / (stages + 64 B)) of them)
 template <class CFG>
 constexpr bool sp_staged_ok(int lds_bytes) {
-  return HGEMM_EPI_STAGED && CFG::MI == 16 && CFG::FN % 4 == 0 &&
+  return CFG::MI == 16 && CFG::FN % 4 == 0 &&
          (160 * 1024) / (lds_bytes + 64 + CFG::NW * SP_STAGED_BYTES_PER_WAVE) == (160 * 1024) / (lds_bytes + 64) &&
          (160 * 1024) / (lds_bytes + 64) >= 1;
 }
@@ -413,8 +410,8 @@ __device__ __forceinline__ void sp_epilogue_staged(const GemmArgs& g, int m_wave
     if (HGEMM_DBG(g, 2)) return;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      if (HGEMM_NT_STORE || nt) __builtin_amdgcn_raw_buffer_store_b128(rb[b][h], rsC, voff[gg], (unsigned)(i * 2 + h) * row8, 2);
-      else                      __builtin_amdgcn_raw_buffer_store_b128(rb[b][h], rsC, voff[gg], (unsigned)(i * 2 + h) * row8, 0);
+      if (nt) __builtin_amdgcn_raw_buffer_store_b128(rb[b][h], rsC, voff[gg], (unsigned)(i * 2 + h) * row8, 2);
+      else    __builtin_amdgcn_raw_buffer_store_b128(rb[b][h], rsC, voff[gg], (unsigned)(i * 2 + h) * row8, 0);
     }
   };
   write_group(0);

@@ -48,32 +48,6 @@
 // source in round 4: no switch of this header selects a kernel that has not passed `hgemm_tune check`.  The stagger that the
 // lock-step one-tile-per-CU plans lack comes from the plans themselves now: split-K / stream-K parts of a tile start their K
 // walks at different offsets.)
-#ifndef HGEMM_SQ_QORDER
-#define HGEMM_SQ_QORDER 0     // behind Q: 0 = B-fragment reads lead the A pieces, 1 = the pieces lead
-#endif
-#ifndef HGEMM_SQ_SPREAD
-#define HGEMM_SQ_SPREAD 1     // 1: the LDS-DMA pieces of a half-tile are spread over a whole interval's worth of slots: the
-                              // first D of them go out behind the sync point that frees their region (as before), the last
-                              // E = NJ - D in the pre-sync window of the NEXT interval, between its leading fragment reads.
-                              // 0: round-2 plan (all pieces in the ~2/3 of an interval behind the sync point, one every 4 slots
-                              // from each of the four waves at once).  Why: round-3 timeline ablation -- the pieces cost 180 of
-                              // the 214 cycles a K-step spends beyond its 2048 MFMA cycles (tools/lab/gpu_round3_a.sh):
-                              // the CU's one address path takes ~20 cycles per piece, four waves x one piece per 64 cycles
-                              // saturates it behind every sync point while it idles in front of the next one.
-#endif
-#ifndef HGEMM_SQ_GAPS
-#define HGEMM_SQ_GAPS 1       // spread plan only.  One wave per SIMD: whatever sits between two MFMAs shares the 16 cycles of the
-                              // first one (about four issue slots, a VMEM or DS instruction takes two).  Round-3 timeline
-                              // ablation: the K-step costs 2284 cycles against 2070 for the bare MFMA stream, 180 of the
-                              // difference vanish with the LDS-DMA pieces although spreading them changes nothing -- what costs
-                              // is the gap that holds buffer_load + s_add m0 + s_add soffset, the one with ds_read between two
-                              // compiler-placed s_waitcnt, and the sync point's seven instructions.  1: (a) a piece is TWO asm
-                              // statements in two different gaps (s_add m0 one gap ahead of the buffer_load; per-piece lane
-                              // offsets instead of scalar ones, so no third instruction); (b) one lgkmcnt(0) the compiler can
-                              // see (builtin) near the end of every interval, after which it places no waits of its own in
-                              // front of the next interval's MFMAs; (c) the sync point's vmcnt wait sits one gap ahead of the
-                              // lgkmcnt wait + barrier.  The vendor kernel's loop has the same one-instruction-per-gap shape.
-#endif
 #ifndef HGEMM_SQ_ABL
 #define HGEMM_SQ_ABL 0        // measurement builds only (results are garbage): drop parts of the K loop to price them with the
                               // timeline stamps: 1 no s_barrier, 2 no vmcnt wait, 4 no lgkmcnt(0) at the sync points,
@@ -110,18 +84,14 @@ struct CfgSQ : Cfg<BM_, BN_, WM_, WN_, MI_, 2> {
   static constexpr int SLACK = (MI_ == 32) ? HGEMM_SQ_SLACK32 : (T >= 64) ? HGEMM_SQ_SLACK : (T >= 32 ? 6 : 2);
   static constexpr int P   = RS * NFB + SLACK;             // slot of interval A that carries sync P
   static constexpr int Q   = RS * NFA + SLACK;             // slot of interval B that carries sync Q
-  // behind a sync point a DMA piece and a fragment read alternate, one item every ST slots
-  static constexpr int STA = (T - P - 1) / (NJB + NFA) >= 2 ? 2 : 1;
-  static constexpr int STB = (T - Q - 1) / (NJA + NFB) >= 2 ? 2 : 1;
-  // spread plan: late pieces per operand (issued in the pre-sync window of the following interval: A's in interval A,
-  // in front of P; B's in interval B, in front of Q) in proportion to that window's share of the interval
-  static constexpr int EA = !HGEMM_SQ_SPREAD ? 0 : ((NJA * P + T / 2) / T < NJA ? (NJA * P + T / 2) / T : NJA - 1);
-  static constexpr int EB = !HGEMM_SQ_SPREAD ? 0 : ((NJB * Q + T / 2) / T < NJB ? (NJB * Q + T / 2) / T : NJB - 1);
+  // late pieces per operand (issued in the pre-sync window of the following interval: A's in interval A, in front of P;
+  // B's in interval B, in front of Q) in proportion to that window's share of the interval (SqPlan)
+  static constexpr int EA = (NJA * P + T / 2) / T < NJA ? (NJA * P + T / 2) / T : NJA - 1;
+  static constexpr int EB = (NJB * Q + T / 2) / T < NJB ? (NJB * Q + T / 2) / T : NJB - 1;
   static constexpr int DA = NJA - EA, DB = NJB - EB;       // early pieces (behind the sync point that frees the region)
   static_assert(KT == 1 || KT == 2, "one or two BK=64 sub-tiles per stage");
   static_assert(MI_ == 16 || (MI_ == 32 && KT == 1), "the 32x32x16 members hold K = 64 per stage");
   static_assert(Base::NI % Base::NW == 0 && Base::NI_A % Base::NW == 0, "every wave owns whole A and B pieces");
-  static_assert(P + 1 + STA * (NJB + NFA) <= T && Q + 1 + STB * (NJA + NFB) <= T, "slot plan does not fit the interval");
   static_assert(Base::FM * Base::FN * ACC <= 256, "accumulators live in a0..a255");
   static_assert(LDS_BYTES + 64 <= 160 * 1024, "LDS budget");
   // AGPRs the kernel descriptor reserves: all 256 (one wave per SIMD owns the file), or exactly the accumulators when the LDS
@@ -136,35 +106,19 @@ struct CfgSQ : Cfg<BM_, BN_, WM_, WN_, MI_, 2> {
 };
 
 #if defined(__HIP_DEVICE_COMPILE__)
-// after sync P (interval A): item 2i = B piece i, item 2i+1 = A-fragment read i (pieces first: they need the flight time)
-// after sync Q (interval B): item 2i = B-fragment read i (needed at the top of the next interval), item 2i+1 = A piece i
+// The slot plan of an interval: which MFMA slot carries which LDS-DMA piece and which trailing fragment read.
+// PH = 0 interval A (sync slot P), 1 interval B (sync slot Q).
+// The LDS-DMA pieces of a half-tile are SPREAD over a whole interval's worth of slots: the first D of them ("early") go out
+// behind the sync point that frees their region, the last E = NJ - D ("late") in the pre-sync window of the NEXT interval,
+// between its leading fragment reads.  Why: round-3 timeline ablation -- the pieces cost 180 of the 214 cycles a K-step spends
+// beyond its 2048 MFMA cycles (tools/lab/gpu_round3_a.sh): the CU's one address path takes ~20 cycles
+// per piece; the round-2 plan put all pieces into the ~2/3 of an interval behind the sync point, one every 4 slots from each
+// of the four waves at once, which saturates that path behind every sync point while it idles in front of the next one.
+// (The round-2 plan, and the spread plan without the one-instruction-per-gap form of sq_interval, were build-time switches of
+// this header; they last existed in commit 23b0e889)
 template <class CFG>
 struct SqPlan {
   static constexpr int FM = CFG::NFA, FN = CFG::NFB, T = CFG::T;   // fragment reads per operand, MFMA slots
-  // interval A
-  static constexpr int a_piece_at(int n) {   // B piece index issued behind slot n of interval A, or -1
-    for (int i = 0; i < CFG::NJB; ++i) if (CFG::P + 1 + CFG::STA * a_item_of_piece(i) == n) return i;
-    return -1;
-  }
-  static constexpr int a_read_at(int n) {    // A-fragment (slice 1, next tile) read index behind slot n, or -1
-    for (int i = 0; i < FM; ++i) if (CFG::P + 1 + CFG::STA * a_item_of_read(i) == n) return i;
-    return -1;
-  }
-  // interleave two lists of possibly different length: alternate while both last, then the rest
-  static constexpr int a_item_of_piece(int i) { return i < FM ? 2 * i : FM + i; }
-  static constexpr int a_item_of_read(int i) { return i < CFG::NJB ? 2 * i + 1 : CFG::NJB + i; }
-  // interval B
-  static constexpr int b_item_of_read(int i) { return i < CFG::NJA ? 2 * i + HGEMM_SQ_QORDER : CFG::NJA + i; }
-  static constexpr int b_item_of_piece(int i) { return i < FN ? 2 * i + 1 - HGEMM_SQ_QORDER : FN + i; }
-  static constexpr int b_read_at(int n) {
-    for (int i = 0; i < FN; ++i) if (CFG::Q + 1 + CFG::STB * b_item_of_read(i) == n) return i;
-    return -1;
-  }
-  static constexpr int b_piece_at(int n) {
-    for (int i = 0; i < CFG::NJA; ++i) if (CFG::Q + 1 + CFG::STB * b_item_of_piece(i) == n) return i;
-    return -1;
-  }
-  // ---- spread plan (HGEMM_SQ_SPREAD): PH = 0 interval A (sync slot P), 1 interval B (sync slot Q) -------------------
   // late piece k of E, in front of sync slot S: centred in its 1/E share of [0, S), on an odd slot when the leading reads
   // sit on the even ones
   // (one-instruction-per-gap form: M0 is written one slot ahead, so slot 0 is out; the vmcnt wait of the sync point sits
@@ -212,10 +166,10 @@ struct SqPlan {
     }
     return trail_slot(n_trail<PH>() - 1, n_trail<PH>(), S) < T;
   }
-  static_assert(!HGEMM_SQ_SPREAD || (slots_ok<0>() && slots_ok<1>()), "spread slot plan does not fit the interval");
+  static_assert(slots_ok<0>() && slots_ok<1>(), "slot plan does not fit the interval");
 };
 
-// The spread plan of one interval as tables indexed by the slot (the K loop's body is unrolled over the slots: a table
+// The plan of one interval as tables indexed by the slot (the K loop's body is unrolled over the slots: a table
 // look-up with a constant index folds, the search loops of SqPlan::*_at would each be unrolled T times first and blow
 // the unroller's size budget).  -1 = nothing in this slot.
 template <class CFG, int PH>
@@ -246,10 +200,10 @@ __device__ __forceinline__ void sq_issue_piece(__amdgpu_buffer_rsrc_t rs, const 
   lds_void_t* dst = (lds_void_t*)(stage + sub * CFG::SUB_BYTES + (wave + p * CFG::NW) * 1024);
   // (the sub-tile's 128 B go into the scalar offset: the instruction's immediate offset would also be added to
   // the LDS address of an LDS-DMA)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff[q], kbyte + sub * ROW_BYTES, 0, HGEMM_DMA_AUX);
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff[q], kbyte + sub * ROW_BYTES, 0, 0);   // (cache-policy bits: default)
 }
 
-// HGEMM_SQ_GAPS form of a piece: the LDS destination goes into M0 in one gap, the load is issued in the next.  M0 is
+// The K loop's form of a piece (sq_interval): the LDS destination goes into M0 in one gap, the load is issued in the next.  M0 is
 // the compiler's register; it has no use for it inside the K loops once every LDS-DMA there is one of these pairs (the
 // builtin form, which sets M0 itself, is only used outside them), and tests/test_build_audit.py checks on the ISA that
 // M0 writes and LDS-DMA loads strictly alternate in every MFMA loop.  An MFMA always sits between the two statements, which
@@ -278,7 +232,6 @@ __device__ __forceinline__ void sq_piece_load(__amdgpu_buffer_rsrc_t rs, const u
                                               uint32_t kbyte) {
   constexpr int POP = OP == 0 ? CFG::PA : CFG::PB;
   const int sub = idx / POP, q = idx % POP;
-  static_assert(HGEMM_DMA_AUX == 0, "cache-policy experiments use the builtin form");
   asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff[q]), "s"(rs), "s"(kbyte + sub * ROW_BYTES) : "memory");
 }
 // every register of the three fragment sets the next MFMAs read is an operand of one asm statement: whatever copies the
@@ -297,9 +250,18 @@ constexpr int kWaitLgkm0 = 0xC07F;   // s_waitcnt lgkmcnt(0) as the builtin's im
 // behind P: B pieces of tile t+2 and trailing reads -> trail (A fragments of the second half of tile t+1).
 // PHASE 1 = B(t): leading reads -> lead (A fragments of the first half of tile t+1); behind Q: trailing reads ->
 // trail (B fragments of the first half of tile t+1) and A pieces of tile t+3.
-// Spread plan: the pieces behind the sync point are the FIRST D of the half-tile ("early", descriptor / cursor rs_e,
-// kbyte_e, stage_e); in front of it go the LAST E pieces of the half-tile whose region the previous sync point freed
-// ("late": interval A: A pieces of tile t+2 into A[s]; interval B: B pieces of tile t+2 into B[s]; rs_l, kbyte_l, stage_l).
+// The pieces behind the sync point are the FIRST D of the half-tile ("early", descriptor / cursor rs_e, kbyte_e, stage_e);
+// in front of it go the LAST E pieces of the half-tile whose region the previous sync point freed ("late": interval A: A
+// pieces of tile t+2 into A[s]; interval B: B pieces of tile t+2 into B[s]; rs_l, kbyte_l, stage_l).
+// One instruction per gap.  One wave per SIMD: whatever sits between two MFMAs shares the 16 cycles of the first one (about
+// four issue slots, a VMEM or DS instruction takes two).  Round-3 timeline ablation: the K-step costs 2284 cycles against 2070
+// for the bare MFMA stream, 180 of the difference vanish with the LDS-DMA pieces although spreading them alone changes nothing
+// -- what costs is the gap that holds buffer_load + s_add m0 + s_add soffset, the one with ds_read between two compiler-placed
+// s_waitcnt, and the sync point's seven instructions.  So (a) a piece is TWO asm statements in two different gaps (the M0 write
+// one gap ahead of the buffer_load; per-piece lane offsets instead of scalar ones, so no third instruction); (b) one
+// lgkmcnt(0) the compiler can see (builtin) near the end of every interval, after which it places no waits of its own in
+// front of the next interval's MFMAs; (c) the sync point's vmcnt wait sits one gap ahead of the lgkmcnt wait + barrier.  The
+// vendor kernel's loop has the same one-instruction-per-gap shape.
 // Fragment read r of a set: slice r / F reads from src0 / src1, row block r % F.
 template <class CFG, int PHASE>
 __device__ __forceinline__ void sq_interval(const f16x8 (&af)[CFG::NFA], const f16x8 (&bf)[CFG::NFB],
@@ -308,29 +270,21 @@ __device__ __forceinline__ void sq_interval(const f16x8 (&af)[CFG::NFA], const f
                                             int wave, const uint32_t (&voffA)[CFG::PA], const uint32_t (&voffB)[CFG::PB],
                                             __amdgpu_buffer_rsrc_t rs_l, char* stage_l, uint32_t kbyte_l,
                                             __amdgpu_buffer_rsrc_t rs_e, char* stage_e, uint32_t kbyte_e) {
-  using PL = SqPlan<CFG>;
   constexpr int FM = CFG::FM, FN = CFG::FN, T = CFG::T, RS = CFG::RS;
   constexpr int NLEAD = PHASE == 0 ? CFG::NFB : CFG::NFA, FLEAD = PHASE == 0 ? FN : FM, FTRAIL = PHASE == 0 ? FM : FN;
   constexpr int OP_E = PHASE == 0 ? 1 : 0, OP_L = PHASE == 0 ? 0 : 1;          // operand of the early / late pieces
   constexpr int D_L = PHASE == 0 ? CFG::DA : CFG::DB;                          // late pieces are D_L .. NJ_op - 1 of their half-tile
   constexpr int S = PHASE == 0 ? CFG::P : CFG::Q;
-  constexpr bool GAPS = HGEMM_SQ_SPREAD && HGEMM_SQ_GAPS;
-  // LDS byte address of this wave's first 1-KiB block of the destination stages (GAPS: M0 = this + a constant per piece)
+  // LDS byte address of this wave's first 1-KiB block of the destination stages (M0 = this + a constant per piece)
   const uint32_t lds_l = (uint32_t)(uintptr_t)(lds_void_t*)stage_l + (uint32_t)wave * 1024u;
   const uint32_t lds_e = (uint32_t)(uintptr_t)(lds_void_t*)stage_e + (uint32_t)wave * 1024u;
-  (void)lds_l; (void)lds_e;
 #pragma unroll
   for (int n = 0; n < T; ++n) {
     const int u = n / (FM * FN), i = (n / FN) % FM, j = n % FN;   // MFMA k-slice, accumulator tile (i, j)
-    if (!GAPS && n == S) {
-      // every fragment read of the region about to be refilled has RETURNED (LDS returns in order, and the
-      // leading reads were the last ones issued), and my pieces of the half-tile the trailing reads are
-      // about to consume have landed; two younger half-tiles may stay in flight
-      if (!(HGEMM_SQ_ABL & 4)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(HGEMM_SQ_ABL & 2)) wait_vmcnt<CFG::NJA + CFG::NJB>();
-      if (!(HGEMM_SQ_ABL & 1)) sp_sync();
-    }
-    if (GAPS && n == S) {   // (the vmcnt wait went out one gap earlier)
+    if (n == S) {
+      // every fragment read of the region about to be refilled has RETURNED (LDS returns in order, and the leading reads
+      // were the last ones issued), and my pieces of the half-tile the trailing reads are about to consume have landed (the
+      // vmcnt wait went out one gap earlier; two younger half-tiles may stay in flight)
       __builtin_amdgcn_sched_barrier(0);
       if (!(HGEMM_SQ_ABL & 4)) __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
       if (!(HGEMM_SQ_ABL & 1)) sp_sync();
@@ -340,39 +294,21 @@ __device__ __forceinline__ void sq_interval(const f16x8 (&af)[CFG::NFA], const f
       const int r = n / RS;
       lead[r] = *(const f16x8*)((r / FLEAD ? lead1 : lead0) + (r % FLEAD) * CFG::MI * ROW_BYTES);
     }
-    if constexpr (GAPS) {
-      // gap n (behind MFMA n): at most one memory instruction besides a leading read; the M0 write of a piece one gap early
-      constexpr SqSlots<CFG, PHASE> tab{};
-      const int l = (HGEMM_SQ_ABL & 8) ? -1 : tab.late[n], l1 = (HGEMM_SQ_ABL & 8) ? -1 : tab.late[n + 1];
-      const int e = (HGEMM_SQ_ABL & 8) ? -1 : tab.early[n], e1 = (HGEMM_SQ_ABL & 8) ? -1 : tab.early[n + 1];
-      const int r = (HGEMM_SQ_ABL & 16) ? -1 : tab.trail[n];
-      if (l >= 0) { if constexpr (OP_L == 0) sq_piece_load<CFG, 0>(rs_l, voffA, D_L + l, kbyte_l); else sq_piece_load<CFG, 1>(rs_l, voffB, D_L + l, kbyte_l); }
-      if (e >= 0) { if constexpr (OP_E == 0) sq_piece_load<CFG, 0>(rs_e, voffA, e, kbyte_e); else sq_piece_load<CFG, 1>(rs_e, voffB, e, kbyte_e); }
-      if (r >= 0) trail[r] = *(const f16x8*)((r / FTRAIL ? trail1 : trail0) + (r % FTRAIL) * CFG::MI * ROW_BYTES);
-      if (l1 >= 0) sq_piece_m0<CFG, OP_L>(lds_l, D_L + l1, l1 > 0);
-      if (e1 >= 0) sq_piece_m0<CFG, OP_E>(lds_e, e1, e1 > 0);
-      if (n == S - 2 && !(HGEMM_SQ_ABL & 2)) wait_vmcnt<CFG::NJA + CFG::NJB>();
-      if (n == T - 3) {   // every read of this interval has long returned: from here on the compiler knows it, too
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else if constexpr (HGEMM_SQ_SPREAD) {
-      constexpr SqSlots<CFG, PHASE> tab{};
-      const int l = (HGEMM_SQ_ABL & 8) ? -1 : tab.late[n];
-      const int e = (HGEMM_SQ_ABL & 8) ? -1 : tab.early[n];
-      const int r = (HGEMM_SQ_ABL & 16) ? -1 : tab.trail[n];
-      if (l >= 0) { if constexpr (OP_L == 0) sq_issue_piece<CFG, 0>(rs_l, voffA, stage_l, wave, D_L + l, kbyte_l); else sq_issue_piece<CFG, 1>(rs_l, voffB, stage_l, wave, D_L + l, kbyte_l); }
-      if (r >= 0) trail[r] = *(const f16x8*)((r / FTRAIL ? trail1 : trail0) + (r % FTRAIL) * CFG::MI * ROW_BYTES);
-      if (e >= 0) { if constexpr (OP_E == 0) sq_issue_piece<CFG, 0>(rs_e, voffA, stage_e, wave, e, kbyte_e); else sq_issue_piece<CFG, 1>(rs_e, voffB, stage_e, wave, e, kbyte_e); }
-    } else if (PHASE == 0) {
-      const int r = (HGEMM_SQ_ABL & 16) ? -1 : PL::a_read_at(n), p = (HGEMM_SQ_ABL & 8) ? -1 : PL::a_piece_at(n);
-      if (p >= 0) { if constexpr (OP_E == 0) sq_issue_piece<CFG, 0>(rs_e, voffA, stage_e, wave, p, kbyte_e); else sq_issue_piece<CFG, 1>(rs_e, voffB, stage_e, wave, p, kbyte_e); }
-      if (r >= 0) trail[r] = *(const f16x8*)((r / FTRAIL ? trail1 : trail0) + (r % FTRAIL) * CFG::MI * ROW_BYTES);
-    } else {
-      const int r = (HGEMM_SQ_ABL & 16) ? -1 : PL::b_read_at(n), p = (HGEMM_SQ_ABL & 8) ? -1 : PL::b_piece_at(n);
-      if (r >= 0) trail[r] = *(const f16x8*)((r / FTRAIL ? trail1 : trail0) + (r % FTRAIL) * CFG::MI * ROW_BYTES);
-      if (p >= 0) { if constexpr (OP_E == 0) sq_issue_piece<CFG, 0>(rs_e, voffA, stage_e, wave, p, kbyte_e); else sq_issue_piece<CFG, 1>(rs_e, voffB, stage_e, wave, p, kbyte_e); }
+    // gap n (behind MFMA n): at most one memory instruction besides a leading read; the M0 write of a piece one gap early
+    constexpr SqSlots<CFG, PHASE> tab{};
+    const int l = (HGEMM_SQ_ABL & 8) ? -1 : tab.late[n], l1 = (HGEMM_SQ_ABL & 8) ? -1 : tab.late[n + 1];
+    const int e = (HGEMM_SQ_ABL & 8) ? -1 : tab.early[n], e1 = (HGEMM_SQ_ABL & 8) ? -1 : tab.early[n + 1];
+    const int r = (HGEMM_SQ_ABL & 16) ? -1 : tab.trail[n];
+    if (l >= 0) { if constexpr (OP_L == 0) sq_piece_load<CFG, 0>(rs_l, voffA, D_L + l, kbyte_l); else sq_piece_load<CFG, 1>(rs_l, voffB, D_L + l, kbyte_l); }
+    if (e >= 0) { if constexpr (OP_E == 0) sq_piece_load<CFG, 0>(rs_e, voffA, e, kbyte_e); else sq_piece_load<CFG, 1>(rs_e, voffB, e, kbyte_e); }
+    if (r >= 0) trail[r] = *(const f16x8*)((r / FTRAIL ? trail1 : trail0) + (r % FTRAIL) * CFG::MI * ROW_BYTES);
+    if (l1 >= 0) sq_piece_m0<CFG, OP_L>(lds_l, D_L + l1, l1 > 0);
+    if (e1 >= 0) sq_piece_m0<CFG, OP_E>(lds_e, e1, e1 > 0);
+    if (n == S - 2 && !(HGEMM_SQ_ABL & 2)) wait_vmcnt<CFG::NJA + CFG::NJB>();
+    if (n == T - 3) {   // every read of this interval has long returned: from here on the compiler knows it, too
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
 }

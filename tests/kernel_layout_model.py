@@ -384,14 +384,13 @@ def sp_plan(FM: int, FN: int, NJA: int, NJB: int, RS: int = 2):
 
 
 # ---- family "q" (hgemm_kernel_sq.hpp): early-A operand split, two sync points per pipeline stage ---------------
-def sq_plan(FM: int, FN: int, PA: int, PB: int, KT: int = 1, slack64: int = 6, rs64: int = 2, MI: int = 16, slack32: int = 4,
-            spread: bool = True):
+def sq_plan(FM: int, FN: int, PA: int, PB: int, KT: int = 1, slack64: int = 6, rs64: int = 2, MI: int = 16, slack32: int = 4):
     """Mirror of CfgSQ / SqPlan: slot numbers of the leading reads, the sync point, the trailing reads and the LDS-DMA
     pieces of interval A (phase 0) and interval B (phase 1).  FM, FN = MFMA tiles per wave tile (TM / MI, TN / MI);
     MI = 32 runs two k = 16 MFMA slices per K = 32 interval.
-    spread (round 3, HGEMM_SQ_SPREAD): a half-tile's first D pieces go out behind the sync point that frees its region
-    ("early_*"), its last E pieces in front of the NEXT interval's sync point ("late_*": interval A carries the late
-    pieces of the A half-tile, interval B those of the B half-tile).  spread = False is the round-2 plan (E = 0)."""
+    The pieces are spread (round 3): a half-tile's first D pieces go out behind the sync point that frees its region
+    ("pieces_*"), its last E pieces in front of the NEXT interval's sync point ("late_*": interval A carries the late
+    pieces of the A half-tile, interval B those of the B half-tile)."""
     SL = KT * (1 if MI == 16 else 2)
     NFA, NFB, T = FM * SL, FN * SL, FM * FN * SL
     NJA, NJB = KT * PA, KT * PB
@@ -400,20 +399,6 @@ def sq_plan(FM: int, FN: int, PA: int, PB: int, KT: int = 1, slack64: int = 6, r
     P, Q = RS * NFB + slack, RS * NFA + slack
     base = {"T": T, "P": P, "Q": Q, "NJA": NJA, "NJB": NJB, "NFA": NFA, "NFB": NFB,
             "lead_A": [RS * r for r in range(NFB)], "lead_B": [RS * r for r in range(NFA)]}
-    if not spread:
-        STA = 2 if (T - P - 1) // (NJB + NFA) >= 2 else 1
-        STB = 2 if (T - Q - 1) // (NJA + NFB) >= 2 else 1
-
-        def interleave(first_n, second_n):     # item index of element i of the list that goes first / second
-            first = [2 * i if i < second_n else second_n + i for i in range(first_n)]
-            second = [2 * i + 1 if i < first_n else first_n + i for i in range(second_n)]
-            return first, second
-
-        a_piece_items, a_read_items = interleave(NJB, NFA)       # behind P: B pieces lead, A-fragment reads follow
-        b_read_items, b_piece_items = interleave(NFB, NJA)       # behind Q: B-fragment reads lead, A pieces follow
-        return dict(base, EA=0, EB=0, late_A=[], late_B=[],
-                    pieces_A=[P + 1 + STA * i for i in a_piece_items], reads_A=[P + 1 + STA * i for i in a_read_items],
-                    reads_B=[Q + 1 + STB * i for i in b_read_items], pieces_B=[Q + 1 + STB * i for i in b_piece_items])
     EA = min((NJA * P + T // 2) // T, NJA - 1)
     EB = min((NJB * Q + T // 2) // T, NJB - 1)
 
@@ -456,12 +441,12 @@ def sq_schedule_hazards(plan: dict, steps: int = 8):
            issued after it BEFORE THE WAIT;
       WAR  a DMA piece into a region must come behind a "bar" that follows every read of the region's previous occupant
            (tile t-2).
-    The round-2 plan and the plain spread plan wait and synchronise in one slot; the one-instruction-per-gap form
-    (plan["gaps"]) waits for vmcnt two slots ahead of the barrier.  Returns a list of violations (empty = hazard-free).
+    The vmcnt wait sits two slots ahead of the barrier (the one-instruction-per-gap form of sq_interval).  Returns a list of
+    violations (empty = hazard-free).
     Every tile must also receive exactly its NJ pieces."""
     T, NJA, NJB = plan["T"], plan["NJA"], plan["NJB"]
-    EA = plan.get("EA", 0)
-    vm_lead = 2 if plan.get("gaps") else 0
+    EA = plan["EA"]
+    vm_lead = 2   # slots between the vmcnt wait and its barrier
     events = []   # (time, kind, arg, tile); a sync sorts before its slot's MFMA (half 0), the slot's other items behind it
 
     def at(interval, slot, half=0):
@@ -486,20 +471,20 @@ def sq_schedule_hazards(plan: dict, steps: int = 8):
         ia, ib = 2 * t, 2 * t + 1
         for s in plan["lead_A"]:
             events.append((at(ia, s, 1), "read", "B", (t, 1)))
-        for s in plan.get("late_A", []):
+        for s in plan["late_A"]:
             events.append((at(ia, s, 1), "dma", "A", t + 2))     # the A stream still points at tile t+2 here
-        events.append((at(ia, plan["P"] - vm_lead, 1 if vm_lead else 0) + (1 if vm_lead else 0), "vm", NJA + NJB, None))
-        events.append((at(ia, plan["P"], 0) + (0 if vm_lead else 0.5), "bar", None, None))
+        events.append((at(ia, plan["P"] - vm_lead, 1) + 1, "vm", NJA + NJB, None))
+        events.append((at(ia, plan["P"], 0), "bar", None, None))
         for s in plan["pieces_A"]:
             events.append((at(ia, s, 1), "dma", "B", t + 2))
         for s in plan["reads_A"]:
             events.append((at(ia, s, 1), "read", "A", (t + 1, 1)))
         for s in plan["lead_B"]:
             events.append((at(ib, s, 1), "read", "A", (t + 1, 0)))
-        for s in plan.get("late_B", []):
+        for s in plan["late_B"]:
             events.append((at(ib, s, 1), "dma", "B", t + 2))
-        events.append((at(ib, plan["Q"] - vm_lead, 1 if vm_lead else 0) + (1 if vm_lead else 0), "vm", NJA + NJB, None))
-        events.append((at(ib, plan["Q"], 0) + (0 if vm_lead else 0.5), "bar", None, None))
+        events.append((at(ib, plan["Q"] - vm_lead, 1) + 1, "vm", NJA + NJB, None))
+        events.append((at(ib, plan["Q"], 0), "bar", None, None))
         for s in plan["reads_B"]:
             events.append((at(ib, s, 1), "read", "B", (t + 1, 0)))
         for s in plan["pieces_B"]:

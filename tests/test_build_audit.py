@@ -145,7 +145,7 @@ def test_sp_k_loops_are_mfma_streams_with_scalar_dma_descriptors(sp_functions):
 
 
 def test_m0_writes_and_lds_dma_loads_alternate_in_the_k_loops(sp_functions):
-    """Family q issues an LDS-DMA piece as two asm statements in two MFMA gaps (hgemm_kernel_sq.hpp, HGEMM_SQ_GAPS): M0 = the
+    """Family q issues an LDS-DMA piece as two asm statements in two MFMA gaps (hgemm_kernel_sq.hpp, sq_interval): M0 = the
     LDS destination, then the load.  M0 is the compiler's register, so the pairing is checked where it counts, on the ISA:
     in every MFMA loop of the q kernels an M0 write is followed by exactly one LDS-DMA load before the next M0 write,
     the loop neither starts with a load nor ends with a dangling M0 write, and at least one MFMA sits between the two

@@ -394,8 +394,8 @@ def test_report_tools_on_synthetic_inputs(tmp_path):
 
 
 def test_fast_division_is_exact(lib):
-    """hgemm_kernel.hpp fast_div / make_fast_div (the multipliers a launch passes to the kernels' raster map when
-    built with HGEMM_FASTDIV): exact for every 32-bit dividend, checked on edge values and a random sample."""
+    """hgemm_kernel.hpp fast_div / make_fast_div (the multipliers a launch passes to the kernels' raster map):
+    exact for every 32-bit dividend, checked on edge values and a random sample."""
     import random
 
     f = lib.hgemm_mi355x_selfcheck_fastdiv

@@ -206,21 +206,18 @@ def test_family_q_schedule_has_no_lds_hazard(bm, bn, wm, wn, kt, mi):
     nw = wm * wn
     FM, FN = bm // wm // mi, bn // wn // mi
     PA, PB = bm // 8 // nw, bn // 8 // nw
-    for spread in (True, False):
-        for slack, rs in [(6, 2), (2, 2), (12, 2), (6, 1)]:
-            plan = klm.sq_plan(FM, FN, PA, PB, kt, slack, rs, mi, slack32=min(slack, 6), spread=spread)
-            T = plan["T"]
-            for pieces, reads, late, sync in ((plan["pieces_A"], plan["reads_A"], plan["late_A"], plan["P"]),
-                                              (plan["pieces_B"], plan["reads_B"], plan["late_B"], plan["Q"])):
-                assert len(set(pieces)) == len(pieces) and len(set(reads)) == len(reads) and len(set(late)) == len(late)
-                assert max(pieces + reads) < T and min(pieces + reads) > sync
-                assert all(0 <= x < sync for x in late)
-                if not spread:
-                    assert len(set(pieces + reads)) == len(pieces + reads) and not late
-            assert len(plan["late_A"]) + len(plan["pieces_B"]) == plan["NJA"] and len(plan["late_B"]) + len(plan["pieces_A"]) == plan["NJB"]
-            assert max(plan["lead_A"]) < plan["P"] and max(plan["lead_B"]) < plan["Q"]
-            assert plan["NJA"] + plan["NJB"] <= 63                      # vmcnt is a 6-bit counter
-            assert klm.sq_schedule_hazards(plan) == []
+    for slack, rs in [(6, 2), (2, 2), (12, 2), (6, 1)]:
+        plan = klm.sq_plan(FM, FN, PA, PB, kt, slack, rs, mi, slack32=min(slack, 6))
+        T = plan["T"]
+        for pieces, reads, late, sync in ((plan["pieces_A"], plan["reads_A"], plan["late_A"], plan["P"]),
+                                          (plan["pieces_B"], plan["reads_B"], plan["late_B"], plan["Q"])):
+            assert len(set(pieces)) == len(pieces) and len(set(reads)) == len(reads) and len(set(late)) == len(late)
+            assert max(pieces + reads) < T and min(pieces + reads) > sync
+            assert all(0 <= x < sync for x in late)
+        assert len(plan["late_A"]) + len(plan["pieces_B"]) == plan["NJA"] and len(plan["late_B"]) + len(plan["pieces_A"]) == plan["NJB"]
+        assert max(plan["lead_A"]) < plan["P"] and max(plan["lead_B"]) < plan["Q"]
+        assert plan["NJA"] + plan["NJB"] <= 63                      # vmcnt is a 6-bit counter
+        assert klm.sq_schedule_hazards(plan) == []
 
 
 def test_family_q_hazard_model_catches_a_misplaced_wait():
