@@ -13,6 +13,7 @@ Restated rules (reference file:line):
   TFLOPS                benchmarking_utils.py:66              2*m*n*k*1e-12*1000/ms (unpadded sizes)
   -max row              summarize_result.py:43-53             lower cuda_l2 speedup of tn/nn
 Parity pinning: see hgemm_oracle.c header and tests/golden/make_golden.py.
+Of this project, not restated: dyadic_inputs / truth_exact and the three wrong-rounding mutants (the rounding tests).
 """
 from __future__ import annotations
 
@@ -135,6 +136,71 @@ def zero_one_inputs(m: int, n: int, k: int, rng: np.random.Generator, force_spar
     a = vals[rng.integers(0, len(vals), size=(m, k))]
     b = vals[rng.integers(0, len(vals), size=(k, n))]
     return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+DYADIC_MAX_K = 8160   # K x (1 + 3 x 2^-10) < 2^13: every partial sum is a multiple of 2^-10 below 2^13, at most 23 significant bits
+
+
+def dyadic_inputs(m: int, n: int, k: int, rng: np.random.Generator):
+    """Operands whose sums are exact in fp32 in ANY order and grouping, yet need a real rounding to fp16 (0/1 sums never do):
+    A in {-1, 0, 1}, B = z x (1 + e x 2^-10) with z in {0, 1}, e in {0, 1, 2, 3}, all uniform.  Every product is 0 or
+    +-(1 + e / 1024); a sum of any subset of K <= 8160 of them is a multiple of 2^-10 below 2^13.  Results are ~sqrt(K / 3) in
+    size, where fp16 spacing is 2^-9 ... 2^-4: most need rounding, many are exact ties, about half are negative."""
+    assert k <= DYADIC_MAX_K
+    a = rng.integers(-1, 2, size=(m, k)).astype(np.float16)
+    z = rng.integers(0, 2, size=(k, n))
+    e = rng.integers(0, 4, size=(k, n))
+    b = (z * (1024 + e) / 1024.0).astype(np.float16)
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def assert_dyadic(a: np.ndarray, b: np.ndarray) -> None:
+    """The class of dyadic_inputs, on which truth_exact's claim (and that of any fp32 accumulation order) rests."""
+    assert a.dtype == np.float16 and b.dtype == np.float16 and a.shape[1] == b.shape[0]
+    assert a.shape[1] <= DYADIC_MAX_K, f"K = {a.shape[1]} > {DYADIC_MAX_K}: a partial sum may need more than 24 bits"
+    assert np.isin(a, (-1.0, 0.0, 1.0)).all(), "A must hold -1 / 0 / 1 only"
+    b1024 = b.astype(np.float64) * 1024.0
+    assert (b1024 == np.floor(b1024)).all() and ((b1024 == 0) | ((b1024 >= 1024) & (b1024 <= 1027))).all(), \
+        "B must hold 0 or 1 + e / 1024, e in 0 ... 3, only"
+
+
+def exact_product(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    assert_dyadic(a, b)
+    return a.astype(np.float64) @ b.astype(np.float64)   # 23-bit sums: exact in fp64 whatever the BLAS order
+
+
+def truth_exact(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """The one right answer for dyadic operands: the exact product, rounded to fp16 once (astype: round-to-nearest-even)."""
+    return exact_product(a, b).astype(np.float16)
+
+
+def round_toward_zero(x: np.ndarray) -> np.ndarray:
+    """MUTANT: fp64 -> fp16 by truncation (finite values inside the fp16 range)."""
+    x = np.asarray(x, dtype=np.float64)
+    h = x.astype(np.float16)
+    return np.where(np.abs(h.astype(np.float64)) > np.abs(x), np.nextafter(h, np.float16(0)), h)
+
+
+def round_half_away(x: np.ndarray) -> np.ndarray:
+    """MUTANT: fp64 -> fp16 to nearest, ties away from zero (finite values inside the fp16 range; the distances to the two
+    fp16 neighbours must be exact in fp64, as they are for dyadic sums)."""
+    x = np.asarray(x, dtype=np.float64)
+    lo = round_toward_zero(x)
+    hi = np.nextafter(lo, np.where(x < 0, -np.inf, np.inf).astype(np.float16))
+    up = (x != lo) & (np.abs(hi.astype(np.float64) - x) <= np.abs(x - lo.astype(np.float64)))
+    return np.where(up, hi, lo)
+
+
+def fp16_partials(a: np.ndarray, b: np.ndarray, cuts) -> np.ndarray:
+    """MUTANT: a split-K whose partials are held in fp16 -- the exact sum of every K chunk [0, cuts[0]), [cuts[0], cuts[1]), ...
+    rounded to fp16, the chunks added in fp32, the total rounded once more."""
+    assert_dyadic(a, b)
+    edges = [0] + [int(c) for c in cuts] + [a.shape[1]]
+    assert all(lo < hi for lo, hi in zip(edges, edges[1:])), edges
+    acc = np.zeros((a.shape[0], b.shape[1]), dtype=np.float32)
+    for lo, hi in zip(edges, edges[1:]):
+        acc += truth_exact(a[:, lo:hi], b[lo:hi]).astype(np.float32)
+    return acc.astype(np.float16)
 
 
 def masked_max_diff(out: np.ndarray, truth: np.ndarray) -> float:

@@ -16,6 +16,8 @@ import bench  # noqa: E402  (bench.load_library: the product's only way in, fail
 
 FORMS = ["reference", "ragged", "stream-K", "split-K", "fused", "hybrid", "plain"]   # enum Form of hgemm_api.hip
 
+C_PAD = -3.0 * 2.0 ** -12   # prefill of C's padding: negative (no 0/1 sum is) and no multiple of 2^-10 (every dyadic sum is one)
+
 _lib = None
 
 
@@ -34,8 +36,8 @@ def stream():
 def gemm(a_np: np.ndarray, b_np: np.ndarray, entry: str = "fp32", plan=None, ld=None) -> np.ndarray:
     """C = A.B on the GPU through the C ABI; plan = (config_id, splits, group_m) for an explicit launch.  ld = (lda, ldb, ldc)
     (explicit plans only) places A, b_col_major and C in wider buffers: A's columns K..lda-1 and b_col_major's K..ldb-1 hold NaN
-    (0 x NaN = NaN: a read of them shows in C), C's columns N..ldc-1 hold -3.0 (no 0/1 product is negative), and every padding
-    element must come back bit-unchanged.  The row-major b stays contiguous (the library reads it at stride N)."""
+    (0 x NaN = NaN: a read of them shows in C), C's columns N..ldc-1 hold C_PAD (no result of 0/1 or dyadic operands), and every
+    padding element must come back bit-unchanged.  The row-major b stays contiguous (the library reads it at stride N)."""
     L = lib()
     m, k = a_np.shape
     n = b_np.shape[1]
@@ -46,7 +48,7 @@ def gemm(a_np: np.ndarray, b_np: np.ndarray, entry: str = "fp32", plan=None, ld=
     a[:, :k] = torch.from_numpy(np.ascontiguousarray(a_np)).cuda()
     bt = torch.full((n, ldb), float("nan"), dtype=torch.half, device="cuda")
     bt[:, :k] = b.t()
-    c = torch.full((m, ldc), -3.0, dtype=torch.half, device="cuda")
+    c = torch.full((m, ldc), C_PAD, dtype=torch.half, device="cuda")
     c[:, :n] = float("nan")  # unwritten outputs stay NaN
     pads = [(x[:, w:], x[:, w:].clone()) for x, w in ((a, k), (bt, k), (c, n))]
     if plan is None:

@@ -105,7 +105,7 @@ def test_the_class_shapes_are_exact(g, oracle, members, shape):
 
 
 def test_padded_strides_never_read_nan_padding_and_leave_c_padding_alone(g, oracle, members):
-    """ld = (K + 8, K + 24, N + 16): A's and b_col_major's padding columns hold NaN (a read of them shows in C), C's hold -3.0
+    """ld = (K + 8, K + 24, N + 16): A's and b_col_major's padding columns hold NaN (a read of them shows in C), C's hold gpu_common.C_PAD
     and must come back bit-unchanged (gpu_common.gemm compares every padding element); ragged M and N, every form."""
     for m, n, k in ((328, 456, 1024), (136, 72, 384)):
         assert check_exact(g, oracle, members, m, n, k, seed=m + k, ld=(k + 8, k + 24, n + 16))[0] == len(MEMBERS) * len(FORMS)

@@ -205,6 +205,13 @@ def test_special_values_round_like_the_reference(g, k, hot):
                         ("q256x256_w2x2_m32", 1), ("r64x64_k256", 1), ("r128x64_k128", 2 | 0x10000), ("r128x128_k128", 0x40000 | 3),
                         ("q128x128_w2x2_k128", 2), ("r64x128_k128_d", 1 | 0x180000)]:
         plans.append((f"{cfg}/{splits:#x}", (names.index(cfg), splits, 1)))
+    # the first table member of every family letter not named above (w and u today), plain and two-pass; like s256x128 it is
+    # served by the any-shape kernel at K = 552 where its family takes no K tail
+    named = {label[0] for label, plan in plans if plan and plan[0] >= 0}
+    for letter in sorted({name[0] for name in names} - named):
+        cfg = next(name for name in names if name[0] == letter)
+        plans += [(f"{cfg}/{splits:#x}", (names.index(cfg), splits, 1)) for splits in (1, 2)]
+    assert {name[0] for name in names} == {label[0] for label, plan in plans if plan and plan[0] >= 0}
     for label, plan in plans:
         c = torch.full((m, n), 7.0, dtype=torch.half, device="cuda")
         if plan is None:

@@ -133,3 +133,102 @@ def test_prefix_k_truths_are_bit_identical_to_the_one_shot_oracle():
         assert seen == ks
     with pytest.raises(AssertionError):
         list(oracle.truth_prefix_k(np.full((4, 64), 0.5, np.float16), np.ones((64, 4), np.float16), [64]))
+
+
+# ---- dyadic operands: the inputs of tests/test_gpu_rounding.py, proved on the CPU ----------------------------------------------
+@pytest.fixture(scope="module")
+def rounding_cases():
+    """The very operands of the GPU rounding tests (same seed, shape and K list, from the same table reader) at every K
+    they run, each with every K cut a kernel makes there: the host's 2-way and 3-way stage cuts of the geometries that run
+    that K, and the stream-K cuts.  The table is read through the C ABI and the launch-decision hook, no GPU."""
+    import build
+
+    build.build_library()
+    import gpu_common
+    import test_gpu_rounding as R
+
+    geos = R.read_table(gpu_common)
+    sk = R.table_cuts(geos)
+    m, n, ks = R.table_extent(geos, sk)
+    ops = R.DyadicOperands(oracle, m, n, ks, R.SEED)
+    cases = []
+    for k in ks:
+        cuts = {tuple(R.stage_cuts(k, geo.stage, ways)) for geo in geos if k in R.rounding_ks(geo) for ways in (2, 3)}
+        cuts |= {tuple(at) for kk, at in sk.values() if kk == k}
+        assert cuts and all(cuts), (k, cuts)
+        cases.append((*ops.sub(m, n, k), sorted(cuts)))
+    return cases
+
+
+def test_dyadic_truth_is_the_same_in_every_fp32_summation_order(rounding_cases):
+    """truth_exact (fp64, exact) equals the C oracle's k-order fp32 accumulation, numpy's BLAS order, and an fp32 accumulation
+    over a random permutation of K cut into uneven chunks: whatever order a kernel sums in, there is one right answer."""
+    rng = np.random.default_rng(9)
+    for a, b, truth, _ in rounding_cases:
+        k = a.shape[1]
+        assert np.array_equal(oracle.truth_exact(a, b).view(np.uint16), truth.view(np.uint16))
+        assert np.array_equal(oracle.truth_f32acc(a, b).view(np.uint16), truth.view(np.uint16))
+        assert np.array_equal(oracle.truth_numpy(a, b).view(np.uint16), truth.view(np.uint16))
+        perm = rng.permutation(k)
+        edges = [0] + sorted(rng.choice(np.arange(1, k), size=6, replace=False).tolist()) + [k]
+        acc = np.zeros(truth.shape, dtype=np.float32)
+        for lo, hi in reversed(list(zip(edges, edges[1:]))):
+            part = np.zeros(truth.shape, dtype=np.float32)
+            for kk in perm[lo:hi]:
+                part += np.outer(a[:, kk].astype(np.float32), b[kk].astype(np.float32))   # one fp32 add per product, this order
+            acc += part
+        assert np.array_equal(acc.astype(np.float64), oracle.exact_product(a, b))       # no fp32 add ever rounded
+        assert np.array_equal(acc.astype(np.float16).view(np.uint16), truth.view(np.uint16))
+
+
+def test_dyadic_operands_discriminate_in_every_16x16_block(rounding_cases):
+    """Conditions on the inputs, not measurements of a kernel: every whole 16x16 block of C (the footprint of one MFMA tile: all
+    lanes, all accumulator registers) holds an element that a truncating convert gets wrong, one that round-half-away gets
+    wrong, and one that fp16-held partials of each host cut get wrong; a tenth of C and more is negative and inexact."""
+    def every_block(differs):
+        mm, nn = differs.shape[0] // 16 * 16, differs.shape[1] // 16 * 16
+        return differs[:mm, :nn].reshape(mm // 16, 16, nn // 16, 16).any(axis=(1, 3)).all()
+
+    for a, b, truth, cut_sets in rounding_cases:
+        x = oracle.exact_product(a, b)
+        assert every_block(oracle.round_toward_zero(x) != truth), "RTZ"
+        assert every_block(oracle.round_half_away(x) != truth), "half-away"
+        for cuts in cut_sets:
+            assert every_block(oracle.fp16_partials(a, b, cuts) != truth), cuts
+        assert ((x < 0) & (truth.astype(np.float64) != x)).mean() >= 0.10
+
+
+def test_dyadic_mutants_round_as_they_say():
+    """The three wrong roundings on hand-made values: ties, both signs, exact values, the first integer fp16 cannot hold."""
+    x = np.array([1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(1 + 2.0 ** -11), 2049.0, -2049.0, 1.0, 0.0, 1 + 2.0 ** -12, 1 + 2.0 ** -11 + 2.0 ** -20,
+                  -(1 + 2.0 ** -10 - 2.0 ** -20)])
+    e = 2.0 ** -10
+    assert x.astype(np.float16).tolist() == [1.0, 1 + 2 * e, -1.0, 2048.0, -2048.0, 1.0, 0.0, 1.0, 1 + e, -(1 + e)]
+    assert oracle.round_half_away(x).tolist() == [1 + e, 1 + 2 * e, -(1 + e), 2050.0, -2050.0, 1.0, 0.0, 1.0, 1 + e, -(1 + e)]
+    assert oracle.round_toward_zero(x).tolist() == [1.0, 1 + e, -1.0, 2048.0, -2048.0, 1.0, 0.0, 1.0, 1.0, -1.0]
+    assert oracle.round_toward_zero(x).dtype == oracle.round_half_away(x).dtype == np.float16
+    # 1 + (1 + e) = 2 + e is a tie and rounds to 2; (1 + e) + (1 + e) is exact: the fp16-held halves give 4 + 2e -> 4, the truth is 4 + 3e -> 4 + 4e
+    a = np.ones((1, 4), np.float16)
+    b = np.array([[1.0], [1 + e], [1 + e], [1 + e]], np.float16)
+    assert oracle.truth_exact(a, b)[0, 0] == 4 + 4 * e and oracle.fp16_partials(a, b, [2])[0, 0] == 4.0
+    assert oracle.fp16_partials(a, b, [])[0, 0] == 4 + 4 * e
+
+
+def test_dyadic_class_assertion_rejects_what_would_break_exactness():
+    rng = np.random.default_rng(5)
+    a, b = oracle.dyadic_inputs(8, 8, 64, rng)
+    oracle.truth_exact(a, b)
+    bad = b.copy()
+    bad[3, 3] = 1 + 4 / 1024                    # e = 4
+    for wrong_b in (bad, np.where(b == 0, np.float16(0.5), b), np.where(b == 0, np.float16("nan"), b)):
+        with pytest.raises(AssertionError):
+            oracle.truth_exact(a, wrong_b)
+    with pytest.raises(AssertionError):
+        oracle.truth_exact(np.where(a == 0, np.float16(2), a), b)
+    a1 = np.ones((1, 8161), np.float16)
+    b1 = np.ones((8161, 1), np.float16)
+    oracle.truth_exact(a1[:, :8160], b1[:8160])
+    with pytest.raises(AssertionError):
+        oracle.truth_exact(a1, b1)               # K = 8161
+    with pytest.raises(AssertionError):
+        oracle.dyadic_inputs(1, 1, 8161, rng)
