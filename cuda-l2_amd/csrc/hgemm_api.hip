@@ -3,6 +3,7 @@
 // hipLaunchKernelGGL: the reference harness times host wall-clock around each call
 // (benchmarking_utils.py:23-31), so a lean host path is part of the hot path.
 #include "hgemm_plan.hpp"
+#include "hgemm_kernel_nn.hpp"
 #include "../../include/hgemm_mi355x.h"
 
 #include <algorithm>
@@ -449,6 +450,95 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
   return hgemm_mi355x_launch(cfg, splits, group_m, a, b, bt, c, M, N, K, K, K, N, stream);
 }
 
+
+// ---- NN layout (family n, hgemm_kernel_nn.hpp): B row-major [K][ldb] ----------------------------------------------------------------
+// The family has its own table (g_nn_table, hgemm_inst_g5.hip) and its own resolution; the geometry table, hgemm_mi355x_plan and what
+// a b-only call of hgemm_mi355x_launch does know nothing of it.
+// the kernel's scope; everything else is answered by the reference kernel (status 0, exact)
+bool nn_path_ok(const void* a, const void* b, const void* c, int N, int K, int lda, int ldb, int ldc) {
+  if (K % BK != 0 || (N & 7) != 0) return false;
+  if ((lda & 7) || (ldb & 7) || (ldc & 7)) return false;
+  return !(((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15));
+}
+// 32-bit tile offsets with bit 31 to spare: A and C from a tile's first row, B from row 0 to the end of the matrix
+bool nn_reach_ok(const NNEntry& e, int N, int K, int lda, int ldb, int ldc) {
+  return (double)e.bm * lda * 2.0 + K * 2.0 < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 &&
+         (double)e.bm * ldc * 2.0 + N * 2.0 < 2147483648.0;
+}
+// (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn shows it to the CPU tests)
+LaunchPlan resolve_nn(int nn_config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc, unsigned ruled_out) {
+  LaunchPlan p;
+  auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
+    if (p.n) p.d[p.n - 1].stop = false;
+    p.d[p.n] = Dispatch{thunk, g, (int)grid, epi, p.n == 0, true};
+    ++p.n;
+  };
+  // rows must not overlap: lda >= K, ldb >= N (B is row-major here), ldc >= N
+  if (nn_config < 0 || nn_config >= g_num_nn || lda < K || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
+  const NNEntry& e = g_nn_table[nn_config];
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
+  g.flags = (splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
+  g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
+  const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
+  if (!aligned || !nn_path_ok(nullptr, nullptr, nullptr, N, K, lda, ldb, ldc) || !nn_reach_ok(e, N, K, lda, ldb, ldc) || tiles > 0x7fffffffL) {
+    p.form = FORM_REFERENCE;
+    add(THUNK_GENERIC, g, 0, EPI_C16);
+    return p;
+  }
+  g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (N + e.bn - 1) / e.bn;
+  g.group_m = std::min(g.tiles_m, 8);
+  // at most one split per stage, no empty split (the arithmetic of split_k); the single-launch and stream-K words have no kernel
+  // here: their split count runs as the two-pass form / the plain launch
+  const int steps = K / BK;
+  int splits = (splits_arg & HGEMM_PLAN_STREAMK) ? 1 : std::max(1, std::min(splits_arg & HGEMM_SPLITK_MASK, steps));
+  if ((ruled_out & (1u << FORM_SPLITK)) || tiles * splits > 0x7fffffffL) splits = 1;
+  const int per = (steps + splits - 1) / splits;
+  splits = (steps + per - 1) / per;
+  g.k_chunk = per * BK; g.splits = splits; g.items = (int)(tiles * splits);
+  set_raster_div(g);
+  if (splits > 1) {
+    p.form = FORM_SPLITK;
+    p.slab_bytes = (size_t)splits * M * N * sizeof(float);
+    add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
+    add(THUNK_SPLITK_REDUCE, g, 0, EPI_SLAB);
+  } else {
+    add(THUNK_ENTRY, g, tiles, EPI_C16);
+  }
+  return p;
+}
+
+// Planner of the family: the largest member whose tiles fill the chip (ties: fewer padded elements, then the taller tile); otherwise
+// the 64 x 64 member with as many two-pass splits as bring tiles x splits up to the CU count -- at most one per K stage, at most 32.
+void nn_model_plan(int M, int N, int K, int* cfg, int* splits) {
+  int best = -1;
+  long best_area = 0, best_pad = 0;
+  for (int i = 0; i < g_num_nn; ++i) {
+    const NNEntry& e = g_nn_table[i];
+    const long tm = (M + e.bm - 1) / e.bm, tn = (N + e.bn - 1) / e.bn, area = (long)e.bm * e.bn, pad = tm * e.bm * tn * e.bn;
+    if (tm * tn < kCUs) continue;
+    if (best < 0 || area > best_area || (area == best_area && (pad < best_pad || (pad == best_pad && e.bm > g_nn_table[best].bm)))) {
+      best = i; best_area = area; best_pad = pad;
+    }
+  }
+  if (best >= 0) { *cfg = best; *splits = 1; return; }
+  int small = 0;
+  for (int i = 1; i < g_num_nn; ++i)
+    if (g_nn_table[i].bm * g_nn_table[i].bn < g_nn_table[small].bm * g_nn_table[small].bn) small = i;
+  const NNEntry& e = g_nn_table[small];
+  const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
+  *cfg = small;
+  *splits = (int)std::max<long>(1, std::min<long>(std::min<long>((kCUs + tiles - 1) / tiles, K / BK), 32));
+}
+
+int run_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
+  int cfg, splits;
+  const int st = hgemm_mi355x_nn_plan(M, N, K, &cfg, &splits);
+  if (st != HGEMM_OK) return st;
+  return hgemm_mi355x_launch_nn(cfg, splits, a, b, c, M, N, K, K, N, N, stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -699,6 +789,112 @@ int hgemm_mi355x_fp32(const void* a, const void* b, const void* bt, void* c, int
 int hgemm_mi355x_fp16(const void* a, const void* b, const void* bt, void* c, int M, int N, int K,
                       void* stream) {
   return run(HGEMM_ACC_FP16, a, b, bt, c, M, N, K, stream);
+}
+
+// ---- NN layout ------------------------------------------------------------------------------------------------------------------
+int hgemm_mi355x_nn_num_configs(void) { return g_num_nn; }
+
+const char* hgemm_mi355x_nn_config_name(int id) { return (id >= 0 && id < g_num_nn) ? g_nn_table[id].name : nullptr; }
+
+int hgemm_mi355x_nn_config_by_name(const char* name) {
+  if (!name) return -1;
+  for (int i = 0; i < g_num_nn; ++i)
+    if (std::strcmp(name, g_nn_table[i].name) == 0) return i;
+  return -1;
+}
+
+int hgemm_mi355x_nn_config_info(int id, int out[8]) {
+  if (id < 0 || id >= g_num_nn || !out) return HGEMM_ERR_BAD_ARG;
+  const NNEntry& e = g_nn_table[id];
+  out[0] = e.bm; out[1] = e.bn; out[2] = e.wm; out[3] = e.wn; out[4] = 16; out[5] = e.nbuf; out[6] = e.threads; out[7] = e.lds_bytes;
+  return HGEMM_OK;
+}
+
+int hgemm_mi355x_nn_plan(int M, int N, int K, int* nn_config, int* splits) {
+  if (M <= 0 || N <= 0 || K <= 0 || !nn_config || !splits) return HGEMM_ERR_BAD_ARG;
+  nn_model_plan(M, N, K, nn_config, splits);
+  return HGEMM_OK;
+}
+
+int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const LaunchPlan p = resolve_nn(nn_config, 1, true, M, N, K, lda, ldb, ldc, 0);
+  return p.status == HGEMM_OK && p.form != FORM_REFERENCE ? 1 : 0;
+}
+
+size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const LaunchPlan p = resolve_nn(nn_config, splits, true, M, N, K, K, N, N, 0);
+  return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
+}
+
+int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  int cfg = 0, splits = 1;
+  nn_model_plan(M, N, K, &cfg, &splits);
+  const size_t ws = hgemm_mi355x_nn_plan_workspace_bytes(cfg, splits, M, N, K);
+  if (!ws) return HGEMM_OK;
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  const int rc = ensure_workspace(ws - kCounterBytes, (hipStream_t)stream, &slabs, &counters);
+  return rc == HGEMM_ERR_NO_WORKSPACE_INTERNAL ? HGEMM_ERR_NO_WORKSPACE : rc;
+}
+
+int hgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
+                           int ldc, void* stream) {
+  struct DisarmTiming {  // the timing hook is one-shot whatever path (or error return) this call takes
+    ~DisarmTiming() { hgemm_mi355x::t_launch_timing = hgemm_mi355x::LaunchTiming{}; }
+  } disarm_timing;
+  if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool aligned = nn_path_ok(a, b, c, N, K, lda, ldb, ldc);
+  unsigned ruled_out = 0;
+  LaunchPlan p = resolve_nn(nn_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
+  if (p.status == HGEMM_OK && p.slab_bytes) {
+    const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
+    if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
+      ruled_out |= 1u << FORM_SPLITK;
+      p = resolve_nn(nn_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+    } else if (st != HGEMM_OK) {
+      return st;
+    }
+  }
+  if (p.status != HGEMM_OK) return p.status;
+  for (int i = 0; i < p.n; ++i) {
+    GemmArgs& g = p.d[i].g;
+    g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (family n reads GemmArgs::Bt as the row-major B)
+    if (p.d[i].epi != EPI_C16) g.partial = slabs;
+    const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
+    switch (p.d[i].thunk) {
+      case THUNK_ENTRY: g_nn_table[nn_config].launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
+      case THUNK_SPLITK_REDUCE: launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts); break;
+      default: launch_generic((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts); break;
+    }
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
+}
+
+int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return run_nn(a, b, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return run_nn(a, b, c, M, N, K, stream); }
+
+// what hgemm_mi355x_launch_nn decides for a call, nothing launched (the twin of hgemm_mi355x_selfcheck_launch; not part of the public
+// header): operands = 4 when the pointers are 16-byte aligned, ruled_out = 1 << form of the two-pass form that got no workspace.
+// Returns the call's status; out = {form, dispatches, slab bytes, counters (0)}, then per dispatch {thunk, grid, epi, splits, k_chunk,
+// items, start, stop}.
+int hgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                     long long out[20]) {
+  if (M <= 0 || N <= 0 || K <= 0 || !out) return HGEMM_ERR_BAD_ARG;
+  const LaunchPlan p = resolve_nn(nn_config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out);
+  out[0] = p.form; out[1] = p.n; out[2] = (long long)p.slab_bytes; out[3] = p.counters;
+  for (int i = 0; i < p.n; ++i) {
+    const Dispatch& d = p.d[i];
+    const long long v[8] = {d.thunk, d.grid, d.epi, d.g.splits, d.g.k_chunk, d.g.items, d.start, d.stop};
+    std::copy(v, v + 8, out + 4 + 8 * i);
+  }
+  return p.status;
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the

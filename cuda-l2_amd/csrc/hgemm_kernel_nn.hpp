@@ -1,0 +1,249 @@
+// Family "n": NN operand form -- C[M,N] = A[M,K] * B[K,N] with B ROW-MAJOR as the caller holds it ([K][ldb], N contiguous), for the
+// caller whose B is an activation and not a pre-transposed weight.  Replaces, for a b-only call, the one-output-per-thread
+// reference kernel (hgemm_generic_kernel); the vendor baselines have the form as hgemm_rocblas_nn / hgemm_hipblaslt_*_nn
+// (reference cublas/fp32/hgemm_cublas.cu:15-41).
+//
+// The classic family's structure (hgemm_kernel.hpp): NBUF-deep LDS ring of K = 64 stages, ONE barrier per stage, counted vmcnt,
+// LDS-DMA fills, v_mfma_f32_16x16x32_f16 with fp32 accumulation, operands swapped so that a lane owns 4 consecutive N of a C row.
+//   * A image: unchanged -- [BM rows][128 B], 16-byte chunk c of row r at slot c ^ ((r >> 1) & 7), fragments by ds_read_b128.
+//   * B image: [64 k-rows][BN halfs], row-major as B lies in memory.  A k-row of the tile is BN * 2 contiguous bytes, so a 1-KiB
+//     DMA piece is 512 / BN whole k-rows and every wave instruction reads whole 128- / 256-byte lines.
+//   * The MFMA operand of lane (n = lane & 15, kq = lane >> 4) is k = 8 kq .. 8 kq + 7 of column n: a COLUMN of the image.  It
+//     comes from two ds_read_b64_tr_b16, each of which hands a 16-lane group a 4-row x 16-column block transposed: lane 4q + p of
+//     the group supplies the address of block row q, columns 4p .. 4p + 3, and lane i receives column i with row q in element q.
+//     The two reads take rows 8 kq .. 8 kq + 3 and 8 kq + 4 .. 8 kq + 7 of the K = 32 slice.
+//   * Swizzle (nn_swz): a permutation of the 16-byte chunks inside a k-row, applied to the per-lane SOURCE address of the DMA (the
+//     destination is lane-linear; inside one row, so coalescing stays) and undone on the read.  A 32-lane half of a transposed read
+//     touches 8 rows x 32 bytes (rows 8g + 4h + q, g = two adjacent groups): unswizzled they share banks 8-way (256-byte rows) /
+//     4-way (128-byte rows); swizzled they tile the 256-byte bank row exactly (tests/nn_layout_model.py replays both maps).
+//     The XOR may swap the two 8-byte halves of a lane pair's 32 bytes, so every lane address is computed from (row, chunk).
+//   * Two hardware rules of the transposed read, each giving wrong data without a fault: every lane address is 8-byte aligned
+//     (all offsets below are multiples of 8 from a 1024-aligned array), and EXEC is all ones at every read -- there is no
+//     lane-dependent branch or early return in front of the K loop; out-of-tile lanes read in-bounds LDS and their products land
+//     in accumulators that are never stored.
+//   * Edges: M rows clamped on load (classic).  N: a chunk at columns >= N reads whatever follows in memory -- the next row, or
+//     zeros behind the end of the matrix, where the B descriptor ends -- and only feeds accumulators of columns >= N; stores are
+//     predicated.  Scope (the host sends anything else to the reference kernel): K % 64 == 0, N % 8 == 0, lda / ldb / ldc
+//     multiples of 8, 16-byte aligned pointers, operands within 2 GiB of 32-bit offsets.
+//   * Epilogues: fp16 C (plain and non-temporal) and the two-pass split-K slab (hgemm_splitk_reduce_kernel combines).
+#pragma once
+
+#include "hgemm_launch.hpp"
+
+namespace hgemm_mi355x {
+
+// chunk XOR of k-row `krow` of the B image (see above); BN = 128: the dual-use image of 256-byte rows, BN = 64: two k-rows per
+// 256-byte bank row, the pair index takes bit 1 and bit 3 of the row
+template <int BN>
+__host__ __device__ constexpr int nn_swz(int krow) {
+  return BN == 128 ? (((krow & 3) << 2) | ((krow >> 2) & 3)) : ((((krow >> 1) & 1) | (((krow >> 3) & 1) << 1)) << 1);
+}
+
+template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
+struct CfgNN {
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MI = 16, NBUF = NBUF_;
+  static constexpr int NW          = WM * WN;
+  static constexpr int THREADS     = NW * 64;
+  static constexpr int TM          = BM / WM;
+  static constexpr int TN          = BN / WN;
+  static constexpr int FM          = TM / 16;
+  static constexpr int FN          = TN / 16;
+  static constexpr int A_BYTES     = BM * ROW_BYTES;
+  static constexpr int B_ROW_BYTES = BN * 2;               // one k-row of the B image
+  static constexpr int B_BYTES     = BK * B_ROW_BYTES;
+  static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
+  static constexpr int LDS_BYTES   = STAGE_BYTES * NBUF;
+  static constexpr int B_CH        = BN / 8;               // 16-byte chunks per k-row
+  static constexpr int B_RPP       = 64 / B_CH;            // k-rows per 1-KiB DMA piece
+  static constexpr int NI_A        = BM / 8;               // DMA pieces of the A tile ...
+  static constexpr int NI_B        = B_BYTES / 1024;       // ... and of the B tile
+  static constexpr int NJ_A        = NI_A / NW;            // pieces per wave: piece wave + j * NW, the first NJ_A of them are A's
+  static constexpr int NJ          = (NI_A + NI_B) / NW;
+  static_assert(BN == 64 || BN == 128, "nn_swz is defined for 128- and 256-byte k-rows");
+  static_assert(BM % (WM * 16) == 0 && BN % (WN * 16) == 0 && FN % 2 == 0, "wave tile: MFMA-aligned, an even number of column tiles");
+  static_assert(NI_A % NW == 0 && NI_B % NW == 0, "every wave owns the same number of A and of B pieces (counted vmcnt)");
+  static_assert(NBUF >= 2 && LDS_BYTES <= 160 * 1024, "LDS budget");
+};
+
+// GemmArgs as the kernel reads it: Bt = the ROW-MAJOR B ([K][ldb]), ldb >= N its row stride; tail_tiles = 0, counters = nullptr.
+template <class CFG, int EPI>
+__global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g) {
+  prefetch_kernargs<sizeof(GemmArgs)>();
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int BM = CFG::BM, BN = CFG::BN, NBUF = CFG::NBUF;
+  constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB, "plain and two-pass slab epilogues");
+
+  __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
+
+  const int tid  = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave_m = wave / CFG::WN;
+  const int wave_n = wave % CFG::WN;
+
+  const TileCoord tc = map_block(g, BM, BN);
+
+  // ---- LDS-DMA source addressing ---------------------------------------------------------------
+  // A: the classic family's (2 GiB descriptor at the tile's first row, the K advance in the scalar offset).
+  // B: the descriptor starts at column n0 of row 0 and ENDS WITH THE MATRIX; the whole offset (k-row and chunk) is in the lane's
+  // register, which is what the range check sees: a chunk behind the last element reads as zeros.
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(g.A + (size_t)tc.m0 * g.lda), 0, 0x80000000u, 0x00020000);
+  const uint32_t b_bytes = (uint32_t)(((size_t)(g.K - 1) * g.ldb + (g.N - tc.n0)) * 2);   // (< 2 GiB: host check)
+  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)(g.Bt + tc.n0), 0, b_bytes, 0x00020000);
+  const uint32_t b_stage = (uint32_t)g.ldb * (uint32_t)(BK * 2);   // bytes between two stages of B
+
+  uint32_t voff[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    if (j < NJ_A) {
+      const int il = wave + j * NW;                     // piece of the A tile
+      const int r  = il * 8 + (lane >> 3);
+      const int rc = min(r, g.M - 1 - tc.m0);
+      const int chunk = (lane & 7) ^ (((il & 1) << 2) | (lane >> 4));   // slot (lane & 7) of row r holds chunk slot ^ ((r >> 1) & 7)
+      voff[j] = ((uint32_t)rc * (uint32_t)g.lda + (uint32_t)chunk * 8u) * 2u;
+    } else {
+      const int il = wave + (j - NJ_A) * NW;            // piece of the B tile: k-rows il * B_RPP ..
+      const int kr = il * CFG::B_RPP + lane / CFG::B_CH;
+      const int chunk = (lane % CFG::B_CH) ^ nn_swz<BN>(kr);
+      voff[j] = ((uint32_t)(tc.k_begin + kr) * (uint32_t)g.ldb + (uint32_t)chunk * 8u) * 2u;
+    }
+  }
+
+  // ---- fragment read offsets (bytes inside a stage) ---------------------------------------------
+  int a_off[2];
+  {
+    const int lr = lane & 15, lq = lane >> 4, sw = (lr >> 1) & 7;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) a_off[ks] = wave_m * CFG::TM * ROW_BYTES + lr * ROW_BYTES + (((ks * 4 + lq) ^ sw) << 4);
+  }
+  // transposed reads: lane 4q + p of 16-lane group gq addresses k-row 8 gq + 4 h + q (h = 0, 1: the two reads), columns 4p .. 4p + 3
+  // of column tile jn -- 16-byte chunk 2 (tile) + (p >> 1), its half p & 1.  (+ ks * 32 rows per K = 32 slice: nn_swz does not see it.)
+  int b_off[2][FN];
+  {
+    const int gq = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int kr = 8 * gq + 4 * h + q;
+#pragma unroll
+      for (int jn = 0; jn < FN; ++jn) {
+        const int chunk = (wave_n * CFG::TN + jn * 16) / 8 + (p >> 1);
+        b_off[h][jn] = CFG::A_BYTES + kr * CFG::B_ROW_BYTES + ((chunk ^ nn_swz<BN>(kr)) << 4) + 8 * (p & 1);
+      }
+    }
+  }
+
+  f32x4 acc[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
+
+  // ---- pipeline ----------------------------------------------------------------------------------
+  uint32_t kbyte = (uint32_t)tc.k_begin * 2u;
+  auto stage = [&](char* lds_stage) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      lds_void_t* dst = (lds_void_t*)(lds_stage + (wave + j * NW) * 1024);
+      if (j < NJ_A) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, voff[j], kbyte, 0, 0);
+      } else {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, voff[j], 0, 0, 0);
+        voff[j] += b_stage;
+      }
+    }
+    kbyte += ROW_BYTES;
+  };
+  const int nk = tc.nk;
+#pragma unroll
+  for (int s = 0; s < NBUF - 1; ++s)
+    if (s < nk) stage(smem + s * CFG::STAGE_BYTES);
+
+  using tr_t = __attribute__((ext_vector_type(4))) short;
+  typedef __attribute__((address_space(3))) tr_t lds_tr_t;
+  int rd = 0, wr = NBUF - 1;
+  for (int t = 0; t < nk; ++t) {
+    if (t + NBUF - 2 < nk)
+      wait_vmcnt<NJ*(NBUF - 2)>();
+    else
+      wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();   // all waves' pieces of stage t landed; stage `wr` is free again
+
+    if (t + NBUF - 1 < nk) stage(smem + wr * CFG::STAGE_BYTES);
+
+    const char* st = smem + rd * CFG::STAGE_BYTES;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      f16x8 af[FM], bf[FN];
+#pragma unroll
+      for (int i = 0; i < FM; ++i) af[i] = *(const f16x8*)(st + i * 16 * ROW_BYTES + a_off[ks]);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const char* pb = st + ks * 32 * CFG::B_ROW_BYTES;
+        const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[0][j])));
+        const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[1][j])));
+        bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
+    }
+    rd = (rd + 1 == NBUF) ? 0 : rd + 1;
+    wr = (wr + 1 == NBUF) ? 0 : wr + 1;
+  }
+
+  if constexpr (EPI == EPI_SLAB) {
+    store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
+  } else {
+    // fp16 C, the 16-byte form of store_tile_row alone (the host sends the kernel N % 8 == 0, ldc % 8 == 0 and a 16-byte aligned
+    // C): v_permlane16_swap exchanges the odd 16-lane rows of column tile j with the even rows of tile j + 1, after which row
+    // q = lane >> 4 owns n = 16 (j + (q & 1)) + 8 (q >> 1) + 0 .. 7 of its C row.  Buffer stores: the non-temporal form is an
+    // instruction of its own (two plain C++ stores that differ only in the hint are merged by the optimiser and the hint is lost);
+    // the tile's bytes are below 2 GiB from its first row (host check).
+    using h2 = __attribute__((ext_vector_type(2))) _Float16;
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
+    const int q = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      __builtin_amdgcn_sched_barrier(0);   // one fragment row's accumulator reads at a time (store_tile)
+      const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < FN; j += 2) {
+        const h2 a01 = {(f16)acc[i][j][0], (f16)acc[i][j][1]}, a23 = {(f16)acc[i][j][2], (f16)acc[i][j][3]};
+        const h2 b01 = {(f16)acc[i][j + 1][0], (f16)acc[i][j + 1][1]}, b23 = {(f16)acc[i][j + 1][2], (f16)acc[i][j + 1][3]};
+        const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, b01), false, false);
+        const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, b23), false, false);
+        const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);
+        if (tc.m0 + row < g.M && n < g.N) {
+          const u32x4 o = {r0[0], r1[0], r0[1], r1[1]};
+          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
+          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 2);
+          else                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 0);
+        }
+      }
+    }
+  }
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
+// ---- host side: the family's own small table (the geometry table of hgemm_configs*.def does not know it) ------------------
+template <class CFG>
+void launch_nn(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB)
+    HGEMM_LAUNCH((hgemm_nn_kernel<CFG, EPI_SLAB>), grid, CFG::THREADS, stream, ts, g);
+  else
+    HGEMM_LAUNCH((hgemm_nn_kernel<CFG, EPI_C16>), grid, CFG::THREADS, stream, ts, g);
+}
+
+struct NNEntry {
+  const char* name;
+  int bm, bn, wm, wn, nbuf, threads, lds_bytes;
+  void (*launch)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+};
+extern const NNEntry g_nn_table[];
+extern const int g_num_nn;
+
+}  // namespace hgemm_mi355x

@@ -16,6 +16,11 @@
 //                                                     back-to-back launches for S seconds (no sync in between); reports
 //                                                     us per call and the board's gfx clock / socket power sampled over
 //                                                     the timed region (rocm_smi gpu metrics, every 10 ms)
+//   hgemm_tune check --layout nn [--shapes ...]       family n (B row-major, hgemm_mi355x_launch_nn): every member x {plain, NT stores,
+//                                                     two-pass splits 2 / 5}, bit-exact as above
+//   hgemm_tune bench --layout nn --shapes ... [--autotune] [--out F.jsonl]
+//                                                     that check first, then per shape interleaved rounds of the planned NN call, the
+//                                                     reference kernel on the same operands, hipBLASLt _nn and the shipped TN plan
 //
 // This is the offline replacement for the reference's first-call in-process autotune variants
 // (h100 kernels that time several variants on first invocation): plans are
@@ -997,6 +1002,118 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
   return 0;
 }
 
+// ---- NN layout (family n, hgemm_kernel_nn.hpp): `check --layout nn`, `bench --layout nn` ------------------------------------------------
+// check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} bit-exact on 0/1 inputs with B ROW-MAJOR; the default
+// shapes hold one tile, ragged M / N, an 8-column sliver, 1 .. 7 K stages, a long K -- and three the kernel does not take
+// (K % 64, N % 8: the reference kernel answers).
+static int cmd_check_nn(std::vector<Shape> shapes) {
+  if (shapes.empty())
+    shapes = parse_shapes("64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
+                          "200_136_72,200_100_128,33_17_40");
+  int failures = 0, runs = 0;
+  const int nc = hgemm_mi355x_nn_num_configs();
+  for (const Shape& sh : shapes) {
+    const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
+    const size_t cn = (size_t)sh.M * sh.N;
+    std::vector<f16> truth(cn), got(cn), b_rm((size_t)sh.K * sh.N);
+    for (int m = 0; m < sh.M; ++m)
+      for (int n = 0; n < sh.N; ++n) {
+        int acc = 0;
+        for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
+        truth[(size_t)m * sh.N + n] = (f16)(float)acc;
+      }
+    for (int n = 0; n < sh.N; ++n)
+      for (int k = 0; k < sh.K; ++k) b_rm[(size_t)k * sh.N + n] = z.bt[(size_t)n * sh.K + k];
+    Buffers s;
+    HIP_OK(hipMalloc(&s.a, z.a.size() * 2));
+    HIP_OK(hipMalloc(&s.b, b_rm.size() * 2));
+    HIP_OK(hipMalloc(&s.c, cn * 2));
+    HIP_OK(hipMemcpy(s.a, z.a.data(), z.a.size() * 2, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(s.b, b_rm.data(), b_rm.size() * 2, hipMemcpyHostToDevice));
+    for (int c = 0; c < nc; ++c) {
+      const char* cname = hgemm_mi355x_nn_config_name(c);
+      const int own = hgemm_mi355x_nn_runs(c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N);
+      for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
+        HIP_OK(hipMemset(s.c, 0xff, cn * 2));  // NaN pattern: unwritten outputs are caught
+        const int st = hgemm_mi355x_launch_nn(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N, nullptr);
+        const hipError_t e = hipDeviceSynchronize();
+        ++runs;
+        if (st != HGEMM_OK || e != hipSuccess) {
+          printf("FAIL nn %d_%d_%d %s s=%d: status %d hip %d\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
+          ++failures;
+          if (e != hipSuccess) return 3;
+          continue;
+        }
+        HIP_OK(hipMemcpy(got.data(), s.c, cn * 2, hipMemcpyDeviceToHost));
+        size_t bad = 0;
+        for (size_t i = 0; i < cn; ++i)
+          if (memcmp(&got[i], &truth[i], 2) != 0) {
+            if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) printf("   bad m=%zu n=%zu got %g want %g\n", i / sh.N, i % sh.N, (float)got[i], (float)truth[i]);
+            ++bad;
+          }
+        if (bad) {
+          printf("FAIL nn %d_%d_%d %s s=%d%s: %zu/%zu elements differ from the exact result\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+                 (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn);
+          ++failures;
+        }
+      }
+      if (c == 0) printf("checked nn %d_%d_%d (%s)\n", sh.M, sh.N, sh.K, own ? "the NN kernels" : "outside their scope: the reference kernel");
+    }
+    free_set(s);
+    fflush(stdout);
+  }
+  printf("check-nn-configs:");
+  for (int c = 0; c < nc; ++c) printf(" %s", hgemm_mi355x_nn_config_name(c));
+  printf("\ncheck-nn-forms: 1 1|nt-store 2 5\n");
+  printf("check nn: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs)\n", runs, failures);
+  return failures ? 1 : 0;
+}
+
+// bench: the check first (no timing of a kernel that is wrong), then per shape ONE set of interleaved rounds (time_interleaved) of the
+// planned NN call, the reference kernel on the same operands (what a b-only call ran before the family), hipBLASLt heuristic / autotune
+// _nn, and -- context only -- the shipped TN plan on a pre-built b_col_major.  One JSON record per shape.
+static int cmd_bench_nn(const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
+  const int rc = cmd_check_nn({});
+  if (rc != 0) { fprintf(stderr, "bench --layout nn: the check failed, nothing is timed\n"); return rc; }
+  FILE* out = out_path ? fopen(out_path, "w") : stdout;
+  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  hgemm_hipblaslt_heuristic_init();
+  if (autotune) hgemm_hipblaslt_autotune_init();
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0));
+  HIP_OK(hipEventCreate(&e1));
+  for (const Shape& sh : shapes) {
+    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
+    std::vector<Buffers> sets(2);
+    for (size_t i = 0; i < sets.size(); ++i) alloc_set(sets[i], sh, 77 + i, true);
+    int cfg = 0, splits = 1;
+    hgemm_mi355x_nn_plan(sh.M, sh.N, sh.K, &cfg, &splits);
+    const int own = hgemm_mi355x_nn_runs(cfg, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N);
+    const bool have_at = autotune && hgemm_hipblaslt_autotune_find_best_nn(sh.M, sh.N, sh.K, 0) == HGEMM_OK;   // the search before any timing
+    std::vector<Contender> cs;
+    cs.push_back({"nn", [&](Buffers& b) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
+    cs.push_back({"generic", [&](Buffers& b) { return hgemm_mi355x_launch(HGEMM_CONFIG_GENERIC, 1, 1, b.a, b.b, nullptr, b.c, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N, nullptr); }});
+    cs.push_back({"heur_nn", [&](Buffers& b) { return hgemm_hipblaslt_heuristic_nn(b.a, b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
+    if (have_at) cs.push_back({"auto_nn", [&](Buffers& b) { return hgemm_hipblaslt_autotune_nn(b.a, b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
+    cs.push_back({"tn_shipped", [&](Buffers& b) { return hgemm_mi355x_fp32(b.a, nullptr, b.bt, b.c, sh.M, sh.N, sh.K, nullptr); }});
+    const int rounds = flops > 1.0e11 ? 5 : 15;   // (the reference kernel takes ~0.1 .. 0.5 s per call on the large shapes)
+    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
+    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"nn\", \"nn_config\": \"%s\", \"nn_splits\": %d, \"nn_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"",
+            sh.M, sh.N, sh.K, hgemm_mi355x_nn_config_name(cfg), splits, own, rounds);
+    for (const Contender& c : cs) {
+      const double us = c.iso_us();
+      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
+    }
+    fprintf(out, "}\n");
+    fflush(out);
+    for (auto& s : sets) free_set(s);
+  }
+  HIP_OK(hipEventDestroy(e0));
+  HIP_OK(hipEventDestroy(e1));
+  if (out != stdout) fclose(out);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1008,7 +1125,7 @@ int main(int argc, char** argv) {
   const char* cfg_name = nullptr;
   double keep = 2.5;
   int max_cand = 12, splits = 1, group = 0, reps = 20;
-  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false;
+  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -1016,6 +1133,11 @@ int main(int argc, char** argv) {
     else if (a == "--shape-file") { auto v = read_shape_file(next()); shapes.insert(shapes.end(), v.begin(), v.end()); }
     else if (a == "--out") out_path = next();
     else if (a == "--autotune") autotune = true;
+    else if (a == "--layout") {
+      const std::string l = next();
+      if (l != "nn" && l != "tn") { fprintf(stderr, "--layout takes nn or tn\n"); return 2; }
+      layout_nn = l == "nn";
+    }
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
     else if (a == "--streamk") g_streamk_too = true;
@@ -1069,6 +1191,15 @@ int main(int argc, char** argv) {
     void* pad = nullptr;
     HIP_OK(hipMalloc(&pad, g_pad_alloc_mib << 20));   // (kept until exit)
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
+  }
+  if (layout_nn) {   // family n: B row-major (hgemm_mi355x_launch_nn); the default shapes of the check are cmd_check_nn's
+    if (mode == "check") return cmd_check_nn(shapes);
+    if (mode == "bench") {
+      if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
+      return cmd_bench_nn(shapes, out_path, autotune);
+    }
+    fprintf(stderr, "--layout nn goes with check or bench\n");
+    return 2;
   }
   if (mode == "check") {
     if (shapes.empty())

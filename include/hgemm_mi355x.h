@@ -249,6 +249,51 @@ size_t hgemm_mi355x_plan_workspace_bytes(int config_id, int splits, int M, int N
 int hgemm_mi355x_reserve_workspace(int M, int N, int K, void* stream);
 int hgemm_mi355x_release_workspaces(void);
 
+/* ------------------------------------------------------------------------------------------
+ * NN layout: C = A x B with B ROW-MAJOR ([K][N], as the conventions above call `b`), for the caller whose B is an activation and
+ * has no pre-transposed copy to hand over.  Replaces what a b-only call of hgemm_mi355x_fp32 / _launch runs (the
+ * one-output-per-thread reference kernel, HGEMM_CONFIG_GENERIC) and is the counterpart of the vendor baselines' _nn entry points
+ * below (reference cublas/fp32/hgemm_cublas.cu:15-41, cublasGemmEx NN).  The kernels ("n" geometries, csrc/hgemm_kernel_nn.hpp) stage
+ * B tiles row-major into LDS and read the MFMA operand through the hardware's transposed LDS read; they have a small table of their
+ * own (ids 0 .. hgemm_mi355x_nn_num_configs() - 1, names n<BM>x<BN>_w<WM>x<WN>) that is separate from the geometry table above:
+ * hgemm_mi355x_num_configs, the config ids and what the b_col_major entry points do are unchanged by it.
+ * Scope of the kernels: K % 64 == 0, N % 8 == 0, lda / ldb / ldc multiples of 8, 16-byte aligned pointers, operands within 2 GiB of
+ * 32-bit tile offsets.  Any other call is answered by the reference kernel: HGEMM_OK, exact, slow (hgemm_mi355x_nn_runs tells).
+ *
+ * hgemm_mi355x_nn_fp32 / _nn_fp16: the planned calls (both accumulate in fp32, as above); contiguous operands.
+ * Replace cuda_l2_<dev>_fp32(a, b, b_col_major, c) (reference kernels/a100_F32F16F16F32/64_4096_64.cu:275-287) for a caller without
+ * b_col_major. */
+int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream);
+int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream);
+/* The explicit call (what hgemm_mi355x_launch is to the geometry table).
+ *   nn_config  index into the NN table
+ *   splits     split-K factor >= 1: the two-pass form (fp32 slabs [splits][M][N] + the combine kernel, added in split order:
+ *              deterministic); clamped to K / 64; degrades to 1 when no workspace is available.  HGEMM_PLAN_NT_STORE is honoured;
+ *              HGEMM_SPLITK_FUSED runs as the two-pass form and HGEMM_PLAN_STREAMK as the plain launch (the family has neither kernel)
+ * lda (>= K), ldb (>= N: the row stride of the ROW-MAJOR b) and ldc (>= N) are in elements; a smaller stride returns
+ * HGEMM_ERR_BAD_ARG, and so does an id outside the table.  Capturable on a stream like every entry point: a split plan needs its
+ * workspace beforehand (hgemm_mi355x_nn_reserve_workspace, or hgemm_mi355x_reserve_workspace, whose floor of 64 MiB covers
+ * splits x M x N x 4 bytes of most plans), otherwise the captured call runs unsplit. */
+int hgemm_mi355x_launch_nn(int nn_config, int splits, const void* a, const void* b, void* c,
+                           int M, int N, int K, int lda, int ldb, int ldc, void* stream);
+/* The NN table (replaces nothing in the reference: it has one kernel file per shape). */
+int hgemm_mi355x_nn_num_configs(void);
+const char* hgemm_mi355x_nn_config_name(int nn_config);
+int hgemm_mi355x_nn_config_by_name(const char* name);
+/* out[0..7] = BM, BN, WM, WN, MI, NBUF, threads, lds_bytes (as hgemm_mi355x_config_info) */
+int hgemm_mi355x_nn_config_info(int nn_config, int out[8]);
+/* The plan hgemm_mi355x_nn_fp32 / _nn_fp16 run: the largest member whose tile count fills the 256 CUs, otherwise the 64 x 64 member
+ * with two-pass splits so that tiles x splits reaches the chip (at most one per 64 of K, at most 32).  An analytic rule; nothing
+ * is tuned per shape yet. */
+int hgemm_mi355x_nn_plan(int M, int N, int K, int* nn_config, int* splits);
+/* 1 when hgemm_mi355x_launch_nn runs the NN kernel itself for these dimensions and strides (pointers taken as 16-byte aligned),
+ * 0 when the call falls back to the reference kernel or is refused. */
+int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc);
+/* Exactly what hgemm_mi355x_launch_nn asks for with this plan on contiguous operands: 256 KiB of counters + splits x M x N x 4 bytes
+ * (0: none); hgemm_mi355x_nn_reserve_workspace makes the stream's workspace hold the planned call's. */
+size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K);
+int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream);
+
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
 const char* hgemm_mi355x_version(void);
