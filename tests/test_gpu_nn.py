@@ -4,7 +4,9 @@ ds_read_b64_tr_b16 (hgemm_kernel_nn.hpp) -- through the C ABI against the CPU or
 Bar: 0/1 inputs BIT-EXACT AND UNMASKED, as tests/test_gpu_lu.py: every partial sum is an integer <= K <= 8192 < 2**24, exact in fp32
 in any order, then one round-to-nearest-even to fp16.  The expected value is oracle.truth_f32acc, above 2**24 multiply-adds
 oracle.truth_numpy (the same exact integer before the same rounding; tests/test_oracle.py pins the two together).
-N(0,1) inputs: oracle.relative_error <= 1e-3 against the CPU fp32 product, the project's REL_TOL."""
+N(0,1) inputs: oracle.relative_error <= 1e-3 against the CPU fp32 product, the project's REL_TOL.
+tests/test_gpu_nn_bars.py holds the family to the other families' bars with these fixtures and helpers: rounding on dyadic operands,
+special values, the reach edges executed, rasters of more than eight tile rows, the launch's workspace behaviour, misaligned pointers."""
 import ctypes
 
 import numpy as np

@@ -160,16 +160,11 @@ def ctypes_ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-@pytest.mark.parametrize("k,hot", [(512, 300), (552, 540)])
-def test_special_values_round_like_the_reference(g, k, hot):
-    """The epilogue's fp32 -> fp16 conversion and the non-finite / denormal paths, which 0/1 inputs (values <= 2047, exact in every
-    rounding mode) cannot see: the result must equal the reference's oracle expression (a.float() @ b.float()).half()
-    (zero_one_correctness_check.py:85-90) -- round-to-nearest-even incl. overflow to inf at 65520, ties to even at the bottom
-    of the denormal range, inf / NaN propagation (inf x 0, inf - inf), denormal operands and results -- for every kernel
-    family, both split-K forms (the slabs carry inf / NaN / denormals in fp32) and stream-K.  Every row's sum is exact in fp32
-    whatever the summation order.  Second case: K = 552 = 8 x 64 + 40 with the second hot column inside the K tail, so the
-    "ktail" variants of families q and r (and the classic family's padded last step) carry inf / NaN / denormals through their tails."""
-    m, n = 128, 192
+def special_value_operands(m, n, k, hot):
+    """(A, B) on the CPU for the special-value tests (this file's, and tests/test_gpu_nn_bars.py's of the NN layout): one row of A per
+    case -- the largest finite value, overflow to inf at 65520, inf x 0, inf - inf, NaN, denormal operands and results, ties at the
+    bottom of the denormal range and at 1 -- against three rows of ones in B (0, 1 and `hot`) and a row of 2^-10.  Every row's sum
+    is exact in fp32 whatever the summation order; the second 64-row band repeats the first."""
     a = torch.zeros((m, k), dtype=torch.half)
     b = torch.zeros((k, n), dtype=torch.half)
     b[0, :] = 1.0; b[1, :] = 1.0; b[hot, :] = 1.0
@@ -192,6 +187,21 @@ def test_special_values_round_like_the_reference(g, k, hot):
     a[13, 1] = 2048.0; a[13, hot] = 1.0                # 2049 -> 2048 (the first integer fp16 cannot hold)
     a[14, 0] = 60000.0; a[14, 1] = 60000.0             # finite operands, overflowing sum
     a[64:, :] = a[:64, :].clone()                      # the same rows in the second 64-row band of every tile
+    return a, b
+
+
+@pytest.mark.parametrize("k,hot", [(512, 300), (552, 540)])
+def test_special_values_round_like_the_reference(g, k, hot):
+    """The epilogue's fp32 -> fp16 conversion and the non-finite / denormal paths, which 0/1 inputs (values <= 2047, exact in every
+    rounding mode) cannot see: the result must equal the reference's oracle expression (a.float() @ b.float()).half()
+    (zero_one_correctness_check.py:85-90) -- round-to-nearest-even incl. overflow to inf at 65520, ties to even at the bottom
+    of the denormal range, inf / NaN propagation (inf x 0, inf - inf), denormal operands and results -- for every kernel
+    family, both split-K forms (the slabs carry inf / NaN / denormals in fp32) and stream-K.  Every row's sum is exact in fp32
+    whatever the summation order.  Second case: K = 552 = 8 x 64 + 40 with the second hot column inside the K tail, so the
+    "ktail" variants of families q and r (and the classic family's padded last step) carry inf / NaN / denormals through their tails."""
+    m, n = 128, 192
+    a, b = special_value_operands(m, n, k, hot)
+    inf = float("inf")
     truth = (a.float() @ b.float()).half()
     assert torch.isinf(truth[1]).all() and truth[2, 0] == 65504 and torch.isnan(truth[4, 5]) and truth[4, 0] == inf
     assert truth[8, 0] == 2.0 ** -24 and truth[9, 0] == 0 and truth[10, 0] == 2.0 ** -24 and truth[11, 0] == 1 and truth[13, 0] == 2048

@@ -186,6 +186,77 @@ def test_bad_strides_and_ids_are_refused(lib):
     assert lib.hgemm_mi355x_nn_fp32(null, null, null, m, n, k, null) == -1 and lib.hgemm_mi355x_nn_fp16(null, null, null, 0, n, k, null) == -1
 
 
+# ---- the 32-bit reach rule (nn_reach_ok), at its boundary ---------------------------------------------------------------------
+GIB = 1 << 30
+
+
+def reach_limit(rows, tail):
+    """The largest stride (a multiple of 8) with rows x ld x 2 + tail < 2 GiB."""
+    return (2 * GIB - tail - 1) // (2 * rows) // 8 * 8
+
+
+def test_the_reach_rule_at_its_boundary(lib):
+    """For every member and each of A, B and C: the largest stride at which the kernel still runs (bisection over
+    hgemm_mi355x_nn_runs, as tests/test_gpu_nn_bars.py finds the strides it executes) is the documented rule's -- A and C:
+    BM x ld x 2 + the row's bytes < 2 GiB; B: (K - 1) x ldb x 2 + N x 2 < 2 GiB -- and around it status and form are the rule's:
+    the kernel below, the reference kernel (status 0) from the edge on, for plain and split calls."""
+    from test_gpu_nn_bars import largest_nn_stride, reach_rule
+
+    for cid in range(len(MEMBERS)):
+        bm, bn = nn_info(lib, cid)[:2]
+        for m, n, k in ((bm + 8, bn + 8, 128), (bm, bn, 64), (2 * bm + 8, 3 * bn + 8, 1024)):
+            for side in range(3):
+                rows, tail = reach_rule(bm, m, n, k, side)
+                edge = reach_limit(rows, tail)
+                assert rows * edge * 2 + tail < 2 * GIB <= rows * (edge + 8) * 2 + tail
+                assert largest_nn_stride(lib, cid, m, n, k, side) == edge, (MEMBERS[cid], (m, n, k), "ABC"[side], edge)
+                for ld in (edge - 8, edge, edge + 8, edge + 16):
+                    lds = [k, n, n]
+                    lds[side] = ld
+                    for splits in (1, 2):
+                        st, form, slab, disp = resolve(lib, cid, splits, m, n, k, ld=tuple(lds))
+                        want = ("reference" if ld > edge else "splitk" if splits == 2 and k > 64 else "plain")
+                        assert (st, form) == (0, want), (MEMBERS[cid], (m, n, k), "ABC"[side], ld, splits, st, form)
+                        assert (slab > 0) == (want == "splitk") and disp[0][0] == (THUNK_GENERIC if want == "reference" else THUNK_ENTRY)
+
+
+def test_contiguous_b_past_2_gib_runs_the_reference_kernel(lib):
+    for cid in range(len(MEMBERS)):
+        bm = nn_info(lib, cid)[0]
+        # K = 128, contiguous: B spans 127 x N x 2 + N x 2 = 256 N bytes -- the last N below 2 GiB runs (where C's BM rows of N
+        # stay below 2 GiB as well: the 64-row members), 2 GiB exactly does not
+        for n, runs in ((8388600, int(bm == 64)), (8388608, 0), (8388616, 0)):
+            assert lib.hgemm_mi355x_nn_runs(cid, 64, n, 128, 128, n, n) == runs, (cid, n)
+            assert resolve(lib, cid, 1, 64, n, 128)[:2] == (0, "plain" if runs else "reference")
+        # a contiguous B of 2 GiB, 4 GiB and more
+        for n, k in ((16384, 65536), (65536, 16448), (32768, 65536), (1 << 20, 4096)):
+            assert n * k * 2 >= 2 * GIB
+            for splits in (1, 4):
+                st, form, slab, disp = resolve(lib, cid, splits, 64, n, k)
+                assert (st, form, slab) == (0, "reference", 0) and disp[0][0] == THUNK_GENERIC, (cid, n, k)
+            assert lib.hgemm_mi355x_nn_plan_workspace_bytes(cid, 4, 64, n, k) == 0
+
+
+def test_strides_near_2_31_do_not_overflow_the_resolver(lib):
+    """lda, ldb, ldc up to 2^31 - 8, alone and together, with one row and with many: status 0, the reference kernel, no slabs --
+    and a stride that would only pass if a product wrapped round 2^32 or 2^64 is not taken for a small one."""
+    top = (1 << 31) - 8
+    for cid in range(len(MEMBERS)):
+        bm, bn = nn_info(lib, cid)[:2]
+        for m, n, k in ((1, 8, 64), (200, 136, 128), (bm + 8, bn + 8, 8192)):
+            for lds in ((top, n, n), (k, top, n), (k, n, top), (top, top, top)):
+                for splits in (1, 4):
+                    st, form, slab, disp = resolve(lib, cid, splits, m, n, k, ld=lds)
+                    assert (st, form, slab) == (0, "reference", 0) and len(disp) == 1, (MEMBERS[cid], (m, n, k), lds, st, form)
+                assert lib.hgemm_mi355x_nn_runs(cid, m, n, k, *lds) == 0
+        # bm x ld x 2 = 2^32 (ld = 2^31 / bm) and (K - 1 + 1) x ldb x 2 = 2^32: a 32-bit product would wrap to 0
+        wrap = (1 << 31) // bm
+        assert lib.hgemm_mi355x_nn_runs(cid, bm + 8, bn, 128, wrap, bn, bn) == 0 and lib.hgemm_mi355x_nn_runs(cid, bm + 8, bn, 128, 128, bn, wrap) == 0
+        assert lib.hgemm_mi355x_nn_runs(cid, 64, bn, 128, 128, (1 << 31) // 128, bn) == 0
+        # M near 2^31 with small strides: the tile count and M x ld stay in 64 bits, and the kernel takes it (each tile is small)
+        assert resolve(lib, cid, 1, top, 8, 64)[:2] == (0, "plain")
+
+
 # ---- CPU replay of the B image --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cid", range(len(MEMBERS)))
 def test_b_image_dma_map_and_transposed_reads_meet_the_mfma_contract(lib, cid):

@@ -232,3 +232,64 @@ def test_dyadic_class_assertion_rejects_what_would_break_exactness():
         oracle.truth_exact(a1, b1)               # K = 8161
     with pytest.raises(AssertionError):
         oracle.dyadic_inputs(1, 1, 8161, rng)
+
+
+# ---- dyadic operands of the NN layout's rounding tests (tests/test_gpu_nn_bars.py), proved on the CPU ---------------------------
+@pytest.fixture(scope="module")
+def nn_rounding_cases():
+    """The very operands of tests/test_gpu_nn_bars.py's rounding tests (same seeds, shapes and K, the members read through the C
+    ABI, no GPU): per case the sub-block the GPU test runs, its truth, and the K cuts of every two-pass form run there."""
+    import ctypes
+
+    import build
+
+    lib = ctypes.CDLL(str(build.build_library()))
+    import test_gpu_nn_bars as B
+
+    infos = B.nn_infos(lib)
+    assert B.member_extent(infos) == (152, 152, [192, 256, 320, 8128]) and B.SEED == 601
+    sets = [(B.DyadicOperands(oracle, *B.member_extent(infos), B.SEED), B.member_cases(infos)),
+            (B.DyadicOperands(oracle, *B.planned_extent(), B.PLANNED_SEED), B.planned_cases())]
+    cases = [(*ops.sub(m, n, k), cuts) for ops, plan in sets for (m, n, k), cuts in sorted(plan.items())]
+    assert len(cases) == len(B.member_cases(infos)) + len(B.PLANNED) and any(cuts for *_, cuts in cases)
+    return cases
+
+
+def test_nn_dyadic_truth_is_the_same_in_every_fp32_summation_order(nn_rounding_cases):
+    """As test_dyadic_truth_is_the_same_in_every_fp32_summation_order, on the NN tests' operands: the exact truth equals the C
+    oracle's k-order fp32 accumulation, numpy's BLAS order, and the two-pass form's own order -- fp32 chunk sums added in split
+    order -- at every cut used, with no fp32 add ever rounding."""
+    for a, b, truth, cut_sets in nn_rounding_cases:
+        k = a.shape[1]
+        x = oracle.exact_product(a, b)
+        assert np.array_equal(oracle.truth_exact(a, b).view(np.uint16), truth.view(np.uint16))
+        assert np.array_equal(oracle.truth_numpy(a, b).view(np.uint16), truth.view(np.uint16))
+        if k <= 512:
+            assert np.array_equal(oracle.truth_f32acc(a, b).view(np.uint16), truth.view(np.uint16))
+        for cuts in cut_sets + [()]:
+            edges = [0, *cuts, k]
+            acc = np.zeros(truth.shape, dtype=np.float32)
+            for lo, hi in zip(edges, edges[1:]):
+                part = a[:, lo:hi].astype(np.float32) @ b[lo:hi].astype(np.float32)
+                assert np.array_equal(part.astype(np.float64), oracle.exact_product(a[:, lo:hi], b[lo:hi]))
+                acc += part
+            assert np.array_equal(acc.astype(np.float64), x) and np.array_equal(acc.astype(np.float16).view(np.uint16), truth.view(np.uint16))
+
+
+def test_nn_dyadic_operands_discriminate_in_every_16x16_block(nn_rounding_cases):
+    """Conditions on the inputs: in every case, every 16 x 16 block of C -- the partial blocks at the right and bottom edges
+    included -- holds an element that a truncating convert gets wrong, one that round-half-away gets wrong, and one that
+    fp16-held partials get wrong at each cut the two-pass forms make there."""
+    def every_block(differs):
+        mm, nn = -(-differs.shape[0] // 16) * 16, -(-differs.shape[1] // 16) * 16
+        padded = np.zeros((mm, nn), dtype=bool)
+        padded[:differs.shape[0], :differs.shape[1]] = differs
+        return padded.reshape(mm // 16, 16, nn // 16, 16).any(axis=(1, 3)).all()
+
+    for a, b, truth, cut_sets in nn_rounding_cases:
+        shape = (a.shape[0], b.shape[1], a.shape[1])
+        x = oracle.exact_product(a, b)
+        assert every_block(oracle.round_toward_zero(x) != truth), ("RTZ", shape)
+        assert every_block(oracle.round_half_away(x) != truth), ("half-away", shape)
+        for cuts in cut_sets:
+            assert every_block(oracle.fp16_partials(a, b, cuts) != truth), (cuts, shape)
