@@ -4,6 +4,7 @@
 // (benchmarking_utils.py:23-31), so a lean host path is part of the hot path.
 #include "hgemm_plan.hpp"
 #include "hgemm_kernel_nn.hpp"
+#include "hgemm_kernel_ta.hpp"
 #include "../../include/hgemm_mi355x.h"
 
 #include <algorithm>
@@ -511,22 +512,23 @@ LaunchPlan resolve_nn(int nn_config, int splits_arg, bool aligned, int M, int N,
 
 // Planner of the family: the largest member whose tiles fill the chip (ties: fewer padded elements, then the taller tile); otherwise
 // the 64 x 64 member with as many two-pass splits as bring tiles x splits up to the CU count -- at most one per K stage, at most 32.
-void nn_model_plan(int M, int N, int K, int* cfg, int* splits) {
+// (the rule of both transposed-read families: `table` is g_nn_table or g_ta_table)
+void nn_model_plan(const NNEntry* table, int count, int M, int N, int K, int* cfg, int* splits) {
   int best = -1;
   long best_area = 0, best_pad = 0;
-  for (int i = 0; i < g_num_nn; ++i) {
-    const NNEntry& e = g_nn_table[i];
+  for (int i = 0; i < count; ++i) {
+    const NNEntry& e = table[i];
     const long tm = (M + e.bm - 1) / e.bm, tn = (N + e.bn - 1) / e.bn, area = (long)e.bm * e.bn, pad = tm * e.bm * tn * e.bn;
     if (tm * tn < kCUs) continue;
-    if (best < 0 || area > best_area || (area == best_area && (pad < best_pad || (pad == best_pad && e.bm > g_nn_table[best].bm)))) {
+    if (best < 0 || area > best_area || (area == best_area && (pad < best_pad || (pad == best_pad && e.bm > table[best].bm)))) {
       best = i; best_area = area; best_pad = pad;
     }
   }
   if (best >= 0) { *cfg = best; *splits = 1; return; }
   int small = 0;
-  for (int i = 1; i < g_num_nn; ++i)
-    if (g_nn_table[i].bm * g_nn_table[i].bn < g_nn_table[small].bm * g_nn_table[small].bn) small = i;
-  const NNEntry& e = g_nn_table[small];
+  for (int i = 1; i < count; ++i)
+    if (table[i].bm * table[i].bn < table[small].bm * table[small].bn) small = i;
+  const NNEntry& e = table[small];
   const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
   *cfg = small;
   *splits = (int)std::max<long>(1, std::min<long>(std::min<long>((kCUs + tiles - 1) / tiles, K / BK), 32));
@@ -537,6 +539,69 @@ int run_nn(const void* a, const void* b, void* c, int M, int N, int K, void* str
   const int st = hgemm_mi355x_nn_plan(M, N, K, &cfg, &splits);
   if (st != HGEMM_OK) return st;
   return hgemm_mi355x_launch_nn(cfg, splits, a, b, c, M, N, K, K, N, N, stream);
+}
+
+// ---- TA layout (family a, hgemm_kernel_ta.hpp): A given as a_col_major [K][lda], B row-major [K][ldb] ---------------------------------
+// The NN block once more: a table of its own (g_ta_table, hgemm_inst_g6.hip), its own resolution, family n's planner rule on that table.
+bool ta_path_ok(const void* a, const void* b, const void* c, int M, int N, int K, int lda, int ldb, int ldc) {
+  if (K % BK != 0 || (M & 7) != 0 || (N & 7) != 0) return false;
+  if ((lda & 7) || (ldb & 7) || (ldc & 7)) return false;
+  return !(((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15));
+}
+// 32-bit offsets with bit 31 to spare: A and B from row 0 to the end of the matrix, C from a tile's first row
+bool ta_reach_ok(const NNEntry& e, int M, int N, int K, int lda, int ldb, int ldc) {
+  return (double)(K - 1) * lda * 2.0 + M * 2.0 < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 &&
+         (double)e.bm * ldc * 2.0 + N * 2.0 < 2147483648.0;
+}
+// (resolve_nn's shape; hgemm_mi355x_selfcheck_launch_ta shows it to the CPU tests)
+LaunchPlan resolve_ta(int ta_config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc, unsigned ruled_out) {
+  LaunchPlan p;
+  auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
+    if (p.n) p.d[p.n - 1].stop = false;
+    p.d[p.n] = Dispatch{thunk, g, (int)grid, epi, p.n == 0, true};
+    ++p.n;
+  };
+  // rows must not overlap: lda >= M (the row stride of a_col_major), ldb >= N (B is row-major), ldc >= N
+  if (ta_config < 0 || ta_config >= g_num_ta || lda < M || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
+  const NNEntry& e = g_ta_table[ta_config];
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
+  g.flags = (splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
+  g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
+  const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
+  if (!aligned || !ta_path_ok(nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !ta_reach_ok(e, M, N, K, lda, ldb, ldc) || tiles > 0x7fffffffL) {
+    p.form = FORM_REFERENCE;
+    add(THUNK_GENERIC, g, 0, EPI_C16);
+    return p;
+  }
+  g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (N + e.bn - 1) / e.bn;
+  g.group_m = std::min(g.tiles_m, 8);
+  // at most one split per stage, no empty split; the single-launch and stream-K words have no kernel here either: their split count
+  // runs as the two-pass form / the plain launch
+  const int steps = K / BK;
+  int splits = (splits_arg & HGEMM_PLAN_STREAMK) ? 1 : std::max(1, std::min(splits_arg & HGEMM_SPLITK_MASK, steps));
+  if ((ruled_out & (1u << FORM_SPLITK)) || tiles * splits > 0x7fffffffL) splits = 1;
+  const int per = (steps + splits - 1) / splits;
+  splits = (steps + per - 1) / per;
+  g.k_chunk = per * BK; g.splits = splits; g.items = (int)(tiles * splits);
+  set_raster_div(g);
+  if (splits > 1) {
+    p.form = FORM_SPLITK;
+    p.slab_bytes = (size_t)splits * M * N * sizeof(float);
+    add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
+    add(THUNK_SPLITK_REDUCE, g, 0, EPI_SLAB);
+  } else {
+    add(THUNK_ENTRY, g, tiles, EPI_C16);
+  }
+  return p;
+}
+
+int run_ta(const void* at, const void* b, void* c, int M, int N, int K, void* stream) {
+  int cfg, splits;
+  const int st = hgemm_mi355x_ta_plan(M, N, K, &cfg, &splits);
+  if (st != HGEMM_OK) return st;
+  return hgemm_mi355x_launch_ta(cfg, splits, at, b, c, M, N, K, M, N, N, stream);
 }
 
 }  // namespace
@@ -812,7 +877,7 @@ int hgemm_mi355x_nn_config_info(int id, int out[8]) {
 
 int hgemm_mi355x_nn_plan(int M, int N, int K, int* nn_config, int* splits) {
   if (M <= 0 || N <= 0 || K <= 0 || !nn_config || !splits) return HGEMM_ERR_BAD_ARG;
-  nn_model_plan(M, N, K, nn_config, splits);
+  nn_model_plan(g_nn_table, g_num_nn, M, N, K, nn_config, splits);
   return HGEMM_OK;
 }
 
@@ -831,7 +896,7 @@ size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, in
 int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   int cfg = 0, splits = 1;
-  nn_model_plan(M, N, K, &cfg, &splits);
+  nn_model_plan(g_nn_table, g_num_nn, M, N, K, &cfg, &splits);
   const size_t ws = hgemm_mi355x_nn_plan_workspace_bytes(cfg, splits, M, N, K);
   if (!ws) return HGEMM_OK;
   float* slabs = nullptr; unsigned* counters = nullptr;
@@ -879,6 +944,109 @@ int hgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const v
 
 int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return run_nn(a, b, c, M, N, K, stream); }
 int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return run_nn(a, b, c, M, N, K, stream); }
+
+// ---- TA layout ------------------------------------------------------------------------------------------------------------------
+int hgemm_mi355x_ta_num_configs(void) { return g_num_ta; }
+
+const char* hgemm_mi355x_ta_config_name(int id) { return (id >= 0 && id < g_num_ta) ? g_ta_table[id].name : nullptr; }
+
+int hgemm_mi355x_ta_config_by_name(const char* name) {
+  if (!name) return -1;
+  for (int i = 0; i < g_num_ta; ++i)
+    if (std::strcmp(name, g_ta_table[i].name) == 0) return i;
+  return -1;
+}
+
+int hgemm_mi355x_ta_config_info(int id, int out[8]) {
+  if (id < 0 || id >= g_num_ta || !out) return HGEMM_ERR_BAD_ARG;
+  const NNEntry& e = g_ta_table[id];
+  out[0] = e.bm; out[1] = e.bn; out[2] = e.wm; out[3] = e.wn; out[4] = 16; out[5] = e.nbuf; out[6] = e.threads; out[7] = e.lds_bytes;
+  return HGEMM_OK;
+}
+
+int hgemm_mi355x_ta_plan(int M, int N, int K, int* ta_config, int* splits) {
+  if (M <= 0 || N <= 0 || K <= 0 || !ta_config || !splits) return HGEMM_ERR_BAD_ARG;
+  nn_model_plan(g_ta_table, g_num_ta, M, N, K, ta_config, splits);
+  return HGEMM_OK;
+}
+
+int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const LaunchPlan p = resolve_ta(ta_config, 1, true, M, N, K, lda, ldb, ldc, 0);
+  return p.status == HGEMM_OK && p.form != FORM_REFERENCE ? 1 : 0;
+}
+
+size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const LaunchPlan p = resolve_ta(ta_config, splits, true, M, N, K, M, N, N, 0);
+  return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
+}
+
+int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  int cfg = 0, splits = 1;
+  nn_model_plan(g_ta_table, g_num_ta, M, N, K, &cfg, &splits);
+  const size_t ws = hgemm_mi355x_ta_plan_workspace_bytes(cfg, splits, M, N, K);
+  if (!ws) return HGEMM_OK;
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  const int rc = ensure_workspace(ws - kCounterBytes, (hipStream_t)stream, &slabs, &counters);
+  return rc == HGEMM_ERR_NO_WORKSPACE_INTERNAL ? HGEMM_ERR_NO_WORKSPACE : rc;
+}
+
+int hgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
+                           int ldb, int ldc, void* stream) {
+  struct DisarmTiming {  // the timing hook is one-shot whatever path (or error return) this call takes
+    ~DisarmTiming() { hgemm_mi355x::t_launch_timing = hgemm_mi355x::LaunchTiming{}; }
+  } disarm_timing;
+  if (!a_col_major || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool aligned = ta_path_ok(a_col_major, b, c, M, N, K, lda, ldb, ldc);
+  unsigned ruled_out = 0;
+  LaunchPlan p = resolve_ta(ta_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
+  if (p.status == HGEMM_OK && p.slab_bytes) {
+    const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
+    if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
+      ruled_out |= 1u << FORM_SPLITK;
+      p = resolve_ta(ta_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+    } else if (st != HGEMM_OK) {
+      return st;
+    }
+  }
+  if (p.status != HGEMM_OK) return p.status;
+  for (int i = 0; i < p.n; ++i) {
+    GemmArgs& g = p.d[i].g;
+    g.A = (const f16*)a_col_major; g.Bt = (const f16*)b; g.C = (f16*)c;   // (family a reads GemmArgs::A as [K][lda], Bt as the row-major B)
+    if (p.d[i].epi != EPI_C16) g.partial = slabs;
+    const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
+    switch (p.d[i].thunk) {
+      case THUNK_ENTRY: g_ta_table[ta_config].launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
+      case THUNK_SPLITK_REDUCE: launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts); break;
+      default: launch_generic_ta((const f16*)a_col_major, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts); break;
+    }
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
+}
+
+int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return run_ta(a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return run_ta(a_col_major, b, c, M, N, K, stream); }
+
+// what hgemm_mi355x_launch_ta decides for a call, nothing launched (hgemm_mi355x_selfcheck_launch_nn's contract and layout of `out`)
+int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                     long long out[20]) {
+  if (M <= 0 || N <= 0 || K <= 0 || !out) return HGEMM_ERR_BAD_ARG;
+  const LaunchPlan p = resolve_ta(ta_config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out);
+  out[0] = p.form; out[1] = p.n; out[2] = (long long)p.slab_bytes; out[3] = p.counters;
+  for (int i = 0; i < p.n; ++i) {
+    const Dispatch& d = p.d[i];
+    const long long v[8] = {d.thunk, d.grid, d.epi, d.g.splits, d.g.k_chunk, d.g.items, d.start, d.stop};
+    std::copy(v, v + 8, out + 4 + 8 * i);
+  }
+  return p.status;
+}
 
 // what hgemm_mi355x_launch_nn decides for a call, nothing launched (the twin of hgemm_mi355x_selfcheck_launch; not part of the public
 // header): operands = 4 when the pointers are 16-byte aligned, ruled_out = 1 << form of the two-pass form that got no workspace.

@@ -66,8 +66,9 @@ __global__ void __launch_bounds__(256) fill_normal_f16_kernel(f16* out, size_t n
 // ---------------------------------------------------------------------------------------------
 rocblas_handle g_rocblas = nullptr;
 
+// ta: A is a_col_major ([K][M]), the column-major product's second operand transposed with ld = M (b then row-major, tn = false)
 int rocblas_run(bool tn, const void* a, const void* b, void* c, int M, int N, int K, int acc,
-                void* stream) {
+                void* stream, bool ta = false) {
   if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   if (!g_rocblas) {
     int st = hgemm_rocblas_init();
@@ -82,8 +83,8 @@ int rocblas_run(bool tn, const void* a, const void* b, void* c, int M, int N, in
   const void* beta  = h ? (const void*)&beta16 : (const void*)&beta32;
   const rocblas_datatype ct = h ? rocblas_datatype_f16_r : rocblas_datatype_f32_r;
   rocblas_status rs = rocblas_gemm_ex(
-      g_rocblas, tn ? rocblas_operation_transpose : rocblas_operation_none, rocblas_operation_none,
-      N, M, K, alpha, b, rocblas_datatype_f16_r, tn ? K : N, a, rocblas_datatype_f16_r, K, beta, c,
+      g_rocblas, tn ? rocblas_operation_transpose : rocblas_operation_none, ta ? rocblas_operation_transpose : rocblas_operation_none,
+      N, M, K, alpha, b, rocblas_datatype_f16_r, tn ? K : N, a, rocblas_datatype_f16_r, ta ? M : K, beta, c,
       rocblas_datatype_f16_r, N, c, rocblas_datatype_f16_r, N, ct, rocblas_gemm_algo_standard, 0, 0);
   return rs == rocblas_status_success ? HGEMM_OK : HGEMM_ERR_BACKEND;
 }
@@ -508,6 +509,9 @@ int hgemm_rocblas_nn(const void* a, const void* b, void* c, int M, int N, int K,
 }
 int hgemm_rocblas_tn(const void* a, const void* bt, void* c, int M, int N, int K, int acc, void* stream) {
   return rocblas_run(true, a, bt, c, M, N, K, acc, stream);
+}
+int hgemm_rocblas_ta(const void* at, const void* b, void* c, int M, int N, int K, int acc, void* stream) {
+  return rocblas_run(false, at, b, c, M, N, K, acc, stream, true);
 }
 
 int hgemm_hipblaslt_heuristic_init(void) { return lt_init(g_heur); }

@@ -1,6 +1,7 @@
 // Kernel registry (config id -> launch thunk) and the two helper kernels' launchers.
 #include "hgemm_launch.hpp"
 #include "hgemm_kernel_rg.hpp"
+#include "hgemm_kernel_ta.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -168,6 +169,21 @@ __global__ void __launch_bounds__(256) hgemm_generic_kernel(const f16* __restric
   }
 }
 
+// The same net for the TA layout (hgemm_kernel_ta.hpp): A given as a_col_major, read as A[k * lda + m].  Same sum order, so the
+// same bits as hgemm_generic_kernel on the transposed operand.
+__global__ void __launch_bounds__(256) hgemm_generic_ta_kernel(const f16* __restrict__ At,
+                                                               const f16* __restrict__ B,
+                                                               f16* __restrict__ C, int M, int N, int K,
+                                                               int lda_colmajor, int ldb_rowmajor, int ldc) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    C[(size_t)m * ldc + n] = (f16)s;
+  }
+}
+
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
   const size_t quads = ((size_t)M * N) >> 2;
@@ -210,6 +226,12 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
                     int ldc, hipStream_t stream, TimingSlot ts) {
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
   HGEMM_LAUNCH(hgemm_generic_kernel, grid, 256, stream, ts, A, B, C, M, N, K, lda, ldb, ldc);
+}
+
+void launch_generic_ta(const f16* a_col_major, const f16* B, f16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
+                       TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH(hgemm_generic_ta_kernel, grid, 256, stream, ts, a_col_major, B, C, M, N, K, lda, ldb, ldc);
 }
 
 }  // namespace hgemm_mi355x

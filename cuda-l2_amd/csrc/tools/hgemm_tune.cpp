@@ -18,6 +18,10 @@
 //                                                     the timed region (rocm_smi gpu metrics, every 10 ms)
 //   hgemm_tune check --layout nn [--shapes ...]       family n (B row-major, hgemm_mi355x_launch_nn): every member x {plain, NT stores,
 //                                                     two-pass splits 2 / 5}, bit-exact as above
+//   hgemm_tune check --layout ta [--shapes ...]       family a (A given as [K][M], hgemm_mi355x_launch_ta): the same check
+//   hgemm_tune bench --layout ta --shapes ... [--out F.jsonl]
+//                                                     that check first, then per shape interleaved rounds of the planned TA call, the
+//                                                     NN call on a pre-transposed A, a copy of A's bytes + that NN call, rocBLAS
 //   hgemm_tune bench --layout nn --shapes ... [--autotune] [--out F.jsonl]
 //                                                     that check first, then per shape interleaved rounds of the planned NN call, the
 //                                                     reference kernel on the same operands, hipBLASLt _nn and the shipped TN plan
@@ -1006,12 +1010,18 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
 // check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} bit-exact on 0/1 inputs with B ROW-MAJOR; the default
 // shapes hold one tile, ragged M / N, an 8-column sliver, 1 .. 7 K stages, a long K -- and three the kernel does not take
 // (K % 64, N % 8: the reference kernel answers).
-static int cmd_check_nn(std::vector<Shape> shapes) {
+// `ta`: the same check of family a (hgemm_kernel_ta.hpp) -- A handed over as a_col_major [K][M], lda = M; the default shapes add
+// M % 8 != 0 to what the kernel does not take and an 8-row sliver to what it does.
+static int cmd_check_nn(std::vector<Shape> shapes, bool ta = false) {
   if (shapes.empty())
-    shapes = parse_shapes("64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
-                          "200_136_72,200_100_128,33_17_40");
+    shapes = parse_shapes(ta ? "64_64_64,8_8_64,72_72_128,200_264_192,136_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
+                               "200_136_72,200_100_128,100_136_128,33_17_40"
+                             : "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
+                               "200_136_72,200_100_128,33_17_40");
   int failures = 0, runs = 0;
-  const int nc = hgemm_mi355x_nn_num_configs();
+  const char* lay = ta ? "ta" : "nn";
+  const int nc = ta ? hgemm_mi355x_ta_num_configs() : hgemm_mi355x_nn_num_configs();
+  auto config_name = [&](int c) { return ta ? hgemm_mi355x_ta_config_name(c) : hgemm_mi355x_nn_config_name(c); };
   for (const Shape& sh : shapes) {
     const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
     const size_t cn = (size_t)sh.M * sh.N;
@@ -1028,18 +1038,26 @@ static int cmd_check_nn(std::vector<Shape> shapes) {
     HIP_OK(hipMalloc(&s.a, z.a.size() * 2));
     HIP_OK(hipMalloc(&s.b, b_rm.size() * 2));
     HIP_OK(hipMalloc(&s.c, cn * 2));
-    HIP_OK(hipMemcpy(s.a, z.a.data(), z.a.size() * 2, hipMemcpyHostToDevice));
+    if (ta) {   // a_col_major[k][m] = a[m][k]
+      std::vector<f16> a_cm(z.a.size());
+      for (int m = 0; m < sh.M; ++m)
+        for (int k = 0; k < sh.K; ++k) a_cm[(size_t)k * sh.M + m] = z.a[(size_t)m * sh.K + k];
+      HIP_OK(hipMemcpy(s.a, a_cm.data(), a_cm.size() * 2, hipMemcpyHostToDevice));
+    } else {
+      HIP_OK(hipMemcpy(s.a, z.a.data(), z.a.size() * 2, hipMemcpyHostToDevice));
+    }
     HIP_OK(hipMemcpy(s.b, b_rm.data(), b_rm.size() * 2, hipMemcpyHostToDevice));
     for (int c = 0; c < nc; ++c) {
-      const char* cname = hgemm_mi355x_nn_config_name(c);
-      const int own = hgemm_mi355x_nn_runs(c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N);
+      const char* cname = config_name(c);
+      const int own = ta ? hgemm_mi355x_ta_runs(c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N) : hgemm_mi355x_nn_runs(c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
         HIP_OK(hipMemset(s.c, 0xff, cn * 2));  // NaN pattern: unwritten outputs are caught
-        const int st = hgemm_mi355x_launch_nn(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N, nullptr);
+        const int st = ta ? hgemm_mi355x_launch_ta(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N, nullptr)
+                          : hgemm_mi355x_launch_nn(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N, nullptr);
         const hipError_t e = hipDeviceSynchronize();
         ++runs;
         if (st != HGEMM_OK || e != hipSuccess) {
-          printf("FAIL nn %d_%d_%d %s s=%d: status %d hip %d\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
+          printf("FAIL %s %d_%d_%d %s s=%d: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
           ++failures;
           if (e != hipSuccess) return 3;
           continue;
@@ -1052,20 +1070,20 @@ static int cmd_check_nn(std::vector<Shape> shapes) {
             ++bad;
           }
         if (bad) {
-          printf("FAIL nn %d_%d_%d %s s=%d%s: %zu/%zu elements differ from the exact result\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+          printf("FAIL %s %d_%d_%d %s s=%d%s: %zu/%zu elements differ from the exact result\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
                  (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn);
           ++failures;
         }
       }
-      if (c == 0) printf("checked nn %d_%d_%d (%s)\n", sh.M, sh.N, sh.K, own ? "the NN kernels" : "outside their scope: the reference kernel");
+      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? (ta ? "the TA kernels" : "the NN kernels") : "outside their scope: the reference kernel");
     }
     free_set(s);
     fflush(stdout);
   }
-  printf("check-nn-configs:");
-  for (int c = 0; c < nc; ++c) printf(" %s", hgemm_mi355x_nn_config_name(c));
-  printf("\ncheck-nn-forms: 1 1|nt-store 2 5\n");
-  printf("check nn: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs)\n", runs, failures);
+  printf("check-%s-configs:", lay);
+  for (int c = 0; c < nc; ++c) printf(" %s", config_name(c));
+  printf("\ncheck-%s-forms: 1 1|nt-store 2 5\n", lay);
+  printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs)\n", lay, runs, failures);
   return failures ? 1 : 0;
 }
 
@@ -1114,6 +1132,59 @@ static int cmd_bench_nn(const std::vector<Shape>& shapes, const char* out_path, 
   return 0;
 }
 
+// bench --layout ta: the check first, then per shape ONE set of interleaved rounds of the planned TA call on a_col_major, the planned
+// NN call on a pre-transposed (row-major) A -- context: what the product costs when the transpose is free --, a device-to-device copy
+// of A's bytes followed by that NN call -- no transpose pass can beat a copy, so a lower bound of what a caller without the TA entry
+// points pays --, and rocBLAS on the TA operands.  One JSON record per shape.
+static int cmd_bench_ta(const std::vector<Shape>& shapes, const char* out_path) {
+  const int rc = cmd_check_nn({}, true);
+  if (rc != 0) { fprintf(stderr, "bench --layout ta: the check failed, nothing is timed\n"); return rc; }
+  FILE* out = out_path ? fopen(out_path, "w") : stdout;
+  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0));
+  HIP_OK(hipEventCreate(&e1));
+  for (const Shape& sh : shapes) {
+    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
+    const size_t a_elems = (size_t)sh.M * sh.K;
+    std::vector<Buffers> sets(2);
+    std::vector<f16*> at(sets.size(), nullptr), tmp(sets.size(), nullptr);   // a_col_major and the copy's destination, per set
+    for (size_t i = 0; i < sets.size(); ++i) {
+      alloc_set(sets[i], sh, 91 + i, true);
+      HIP_OK(hipMalloc(&at[i], a_elems * 2));
+      HIP_OK(hipMalloc(&tmp[i], a_elems * 2));
+      transpose_kernel<<<(unsigned)((a_elems + 255) / 256), 256>>>(sets[i].a, at[i], sh.M, sh.K);   // at[k][m] = a[m][k]
+    }
+    HIP_OK(hipDeviceSynchronize());
+    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
+    int cfg = 0, splits = 1;
+    hgemm_mi355x_ta_plan(sh.M, sh.N, sh.K, &cfg, &splits);
+    const int own = hgemm_mi355x_ta_runs(cfg, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N);
+    std::vector<Contender> cs;
+    cs.push_back({"ta", [&](Buffers& b) { return hgemm_mi355x_ta_fp32(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
+    cs.push_back({"nn_pretransposed", [&](Buffers& b) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
+    cs.push_back({"copy_nn", [&](Buffers& b) {
+                    if (hipMemcpyAsync(tmp[idx(b)], b.a, a_elems * 2, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) return (int)HGEMM_ERR_HIP;
+                    return hgemm_mi355x_nn_fp32(tmp[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
+    cs.push_back({"rocblas_ta", [&](Buffers& b) { return hgemm_rocblas_ta(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
+    const int rounds = 15;
+    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
+    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"ta\", \"ta_config\": \"%s\", \"ta_splits\": %d, \"ta_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"",
+            sh.M, sh.N, sh.K, hgemm_mi355x_ta_config_name(cfg), splits, own, rounds);
+    for (const Contender& c : cs) {
+      const double us = c.iso_us();
+      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
+    }
+    fprintf(out, "}\n");
+    fflush(out);
+    for (size_t i = 0; i < sets.size(); ++i) { free_set(sets[i]); HIP_OK(hipFree(at[i])); HIP_OK(hipFree(tmp[i])); }
+  }
+  HIP_OK(hipEventDestroy(e0));
+  HIP_OK(hipEventDestroy(e1));
+  if (out != stdout) fclose(out);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1125,7 +1196,7 @@ int main(int argc, char** argv) {
   const char* cfg_name = nullptr;
   double keep = 2.5;
   int max_cand = 12, splits = 1, group = 0, reps = 20;
-  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false;
+  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false, layout_ta = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -1135,8 +1206,8 @@ int main(int argc, char** argv) {
     else if (a == "--autotune") autotune = true;
     else if (a == "--layout") {
       const std::string l = next();
-      if (l != "nn" && l != "tn") { fprintf(stderr, "--layout takes nn or tn\n"); return 2; }
-      layout_nn = l == "nn";
+      if (l != "nn" && l != "tn" && l != "ta") { fprintf(stderr, "--layout takes nn, ta or tn\n"); return 2; }
+      layout_nn = l == "nn"; layout_ta = l == "ta";
     }
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
@@ -1191,6 +1262,15 @@ int main(int argc, char** argv) {
     void* pad = nullptr;
     HIP_OK(hipMalloc(&pad, g_pad_alloc_mib << 20));   // (kept until exit)
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
+  }
+  if (layout_ta) {   // family a: A given as [K][M] (hgemm_mi355x_launch_ta)
+    if (mode == "check") return cmd_check_nn(shapes, true);
+    if (mode == "bench") {
+      if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
+      return cmd_bench_ta(shapes, out_path);
+    }
+    fprintf(stderr, "--layout ta goes with check or bench\n");
+    return 2;
   }
   if (layout_nn) {   // family n: B row-major (hgemm_mi355x_launch_nn); the default shapes of the check are cmd_check_nn's
     if (mode == "check") return cmd_check_nn(shapes);

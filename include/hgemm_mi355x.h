@@ -294,6 +294,44 @@ int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, i
 size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K);
 int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * TA layout (transposed A): C = A x B with A given as a_col_major ([K][M]: M contiguous) and B ROW-MAJOR ([K][N]) -- a linear
+ * layer's weight gradient dW = X^T x dY, where the first operand is the activation as it is stored, [tokens][features].  With the
+ * b_col_major entry points (forward) and the NN layout (input gradient) it completes the layer's three products.  The vendor
+ * libraries call this form "nt"; NT means non-temporal stores throughout this library, hence "ta".  Replaces a transposed copy of A
+ * (2 x M x K bytes read and written) in front of hgemm_mi355x_nn_fp32; the vendor counterpart is hgemm_rocblas_ta below.  The kernels
+ * ("a" geometries, csrc/hgemm_kernel_ta.hpp) stage both operands as they lie in memory and read both MFMA operands through the
+ * hardware's transposed LDS read; their table (ids 0 .. hgemm_mi355x_ta_num_configs() - 1, names a<BM>x<BN>_w<WM>x<WN>) is separate
+ * from the geometry table and the NN table, which are unchanged by it.
+ * Scope of the kernels: K % 64 == 0, M % 8 == 0, N % 8 == 0, lda / ldb / ldc multiples of 8, 16-byte aligned pointers, and 32-bit
+ * offsets with bit 31 to spare: ((K - 1) x lda + M) x 2, ((K - 1) x ldb + N) x 2 and (BM x ldc + N) x 2 bytes each below 2 GiB.  Any
+ * other call is answered by a one-output-per-thread reference kernel: HGEMM_OK, exact, slow (hgemm_mi355x_ta_runs tells).
+ *
+ * hgemm_mi355x_ta_fp32 / _ta_fp16: the planned calls (both accumulate in fp32); contiguous operands (lda = M, ldb = ldc = N).
+ * Replace torch.matmul(x.t(), dy) / cublasGemmEx with the first operand transposed for a caller of the reference's entry points. */
+int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream);
+int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream);
+/* The explicit call (what hgemm_mi355x_launch_nn is to the NN table).
+ *   ta_config  index into the TA table
+ *   splits     as hgemm_mi355x_launch_nn: the two-pass form, clamped to K / 64, 1 when no workspace is available; HGEMM_PLAN_NT_STORE is
+ *              honoured, HGEMM_SPLITK_FUSED runs as the two-pass form and HGEMM_PLAN_STREAMK as the plain launch
+ * lda (>= M: the row stride of a_col_major), ldb (>= N) and ldc (>= N) are in elements; a smaller stride returns HGEMM_ERR_BAD_ARG,
+ * and so does an id outside the table.  Capturable like every entry point: a split plan needs its workspace beforehand
+ * (hgemm_mi355x_ta_reserve_workspace), otherwise the captured call runs unsplit. */
+int hgemm_mi355x_launch_ta(int ta_config, int splits, const void* a_col_major, const void* b, void* c,
+                           int M, int N, int K, int lda, int ldb, int ldc, void* stream);
+/* The TA table (replaces nothing in the reference: it has one kernel file per shape), with the NN functions' contracts. */
+int hgemm_mi355x_ta_num_configs(void);
+const char* hgemm_mi355x_ta_config_name(int ta_config);
+int hgemm_mi355x_ta_config_by_name(const char* name);
+int hgemm_mi355x_ta_config_info(int ta_config, int out[8]);
+/* hgemm_mi355x_nn_plan's rule on the TA table: the largest member whose tile count fills the 256 CUs, otherwise the 64 x 64 member
+ * with min(ceil(256 / tiles), K / 64, 32) two-pass splits. */
+int hgemm_mi355x_ta_plan(int M, int N, int K, int* ta_config, int* splits);
+int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
+size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, int N, int K);
+int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream);
+
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
 const char* hgemm_mi355x_version(void);
@@ -307,6 +345,8 @@ int hgemm_rocblas_init(void);      /* init_cublas_handle    (hgemm_cublas.cu:15-
 int hgemm_rocblas_destroy(void);   /* destroy_cublas_handle (hgemm_cublas.cu:30-38) */
 int hgemm_rocblas_nn(const void* a, const void* b, void* c, int M, int N, int K, int acc, void* stream);
 int hgemm_rocblas_tn(const void* a, const void* b_col_major, void* c, int M, int N, int K, int acc, void* stream);
+/* the TA layout (a_col_major [K][M], b row-major): the same rocblas_gemm_ex with its second operand transposed, ld = M */
+int hgemm_rocblas_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, int acc, void* stream);
 
 /* hipBLASLt heuristic  <-  cublasLtMatmulAlgoGetHeuristic top-1 of 4, cached
  * (reference cublas/fp32/hgemm_cublaslt_heuristic.cu:65-217). */
