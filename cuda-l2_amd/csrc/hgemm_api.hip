@@ -153,6 +153,20 @@ struct LaunchPlan {
   bool counters = false;   // the form uses the arrival counters
   Dispatch d[3];
 };
+// the selfcheck hooks' view of a plan: out = {form, dispatches, slab bytes, counters}, then per dispatch {thunk, grid, epi, splits,
+// k_chunk, items, start, stop}; returns the plan's status
+int show_plan(const LaunchPlan& p, long long* out) {
+  out[0] = p.form; out[1] = p.n; out[2] = (long long)p.slab_bytes; out[3] = p.counters;
+  for (int i = 0; i < p.n; ++i) {
+    const Dispatch& d = p.d[i];
+    const long long v[8] = {d.thunk, d.grid, d.epi, d.g.splits, d.g.k_chunk, d.g.items, d.start, d.stop};
+    std::copy(v, v + 8, out + 4 + 8 * i);
+  }
+  return p.status;
+}
+struct DisarmTiming {  // the timing hook is one-shot whatever path (or error return) a launch call takes
+  ~DisarmTiming() { hgemm_mi355x::t_launch_timing = hgemm_mi355x::LaunchTiming{}; }
+};
 constexpr struct { int plan, arg; } kArgFlags[] = {   // plan flags -> GemmArgs::flags
     {HGEMM_PLAN_NT_STORE, ARG_NT_STORE}, {HGEMM_PLAN_RS_XCD_STAGGER, ARG_XCD_STAGGER}, {HGEMM_PLAN_RS_NT_LOADS, ARG_NT_LOADS},
     {HGEMM_PLAN_PHASE_OFFSET, ARG_PHASE_OFFSET}, {HGEMM_PLAN_WAVE_PRIORITY, ARG_WAVE_PRIORITY}, {HGEMM_PLAN_PHASE_OFFSET4, ARG_PHASE_OFFSET4}};
@@ -452,38 +466,57 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 }
 
 
-// ---- NN layout (family n, hgemm_kernel_nn.hpp): B row-major [K][ldb] ----------------------------------------------------------------
-// The family has its own table (g_nn_table, hgemm_inst_g5.hip) and its own resolution; the geometry table, hgemm_mi355x_plan and what
-// a b-only call of hgemm_mi355x_launch does know nothing of it.
-// the kernel's scope; everything else is answered by the reference kernel (status 0, exact)
-bool nn_path_ok(const void* a, const void* b, const void* c, int N, int K, int lda, int ldb, int ldc) {
-  if (K % BK != 0 || (N & 7) != 0) return false;
-  if ((lda & 7) || (ldb & 7) || (ldc & 7)) return false;
-  return !(((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15));
-}
-// 32-bit tile offsets with bit 31 to spare: A and C from a tile's first row, B from row 0 to the end of the matrix
-bool nn_reach_ok(const NNEntry& e, int N, int K, int lda, int ldb, int ldc) {
-  return (double)e.bm * lda * 2.0 + K * 2.0 < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 &&
-         (double)e.bm * ldc * 2.0 + N * 2.0 < 2147483648.0;
-}
-// (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn shows it to the CPU tests)
-LaunchPlan resolve_nn(int nn_config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc, unsigned ruled_out) {
+// ---- the transposed-read layouts: NN (family n, hgemm_kernel_nn.hpp: B row-major [K][ldb]) and TA (family a, hgemm_kernel_ta.hpp: A given
+// as a_col_major [K][lda] as well) ------------------------------------------------------------------------------------------------------
+// Each family has its own table (g_nn_table: hgemm_inst_g5.hip, g_ta_table: hgemm_inst_g6.hip); the geometry table, hgemm_mi355x_plan and
+// what a b-only call of hgemm_mi355x_launch does know nothing of them.  A layout is described once, here; resolution, launch, planner and
+// the queries below are written once and take the description.
+struct TrLayout {
+  const NNEntry* table;
+  const int& count;
+  // How A lies in memory decides every rule in which the two layouts differ.  false (n): [M][lda], rows of K elements, staged and
+  // addressed from a tile's first row.  true (a): [K][lda], k-rows of M elements, staged as B is and addressed from row 0 to the end
+  // of the matrix; a chunk of a k-row must not straddle M, so M % 8 == 0 joins the scope.
+  bool a_col_major;
+  // the reference kernel of the layout (status 0, exact): answers whatever is outside the kernels' scope or reach
+  void (*reference)(const f16*, const f16*, f16*, int, int, int, int, int, int, hipStream_t, TimingSlot);
+
+  // elements in a row of A: the least lda, and the lda of a contiguous A (the planned calls pass strides (a_row, N, N))
+  int a_row(int M, int K) const { return a_col_major ? M : K; }
+  // the kernels' scope; everything else is answered by the reference kernel
+  bool path_ok(const void* a, const void* b, const void* c, int M, int N, int K, int lda, int ldb, int ldc) const {
+    if (K % BK != 0 || (N & 7) != 0 || (a_col_major && (M & 7) != 0)) return false;
+    if ((lda & 7) || (ldb & 7) || (ldc & 7)) return false;
+    return !(((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15));
+  }
+  // 32-bit offsets with bit 31 to spare: B from row 0 to the end of the matrix, C from a tile's first row, A as a_col_major says
+  bool reach_ok(const NNEntry& e, int M, int N, int K, int lda, int ldb, int ldc) const {
+    const double a_bytes = a_col_major ? (double)(K - 1) * lda * 2.0 + M * 2.0 : (double)e.bm * lda * 2.0 + K * 2.0;
+    return a_bytes < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 && (double)e.bm * ldc * 2.0 + N * 2.0 < 2147483648.0;
+  }
+};
+const TrLayout kLayoutNN{g_nn_table, g_num_nn, false, launch_generic};
+const TrLayout kLayoutTA{g_ta_table, g_num_ta, true, launch_generic_ta};
+
+// (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn / _ta show it to the CPU tests)
+LaunchPlan tr_resolve(const TrLayout& L, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
+                      unsigned ruled_out) {
   LaunchPlan p;
   auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
     if (p.n) p.d[p.n - 1].stop = false;
     p.d[p.n] = Dispatch{thunk, g, (int)grid, epi, p.n == 0, true};
     ++p.n;
   };
-  // rows must not overlap: lda >= K, ldb >= N (B is row-major here), ldc >= N
-  if (nn_config < 0 || nn_config >= g_num_nn || lda < K || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
-  const NNEntry& e = g_nn_table[nn_config];
+  // rows must not overlap: lda >= K (n) / >= M, the row stride of a_col_major (a); ldb >= N (B is row-major here), ldc >= N
+  if (config < 0 || config >= L.count || lda < L.a_row(M, K) || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
+  const NNEntry& e = L.table[config];
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
   g.flags = (splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
   g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
   const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
-  if (!aligned || !nn_path_ok(nullptr, nullptr, nullptr, N, K, lda, ldb, ldc) || !nn_reach_ok(e, N, K, lda, ldb, ldc) || tiles > 0x7fffffffL) {
+  if (!aligned || !L.path_ok(nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !L.reach_ok(e, M, N, K, lda, ldb, ldc) || tiles > 0x7fffffffL) {
     p.form = FORM_REFERENCE;
     add(THUNK_GENERIC, g, 0, EPI_C16);
     return p;
@@ -510,13 +543,13 @@ LaunchPlan resolve_nn(int nn_config, int splits_arg, bool aligned, int M, int N,
   return p;
 }
 
-// Planner of the family: the largest member whose tiles fill the chip (ties: fewer padded elements, then the taller tile); otherwise
+// Planner of both families: the largest member whose tiles fill the chip (ties: fewer padded elements, then the taller tile); otherwise
 // the 64 x 64 member with as many two-pass splits as bring tiles x splits up to the CU count -- at most one per K stage, at most 32.
-// (the rule of both transposed-read families: `table` is g_nn_table or g_ta_table)
-void nn_model_plan(const NNEntry* table, int count, int M, int N, int K, int* cfg, int* splits) {
+void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits) {
+  const NNEntry* table = L.table;
   int best = -1;
   long best_area = 0, best_pad = 0;
-  for (int i = 0; i < count; ++i) {
+  for (int i = 0; i < L.count; ++i) {
     const NNEntry& e = table[i];
     const long tm = (M + e.bm - 1) / e.bm, tn = (N + e.bn - 1) / e.bn, area = (long)e.bm * e.bn, pad = tm * e.bm * tn * e.bn;
     if (tm * tn < kCUs) continue;
@@ -526,7 +559,7 @@ void nn_model_plan(const NNEntry* table, int count, int M, int N, int K, int* cf
   }
   if (best >= 0) { *cfg = best; *splits = 1; return; }
   int small = 0;
-  for (int i = 1; i < count; ++i)
+  for (int i = 1; i < L.count; ++i)
     if (table[i].bm * table[i].bn < table[small].bm * table[small].bn) small = i;
   const NNEntry& e = table[small];
   const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
@@ -534,74 +567,104 @@ void nn_model_plan(const NNEntry* table, int count, int M, int N, int K, int* cf
   *splits = (int)std::max<long>(1, std::min<long>(std::min<long>((kCUs + tiles - 1) / tiles, K / BK), 32));
 }
 
-int run_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
-  int cfg, splits;
-  const int st = hgemm_mi355x_nn_plan(M, N, K, &cfg, &splits);
-  if (st != HGEMM_OK) return st;
-  return hgemm_mi355x_launch_nn(cfg, splits, a, b, c, M, N, K, K, N, N, stream);
+// GemmArgs as the kernels read it: A = a (n: [M][lda], a: [K][lda]), Bt = the row-major B
+int tr_launch(const TrLayout& L, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
+              int ldc, void* stream) {
+  DisarmTiming disarm_timing;
+  if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const bool aligned = L.path_ok(a, b, c, M, N, K, lda, ldb, ldc);
+  unsigned ruled_out = 0;
+  LaunchPlan p = tr_resolve(L, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
+  if (p.status == HGEMM_OK && p.slab_bytes) {
+    const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
+    if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
+      ruled_out |= 1u << FORM_SPLITK;
+      p = tr_resolve(L, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+    } else if (st != HGEMM_OK) {
+      return st;
+    }
+  }
+  if (p.status != HGEMM_OK) return p.status;
+  for (int i = 0; i < p.n; ++i) {
+    GemmArgs& g = p.d[i].g;
+    g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;
+    if (p.d[i].epi != EPI_C16) g.partial = slabs;
+    const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
+    switch (p.d[i].thunk) {
+      case THUNK_ENTRY: L.table[config].launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
+      case THUNK_SPLITK_REDUCE: launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts); break;
+      default: L.reference((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts); break;
+    }
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
 }
 
-// ---- TA layout (family a, hgemm_kernel_ta.hpp): A given as a_col_major [K][lda], B row-major [K][ldb] ---------------------------------
-// The NN block once more: a table of its own (g_ta_table, hgemm_inst_g6.hip), its own resolution, family n's planner rule on that table.
-bool ta_path_ok(const void* a, const void* b, const void* c, int M, int N, int K, int lda, int ldb, int ldc) {
-  if (K % BK != 0 || (M & 7) != 0 || (N & 7) != 0) return false;
-  if ((lda & 7) || (ldb & 7) || (ldc & 7)) return false;
-  return !(((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15));
-}
-// 32-bit offsets with bit 31 to spare: A and B from row 0 to the end of the matrix, C from a tile's first row
-bool ta_reach_ok(const NNEntry& e, int M, int N, int K, int lda, int ldb, int ldc) {
-  return (double)(K - 1) * lda * 2.0 + M * 2.0 < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 &&
-         (double)e.bm * ldc * 2.0 + N * 2.0 < 2147483648.0;
-}
-// (resolve_nn's shape; hgemm_mi355x_selfcheck_launch_ta shows it to the CPU tests)
-LaunchPlan resolve_ta(int ta_config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc, unsigned ruled_out) {
-  LaunchPlan p;
-  auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
-    if (p.n) p.d[p.n - 1].stop = false;
-    p.d[p.n] = Dispatch{thunk, g, (int)grid, epi, p.n == 0, true};
-    ++p.n;
-  };
-  // rows must not overlap: lda >= M (the row stride of a_col_major), ldb >= N (B is row-major), ldc >= N
-  if (ta_config < 0 || ta_config >= g_num_ta || lda < M || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
-  const NNEntry& e = g_ta_table[ta_config];
-  GemmArgs g{};
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
-  g.flags = (splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
-  g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
-  const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
-  if (!aligned || !ta_path_ok(nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !ta_reach_ok(e, M, N, K, lda, ldb, ldc) || tiles > 0x7fffffffL) {
-    p.form = FORM_REFERENCE;
-    add(THUNK_GENERIC, g, 0, EPI_C16);
-    return p;
-  }
-  g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (N + e.bn - 1) / e.bn;
-  g.group_m = std::min(g.tiles_m, 8);
-  // at most one split per stage, no empty split; the single-launch and stream-K words have no kernel here either: their split count
-  // runs as the two-pass form / the plain launch
-  const int steps = K / BK;
-  int splits = (splits_arg & HGEMM_PLAN_STREAMK) ? 1 : std::max(1, std::min(splits_arg & HGEMM_SPLITK_MASK, steps));
-  if ((ruled_out & (1u << FORM_SPLITK)) || tiles * splits > 0x7fffffffL) splits = 1;
-  const int per = (steps + splits - 1) / splits;
-  splits = (steps + per - 1) / per;
-  g.k_chunk = per * BK; g.splits = splits; g.items = (int)(tiles * splits);
-  set_raster_div(g);
-  if (splits > 1) {
-    p.form = FORM_SPLITK;
-    p.slab_bytes = (size_t)splits * M * N * sizeof(float);
-    add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
-    add(THUNK_SPLITK_REDUCE, g, 0, EPI_SLAB);
-  } else {
-    add(THUNK_ENTRY, g, tiles, EPI_C16);
-  }
-  return p;
+// the planned call on contiguous operands
+int tr_run(const TrLayout& L, const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  int cfg, splits;
+  tr_model_plan(L, M, N, K, &cfg, &splits);
+  return tr_launch(L, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), N, N, stream);
 }
 
-int run_ta(const void* at, const void* b, void* c, int M, int N, int K, void* stream) {
-  int cfg, splits;
-  const int st = hgemm_mi355x_ta_plan(M, N, K, &cfg, &splits);
-  if (st != HGEMM_OK) return st;
-  return hgemm_mi355x_launch_ta(cfg, splits, at, b, c, M, N, K, M, N, N, stream);
+const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.count) ? L.table[id].name : nullptr; }
+
+int tr_config_by_name(const TrLayout& L, const char* name) {
+  if (!name) return -1;
+  for (int i = 0; i < L.count; ++i)
+    if (std::strcmp(name, L.table[i].name) == 0) return i;
+  return -1;
+}
+
+int tr_config_info(const TrLayout& L, int id, int out[8]) {
+  if (id < 0 || id >= L.count || !out) return HGEMM_ERR_BAD_ARG;
+  const NNEntry& e = L.table[id];
+  out[0] = e.bm; out[1] = e.bn; out[2] = e.wm; out[3] = e.wn; out[4] = 16; out[5] = e.nbuf; out[6] = e.threads; out[7] = e.lds_bytes;
+  return HGEMM_OK;
+}
+
+int tr_plan(const TrLayout& L, int M, int N, int K, int* config, int* splits) {
+  if (M <= 0 || N <= 0 || K <= 0 || !config || !splits) return HGEMM_ERR_BAD_ARG;
+  tr_model_plan(L, M, N, K, config, splits);
+  return HGEMM_OK;
+}
+
+int tr_runs(const TrLayout& L, int config, int M, int N, int K, int lda, int ldb, int ldc) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const LaunchPlan p = tr_resolve(L, config, 1, true, M, N, K, lda, ldb, ldc, 0);
+  return p.status == HGEMM_OK && p.form != FORM_REFERENCE ? 1 : 0;
+}
+
+size_t tr_plan_workspace_bytes(const TrLayout& L, int config, int splits, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const LaunchPlan p = tr_resolve(L, config, splits, true, M, N, K, L.a_row(M, K), N, N, 0);
+  return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
+}
+
+int tr_reserve_workspace(const TrLayout& L, int M, int N, int K, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  int cfg = 0, splits = 1;
+  tr_model_plan(L, M, N, K, &cfg, &splits);
+  const size_t ws = tr_plan_workspace_bytes(L, cfg, splits, M, N, K);
+  if (!ws) return HGEMM_OK;
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  const int rc = ensure_workspace(ws - kCounterBytes, (hipStream_t)stream, &slabs, &counters);
+  return rc == HGEMM_ERR_NO_WORKSPACE_INTERNAL ? HGEMM_ERR_NO_WORKSPACE : rc;
+}
+
+// what tr_launch decides for a call, nothing launched (the twin of hgemm_mi355x_selfcheck_launch; not part of the public header):
+// operands = 4 when the pointers are 16-byte aligned, ruled_out = 1 << form of the two-pass form that got no workspace.  Returns the
+// call's status; out = {form, dispatches, slab bytes, counters (0)}, then per dispatch {thunk, grid, epi, splits, k_chunk, items,
+// start, stop}.
+int tr_selfcheck_launch(const TrLayout& L, int config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc,
+                        int ruled_out, long long out[20]) {
+  if (M <= 0 || N <= 0 || K <= 0 || !out) return HGEMM_ERR_BAD_ARG;
+  return show_plan(tr_resolve(L, config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out), out);
 }
 
 }  // namespace
@@ -769,9 +832,7 @@ int hgemm_mi355x_reserve_workspace(int M, int N, int K, void* stream) {
 int hgemm_mi355x_launch(int config_id, int splits_arg, int group_m, const void* a, const void* b,
                         const void* b_col_major, void* c, int M, int N, int K, int lda, int ldb,
                         int ldc, void* stream) {
-  struct DisarmTiming {  // the timing hook is one-shot whatever path (or error return) this call takes
-    ~DisarmTiming() { hgemm_mi355x::t_launch_timing = hgemm_mi355x::LaunchTiming{}; }
-  } disarm_timing;
+  DisarmTiming disarm_timing;
   if (!a || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   if (config_id >= g_num_kernels || config_id < HGEMM_CONFIG_RAGGED) return HGEMM_ERR_BAD_ARG;
 #ifdef HGEMM_TIMELINE
@@ -856,213 +917,47 @@ int hgemm_mi355x_fp16(const void* a, const void* b, const void* bt, void* c, int
   return run(HGEMM_ACC_FP16, a, b, bt, c, M, N, K, stream);
 }
 
-// ---- NN layout ------------------------------------------------------------------------------------------------------------------
+// ---- NN layout (kLayoutNN) and TA layout (kLayoutTA): forwards to the one host path of the transposed-read layouts ---------------------
 int hgemm_mi355x_nn_num_configs(void) { return g_num_nn; }
-
-const char* hgemm_mi355x_nn_config_name(int id) { return (id >= 0 && id < g_num_nn) ? g_nn_table[id].name : nullptr; }
-
-int hgemm_mi355x_nn_config_by_name(const char* name) {
-  if (!name) return -1;
-  for (int i = 0; i < g_num_nn; ++i)
-    if (std::strcmp(name, g_nn_table[i].name) == 0) return i;
-  return -1;
-}
-
-int hgemm_mi355x_nn_config_info(int id, int out[8]) {
-  if (id < 0 || id >= g_num_nn || !out) return HGEMM_ERR_BAD_ARG;
-  const NNEntry& e = g_nn_table[id];
-  out[0] = e.bm; out[1] = e.bn; out[2] = e.wm; out[3] = e.wn; out[4] = 16; out[5] = e.nbuf; out[6] = e.threads; out[7] = e.lds_bytes;
-  return HGEMM_OK;
-}
-
-int hgemm_mi355x_nn_plan(int M, int N, int K, int* nn_config, int* splits) {
-  if (M <= 0 || N <= 0 || K <= 0 || !nn_config || !splits) return HGEMM_ERR_BAD_ARG;
-  nn_model_plan(g_nn_table, g_num_nn, M, N, K, nn_config, splits);
-  return HGEMM_OK;
-}
-
-int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = resolve_nn(nn_config, 1, true, M, N, K, lda, ldb, ldc, 0);
-  return p.status == HGEMM_OK && p.form != FORM_REFERENCE ? 1 : 0;
-}
-
+const char* hgemm_mi355x_nn_config_name(int id) { return tr_config_name(kLayoutNN, id); }
+int hgemm_mi355x_nn_config_by_name(const char* name) { return tr_config_by_name(kLayoutNN, name); }
+int hgemm_mi355x_nn_config_info(int id, int out[8]) { return tr_config_info(kLayoutNN, id, out); }
+int hgemm_mi355x_nn_plan(int M, int N, int K, int* nn_config, int* splits) { return tr_plan(kLayoutNN, M, N, K, nn_config, splits); }
+int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, nn_config, M, N, K, lda, ldb, ldc); }
 size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = resolve_nn(nn_config, splits, true, M, N, K, K, N, N, 0);
-  return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
+  return tr_plan_workspace_bytes(kLayoutNN, nn_config, splits, M, N, K);
 }
-
-int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
-  int cfg = 0, splits = 1;
-  nn_model_plan(g_nn_table, g_num_nn, M, N, K, &cfg, &splits);
-  const size_t ws = hgemm_mi355x_nn_plan_workspace_bytes(cfg, splits, M, N, K);
-  if (!ws) return HGEMM_OK;
-  float* slabs = nullptr; unsigned* counters = nullptr;
-  const int rc = ensure_workspace(ws - kCounterBytes, (hipStream_t)stream, &slabs, &counters);
-  return rc == HGEMM_ERR_NO_WORKSPACE_INTERNAL ? HGEMM_ERR_NO_WORKSPACE : rc;
-}
-
+int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutNN, M, N, K, stream); }
 int hgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
                            int ldc, void* stream) {
-  struct DisarmTiming {  // the timing hook is one-shot whatever path (or error return) this call takes
-    ~DisarmTiming() { hgemm_mi355x::t_launch_timing = hgemm_mi355x::LaunchTiming{}; }
-  } disarm_timing;
-  if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool aligned = nn_path_ok(a, b, c, N, K, lda, ldb, ldc);
-  unsigned ruled_out = 0;
-  LaunchPlan p = resolve_nn(nn_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
-  float* slabs = nullptr; unsigned* counters = nullptr;
-  // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
-  if (p.status == HGEMM_OK && p.slab_bytes) {
-    const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
-    if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
-      ruled_out |= 1u << FORM_SPLITK;
-      p = resolve_nn(nn_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
-    } else if (st != HGEMM_OK) {
-      return st;
-    }
-  }
-  if (p.status != HGEMM_OK) return p.status;
-  for (int i = 0; i < p.n; ++i) {
-    GemmArgs& g = p.d[i].g;
-    g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (family n reads GemmArgs::Bt as the row-major B)
-    if (p.d[i].epi != EPI_C16) g.partial = slabs;
-    const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
-    switch (p.d[i].thunk) {
-      case THUNK_ENTRY: g_nn_table[nn_config].launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
-      case THUNK_SPLITK_REDUCE: launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts); break;
-      default: launch_generic((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts); break;
-    }
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
-  return HGEMM_OK;
+  return tr_launch(kLayoutNN, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
 }
-
-int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return run_nn(a, b, c, M, N, K, stream); }
-int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return run_nn(a, b, c, M, N, K, stream); }
-
-// ---- TA layout ------------------------------------------------------------------------------------------------------------------
-int hgemm_mi355x_ta_num_configs(void) { return g_num_ta; }
-
-const char* hgemm_mi355x_ta_config_name(int id) { return (id >= 0 && id < g_num_ta) ? g_ta_table[id].name : nullptr; }
-
-int hgemm_mi355x_ta_config_by_name(const char* name) {
-  if (!name) return -1;
-  for (int i = 0; i < g_num_ta; ++i)
-    if (std::strcmp(name, g_ta_table[i].name) == 0) return i;
-  return -1;
-}
-
-int hgemm_mi355x_ta_config_info(int id, int out[8]) {
-  if (id < 0 || id >= g_num_ta || !out) return HGEMM_ERR_BAD_ARG;
-  const NNEntry& e = g_ta_table[id];
-  out[0] = e.bm; out[1] = e.bn; out[2] = e.wm; out[3] = e.wn; out[4] = 16; out[5] = e.nbuf; out[6] = e.threads; out[7] = e.lds_bytes;
-  return HGEMM_OK;
-}
-
-int hgemm_mi355x_ta_plan(int M, int N, int K, int* ta_config, int* splits) {
-  if (M <= 0 || N <= 0 || K <= 0 || !ta_config || !splits) return HGEMM_ERR_BAD_ARG;
-  nn_model_plan(g_ta_table, g_num_ta, M, N, K, ta_config, splits);
-  return HGEMM_OK;
-}
-
-int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = resolve_ta(ta_config, 1, true, M, N, K, lda, ldb, ldc, 0);
-  return p.status == HGEMM_OK && p.form != FORM_REFERENCE ? 1 : 0;
-}
-
-size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = resolve_ta(ta_config, splits, true, M, N, K, M, N, N, 0);
-  return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
-}
-
-int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream) {
-  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
-  int cfg = 0, splits = 1;
-  nn_model_plan(g_ta_table, g_num_ta, M, N, K, &cfg, &splits);
-  const size_t ws = hgemm_mi355x_ta_plan_workspace_bytes(cfg, splits, M, N, K);
-  if (!ws) return HGEMM_OK;
-  float* slabs = nullptr; unsigned* counters = nullptr;
-  const int rc = ensure_workspace(ws - kCounterBytes, (hipStream_t)stream, &slabs, &counters);
-  return rc == HGEMM_ERR_NO_WORKSPACE_INTERNAL ? HGEMM_ERR_NO_WORKSPACE : rc;
-}
-
-int hgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
-                           int ldb, int ldc, void* stream) {
-  struct DisarmTiming {  // the timing hook is one-shot whatever path (or error return) this call takes
-    ~DisarmTiming() { hgemm_mi355x::t_launch_timing = hgemm_mi355x::LaunchTiming{}; }
-  } disarm_timing;
-  if (!a_col_major || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  const bool aligned = ta_path_ok(a_col_major, b, c, M, N, K, lda, ldb, ldc);
-  unsigned ruled_out = 0;
-  LaunchPlan p = resolve_ta(ta_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
-  float* slabs = nullptr; unsigned* counters = nullptr;
-  // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
-  if (p.status == HGEMM_OK && p.slab_bytes) {
-    const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
-    if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
-      ruled_out |= 1u << FORM_SPLITK;
-      p = resolve_ta(ta_config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
-    } else if (st != HGEMM_OK) {
-      return st;
-    }
-  }
-  if (p.status != HGEMM_OK) return p.status;
-  for (int i = 0; i < p.n; ++i) {
-    GemmArgs& g = p.d[i].g;
-    g.A = (const f16*)a_col_major; g.Bt = (const f16*)b; g.C = (f16*)c;   // (family a reads GemmArgs::A as [K][lda], Bt as the row-major B)
-    if (p.d[i].epi != EPI_C16) g.partial = slabs;
-    const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
-    switch (p.d[i].thunk) {
-      case THUNK_ENTRY: g_ta_table[ta_config].launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
-      case THUNK_SPLITK_REDUCE: launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts); break;
-      default: launch_generic_ta((const f16*)a_col_major, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts); break;
-    }
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
-  return HGEMM_OK;
-}
-
-int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return run_ta(a_col_major, b, c, M, N, K, stream); }
-int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return run_ta(a_col_major, b, c, M, N, K, stream); }
-
-// what hgemm_mi355x_launch_ta decides for a call, nothing launched (hgemm_mi355x_selfcheck_launch_nn's contract and layout of `out`)
-int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
-                                     long long out[20]) {
-  if (M <= 0 || N <= 0 || K <= 0 || !out) return HGEMM_ERR_BAD_ARG;
-  const LaunchPlan p = resolve_ta(ta_config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out);
-  out[0] = p.form; out[1] = p.n; out[2] = (long long)p.slab_bytes; out[3] = p.counters;
-  for (int i = 0; i < p.n; ++i) {
-    const Dispatch& d = p.d[i];
-    const long long v[8] = {d.thunk, d.grid, d.epi, d.g.splits, d.g.k_chunk, d.g.items, d.start, d.stop};
-    std::copy(v, v + 8, out + 4 + 8 * i);
-  }
-  return p.status;
-}
-
-// what hgemm_mi355x_launch_nn decides for a call, nothing launched (the twin of hgemm_mi355x_selfcheck_launch; not part of the public
-// header): operands = 4 when the pointers are 16-byte aligned, ruled_out = 1 << form of the two-pass form that got no workspace.
-// Returns the call's status; out = {form, dispatches, slab bytes, counters (0)}, then per dispatch {thunk, grid, epi, splits, k_chunk,
-// items, start, stop}.
+int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, a, b, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, a, b, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
-  if (M <= 0 || N <= 0 || K <= 0 || !out) return HGEMM_ERR_BAD_ARG;
-  const LaunchPlan p = resolve_nn(nn_config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out);
-  out[0] = p.form; out[1] = p.n; out[2] = (long long)p.slab_bytes; out[3] = p.counters;
-  for (int i = 0; i < p.n; ++i) {
-    const Dispatch& d = p.d[i];
-    const long long v[8] = {d.thunk, d.grid, d.epi, d.g.splits, d.g.k_chunk, d.g.items, d.start, d.stop};
-    std::copy(v, v + 8, out + 4 + 8 * i);
-  }
-  return p.status;
+  return tr_selfcheck_launch(kLayoutNN, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+int hgemm_mi355x_ta_num_configs(void) { return g_num_ta; }
+const char* hgemm_mi355x_ta_config_name(int id) { return tr_config_name(kLayoutTA, id); }
+int hgemm_mi355x_ta_config_by_name(const char* name) { return tr_config_by_name(kLayoutTA, name); }
+int hgemm_mi355x_ta_config_info(int id, int out[8]) { return tr_config_info(kLayoutTA, id, out); }
+int hgemm_mi355x_ta_plan(int M, int N, int K, int* ta_config, int* splits) { return tr_plan(kLayoutTA, M, N, K, ta_config, splits); }
+int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, ta_config, M, N, K, lda, ldb, ldc); }
+size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, int N, int K) {
+  return tr_plan_workspace_bytes(kLayoutTA, ta_config, splits, M, N, K);
+}
+int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutTA, M, N, K, stream); }
+int hgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
+                           int ldb, int ldc, void* stream) {
+  return tr_launch(kLayoutTA, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
+}
+int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                     long long out[20]) {
+  return tr_selfcheck_launch(kLayoutTA, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the
@@ -1101,14 +996,7 @@ int hgemm_mi355x_selfcheck_launch(int config_id, int splits, int group_m, int op
                                   int ruled_out, long long out[28]) {
   if (M <= 0 || N <= 0 || K <= 0 || config_id >= g_num_kernels || config_id < HGEMM_CONFIG_RAGGED || !out) return HGEMM_ERR_BAD_ARG;
   const bool aligned = (operands & 4) && mfma_path_ok(nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc);
-  const LaunchPlan p = resolve_launch(config_id, splits, group_m, operands & 1, operands & 2, aligned, M, N, K, lda, ldb, ldc, ruled_out);
-  out[0] = p.form; out[1] = p.n; out[2] = (long long)p.slab_bytes; out[3] = p.counters;
-  for (int i = 0; i < p.n; ++i) {
-    const Dispatch& d = p.d[i];
-    const long long v[8] = {d.thunk, d.grid, d.epi, d.g.splits, d.g.k_chunk, d.g.items, d.start, d.stop};
-    std::copy(v, v + 8, out + 4 + 8 * i);
-  }
-  return p.status;
+  return show_plan(resolve_launch(config_id, splits, group_m, operands & 1, operands & 2, aligned, M, N, K, lda, ldb, ldc, ruled_out), out);
 }
 unsigned hgemm_mi355x_selfcheck_fastdiv(unsigned n, unsigned d) { return d ? fast_div(n, make_fast_div(d)) : 0xFFFFFFFFu; }
 

@@ -39,8 +39,11 @@ __host__ __device__ constexpr int nn_swz(int krow) {
   return BN == 128 ? (((krow & 3) << 2) | ((krow >> 2) & 3)) : ((((krow >> 1) & 1) | (((krow >> 3) & 1) << 1)) << 1);
 }
 
-template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
-struct CfgNN {
+// ---- what the transposed-read families share (family a, hgemm_kernel_ta.hpp, builds on this header) ----------------------------
+// The Cfg of both: the wave tiling, the B image and the ring.  A_BYTES is the family's A image of one stage; whatever it looks like, it
+// is filled in 1-KiB DMA pieces, A_BYTES / 1024 of them.
+template <int BM_, int BN_, int WM_, int WN_, int NBUF_, int A_BYTES_>
+struct CfgTR {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MI = 16, NBUF = NBUF_;
   static constexpr int NW          = WM * WN;
   static constexpr int THREADS     = NW * 64;
@@ -48,21 +51,35 @@ struct CfgNN {
   static constexpr int TN          = BN / WN;
   static constexpr int FM          = TM / 16;
   static constexpr int FN          = TN / 16;
-  static constexpr int A_BYTES     = BM * ROW_BYTES;
+  static constexpr int A_BYTES     = A_BYTES_;
   static constexpr int B_ROW_BYTES = BN * 2;               // one k-row of the B image
   static constexpr int B_BYTES     = BK * B_ROW_BYTES;
   static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
   static constexpr int LDS_BYTES   = STAGE_BYTES * NBUF;
   static constexpr int B_CH        = BN / 8;               // 16-byte chunks per k-row
   static constexpr int B_RPP       = 64 / B_CH;            // k-rows per 1-KiB DMA piece
-  static constexpr int NI_A        = BM / 8;               // DMA pieces of the A tile ...
-  static constexpr int NI_B        = B_BYTES / 1024;       // ... and of the B tile
+  static constexpr int NI_A        = A_BYTES / 1024;       // DMA pieces of the A tile (BM / 8) ...
+  static constexpr int NI_B        = B_BYTES / 1024;       // ... and of the B tile (BN / 8)
   static constexpr int NJ_A        = NI_A / NW;            // pieces per wave: piece wave + j * NW, the first NJ_A of them are A's
   static constexpr int NJ          = (NI_A + NI_B) / NW;
   static_assert(BN == 64 || BN == 128, "nn_swz is defined for 128- and 256-byte k-rows");
   static_assert(BM % (WM * 16) == 0 && BN % (WN * 16) == 0 && FN % 2 == 0, "wave tile: MFMA-aligned, an even number of column tiles");
   static_assert(NI_A % NW == 0 && NI_B % NW == 0, "every wave owns the same number of A and of B pieces (counted vmcnt)");
   static_assert(NBUF >= 2 && LDS_BYTES <= 160 * 1024, "LDS budget");
+};
+
+// the vector a transposed read returns, in LDS
+using tr_t = __attribute__((ext_vector_type(4))) short;
+typedef __attribute__((address_space(3))) tr_t lds_tr_t;
+
+template <class CFG, int EPI>
+__global__ void hgemm_nn_kernel(const GemmArgs g);
+
+// family n: the classic A image, [BM rows][128 B]
+template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
+struct CfgNN : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
+  template <int EPI>
+  static constexpr auto kernel() { return &hgemm_nn_kernel<CfgNN, EPI>; }   // the family's entry point (launch_tr)
 };
 
 // GemmArgs as the kernel reads it: Bt = the ROW-MAJOR B ([K][ldb]), ldb >= N its row stride; tail_tiles = 0, counters = nullptr.
@@ -161,8 +178,6 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
   for (int s = 0; s < NBUF - 1; ++s)
     if (s < nk) stage(smem + s * CFG::STAGE_BYTES);
 
-  using tr_t = __attribute__((ext_vector_type(4))) short;
-  typedef __attribute__((address_space(3))) tr_t lds_tr_t;
   int rd = 0, wr = NBUF - 1;
   for (int t = 0; t < nk; ++t) {
     if (t + NBUF - 2 < nk)
@@ -229,13 +244,13 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// ---- host side: the family's own small table (the geometry table of hgemm_configs*.def does not know it) ------------------
+// ---- host side: each family's own small table (the geometry table of hgemm_configs*.def does not know them) ----------------------
 template <class CFG>
-void launch_nn(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+void launch_tr(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
   if (epi == EPI_SLAB)
-    HGEMM_LAUNCH((hgemm_nn_kernel<CFG, EPI_SLAB>), grid, CFG::THREADS, stream, ts, g);
+    HGEMM_LAUNCH((CFG::template kernel<EPI_SLAB>()), grid, CFG::THREADS, stream, ts, g);
   else
-    HGEMM_LAUNCH((hgemm_nn_kernel<CFG, EPI_C16>), grid, CFG::THREADS, stream, ts, g);
+    HGEMM_LAUNCH((CFG::template kernel<EPI_C16>()), grid, CFG::THREADS, stream, ts, g);
 }
 
 struct NNEntry {
@@ -245,5 +260,13 @@ struct NNEntry {
 };
 extern const NNEntry g_nn_table[];
 extern const int g_num_nn;
+
+// The members of both families, smallest tile first (a family's ids are positions in its table), and what a family's translation unit
+// makes of them: X(P, CFG, ...) with P the prefix of the members' names and CFG the family's Cfg template.
+#define HGEMM_TR_MEMBERS(X, P, CFG) X(P, CFG, 64, 64, 2, 2, 4) X(P, CFG, 128, 64, 2, 2, 3) X(P, CFG, 64, 128, 2, 2, 3) X(P, CFG, 128, 128, 2, 2, 3)
+#define HGEMM_TR_INST(P, CFG, BM, BN, WM, WN, NB) template void launch_tr<CFG<BM, BN, WM, WN, NB>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TR_ROW(P, CFG, BM, BN, WM, WN, NB)                                                                                \
+  {P #BM "x" #BN "_w" #WM "x" #WN, BM, BN, WM, WN, NB, CFG<BM, BN, WM, WN, NB>::THREADS, CFG<BM, BN, WM, WN, NB>::LDS_BYTES, \
+   &launch_tr<CFG<BM, BN, WM, WN, NB>>},
 
 }  // namespace hgemm_mi355x

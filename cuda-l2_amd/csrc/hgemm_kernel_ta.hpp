@@ -26,8 +26,10 @@
 //     stored; stores are predicated.  Scope (the host sends anything else to the reference kernel): K % 64 == 0, M % 8 == 0,
 //     N % 8 == 0, lda / ldb / ldc multiples of 8, 16-byte aligned pointers; A and B within 2 GiB from row 0 to the end of the matrix,
 //     a C tile within 2 GiB from its first row.
-//   * Epilogues: family n's, repeated here (hgemm_kernel_nn.hpp and unit g5 stay as they are): fp16 C (plain and non-temporal) and
-//     the two-pass split-K slab (hgemm_splitk_reduce_kernel combines).
+//   * Epilogues: family n's: fp16 C (plain and non-temporal) and the two-pass split-K slab (hgemm_splitk_reduce_kernel combines).
+//   * Shared with family n: the Cfg base (CfgTR), launch_tr, the member list and table macros, nn_swz.  The kernel body is family n's
+//     text once more, on purpose: as one force-inlined function template under two __global__ wrappers it compiled to a different K
+//     loop in every kernel.
 //   tests/test_ta_host.py replays the A image with tests/nn_layout_model.py (bn := BM, tn := TM, wave_n := wave_m) and restates the
 //   lane address expression of a_off below.
 #pragma once
@@ -36,33 +38,19 @@
 
 namespace hgemm_mi355x {
 
+template <class CFG, int EPI>
+__global__ void hgemm_ta_kernel(const GemmArgs g);
+
+// family n's Cfg (CfgTR: wave tiling, B image, ring) with the A image above
 template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
-struct CfgTA {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MI = 16, NBUF = NBUF_;
-  static constexpr int NW          = WM * WN;
-  static constexpr int THREADS     = NW * 64;
-  static constexpr int TM          = BM / WM;
-  static constexpr int TN          = BN / WN;
-  static constexpr int FM          = TM / 16;
-  static constexpr int FN          = TN / 16;
-  static constexpr int A_ROW_BYTES = BM * 2;               // one k-row of the A image ...
-  static constexpr int B_ROW_BYTES = BN * 2;               // ... and of the B image
-  static constexpr int A_BYTES     = BK * A_ROW_BYTES;
-  static constexpr int B_BYTES     = BK * B_ROW_BYTES;
-  static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
-  static constexpr int LDS_BYTES   = STAGE_BYTES * NBUF;
+struct CfgTA : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BK * BM_ * 2> {
+  static constexpr int BM          = BM_;                  // (CfgTR's: a dependent base's names are not found unqualified)
+  static constexpr int A_ROW_BYTES = BM * 2;               // one k-row of the A image
   static constexpr int A_CH        = BM / 8;               // 16-byte chunks per k-row
-  static constexpr int B_CH        = BN / 8;
   static constexpr int A_RPP       = 64 / A_CH;            // k-rows per 1-KiB DMA piece
-  static constexpr int B_RPP       = 64 / B_CH;
-  static constexpr int NI_A        = A_BYTES / 1024;       // DMA pieces of the A tile (BM / 8) ...
-  static constexpr int NI_B        = B_BYTES / 1024;       // ... and of the B tile (BN / 8)
-  static constexpr int NJ_A        = NI_A / NW;            // pieces per wave: piece wave + j * NW, the first NJ_A of them are A's
-  static constexpr int NJ          = (NI_A + NI_B) / NW;
-  static_assert((BM == 64 || BM == 128) && (BN == 64 || BN == 128), "nn_swz is defined for 128- and 256-byte k-rows");
-  static_assert(BM % (WM * 16) == 0 && BN % (WN * 16) == 0 && FN % 2 == 0, "wave tile: MFMA-aligned, an even number of column tiles");
-  static_assert(NI_A % NW == 0 && NI_B % NW == 0, "every wave owns the same number of A and of B pieces (counted vmcnt)");
-  static_assert(NBUF >= 2 && LDS_BYTES <= 160 * 1024, "LDS budget");
+  static_assert(BM == 64 || BM == 128, "nn_swz is defined for 128- and 256-byte k-rows");
+  template <int EPI>
+  static constexpr auto kernel() { return &hgemm_ta_kernel<CfgTA, EPI>; }   // the family's entry point (launch_tr)
 };
 
 // GemmArgs as the kernel reads it: A = a_col_major ([K][lda], lda >= M its row stride), Bt = the ROW-MAJOR B ([K][ldb], ldb >= N);
@@ -161,8 +149,6 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
   for (int s = 0; s < NBUF - 1; ++s)
     if (s < nk) stage(smem + s * CFG::STAGE_BYTES);
 
-  using tr_t = __attribute__((ext_vector_type(4))) short;
-  typedef __attribute__((address_space(3))) tr_t lds_tr_t;
   int rd = 0, wr = NBUF - 1;
   for (int t = 0; t < nk; ++t) {
     if (t + NBUF - 2 < nk)
@@ -233,15 +219,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// ---- host side: the family's own small table, rows of family n's NNEntry ------------------------------------------------------
-template <class CFG>
-void launch_ta(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  if (epi == EPI_SLAB)
-    HGEMM_LAUNCH((hgemm_ta_kernel<CFG, EPI_SLAB>), grid, CFG::THREADS, stream, ts, g);
-  else
-    HGEMM_LAUNCH((hgemm_ta_kernel<CFG, EPI_C16>), grid, CFG::THREADS, stream, ts, g);
-}
-
+// ---- host side: the family's own small table, rows of family n's NNEntry, launched by its launch_tr ----------------------------
 extern const NNEntry g_ta_table[];
 extern const int g_num_ta;
 

@@ -1010,18 +1010,37 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
 // check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} bit-exact on 0/1 inputs with B ROW-MAJOR; the default
 // shapes hold one tile, ragged M / N, an 8-column sliver, 1 .. 7 K stages, a long K -- and three the kernel does not take
 // (K % 64, N % 8: the reference kernel answers).
-// `ta`: the same check of family a (hgemm_kernel_ta.hpp) -- A handed over as a_col_major [K][M], lda = M; the default shapes add
+// kLayoutTA: the same check of family a (hgemm_kernel_ta.hpp) -- A handed over as a_col_major [K][M], lda = M; the default shapes add
 // M % 8 != 0 to what the kernel does not take and an 8-row sliver to what it does.
-static int cmd_check_nn(std::vector<Shape> shapes, bool ta = false) {
-  if (shapes.empty())
-    shapes = parse_shapes(ta ? "64_64_64,8_8_64,72_72_128,200_264_192,136_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
-                               "200_136_72,200_100_128,100_136_128,33_17_40"
-                             : "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
-                               "200_136_72,200_100_128,33_17_40");
+// One record per transposed-read layout: the family's C ABI, how A is handed over, the words of its output.
+struct TrLayout {
+  const char* label;            // "nn" / "ta": --layout, the JSON field prefix, the check's lines
+  const char* kernels;
+  const char* check_shapes;     // the check's default shapes
+  bool a_col_major;             // A handed over as [K][M] with lda = M (else [M][K], lda = K); ldb = ldc = N either way
+  int (*num_configs)(void);
+  const char* (*config_name)(int);
+  int (*plan)(int, int, int, int*, int*);
+  int (*runs)(int, int, int, int, int, int, int);
+  int (*launch)(int, int, const void*, const void*, void*, int, int, int, int, int, int, void*);
+  int lda(const Shape& sh) const { return a_col_major ? sh.M : sh.K; }
+};
+static const TrLayout kLayoutNN = {"nn", "the NN kernels",
+                                   "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
+                                   "200_136_72,200_100_128,33_17_40",
+                                   false, hgemm_mi355x_nn_num_configs, hgemm_mi355x_nn_config_name, hgemm_mi355x_nn_plan, hgemm_mi355x_nn_runs,
+                                   hgemm_mi355x_launch_nn};
+static const TrLayout kLayoutTA = {"ta", "the TA kernels",
+                                   "64_64_64,8_8_64,72_72_128,200_264_192,136_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
+                                   "200_136_72,200_100_128,100_136_128,33_17_40",
+                                   true, hgemm_mi355x_ta_num_configs, hgemm_mi355x_ta_config_name, hgemm_mi355x_ta_plan, hgemm_mi355x_ta_runs,
+                                   hgemm_mi355x_launch_ta};
+
+static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
+  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
   int failures = 0, runs = 0;
-  const char* lay = ta ? "ta" : "nn";
-  const int nc = ta ? hgemm_mi355x_ta_num_configs() : hgemm_mi355x_nn_num_configs();
-  auto config_name = [&](int c) { return ta ? hgemm_mi355x_ta_config_name(c) : hgemm_mi355x_nn_config_name(c); };
+  const char* lay = L.label;
+  const int nc = L.num_configs();
   for (const Shape& sh : shapes) {
     const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
     const size_t cn = (size_t)sh.M * sh.N;
@@ -1038,7 +1057,7 @@ static int cmd_check_nn(std::vector<Shape> shapes, bool ta = false) {
     HIP_OK(hipMalloc(&s.a, z.a.size() * 2));
     HIP_OK(hipMalloc(&s.b, b_rm.size() * 2));
     HIP_OK(hipMalloc(&s.c, cn * 2));
-    if (ta) {   // a_col_major[k][m] = a[m][k]
+    if (L.a_col_major) {   // a_col_major[k][m] = a[m][k]
       std::vector<f16> a_cm(z.a.size());
       for (int m = 0; m < sh.M; ++m)
         for (int k = 0; k < sh.K; ++k) a_cm[(size_t)k * sh.M + m] = z.a[(size_t)m * sh.K + k];
@@ -1048,12 +1067,11 @@ static int cmd_check_nn(std::vector<Shape> shapes, bool ta = false) {
     }
     HIP_OK(hipMemcpy(s.b, b_rm.data(), b_rm.size() * 2, hipMemcpyHostToDevice));
     for (int c = 0; c < nc; ++c) {
-      const char* cname = config_name(c);
-      const int own = ta ? hgemm_mi355x_ta_runs(c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N) : hgemm_mi355x_nn_runs(c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N);
+      const char* cname = L.config_name(c);
+      const int own = L.runs(c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
         HIP_OK(hipMemset(s.c, 0xff, cn * 2));  // NaN pattern: unwritten outputs are caught
-        const int st = ta ? hgemm_mi355x_launch_ta(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N, nullptr)
-                          : hgemm_mi355x_launch_nn(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N, nullptr);
+        const int st = L.launch(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N, nullptr);
         const hipError_t e = hipDeviceSynchronize();
         ++runs;
         if (st != HGEMM_OK || e != hipSuccess) {
@@ -1075,26 +1093,51 @@ static int cmd_check_nn(std::vector<Shape> shapes, bool ta = false) {
           ++failures;
         }
       }
-      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? (ta ? "the TA kernels" : "the NN kernels") : "outside their scope: the reference kernel");
+      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
     }
     free_set(s);
     fflush(stdout);
   }
   printf("check-%s-configs:", lay);
-  for (int c = 0; c < nc; ++c) printf(" %s", config_name(c));
+  for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
   printf("\ncheck-%s-forms: 1 1|nt-store 2 5\n", lay);
   printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs)\n", lay, runs, failures);
   return failures ? 1 : 0;
 }
 
-// bench: the check first (no timing of a kernel that is wrong), then per shape ONE set of interleaved rounds (time_interleaved) of the
+// What the two bench commands do around their contenders.  The check first (no timing of a kernel that is wrong), then the output file:
+// nullptr (and *rc set) when nothing is to be timed.
+static FILE* tr_bench_open(const TrLayout& L, const char* out_path, int* rc) {
+  *rc = cmd_check_nn(L, {});
+  if (*rc != 0) { fprintf(stderr, "bench --layout %s: the check failed, nothing is timed\n", L.label); return nullptr; }
+  FILE* out = out_path ? fopen(out_path, "w") : stdout;
+  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); *rc = 2; }
+  return out;
+}
+// one JSON record per shape: the planned member, its splits, whether the family's kernel runs it, then the contenders' times
+static void tr_bench_record(FILE* out, const TrLayout& L, const Shape& sh, int rounds, const std::vector<Contender>& cs) {
+  const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
+  int cfg = 0, splits = 1;
+  L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
+  const int own = L.runs(cfg, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
+  const char* l = L.label;
+  fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"%s\", \"%s_config\": \"%s\", \"%s_splits\": %d, \"%s_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"",
+          sh.M, sh.N, sh.K, l, l, L.config_name(cfg), l, splits, l, own, rounds);
+  for (const Contender& c : cs) {
+    const double us = c.iso_us();
+    fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
+  }
+  fprintf(out, "}\n");
+  fflush(out);
+}
+
+// bench: the check first, then per shape ONE set of interleaved rounds (time_interleaved) of the
 // planned NN call, the reference kernel on the same operands (what a b-only call ran before the family), hipBLASLt heuristic / autotune
 // _nn, and -- context only -- the shipped TN plan on a pre-built b_col_major.  One JSON record per shape.
 static int cmd_bench_nn(const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
-  const int rc = cmd_check_nn({});
-  if (rc != 0) { fprintf(stderr, "bench --layout nn: the check failed, nothing is timed\n"); return rc; }
-  FILE* out = out_path ? fopen(out_path, "w") : stdout;
-  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  int rc = 0;
+  FILE* out = tr_bench_open(kLayoutNN, out_path, &rc);
+  if (!out) return rc;
   hgemm_hipblaslt_heuristic_init();
   if (autotune) hgemm_hipblaslt_autotune_init();
   hipEvent_t e0, e1;
@@ -1104,9 +1147,6 @@ static int cmd_bench_nn(const std::vector<Shape>& shapes, const char* out_path, 
     const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
     std::vector<Buffers> sets(2);
     for (size_t i = 0; i < sets.size(); ++i) alloc_set(sets[i], sh, 77 + i, true);
-    int cfg = 0, splits = 1;
-    hgemm_mi355x_nn_plan(sh.M, sh.N, sh.K, &cfg, &splits);
-    const int own = hgemm_mi355x_nn_runs(cfg, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N);
     const bool have_at = autotune && hgemm_hipblaslt_autotune_find_best_nn(sh.M, sh.N, sh.K, 0) == HGEMM_OK;   // the search before any timing
     std::vector<Contender> cs;
     cs.push_back({"nn", [&](Buffers& b) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
@@ -1116,14 +1156,7 @@ static int cmd_bench_nn(const std::vector<Shape>& shapes, const char* out_path, 
     cs.push_back({"tn_shipped", [&](Buffers& b) { return hgemm_mi355x_fp32(b.a, nullptr, b.bt, b.c, sh.M, sh.N, sh.K, nullptr); }});
     const int rounds = flops > 1.0e11 ? 5 : 15;   // (the reference kernel takes ~0.1 .. 0.5 s per call on the large shapes)
     time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
-    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"nn\", \"nn_config\": \"%s\", \"nn_splits\": %d, \"nn_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"",
-            sh.M, sh.N, sh.K, hgemm_mi355x_nn_config_name(cfg), splits, own, rounds);
-    for (const Contender& c : cs) {
-      const double us = c.iso_us();
-      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
-    }
-    fprintf(out, "}\n");
-    fflush(out);
+    tr_bench_record(out, kLayoutNN, sh, rounds, cs);
     for (auto& s : sets) free_set(s);
   }
   HIP_OK(hipEventDestroy(e0));
@@ -1137,15 +1170,13 @@ static int cmd_bench_nn(const std::vector<Shape>& shapes, const char* out_path, 
 // of A's bytes followed by that NN call -- no transpose pass can beat a copy, so a lower bound of what a caller without the TA entry
 // points pays --, and rocBLAS on the TA operands.  One JSON record per shape.
 static int cmd_bench_ta(const std::vector<Shape>& shapes, const char* out_path) {
-  const int rc = cmd_check_nn({}, true);
-  if (rc != 0) { fprintf(stderr, "bench --layout ta: the check failed, nothing is timed\n"); return rc; }
-  FILE* out = out_path ? fopen(out_path, "w") : stdout;
-  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  int rc = 0;
+  FILE* out = tr_bench_open(kLayoutTA, out_path, &rc);
+  if (!out) return rc;
   hipEvent_t e0, e1;
   HIP_OK(hipEventCreate(&e0));
   HIP_OK(hipEventCreate(&e1));
   for (const Shape& sh : shapes) {
-    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
     const size_t a_elems = (size_t)sh.M * sh.K;
     std::vector<Buffers> sets(2);
     std::vector<f16*> at(sets.size(), nullptr), tmp(sets.size(), nullptr);   // a_col_major and the copy's destination, per set
@@ -1157,9 +1188,6 @@ static int cmd_bench_ta(const std::vector<Shape>& shapes, const char* out_path) 
     }
     HIP_OK(hipDeviceSynchronize());
     auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
-    int cfg = 0, splits = 1;
-    hgemm_mi355x_ta_plan(sh.M, sh.N, sh.K, &cfg, &splits);
-    const int own = hgemm_mi355x_ta_runs(cfg, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N);
     std::vector<Contender> cs;
     cs.push_back({"ta", [&](Buffers& b) { return hgemm_mi355x_ta_fp32(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
     cs.push_back({"nn_pretransposed", [&](Buffers& b) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
@@ -1169,14 +1197,7 @@ static int cmd_bench_ta(const std::vector<Shape>& shapes, const char* out_path) 
     cs.push_back({"rocblas_ta", [&](Buffers& b) { return hgemm_rocblas_ta(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
     const int rounds = 15;
     time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
-    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"ta\", \"ta_config\": \"%s\", \"ta_splits\": %d, \"ta_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"",
-            sh.M, sh.N, sh.K, hgemm_mi355x_ta_config_name(cfg), splits, own, rounds);
-    for (const Contender& c : cs) {
-      const double us = c.iso_us();
-      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
-    }
-    fprintf(out, "}\n");
-    fflush(out);
+    tr_bench_record(out, kLayoutTA, sh, rounds, cs);
     for (size_t i = 0; i < sets.size(); ++i) { free_set(sets[i]); HIP_OK(hipFree(at[i])); HIP_OK(hipFree(tmp[i])); }
   }
   HIP_OK(hipEventDestroy(e0));
@@ -1264,7 +1285,7 @@ int main(int argc, char** argv) {
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
   }
   if (layout_ta) {   // family a: A given as [K][M] (hgemm_mi355x_launch_ta)
-    if (mode == "check") return cmd_check_nn(shapes, true);
+    if (mode == "check") return cmd_check_nn(kLayoutTA, shapes);
     if (mode == "bench") {
       if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
       return cmd_bench_ta(shapes, out_path);
@@ -1273,7 +1294,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (layout_nn) {   // family n: B row-major (hgemm_mi355x_launch_nn); the default shapes of the check are cmd_check_nn's
-    if (mode == "check") return cmd_check_nn(shapes);
+    if (mode == "check") return cmd_check_nn(kLayoutNN, shapes);
     if (mode == "bench") {
       if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
       return cmd_bench_nn(shapes, out_path, autotune);

@@ -8,7 +8,7 @@ these tests use.
    very operands, that the truth is order-independent and that each mutant shows in every 16 x 16 block of every case.
 2. Special values: inf, NaN, -0, denormal operands and results, overflow at 65520, in rows of A AND in rows of B (the operand of
    the transposed reads), against the reference's CPU expression.
-3. The 32-bit reach rule of nn_reach_ok, executed on both sides of its edge for A, B and C.
+3. The 32-bit reach rule of TrLayout::reach_ok, executed on both sides of its edge for A, B and C.
 4. Rasters of more than eight tile rows (group_m = 8 with a ragged last group), split items across them.
 5. The workspace behaviour of hgemm_mi355x_launch_nn: capture without and with a reserved workspace, a lent buffer, two streams.
 6. Misaligned A, B or C: the reference kernel answers.
@@ -42,7 +42,7 @@ EDGE, NARROW = 24, 20                     # M = BM + 24; N = BN + 24: a whole ti
 ROUNDING_FORMS = (1, 1 | NT_STORE, 2, 3, 5)
 LONG = (64, 64, 8128)                     # 127 stages: the largest multiple of 64 within oracle.DYADIC_MAX_K
 LONG_FORMS = (1, 5)
-PLANNED = ((256, 264, 512, 8), (200, 136, 192, 3))           # (M, N, K, the splits nn_model_plan gives the 64 x 64 member)
+PLANNED = ((256, 264, 512, 8), (200, 136, 192, 3))           # (M, N, K, the splits tr_model_plan gives the 64 x 64 member)
 
 
 def nn_infos(lib):
@@ -58,7 +58,7 @@ def nn_infos(lib):
 
 
 def two_pass(k, word):
-    """(splits, K per chunk) of the two-pass form, resolve_nn's clamp rule: at most one split per stage, per = ceil(steps / splits)
+    """(splits, K per chunk) of the two-pass form, tr_resolve's clamp rule: at most one split per stage, per = ceil(steps / splits)
     stages per chunk, no empty chunk."""
     steps = k // BK
     splits = max(1, min(word & 0xFFFF, steps))
@@ -192,7 +192,7 @@ def test_long_k_rounds_to_nearest_even(g, L, oracle, infos, member_operands):
 
 def test_the_planned_entries_round_to_nearest_even_through_their_split_plans(g, L, oracle):
     """hgemm_mi355x_nn_fp32 / _fp16 at two shapes whose 64 x 64 tiles do not fill the chip: the planner splits (8 and 3 ways), so the
-    planned split path -- nn_model_plan's split branch, the stream workspace, the slab epilogue and the reduce -- carries values
+    planned split path -- tr_model_plan's split branch, the stream workspace, the slab epilogue and the reduce -- carries values
     that need rounding."""
     ops = DyadicOperands(oracle, *planned_extent(), PLANNED_SEED)
     r = Rounding(g, L, oracle)
@@ -301,7 +301,7 @@ def largest_nn_stride(lib, cid, m, n, k, side):
 
 
 def reach_rule(bm, m, n, k, side):
-    """(rows, tail bytes) of nn_reach_ok's limit on operand `side`: rows x ld x 2 + tail < 2 GiB.  A and C are addressed from a tile's
+    """(rows, tail bytes) of TrLayout::reach_ok's limit on operand `side`: rows x ld x 2 + tail < 2 GiB.  A and C are addressed from a tile's
     first row (BM rows, then the row's K or N elements), B from row 0 to the end of the matrix (K - 1 rows, then N elements)."""
     return ((bm, 2 * k), (k - 1, 2 * n), (bm, 2 * n))[side]
 

@@ -186,7 +186,7 @@ def test_bad_strides_and_ids_are_refused(lib):
     assert lib.hgemm_mi355x_nn_fp32(null, null, null, m, n, k, null) == -1 and lib.hgemm_mi355x_nn_fp16(null, null, null, 0, n, k, null) == -1
 
 
-# ---- the 32-bit reach rule (nn_reach_ok), at its boundary ---------------------------------------------------------------------
+# ---- the 32-bit reach rule (TrLayout::reach_ok), at its boundary ---------------------------------------------------------------------
 GIB = 1 << 30
 
 
