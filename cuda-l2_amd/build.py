@@ -42,6 +42,7 @@ LIB_SOURCES = [
     "hgemm_inst_g4.hip",
     "hgemm_inst_g5.hip",
     "hgemm_inst_g6.hip",
+    "hgemm_inst_g7.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -471,6 +471,14 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // Each family has its own table (g_nn_table: hgemm_inst_g5.hip, g_ta_table: hgemm_inst_g6.hip); the geometry table, hgemm_mi355x_plan and
 // what a b-only call of hgemm_mi355x_launch does know nothing of them.  A layout is described once, here; resolution, launch, planner and
 // the queries below are written once and take the description.
+// What a call writes: fp16 C (every nn_ / ta_ entry point) or fp32 C (c32: hgemm_mi355x_ta_c32, family a only), stored or -- c32 only --
+// added into what C holds.  ldc counts C's own elements.
+struct TrOut {
+  bool c32, accumulate;
+  int elem_bytes() const { return c32 ? 4 : 2; }
+};
+constexpr TrOut kOutC16{false, false};
+
 struct TrLayout {
   const NNEntry* table;
   const int& count;
@@ -480,26 +488,35 @@ struct TrLayout {
   bool a_col_major;
   // the reference kernel of the layout (status 0, exact): answers whatever is outside the kernels' scope or reach
   void (*reference)(const f16*, const f16*, f16*, int, int, int, int, int, int, hipStream_t, TimingSlot);
+  // fp32 C: the EPI_C32 launchers by config id and the reference kernel of that output; null where the layout has none (a c32 call is
+  // refused with HGEMM_ERR_BAD_ARG)
+  const TaC32Launch* launch_c32;
+  void (*reference_c32)(const f16*, const f16*, float*, int, int, int, int, int, int, bool, hipStream_t, TimingSlot);
 
   // elements in a row of A: the least lda, and the lda of a contiguous A (the planned calls pass strides (a_row, N, N))
   int a_row(int M, int K) const { return a_col_major ? M : K; }
-  // the kernels' scope; everything else is answered by the reference kernel
-  bool path_ok(const void* a, const void* b, const void* c, int M, int N, int K, int lda, int ldb, int ldc) const {
+  // the kernels' scope; everything else is answered by the reference kernel.  Rows of C start at 16-byte boundaries: ldc % 8 == 0 of
+  // an fp16 C, ldc % 4 == 0 of an fp32 C (next to a_col_major's rule: the output kind changes C's rules only)
+  bool path_ok(TrOut out, const void* a, const void* b, const void* c, int M, int N, int K, int lda, int ldb, int ldc) const {
     if (K % BK != 0 || (N & 7) != 0 || (a_col_major && (M & 7) != 0)) return false;
-    if ((lda & 7) || (ldb & 7) || (ldc & 7)) return false;
+    if ((lda & 7) || (ldb & 7) || (ldc & (out.c32 ? 3 : 7))) return false;
     return !(((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15));
   }
-  // 32-bit offsets with bit 31 to spare: B from row 0 to the end of the matrix, C from a tile's first row, A as a_col_major says
-  bool reach_ok(const NNEntry& e, int M, int N, int K, int lda, int ldb, int ldc) const {
+  // 32-bit offsets with bit 31 to spare: B from row 0 to the end of the matrix, C from a tile's first row -- (BM ldc + N) elements of 2
+  // bytes, of 4 for an fp32 C --, A as a_col_major says
+  bool reach_ok(TrOut out, const NNEntry& e, int M, int N, int K, int lda, int ldb, int ldc) const {
     const double a_bytes = a_col_major ? (double)(K - 1) * lda * 2.0 + M * 2.0 : (double)e.bm * lda * 2.0 + K * 2.0;
-    return a_bytes < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 && (double)e.bm * ldc * 2.0 + N * 2.0 < 2147483648.0;
+    const double c_bytes = ((double)e.bm * ldc + N) * out.elem_bytes();
+    return a_bytes < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 && c_bytes < 2147483648.0;
   }
 };
-const TrLayout kLayoutNN{g_nn_table, g_num_nn, false, launch_generic};
-const TrLayout kLayoutTA{g_ta_table, g_num_ta, true, launch_generic_ta};
+const TrLayout kLayoutNN{g_nn_table, g_num_nn, false, launch_generic, nullptr, nullptr};
+const TrLayout kLayoutTA{g_ta_table, g_num_ta, true, launch_generic_ta, g_ta_c32_launch, launch_generic_ta_c32};
 
 // (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn / _ta show it to the CPU tests)
-LaunchPlan tr_resolve(const TrLayout& L, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
+// out.c32: the same tiles, cuts and slabs; the plain dispatch and the combine carry EPI_C32 (the K slices are the family's EPI_SLAB
+// kernels), the least ldc is still N
+LaunchPlan tr_resolve(const TrLayout& L, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
                       unsigned ruled_out) {
   LaunchPlan p;
   auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
@@ -509,16 +526,19 @@ LaunchPlan tr_resolve(const TrLayout& L, int config, int splits_arg, bool aligne
   };
   // rows must not overlap: lda >= K (n) / >= M, the row stride of a_col_major (a); ldb >= N (B is row-major here), ldc >= N
   if (config < 0 || config >= L.count || lda < L.a_row(M, K) || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
+  if ((out.c32 && !L.launch_c32) || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no fp32 C in this layout
+  const int epi_out = out.c32 ? EPI_C32 : EPI_C16;
   const NNEntry& e = L.table[config];
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
-  g.flags = (splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
+  g.flags = ((splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0) | (out.accumulate ? ARG_ACCUMULATE : 0);
   g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
   const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
-  if (!aligned || !L.path_ok(nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !L.reach_ok(e, M, N, K, lda, ldb, ldc) || tiles > 0x7fffffffL) {
+  if (!aligned || !L.path_ok(out, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !L.reach_ok(out, e, M, N, K, lda, ldb, ldc) ||
+      tiles > 0x7fffffffL) {
     p.form = FORM_REFERENCE;
-    add(THUNK_GENERIC, g, 0, EPI_C16);
+    add(THUNK_GENERIC, g, 0, epi_out);
     return p;
   }
   g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (N + e.bn - 1) / e.bn;
@@ -536,9 +556,9 @@ LaunchPlan tr_resolve(const TrLayout& L, int config, int splits_arg, bool aligne
     p.form = FORM_SPLITK;
     p.slab_bytes = (size_t)splits * M * N * sizeof(float);
     add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
-    add(THUNK_SPLITK_REDUCE, g, 0, EPI_SLAB);
+    add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : EPI_SLAB);
   } else {
-    add(THUNK_ENTRY, g, tiles, EPI_C16);
+    add(THUNK_ENTRY, g, tiles, epi_out);
   }
   return p;
 }
@@ -568,21 +588,22 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 }
 
 // GemmArgs as the kernels read it: A = a (n: [M][lda], a: [K][lda]), Bt = the row-major B
-int tr_launch(const TrLayout& L, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
-              int ldc, void* stream) {
+// (out.c32: c is the float pointer; it travels in g.C and the EPI_C32 kernels reinterpret it)
+int tr_launch(const TrLayout& L, TrOut out, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda,
+              int ldb, int ldc, void* stream) {
   DisarmTiming disarm_timing;
   if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const bool aligned = L.path_ok(a, b, c, M, N, K, lda, ldb, ldc);
+  const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc);
   unsigned ruled_out = 0;
-  LaunchPlan p = tr_resolve(L, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  LaunchPlan p = tr_resolve(L, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
   // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
   if (p.status == HGEMM_OK && p.slab_bytes) {
     const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
     if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
       ruled_out |= 1u << FORM_SPLITK;
-      p = tr_resolve(L, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+      p = tr_resolve(L, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
     } else if (st != HGEMM_OK) {
       return st;
     }
@@ -593,10 +614,20 @@ int tr_launch(const TrLayout& L, int config, int splits_arg, const void* a, cons
     g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
+    const bool c32 = p.d[i].epi == EPI_C32;
     switch (p.d[i].thunk) {
-      case THUNK_ENTRY: L.table[config].launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
-      case THUNK_SPLITK_REDUCE: launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts); break;
-      default: L.reference((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts); break;
+      case THUNK_ENTRY:
+        if (c32) L.launch_c32[config](g, p.d[i].grid, s, ts);
+        else     L.table[config].launch(g, p.d[i].grid, s, p.d[i].epi, ts);
+        break;
+      case THUNK_SPLITK_REDUCE:
+        if (c32) launch_splitk_reduce_c32(g.partial, (float*)c, M, N, ldc, g.splits, out.accumulate, s, ts);
+        else     launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts);
+        break;
+      default:
+        if (c32) L.reference_c32((const f16*)a, (const f16*)b, (float*)c, M, N, K, lda, ldb, ldc, out.accumulate, s, ts);
+        else     L.reference((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts);
+        break;
     }
   }
   hipError_t err = hipGetLastError();
@@ -605,11 +636,11 @@ int tr_launch(const TrLayout& L, int config, int splits_arg, const void* a, cons
 }
 
 // the planned call on contiguous operands
-int tr_run(const TrLayout& L, const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
+int tr_run(const TrLayout& L, TrOut out, const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   int cfg, splits;
   tr_model_plan(L, M, N, K, &cfg, &splits);
-  return tr_launch(L, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), N, N, stream);
+  return tr_launch(L, out, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), N, N, stream);
 }
 
 const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.count) ? L.table[id].name : nullptr; }
@@ -634,15 +665,15 @@ int tr_plan(const TrLayout& L, int M, int N, int K, int* config, int* splits) {
   return HGEMM_OK;
 }
 
-int tr_runs(const TrLayout& L, int config, int M, int N, int K, int lda, int ldb, int ldc) {
+int tr_runs(const TrLayout& L, TrOut out, int config, int M, int N, int K, int lda, int ldb, int ldc) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = tr_resolve(L, config, 1, true, M, N, K, lda, ldb, ldc, 0);
+  const LaunchPlan p = tr_resolve(L, out, config, 1, true, M, N, K, lda, ldb, ldc, 0);
   return p.status == HGEMM_OK && p.form != FORM_REFERENCE ? 1 : 0;
 }
 
 size_t tr_plan_workspace_bytes(const TrLayout& L, int config, int splits, int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = tr_resolve(L, config, splits, true, M, N, K, L.a_row(M, K), N, N, 0);
+  const LaunchPlan p = tr_resolve(L, kOutC16, config, splits, true, M, N, K, L.a_row(M, K), N, N, 0);   // (the slabs of both output kinds)
   return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
 }
 
@@ -661,10 +692,10 @@ int tr_reserve_workspace(const TrLayout& L, int M, int N, int K, void* stream) {
 // operands = 4 when the pointers are 16-byte aligned, ruled_out = 1 << form of the two-pass form that got no workspace.  Returns the
 // call's status; out = {form, dispatches, slab bytes, counters (0)}, then per dispatch {thunk, grid, epi, splits, k_chunk, items,
 // start, stop}.
-int tr_selfcheck_launch(const TrLayout& L, int config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc,
+int tr_selfcheck_launch(const TrLayout& L, TrOut kind, int config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc,
                         int ruled_out, long long out[20]) {
   if (M <= 0 || N <= 0 || K <= 0 || !out) return HGEMM_ERR_BAD_ARG;
-  return show_plan(tr_resolve(L, config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out), out);
+  return show_plan(tr_resolve(L, kind, config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out), out);
 }
 
 }  // namespace
@@ -923,20 +954,20 @@ const char* hgemm_mi355x_nn_config_name(int id) { return tr_config_name(kLayoutN
 int hgemm_mi355x_nn_config_by_name(const char* name) { return tr_config_by_name(kLayoutNN, name); }
 int hgemm_mi355x_nn_config_info(int id, int out[8]) { return tr_config_info(kLayoutNN, id, out); }
 int hgemm_mi355x_nn_plan(int M, int N, int K, int* nn_config, int* splits) { return tr_plan(kLayoutNN, M, N, K, nn_config, splits); }
-int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, nn_config, M, N, K, lda, ldb, ldc); }
+int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, kOutC16, nn_config, M, N, K, lda, ldb, ldc); }
 size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K) {
   return tr_plan_workspace_bytes(kLayoutNN, nn_config, splits, M, N, K);
 }
 int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutNN, M, N, K, stream); }
 int hgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
                            int ldc, void* stream) {
-  return tr_launch(kLayoutNN, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutNN, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
 }
-int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, a, b, c, M, N, K, stream); }
-int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, a, b, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, kOutC16, a, b, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, kOutC16, a, b, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
-  return tr_selfcheck_launch(kLayoutNN, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutNN, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 int hgemm_mi355x_ta_num_configs(void) { return g_num_ta; }
@@ -944,20 +975,40 @@ const char* hgemm_mi355x_ta_config_name(int id) { return tr_config_name(kLayoutT
 int hgemm_mi355x_ta_config_by_name(const char* name) { return tr_config_by_name(kLayoutTA, name); }
 int hgemm_mi355x_ta_config_info(int id, int out[8]) { return tr_config_info(kLayoutTA, id, out); }
 int hgemm_mi355x_ta_plan(int M, int N, int K, int* ta_config, int* splits) { return tr_plan(kLayoutTA, M, N, K, ta_config, splits); }
-int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, ta_config, M, N, K, lda, ldb, ldc); }
+int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, kOutC16, ta_config, M, N, K, lda, ldb, ldc); }
 size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, int N, int K) {
   return tr_plan_workspace_bytes(kLayoutTA, ta_config, splits, M, N, K);
 }
 int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutTA, M, N, K, stream); }
 int hgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
                            int ldb, int ldc, void* stream) {
-  return tr_launch(kLayoutTA, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTA, kOutC16, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
 }
-int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, a_col_major, b, c, M, N, K, stream); }
-int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, kOutC16, a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, kOutC16, a_col_major, b, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
-  return tr_selfcheck_launch(kLayoutTA, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutTA, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// fp32 C (family a, EPI_C32): the same path with the other output kind.  Plan, workspace size and reserve call are the TA layout's own
+// (hgemm_mi355x_ta_plan / _ta_plan_workspace_bytes / _ta_reserve_workspace): the tiles and the slabs are the same.
+int hgemm_mi355x_launch_ta_c32(int ta_config, int splits_arg, const void* a_col_major, const void* b, float* c32, int M, int N, int K, int lda,
+                               int ldb, int ldc, int accumulate, void* stream) {
+  if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutTA, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, c32, M, N, K, lda, ldb, ldc, stream);
+}
+int hgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int M, int N, int K, int accumulate, void* stream) {
+  if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutTA, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
+}
+int hgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
+  return tr_runs(kLayoutTA, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
+}
+int hgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int accumulate,
+                                         int ruled_out, long long out[20]) {
+  if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTA, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the

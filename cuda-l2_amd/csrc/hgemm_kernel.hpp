@@ -51,6 +51,7 @@ constexpr int ARG_NT_LOADS      = 4;    // HGEMM_PLAN_RS_NT_LOADS: non-temporal 
 constexpr int ARG_PHASE_OFFSET  = 8;    // HGEMM_PLAN_PHASE_OFFSET: family q's phase groups of the persistent walk
 constexpr int ARG_WAVE_PRIORITY = 16;   // HGEMM_PLAN_WAVE_PRIORITY: family q's two-resident members
 constexpr int ARG_PHASE_OFFSET4 = 32;   // HGEMM_PLAN_PHASE_OFFSET4: four phase groups instead of two (both bits: eight)
+constexpr int ARG_ACCUMULATE    = 64;   // no plan flag: the `accumulate` argument of the fp32-C calls (EPI_C32: C32 += A x B)
 
 // Build-time switches retired with the experiments they selected: each either forced on what is a plan flag now (ARG_* above),
 // or guarded the "off" path of something every measured library has had on.  A stale -D must not silently measure the shipping
@@ -287,6 +288,8 @@ constexpr int EPI_C16    = 0;  // fp16 C, written directly (splits == 1)
 constexpr int EPI_SLAB   = 1;  // fp32 partials to [splits][M][N] (or compact tail slabs); a second kernel combines
 constexpr int EPI_FUSED  = 2;  // single-launch split-K: fp32 partials + arrival counter, the last arriver combines
 constexpr int EPI_STREAMK = 3; // stream-K: one persistent launch over the tile-major K-stage sequence (StreamK above)
+constexpr int EPI_C32    = 4;  // fp32 C (family a): the accumulators stored as they are, or added into C (ARG_ACCUMULATE); g.C holds
+                               // the float pointer, g.ldc counts fp32 elements
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

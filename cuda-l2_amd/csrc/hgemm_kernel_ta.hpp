@@ -27,6 +27,9 @@
 //     N % 8 == 0, lda / ldb / ldc multiples of 8, 16-byte aligned pointers; A and B within 2 GiB from row 0 to the end of the matrix,
 //     a C tile within 2 GiB from its first row.
 //   * Epilogues: family n's: fp16 C (plain and non-temporal) and the two-pass split-K slab (hgemm_splitk_reduce_kernel combines).
+//     EPI_C32 (hgemm_inst_g7.hip, hgemm_mi355x_ta_c32): the fp32 accumulators stored to, or added into, the caller's fp32 C -- the
+//     weight gradient where a training step consumes it; its two-pass form combines the same slabs with
+//     hgemm_splitk_reduce_c32_kernel.
 //   * Shared with family n: the Cfg base (CfgTR), launch_tr, the member list and table macros, nn_swz.  The kernel body is family n's
 //     text once more, on purpose: as one force-inlined function template under two __global__ wrappers it compiled to a different K
 //     loop in every kernel.
@@ -61,7 +64,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BM = CFG::BM, BN = CFG::BN, NBUF = CFG::NBUF;
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB, "plain and two-pass slab epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || EPI == EPI_C32, "plain (fp16 C, fp32 C) and two-pass slab epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -188,6 +191,48 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
 
   if constexpr (EPI == EPI_SLAB) {
     store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
+  } else if constexpr (EPI == EPI_C32) {
+    // fp32 C (the weight gradient added into an fp32 gradient buffer): g.C holds the float pointer, g.ldc counts fp32 elements.  A lane
+    // owns n = 16 j + 4 (lane >> 4) + 0 .. 3 of C row lane & 15 per acc[i][j], 16 consecutive bytes: one buffer store per (i, j), no lane
+    // exchange and no conversion.  With ARG_ACCUMULATE (wave-uniform) the old 16 bytes are loaded first -- a fragment row's FN loads in
+    // flight together -- and new = old + acc, one fp32 add per element; without it C is never read.  Scope (host): N % 8 == 0 (a lane's
+    // four columns are inside or outside together), ldc % 4 == 0, a 16-byte aligned C, (BM ldc + N) 4 bytes below 2 GiB from the
+    // tile's first row.  The non-temporal form is an instruction of its own, as below.
+    const __amdgpu_buffer_rsrc_t rsC =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<float*>(g.C) + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
+    const int q = lane >> 4;
+    const bool accumulate = (g.flags & ARG_ACCUMULATE) != 0;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      __builtin_amdgcn_sched_barrier(0);   // one fragment row's accumulator reads at a time (store_tile)
+      const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
+      const bool row_ok = tc.m0 + row < g.M;
+      f32x4 v[FN];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) v[j] = acc[i][j];
+      if (accumulate) {
+        f32x4 old[FN];
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          const int n = tc.n0 + wave_n * CFG::TN + 16 * j + 4 * q;
+          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 4u;
+          old[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (row_ok && n < g.N) old[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsC, off, 0, 0));
+        }
+#pragma unroll
+        for (int j = 0; j < FN; ++j) v[j] = old[j] + v[j];
+      }
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const int n = tc.n0 + wave_n * CFG::TN + 16 * j + 4 * q;
+        if (row_ok && n < g.N) {
+          const u32x4 o = __builtin_bit_cast(u32x4, v[j]);
+          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 4u;
+          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 2);
+          else                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 0);
+        }
+      }
+    }
   } else {
     // fp16 C, family n's 16-byte form (N % 8 == 0, ldc % 8 == 0, a 16-byte aligned C): v_permlane16_swap exchanges the odd 16-lane
     // rows of column tile j with the even rows of tile j + 1, after which row q = lane >> 4 owns n = 16 (j + (q & 1)) + 8 (q >> 1)
@@ -226,5 +271,15 @@ extern const int g_num_ta;
 // the reference kernel of the layout (hgemm_registry.hip): one output per thread, A read as A[k * lda + m]
 void launch_generic_ta(const f16* a_col_major, const f16* B, f16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
                        TimingSlot ts);
+
+// ---- fp32 C (EPI_C32): launchers by TA config id (hgemm_inst_g7.hip; g_ta_table and NNEntry keep their shape), the combine of the
+// two-pass form and the reference kernel (hgemm_registry.hip).  ldc in fp32 elements; accumulate: C32 += A x B, otherwise C32 is never read.
+using TaC32Launch = void (*)(const GemmArgs&, int, hipStream_t, TimingSlot);
+extern const TaC32Launch g_ta_c32_launch[];
+extern const int g_num_ta_c32;
+void launch_splitk_reduce_c32(const float* partial, float* C32, int M, int N, int ldc, int splits, bool accumulate, hipStream_t stream,
+                              TimingSlot ts);
+void launch_generic_ta_c32(const f16* a_col_major, const f16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
+                           hipStream_t stream, TimingSlot ts);
 
 }  // namespace hgemm_mi355x

@@ -131,6 +131,37 @@ __global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* _
   }
 }
 
+// The combine of family a's fp32-C calls (hgemm_mi355x_ta_c32): t = p[0] + p[1] + ... + p[S-1] in split order, then
+// C32 = accumulate ? C32 + t : t -- the shape of the unsplit result, old + fl(sum), and one fixed order per plan.  C32 is read only
+// with `accumulate`; rows are ldc fp32 elements apart and the pad between N and ldc is never touched.  (N % 4 == 0, ldc % 4 == 0 and
+// a 16-byte aligned C32 on this path.)
+__global__ void __launch_bounds__(256) hgemm_splitk_reduce_c32_kernel(const float* __restrict__ partial, float* __restrict__ C32, int M,
+                                                                      int N, int ldc, int splits, int accumulate) {
+  const size_t total4 = ((size_t)M * N) >> 2;
+  const size_t slab   = (size_t)M * N;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = q << 2;
+    const int m = (int)(e / N), n = (int)(e % N);
+    f32x4* out = (f32x4*)(C32 + (size_t)m * ldc + n);
+    f32x4 old = {0.f, 0.f, 0.f, 0.f};
+    if (accumulate) old = *out;   // in flight with the slab loads
+    f32x4 s = *(const f32x4*)(partial + e);
+    int k = 1;
+    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
+      f32x4 p[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += p[u];
+    }
+    for (; k < splits; ++k) {
+      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
+      s += p;
+    }
+    *out = accumulate ? old + s : s;
+  }
+}
+
 // Combine of the hybrid schedule's tail pass: C tile t = fp16( sum_s partial[s * tail_tiles + t][BM][BN] ),
 // slices added in K order.  One workgroup per (tail tile, 16-row band); the tile origin comes from the same
 // raster map the GEMM kernel used.
@@ -184,6 +215,20 @@ __global__ void __launch_bounds__(256) hgemm_generic_ta_kernel(const f16* __rest
   }
 }
 
+// The reference kernel of the fp32-C calls: hgemm_generic_ta_kernel's fma chain in k order, then C32 = accumulate ? C32 + s : s.
+__global__ void __launch_bounds__(256) hgemm_generic_ta_c32_kernel(const f16* __restrict__ At, const f16* __restrict__ B,
+                                                                   float* __restrict__ C32, int M, int N, int K, int lda_colmajor,
+                                                                   int ldb_rowmajor, int ldc, int accumulate) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    float* out = C32 + (size_t)m * ldc + n;
+    *out = accumulate ? *out + s : s;
+  }
+}
+
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
   const size_t quads = ((size_t)M * N) >> 2;
@@ -193,6 +238,16 @@ void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, i
   if (grid > 256 * 8) grid = 256 * 8;  // grid-stride beyond 8 blocks per CU
   if (grid < 1) grid = 1;
   HGEMM_LAUNCH(hgemm_splitk_reduce_kernel, grid, threads, stream, ts, partial, C, M, N, ldc, splits);
+}
+
+void launch_splitk_reduce_c32(const float* partial, float* C32, int M, int N, int ldc, int splits, bool accumulate, hipStream_t stream,
+                              TimingSlot ts) {
+  const size_t quads = ((size_t)M * N) >> 2;
+  const int threads = quads <= 64 * 1024 ? 64 : 256;   // (launch_splitk_reduce's sizing)
+  int grid = (int)((quads + threads - 1) / threads);
+  if (grid > 256 * 8) grid = 256 * 8;
+  if (grid < 1) grid = 1;
+  HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, grid, threads, stream, ts, partial, C32, M, N, ldc, splits, accumulate ? 1 : 0);
 }
 
 void launch_tail_reduce(const GemmArgs& g, int BM, int BN, hipStream_t stream, TimingSlot ts) {
@@ -232,6 +287,12 @@ void launch_generic_ta(const f16* a_col_major, const f16* B, f16* C, int M, int 
                        TimingSlot ts) {
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
   HGEMM_LAUNCH(hgemm_generic_ta_kernel, grid, 256, stream, ts, a_col_major, B, C, M, N, K, lda, ldb, ldc);
+}
+
+void launch_generic_ta_c32(const f16* a_col_major, const f16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
+                           hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH(hgemm_generic_ta_c32_kernel, grid, 256, stream, ts, a_col_major, B, C32, M, N, K, lda, ldb, ldc, accumulate ? 1 : 0);
 }
 
 }  // namespace hgemm_mi355x

@@ -20,6 +20,8 @@
 //                                                     two-pass splits 2 / 5}, bit-exact as above
 //   hgemm_tune check --layout ta [--shapes ...]       family a (A given as [K][M], hgemm_mi355x_launch_ta): the same check
 //   hgemm_tune bench --layout ta --shapes ... [--out F.jsonl]
+//   hgemm_tune check --layout ta --c32 [--shapes ...] fp32 C (hgemm_mi355x_launch_ta_c32): the same forms x {store, accumulate}, exact
+//   hgemm_tune bench --layout ta --c32 --shapes ... [--out F.jsonl]   the accumulate call against ta_fp32 + an elementwise add
 //                                                     that check first, then per shape interleaved rounds of the planned TA call, the
 //                                                     NN call on a pre-transposed A, a copy of A's bytes + that NN call, rocBLAS
 //   hgemm_tune bench --layout nn --shapes ... [--autotune] [--out F.jsonl]
@@ -1206,6 +1208,139 @@ static int cmd_bench_ta(const std::vector<Shape>& shapes, const char* out_path) 
   return 0;
 }
 
+// ---- fp32 C of the TA layout (hgemm_mi355x_ta_c32): `check --layout ta --c32`, `bench --layout ta --c32` --------------------------------
+// check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} x {store, accumulate} on the shapes of the TA check, exact
+// against the host's integer result: 0/1 operands, an old C32 of integers in +-1000 (store mode starts from a NaN pattern instead).
+static int cmd_check_ta_c32(std::vector<Shape> shapes) {
+  const TrLayout& L = kLayoutTA;
+  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
+  int failures = 0, runs = 0;
+  const int nc = L.num_configs();
+  for (const Shape& sh : shapes) {
+    const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
+    const size_t cn = (size_t)sh.M * sh.N;
+    std::vector<float> product(cn), old(cn), got(cn);
+    std::vector<f16> b_rm((size_t)sh.K * sh.N), a_cm(z.a.size());
+    uint64_t lcg = 88172645463325252ull + cn;
+    for (int m = 0; m < sh.M; ++m)
+      for (int n = 0; n < sh.N; ++n) {
+        int acc = 0;
+        for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
+        product[(size_t)m * sh.N + n] = (float)acc;
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        old[(size_t)m * sh.N + n] = (float)((int)((lcg >> 33) % 2001) - 1000);
+      }
+    for (int n = 0; n < sh.N; ++n)
+      for (int k = 0; k < sh.K; ++k) b_rm[(size_t)k * sh.N + n] = z.bt[(size_t)n * sh.K + k];
+    for (int m = 0; m < sh.M; ++m)
+      for (int k = 0; k < sh.K; ++k) a_cm[(size_t)k * sh.M + m] = z.a[(size_t)m * sh.K + k];
+    f16 *da = nullptr, *db = nullptr;
+    float* dc = nullptr;
+    HIP_OK(hipMalloc(&da, a_cm.size() * 2));
+    HIP_OK(hipMalloc(&db, b_rm.size() * 2));
+    HIP_OK(hipMalloc(&dc, cn * 4));
+    HIP_OK(hipMemcpy(da, a_cm.data(), a_cm.size() * 2, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(db, b_rm.data(), b_rm.size() * 2, hipMemcpyHostToDevice));
+    for (int c = 0; c < nc; ++c) {
+      const char* cname = L.config_name(c);
+      const int own = hgemm_mi355x_ta_c32_runs(c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N);
+      for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5})
+        for (int accumulate : {0, 1}) {
+          if (accumulate) HIP_OK(hipMemcpy(dc, old.data(), cn * 4, hipMemcpyHostToDevice));
+          else            HIP_OK(hipMemset(dc, 0xff, cn * 4));   // NaN pattern: store mode must not read it, unwritten outputs are caught
+          const int st = hgemm_mi355x_launch_ta_c32(c, splits, da, db, dc, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N, accumulate, nullptr);
+          const hipError_t e = hipDeviceSynchronize();
+          ++runs;
+          if (st != HGEMM_OK || e != hipSuccess) {
+            printf("FAIL ta-c32 %d_%d_%d %s s=%d acc=%d: status %d hip %d\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, accumulate, st, (int)e);
+            ++failures;
+            if (e != hipSuccess) return 3;
+            continue;
+          }
+          HIP_OK(hipMemcpy(got.data(), dc, cn * 4, hipMemcpyDeviceToHost));
+          size_t bad = 0;
+          for (size_t i = 0; i < cn; ++i) {
+            const float want = accumulate ? old[i] + product[i] : product[i];   // integers below 2^24: exact
+            if (memcmp(&got[i], &want, 4) != 0) ++bad;
+          }
+          if (bad) {
+            printf("FAIL ta-c32 %d_%d_%d %s s=%d%s %s: %zu/%zu elements differ from the exact result\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+                   (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", accumulate ? "accumulate" : "store", bad, cn);
+            ++failures;
+          }
+        }
+      if (c == 0) printf("checked ta-c32 %d_%d_%d (%s)\n", sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
+    }
+    HIP_OK(hipFree(da)); HIP_OK(hipFree(db)); HIP_OK(hipFree(dc));
+    fflush(stdout);
+  }
+  printf("check-ta-c32-forms: 1 1|nt-store 2 5 x store accumulate\n");
+  printf("check ta-c32: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs and an integer old C32)\n", runs, failures);
+  return failures ? 1 : 0;
+}
+
+// what a caller without the fp32-C call runs behind hgemm_mi355x_ta_fp32: main_grad += float(dW16), a plain grid-stride kernel
+__global__ void add_f16_into_f32_kernel(float* __restrict__ c32, const f16* __restrict__ c16, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) c32[i] += (float)c16[i];
+}
+
+// bench --layout ta --c32: the check first, then per shape ONE set of interleaved rounds of the accumulate call, the store call, and the
+// comparator -- hgemm_mi355x_ta_fp32 into an fp16 scratch followed by the elementwise add.  One JSON record per shape; "c32_le_two_step"
+// is the first look's condition (accumulate call <= comparator).
+static int cmd_bench_ta_c32(const std::vector<Shape>& shapes, const char* out_path) {
+  int rc = cmd_check_ta_c32({});
+  if (rc != 0) { fprintf(stderr, "bench --layout ta --c32: the check failed, nothing is timed\n"); return rc; }
+  FILE* out = out_path ? fopen(out_path, "w") : stdout;
+  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0));
+  HIP_OK(hipEventCreate(&e1));
+  for (const Shape& sh : shapes) {
+    const size_t a_elems = (size_t)sh.M * sh.K, cn = (size_t)sh.M * sh.N;
+    std::vector<Buffers> sets(2);
+    std::vector<f16*> at(sets.size(), nullptr);
+    std::vector<float*> c32(sets.size(), nullptr);
+    for (size_t i = 0; i < sets.size(); ++i) {
+      alloc_set(sets[i], sh, 91 + i, true);
+      HIP_OK(hipMalloc(&at[i], a_elems * 2));
+      HIP_OK(hipMalloc(&c32[i], cn * 4));
+      HIP_OK(hipMemset(c32[i], 0, cn * 4));
+      transpose_kernel<<<(unsigned)((a_elems + 255) / 256), 256>>>(sets[i].a, at[i], sh.M, sh.K);   // at[k][m] = a[m][k]
+    }
+    HIP_OK(hipDeviceSynchronize());
+    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
+    const unsigned add_grid = (unsigned)std::min<size_t>((cn + 255) / 256, 256 * 8);
+    std::vector<Contender> cs;
+    cs.push_back({"c32_accumulate", [&](Buffers& b) { return hgemm_mi355x_ta_c32(at[idx(b)], b.b, c32[idx(b)], sh.M, sh.N, sh.K, 1, nullptr); }});
+    cs.push_back({"c32_store", [&](Buffers& b) { return hgemm_mi355x_ta_c32(at[idx(b)], b.b, c32[idx(b)], sh.M, sh.N, sh.K, 0, nullptr); }});
+    cs.push_back({"two_step", [&](Buffers& b) {
+                    const int st = hgemm_mi355x_ta_fp32(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, nullptr);
+                    if (st != HGEMM_OK) return st;
+                    add_f16_into_f32_kernel<<<add_grid, 256>>>(c32[idx(b)], b.c, cn);
+                    return hipGetLastError() == hipSuccess ? (int)HGEMM_OK : (int)HGEMM_ERR_HIP; }});
+    const int rounds = 15;
+    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
+    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
+    int cfg = 0, splits = 1;
+    hgemm_mi355x_ta_plan(sh.M, sh.N, sh.K, &cfg, &splits);
+    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"ta\", \"output\": \"c32\", \"ta_config\": \"%s\", \"ta_splits\": %d, \"ta_c32_runs\": %d, \"rounds\": %d, "
+                 "\"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, hgemm_mi355x_ta_config_name(cfg), splits,
+            hgemm_mi355x_ta_c32_runs(cfg, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N), rounds);
+    for (const Contender& c : cs) {
+      const double us = c.iso_us();
+      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
+    }
+    const double acc_us = cs[0].iso_us(), two_us = cs[2].iso_us();
+    fprintf(out, ", \"c32_le_two_step\": %s}\n", acc_us > 0 && two_us > 0 && acc_us <= two_us ? "true" : "false");
+    fflush(out);
+    for (size_t i = 0; i < sets.size(); ++i) { free_set(sets[i]); HIP_OK(hipFree(at[i])); HIP_OK(hipFree(c32[i])); }
+  }
+  HIP_OK(hipEventDestroy(e0));
+  HIP_OK(hipEventDestroy(e1));
+  if (out != stdout) fclose(out);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1217,7 +1352,7 @@ int main(int argc, char** argv) {
   const char* cfg_name = nullptr;
   double keep = 2.5;
   int max_cand = 12, splits = 1, group = 0, reps = 20;
-  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false, layout_ta = false;
+  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false, layout_ta = false, c32 = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -1230,6 +1365,7 @@ int main(int argc, char** argv) {
       if (l != "nn" && l != "tn" && l != "ta") { fprintf(stderr, "--layout takes nn, ta or tn\n"); return 2; }
       layout_nn = l == "nn"; layout_ta = l == "ta";
     }
+    else if (a == "--c32") c32 = true;
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
     else if (a == "--streamk") g_streamk_too = true;
@@ -1285,14 +1421,15 @@ int main(int argc, char** argv) {
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
   }
   if (layout_ta) {   // family a: A given as [K][M] (hgemm_mi355x_launch_ta)
-    if (mode == "check") return cmd_check_nn(kLayoutTA, shapes);
+    if (mode == "check") return c32 ? cmd_check_ta_c32(shapes) : cmd_check_nn(kLayoutTA, shapes);
     if (mode == "bench") {
       if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
-      return cmd_bench_ta(shapes, out_path);
+      return c32 ? cmd_bench_ta_c32(shapes, out_path) : cmd_bench_ta(shapes, out_path);
     }
     fprintf(stderr, "--layout ta goes with check or bench\n");
     return 2;
   }
+  if (c32) { fprintf(stderr, "--c32 goes with --layout ta\n"); return 2; }
   if (layout_nn) {   // family n: B row-major (hgemm_mi355x_launch_nn); the default shapes of the check are cmd_check_nn's
     if (mode == "check") return cmd_check_nn(kLayoutNN, shapes);
     if (mode == "bench") {

@@ -331,6 +331,27 @@ int hgemm_mi355x_ta_plan(int M, int N, int K, int* ta_config, int* splits);
 int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
 size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, int N, int K);
 int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream);
+/* fp32 C, stored or accumulated ("c32"): c32 = A x B or c32 += A x B with the kernels' fp32 accumulators as they are -- the weight
+ * gradient where a training step consumes it, added into an fp32 gradient buffer over the micro-batches (Megatron's main_grad, "wgrad
+ * GEMM accumulate fp32").  Replaces hgemm_mi355x_ta_fp32 into an fp16 scratch (which rounds the sums to fp16: K is the token count, and
+ * a sum beyond 65504 becomes inf) followed by an elementwise main_grad += float(dW16) kernel.  No fp16 value exists on the path: the result is
+ * old + fl32(A x B), one fp32 add per element; the order of the sum is fixed per plan (a split plan adds its K slices in split order,
+ * then the old value), so a call is deterministic.
+ *   accumulate  0: c32 = A x B, the old contents of c32 are never read (they may be NaN or uninitialised); 1: c32 += A x B; any other
+ *               value returns HGEMM_ERR_BAD_ARG
+ * Where the rules differ from the fp16-C calls above: ldc counts fp32 elements, the kernels take ldc % 4 == 0 (not % 8) with a 16-byte
+ * aligned c32, and C's reach is (BM x ldc + N) x 4 bytes below 2 GiB; the least ldc is still N.  Everything else is the TA layout's: the
+ * same table and ids, the same plan (hgemm_mi355x_ta_plan: the tiles are the same), the same workspace
+ * (hgemm_mi355x_ta_plan_workspace_bytes: the slabs are the same; hgemm_mi355x_ta_reserve_workspace serves both forms), the same
+ * meaning of the splits word, bad strides, null pointers and ids outside the table return HGEMM_ERR_BAD_ARG, a split call without a
+ * workspace runs unsplit, any call outside the kernels' scope is answered by a reference kernel (HGEMM_OK, exact, slow:
+ * hgemm_mi355x_ta_c32_runs tells), and every call is capturable.  The NN and b_col_major layouts have no fp32-C form. */
+/* planned, contiguous (lda = M, ldb = ldc = N) */
+int hgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int M, int N, int K, int accumulate, void* stream);
+/* explicit: ta_config / splits words exactly as hgemm_mi355x_launch_ta; ldc in fp32 elements */
+int hgemm_mi355x_launch_ta_c32(int ta_config, int splits, const void* a_col_major, const void* b, float* c32,
+                               int M, int N, int K, int lda, int ldb, int ldc, int accumulate, void* stream);
+int hgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
