@@ -43,6 +43,9 @@ LIB_SOURCES = [
     "hgemm_inst_g5.hip",
     "hgemm_inst_g6.hip",
     "hgemm_inst_g7.hip",
+    "hgemm_inst_g8.hip",
+    "hgemm_inst_g9.hip",
+    "hgemm_inst_g10.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -479,6 +479,33 @@ struct TrOut {
 };
 constexpr TrOut kOutC16{false, false};
 
+// What the operands and a 16-bit C hold: fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements are 2
+// bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  The kind selects a kernel set and nothing else.
+enum TrElem { TR_F16 = 0, TR_BF16 = 1 };
+struct TrKernels {
+  // the EPI_C16 / EPI_SLAB launchers by config id, in the order of the table's rows; null: the rows' own (fp16)
+  const TrLaunch* launch;
+  // fp32 C: the EPI_C32 launchers by config id; null where the layout has none (a c32 call is refused with HGEMM_ERR_BAD_ARG)
+  const TaC32Launch* launch_c32;
+  // the combine of the two-pass form with a 16-bit C (an fp32 C: launch_splitk_reduce_c32, whatever the operands were)
+  void (*combine)(const float*, void*, int, int, int, int, hipStream_t, TimingSlot);
+  // the reference kernels (status 0, exact): answer whatever is outside the kernels' scope or reach
+  void (*reference)(const void*, const void*, void*, int, int, int, int, int, int, hipStream_t, TimingSlot);
+  void (*reference_c32)(const void*, const void*, float*, int, int, int, int, int, int, bool, hipStream_t, TimingSlot);
+};
+// the typed launchers of hgemm_registry.hip behind TrKernels' untyped pointers
+template <class T, void (*F)(const float*, T*, int, int, int, int, hipStream_t, TimingSlot)>
+void tr_combine(const float* p, void* c, int M, int N, int ldc, int splits, hipStream_t s, TimingSlot ts) { F(p, (T*)c, M, N, ldc, splits, s, ts); }
+template <class T, void (*F)(const T*, const T*, T*, int, int, int, int, int, int, hipStream_t, TimingSlot)>
+void tr_reference(const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t s, TimingSlot ts) {
+  F((const T*)a, (const T*)b, (T*)c, M, N, K, lda, ldb, ldc, s, ts);
+}
+template <class T, void (*F)(const T*, const T*, float*, int, int, int, int, int, int, bool, hipStream_t, TimingSlot)>
+void tr_reference_c32(const void* a, const void* b, float* c, int M, int N, int K, int lda, int ldb, int ldc, bool acc, hipStream_t s,
+                      TimingSlot ts) {
+  F((const T*)a, (const T*)b, c, M, N, K, lda, ldb, ldc, acc, s, ts);
+}
+
 struct TrLayout {
   const NNEntry* table;
   const int& count;
@@ -486,17 +513,12 @@ struct TrLayout {
   // addressed from a tile's first row.  true (a): [K][lda], k-rows of M elements, staged as B is and addressed from row 0 to the end
   // of the matrix; a chunk of a k-row must not straddle M, so M % 8 == 0 joins the scope.
   bool a_col_major;
-  // the reference kernel of the layout (status 0, exact): answers whatever is outside the kernels' scope or reach
-  void (*reference)(const f16*, const f16*, f16*, int, int, int, int, int, int, hipStream_t, TimingSlot);
-  // fp32 C: the EPI_C32 launchers by config id and the reference kernel of that output; null where the layout has none (a c32 call is
-  // refused with HGEMM_ERR_BAD_ARG)
-  const TaC32Launch* launch_c32;
-  void (*reference_c32)(const f16*, const f16*, float*, int, int, int, int, int, int, bool, hipStream_t, TimingSlot);
+  TrKernels kernels[2];   // by TrElem
 
   // elements in a row of A: the least lda, and the lda of a contiguous A (the planned calls pass strides (a_row, N, N))
   int a_row(int M, int K) const { return a_col_major ? M : K; }
   // the kernels' scope; everything else is answered by the reference kernel.  Rows of C start at 16-byte boundaries: ldc % 8 == 0 of
-  // an fp16 C, ldc % 4 == 0 of an fp32 C (next to a_col_major's rule: the output kind changes C's rules only)
+  // a 16-bit C, ldc % 4 == 0 of an fp32 C (next to a_col_major's rule: the output kind changes C's rules only)
   bool path_ok(TrOut out, const void* a, const void* b, const void* c, int M, int N, int K, int lda, int ldb, int ldc) const {
     if (K % BK != 0 || (N & 7) != 0 || (a_col_major && (M & 7) != 0)) return false;
     if ((lda & 7) || (ldb & 7) || (ldc & (out.c32 ? 3 : 7))) return false;
@@ -510,8 +532,14 @@ struct TrLayout {
     return a_bytes < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 && c_bytes < 2147483648.0;
   }
 };
-const TrLayout kLayoutNN{g_nn_table, g_num_nn, false, launch_generic, nullptr, nullptr};
-const TrLayout kLayoutTA{g_ta_table, g_num_ta, true, launch_generic_ta, g_ta_c32_launch, launch_generic_ta_c32};
+const TrLayout kLayoutNN{g_nn_table, g_num_nn, false,
+                         {{nullptr, nullptr, tr_combine<f16, launch_splitk_reduce>, tr_reference<f16, launch_generic>, nullptr},
+                          {g_nn_bf16_launch, nullptr, tr_combine<bf16, launch_splitk_reduce_bf16>, tr_reference<bf16, launch_generic_nn_bf16>, nullptr}}};
+const TrLayout kLayoutTA{g_ta_table, g_num_ta, true,
+                         {{nullptr, g_ta_c32_launch, tr_combine<f16, launch_splitk_reduce>, tr_reference<f16, launch_generic_ta>,
+                           tr_reference_c32<f16, launch_generic_ta_c32>},
+                          {g_ta_bf16_launch, g_ta_bf16_c32_launch, tr_combine<bf16, launch_splitk_reduce_bf16>,
+                           tr_reference<bf16, launch_generic_ta_bf16>, tr_reference_c32<bf16, launch_generic_ta_c32_bf16>}}};
 
 // (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn / _ta show it to the CPU tests)
 // out.c32: the same tiles, cuts and slabs; the plain dispatch and the combine carry EPI_C32 (the K slices are the family's EPI_SLAB
@@ -526,7 +554,7 @@ LaunchPlan tr_resolve(const TrLayout& L, TrOut out, int config, int splits_arg, 
   };
   // rows must not overlap: lda >= K (n) / >= M, the row stride of a_col_major (a); ldb >= N (B is row-major here), ldc >= N
   if (config < 0 || config >= L.count || lda < L.a_row(M, K) || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
-  if ((out.c32 && !L.launch_c32) || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no fp32 C in this layout
+  if ((out.c32 && !L.kernels[TR_F16].launch_c32) || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no fp32 C in this layout
   const int epi_out = out.c32 ? EPI_C32 : EPI_C16;
   const NNEntry& e = L.table[config];
   GemmArgs g{};
@@ -589,7 +617,8 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 
 // GemmArgs as the kernels read it: A = a (n: [M][lda], a: [K][lda]), Bt = the row-major B
 // (out.c32: c is the float pointer; it travels in g.C and the EPI_C32 kernels reinterpret it)
-int tr_launch(const TrLayout& L, TrOut out, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda,
+// elem: the kernel set (by config id), the combine and the reference kernel; the plan does not depend on it
+int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda,
               int ldb, int ldc, void* stream) {
   DisarmTiming disarm_timing;
   if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
@@ -609,24 +638,26 @@ int tr_launch(const TrLayout& L, TrOut out, int config, int splits_arg, const vo
     }
   }
   if (p.status != HGEMM_OK) return p.status;
+  const TrKernels& kern = L.kernels[elem];
   for (int i = 0; i < p.n; ++i) {
     GemmArgs& g = p.d[i].g;
-    g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;
+    g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (bf16 travels in the same fields: the kernels of its Cfgs reinterpret)
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
     const bool c32 = p.d[i].epi == EPI_C32;
     switch (p.d[i].thunk) {
       case THUNK_ENTRY:
-        if (c32) L.launch_c32[config](g, p.d[i].grid, s, ts);
-        else     L.table[config].launch(g, p.d[i].grid, s, p.d[i].epi, ts);
+        if (c32)           kern.launch_c32[config](g, p.d[i].grid, s, ts);
+        else if (kern.launch) kern.launch[config](g, p.d[i].grid, s, p.d[i].epi, ts);
+        else               L.table[config].launch(g, p.d[i].grid, s, p.d[i].epi, ts);
         break;
       case THUNK_SPLITK_REDUCE:
         if (c32) launch_splitk_reduce_c32(g.partial, (float*)c, M, N, ldc, g.splits, out.accumulate, s, ts);
-        else     launch_splitk_reduce(g.partial, g.C, M, N, ldc, g.splits, s, ts);
+        else     kern.combine(g.partial, c, M, N, ldc, g.splits, s, ts);
         break;
       default:
-        if (c32) L.reference_c32((const f16*)a, (const f16*)b, (float*)c, M, N, K, lda, ldb, ldc, out.accumulate, s, ts);
-        else     L.reference((const f16*)a, (const f16*)b, (f16*)c, M, N, K, lda, ldb, ldc, s, ts);
+        if (c32) kern.reference_c32(a, b, (float*)c, M, N, K, lda, ldb, ldc, out.accumulate, s, ts);
+        else     kern.reference(a, b, c, M, N, K, lda, ldb, ldc, s, ts);
         break;
     }
   }
@@ -636,11 +667,11 @@ int tr_launch(const TrLayout& L, TrOut out, int config, int splits_arg, const vo
 }
 
 // the planned call on contiguous operands
-int tr_run(const TrLayout& L, TrOut out, const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
+int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   int cfg, splits;
   tr_model_plan(L, M, N, K, &cfg, &splits);
-  return tr_launch(L, out, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), N, N, stream);
+  return tr_launch(L, elem, out, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), N, N, stream);
 }
 
 const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.count) ? L.table[id].name : nullptr; }
@@ -961,10 +992,10 @@ size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, in
 int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutNN, M, N, K, stream); }
 int hgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
                            int ldc, void* stream) {
-  return tr_launch(kLayoutNN, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutNN, TR_F16, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
 }
-int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, kOutC16, a, b, c, M, N, K, stream); }
-int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, kOutC16, a, b, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_F16, kOutC16, a, b, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_F16, kOutC16, a, b, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
   return tr_selfcheck_launch(kLayoutNN, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
@@ -982,10 +1013,10 @@ size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, in
 int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutTA, M, N, K, stream); }
 int hgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
                            int ldb, int ldc, void* stream) {
-  return tr_launch(kLayoutTA, kOutC16, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTA, TR_F16, kOutC16, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
 }
-int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, kOutC16, a_col_major, b, c, M, N, K, stream); }
-int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, kOutC16, a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_F16, kOutC16, a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_F16, kOutC16, a_col_major, b, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
   return tr_selfcheck_launch(kLayoutTA, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
@@ -996,16 +1027,58 @@ int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, in
 int hgemm_mi355x_launch_ta_c32(int ta_config, int splits_arg, const void* a_col_major, const void* b, float* c32, int M, int N, int K, int lda,
                                int ldb, int ldc, int accumulate, void* stream) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_launch(kLayoutTA, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, c32, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, c32, M, N, K, lda, ldb, ldc, stream);
 }
 int hgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int M, int N, int K, int accumulate, void* stream) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_run(kLayoutTA, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
+  return tr_run(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
 }
 int hgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
   return tr_runs(kLayoutTA, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
 }
 int hgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int accumulate,
+                                         int ruled_out, long long out[20]) {
+  if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTA, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- bfloat16 operands and 16-bit C on the two transposed-read layouts: the same path with the other element kind.  Tables, ids, plans,
+// workspace sizes and the reserve calls are the hgemm_mi355x_nn_ / _ta_ functions' (elements are 2 bytes either way); the b_col_major
+// families have no bf16 form.
+int bgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
+                           int ldc, void* stream) {
+  return tr_launch(kLayoutNN, TR_BF16, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
+}
+int bgemm_mi355x_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_BF16, kOutC16, a, b, c, M, N, K, stream); }
+int bgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, kOutC16, nn_config, M, N, K, lda, ldb, ldc); }
+int bgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
+                           int ldb, int ldc, void* stream) {
+  return tr_launch(kLayoutTA, TR_BF16, kOutC16, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
+}
+int bgemm_mi355x_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_BF16, kOutC16, a_col_major, b, c, M, N, K, stream); }
+int bgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, kOutC16, ta_config, M, N, K, lda, ldb, ldc); }
+int bgemm_mi355x_launch_ta_c32(int ta_config, int splits_arg, const void* a_col_major, const void* b, float* c32, int M, int N, int K, int lda,
+                               int ldb, int ldc, int accumulate, void* stream) {
+  if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, c32, M, N, K, lda, ldb, ldc, stream);
+}
+int bgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int M, int N, int K, int accumulate, void* stream) {
+  if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
+}
+int bgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
+  return tr_runs(kLayoutTA, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
+}
+// (the CPU tests' view, not part of the public header: the plan is the fp16 twin's -- the element kind is not an input of tr_resolve)
+int bgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                     long long out[20]) {
+  return tr_selfcheck_launch(kLayoutNN, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                     long long out[20]) {
+  return tr_selfcheck_launch(kLayoutTA, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int accumulate,
                                          int ruled_out, long long out[20]) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
   return tr_selfcheck_launch(kLayoutTA, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);

@@ -68,7 +68,7 @@ rocblas_handle g_rocblas = nullptr;
 
 // ta: A is a_col_major ([K][M]), the column-major product's second operand transposed with ld = M (b then row-major, tn = false)
 int rocblas_run(bool tn, const void* a, const void* b, void* c, int M, int N, int K, int acc,
-                void* stream, bool ta = false) {
+                void* stream, bool ta = false, bool bf16 = false) {
   if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   if (!g_rocblas) {
     int st = hgemm_rocblas_init();
@@ -78,14 +78,14 @@ int rocblas_run(bool tn, const void* a, const void* b, void* c, int M, int N, in
     return HGEMM_ERR_BACKEND;
   const float alpha32 = 1.0f, beta32 = 0.0f;
   const f16 alpha16 = (f16)1.0f, beta16 = (f16)0.0f;
-  const bool h = (acc == HGEMM_ACC_FP16);
+  const bool h = (acc == HGEMM_ACC_FP16) && !bf16;   // (bf16 operands and C: fp32 compute only)
+  const rocblas_datatype et = bf16 ? rocblas_datatype_bf16_r : rocblas_datatype_f16_r;
   const void* alpha = h ? (const void*)&alpha16 : (const void*)&alpha32;
   const void* beta  = h ? (const void*)&beta16 : (const void*)&beta32;
   const rocblas_datatype ct = h ? rocblas_datatype_f16_r : rocblas_datatype_f32_r;
   rocblas_status rs = rocblas_gemm_ex(
       g_rocblas, tn ? rocblas_operation_transpose : rocblas_operation_none, ta ? rocblas_operation_transpose : rocblas_operation_none,
-      N, M, K, alpha, b, rocblas_datatype_f16_r, tn ? K : N, a, rocblas_datatype_f16_r, ta ? M : K, beta, c,
-      rocblas_datatype_f16_r, N, c, rocblas_datatype_f16_r, N, ct, rocblas_gemm_algo_standard, 0, 0);
+      N, M, K, alpha, b, et, tn ? K : N, a, et, ta ? M : K, beta, c, et, N, c, et, N, ct, rocblas_gemm_algo_standard, 0, 0);
   return rs == rocblas_status_success ? HGEMM_OK : HGEMM_ERR_BACKEND;
 }
 
@@ -512,6 +512,13 @@ int hgemm_rocblas_tn(const void* a, const void* bt, void* c, int M, int N, int K
 }
 int hgemm_rocblas_ta(const void* at, const void* b, void* c, int M, int N, int K, int acc, void* stream) {
   return rocblas_run(false, at, b, c, M, N, K, acc, stream, true);
+}
+
+int bgemm_rocblas_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
+  return rocblas_run(false, a, b, c, M, N, K, HGEMM_ACC_FP32, stream, false, true);
+}
+int bgemm_rocblas_ta(const void* at, const void* b, void* c, int M, int N, int K, void* stream) {
+  return rocblas_run(false, at, b, c, M, N, K, HGEMM_ACC_FP32, stream, true, true);
 }
 
 int hgemm_hipblaslt_heuristic_init(void) { return lt_init(g_heur); }

@@ -44,6 +44,7 @@ __host__ __device__ constexpr int nn_swz(int krow) {
 // is filled in 1-KiB DMA pieces, A_BYTES / 1024 of them.
 template <int BM_, int BN_, int WM_, int WN_, int NBUF_, int A_BYTES_>
 struct CfgTR {
+  using elem = f16;   // the operands' and the 16-bit C's element; the bf16 Cfgs (CfgNNB below, CfgTAB) name __bf16
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, MI = 16, NBUF = NBUF_;
   static constexpr int NW          = WM * WN;
   static constexpr int THREADS     = NW * 64;
@@ -82,6 +83,24 @@ struct CfgNN : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
   static constexpr auto kernel() { return &hgemm_nn_kernel<CfgNN, EPI>; }   // the family's entry point (launch_tr)
 };
 
+// bfloat16 operands and 16-bit C (bgemm_mi355x_nn, hgemm_inst_g8.hip): the same images, DMA pieces, counts and ring -- elements are 2
+// bytes either way and the transposed read does not look into them.  CFG::elem selects, in the kernel text below, the fragment type,
+// v_mfma_f32_16x16x32_bf16 and the epilogue's convert (v_cvt_pk_bf16_f32: round to nearest even, once); nothing else asks for it.  A
+// Cfg of its own, so that CfgNN's kernels keep their symbols and, as compiled, their instruction streams.
+template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
+struct CfgNNB : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
+  using elem = __bf16;
+  template <int EPI>
+  static constexpr auto kernel() { return &hgemm_nn_kernel<CfgNNB, EPI>; }
+};
+
+// the K = 32 MFMA of the element type: fp32 accumulation, eight-element fragments, the same rate for both
+template <class V>
+__device__ __forceinline__ f32x4 tr_mfma(V b, V a, f32x4 c) {
+  if constexpr (__is_same(V, f16x8)) return __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, c, 0, 0, 0);
+  else                               return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
+}
+
 // GemmArgs as the kernel reads it: Bt = the ROW-MAJOR B ([K][ldb]), ldb >= N its row stride; tail_tiles = 0, counters = nullptr.
 template <class CFG, int EPI>
 __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g) {
@@ -89,6 +108,9 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BM = CFG::BM, BN = CFG::BN, NBUF = CFG::NBUF;
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
+  using elem = typename CFG::elem;   // f16, or __bf16 (the bgemm_ entry points)
+  using ex4 = __attribute__((ext_vector_type(4))) elem;
+  using ex8 = __attribute__((ext_vector_type(8))) elem;
   static_assert(EPI == EPI_C16 || EPI == EPI_SLAB, "plain and two-pass slab epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
@@ -191,20 +213,20 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
     const char* st = smem + rd * CFG::STAGE_BYTES;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      f16x8 af[FM], bf[FN];
+      ex8 af[FM], bf[FN];
 #pragma unroll
-      for (int i = 0; i < FM; ++i) af[i] = *(const f16x8*)(st + i * 16 * ROW_BYTES + a_off[ks]);
+      for (int i = 0; i < FM; ++i) af[i] = *(const ex8*)(st + i * 16 * ROW_BYTES + a_off[ks]);
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
         const char* pb = st + ks * 32 * CFG::B_ROW_BYTES;
-        const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[0][j])));
-        const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[1][j])));
+        const ex4 lo = __builtin_bit_cast(ex4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[0][j])));
+        const ex4 hi = __builtin_bit_cast(ex4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[1][j])));
         bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
       }
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < FN; ++j) acc[i][j] = tr_mfma(bf[j], af[i], acc[i][j]);
     }
     rd = (rd + 1 == NBUF) ? 0 : rd + 1;
     wr = (wr + 1 == NBUF) ? 0 : wr + 1;
@@ -213,12 +235,12 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
   if constexpr (EPI == EPI_SLAB) {
     store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
   } else {
-    // fp16 C, the 16-byte form of store_tile_row alone (the host sends the kernel N % 8 == 0, ldc % 8 == 0 and a 16-byte aligned
+    // 16-bit C (fp16, or bf16 from v_cvt_pk_bf16_f32: round to nearest even, once), the 16-byte form of store_tile_row alone (the host sends the kernel N % 8 == 0, ldc % 8 == 0 and a 16-byte aligned
     // C): v_permlane16_swap exchanges the odd 16-lane rows of column tile j with the even rows of tile j + 1, after which row
     // q = lane >> 4 owns n = 16 (j + (q & 1)) + 8 (q >> 1) + 0 .. 7 of its C row.  Buffer stores: the non-temporal form is an
     // instruction of its own (two plain C++ stores that differ only in the hint are merged by the optimiser and the hint is lost);
     // the tile's bytes are below 2 GiB from its first row (host check).
-    using h2 = __attribute__((ext_vector_type(2))) _Float16;
+    using h2 = __attribute__((ext_vector_type(2))) elem;
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
     const int q = lane >> 4;
 #pragma unroll
@@ -227,8 +249,8 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
       const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
 #pragma unroll
       for (int j = 0; j < FN; j += 2) {
-        const h2 a01 = {(f16)acc[i][j][0], (f16)acc[i][j][1]}, a23 = {(f16)acc[i][j][2], (f16)acc[i][j][3]};
-        const h2 b01 = {(f16)acc[i][j + 1][0], (f16)acc[i][j + 1][1]}, b23 = {(f16)acc[i][j + 1][2], (f16)acc[i][j + 1][3]};
+        const h2 a01 = {(elem)acc[i][j][0], (elem)acc[i][j][1]}, a23 = {(elem)acc[i][j][2], (elem)acc[i][j][3]};
+        const h2 b01 = {(elem)acc[i][j + 1][0], (elem)acc[i][j + 1][1]}, b23 = {(elem)acc[i][j + 1][2], (elem)acc[i][j + 1][3]};
         const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, b01), false, false);
         const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, b23), false, false);
         const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);

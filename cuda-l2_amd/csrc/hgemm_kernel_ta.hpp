@@ -56,6 +56,14 @@ struct CfgTA : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BK * BM_ * 2> {
   static constexpr auto kernel() { return &hgemm_ta_kernel<CfgTA, EPI>; }   // the family's entry point (launch_tr)
 };
 
+// bfloat16 operands and 16-bit C (bgemm_mi355x_ta / _ta_c32, hgemm_inst_g9.hip / g10): CfgNNB's trait on this family's Cfg (hgemm_kernel_nn.hpp)
+template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
+struct CfgTAB : CfgTA<BM_, BN_, WM_, WN_, NBUF_> {
+  using elem = __bf16;
+  template <int EPI>
+  static constexpr auto kernel() { return &hgemm_ta_kernel<CfgTAB, EPI>; }
+};
+
 // GemmArgs as the kernel reads it: A = a_col_major ([K][lda], lda >= M its row stride), Bt = the ROW-MAJOR B ([K][ldb], ldb >= N);
 // tail_tiles = 0, counters = nullptr.
 template <class CFG, int EPI>
@@ -64,6 +72,9 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int BM = CFG::BM, BN = CFG::BN, NBUF = CFG::NBUF;
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
+  using elem = typename CFG::elem;   // f16, or __bf16 (the bgemm_ entry points)
+  using ex4 = __attribute__((ext_vector_type(4))) elem;
+  using ex8 = __attribute__((ext_vector_type(8))) elem;
   static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || EPI == EPI_C32, "plain (fp16 C, fp32 C) and two-pass slab epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
@@ -165,25 +176,25 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
     const char* st = smem + rd * CFG::STAGE_BYTES;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      f16x8 af[FM], bf[FN];
+      ex8 af[FM], bf[FN];
       const char* pa = st + ks * 32 * CFG::A_ROW_BYTES;
       const char* pb = st + ks * 32 * CFG::B_ROW_BYTES;
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
-        const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pa + a_off[0][i])));
-        const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pa + a_off[1][i])));
+        const ex4 lo = __builtin_bit_cast(ex4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pa + a_off[0][i])));
+        const ex4 hi = __builtin_bit_cast(ex4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pa + a_off[1][i])));
         af[i] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
       }
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
-        const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[0][j])));
-        const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[1][j])));
+        const ex4 lo = __builtin_bit_cast(ex4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[0][j])));
+        const ex4 hi = __builtin_bit_cast(ex4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_t*)(pb + b_off[1][j])));
         bf[j] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
       }
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
-        for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < FN; ++j) acc[i][j] = tr_mfma(bf[j], af[i], acc[i][j]);
     }
     rd = (rd + 1 == NBUF) ? 0 : rd + 1;
     wr = (wr + 1 == NBUF) ? 0 : wr + 1;
@@ -234,11 +245,11 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
       }
     }
   } else {
-    // fp16 C, family n's 16-byte form (N % 8 == 0, ldc % 8 == 0, a 16-byte aligned C): v_permlane16_swap exchanges the odd 16-lane
+    // 16-bit C (fp16, or bf16 from v_cvt_pk_bf16_f32: round to nearest even, once), family n's 16-byte form (N % 8 == 0, ldc % 8 == 0, a 16-byte aligned C): v_permlane16_swap exchanges the odd 16-lane
     // rows of column tile j with the even rows of tile j + 1, after which row q = lane >> 4 owns n = 16 (j + (q & 1)) + 8 (q >> 1)
     // + 0 .. 7 of its C row.  Buffer stores, the non-temporal form an instruction of its own; the tile's bytes are below 2 GiB from
     // its first row (host check).
-    using h2 = __attribute__((ext_vector_type(2))) _Float16;
+    using h2 = __attribute__((ext_vector_type(2))) elem;
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
     const int q = lane >> 4;
 #pragma unroll
@@ -247,8 +258,8 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
       const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
 #pragma unroll
       for (int j = 0; j < FN; j += 2) {
-        const h2 a01 = {(f16)acc[i][j][0], (f16)acc[i][j][1]}, a23 = {(f16)acc[i][j][2], (f16)acc[i][j][3]};
-        const h2 b01 = {(f16)acc[i][j + 1][0], (f16)acc[i][j + 1][1]}, b23 = {(f16)acc[i][j + 1][2], (f16)acc[i][j + 1][3]};
+        const h2 a01 = {(elem)acc[i][j][0], (elem)acc[i][j][1]}, a23 = {(elem)acc[i][j][2], (elem)acc[i][j][3]};
+        const h2 b01 = {(elem)acc[i][j + 1][0], (elem)acc[i][j + 1][1]}, b23 = {(elem)acc[i][j + 1][2], (elem)acc[i][j + 1][3]};
         const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, b01), false, false);
         const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, b23), false, false);
         const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);
@@ -281,5 +292,26 @@ void launch_splitk_reduce_c32(const float* partial, float* C32, int M, int N, in
                               TimingSlot ts);
 void launch_generic_ta_c32(const f16* a_col_major, const f16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
                            hipStream_t stream, TimingSlot ts);
+
+// ---- bfloat16 (CfgNNB / CfgTAB; the bgemm_mi355x_ entry points): launchers by config id in HGEMM_TR_MEMBERS order, the order of
+// g_nn_table's and g_ta_table's rows (hgemm_inst_g8.hip: family n, g9: family a, g10: family a's fp32 C); the bf16 combine of the two-pass
+// form and the three reference kernels (hgemm_registry.hip).  The fp32-C combine is launch_splitk_reduce_c32: slabs are fp32 whatever
+// the operands were.
+using bf16 = __bf16;
+using TrLaunch = void (*)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+extern const TrLaunch g_nn_bf16_launch[];
+extern const int g_num_nn_bf16;
+extern const TrLaunch g_ta_bf16_launch[];
+extern const int g_num_ta_bf16;
+extern const TaC32Launch g_ta_bf16_c32_launch[];
+extern const int g_num_ta_bf16_c32;
+#define HGEMM_TR_LAUNCH_ROW(P, CFG, BM, BN, WM, WN, NB) &launch_tr<CFG<BM, BN, WM, WN, NB>>,
+void launch_splitk_reduce_bf16(const float* partial, bf16* C, int M, int N, int ldc, int splits, hipStream_t stream, TimingSlot ts);
+void launch_generic_nn_bf16(const bf16* A, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
+                            TimingSlot ts);
+void launch_generic_ta_bf16(const bf16* a_col_major, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc,
+                            hipStream_t stream, TimingSlot ts);
+void launch_generic_ta_c32_bf16(const bf16* a_col_major, const bf16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc,
+                                bool accumulate, hipStream_t stream, TimingSlot ts);
 
 }  // namespace hgemm_mi355x

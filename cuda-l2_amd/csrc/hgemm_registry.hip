@@ -131,6 +131,35 @@ __global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* _
   }
 }
 
+// The combine of the bfloat16 calls (bgemm_mi355x_nn / _ta): hgemm_splitk_reduce_kernel with the other last step -- the fp32 slabs added in
+// split order, the sum rounded to bf16 once (round to nearest even).  Slabs are fp32 whatever the operands were; the fp32-C form of the
+// bf16 calls combines with hgemm_splitk_reduce_c32_kernel below as it is.
+__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bf16_kernel(const float* __restrict__ partial, bf16* __restrict__ C, int M, int N,
+                                                                       int ldc, int splits) {
+  using bf16x4 = __attribute__((ext_vector_type(4))) bf16;
+  const size_t total4 = ((size_t)M * N) >> 2;  // N % 4 == 0 on this path
+  const size_t slab   = (size_t)M * N;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = q << 2;
+    f32x4 s = *(const f32x4*)(partial + e);
+    int k = 1;
+    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
+      f32x4 p[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += p[u];
+    }
+    for (; k < splits; ++k) {
+      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
+      s += p;
+    }
+    const int m = (int)(e / N), n = (int)(e % N);
+    bf16x4 o = {(bf16)s[0], (bf16)s[1], (bf16)s[2], (bf16)s[3]};
+    *(bf16x4*)(C + (size_t)m * ldc + n) = o;
+  }
+}
+
 // The combine of family a's fp32-C calls (hgemm_mi355x_ta_c32): t = p[0] + p[1] + ... + p[S-1] in split order, then
 // C32 = accumulate ? C32 + t : t -- the shape of the unsplit result, old + fl(sum), and one fixed order per plan.  C32 is read only
 // with `accumulate`; rows are ldc fp32 elements apart and the pad between N and ldc is never touched.  (N % 4 == 0, ldc % 4 == 0 and
@@ -229,6 +258,45 @@ __global__ void __launch_bounds__(256) hgemm_generic_ta_c32_kernel(const f16* __
   }
 }
 
+// The reference kernels of the bfloat16 calls: the three above on bf16 operands -- one output per thread, an fma chain in k order, the
+// same last step (one round to nearest even to bf16; none for the fp32 C).
+__global__ void __launch_bounds__(256) hgemm_generic_nn_bf16_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
+                                                                    bf16* __restrict__ C, int M, int N, int K, int lda, int ldb_rowmajor,
+                                                                    int ldc) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    C[(size_t)m * ldc + n] = (bf16)s;
+  }
+}
+
+__global__ void __launch_bounds__(256) hgemm_generic_ta_bf16_kernel(const bf16* __restrict__ At, const bf16* __restrict__ B,
+                                                                    bf16* __restrict__ C, int M, int N, int K, int lda_colmajor,
+                                                                    int ldb_rowmajor, int ldc) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    C[(size_t)m * ldc + n] = (bf16)s;
+  }
+}
+
+__global__ void __launch_bounds__(256) hgemm_generic_ta_c32_bf16_kernel(const bf16* __restrict__ At, const bf16* __restrict__ B,
+                                                                        float* __restrict__ C32, int M, int N, int K, int lda_colmajor,
+                                                                        int ldb_rowmajor, int ldc, int accumulate) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    float* out = C32 + (size_t)m * ldc + n;
+    *out = accumulate ? *out + s : s;
+  }
+}
+
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
   const size_t quads = ((size_t)M * N) >> 2;
@@ -248,6 +316,15 @@ void launch_splitk_reduce_c32(const float* partial, float* C32, int M, int N, in
   if (grid > 256 * 8) grid = 256 * 8;
   if (grid < 1) grid = 1;
   HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, grid, threads, stream, ts, partial, C32, M, N, ldc, splits, accumulate ? 1 : 0);
+}
+
+void launch_splitk_reduce_bf16(const float* partial, bf16* C, int M, int N, int ldc, int splits, hipStream_t stream, TimingSlot ts) {
+  const size_t quads = ((size_t)M * N) >> 2;
+  const int threads = quads <= 64 * 1024 ? 64 : 256;   // (launch_splitk_reduce's sizing)
+  int grid = (int)((quads + threads - 1) / threads);
+  if (grid > 256 * 8) grid = 256 * 8;
+  if (grid < 1) grid = 1;
+  HGEMM_LAUNCH(hgemm_splitk_reduce_bf16_kernel, grid, threads, stream, ts, partial, C, M, N, ldc, splits);
 }
 
 void launch_tail_reduce(const GemmArgs& g, int BM, int BN, hipStream_t stream, TimingSlot ts) {
@@ -293,6 +370,24 @@ void launch_generic_ta_c32(const f16* a_col_major, const f16* B, float* C32, int
                            hipStream_t stream, TimingSlot ts) {
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
   HGEMM_LAUNCH(hgemm_generic_ta_c32_kernel, grid, 256, stream, ts, a_col_major, B, C32, M, N, K, lda, ldb, ldc, accumulate ? 1 : 0);
+}
+
+void launch_generic_nn_bf16(const bf16* A, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
+                            TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH(hgemm_generic_nn_bf16_kernel, grid, 256, stream, ts, A, B, C, M, N, K, lda, ldb, ldc);
+}
+
+void launch_generic_ta_bf16(const bf16* a_col_major, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc,
+                            hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH(hgemm_generic_ta_bf16_kernel, grid, 256, stream, ts, a_col_major, B, C, M, N, K, lda, ldb, ldc);
+}
+
+void launch_generic_ta_c32_bf16(const bf16* a_col_major, const bf16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc,
+                                bool accumulate, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH(hgemm_generic_ta_c32_bf16_kernel, grid, 256, stream, ts, a_col_major, B, C32, M, N, K, lda, ldb, ldc, accumulate ? 1 : 0);
 }
 
 }  // namespace hgemm_mi355x

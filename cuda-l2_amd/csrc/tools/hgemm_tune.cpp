@@ -24,6 +24,13 @@
 //   hgemm_tune bench --layout ta --c32 --shapes ... [--out F.jsonl]   the accumulate call against ta_fp32 + an elementwise add
 //                                                     that check first, then per shape interleaved rounds of the planned TA call, the
 //                                                     NN call on a pre-transposed A, a copy of A's bytes + that NN call, rocBLAS
+//   hgemm_tune check --layout nn|ta [--c32] --bf16 [--shapes ...]   the bfloat16 calls (bgemm_mi355x_launch_nn / _ta / _ta_c32): the same
+//                                                     check, the expected 16-bit C rounded to bf16 once (nearest even)
+//   hgemm_tune bench --layout nn|ta [--c32] --bf16 --shapes ... [--out F.jsonl]
+//                                                     that check first, then per shape interleaved rounds of the planned bf16 call, the
+//                                                     fp16 call of the same plan and shape (c32: both accumulate) and -- context only --
+//                                                     rocBLAS with bf16 in and out; "bf16_le_fp16": bf16 <= fp16 + the fp16 call's own
+//                                                     round-to-round spread (its slowest round minus its median)
 //   hgemm_tune bench --layout nn --shapes ... [--autotune] [--out F.jsonl]
 //                                                     that check first, then per shape interleaved rounds of the planned NN call, the
 //                                                     reference kernel on the same operands, hipBLASLt _nn and the shipped TN plan
@@ -460,7 +467,7 @@ static int cmd_check(const std::vector<Shape>& shapes) {
             size_t bad = 0;
             for (size_t i = 0; i < cn; ++i)
               if (memcmp(&got[i], &truth[i], 2) != 0) {
-                if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) printf("   bad m=%zu n=%zu got %g want %g\n", i / sh.N, i % sh.N, (float)got[i], (float)truth[i]);
+                if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) printf("   bad m=%zu n=%zu got 0x%04x want 0x%04x\n", i / sh.N, i % sh.N, got[i], truth[i]);
                 ++bad;
               }
             if (bad) {
@@ -1015,6 +1022,24 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
 // kLayoutTA: the same check of family a (hgemm_kernel_ta.hpp) -- A handed over as a_col_major [K][M], lda = M; the default shapes add
 // M % 8 != 0 to what the kernel does not take and an 8-row sliver to what it does.
 // One record per transposed-read layout: the family's C ABI, how A is handed over, the words of its output.
+// --bf16: the record's bfloat16 entry points; operands are converted on the host (0 and 1 are bf16 values), the expected 16-bit C is the
+// integer sum rounded to bf16 once.
+static bool g_bf16 = false;
+static uint16_t bf16_rne(float x) {   // round to nearest even (finite inputs)
+  uint32_t u;
+  memcpy(&u, &x, 4);
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+// fp16 values as fp16 or -- --bf16 -- as bf16 bits, ready for upload
+static std::vector<uint16_t> operand_bits(const std::vector<f16>& v) {
+  std::vector<uint16_t> o(v.size());
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (g_bf16) o[i] = bf16_rne((float)v[i]);
+    else memcpy(&o[i], &v[i], 2);
+  }
+  return o;
+}
+
 struct TrLayout {
   const char* label;            // "nn" / "ta": --layout, the JSON field prefix, the check's lines
   const char* kernels;
@@ -1025,33 +1050,45 @@ struct TrLayout {
   int (*plan)(int, int, int, int*, int*);
   int (*runs)(int, int, int, int, int, int, int);
   int (*launch)(int, int, const void*, const void*, void*, int, int, int, int, int, int, void*);
+  int (*planned)(const void*, const void*, void*, int, int, int, void*);
+  // the bfloat16 twins (--bf16); table, names and plan are shared
+  int (*runs_bf16)(int, int, int, int, int, int, int);
+  int (*launch_bf16)(int, int, const void*, const void*, void*, int, int, int, int, int, int, void*);
+  int (*planned_bf16)(const void*, const void*, void*, int, int, int, void*);
+  int (*rocblas_bf16)(const void*, const void*, void*, int, int, int, void*);
   int lda(const Shape& sh) const { return a_col_major ? sh.M : sh.K; }
 };
 static const TrLayout kLayoutNN = {"nn", "the NN kernels",
                                    "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
                                    "200_136_72,200_100_128,33_17_40",
                                    false, hgemm_mi355x_nn_num_configs, hgemm_mi355x_nn_config_name, hgemm_mi355x_nn_plan, hgemm_mi355x_nn_runs,
-                                   hgemm_mi355x_launch_nn};
+                                   hgemm_mi355x_launch_nn, hgemm_mi355x_nn_fp32, bgemm_mi355x_nn_runs, bgemm_mi355x_launch_nn, bgemm_mi355x_nn,
+                                   bgemm_rocblas_nn};
 static const TrLayout kLayoutTA = {"ta", "the TA kernels",
                                    "64_64_64,8_8_64,72_72_128,200_264_192,136_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
                                    "200_136_72,200_100_128,100_136_128,33_17_40",
                                    true, hgemm_mi355x_ta_num_configs, hgemm_mi355x_ta_config_name, hgemm_mi355x_ta_plan, hgemm_mi355x_ta_runs,
-                                   hgemm_mi355x_launch_ta};
+                                   hgemm_mi355x_launch_ta, hgemm_mi355x_ta_fp32, bgemm_mi355x_ta_runs, bgemm_mi355x_launch_ta, bgemm_mi355x_ta,
+                                   bgemm_rocblas_ta};
 
 static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
   if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
   int failures = 0, runs = 0;
-  const char* lay = L.label;
+  const std::string lay_s = std::string(L.label) + (g_bf16 ? "-bf16" : "");
+  const char* lay = lay_s.c_str();
   const int nc = L.num_configs();
   for (const Shape& sh : shapes) {
     const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
     const size_t cn = (size_t)sh.M * sh.N;
-    std::vector<f16> truth(cn), got(cn), b_rm((size_t)sh.K * sh.N);
+    std::vector<uint16_t> truth(cn), got(cn);
+    std::vector<f16> b_rm((size_t)sh.K * sh.N);
     for (int m = 0; m < sh.M; ++m)
       for (int n = 0; n < sh.N; ++n) {
         int acc = 0;
         for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
-        truth[(size_t)m * sh.N + n] = (f16)(float)acc;
+        const f16 t16 = (f16)(float)acc;
+        if (g_bf16) truth[(size_t)m * sh.N + n] = bf16_rne((float)acc);
+        else memcpy(&truth[(size_t)m * sh.N + n], &t16, 2);
       }
     for (int n = 0; n < sh.N; ++n)
       for (int k = 0; k < sh.K; ++k) b_rm[(size_t)k * sh.N + n] = z.bt[(size_t)n * sh.K + k];
@@ -1063,17 +1100,17 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
       std::vector<f16> a_cm(z.a.size());
       for (int m = 0; m < sh.M; ++m)
         for (int k = 0; k < sh.K; ++k) a_cm[(size_t)k * sh.M + m] = z.a[(size_t)m * sh.K + k];
-      HIP_OK(hipMemcpy(s.a, a_cm.data(), a_cm.size() * 2, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(s.a, operand_bits(a_cm).data(), a_cm.size() * 2, hipMemcpyHostToDevice));
     } else {
-      HIP_OK(hipMemcpy(s.a, z.a.data(), z.a.size() * 2, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(s.a, operand_bits(z.a).data(), z.a.size() * 2, hipMemcpyHostToDevice));
     }
-    HIP_OK(hipMemcpy(s.b, b_rm.data(), b_rm.size() * 2, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(s.b, operand_bits(b_rm).data(), b_rm.size() * 2, hipMemcpyHostToDevice));
     for (int c = 0; c < nc; ++c) {
       const char* cname = L.config_name(c);
-      const int own = L.runs(c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
+      const int own = (g_bf16 ? L.runs_bf16 : L.runs)(c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
         HIP_OK(hipMemset(s.c, 0xff, cn * 2));  // NaN pattern: unwritten outputs are caught
-        const int st = L.launch(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N, nullptr);
+        const int st = (g_bf16 ? L.launch_bf16 : L.launch)(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N, nullptr);
         const hipError_t e = hipDeviceSynchronize();
         ++runs;
         if (st != HGEMM_OK || e != hipSuccess) {
@@ -1086,7 +1123,7 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
         size_t bad = 0;
         for (size_t i = 0; i < cn; ++i)
           if (memcmp(&got[i], &truth[i], 2) != 0) {
-            if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) printf("   bad m=%zu n=%zu got %g want %g\n", i / sh.N, i % sh.N, (float)got[i], (float)truth[i]);
+            if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) printf("   bad m=%zu n=%zu got 0x%04x want 0x%04x\n", i / sh.N, i % sh.N, got[i], truth[i]);
             ++bad;
           }
         if (bad) {
@@ -1103,7 +1140,8 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
   printf("check-%s-configs:", lay);
   for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
   printf("\ncheck-%s-forms: 1 1|nt-store 2 5\n", lay);
-  printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs)\n", lay, runs, failures);
+  printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs%s)\n", lay, runs, failures,
+         g_bf16 ? ", rounded to bf16 once" : "");
   return failures ? 1 : 0;
 }
 
@@ -1239,16 +1277,17 @@ static int cmd_check_ta_c32(std::vector<Shape> shapes) {
     HIP_OK(hipMalloc(&da, a_cm.size() * 2));
     HIP_OK(hipMalloc(&db, b_rm.size() * 2));
     HIP_OK(hipMalloc(&dc, cn * 4));
-    HIP_OK(hipMemcpy(da, a_cm.data(), a_cm.size() * 2, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(db, b_rm.data(), b_rm.size() * 2, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(da, operand_bits(a_cm).data(), a_cm.size() * 2, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(db, operand_bits(b_rm).data(), b_rm.size() * 2, hipMemcpyHostToDevice));
     for (int c = 0; c < nc; ++c) {
       const char* cname = L.config_name(c);
-      const int own = hgemm_mi355x_ta_c32_runs(c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N);
+      const int own = (g_bf16 ? bgemm_mi355x_ta_c32_runs : hgemm_mi355x_ta_c32_runs)(c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5})
         for (int accumulate : {0, 1}) {
           if (accumulate) HIP_OK(hipMemcpy(dc, old.data(), cn * 4, hipMemcpyHostToDevice));
           else            HIP_OK(hipMemset(dc, 0xff, cn * 4));   // NaN pattern: store mode must not read it, unwritten outputs are caught
-          const int st = hgemm_mi355x_launch_ta_c32(c, splits, da, db, dc, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N, accumulate, nullptr);
+          const int st = (g_bf16 ? bgemm_mi355x_launch_ta_c32 : hgemm_mi355x_launch_ta_c32)(c, splits, da, db, dc, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N,
+                                                                                            accumulate, nullptr);
           const hipError_t e = hipDeviceSynchronize();
           ++runs;
           if (st != HGEMM_OK || e != hipSuccess) {
@@ -1275,7 +1314,7 @@ static int cmd_check_ta_c32(std::vector<Shape> shapes) {
     fflush(stdout);
   }
   printf("check-ta-c32-forms: 1 1|nt-store 2 5 x store accumulate\n");
-  printf("check ta-c32: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs and an integer old C32)\n", runs, failures);
+  printf("check ta-c32%s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs and an integer old C32)\n", g_bf16 ? "-bf16" : "", runs, failures);
   return failures ? 1 : 0;
 }
 
@@ -1341,6 +1380,92 @@ static int cmd_bench_ta_c32(const std::vector<Shape>& shapes, const char* out_pa
   return 0;
 }
 
+// ---- bfloat16 (bgemm_mi355x_nn / _ta / _ta_c32): `bench --layout nn|ta [--c32] --bf16` ---------------------------------------------------
+__global__ void f16_to_bf16_kernel(const f16* __restrict__ in, __bf16* __restrict__ out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (__bf16)(float)in[i];
+}
+
+// The check first, then per shape ONE set of interleaved rounds of the planned bf16 call, the planned fp16 call -- the same plan on the
+// same shape: the planner does not know the element kind -- on the fp16 N(0,1) operands the bf16 ones were rounded from, and, context
+// only, rocBLAS with bf16 in and out (16-bit C only).  c32: both calls accumulate.  The two calls move the same bytes and issue the same
+// number of MFMAs, so the one condition is bf16 <= fp16 within the fp16 call's own round-to-round spread in this run (its slowest round
+// minus its median): "bf16_le_fp16".
+static int cmd_bench_bf16(const TrLayout& L, bool c32, const std::vector<Shape>& shapes, const char* out_path) {
+  int rc = c32 ? cmd_check_ta_c32({}) : cmd_check_nn(L, {});
+  if (rc != 0) { fprintf(stderr, "bench --layout %s --bf16: the check failed, nothing is timed\n", L.label); return rc; }
+  FILE* out = out_path ? fopen(out_path, "w") : stdout;
+  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  hgemm_rocblas_init();
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0));
+  HIP_OK(hipEventCreate(&e1));
+  for (const Shape& sh : shapes) {
+    const size_t a_elems = (size_t)sh.M * sh.K, b_elems = (size_t)sh.K * sh.N, cn = (size_t)sh.M * sh.N;
+    std::vector<Buffers> sets(2);
+    std::vector<f16*> a16(sets.size(), nullptr);      // A as the layout takes it, fp16 ...
+    std::vector<__bf16*> ab(sets.size(), nullptr), bb(sets.size(), nullptr), cb(sets.size(), nullptr);   // ... and the bf16 operands and C
+    std::vector<float*> c32h(sets.size(), nullptr), c32b(sets.size(), nullptr);
+    for (size_t i = 0; i < sets.size(); ++i) {
+      alloc_set(sets[i], sh, 91 + i, true);
+      HIP_OK(hipMalloc(&ab[i], a_elems * 2));
+      HIP_OK(hipMalloc(&bb[i], b_elems * 2));
+      HIP_OK(hipMalloc(&cb[i], cn * 2));
+      if (L.a_col_major) {
+        HIP_OK(hipMalloc(&a16[i], a_elems * 2));
+        transpose_kernel<<<(unsigned)((a_elems + 255) / 256), 256>>>(sets[i].a, a16[i], sh.M, sh.K);   // a16[k][m] = a[m][k]
+      }
+      const f16* a_src = L.a_col_major ? a16[i] : sets[i].a;
+      f16_to_bf16_kernel<<<2048, 256>>>(a_src, ab[i], a_elems);
+      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].b, bb[i], b_elems);
+      if (c32) {
+        HIP_OK(hipMalloc(&c32h[i], cn * 4));
+        HIP_OK(hipMalloc(&c32b[i], cn * 4));
+        HIP_OK(hipMemset(c32h[i], 0, cn * 4));
+        HIP_OK(hipMemset(c32b[i], 0, cn * 4));
+      }
+    }
+    HIP_OK(hipDeviceSynchronize());
+    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
+    auto a_of = [&](Buffers& b) { return L.a_col_major ? (const void*)a16[idx(b)] : (const void*)b.a; };
+    std::vector<Contender> cs;
+    if (c32) {
+      cs.push_back({"bf16", [&](Buffers& b) { return bgemm_mi355x_ta_c32(ab[idx(b)], bb[idx(b)], c32b[idx(b)], sh.M, sh.N, sh.K, 1, nullptr); }});
+      cs.push_back({"fp16", [&](Buffers& b) { return hgemm_mi355x_ta_c32(a_of(b), b.b, c32h[idx(b)], sh.M, sh.N, sh.K, 1, nullptr); }});
+    } else {
+      cs.push_back({"bf16", [&](Buffers& b) { return L.planned_bf16(ab[idx(b)], bb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
+      cs.push_back({"fp16", [&](Buffers& b) { return L.planned(a_of(b), b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
+      cs.push_back({"rocblas_bf16", [&](Buffers& b) { return L.rocblas_bf16(ab[idx(b)], bb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
+    }
+    const int rounds = 15;
+    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
+    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
+    int cfg = 0, splits = 1;
+    L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
+    const int own = c32 ? bgemm_mi355x_ta_c32_runs(cfg, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N) : L.runs_bf16(cfg, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
+    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"%s\", \"output\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d, "
+                 "\"rounds\": %d, \"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, L.label, c32 ? "c32_accumulate" : "c16", L.config_name(cfg), splits, own, rounds);
+    for (const Contender& c : cs) {
+      const double us = c.iso_us();
+      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
+    }
+    const double b_us = cs[0].iso_us(), h_us = cs[1].iso_us();
+    const double spread = cs[1].ok && !cs[1].iso.empty() ? *std::max_element(cs[1].iso.begin(), cs[1].iso.end()) - h_us : -1.0;
+    fprintf(out, ", \"fp16_spread_us\": %.3f, \"bf16_le_fp16\": %s}\n", spread, b_us > 0 && h_us > 0 && b_us <= h_us + spread ? "true" : "false");
+    fflush(out);
+    for (size_t i = 0; i < sets.size(); ++i) {
+      free_set(sets[i]);
+      HIP_OK(hipFree(ab[i])); HIP_OK(hipFree(bb[i])); HIP_OK(hipFree(cb[i]));
+      if (a16[i]) HIP_OK(hipFree(a16[i]));
+      if (c32h[i]) HIP_OK(hipFree(c32h[i]));
+      if (c32b[i]) HIP_OK(hipFree(c32b[i]));
+    }
+  }
+  HIP_OK(hipEventDestroy(e0));
+  HIP_OK(hipEventDestroy(e1));
+  if (out != stdout) fclose(out);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1366,6 +1491,7 @@ int main(int argc, char** argv) {
       layout_nn = l == "nn"; layout_ta = l == "ta";
     }
     else if (a == "--c32") c32 = true;
+    else if (a == "--bf16") g_bf16 = true;
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
     else if (a == "--streamk") g_streamk_too = true;
@@ -1424,6 +1550,7 @@ int main(int argc, char** argv) {
     if (mode == "check") return c32 ? cmd_check_ta_c32(shapes) : cmd_check_nn(kLayoutTA, shapes);
     if (mode == "bench") {
       if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
+      if (g_bf16) return cmd_bench_bf16(kLayoutTA, c32, shapes, out_path);
       return c32 ? cmd_bench_ta_c32(shapes, out_path) : cmd_bench_ta(shapes, out_path);
     }
     fprintf(stderr, "--layout ta goes with check or bench\n");
@@ -1434,11 +1561,13 @@ int main(int argc, char** argv) {
     if (mode == "check") return cmd_check_nn(kLayoutNN, shapes);
     if (mode == "bench") {
       if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
+      if (g_bf16) return cmd_bench_bf16(kLayoutNN, false, shapes, out_path);
       return cmd_bench_nn(shapes, out_path, autotune);
     }
     fprintf(stderr, "--layout nn goes with check or bench\n");
     return 2;
   }
+  if (g_bf16) { fprintf(stderr, "--bf16 goes with --layout nn or ta (the b_col_major families have no bf16 form)\n"); return 2; }
   if (mode == "check") {
     if (shapes.empty())
       // (the last two: K tails -- 2104 = 32 x 64 + 56 = 8 x 256 + 56, 728 = 11 x 64 + 24 = 5 x 128 + 88 = 2 x 256 + 216: odd and even

@@ -353,6 +353,40 @@ int hgemm_mi355x_launch_ta_c32(int ta_config, int splits, const void* a_col_majo
                                int M, int N, int K, int lda, int ldb, int ldc, int accumulate, void* stream);
 int hgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
 
+/* ------------------------------------------------------------------------------------------
+ * bfloat16 on the NN and TA layouts ("bgemm"): the three calls above with bfloat16 operands and, for the 16-bit C, a bfloat16 result --
+ * the input gradient dX = dY x W (bgemm_mi355x_nn), the weight gradient dW = X^T x dY (bgemm_mi355x_ta) and the weight gradient added
+ * into an fp32 gradient buffer (bgemm_mi355x_ta_c32) for a training stack that keeps dY, X and W in bf16.  Replaces a cast of the
+ * operands to fp16 in front of the hgemm_ calls (dY overflows or flushes without loss scaling) or a rocblas_gemm_ex call with bf16
+ * types.  Accumulation is fp32.  The kernels are families n and a with v_mfma_f32_16x16x32_bf16 in the K loop (csrc/hgemm_kernel_nn.hpp,
+ * hgemm_kernel_ta.hpp: CfgNNB / CfgTAB); the 16-bit C is the fp32 sum rounded to bf16 ONCE, to nearest even (NaN stays NaN, a sum beyond
+ * the bf16 maximum becomes inf) -- in the kernel's epilogue, or in the combine of a two-pass plan, whose slabs are fp32.  The fp32 C has
+ * no conversion on its path.
+ * Everything else is the fp16 calls': elements are 2 bytes either way, so scope, reach and stride rules, the two tables, their ids and
+ * names, the meaning of the splits word (HGEMM_PLAN_NT_STORE is honoured, HGEMM_SPLITK_FUSED runs two-pass, HGEMM_PLAN_STREAMK plain)
+ * and every status are those of hgemm_mi355x_launch_nn / _launch_ta / _launch_ta_c32.  Plan, workspace size and reserve call are the
+ * hgemm_mi355x_nn_* / _ta_* functions (hgemm_mi355x_nn_plan, _nn_plan_workspace_bytes, _nn_reserve_workspace, and their _ta_ twins).
+ * A call outside the kernels' scope is answered by a bf16 reference kernel (HGEMM_OK, exact, slow: the _runs functions tell); every call
+ * is capturable, and a captured split call without a workspace runs unsplit with status 0.  The names carry no accumulate mode: there
+ * is one, fp32.
+ * The b_col_major (forward) families -- hgemm_mi355x_fp32 / _fp16 / _launch -- have NO bf16 form, and no existing entry point changes what
+ * it does. */
+/* planned, contiguous (nn: lda = K; ta: lda = M; ldb = ldc = N) */
+int bgemm_mi355x_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream);
+int bgemm_mi355x_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream);
+int bgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int M, int N, int K, int accumulate, void* stream);
+/* explicit: config / splits words and strides exactly as hgemm_mi355x_launch_nn / _launch_ta / _launch_ta_c32 */
+int bgemm_mi355x_launch_nn(int nn_config, int splits, const void* a, const void* b, void* c,
+                           int M, int N, int K, int lda, int ldb, int ldc, void* stream);
+int bgemm_mi355x_launch_ta(int ta_config, int splits, const void* a_col_major, const void* b, void* c,
+                           int M, int N, int K, int lda, int ldb, int ldc, void* stream);
+int bgemm_mi355x_launch_ta_c32(int ta_config, int splits, const void* a_col_major, const void* b, float* c32,
+                               int M, int N, int K, int lda, int ldb, int ldc, int accumulate, void* stream);
+/* 1 when the call runs one of the bf16 kernels, 0 when it falls back to the reference kernel or is refused (the fp16 twins' answers) */
+int bgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc);
+int bgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
+int bgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
+
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
 const char* hgemm_mi355x_version(void);
@@ -368,6 +402,9 @@ int hgemm_rocblas_nn(const void* a, const void* b, void* c, int M, int N, int K,
 int hgemm_rocblas_tn(const void* a, const void* b_col_major, void* c, int M, int N, int K, int acc, void* stream);
 /* the TA layout (a_col_major [K][M], b row-major): the same rocblas_gemm_ex with its second operand transposed, ld = M */
 int hgemm_rocblas_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, int acc, void* stream);
+/* the vendor counterparts of bgemm_mi355x_nn / _ta: the same rocblas_gemm_ex calls with bf16 operands and C, fp32 compute */
+int bgemm_rocblas_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream);
+int bgemm_rocblas_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream);
 
 /* hipBLASLt heuristic  <-  cublasLtMatmulAlgoGetHeuristic top-1 of 4, cached
  * (reference cublas/fp32/hgemm_cublaslt_heuristic.cu:65-217). */
