@@ -4,7 +4,6 @@
 // (benchmarking_utils.py:23-31), so a lean host path is part of the hot path.
 #include "hgemm_plan.hpp"
 #include "hgemm_kernel_nn.hpp"
-#include "hgemm_kernel_ta.hpp"
 #include "../../include/hgemm_mi355x.h"
 
 #include <algorithm>
@@ -468,9 +467,9 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 
 // ---- the transposed-read layouts: NN (family n, hgemm_kernel_nn.hpp: B row-major [K][ldb]) and TA (family a, hgemm_kernel_ta.hpp: A given
 // as a_col_major [K][lda] as well) ------------------------------------------------------------------------------------------------------
-// Each family has its own table (g_nn_table: hgemm_inst_g5.hip, g_ta_table: hgemm_inst_g6.hip); the geometry table, hgemm_mi355x_plan and
-// what a b-only call of hgemm_mi355x_launch does know nothing of them.  A layout is described once, here; resolution, launch, planner and
-// the queries below are written once and take the description.
+// The tables and kernel sets of both are built in hgemm_registry.hip (TrTable: hgemm_kernel_nn.hpp); the geometry table,
+// hgemm_mi355x_plan and what a b-only call of hgemm_mi355x_launch does know nothing of them.  A layout is described once, here;
+// resolution, launch, planner and the queries below are written once and take the description.
 // What a call writes: fp16 C (every nn_ / ta_ entry point) or fp32 C (c32: hgemm_mi355x_ta_c32, family a only), stored or -- c32 only --
 // added into what C holds.  ldc counts C's own elements.
 struct TrOut {
@@ -479,41 +478,15 @@ struct TrOut {
 };
 constexpr TrOut kOutC16{false, false};
 
-// What the operands and a 16-bit C hold: fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements are 2
-// bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  The kind selects a kernel set and nothing else.
-enum TrElem { TR_F16 = 0, TR_BF16 = 1 };
-struct TrKernels {
-  // the EPI_C16 / EPI_SLAB launchers by config id, in the order of the table's rows; null: the rows' own (fp16)
-  const TrLaunch* launch;
-  // fp32 C: the EPI_C32 launchers by config id; null where the layout has none (a c32 call is refused with HGEMM_ERR_BAD_ARG)
-  const TaC32Launch* launch_c32;
-  // the combine of the two-pass form with a 16-bit C (an fp32 C: launch_splitk_reduce_c32, whatever the operands were)
-  void (*combine)(const float*, void*, int, int, int, int, hipStream_t, TimingSlot);
-  // the reference kernels (status 0, exact): answer whatever is outside the kernels' scope or reach
-  void (*reference)(const void*, const void*, void*, int, int, int, int, int, int, hipStream_t, TimingSlot);
-  void (*reference_c32)(const void*, const void*, float*, int, int, int, int, int, int, bool, hipStream_t, TimingSlot);
-};
-// the typed launchers of hgemm_registry.hip behind TrKernels' untyped pointers
-template <class T, void (*F)(const float*, T*, int, int, int, int, hipStream_t, TimingSlot)>
-void tr_combine(const float* p, void* c, int M, int N, int ldc, int splits, hipStream_t s, TimingSlot ts) { F(p, (T*)c, M, N, ldc, splits, s, ts); }
-template <class T, void (*F)(const T*, const T*, T*, int, int, int, int, int, int, hipStream_t, TimingSlot)>
-void tr_reference(const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t s, TimingSlot ts) {
-  F((const T*)a, (const T*)b, (T*)c, M, N, K, lda, ldb, ldc, s, ts);
-}
-template <class T, void (*F)(const T*, const T*, float*, int, int, int, int, int, int, bool, hipStream_t, TimingSlot)>
-void tr_reference_c32(const void* a, const void* b, float* c, int M, int N, int K, int lda, int ldb, int ldc, bool acc, hipStream_t s,
-                      TimingSlot ts) {
-  F((const T*)a, (const T*)b, c, M, N, K, lda, ldb, ldc, acc, s, ts);
-}
-
+// What the operands and a 16-bit C hold (TrElem): fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements
+// are 2 bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  (TrElem, c32) selects a kernel set and nothing
+// else: the member's launcher in its row, the set's combine and reference kernel in the table's `kernels`.
 struct TrLayout {
-  const NNEntry* table;
-  const int& count;
+  const TrTable& t;   // rows by config id and kernels[TrElem][c32]; a set the layout does not have is empty, and a call for it is refused
   // How A lies in memory decides every rule in which the two layouts differ.  false (n): [M][lda], rows of K elements, staged and
   // addressed from a tile's first row.  true (a): [K][lda], k-rows of M elements, staged as B is and addressed from row 0 to the end
   // of the matrix; a chunk of a k-row must not straddle M, so M % 8 == 0 joins the scope.
   bool a_col_major;
-  TrKernels kernels[2];   // by TrElem
 
   // elements in a row of A: the least lda, and the lda of a contiguous A (the planned calls pass strides (a_row, N, N))
   int a_row(int M, int K) const { return a_col_major ? M : K; }
@@ -526,25 +499,19 @@ struct TrLayout {
   }
   // 32-bit offsets with bit 31 to spare: B from row 0 to the end of the matrix, C from a tile's first row -- (BM ldc + N) elements of 2
   // bytes, of 4 for an fp32 C --, A as a_col_major says
-  bool reach_ok(TrOut out, const NNEntry& e, int M, int N, int K, int lda, int ldb, int ldc) const {
+  bool reach_ok(TrOut out, const TrEntry& e, int M, int N, int K, int lda, int ldb, int ldc) const {
     const double a_bytes = a_col_major ? (double)(K - 1) * lda * 2.0 + M * 2.0 : (double)e.bm * lda * 2.0 + K * 2.0;
     const double c_bytes = ((double)e.bm * ldc + N) * out.elem_bytes();
     return a_bytes < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 && c_bytes < 2147483648.0;
   }
 };
-const TrLayout kLayoutNN{g_nn_table, g_num_nn, false,
-                         {{nullptr, nullptr, tr_combine<f16, launch_splitk_reduce>, tr_reference<f16, launch_generic>, nullptr},
-                          {g_nn_bf16_launch, nullptr, tr_combine<bf16, launch_splitk_reduce_bf16>, tr_reference<bf16, launch_generic_nn_bf16>, nullptr}}};
-const TrLayout kLayoutTA{g_ta_table, g_num_ta, true,
-                         {{nullptr, g_ta_c32_launch, tr_combine<f16, launch_splitk_reduce>, tr_reference<f16, launch_generic_ta>,
-                           tr_reference_c32<f16, launch_generic_ta_c32>},
-                          {g_ta_bf16_launch, g_ta_bf16_c32_launch, tr_combine<bf16, launch_splitk_reduce_bf16>,
-                           tr_reference<bf16, launch_generic_ta_bf16>, tr_reference_c32<bf16, launch_generic_ta_c32_bf16>}}};
+const TrLayout kLayoutNN{tr_table_nn(), false};
+const TrLayout kLayoutTA{tr_table_ta(), true};
 
 // (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn / _ta show it to the CPU tests)
 // out.c32: the same tiles, cuts and slabs; the plain dispatch and the combine carry EPI_C32 (the K slices are the family's EPI_SLAB
 // kernels), the least ldc is still N
-LaunchPlan tr_resolve(const TrLayout& L, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
+LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
                       unsigned ruled_out) {
   LaunchPlan p;
   auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
@@ -553,10 +520,10 @@ LaunchPlan tr_resolve(const TrLayout& L, TrOut out, int config, int splits_arg, 
     ++p.n;
   };
   // rows must not overlap: lda >= K (n) / >= M, the row stride of a_col_major (a); ldb >= N (B is row-major here), ldc >= N
-  if (config < 0 || config >= L.count || lda < L.a_row(M, K) || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
-  if ((out.c32 && !L.kernels[TR_F16].launch_c32) || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no fp32 C in this layout
+  if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
+  if (!L.t.kernels[elem][out.c32].reference || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no such kernel set in this layout
   const int epi_out = out.c32 ? EPI_C32 : EPI_C16;
-  const NNEntry& e = L.table[config];
+  const TrEntry& e = L.t.rows[config].e;
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
@@ -594,22 +561,22 @@ LaunchPlan tr_resolve(const TrLayout& L, TrOut out, int config, int splits_arg, 
 // Planner of both families: the largest member whose tiles fill the chip (ties: fewer padded elements, then the taller tile); otherwise
 // the 64 x 64 member with as many two-pass splits as bring tiles x splits up to the CU count -- at most one per K stage, at most 32.
 void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits) {
-  const NNEntry* table = L.table;
+  const TrRow* table = L.t.rows;
   int best = -1;
   long best_area = 0, best_pad = 0;
-  for (int i = 0; i < L.count; ++i) {
-    const NNEntry& e = table[i];
+  for (int i = 0; i < L.t.count; ++i) {
+    const TrEntry& e = table[i].e;
     const long tm = (M + e.bm - 1) / e.bm, tn = (N + e.bn - 1) / e.bn, area = (long)e.bm * e.bn, pad = tm * e.bm * tn * e.bn;
     if (tm * tn < kCUs) continue;
-    if (best < 0 || area > best_area || (area == best_area && (pad < best_pad || (pad == best_pad && e.bm > table[best].bm)))) {
+    if (best < 0 || area > best_area || (area == best_area && (pad < best_pad || (pad == best_pad && e.bm > table[best].e.bm)))) {
       best = i; best_area = area; best_pad = pad;
     }
   }
   if (best >= 0) { *cfg = best; *splits = 1; return; }
   int small = 0;
-  for (int i = 1; i < L.count; ++i)
-    if (table[i].bm * table[i].bn < table[small].bm * table[small].bn) small = i;
-  const NNEntry& e = table[small];
+  for (int i = 1; i < L.t.count; ++i)
+    if (table[i].e.bm * table[i].e.bn < table[small].e.bm * table[small].e.bn) small = i;
+  const TrEntry& e = table[small].e;
   const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
   *cfg = small;
   *splits = (int)std::max<long>(1, std::min<long>(std::min<long>((kCUs + tiles - 1) / tiles, K / BK), 32));
@@ -617,7 +584,7 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 
 // GemmArgs as the kernels read it: A = a (n: [M][lda], a: [K][lda]), Bt = the row-major B
 // (out.c32: c is the float pointer; it travels in g.C and the EPI_C32 kernels reinterpret it)
-// elem: the kernel set (by config id), the combine and the reference kernel; the plan does not depend on it
+// (elem, out.c32): the kernel set -- the member's launcher, the combine and the reference kernel; the plan does not depend on elem
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda,
               int ldb, int ldc, void* stream) {
   DisarmTiming disarm_timing;
@@ -625,40 +592,30 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
   hipStream_t s = (hipStream_t)stream;
   const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc);
   unsigned ruled_out = 0;
-  LaunchPlan p = tr_resolve(L, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  LaunchPlan p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
   // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
   if (p.status == HGEMM_OK && p.slab_bytes) {
     const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
     if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
       ruled_out |= 1u << FORM_SPLITK;
-      p = tr_resolve(L, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+      p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
     } else if (st != HGEMM_OK) {
       return st;
     }
   }
   if (p.status != HGEMM_OK) return p.status;
-  const TrKernels& kern = L.kernels[elem];
+  const TrKernels& kern = L.t.kernels[elem][out.c32];
+  const TrLaunch launch = L.t.rows[config].launch[elem][out.c32];
   for (int i = 0; i < p.n; ++i) {
     GemmArgs& g = p.d[i].g;
     g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (bf16 travels in the same fields: the kernels of its Cfgs reinterpret)
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
-    const bool c32 = p.d[i].epi == EPI_C32;
     switch (p.d[i].thunk) {
-      case THUNK_ENTRY:
-        if (c32)           kern.launch_c32[config](g, p.d[i].grid, s, ts);
-        else if (kern.launch) kern.launch[config](g, p.d[i].grid, s, p.d[i].epi, ts);
-        else               L.table[config].launch(g, p.d[i].grid, s, p.d[i].epi, ts);
-        break;
-      case THUNK_SPLITK_REDUCE:
-        if (c32) launch_splitk_reduce_c32(g.partial, (float*)c, M, N, ldc, g.splits, out.accumulate, s, ts);
-        else     kern.combine(g.partial, c, M, N, ldc, g.splits, s, ts);
-        break;
-      default:
-        if (c32) kern.reference_c32(a, b, (float*)c, M, N, K, lda, ldb, ldc, out.accumulate, s, ts);
-        else     kern.reference(a, b, c, M, N, K, lda, ldb, ldc, s, ts);
-        break;
+      case THUNK_ENTRY: launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
+      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, M, N, ldc, g.splits, out.accumulate, s, ts); break;
+      default: kern.reference(a, b, c, M, N, K, lda, ldb, ldc, out.accumulate, s, ts); break;
     }
   }
   hipError_t err = hipGetLastError();
@@ -674,18 +631,18 @@ int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void*
   return tr_launch(L, elem, out, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), N, N, stream);
 }
 
-const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.count) ? L.table[id].name : nullptr; }
+const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.t.count) ? L.t.rows[id].e.name : nullptr; }
 
 int tr_config_by_name(const TrLayout& L, const char* name) {
   if (!name) return -1;
-  for (int i = 0; i < L.count; ++i)
-    if (std::strcmp(name, L.table[i].name) == 0) return i;
+  for (int i = 0; i < L.t.count; ++i)
+    if (std::strcmp(name, L.t.rows[i].e.name) == 0) return i;
   return -1;
 }
 
 int tr_config_info(const TrLayout& L, int id, int out[8]) {
-  if (id < 0 || id >= L.count || !out) return HGEMM_ERR_BAD_ARG;
-  const NNEntry& e = L.table[id];
+  if (id < 0 || id >= L.t.count || !out) return HGEMM_ERR_BAD_ARG;
+  const TrEntry& e = L.t.rows[id].e;
   out[0] = e.bm; out[1] = e.bn; out[2] = e.wm; out[3] = e.wn; out[4] = 16; out[5] = e.nbuf; out[6] = e.threads; out[7] = e.lds_bytes;
   return HGEMM_OK;
 }
@@ -696,15 +653,15 @@ int tr_plan(const TrLayout& L, int M, int N, int K, int* config, int* splits) {
   return HGEMM_OK;
 }
 
-int tr_runs(const TrLayout& L, TrOut out, int config, int M, int N, int K, int lda, int ldb, int ldc) {
+int tr_runs(const TrLayout& L, TrElem elem, TrOut out, int config, int M, int N, int K, int lda, int ldb, int ldc) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = tr_resolve(L, out, config, 1, true, M, N, K, lda, ldb, ldc, 0);
+  const LaunchPlan p = tr_resolve(L, elem, out, config, 1, true, M, N, K, lda, ldb, ldc, 0);
   return p.status == HGEMM_OK && p.form != FORM_REFERENCE ? 1 : 0;
 }
 
 size_t tr_plan_workspace_bytes(const TrLayout& L, int config, int splits, int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = tr_resolve(L, kOutC16, config, splits, true, M, N, K, L.a_row(M, K), N, N, 0);   // (the slabs of both output kinds)
+  const LaunchPlan p = tr_resolve(L, TR_F16, kOutC16, config, splits, true, M, N, K, L.a_row(M, K), N, N, 0);   // (the slabs of both output kinds)
   return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
 }
 
@@ -723,10 +680,10 @@ int tr_reserve_workspace(const TrLayout& L, int M, int N, int K, void* stream) {
 // operands = 4 when the pointers are 16-byte aligned, ruled_out = 1 << form of the two-pass form that got no workspace.  Returns the
 // call's status; out = {form, dispatches, slab bytes, counters (0)}, then per dispatch {thunk, grid, epi, splits, k_chunk, items,
 // start, stop}.
-int tr_selfcheck_launch(const TrLayout& L, TrOut kind, int config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc,
+int tr_selfcheck_launch(const TrLayout& L, TrElem elem, TrOut kind, int config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc,
                         int ruled_out, long long out[20]) {
   if (M <= 0 || N <= 0 || K <= 0 || !out) return HGEMM_ERR_BAD_ARG;
-  return show_plan(tr_resolve(L, kind, config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out), out);
+  return show_plan(tr_resolve(L, elem, kind, config, splits, (operands & 4) != 0, M, N, K, lda, ldb, ldc, (unsigned)ruled_out), out);
 }
 
 }  // namespace
@@ -980,12 +937,12 @@ int hgemm_mi355x_fp16(const void* a, const void* b, const void* bt, void* c, int
 }
 
 // ---- NN layout (kLayoutNN) and TA layout (kLayoutTA): forwards to the one host path of the transposed-read layouts ---------------------
-int hgemm_mi355x_nn_num_configs(void) { return g_num_nn; }
+int hgemm_mi355x_nn_num_configs(void) { return kLayoutNN.t.count; }
 const char* hgemm_mi355x_nn_config_name(int id) { return tr_config_name(kLayoutNN, id); }
 int hgemm_mi355x_nn_config_by_name(const char* name) { return tr_config_by_name(kLayoutNN, name); }
 int hgemm_mi355x_nn_config_info(int id, int out[8]) { return tr_config_info(kLayoutNN, id, out); }
 int hgemm_mi355x_nn_plan(int M, int N, int K, int* nn_config, int* splits) { return tr_plan(kLayoutNN, M, N, K, nn_config, splits); }
-int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, kOutC16, nn_config, M, N, K, lda, ldb, ldc); }
+int hgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, TR_F16, kOutC16, nn_config, M, N, K, lda, ldb, ldc); }
 size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K) {
   return tr_plan_workspace_bytes(kLayoutNN, nn_config, splits, M, N, K);
 }
@@ -998,15 +955,15 @@ int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, in
 int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_F16, kOutC16, a, b, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
-  return tr_selfcheck_launch(kLayoutNN, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutNN, TR_F16, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
-int hgemm_mi355x_ta_num_configs(void) { return g_num_ta; }
+int hgemm_mi355x_ta_num_configs(void) { return kLayoutTA.t.count; }
 const char* hgemm_mi355x_ta_config_name(int id) { return tr_config_name(kLayoutTA, id); }
 int hgemm_mi355x_ta_config_by_name(const char* name) { return tr_config_by_name(kLayoutTA, name); }
 int hgemm_mi355x_ta_config_info(int id, int out[8]) { return tr_config_info(kLayoutTA, id, out); }
 int hgemm_mi355x_ta_plan(int M, int N, int K, int* ta_config, int* splits) { return tr_plan(kLayoutTA, M, N, K, ta_config, splits); }
-int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, kOutC16, ta_config, M, N, K, lda, ldb, ldc); }
+int hgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, TR_F16, kOutC16, ta_config, M, N, K, lda, ldb, ldc); }
 size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, int N, int K) {
   return tr_plan_workspace_bytes(kLayoutTA, ta_config, splits, M, N, K);
 }
@@ -1019,7 +976,7 @@ int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M,
 int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_F16, kOutC16, a_col_major, b, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
-  return tr_selfcheck_launch(kLayoutTA, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutTA, TR_F16, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // fp32 C (family a, EPI_C32): the same path with the other output kind.  Plan, workspace size and reserve call are the TA layout's own
@@ -1034,12 +991,12 @@ int hgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int 
   return tr_run(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
 }
 int hgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
-  return tr_runs(kLayoutTA, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
+  return tr_runs(kLayoutTA, TR_F16, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
 }
 int hgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int accumulate,
                                          int ruled_out, long long out[20]) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_selfcheck_launch(kLayoutTA, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // ---- bfloat16 operands and 16-bit C on the two transposed-read layouts: the same path with the other element kind.  Tables, ids, plans,
@@ -1050,13 +1007,13 @@ int bgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const v
   return tr_launch(kLayoutNN, TR_BF16, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
 }
 int bgemm_mi355x_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_BF16, kOutC16, a, b, c, M, N, K, stream); }
-int bgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, kOutC16, nn_config, M, N, K, lda, ldb, ldc); }
+int bgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, TR_BF16, kOutC16, nn_config, M, N, K, lda, ldb, ldc); }
 int bgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
                            int ldb, int ldc, void* stream) {
   return tr_launch(kLayoutTA, TR_BF16, kOutC16, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
 }
 int bgemm_mi355x_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_BF16, kOutC16, a_col_major, b, c, M, N, K, stream); }
-int bgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, kOutC16, ta_config, M, N, K, lda, ldb, ldc); }
+int bgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, TR_BF16, kOutC16, ta_config, M, N, K, lda, ldb, ldc); }
 int bgemm_mi355x_launch_ta_c32(int ta_config, int splits_arg, const void* a_col_major, const void* b, float* c32, int M, int N, int K, int lda,
                                int ldb, int ldc, int accumulate, void* stream) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
@@ -1067,21 +1024,21 @@ int bgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int 
   return tr_run(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
 }
 int bgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
-  return tr_runs(kLayoutTA, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
+  return tr_runs(kLayoutTA, TR_BF16, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
 }
 // (the CPU tests' view, not part of the public header: the plan is the fp16 twin's -- the element kind is not an input of tr_resolve)
 int bgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
-  return tr_selfcheck_launch(kLayoutNN, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 int bgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
-  return tr_selfcheck_launch(kLayoutTA, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutTA, TR_BF16, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 int bgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int accumulate,
                                          int ruled_out, long long out[20]) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_selfcheck_launch(kLayoutTA, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+  return tr_selfcheck_launch(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the

@@ -266,29 +266,66 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// ---- host side: each family's own small table (the geometry table of hgemm_configs*.def does not know them) ----------------------
-template <class CFG>
+// ---- host side of both transposed-read families (family a builds on it) -----------------------------------------------------------
+// A kernel set is one (element, output) of a layout: CfgNN / CfgNNB / CfgTA / CfgTAB, with a 16-bit C or -- C32 -- the fp32 C.  Each
+// set is instantiated in a unit of its own (hgemm_inst_g5.hip .. g10.hip).
+//
+// The one launcher: member CFG's kernel of epilogue `epi`.  The 16-bit set has the EPI_C16 and EPI_SLAB kernels.  The fp32-C set has
+// the EPI_C32 kernel alone: the K slices of its two-pass form are the 16-bit set's EPI_SLAB kernels (slabs are fp32 either way), reached
+// through that set's launcher in its own unit -- the extern declarations below keep it from being instantiated a second time.
+template <class CFG, bool C32>
 void launch_tr(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  if (epi == EPI_SLAB)
+  if constexpr (C32) {
+    if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+    HGEMM_LAUNCH((CFG::template kernel<EPI_C32>()), grid, CFG::THREADS, stream, ts, g);
+  } else if (epi == EPI_SLAB) {
     HGEMM_LAUNCH((CFG::template kernel<EPI_SLAB>()), grid, CFG::THREADS, stream, ts, g);
-  else
+  } else {
     HGEMM_LAUNCH((CFG::template kernel<EPI_C16>()), grid, CFG::THREADS, stream, ts, g);
+  }
 }
+using TrLaunch = void (*)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
 
-struct NNEntry {
+// The members of both families, smallest tile first, and what is made of them: X(args ..., BM, BN, WM, WN, NBUF) per member.
+//   HGEMM_TR_INST(CFG, C32)    a unit's one line: the explicit instantiation of a kernel set's launchers, and with them its kernels
+//   HGEMM_TR_EXTERN(CFG, C32)  everyone else's view of the set: no unit but the set's own instantiates a launcher or a kernel
+//   HGEMM_TR_ENTRY(P, CFG)     the member's geometry row, named P<BM>x<BN>_w<WM>x<WN>
+#define HGEMM_TR_MEMBERS(X, ...) \
+  X(__VA_ARGS__, 64, 64, 2, 2, 4) X(__VA_ARGS__, 128, 64, 2, 2, 3) X(__VA_ARGS__, 64, 128, 2, 2, 3) X(__VA_ARGS__, 128, 128, 2, 2, 3)
+#define HGEMM_TR_LAUNCHER(CFG, C32, BM, BN, WM, WN, NB) launch_tr<CFG<BM, BN, WM, WN, NB>, C32>
+#define HGEMM_TR_INST(...) template void HGEMM_TR_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TR_EXTERN(...) extern HGEMM_TR_INST(__VA_ARGS__)
+#define HGEMM_TR_ENTRY(P, CFG, BM, BN, WM, WN, NB) \
+  {P #BM "x" #BN "_w" #WM "x" #WN, BM, BN, WM, WN, NB, CFG<BM, BN, WM, WN, NB>::THREADS, CFG<BM, BN, WM, WN, NB>::LDS_BYTES}
+
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNN, false)    // hgemm_inst_g5.hip
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNNB, false)   // hgemm_inst_g8.hip
+
+// A layout's table (hgemm_registry.hip builds both, each by one expansion of the member list: a config id is a position in `rows`; the
+// geometry table of hgemm_configs*.def does not know these families).  A row is the member's geometry and its launcher in every kernel
+// set of the layout; TrKernels is what a set has besides: the combine of the two-pass form and the reference kernel (status 0, exact:
+// answers whatever is outside the kernels' scope or reach).  All sets share the signatures; a set with a 16-bit C is handed
+// accumulate = false and ignores it.  A set the layout does not have (NN with an fp32 C) is empty: null launchers, TrKernels{}.
+struct TrEntry {
   const char* name;
   int bm, bn, wm, wn, nbuf, threads, lds_bytes;
-  void (*launch)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
 };
-extern const NNEntry g_nn_table[];
-extern const int g_num_nn;
-
-// The members of both families, smallest tile first (a family's ids are positions in its table), and what a family's translation unit
-// makes of them: X(P, CFG, ...) with P the prefix of the members' names and CFG the family's Cfg template.
-#define HGEMM_TR_MEMBERS(X, P, CFG) X(P, CFG, 64, 64, 2, 2, 4) X(P, CFG, 128, 64, 2, 2, 3) X(P, CFG, 64, 128, 2, 2, 3) X(P, CFG, 128, 128, 2, 2, 3)
-#define HGEMM_TR_INST(P, CFG, BM, BN, WM, WN, NB) template void launch_tr<CFG<BM, BN, WM, WN, NB>>(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_TR_ROW(P, CFG, BM, BN, WM, WN, NB)                                                                                \
-  {P #BM "x" #BN "_w" #WM "x" #WN, BM, BN, WM, WN, NB, CFG<BM, BN, WM, WN, NB>::THREADS, CFG<BM, BN, WM, WN, NB>::LDS_BYTES, \
-   &launch_tr<CFG<BM, BN, WM, WN, NB>>},
+enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C hold: 2 bytes either way
+struct TrRow {
+  TrEntry e;
+  TrLaunch launch[2][2];   // [TrElem][fp32 C]
+};
+struct TrKernels {
+  void (*combine)(const float* partial, void* c, int M, int N, int ldc, int splits, bool accumulate, hipStream_t, TimingSlot);
+  void (*reference)(const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate, hipStream_t,
+                    TimingSlot);
+};
+struct TrTable {
+  const TrRow* rows;
+  int count;
+  TrKernels kernels[2][2];   // [TrElem][fp32 C]
+};
+const TrTable& tr_table_nn();
+const TrTable& tr_table_ta();
 
 }  // namespace hgemm_mi355x

@@ -30,7 +30,7 @@
 //     EPI_C32 (hgemm_inst_g7.hip, hgemm_mi355x_ta_c32): the fp32 accumulators stored to, or added into, the caller's fp32 C -- the
 //     weight gradient where a training step consumes it; its two-pass form combines the same slabs with
 //     hgemm_splitk_reduce_c32_kernel.
-//   * Shared with family n: the Cfg base (CfgTR), launch_tr, the member list and table macros, nn_swz.  The kernel body is family n's
+//   * Shared with family n: the Cfg base (CfgTR), launch_tr, the member list and its macros, the table types, nn_swz.  The kernel body is family n's
 //     text once more, on purpose: as one force-inlined function template under two __global__ wrappers it compiled to a different K
 //     loop in every kernel.
 //   tests/test_ta_host.py replays the A image with tests/nn_layout_model.py (bn := BM, tn := TM, wave_n := wave_m) and restates the
@@ -275,43 +275,10 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// ---- host side: the family's own small table, rows of family n's NNEntry, launched by its launch_tr ----------------------------
-extern const NNEntry g_ta_table[];
-extern const int g_num_ta;
-
-// the reference kernel of the layout (hgemm_registry.hip): one output per thread, A read as A[k * lda + m]
-void launch_generic_ta(const f16* a_col_major, const f16* B, f16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
-                       TimingSlot ts);
-
-// ---- fp32 C (EPI_C32): launchers by TA config id (hgemm_inst_g7.hip; g_ta_table and NNEntry keep their shape), the combine of the
-// two-pass form and the reference kernel (hgemm_registry.hip).  ldc in fp32 elements; accumulate: C32 += A x B, otherwise C32 is never read.
-using TaC32Launch = void (*)(const GemmArgs&, int, hipStream_t, TimingSlot);
-extern const TaC32Launch g_ta_c32_launch[];
-extern const int g_num_ta_c32;
-void launch_splitk_reduce_c32(const float* partial, float* C32, int M, int N, int ldc, int splits, bool accumulate, hipStream_t stream,
-                              TimingSlot ts);
-void launch_generic_ta_c32(const f16* a_col_major, const f16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
-                           hipStream_t stream, TimingSlot ts);
-
-// ---- bfloat16 (CfgNNB / CfgTAB; the bgemm_mi355x_ entry points): launchers by config id in HGEMM_TR_MEMBERS order, the order of
-// g_nn_table's and g_ta_table's rows (hgemm_inst_g8.hip: family n, g9: family a, g10: family a's fp32 C); the bf16 combine of the two-pass
-// form and the three reference kernels (hgemm_registry.hip).  The fp32-C combine is launch_splitk_reduce_c32: slabs are fp32 whatever
-// the operands were.
-using bf16 = __bf16;
-using TrLaunch = void (*)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-extern const TrLaunch g_nn_bf16_launch[];
-extern const int g_num_nn_bf16;
-extern const TrLaunch g_ta_bf16_launch[];
-extern const int g_num_ta_bf16;
-extern const TaC32Launch g_ta_bf16_c32_launch[];
-extern const int g_num_ta_bf16_c32;
-#define HGEMM_TR_LAUNCH_ROW(P, CFG, BM, BN, WM, WN, NB) &launch_tr<CFG<BM, BN, WM, WN, NB>>,
-void launch_splitk_reduce_bf16(const float* partial, bf16* C, int M, int N, int ldc, int splits, hipStream_t stream, TimingSlot ts);
-void launch_generic_nn_bf16(const bf16* A, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
-                            TimingSlot ts);
-void launch_generic_ta_bf16(const bf16* a_col_major, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc,
-                            hipStream_t stream, TimingSlot ts);
-void launch_generic_ta_c32_bf16(const bf16* a_col_major, const bf16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc,
-                                bool accumulate, hipStream_t stream, TimingSlot ts);
+// ---- host side: hgemm_kernel_nn.hpp's; the family's four kernel sets -------------------------------------------------------------
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgTA, false)    // hgemm_inst_g6.hip
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgTA, true)     // hgemm_inst_g7.hip
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgTAB, false)   // hgemm_inst_g9.hip
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgTAB, true)    // hgemm_inst_g10.hip
 
 }  // namespace hgemm_mi355x

@@ -100,11 +100,15 @@ const KernelEntry g_kernel_table[] = {
 const int g_num_kernels = (int)(sizeof(g_kernel_table) / sizeof(g_kernel_table[0]));
 #endif  // !__HIP_DEVICE_COMPILE__
 
-// Split-K combine: C[m][n] = fp16( sum_s partial[s][m][n] ), fp32 adds in split order
+// Split-K combine: C[m][n] = T( sum_s partial[s][m][n] ), fp32 adds in split order, the sum rounded to T once -- fp16 (the b_col_major
+// families and the fp16 calls of the transposed-read layouts) or bf16 (bgemm_mi355x_nn / _ta: round to nearest even).  Slabs are fp32
+// whatever the operands were.
 // (deterministic, unlike the reference's atomicAdd split-K, a100_F32F16F16F32/64_256_16384.cu:149-152).
+template <class T>
 __global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* __restrict__ partial,
-                                                                  f16* __restrict__ C, int M, int N,
+                                                                  T* __restrict__ C, int M, int N,
                                                                   int ldc, int splits) {
+  using Tx4 = __attribute__((ext_vector_type(4))) T;
   const size_t total4 = ((size_t)M * N) >> 2;  // N % 4 == 0 on this path
   const size_t slab   = (size_t)M * N;
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4;
@@ -126,41 +130,12 @@ __global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* _
       s += p;
     }
     const int m = (int)(e / N), n = (int)(e % N);
-    f16x4 o = {(f16)s[0], (f16)s[1], (f16)s[2], (f16)s[3]};
-    *(f16x4*)(C + (size_t)m * ldc + n) = o;
+    Tx4 o = {(T)s[0], (T)s[1], (T)s[2], (T)s[3]};
+    *(Tx4*)(C + (size_t)m * ldc + n) = o;
   }
 }
 
-// The combine of the bfloat16 calls (bgemm_mi355x_nn / _ta): hgemm_splitk_reduce_kernel with the other last step -- the fp32 slabs added in
-// split order, the sum rounded to bf16 once (round to nearest even).  Slabs are fp32 whatever the operands were; the fp32-C form of the
-// bf16 calls combines with hgemm_splitk_reduce_c32_kernel below as it is.
-__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bf16_kernel(const float* __restrict__ partial, bf16* __restrict__ C, int M, int N,
-                                                                       int ldc, int splits) {
-  using bf16x4 = __attribute__((ext_vector_type(4))) bf16;
-  const size_t total4 = ((size_t)M * N) >> 2;  // N % 4 == 0 on this path
-  const size_t slab   = (size_t)M * N;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
-    const size_t e = q << 2;
-    f32x4 s = *(const f32x4*)(partial + e);
-    int k = 1;
-    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
-      f32x4 p[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += p[u];
-    }
-    for (; k < splits; ++k) {
-      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
-      s += p;
-    }
-    const int m = (int)(e / N), n = (int)(e % N);
-    bf16x4 o = {(bf16)s[0], (bf16)s[1], (bf16)s[2], (bf16)s[3]};
-    *(bf16x4*)(C + (size_t)m * ldc + n) = o;
-  }
-}
-
-// The combine of family a's fp32-C calls (hgemm_mi355x_ta_c32): t = p[0] + p[1] + ... + p[S-1] in split order, then
+// The combine of the fp32-C calls (hgemm_mi355x_ta_c32, bgemm_mi355x_ta_c32): t = p[0] + p[1] + ... + p[S-1] in split order, then
 // C32 = accumulate ? C32 + t : t -- the shape of the unsplit result, old + fl(sum), and one fixed order per plan.  C32 is read only
 // with `accumulate`; rows are ldc fp32 elements apart and the pad between N and ldc is never touched.  (N % 4 == 0, ldc % 4 == 0 and
 // a 16-byte aligned C32 on this path.)
@@ -213,118 +188,112 @@ __global__ void __launch_bounds__(256) hgemm_tail_reduce_kernel(const GemmArgs g
   }
 }
 
-// Any-shape / any-alignment fallback (one output per thread, fp32 accumulate).  Correctness
-// net for shapes the MFMA paths do not accept (K % 8 != 0, unaligned views); never tuned.
-__global__ void __launch_bounds__(256) hgemm_generic_kernel(const f16* __restrict__ A,
-                                                            const f16* __restrict__ B,
-                                                            f16* __restrict__ C, int M, int N, int K,
+// Any-shape / any-alignment fallback (one output per thread, an fmaf chain in k order, fp32 accumulate, rounded to T once).
+// Correctness net for shapes the MFMA paths do not accept (K % 8 != 0, unaligned views); never tuned.  The reference kernel of every
+// 16-bit call: <f16, false> the b_col_major families' and the NN layout's, A_COL the TA layout's (hgemm_kernel_ta.hpp: A given as
+// a_col_major, read as A[k * lda + m] -- same sum order, so the same bits on the transposed operand), T = __bf16 the bgemm_ calls'.
+template <class T, bool A_COL>
+__global__ void __launch_bounds__(256) hgemm_generic_kernel(const T* __restrict__ A,
+                                                            const T* __restrict__ B,
+                                                            T* __restrict__ C, int M, int N, int K,
                                                             int lda, int ldb_rowmajor, int ldc) {
   const int n = blockIdx.x * 64 + (threadIdx.x & 63);
   if (n >= N) return;
   // grid-stride over M: gridDim.y is capped at 65535 (M > 262140 used to fail the launch)
   for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
     float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    C[(size_t)m * ldc + n] = (f16)s;
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[A_COL ? (size_t)k * lda + m : (size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    C[(size_t)m * ldc + n] = (T)s;
   }
 }
 
-// The same net for the TA layout (hgemm_kernel_ta.hpp): A given as a_col_major, read as A[k * lda + m].  Same sum order, so the
-// same bits as hgemm_generic_kernel on the transposed operand.
-__global__ void __launch_bounds__(256) hgemm_generic_ta_kernel(const f16* __restrict__ At,
-                                                               const f16* __restrict__ B,
-                                                               f16* __restrict__ C, int M, int N, int K,
-                                                               int lda_colmajor, int ldb_rowmajor, int ldc) {
+// The reference kernel of the fp32-C calls: the same fma chain in k order, then C32 = accumulate ? C32 + s : s (no rounding).
+template <class T, bool A_COL>
+__global__ void __launch_bounds__(256) hgemm_generic_c32_kernel(const T* __restrict__ A, const T* __restrict__ B,
+                                                                float* __restrict__ C32, int M, int N, int K, int lda,
+                                                                int ldb_rowmajor, int ldc, int accumulate) {
   const int n = blockIdx.x * 64 + (threadIdx.x & 63);
   if (n >= N) return;
   for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
     float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    C[(size_t)m * ldc + n] = (f16)s;
-  }
-}
-
-// The reference kernel of the fp32-C calls: hgemm_generic_ta_kernel's fma chain in k order, then C32 = accumulate ? C32 + s : s.
-__global__ void __launch_bounds__(256) hgemm_generic_ta_c32_kernel(const f16* __restrict__ At, const f16* __restrict__ B,
-                                                                   float* __restrict__ C32, int M, int N, int K, int lda_colmajor,
-                                                                   int ldb_rowmajor, int ldc, int accumulate) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[A_COL ? (size_t)k * lda + m : (size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
     float* out = C32 + (size_t)m * ldc + n;
     *out = accumulate ? *out + s : s;
   }
 }
 
-// The reference kernels of the bfloat16 calls: the three above on bf16 operands -- one output per thread, an fma chain in k order, the
-// same last step (one round to nearest even to bf16; none for the fp32 C).
-__global__ void __launch_bounds__(256) hgemm_generic_nn_bf16_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
-                                                                    bf16* __restrict__ C, int M, int N, int K, int lda, int ldb_rowmajor,
-                                                                    int ldc) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    C[(size_t)m * ldc + n] = (bf16)s;
-  }
-}
-
-__global__ void __launch_bounds__(256) hgemm_generic_ta_bf16_kernel(const bf16* __restrict__ At, const bf16* __restrict__ B,
-                                                                    bf16* __restrict__ C, int M, int N, int K, int lda_colmajor,
-                                                                    int ldb_rowmajor, int ldc) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    C[(size_t)m * ldc + n] = (bf16)s;
-  }
-}
-
-__global__ void __launch_bounds__(256) hgemm_generic_ta_c32_bf16_kernel(const bf16* __restrict__ At, const bf16* __restrict__ B,
-                                                                        float* __restrict__ C32, int M, int N, int K, int lda_colmajor,
-                                                                        int ldb_rowmajor, int ldc, int accumulate) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)At[(size_t)k * lda_colmajor + m], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    float* out = C32 + (size_t)m * ldc + n;
-    *out = accumulate ? *out + s : s;
-  }
-}
-
-void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
-                          hipStream_t stream, TimingSlot ts) {
+// ---- launchers of the combines and the reference kernels, with the signatures of TrKernels (hgemm_kernel_nn.hpp) ----------------------
+// grid and block of a combine: a thread per four outputs
+struct CombineGrid { int grid, threads; };
+static CombineGrid combine_grid(int M, int N) {
   const size_t quads = ((size_t)M * N) >> 2;
   // small outputs: 64-thread blocks so the (latency-bound) slab reads spread over more CUs
   const int threads = quads <= 64 * 1024 ? 64 : 256;
   int grid = (int)((quads + threads - 1) / threads);
   if (grid > 256 * 8) grid = 256 * 8;  // grid-stride beyond 8 blocks per CU
   if (grid < 1) grid = 1;
-  HGEMM_LAUNCH(hgemm_splitk_reduce_kernel, grid, threads, stream, ts, partial, C, M, N, ldc, splits);
+  return {grid, threads};
 }
 
-void launch_splitk_reduce_c32(const float* partial, float* C32, int M, int N, int ldc, int splits, bool accumulate, hipStream_t stream,
-                              TimingSlot ts) {
-  const size_t quads = ((size_t)M * N) >> 2;
-  const int threads = quads <= 64 * 1024 ? 64 : 256;   // (launch_splitk_reduce's sizing)
-  int grid = (int)((quads + threads - 1) / threads);
-  if (grid > 256 * 8) grid = 256 * 8;
-  if (grid < 1) grid = 1;
-  HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, grid, threads, stream, ts, partial, C32, M, N, ldc, splits, accumulate ? 1 : 0);
+template <class T>
+static void launch_combine(const float* partial, void* C, int M, int N, int ldc, int splits, bool, hipStream_t stream, TimingSlot ts) {
+  const CombineGrid cg = combine_grid(M, N);
+  HGEMM_LAUNCH((hgemm_splitk_reduce_kernel<T>), cg.grid, cg.threads, stream, ts, partial, (T*)C, M, N, ldc, splits);
 }
 
-void launch_splitk_reduce_bf16(const float* partial, bf16* C, int M, int N, int ldc, int splits, hipStream_t stream, TimingSlot ts) {
-  const size_t quads = ((size_t)M * N) >> 2;
-  const int threads = quads <= 64 * 1024 ? 64 : 256;   // (launch_splitk_reduce's sizing)
-  int grid = (int)((quads + threads - 1) / threads);
-  if (grid > 256 * 8) grid = 256 * 8;
-  if (grid < 1) grid = 1;
-  HGEMM_LAUNCH(hgemm_splitk_reduce_bf16_kernel, grid, threads, stream, ts, partial, C, M, N, ldc, splits);
+// ldc in fp32 elements; accumulate: C32 += the sum, otherwise C32 is never read
+static void launch_combine_c32(const float* partial, void* C32, int M, int N, int ldc, int splits, bool accumulate, hipStream_t stream,
+                               TimingSlot ts) {
+  const CombineGrid cg = combine_grid(M, N);
+  HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, cg.grid, cg.threads, stream, ts, partial, (float*)C32, M, N, ldc, splits, accumulate ? 1 : 0);
+}
+
+template <class T, bool A_COL, bool C32>
+static void launch_reference(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
+                             hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  if constexpr (C32)
+    HGEMM_LAUNCH((hgemm_generic_c32_kernel<T, A_COL>), grid, 256, stream, ts, (const T*)A, (const T*)B, (float*)C, M, N, K, lda, ldb, ldc,
+                 accumulate ? 1 : 0);
+  else
+    HGEMM_LAUNCH((hgemm_generic_kernel<T, A_COL>), grid, 256, stream, ts, (const T*)A, (const T*)B, (T*)C, M, N, K, lda, ldb, ldc);
+}
+
+// the b_col_major families' names for their two (hgemm_launch.hpp)
+void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
+                          hipStream_t stream, TimingSlot ts) {
+  launch_combine<f16>(partial, C, M, N, ldc, splits, false, stream, ts);
+}
+
+void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int lda, int ldb,
+                    int ldc, hipStream_t stream, TimingSlot ts) {
+  launch_reference<f16, false, false>(A, B, C, M, N, K, lda, ldb, ldc, false, stream, ts);
+}
+
+// ---- the tables of the two transposed-read layouts (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the member list: a
+// row is the member's geometry and its launcher in every kernel set of the layout, [TrElem][fp32 C]; `kernels` names the same sets'
+// combine and reference kernel.  A new kernel set is one more cell in the layout's row macro and in its `kernels`.
+// (Inside functions, which both passes read: the device pass instantiates a combine or a reference kernel where it sees its launcher
+// named, and a table of host function pointers at namespace scope would be emitted as a device constant.)
+#define HGEMM_NN_ROW(P, ...)                                                                                \
+  {HGEMM_TR_ENTRY(P, CfgNN, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgNN, false, __VA_ARGS__), nullptr},        \
+                                           {&HGEMM_TR_LAUNCHER(CfgNNB, false, __VA_ARGS__), nullptr}}},
+#define HGEMM_TA_ROW(P, ...)                                                                                                                 \
+  {HGEMM_TR_ENTRY(P, CfgTA, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgTA, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTA, true, __VA_ARGS__)},    \
+                                           {&HGEMM_TR_LAUNCHER(CfgTAB, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTAB, true, __VA_ARGS__)}}},
+const TrTable& tr_table_nn() {
+  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_NN_ROW, "n")};
+  static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
+                            {{{launch_combine<f16>, launch_reference<f16, false, false>}, {}},
+                             {{launch_combine<__bf16>, launch_reference<__bf16, false, false>}, {}}}};
+  return t;
+}
+const TrTable& tr_table_ta() {
+  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TA_ROW, "a")};
+  static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
+                            {{{launch_combine<f16>, launch_reference<f16, true, false>}, {launch_combine_c32, launch_reference<f16, true, true>}},
+                             {{launch_combine<__bf16>, launch_reference<__bf16, true, false>}, {launch_combine_c32, launch_reference<__bf16, true, true>}}}};
+  return t;
 }
 
 void launch_tail_reduce(const GemmArgs& g, int BM, int BN, hipStream_t stream, TimingSlot ts) {
@@ -352,42 +321,6 @@ void launch_ragged(const GemmArgs& g0, hipStream_t stream, TimingSlot ts) {
     g.tiles_m = (g.M + 63) / 64; g.tiles_n = (g.N + 63) / 64;
     HGEMM_LAUNCH((hgemm_tn_ragged_kernel<Small>), g.tiles_m * g.tiles_n, Small::THREADS, stream, ts, g, wa, wb, vec_c);
   }
-}
-
-void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int lda, int ldb,
-                    int ldc, hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH(hgemm_generic_kernel, grid, 256, stream, ts, A, B, C, M, N, K, lda, ldb, ldc);
-}
-
-void launch_generic_ta(const f16* a_col_major, const f16* B, f16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
-                       TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH(hgemm_generic_ta_kernel, grid, 256, stream, ts, a_col_major, B, C, M, N, K, lda, ldb, ldc);
-}
-
-void launch_generic_ta_c32(const f16* a_col_major, const f16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
-                           hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH(hgemm_generic_ta_c32_kernel, grid, 256, stream, ts, a_col_major, B, C32, M, N, K, lda, ldb, ldc, accumulate ? 1 : 0);
-}
-
-void launch_generic_nn_bf16(const bf16* A, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t stream,
-                            TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH(hgemm_generic_nn_bf16_kernel, grid, 256, stream, ts, A, B, C, M, N, K, lda, ldb, ldc);
-}
-
-void launch_generic_ta_bf16(const bf16* a_col_major, const bf16* B, bf16* C, int M, int N, int K, int lda, int ldb, int ldc,
-                            hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH(hgemm_generic_ta_bf16_kernel, grid, 256, stream, ts, a_col_major, B, C, M, N, K, lda, ldb, ldc);
-}
-
-void launch_generic_ta_c32_bf16(const bf16* a_col_major, const bf16* B, float* C32, int M, int N, int K, int lda, int ldb, int ldc,
-                                bool accumulate, hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH(hgemm_generic_ta_c32_bf16_kernel, grid, 256, stream, ts, a_col_major, B, C32, M, N, K, lda, ldb, ldc, accumulate ? 1 : 0);
 }
 
 }  // namespace hgemm_mi355x
