@@ -466,7 +466,8 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 
 
 // ---- the transposed-read layouts: NN (family n, hgemm_kernel_nn.hpp: B row-major [K][ldb]) and TA (family a, hgemm_kernel_ta.hpp: A given
-// as a_col_major [K][lda] as well) ------------------------------------------------------------------------------------------------------
+// as a_col_major [K][lda] as well); and on the same host path TN (family f, hgemm_kernel_tn.hpp: bf16 only, B given as b_col_major
+// [N][ldb], no transposed read) ---------------------------------------------------------------------------------------------------------
 // The tables and kernel sets of both are built in hgemm_registry.hip (TrTable: hgemm_kernel_nn.hpp); the geometry table,
 // hgemm_mi355x_plan and what a b-only call of hgemm_mi355x_launch does know nothing of them.  A layout is described once, here;
 // resolution, launch, planner and the queries below are written once and take the description.
@@ -487,9 +488,16 @@ struct TrLayout {
   // addressed from a tile's first row.  true (a): [K][lda], k-rows of M elements, staged as B is and addressed from row 0 to the end
   // of the matrix; a chunk of a k-row must not straddle M, so M % 8 == 0 joins the scope.
   bool a_col_major;
+  // How B lies.  false (n, a): row-major [K][ldb], k-rows of N elements, addressed from row 0 to the end of the matrix.  true (f,
+  // hgemm_kernel_tn.hpp): b_col_major [N][ldb], rows of K elements, staged and addressed from a tile's first row, as a row-major A is.
+  bool b_col_major = false;
+  // the kernel set a query that does not ask for an element kind resolves with (scope, reach, cuts and slabs are the same in every set):
+  // one the layout has
+  TrElem any_elem = TR_F16;
 
-  // elements in a row of A: the least lda, and the lda of a contiguous A (the planned calls pass strides (a_row, N, N))
+  // elements in a row of A / of B: the least lda / ldb, and the strides of contiguous operands (the planned calls pass (a_row, b_row, N))
   int a_row(int M, int K) const { return a_col_major ? M : K; }
+  int b_row(int N, int K) const { return b_col_major ? K : N; }
   // the kernels' scope; everything else is answered by the reference kernel.  Rows of C start at 16-byte boundaries: ldc % 8 == 0 of
   // a 16-bit C, ldc % 4 == 0 of an fp32 C (next to a_col_major's rule: the output kind changes C's rules only)
   bool path_ok(TrOut out, const void* a, const void* b, const void* c, int M, int N, int K, int lda, int ldb, int ldc) const {
@@ -497,16 +505,19 @@ struct TrLayout {
     if ((lda & 7) || (ldb & 7) || (ldc & (out.c32 ? 3 : 7))) return false;
     return !(((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15));
   }
-  // 32-bit offsets with bit 31 to spare: B from row 0 to the end of the matrix, C from a tile's first row -- (BM ldc + N) elements of 2
-  // bytes, of 4 for an fp32 C --, A as a_col_major says
+  // 32-bit offsets with bit 31 to spare: C from a tile's first row -- (BM ldc + N) elements of 2 bytes, of 4 for an fp32 C --, A and B
+  // as a_col_major / b_col_major say: an operand of k-rows from row 0 to the end of the matrix, one of K-element rows (BM / BN of them)
+  // from a tile's first row
   bool reach_ok(TrOut out, const TrEntry& e, int M, int N, int K, int lda, int ldb, int ldc) const {
     const double a_bytes = a_col_major ? (double)(K - 1) * lda * 2.0 + M * 2.0 : (double)e.bm * lda * 2.0 + K * 2.0;
+    const double b_bytes = b_col_major ? (double)e.bn * ldb * 2.0 + K * 2.0 : (double)(K - 1) * ldb * 2.0 + N * 2.0;
     const double c_bytes = ((double)e.bm * ldc + N) * out.elem_bytes();
-    return a_bytes < 2147483648.0 && (double)(K - 1) * ldb * 2.0 + N * 2.0 < 2147483648.0 && c_bytes < 2147483648.0;
+    return a_bytes < 2147483648.0 && b_bytes < 2147483648.0 && c_bytes < 2147483648.0;
   }
 };
 const TrLayout kLayoutNN{tr_table_nn(), false};
 const TrLayout kLayoutTA{tr_table_ta(), true};
+const TrLayout kLayoutTN{tr_table_tn(), false, true, TR_BF16};   // the bf16 forward product: no transposed read, the same host path
 
 // (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn / _ta show it to the CPU tests)
 // out.c32: the same tiles, cuts and slabs; the plain dispatch and the combine carry EPI_C32 (the K slices are the family's EPI_SLAB
@@ -519,8 +530,9 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
     p.d[p.n] = Dispatch{thunk, g, (int)grid, epi, p.n == 0, true};
     ++p.n;
   };
-  // rows must not overlap: lda >= K (n) / >= M, the row stride of a_col_major (a); ldb >= N (B is row-major here), ldc >= N
-  if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < N || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
+  // rows must not overlap: lda >= K (n, f) / >= M, the row stride of a_col_major (a); ldb >= N (n, a: B is row-major) / >= K, the row
+  // stride of b_col_major (f); ldc >= N
+  if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < L.b_row(N, K) || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
   if (!L.t.kernels[elem][out.c32].reference || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no such kernel set in this layout
   const int epi_out = out.c32 ? EPI_C32 : EPI_C16;
   const TrEntry& e = L.t.rows[config].e;
@@ -582,7 +594,7 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
   *splits = (int)std::max<long>(1, std::min<long>(std::min<long>((kCUs + tiles - 1) / tiles, K / BK), 32));
 }
 
-// GemmArgs as the kernels read it: A = a (n: [M][lda], a: [K][lda]), Bt = the row-major B
+// GemmArgs as the kernels read it: A = a (n, f: [M][lda], a: [K][lda]), Bt = the row-major B (n, a) / b_col_major (f)
 // (out.c32: c is the float pointer; it travels in g.C and the EPI_C32 kernels reinterpret it)
 // (elem, out.c32): the kernel set -- the member's launcher, the combine and the reference kernel; the plan does not depend on elem
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda,
@@ -628,7 +640,7 @@ int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void*
   if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   int cfg, splits;
   tr_model_plan(L, M, N, K, &cfg, &splits);
-  return tr_launch(L, elem, out, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), N, N, stream);
+  return tr_launch(L, elem, out, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), L.b_row(N, K), N, stream);
 }
 
 const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.t.count) ? L.t.rows[id].e.name : nullptr; }
@@ -661,7 +673,7 @@ int tr_runs(const TrLayout& L, TrElem elem, TrOut out, int config, int M, int N,
 
 size_t tr_plan_workspace_bytes(const TrLayout& L, int config, int splits, int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const LaunchPlan p = tr_resolve(L, TR_F16, kOutC16, config, splits, true, M, N, K, L.a_row(M, K), N, N, 0);   // (the slabs of both output kinds)
+  const LaunchPlan p = tr_resolve(L, L.any_elem, kOutC16, config, splits, true, M, N, K, L.a_row(M, K), L.b_row(N, K), N, 0);   // (the slabs of both output kinds)
   return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
 }
 
@@ -1001,7 +1013,7 @@ int hgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands
 
 // ---- bfloat16 operands and 16-bit C on the two transposed-read layouts: the same path with the other element kind.  Tables, ids, plans,
 // workspace sizes and the reserve calls are the hgemm_mi355x_nn_ / _ta_ functions' (elements are 2 bytes either way); the b_col_major
-// families have no bf16 form.
+// families have no bf16 form (the bf16 forward product is the TN layout below, kernels of its own).
 int bgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
                            int ldc, void* stream) {
   return tr_launch(kLayoutNN, TR_BF16, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
@@ -1039,6 +1051,29 @@ int bgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands
                                          int ruled_out, long long out[20]) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
   return tr_selfcheck_launch(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+
+// ---- the bf16 forward product, Y = X W^T (kLayoutTN, family f): the same path once more.  A table, ids, plan, workspace size and reserve
+// call of its own -- the layout has no fp16 twin to borrow them from.
+int bgemm_mi355x_tn_num_configs(void) { return kLayoutTN.t.count; }
+const char* bgemm_mi355x_tn_config_name(int id) { return tr_config_name(kLayoutTN, id); }
+int bgemm_mi355x_tn_config_by_name(const char* name) { return tr_config_by_name(kLayoutTN, name); }
+int bgemm_mi355x_tn_config_info(int id, int out[8]) { return tr_config_info(kLayoutTN, id, out); }
+int bgemm_mi355x_tn_plan(int M, int N, int K, int* tn_config, int* splits) { return tr_plan(kLayoutTN, M, N, K, tn_config, splits); }
+int bgemm_mi355x_tn_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTN, TR_BF16, kOutC16, tn_config, M, N, K, lda, ldb, ldc); }
+size_t bgemm_mi355x_tn_plan_workspace_bytes(int tn_config, int splits, int M, int N, int K) {
+  return tr_plan_workspace_bytes(kLayoutTN, tn_config, splits, M, N, K);
+}
+int bgemm_mi355x_tn_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutTN, M, N, K, stream); }
+int bgemm_mi355x_launch_tn(int tn_config, int splits_arg, const void* a, const void* b_col_major, void* c, int M, int N, int K, int lda,
+                           int ldb, int ldc, void* stream) {
+  return tr_launch(kLayoutTN, TR_BF16, kOutC16, tn_config, splits_arg, a, b_col_major, c, M, N, K, lda, ldb, ldc, stream);
+}
+int bgemm_mi355x_tn(const void* a, const void* b_col_major, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTN, TR_BF16, kOutC16, a, b_col_major, c, M, N, K, stream); }
+int bgemm_mi355x_selfcheck_launch_tn(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                     long long out[20]) {
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, kOutC16, tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the

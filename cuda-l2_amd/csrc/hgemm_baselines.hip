@@ -517,6 +517,9 @@ int hgemm_rocblas_ta(const void* at, const void* b, void* c, int M, int N, int K
 int bgemm_rocblas_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
   return rocblas_run(false, a, b, c, M, N, K, HGEMM_ACC_FP32, stream, false, true);
 }
+int bgemm_rocblas_tn(const void* a, const void* bt, void* c, int M, int N, int K, void* stream) {
+  return rocblas_run(true, a, bt, c, M, N, K, HGEMM_ACC_FP32, stream, false, true);
+}
 int bgemm_rocblas_ta(const void* at, const void* b, void* c, int M, int N, int K, void* stream) {
   return rocblas_run(false, at, b, c, M, N, K, HGEMM_ACC_FP32, stream, true, true);
 }

@@ -327,5 +327,6 @@ struct TrTable {
 };
 const TrTable& tr_table_nn();
 const TrTable& tr_table_ta();
+const TrTable& tr_table_tn();   // family f (hgemm_kernel_tn.hpp): the bf16 forward product, B given as b_col_major; no transposed read
 
 }  // namespace hgemm_mi355x

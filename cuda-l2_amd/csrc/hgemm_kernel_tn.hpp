@@ -1,0 +1,180 @@
+// Family "f": the forward product of a linear layer in bfloat16 -- C[M,N] = A[M,K] * B[K,N] with A ROW-MAJOR ([M][lda], K contiguous)
+// and B given as b_col_major ([N][ldb], K contiguous): Y = X W^T with W stored [out][in].  The third of the layer's three products next
+// to family n (input gradient) and family a (weight gradient); the operand form of hgemm_mi355x_fp32's b_col_major and of
+// hgemm_rocblas_tn.  Replaces, for a bf16 caller, a cast of X and W to fp16 in front of hgemm_mi355x_fp32 or a rocblas_gemm_ex call with
+// bf16 types; the vendor baseline is bgemm_rocblas_tn.  bf16 only: the fp16 forward families (hgemm_kernel.hpp and the rest) are
+// untouched and there is no fp16 kernel here.
+//
+// Family n's structure (hgemm_kernel_nn.hpp): NBUF-deep LDS ring of K = 64 stages, ONE barrier per stage, counted vmcnt, LDS-DMA
+// fills in 1-KiB pieces, v_mfma_f32_16x16x32_bf16 (tr_mfma) with fp32 accumulation, operands swapped so that a lane owns 4 consecutive
+// N of a C row.
+//   * A image, its DMA and its reads: family n's text -- [BM rows][128 B], 16-byte chunk c of row r at slot c ^ ((r >> 1) & 7),
+//     descriptor (2 GiB) at the tile's first row, the K advance in the scalar offset, rows clamped to M - 1 - m0, ds_read_b128.
+//   * B image: THE SAME image over the tile's BN rows of b_col_major, [BN rows][128 B] = BN * 128 bytes -- as many as family n's
+//     [64 k-rows][BN halfs], so CfgTR's B_BYTES, piece counts, ring depths and LDS bytes are the n members'.  Piece il of B holds rows
+//     8 il .. 8 il + 7; descriptor (2 GiB) at row n0, the K advance in the scalar offset, rows clamped to N - 1 - n0 on load: a row
+//     at or past N reads row N - 1 again and only feeds accumulators of columns >= N, which are never stored.
+//   * B fragments: the MFMA operand of lane (n = lane & 15, kq = lane >> 4) is k = 8 kq .. 8 kq + 7 of ROW n of the image: 16
+//     contiguous bytes, one ds_read_b128 at row n, slot (4 ks + kq) ^ ((n >> 1) & 7).  There is no transposed read in this family, so
+//     neither of that instruction's rules (8-byte lane addresses by construction, EXEC all ones) is needed here.
+//   * Scope (the host sends anything else to the reference kernel): K % 64 == 0, N % 8 == 0 (C's 16-byte stores; M is free),
+//     lda / ldb / ldc multiples of 8, 16-byte aligned pointers, (BM lda + K) 2, (BN ldb + K) 2 and (BM ldc + N) 2 bytes below 2 GiB.
+//   * Epilogues: family n's: bf16 C (each accumulator rounded once by v_cvt_pk_bf16_f32, v_permlane16_swap, 16-byte buffer stores, the
+//     plain and the non-temporal store an instruction each) and the two-pass split-K slab (hgemm_splitk_reduce_kernel<__bf16> combines).
+//   * Shared with family n: CfgTR, tr_mfma, launch_tr, the member list and its macros, the table types.  The kernel body is family n's
+//     text a third time, on purpose (a repeated body over a changed loop); families n and a keep their symbols and,
+//     as compiled, their instruction streams.
+#pragma once
+
+#include "hgemm_kernel_nn.hpp"
+
+namespace hgemm_mi355x {
+
+template <class CFG, int EPI>
+__global__ void hgemm_tn_bf16_kernel(const GemmArgs g);
+
+// family f: both operand images are the classic one; elements are bfloat16
+template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
+struct CfgTNB : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
+  using elem = __bf16;
+  static_assert(BN_ * ROW_BYTES == CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES>::B_BYTES, "[BN rows][128 B] fills CfgTR's B image");
+  template <int EPI>
+  static constexpr auto kernel() { return &hgemm_tn_bf16_kernel<CfgTNB, EPI>; }   // the family's entry point (launch_tr)
+};
+
+// GemmArgs as the kernel reads it: A = [M][lda], Bt = b_col_major ([N][ldb], ldb >= K its row stride); tail_tiles = 0, counters = nullptr.
+template <class CFG, int EPI>
+__global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmArgs g) {
+  prefetch_kernargs<sizeof(GemmArgs)>();
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int BM = CFG::BM, BN = CFG::BN, NBUF = CFG::NBUF;
+  constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
+  using elem = typename CFG::elem;   // __bf16
+  using ex8 = __attribute__((ext_vector_type(8))) elem;
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB, "plain and two-pass slab epilogues");
+
+  __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
+
+  const int tid  = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave_m = wave / CFG::WN;
+  const int wave_n = wave % CFG::WN;
+
+  const TileCoord tc = map_block(g, BM, BN);
+
+  // ---- LDS-DMA source addressing ---------------------------------------------------------------
+  // Both operands as the classic family has them: a 2 GiB descriptor at the tile's first row, rows past the matrix edge clamped to the
+  // last valid row, the K advance in the scalar offset (every real offset is below 2 GiB: host check).
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(g.A + (size_t)tc.m0 * g.lda), 0, 0x80000000u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)(g.Bt + (size_t)tc.n0 * g.ldb), 0, 0x80000000u, 0x00020000);
+
+  uint32_t voff[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const bool isA = j < NJ_A;
+    const int il = wave + (isA ? j : j - NJ_A) * NW;    // piece of its operand's tile: rows 8 il .. 8 il + 7
+    const int r  = il * 8 + (lane >> 3);
+    const int rc = min(r, isA ? g.M - 1 - tc.m0 : g.N - 1 - tc.n0);
+    const int chunk = (lane & 7) ^ (((il & 1) << 2) | (lane >> 4));   // slot (lane & 7) of row r holds chunk slot ^ ((r >> 1) & 7)
+    voff[j] = ((uint32_t)rc * (uint32_t)(isA ? g.lda : g.ldb) + (uint32_t)chunk * 8u) * 2u;
+  }
+
+  // ---- fragment read offsets (bytes inside an operand's image): row lane & 15 of a 16-row fragment, chunk 4 ks + (lane >> 4) -------
+  int f_off[2];
+  {
+    const int lr = lane & 15, lq = lane >> 4, sw = (lr >> 1) & 7;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) f_off[ks] = lr * ROW_BYTES + (((ks * 4 + lq) ^ sw) << 4);
+  }
+  const int a_row_base = wave_m * CFG::TM * ROW_BYTES;
+  const int b_row_base = CFG::A_BYTES + wave_n * CFG::TN * ROW_BYTES;
+
+  f32x4 acc[FM][FN];
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
+
+  // ---- pipeline ----------------------------------------------------------------------------------
+  uint32_t kbyte = (uint32_t)tc.k_begin * 2u;
+  auto stage = [&](char* lds_stage) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      lds_void_t* dst = (lds_void_t*)(lds_stage + (wave + j * NW) * 1024);
+      if (j < NJ_A) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, dst, 16, voff[j], kbyte, 0, 0);
+      else          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, dst, 16, voff[j], kbyte, 0, 0);
+    }
+    kbyte += ROW_BYTES;
+  };
+  const int nk = tc.nk;
+#pragma unroll
+  for (int s = 0; s < NBUF - 1; ++s)
+    if (s < nk) stage(smem + s * CFG::STAGE_BYTES);
+
+  int rd = 0, wr = NBUF - 1;
+  for (int t = 0; t < nk; ++t) {
+    if (t + NBUF - 2 < nk)
+      wait_vmcnt<NJ*(NBUF - 2)>();
+    else
+      wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();   // all waves' pieces of stage t landed; stage `wr` is free again
+
+    if (t + NBUF - 1 < nk) stage(smem + wr * CFG::STAGE_BYTES);
+
+    const char* st = smem + rd * CFG::STAGE_BYTES;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      ex8 af[FM], bf[FN];
+#pragma unroll
+      for (int i = 0; i < FM; ++i) af[i] = *(const ex8*)(st + a_row_base + i * 16 * ROW_BYTES + f_off[ks]);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) bf[j] = *(const ex8*)(st + b_row_base + j * 16 * ROW_BYTES + f_off[ks]);
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = tr_mfma(bf[j], af[i], acc[i][j]);
+    }
+    rd = (rd + 1 == NBUF) ? 0 : rd + 1;
+    wr = (wr + 1 == NBUF) ? 0 : wr + 1;
+  }
+
+  if constexpr (EPI == EPI_SLAB) {
+    store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
+  } else {
+    // bf16 C (v_cvt_pk_bf16_f32: round to nearest even, once), family n's 16-byte form (N % 8 == 0, ldc % 8 == 0, a 16-byte aligned C):
+    // v_permlane16_swap exchanges the odd 16-lane rows of column tile j with the even rows of tile j + 1, after which row q = lane >> 4
+    // owns n = 16 (j + (q & 1)) + 8 (q >> 1) + 0 .. 7 of its C row.  Buffer stores, the non-temporal form an instruction of its own;
+    // the tile's bytes are below 2 GiB from its first row (host check).
+    using h2 = __attribute__((ext_vector_type(2))) elem;
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
+    const int q = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      __builtin_amdgcn_sched_barrier(0);   // one fragment row's accumulator reads at a time (store_tile)
+      const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < FN; j += 2) {
+        const h2 a01 = {(elem)acc[i][j][0], (elem)acc[i][j][1]}, a23 = {(elem)acc[i][j][2], (elem)acc[i][j][3]};
+        const h2 b01 = {(elem)acc[i][j + 1][0], (elem)acc[i][j + 1][1]}, b23 = {(elem)acc[i][j + 1][2], (elem)acc[i][j + 1][3]};
+        const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, b01), false, false);
+        const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, b23), false, false);
+        const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);
+        if (tc.m0 + row < g.M && n < g.N) {
+          const u32x4 o = {r0[0], r1[0], r0[1], r1[1]};
+          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
+          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 2);
+          else                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 0);
+        }
+      }
+    }
+  }
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
+// ---- host side: hgemm_kernel_nn.hpp's (tr_table_tn is declared there); the family's one kernel set -------------------------------------
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgTNB, false)   // hgemm_inst_g11.hip
+
+}  // namespace hgemm_mi355x

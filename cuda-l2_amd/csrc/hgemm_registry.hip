@@ -2,6 +2,7 @@
 #include "hgemm_launch.hpp"
 #include "hgemm_kernel_rg.hpp"
 #include "hgemm_kernel_ta.hpp"
+#include "hgemm_kernel_tn.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -207,6 +208,21 @@ __global__ void __launch_bounds__(256) hgemm_generic_kernel(const T* __restrict_
   }
 }
 
+// The reference kernel of the TN layout (bgemm_mi355x_tn, hgemm_kernel_tn.hpp): B given as b_col_major, read as B[n * ldb + k] -- the same
+// one output per thread, the same fma chain in k order and the one rounding to T.  A kernel of its own: hgemm_generic_kernel keeps its
+// template arguments, and with them the symbols of its instances.
+template <class T>
+__global__ void __launch_bounds__(256) hgemm_generic_tn_kernel(const T* __restrict__ A, const T* __restrict__ Bcol, T* __restrict__ C, int M,
+                                                               int N, int K, int lda, int ldb_colmajor, int ldc) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
+    C[(size_t)m * ldc + n] = (T)s;
+  }
+}
+
 // The reference kernel of the fp32-C calls: the same fma chain in k order, then C32 = accumulate ? C32 + s : s (no rounding).
 template <class T, bool A_COL>
 __global__ void __launch_bounds__(256) hgemm_generic_c32_kernel(const T* __restrict__ A, const T* __restrict__ B,
@@ -259,6 +275,13 @@ static void launch_reference(const void* A, const void* B, void* C, int M, int N
     HGEMM_LAUNCH((hgemm_generic_kernel<T, A_COL>), grid, 256, stream, ts, (const T*)A, (const T*)B, (T*)C, M, N, K, lda, ldb, ldc);
 }
 
+template <class T>
+static void launch_reference_tn(const void* A, const void* Bcol, void* C, int M, int N, int K, int lda, int ldb, int ldc, bool, hipStream_t stream,
+                                TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH((hgemm_generic_tn_kernel<T>), grid, 256, stream, ts, (const T*)A, (const T*)Bcol, (T*)C, M, N, K, lda, ldb, ldc);
+}
+
 // the b_col_major families' names for their two (hgemm_launch.hpp)
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
@@ -270,7 +293,7 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
   launch_reference<f16, false, false>(A, B, C, M, N, K, lda, ldb, ldc, false, stream, ts);
 }
 
-// ---- the tables of the two transposed-read layouts (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the member list: a
+// ---- the tables of the three layouts of the transposed-read host path (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the member list: a
 // row is the member's geometry and its launcher in every kernel set of the layout, [TrElem][fp32 C]; `kernels` names the same sets'
 // combine and reference kernel.  A new kernel set is one more cell in the layout's row macro and in its `kernels`.
 // (Inside functions, which both passes read: the device pass instantiates a combine or a reference kernel where it sees its launcher
@@ -281,6 +304,9 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
 #define HGEMM_TA_ROW(P, ...)                                                                                                                 \
   {HGEMM_TR_ENTRY(P, CfgTA, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgTA, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTA, true, __VA_ARGS__)},    \
                                            {&HGEMM_TR_LAUNCHER(CfgTAB, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTAB, true, __VA_ARGS__)}}},
+// TN (family f, hgemm_kernel_tn.hpp): the bf16 set with a 16-bit C alone; every other cell is empty and a call for it is refused
+#define HGEMM_TN_ROW(P, ...) \
+  {HGEMM_TR_ENTRY(P, CfgTNB, __VA_ARGS__), {{nullptr, nullptr}, {&HGEMM_TR_LAUNCHER(CfgTNB, false, __VA_ARGS__), nullptr}}},
 const TrTable& tr_table_nn() {
   static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_NN_ROW, "n")};
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
@@ -293,6 +319,13 @@ const TrTable& tr_table_ta() {
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
                             {{{launch_combine<f16>, launch_reference<f16, true, false>}, {launch_combine_c32, launch_reference<f16, true, true>}},
                              {{launch_combine<__bf16>, launch_reference<__bf16, true, false>}, {launch_combine_c32, launch_reference<__bf16, true, true>}}}};
+  return t;
+}
+
+const TrTable& tr_table_tn() {
+  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TN_ROW, "f")};
+  static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
+                            {{{}, {}}, {{launch_combine<__bf16>, launch_reference_tn<__bf16>}, {}}}};
   return t;
 }
 

@@ -31,6 +31,10 @@
 //                                                     fp16 call of the same plan and shape (c32: both accumulate) and -- context only --
 //                                                     rocBLAS with bf16 in and out; "bf16_le_fp16": bf16 <= fp16 + the fp16 call's own
 //                                                     round-to-round spread (its slowest round minus its median)
+//   hgemm_tune check --layout tn --bf16 [--shapes ...] the bf16 forward product (bgemm_mi355x_launch_tn, family f: B given as b_col_major)
+//   hgemm_tune bench --layout tn --bf16 --shapes ... [--out F.jsonl]
+//                                                     that check first, then per shape interleaved rounds of the planned call, of
+//                                                     bgemm_mi355x_launch_nn with the same member and splits, and -- context -- rocBLAS
 //   hgemm_tune bench --layout nn --shapes ... [--autotune] [--out F.jsonl]
 //                                                     that check first, then per shape interleaved rounds of the planned NN call, the
 //                                                     reference kernel on the same operands, hipBLASLt _nn and the shipped TN plan
@@ -1056,7 +1060,9 @@ struct TrLayout {
   int (*launch_bf16)(int, int, const void*, const void*, void*, int, int, int, int, int, int, void*);
   int (*planned_bf16)(const void*, const void*, void*, int, int, int, void*);
   int (*rocblas_bf16)(const void*, const void*, void*, int, int, int, void*);
+  bool b_col_major = false;     // B handed over as b_col_major [N][K] with ldb = K (else row-major [K][N], ldb = N)
   int lda(const Shape& sh) const { return a_col_major ? sh.M : sh.K; }
+  int ldb(const Shape& sh) const { return b_col_major ? sh.K : sh.N; }
 };
 static const TrLayout kLayoutNN = {"nn", "the NN kernels",
                                    "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
@@ -1070,6 +1076,15 @@ static const TrLayout kLayoutTA = {"ta", "the TA kernels",
                                    true, hgemm_mi355x_ta_num_configs, hgemm_mi355x_ta_config_name, hgemm_mi355x_ta_plan, hgemm_mi355x_ta_runs,
                                    hgemm_mi355x_launch_ta, hgemm_mi355x_ta_fp32, bgemm_mi355x_ta_runs, bgemm_mi355x_launch_ta, bgemm_mi355x_ta,
                                    bgemm_rocblas_ta};
+
+// the bf16 forward product (family f, hgemm_kernel_tn.hpp): bf16 entry points alone (--bf16 is required), a table of its own; the
+// default shapes are the NN layout's -- M is free, K % 64 and N % 8 go to the reference kernel
+static const TrLayout kLayoutTN = {"tn", "the TN kernels",
+                                   "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
+                                   "200_136_72,200_100_128,33_17_40",
+                                   false, bgemm_mi355x_tn_num_configs, bgemm_mi355x_tn_config_name, bgemm_mi355x_tn_plan, nullptr,
+                                   nullptr, nullptr, bgemm_mi355x_tn_runs, bgemm_mi355x_launch_tn, bgemm_mi355x_tn,
+                                   bgemm_rocblas_tn, true};
 
 static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
   if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
@@ -1104,13 +1119,13 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
     } else {
       HIP_OK(hipMemcpy(s.a, operand_bits(z.a).data(), z.a.size() * 2, hipMemcpyHostToDevice));
     }
-    HIP_OK(hipMemcpy(s.b, operand_bits(b_rm).data(), b_rm.size() * 2, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(s.b, operand_bits(L.b_col_major ? z.bt : b_rm).data(), b_rm.size() * 2, hipMemcpyHostToDevice));   // (z.bt: [N][K])
     for (int c = 0; c < nc; ++c) {
       const char* cname = L.config_name(c);
-      const int own = (g_bf16 ? L.runs_bf16 : L.runs)(c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
+      const int own = (g_bf16 ? L.runs_bf16 : L.runs)(c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
         HIP_OK(hipMemset(s.c, 0xff, cn * 2));  // NaN pattern: unwritten outputs are caught
-        const int st = (g_bf16 ? L.launch_bf16 : L.launch)(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N, nullptr);
+        const int st = (g_bf16 ? L.launch_bf16 : L.launch)(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, nullptr);
         const hipError_t e = hipDeviceSynchronize();
         ++runs;
         if (st != HGEMM_OK || e != hipSuccess) {
@@ -1466,6 +1481,69 @@ static int cmd_bench_bf16(const TrLayout& L, bool c32, const std::vector<Shape>&
   return 0;
 }
 
+// bench --layout tn --bf16: the check first, then per shape ONE set of interleaved rounds of the planned bgemm_mi355x_tn call, of
+// bgemm_mi355x_launch_nn with the same member (the two tables list the same tiles in the same order) and the same splits on the same
+// shape -- the same bytes and MFMAs; ds_read_b128 where family n issues pairs of transposed reads --, and, context only, rocBLAS with
+// bf16 in and out on the tn operands.  The one condition: tn <= nn within the nn call's own round-to-round spread in this run (its slowest
+// round minus its median): "tn_le_nn".
+static int cmd_bench_tn_bf16(const std::vector<Shape>& shapes, const char* out_path) {
+  const TrLayout& L = kLayoutTN;
+  int rc = cmd_check_nn(L, {});
+  if (rc != 0) { fprintf(stderr, "bench --layout tn --bf16: the check failed, nothing is timed\n"); return rc; }
+  FILE* out = out_path ? fopen(out_path, "w") : stdout;
+  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  hgemm_rocblas_init();
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0));
+  HIP_OK(hipEventCreate(&e1));
+  for (const Shape& sh : shapes) {
+    const size_t a_elems = (size_t)sh.M * sh.K, b_elems = (size_t)sh.K * sh.N, cn = (size_t)sh.M * sh.N;
+    std::vector<Buffers> sets(2);
+    std::vector<__bf16*> ab(sets.size(), nullptr), bb(sets.size(), nullptr), btb(sets.size(), nullptr), cb(sets.size(), nullptr);
+    for (size_t i = 0; i < sets.size(); ++i) {
+      alloc_set(sets[i], sh, 91 + i, true);   // a [M][K], b [K][N] and bt = b_col_major [N][K] of the same B
+      HIP_OK(hipMalloc(&ab[i], a_elems * 2));
+      HIP_OK(hipMalloc(&bb[i], b_elems * 2));
+      HIP_OK(hipMalloc(&btb[i], b_elems * 2));
+      HIP_OK(hipMalloc(&cb[i], cn * 2));
+      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].a, ab[i], a_elems);
+      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].b, bb[i], b_elems);
+      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].bt, btb[i], b_elems);
+    }
+    HIP_OK(hipDeviceSynchronize());
+    int cfg = 0, splits = 1;
+    L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
+    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
+    std::vector<Contender> cs;
+    cs.push_back({"tn", [&](Buffers& b) { return bgemm_mi355x_tn(ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
+    cs.push_back({"nn", [&](Buffers& b) { return bgemm_mi355x_launch_nn(cfg, splits, ab[idx(b)], bb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, sh.K, sh.N, sh.N, nullptr); }});
+    cs.push_back({"rocblas_tn", [&](Buffers& b) { return bgemm_rocblas_tn(ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
+    const int rounds = 15;
+    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
+    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
+    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"tn\", \"output\": \"c16\", \"elem\": \"bf16\", \"config\": \"%s\", \"nn_config\": \"%s\", \"splits\": %d, "
+                 "\"runs\": %d, \"nn_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, L.config_name(cfg),
+            hgemm_mi355x_nn_config_name(cfg), splits, L.runs_bf16(cfg, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N),
+            bgemm_mi355x_nn_runs(cfg, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N), rounds);
+    for (const Contender& c : cs) {
+      const double us = c.iso_us();
+      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
+    }
+    const double t_us = cs[0].iso_us(), n_us = cs[1].iso_us();
+    const double spread = cs[1].ok && !cs[1].iso.empty() ? *std::max_element(cs[1].iso.begin(), cs[1].iso.end()) - n_us : -1.0;
+    fprintf(out, ", \"nn_spread_us\": %.3f, \"tn_le_nn\": %s}\n", spread, t_us > 0 && n_us > 0 && t_us <= n_us + spread ? "true" : "false");
+    fflush(out);
+    for (size_t i = 0; i < sets.size(); ++i) {
+      free_set(sets[i]);
+      HIP_OK(hipFree(ab[i])); HIP_OK(hipFree(bb[i])); HIP_OK(hipFree(btb[i])); HIP_OK(hipFree(cb[i]));
+    }
+  }
+  HIP_OK(hipEventDestroy(e0));
+  HIP_OK(hipEventDestroy(e1));
+  if (out != stdout) fclose(out);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1477,7 +1555,7 @@ int main(int argc, char** argv) {
   const char* cfg_name = nullptr;
   double keep = 2.5;
   int max_cand = 12, splits = 1, group = 0, reps = 20;
-  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false, layout_ta = false, c32 = false;
+  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false, layout_ta = false, layout_tn = false, c32 = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -1488,7 +1566,7 @@ int main(int argc, char** argv) {
     else if (a == "--layout") {
       const std::string l = next();
       if (l != "nn" && l != "tn" && l != "ta") { fprintf(stderr, "--layout takes nn, ta or tn\n"); return 2; }
-      layout_nn = l == "nn"; layout_ta = l == "ta";
+      layout_nn = l == "nn"; layout_ta = l == "ta"; layout_tn = l == "tn";
     }
     else if (a == "--c32") c32 = true;
     else if (a == "--bf16") g_bf16 = true;
@@ -1567,7 +1645,16 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--layout nn goes with check or bench\n");
     return 2;
   }
-  if (g_bf16) { fprintf(stderr, "--bf16 goes with --layout nn or ta (the b_col_major families have no bf16 form)\n"); return 2; }
+  if (g_bf16 && layout_tn) {   // family f: the bf16 forward product (bgemm_mi355x_launch_tn); without --bf16, tn is the fp16 families below
+    if (mode == "check") return cmd_check_nn(kLayoutTN, shapes);
+    if (mode == "bench") {
+      if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
+      return cmd_bench_tn_bf16(shapes, out_path);
+    }
+    fprintf(stderr, "--layout tn --bf16 goes with check or bench\n");
+    return 2;
+  }
+  if (g_bf16) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
   if (mode == "check") {
     if (shapes.empty())
       // (the last two: K tails -- 2104 = 32 x 64 + 56 = 8 x 256 + 56, 728 = 11 x 64 + 24 = 5 x 128 + 88 = 2 x 256 + 216: odd and even

@@ -369,8 +369,8 @@ int hgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ld
  * A call outside the kernels' scope is answered by a bf16 reference kernel (HGEMM_OK, exact, slow: the _runs functions tell); every call
  * is capturable, and a captured split call without a workspace runs unsplit with status 0.  The names carry no accumulate mode: there
  * is one, fp32.
- * The b_col_major (forward) families -- hgemm_mi355x_fp32 / _fp16 / _launch -- have NO bf16 form, and no existing entry point changes what
- * it does. */
+ * The b_col_major (forward) families -- hgemm_mi355x_fp32 / _fp16 / _launch -- have NO bf16 form of their own (the bf16 forward product is
+ * bgemm_mi355x_tn below: kernels of its own on this path), and no existing entry point changes what it does. */
 /* planned, contiguous (nn: lda = K; ta: lda = M; ldb = ldc = N) */
 int bgemm_mi355x_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream);
 int bgemm_mi355x_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream);
@@ -386,6 +386,37 @@ int bgemm_mi355x_launch_ta_c32(int ta_config, int splits, const void* a_col_majo
 int bgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc);
 int bgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
 int bgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc);
+
+/* ------------------------------------------------------------------------------------------
+ * bfloat16 forward product ("tn"): Y = X x W^T with W stored [out][in] -- C[M,N] = A[M,K] x B[K,N], A row-major [M][lda] and B given as
+ * b_col_major [N][ldb] (K contiguous), the operand form of hgemm_mi355x_fp32's b_col_major and of hgemm_rocblas_tn, with bfloat16
+ * operands and a bfloat16 C.  With bgemm_mi355x_nn (dX) and bgemm_mi355x_ta / _ta_c32 (dW) a bf16 linear layer's three products.
+ * Replaces a cast of X and W to fp16 in front of hgemm_mi355x_fp32 (which loses bf16's range) or a rocblas_gemm_ex call with bf16 types.
+ * Accumulation is fp32; C is the fp32 sum rounded to bf16 ONCE, to nearest even -- in the kernel's epilogue, or in the combine of a
+ * two-pass plan, whose slabs are fp32.  The kernels are family f (csrc/hgemm_kernel_tn.hpp): family n's ring and epilogues, both operand
+ * images the classic [rows][128 B] one, v_mfma_f32_16x16x32_bf16, no transposed LDS read.
+ * A third layout of the NN / TA host path, with a table of its own (four members, f64x64_w2x2 .. f128x128_w2x2: the n members' tiles,
+ * ring depths and LDS bytes).  The splits word (HGEMM_PLAN_NT_STORE is honoured, HGEMM_SPLITK_FUSED runs two-pass, HGEMM_PLAN_STREAMK
+ * plain), the statuses, the capture behaviour (capturable; a captured split call without a workspace runs unsplit with status 0) and
+ * the planner's rule are those of hgemm_mi355x_launch_nn / _nn_plan.
+ * Scope of the kernels: K % 64 == 0, N % 8 == 0 (M is free), lda / ldb / ldc multiples of 8, 16-byte aligned pointers, and
+ * (BM lda + K) 2, (BN ldb + K) 2, (BM ldc + N) 2 bytes below 2 GiB.  Least strides: lda >= K, ldb >= K, ldc >= N (less: HGEMM_ERR_BAD_ARG).
+ * A call outside the scope is answered by a bf16 reference kernel (HGEMM_OK, exact, slow: bgemm_mi355x_tn_runs tells).
+ * The fp16 forward calls (hgemm_mi355x_fp32 / _fp16 / _launch, the geometry table, hgemm_mi355x_plan) are unchanged, and there is no
+ * fp16 "tn" call on this path: fp16 callers have those. */
+/* planned, contiguous (lda = ldb = K, ldc = N) */
+int bgemm_mi355x_tn(const void* a, const void* b_col_major, void* c, int M, int N, int K, void* stream);
+int bgemm_mi355x_launch_tn(int tn_config, int splits, const void* a, const void* b_col_major, void* c,
+                           int M, int N, int K, int lda, int ldb, int ldc, void* stream);
+/* 1 when the call runs one of the family's kernels, 0 when it falls back to the reference kernel or is refused */
+int bgemm_mi355x_tn_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc);
+int bgemm_mi355x_tn_num_configs(void);
+const char* bgemm_mi355x_tn_config_name(int tn_config);
+int bgemm_mi355x_tn_config_by_name(const char* name);
+int bgemm_mi355x_tn_config_info(int tn_config, int out[8]);   /* as hgemm_mi355x_nn_config_info */
+int bgemm_mi355x_tn_plan(int M, int N, int K, int* tn_config, int* splits);
+size_t bgemm_mi355x_tn_plan_workspace_bytes(int tn_config, int splits, int M, int N, int K);
+int bgemm_mi355x_tn_reserve_workspace(int M, int N, int K, void* stream);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
@@ -405,6 +436,8 @@ int hgemm_rocblas_ta(const void* a_col_major, const void* b, void* c, int M, int
 /* the vendor counterparts of bgemm_mi355x_nn / _ta: the same rocblas_gemm_ex calls with bf16 operands and C, fp32 compute */
 int bgemm_rocblas_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream);
 int bgemm_rocblas_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream);
+/* ... and of bgemm_mi355x_tn: hgemm_rocblas_tn's call with bf16 operands and C */
+int bgemm_rocblas_tn(const void* a, const void* b_col_major, void* c, int M, int N, int K, void* stream);
 
 /* hipBLASLt heuristic  <-  cublasLtMatmulAlgoGetHeuristic top-1 of 4, cached
  * (reference cublas/fp32/hgemm_cublaslt_heuristic.cu:65-217). */
