@@ -26,6 +26,10 @@
 //     predicated.  Scope (the host sends anything else to the reference kernel): K % 64 == 0, N % 8 == 0, lda / ldb / ldc
 //     multiples of 8, 16-byte aligned pointers, operands within 2 GiB of 32-bit offsets.
 //   * Epilogues: fp16 C (plain and non-temporal) and the two-pass split-K slab (hgemm_splitk_reduce_kernel combines).
+//   * One text for families n, a and f (hgemm_kernel_ta.hpp, hgemm_kernel_tn.hpp): the 16-bit C epilogue (hgemm_tr_store_c16.inc,
+//     included by the three kernels) and, for n and a, the accumulator zeroing (tr_zero).  The bar: every kernel's instruction stream,
+//     register counts, LDS and scratch as they were.  The preamble, the ring and the operand images did not meet it in
+//     any form tried and stay in each kernel, on purpose; an edit to one of them is made in all three.
 #pragma once
 
 #include "hgemm_launch.hpp"
@@ -101,6 +105,17 @@ __device__ __forceinline__ f32x4 tr_mfma(V b, V a, f32x4 c) {
   else                               return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
 }
 
+// accumulators of a wave tile, zeroed (families n and a; family f keeps the loop in place, see there)
+template <int FM, int FN>
+__device__ __forceinline__ void tr_zero(f32x4 (&acc)[FM][FN]) {
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
+}
+
 // GemmArgs as the kernel reads it: Bt = the ROW-MAJOR B ([K][ldb]), ldb >= N its row stride; tail_tiles = 0, counters = nullptr.
 template <class CFG, int EPI>
 __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g) {
@@ -173,12 +188,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
   }
 
   f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
+  tr_zero(acc);
 
   // ---- pipeline ----------------------------------------------------------------------------------
   uint32_t kbyte = (uint32_t)tc.k_begin * 2u;
@@ -235,33 +245,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
   if constexpr (EPI == EPI_SLAB) {
     store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
   } else {
-    // 16-bit C (fp16, or bf16 from v_cvt_pk_bf16_f32: round to nearest even, once), the 16-byte form of store_tile_row alone (the host sends the kernel N % 8 == 0, ldc % 8 == 0 and a 16-byte aligned
-    // C): v_permlane16_swap exchanges the odd 16-lane rows of column tile j with the even rows of tile j + 1, after which row
-    // q = lane >> 4 owns n = 16 (j + (q & 1)) + 8 (q >> 1) + 0 .. 7 of its C row.  Buffer stores: the non-temporal form is an
-    // instruction of its own (two plain C++ stores that differ only in the hint are merged by the optimiser and the hint is lost);
-    // the tile's bytes are below 2 GiB from its first row (host check).
-    using h2 = __attribute__((ext_vector_type(2))) elem;
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
-    const int q = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      __builtin_amdgcn_sched_barrier(0);   // one fragment row's accumulator reads at a time (store_tile)
-      const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < FN; j += 2) {
-        const h2 a01 = {(elem)acc[i][j][0], (elem)acc[i][j][1]}, a23 = {(elem)acc[i][j][2], (elem)acc[i][j][3]};
-        const h2 b01 = {(elem)acc[i][j + 1][0], (elem)acc[i][j + 1][1]}, b23 = {(elem)acc[i][j + 1][2], (elem)acc[i][j + 1][3]};
-        const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, b01), false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, b23), false, false);
-        const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);
-        if (tc.m0 + row < g.M && n < g.N) {
-          const u32x4 o = {r0[0], r1[0], r0[1], r1[1]};
-          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
-          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 2);
-          else                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 0);
-        }
-      }
-    }
+#include "hgemm_tr_store_c16.inc"   // the 16-bit C epilogue, one text for families n, a and f
   }
 #endif  // __HIP_DEVICE_COMPILE__
 }

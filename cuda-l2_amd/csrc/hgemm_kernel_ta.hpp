@@ -30,9 +30,10 @@
 //     EPI_C32 (hgemm_inst_g7.hip, hgemm_mi355x_ta_c32): the fp32 accumulators stored to, or added into, the caller's fp32 C -- the
 //     weight gradient where a training step consumes it; its two-pass form combines the same slabs with
 //     hgemm_splitk_reduce_c32_kernel.
-//   * Shared with family n: the Cfg base (CfgTR), launch_tr, the member list and its macros, the table types, nn_swz.  The kernel body is family n's
-//     text once more, on purpose: as one force-inlined function template under two __global__ wrappers it compiled to a different K
-//     loop in every kernel.
+//   * Shared with family n: the Cfg base (CfgTR), launch_tr, the member list and its macros, the table types, nn_swz, tr_zero and the 16-bit C
+//     epilogue (hgemm_tr_store_c16.inc).  The preamble, the images and the ring are family n's text once more, on purpose: as shared
+//     functions -- the whole body, or an image's addressing and reads alone -- they compiled to a different K loop in every kernel
+//     (DESIGN.md 4.22).
 //   tests/test_ta_host.py replays the A image with tests/nn_layout_model.py (bn := BM, tn := TM, wave_n := wave_m) and restates the
 //   lane address expression of a_off below.
 #pragma once
@@ -137,12 +138,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
   }
 
   f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
+  tr_zero(acc);
 
   // ---- pipeline ----------------------------------------------------------------------------------
   auto stage = [&](char* lds_stage) __attribute__((always_inline)) {
@@ -245,32 +241,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_ta_kernel(const GemmArgs g
       }
     }
   } else {
-    // 16-bit C (fp16, or bf16 from v_cvt_pk_bf16_f32: round to nearest even, once), family n's 16-byte form (N % 8 == 0, ldc % 8 == 0, a 16-byte aligned C): v_permlane16_swap exchanges the odd 16-lane
-    // rows of column tile j with the even rows of tile j + 1, after which row q = lane >> 4 owns n = 16 (j + (q & 1)) + 8 (q >> 1)
-    // + 0 .. 7 of its C row.  Buffer stores, the non-temporal form an instruction of its own; the tile's bytes are below 2 GiB from
-    // its first row (host check).
-    using h2 = __attribute__((ext_vector_type(2))) elem;
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
-    const int q = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      __builtin_amdgcn_sched_barrier(0);   // one fragment row's accumulator reads at a time (store_tile)
-      const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < FN; j += 2) {
-        const h2 a01 = {(elem)acc[i][j][0], (elem)acc[i][j][1]}, a23 = {(elem)acc[i][j][2], (elem)acc[i][j][3]};
-        const h2 b01 = {(elem)acc[i][j + 1][0], (elem)acc[i][j + 1][1]}, b23 = {(elem)acc[i][j + 1][2], (elem)acc[i][j + 1][3]};
-        const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, b01), false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, b23), false, false);
-        const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);
-        if (tc.m0 + row < g.M && n < g.N) {
-          const u32x4 o = {r0[0], r1[0], r0[1], r1[1]};
-          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
-          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 2);
-          else                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 0);
-        }
-      }
-    }
+#include "hgemm_tr_store_c16.inc"   // the 16-bit C epilogue, one text for families n, a and f
   }
 #endif  // __HIP_DEVICE_COMPILE__
 }

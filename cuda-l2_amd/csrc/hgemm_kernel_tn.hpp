@@ -21,9 +21,9 @@
 //     lda / ldb / ldc multiples of 8, 16-byte aligned pointers, (BM lda + K) 2, (BN ldb + K) 2 and (BM ldc + N) 2 bytes below 2 GiB.
 //   * Epilogues: family n's: bf16 C (each accumulator rounded once by v_cvt_pk_bf16_f32, v_permlane16_swap, 16-byte buffer stores, the
 //     plain and the non-temporal store an instruction each) and the two-pass split-K slab (hgemm_splitk_reduce_kernel<__bf16> combines).
-//   * Shared with family n: CfgTR, tr_mfma, launch_tr, the member list and its macros, the table types.  The kernel body is family n's
-//     text a third time, on purpose (a repeated body over a changed loop); families n and a keep their symbols and,
-//     as compiled, their instruction streams.
+//   * Shared with family n: CfgTR, tr_mfma, launch_tr, the member list and its macros, the table types and the 16-bit C epilogue
+//     (hgemm_tr_store_c16.inc).  The preamble, the images and the ring are family n's text a third time, on purpose (a
+//     repeated text over a changed loop); families n and a keep their symbols and, as compiled, their instruction streams.
 #pragma once
 
 #include "hgemm_kernel_nn.hpp"
@@ -91,6 +91,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
   const int b_row_base = CFG::A_BYTES + wave_n * CFG::TN * ROW_BYTES;
 
   f32x4 acc[FM][FN];
+  // (not tr_zero, hgemm_kernel_nn.hpp: through the function, the four EPI_C16 kernels here number their scalar registers differently)
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -144,32 +145,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
   if constexpr (EPI == EPI_SLAB) {
     store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
   } else {
-    // bf16 C (v_cvt_pk_bf16_f32: round to nearest even, once), family n's 16-byte form (N % 8 == 0, ldc % 8 == 0, a 16-byte aligned C):
-    // v_permlane16_swap exchanges the odd 16-lane rows of column tile j with the even rows of tile j + 1, after which row q = lane >> 4
-    // owns n = 16 (j + (q & 1)) + 8 (q >> 1) + 0 .. 7 of its C row.  Buffer stores, the non-temporal form an instruction of its own;
-    // the tile's bytes are below 2 GiB from its first row (host check).
-    using h2 = __attribute__((ext_vector_type(2))) elem;
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
-    const int q = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      __builtin_amdgcn_sched_barrier(0);   // one fragment row's accumulator reads at a time (store_tile)
-      const int row = wave_m * CFG::TM + i * 16 + (lane & 15);
-#pragma unroll
-      for (int j = 0; j < FN; j += 2) {
-        const h2 a01 = {(elem)acc[i][j][0], (elem)acc[i][j][1]}, a23 = {(elem)acc[i][j][2], (elem)acc[i][j][3]};
-        const h2 b01 = {(elem)acc[i][j + 1][0], (elem)acc[i][j + 1][1]}, b23 = {(elem)acc[i][j + 1][2], (elem)acc[i][j + 1][3]};
-        const auto r0 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, b01), false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a23), __builtin_bit_cast(unsigned, b23), false, false);
-        const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);
-        if (tc.m0 + row < g.M && n < g.N) {
-          const u32x4 o = {r0[0], r1[0], r0[1], r1[1]};
-          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
-          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 2);
-          else                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 0);
-        }
-      }
-    }
+#include "hgemm_tr_store_c16.inc"   // the 16-bit C epilogue, one text for families n, a and f
   }
 #endif  // __HIP_DEVICE_COMPILE__
 }
