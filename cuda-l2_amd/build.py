@@ -47,6 +47,7 @@ LIB_SOURCES = [
     "hgemm_inst_g9.hip",
     "hgemm_inst_g10.hip",
     "hgemm_inst_g11.hip",
+    "hgemm_inst_g12.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

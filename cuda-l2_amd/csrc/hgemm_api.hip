@@ -473,17 +473,22 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // resolution, launch, planner and the queries below are written once and take the description.
 // What a call writes: fp16 C (every nn_ / ta_ entry point) or fp32 C (c32: hgemm_mi355x_ta_c32, family a only), stored or -- c32 only --
 // added into what C holds.  ldc counts C's own elements.
+// bias (bgemm_mi355x_tn_bias, family f only): a 16-bit C with a bf16 bias vector fused into the epilogue -- C = T(sum + float(bias[n])), the
+// bias added last and the sum rounded once.  The third output kind: the same tiles, cuts and slabs as the plain 16-bit C.
 struct TrOut {
   bool c32, accumulate;
+  bool bias = false;
   int elem_bytes() const { return c32 ? 4 : 2; }
+  TrKind kind() const { return bias ? TR_C16_BIAS : c32 ? TR_C32 : TR_C16; }   // the kernel set's cell in TrRow / TrTable
 };
 constexpr TrOut kOutC16{false, false};
+constexpr TrOut kOutC16Bias{false, false, true};
 
 // What the operands and a 16-bit C hold (TrElem): fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements
 // are 2 bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  (TrElem, c32) selects a kernel set and nothing
 // else: the member's launcher in its row, the set's combine and reference kernel in the table's `kernels`.
 struct TrLayout {
-  const TrTable& t;   // rows by config id and kernels[TrElem][c32]; a set the layout does not have is empty, and a call for it is refused
+  const TrTable& t;   // rows by config id and kernels[TrElem][TrKind]; a set the layout does not have is empty, and a call for it is refused
   // How A lies in memory decides every rule in which the two layouts differ.  false (n): [M][lda], rows of K elements, staged and
   // addressed from a tile's first row.  true (a): [K][lda], k-rows of M elements, staged as B is and addressed from row 0 to the end
   // of the matrix; a chunk of a k-row must not straddle M, so M % 8 == 0 joins the scope.
@@ -522,6 +527,8 @@ const TrLayout kLayoutTN{tr_table_tn(), false, true, TR_BF16};   // the bf16 for
 // (same shape as resolve_launch: host logic only; hgemm_mi355x_selfcheck_launch_nn / _ta show it to the CPU tests)
 // out.c32: the same tiles, cuts and slabs; the plain dispatch and the combine carry EPI_C32 (the K slices are the family's EPI_SLAB
 // kernels), the least ldc is still N
+// out.bias: the plan of the plain 16-bit call in everything but the epi of the plain dispatch and of the combine dispatch, EPI_C16_BIAS;
+// the bias pointer is no input (its alignment arrives in `aligned`, as the operands' does)
 LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
                       unsigned ruled_out) {
   LaunchPlan p;
@@ -533,8 +540,8 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
   // rows must not overlap: lda >= K (n, f) / >= M, the row stride of a_col_major (a); ldb >= N (n, a: B is row-major) / >= K, the row
   // stride of b_col_major (f); ldc >= N
   if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < L.b_row(N, K) || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
-  if (!L.t.kernels[elem][out.c32].reference || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no such kernel set in this layout
-  const int epi_out = out.c32 ? EPI_C32 : EPI_C16;
+  if (!L.t.kernels[elem][out.kind()].reference || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no such kernel set in this layout
+  const int epi_out = out.c32 ? EPI_C32 : out.bias ? EPI_C16_BIAS : EPI_C16;
   const TrEntry& e = L.t.rows[config].e;
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -563,7 +570,7 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
     p.form = FORM_SPLITK;
     p.slab_bytes = (size_t)splits * M * N * sizeof(float);
     add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
-    add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : EPI_SLAB);
+    add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : out.bias ? EPI_C16_BIAS : EPI_SLAB);
   } else {
     add(THUNK_ENTRY, g, tiles, epi_out);
   }
@@ -596,13 +603,17 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 
 // GemmArgs as the kernels read it: A = a (n, f: [M][lda], a: [K][lda]), Bt = the row-major B (n, a) / b_col_major (f)
 // (out.c32: c is the float pointer; it travels in g.C and the EPI_C32 kernels reinterpret it)
-// (elem, out.c32): the kernel set -- the member's launcher, the combine and the reference kernel; the plan does not depend on elem
-int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda,
-              int ldb, int ldc, void* stream) {
+// (elem, out.kind()): the kernel set -- the member's launcher, the combine and the reference kernel; the plan does not depend on elem
+// (out.bias: `bias` is the bf16 vector of N elements, required, and joins the kernels' 16-byte alignment rule.  It reaches the combine and
+// the reference kernel as an argument and the member's EPI_C16_BIAS kernel in g.counters -- a field the launches of these families leave
+// null; GemmArgs keeps its layout, the kernel reinterprets the pointer (hgemm_kernel_tn.hpp).  The EPI_SLAB dispatch of a split call keeps
+// counters null: store_tile reads a non-null counters as "compact slabs".)
+int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
+              int N, int K, int lda, int ldb, int ldc, void* stream) {
   DisarmTiming disarm_timing;
-  if (!a || !b || !c || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  if (!a || !b || !c || (out.bias && !bias) || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc);
+  const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15));
   unsigned ruled_out = 0;
   LaunchPlan p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
@@ -617,17 +628,18 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
     }
   }
   if (p.status != HGEMM_OK) return p.status;
-  const TrKernels& kern = L.t.kernels[elem][out.c32];
-  const TrLaunch launch = L.t.rows[config].launch[elem][out.c32];
+  const TrKernels& kern = L.t.kernels[elem][out.kind()];
+  const TrLaunch launch = L.t.rows[config].launch[elem][out.kind()];
   for (int i = 0; i < p.n; ++i) {
     GemmArgs& g = p.d[i].g;
     g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (bf16 travels in the same fields: the kernels of its Cfgs reinterpret)
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
+    if (p.d[i].epi == EPI_C16_BIAS) g.counters = (unsigned*)const_cast<void*>(bias);   // read-only there: the kernel's bf16 bias vector
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
     switch (p.d[i].thunk) {
       case THUNK_ENTRY: launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
-      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, M, N, ldc, g.splits, out.accumulate, s, ts); break;
-      default: kern.reference(a, b, c, M, N, K, lda, ldb, ldc, out.accumulate, s, ts); break;
+      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, bias, M, N, ldc, g.splits, out.accumulate, s, ts); break;
+      default: kern.reference(a, b, c, bias, M, N, K, lda, ldb, ldc, out.accumulate, s, ts); break;
     }
   }
   hipError_t err = hipGetLastError();
@@ -636,11 +648,11 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
 }
 
 // the planned call on contiguous operands
-int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void* b, void* c, int M, int N, int K, void* stream) {
+int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void* b, const void* bias, void* c, int M, int N, int K, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   int cfg, splits;
   tr_model_plan(L, M, N, K, &cfg, &splits);
-  return tr_launch(L, elem, out, cfg, splits, a, b, c, M, N, K, L.a_row(M, K), L.b_row(N, K), N, stream);
+  return tr_launch(L, elem, out, cfg, splits, a, b, bias, c, M, N, K, L.a_row(M, K), L.b_row(N, K), N, stream);
 }
 
 const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.t.count) ? L.t.rows[id].e.name : nullptr; }
@@ -961,10 +973,10 @@ size_t hgemm_mi355x_nn_plan_workspace_bytes(int nn_config, int splits, int M, in
 int hgemm_mi355x_nn_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutNN, M, N, K, stream); }
 int hgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
                            int ldc, void* stream) {
-  return tr_launch(kLayoutNN, TR_F16, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutNN, TR_F16, kOutC16, nn_config, splits_arg, a, b, nullptr, c, M, N, K, lda, ldb, ldc, stream);
 }
-int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_F16, kOutC16, a, b, c, M, N, K, stream); }
-int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_F16, kOutC16, a, b, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp32(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_F16, kOutC16, a, b, nullptr, c, M, N, K, stream); }
+int hgemm_mi355x_nn_fp16(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_F16, kOutC16, a, b, nullptr, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_nn(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
   return tr_selfcheck_launch(kLayoutNN, TR_F16, kOutC16, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
@@ -982,10 +994,10 @@ size_t hgemm_mi355x_ta_plan_workspace_bytes(int ta_config, int splits, int M, in
 int hgemm_mi355x_ta_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutTA, M, N, K, stream); }
 int hgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
                            int ldb, int ldc, void* stream) {
-  return tr_launch(kLayoutTA, TR_F16, kOutC16, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTA, TR_F16, kOutC16, ta_config, splits_arg, a_col_major, b, nullptr, c, M, N, K, lda, ldb, ldc, stream);
 }
-int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_F16, kOutC16, a_col_major, b, c, M, N, K, stream); }
-int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_F16, kOutC16, a_col_major, b, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp32(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_F16, kOutC16, a_col_major, b, nullptr, c, M, N, K, stream); }
+int hgemm_mi355x_ta_fp16(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_F16, kOutC16, a_col_major, b, nullptr, c, M, N, K, stream); }
 int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
   return tr_selfcheck_launch(kLayoutTA, TR_F16, kOutC16, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
@@ -996,11 +1008,11 @@ int hgemm_mi355x_selfcheck_launch_ta(int ta_config, int splits, int operands, in
 int hgemm_mi355x_launch_ta_c32(int ta_config, int splits_arg, const void* a_col_major, const void* b, float* c32, int M, int N, int K, int lda,
                                int ldb, int ldc, int accumulate, void* stream) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_launch(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, c32, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, nullptr, c32, M, N, K, lda, ldb, ldc, stream);
 }
 int hgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int M, int N, int K, int accumulate, void* stream) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_run(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
+  return tr_run(kLayoutTA, TR_F16, TrOut{true, accumulate == 1}, a_col_major, b, nullptr, c32, M, N, K, stream);
 }
 int hgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
   return tr_runs(kLayoutTA, TR_F16, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
@@ -1016,24 +1028,24 @@ int hgemm_mi355x_selfcheck_launch_ta_c32(int ta_config, int splits, int operands
 // families have no bf16 form (the bf16 forward product is the TN layout below, kernels of its own).
 int bgemm_mi355x_launch_nn(int nn_config, int splits_arg, const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb,
                            int ldc, void* stream) {
-  return tr_launch(kLayoutNN, TR_BF16, kOutC16, nn_config, splits_arg, a, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutNN, TR_BF16, kOutC16, nn_config, splits_arg, a, b, nullptr, c, M, N, K, lda, ldb, ldc, stream);
 }
-int bgemm_mi355x_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_BF16, kOutC16, a, b, c, M, N, K, stream); }
+int bgemm_mi355x_nn(const void* a, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutNN, TR_BF16, kOutC16, a, b, nullptr, c, M, N, K, stream); }
 int bgemm_mi355x_nn_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutNN, TR_BF16, kOutC16, nn_config, M, N, K, lda, ldb, ldc); }
 int bgemm_mi355x_launch_ta(int ta_config, int splits_arg, const void* a_col_major, const void* b, void* c, int M, int N, int K, int lda,
                            int ldb, int ldc, void* stream) {
-  return tr_launch(kLayoutTA, TR_BF16, kOutC16, ta_config, splits_arg, a_col_major, b, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTA, TR_BF16, kOutC16, ta_config, splits_arg, a_col_major, b, nullptr, c, M, N, K, lda, ldb, ldc, stream);
 }
-int bgemm_mi355x_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_BF16, kOutC16, a_col_major, b, c, M, N, K, stream); }
+int bgemm_mi355x_ta(const void* a_col_major, const void* b, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTA, TR_BF16, kOutC16, a_col_major, b, nullptr, c, M, N, K, stream); }
 int bgemm_mi355x_ta_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTA, TR_BF16, kOutC16, ta_config, M, N, K, lda, ldb, ldc); }
 int bgemm_mi355x_launch_ta_c32(int ta_config, int splits_arg, const void* a_col_major, const void* b, float* c32, int M, int N, int K, int lda,
                                int ldb, int ldc, int accumulate, void* stream) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_launch(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, c32, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, ta_config, splits_arg, a_col_major, b, nullptr, c32, M, N, K, lda, ldb, ldc, stream);
 }
 int bgemm_mi355x_ta_c32(const void* a_col_major, const void* b, float* c32, int M, int N, int K, int accumulate, void* stream) {
   if (accumulate != 0 && accumulate != 1) return HGEMM_ERR_BAD_ARG;
-  return tr_run(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, a_col_major, b, c32, M, N, K, stream);
+  return tr_run(kLayoutTA, TR_BF16, TrOut{true, accumulate == 1}, a_col_major, b, nullptr, c32, M, N, K, stream);
 }
 int bgemm_mi355x_ta_c32_runs(int ta_config, int M, int N, int K, int lda, int ldb, int ldc) {
   return tr_runs(kLayoutTA, TR_BF16, TrOut{true, false}, ta_config, M, N, K, lda, ldb, ldc);
@@ -1068,12 +1080,38 @@ size_t bgemm_mi355x_tn_plan_workspace_bytes(int tn_config, int splits, int M, in
 int bgemm_mi355x_tn_reserve_workspace(int M, int N, int K, void* stream) { return tr_reserve_workspace(kLayoutTN, M, N, K, stream); }
 int bgemm_mi355x_launch_tn(int tn_config, int splits_arg, const void* a, const void* b_col_major, void* c, int M, int N, int K, int lda,
                            int ldb, int ldc, void* stream) {
-  return tr_launch(kLayoutTN, TR_BF16, kOutC16, tn_config, splits_arg, a, b_col_major, c, M, N, K, lda, ldb, ldc, stream);
+  return tr_launch(kLayoutTN, TR_BF16, kOutC16, tn_config, splits_arg, a, b_col_major, nullptr, c, M, N, K, lda, ldb, ldc, stream);
 }
-int bgemm_mi355x_tn(const void* a, const void* b_col_major, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTN, TR_BF16, kOutC16, a, b_col_major, c, M, N, K, stream); }
+int bgemm_mi355x_tn(const void* a, const void* b_col_major, void* c, int M, int N, int K, void* stream) { return tr_run(kLayoutTN, TR_BF16, kOutC16, a, b_col_major, nullptr, c, M, N, K, stream); }
 int bgemm_mi355x_selfcheck_launch_tn(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                      long long out[20]) {
   return tr_selfcheck_launch(kLayoutTN, TR_BF16, kOutC16, tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- the forward product with a fused bias, Y = X W^T + b (the layout's third output kind, kOutC16Bias): C = bf16(S + float(bias[n])), S
+// the finished fp32 sum, the bias added last and the result rounded once.  Table, ids, names, plan, workspace size and reserve call are
+// bgemm_mi355x_tn_*'s: the tiles, cuts and slabs are the same.  bias: bf16, N elements, required (a caller without one has bgemm_mi355x_tn).
+int bgemm_mi355x_tn_bias_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc) { return tr_runs(kLayoutTN, TR_BF16, kOutC16Bias, tn_config, M, N, K, lda, ldb, ldc); }
+int bgemm_mi355x_launch_tn_bias(int tn_config, int splits_arg, const void* a, const void* b_col_major, const void* bias, void* c, int M, int N,
+                                int K, int lda, int ldb, int ldc, void* stream) {
+  return tr_launch(kLayoutTN, TR_BF16, kOutC16Bias, tn_config, splits_arg, a, b_col_major, bias, c, M, N, K, lda, ldb, ldc, stream);
+}
+int bgemm_mi355x_tn_bias(const void* a, const void* b_col_major, const void* bias, void* c, int M, int N, int K, void* stream) {
+  if (!bias) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutTN, TR_BF16, kOutC16Bias, a, b_col_major, bias, c, M, N, K, stream);
+}
+// (operands & 4: a, b_col_major, c AND bias 16-byte aligned.  The NN and TA layouts have no such kernel set: their twins show the refusal.)
+int bgemm_mi355x_selfcheck_launch_tn_bias(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                          long long out[20]) {
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, kOutC16Bias, tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_nn_bias(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                          long long out[20]) {
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, kOutC16Bias, nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_ta_bias(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                          long long out[20]) {
+  return tr_selfcheck_launch(kLayoutTA, TR_BF16, kOutC16Bias, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the

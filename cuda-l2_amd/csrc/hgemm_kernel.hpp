@@ -200,6 +200,8 @@ struct GemmArgs {
   int tail_first, tail_tiles;
   // Single-launch split-K (EPI_FUSED): one arrival counter per output tile (zero before the launch, reset
   // by the last arriver) and compact per-item slabs partial[item][BM*BN] in the kernel's own lane order.
+  // (Families n, a and f launch with nullptr here; the one exception is an EPI_C16_BIAS launch of family f, which carries the bf16 bias
+  // vector in this field -- the struct keeps its size and every kernarg offset.)
   unsigned* counters;
   int flags;       // ARG_* bits (above)
   RasterDiv rd;    // multipliers for the raster map's divisions (set_raster_div on the host, after the fields above are final)
@@ -290,6 +292,8 @@ constexpr int EPI_FUSED  = 2;  // single-launch split-K: fp32 partials + arrival
 constexpr int EPI_STREAMK = 3; // stream-K: one persistent launch over the tile-major K-stage sequence (StreamK above)
 constexpr int EPI_C32    = 4;  // fp32 C (family a): the accumulators stored as they are, or added into C (ARG_ACCUMULATE); g.C holds
                                // the float pointer, g.ldc counts fp32 elements
+constexpr int EPI_C16_BIAS = 5;  // bf16 C with a fused bias (family f, bgemm_mi355x_tn_bias): C = bf16(acc + float(bias[n])), the bias added
+                                 // last and the sum rounded once; g.counters holds the bias pointer (hgemm_kernel_tn.hpp)
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

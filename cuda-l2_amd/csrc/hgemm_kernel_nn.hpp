@@ -289,25 +289,30 @@ HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNNB, false)   // hgemm_inst_g8.hip
 // geometry table of hgemm_configs*.def does not know these families).  A row is the member's geometry and its launcher in every kernel
 // set of the layout; TrKernels is what a set has besides: the combine of the two-pass form and the reference kernel (status 0, exact:
 // answers whatever is outside the kernels' scope or reach).  All sets share the signatures; a set with a 16-bit C is handed
-// accumulate = false and ignores it.  A set the layout does not have (NN with an fp32 C) is empty: null launchers, TrKernels{}.
+// accumulate = false and ignores it.  A set the layout does not have (NN with an fp32 C, NN / TA with a fused bias) is empty: null
+// launchers, TrKernels{}.
 struct TrEntry {
   const char* name;
   int bm, bn, wm, wn, nbuf, threads, lds_bytes;
 };
 enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C hold: 2 bytes either way
+// The output kinds of a layout: a 16-bit C, an fp32 C (family a), a 16-bit C with a fused bias (family f: bgemm_mi355x_tn_bias).
+enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_KINDS = 3 };
 struct TrRow {
   TrEntry e;
-  TrLaunch launch[2][2];   // [TrElem][fp32 C]
+  TrLaunch launch[2][TR_KINDS];   // [TrElem][TrKind]
 };
+// `bias`: the bf16 bias vector of the TR_C16_BIAS set (N elements, added last in fp32, the sum rounded once); every other set is handed
+// nullptr and ignores it.
 struct TrKernels {
-  void (*combine)(const float* partial, void* c, int M, int N, int ldc, int splits, bool accumulate, hipStream_t, TimingSlot);
-  void (*reference)(const void* a, const void* b, void* c, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate, hipStream_t,
-                    TimingSlot);
+  void (*combine)(const float* partial, void* c, const void* bias, int M, int N, int ldc, int splits, bool accumulate, hipStream_t, TimingSlot);
+  void (*reference)(const void* a, const void* b, void* c, const void* bias, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
+                    hipStream_t, TimingSlot);
 };
 struct TrTable {
   const TrRow* rows;
   int count;
-  TrKernels kernels[2][2];   // [TrElem][fp32 C]
+  TrKernels kernels[2][TR_KINDS];   // [TrElem][TrKind]
 };
 const TrTable& tr_table_nn();
 const TrTable& tr_table_ta();

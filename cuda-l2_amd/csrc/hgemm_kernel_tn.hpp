@@ -42,7 +42,9 @@ struct CfgTNB : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
   static constexpr auto kernel() { return &hgemm_tn_bf16_kernel<CfgTNB, EPI>; }   // the family's entry point (launch_tr)
 };
 
-// GemmArgs as the kernel reads it: A = [M][lda], Bt = b_col_major ([N][ldb], ldb >= K its row stride); tail_tiles = 0, counters = nullptr.
+// GemmArgs as the kernel reads it: A = [M][lda], Bt = b_col_major ([N][ldb], ldb >= K its row stride); tail_tiles = 0, counters = nullptr
+// -- except EPI_C16_BIAS, where counters is the bias vector (const __bf16*, N elements, 16-byte aligned), reinterpreted below as the fp32-C
+// kernels reinterpret g.C.
 template <class CFG, int EPI>
 __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmArgs g) {
   prefetch_kernargs<sizeof(GemmArgs)>();
@@ -51,7 +53,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
   using elem = typename CFG::elem;   // __bf16
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB, "plain and two-pass slab epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || EPI == EPI_C16_BIAS, "plain, two-pass slab and fused-bias epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -142,6 +144,33 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
     wr = (wr + 1 == NBUF) ? 0 : wr + 1;
   }
 
+  // ---- fused bias (EPI_C16_BIAS, bgemm_mi355x_tn_bias): C = bf16(acc + float(bias[n])), added LAST and rounded ONCE ----------------------
+  // g.counters is the bf16 bias vector of N elements (the host puts it there for this epilogue alone: GemmArgs keeps its layout), read
+  // through a descriptor that ENDS at N * 2 bytes.  tr_mfma(bf, af, acc) leaves lane (row = lane & 15, q = lane >> 4) with
+  // acc[i][j][e] = C[16 i + row][16 j + 4 q + e]: the operands are swapped, the MFMA's lane owns 4 consecutive N of a C row.  So the lane
+  // adds bias[n_b + e], n_b = n0 + wave_n TN + 16 j + 4 q, one 8-byte load per column tile; N % 8 == 0, so a group of 4 is inside N or
+  // wholly behind it, where the load returns zeros and the values are never stored.  The add stands in front of the convert and the
+  // swap of the shared epilogue, which moves finished bf16 values only.
+  // The loads are issued HERE, behind the K loop: the loop keeps the EPI_C16 kernel's registers and its counted vmcnt; the price is
+  // one L2 round trip per tile in front of the stores.
+  if constexpr (EPI == EPI_C16_BIAS) {
+    using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+    using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+    const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc((void*)g.counters, 0, (uint32_t)g.N * 2u, 0x00020000);
+    bx4 bias[FN];
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      const int n_b = tc.n0 + wave_n * CFG::TN + 16 * j + 4 * (lane >> 4);
+      bias[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsBias, (uint32_t)n_b * 2u, 0, 0));
+    }
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][j][e] += (float)bias[j][e];
+  }
+
   if constexpr (EPI == EPI_SLAB) {
     store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
   } else {
@@ -150,7 +179,20 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
-// ---- host side: hgemm_kernel_nn.hpp's (tr_table_tn is declared there); the family's one kernel set -------------------------------------
+// ---- host side: hgemm_kernel_nn.hpp's (tr_table_tn is declared there); the family's kernel sets ----------------------------------------
 HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgTNB, false)   // hgemm_inst_g11.hip
+
+// The fused-bias set (bgemm_mi355x_tn_bias): the member's EPI_C16_BIAS kernel alone.  The K slices of its two-pass form are the 16-bit
+// set's EPI_SLAB kernels, reached through that set's launcher in its own unit (as launch_tr's fp32-C set reaches them): no slab kernel is
+// instantiated twice.  TrLaunch's signature; g.counters of an EPI_C16_BIAS dispatch is the bias pointer (tr_launch, hgemm_api.hip).
+template <class CFG>
+void launch_tn_bias(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_BIAS>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_TN_BIAS_LAUNCHER(CFG, BM, BN, WM, WN, NB) launch_tn_bias<CFG<BM, BN, WM, WN, NB>>
+#define HGEMM_TN_BIAS_INST(...) template void HGEMM_TN_BIAS_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TN_BIAS_EXTERN(...) extern HGEMM_TN_BIAS_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_TN_BIAS_EXTERN, CfgTNB)     // hgemm_inst_g12.hip
 
 }  // namespace hgemm_mi355x

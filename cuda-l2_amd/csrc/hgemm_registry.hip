@@ -238,6 +238,52 @@ __global__ void __launch_bounds__(256) hgemm_generic_c32_kernel(const T* __restr
   }
 }
 
+// The combine of the fused-bias calls (bgemm_mi355x_tn_bias): s = p[0] + p[1] + ... + p[S-1] in split order, as hgemm_splitk_reduce_kernel
+// adds them, THEN s + float(bias[n]) as one fp32 add, then the one rounding to bf16 (nearest even).  The bias is not added into a slab.
+// A kernel of its own: hgemm_splitk_reduce_kernel keeps its symbols and streams.  (N % 8 == 0 and a 16-byte aligned bias on this path, so
+// the four bias values of a quad are one aligned 8-byte load inside the vector.)
+__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bias_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
+                                                                       const __bf16* __restrict__ bias, int M, int N, int ldc, int splits) {
+  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+  const size_t total4 = ((size_t)M * N) >> 2;
+  const size_t slab   = (size_t)M * N;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = q << 2;
+    const int m = (int)(e / N), n = (int)(e % N);
+    const bx4 b = *(const bx4*)(bias + n);   // in flight with the slab loads
+    f32x4 s = *(const f32x4*)(partial + e);
+    int k = 1;
+    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
+      f32x4 p[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += p[u];
+    }
+    for (; k < splits; ++k) {
+      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
+      s += p;
+    }
+    const bx4 o = {(__bf16)(s[0] + (float)b[0]), (__bf16)(s[1] + (float)b[1]), (__bf16)(s[2] + (float)b[2]), (__bf16)(s[3] + (float)b[3])};
+    *(bx4*)(C + (size_t)m * ldc + n) = o;
+  }
+}
+
+// The reference kernel of the fused-bias calls: hgemm_generic_tn_kernel's one output per thread and its fma chain in k order, then the
+// fp32 add of float(bias[n]) to the finished sum, then the one rounding.  Any shape, stride and alignment (bias 2-byte aligned).
+__global__ void __launch_bounds__(256) hgemm_generic_tn_bias_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bcol,
+                                                                    __bf16* __restrict__ C, const __bf16* __restrict__ bias, int M, int N,
+                                                                    int K, int lda, int ldb_colmajor, int ldc) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  const float b = (float)bias[n];
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
+    C[(size_t)m * ldc + n] = (__bf16)(s + b);
+  }
+}
+
 // ---- launchers of the combines and the reference kernels, with the signatures of TrKernels (hgemm_kernel_nn.hpp) ----------------------
 // grid and block of a combine: a thread per four outputs
 struct CombineGrid { int grid, threads; };
@@ -252,21 +298,21 @@ static CombineGrid combine_grid(int M, int N) {
 }
 
 template <class T>
-static void launch_combine(const float* partial, void* C, int M, int N, int ldc, int splits, bool, hipStream_t stream, TimingSlot ts) {
+static void launch_combine(const float* partial, void* C, const void*, int M, int N, int ldc, int splits, bool, hipStream_t stream, TimingSlot ts) {
   const CombineGrid cg = combine_grid(M, N);
   HGEMM_LAUNCH((hgemm_splitk_reduce_kernel<T>), cg.grid, cg.threads, stream, ts, partial, (T*)C, M, N, ldc, splits);
 }
 
 // ldc in fp32 elements; accumulate: C32 += the sum, otherwise C32 is never read
-static void launch_combine_c32(const float* partial, void* C32, int M, int N, int ldc, int splits, bool accumulate, hipStream_t stream,
-                               TimingSlot ts) {
+static void launch_combine_c32(const float* partial, void* C32, const void*, int M, int N, int ldc, int splits, bool accumulate,
+                               hipStream_t stream, TimingSlot ts) {
   const CombineGrid cg = combine_grid(M, N);
   HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, cg.grid, cg.threads, stream, ts, partial, (float*)C32, M, N, ldc, splits, accumulate ? 1 : 0);
 }
 
 template <class T, bool A_COL, bool C32>
-static void launch_reference(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
-                             hipStream_t stream, TimingSlot ts) {
+static void launch_reference(const void* A, const void* B, void* C, const void*, int M, int N, int K, int lda, int ldb, int ldc,
+                             bool accumulate, hipStream_t stream, TimingSlot ts) {
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
   if constexpr (C32)
     HGEMM_LAUNCH((hgemm_generic_c32_kernel<T, A_COL>), grid, 256, stream, ts, (const T*)A, (const T*)B, (float*)C, M, N, K, lda, ldb, ldc,
@@ -276,26 +322,41 @@ static void launch_reference(const void* A, const void* B, void* C, int M, int N
 }
 
 template <class T>
-static void launch_reference_tn(const void* A, const void* Bcol, void* C, int M, int N, int K, int lda, int ldb, int ldc, bool, hipStream_t stream,
-                                TimingSlot ts) {
+static void launch_reference_tn(const void* A, const void* Bcol, void* C, const void*, int M, int N, int K, int lda, int ldb, int ldc, bool,
+                                hipStream_t stream, TimingSlot ts) {
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
   HGEMM_LAUNCH((hgemm_generic_tn_kernel<T>), grid, 256, stream, ts, (const T*)A, (const T*)Bcol, (T*)C, M, N, K, lda, ldb, ldc);
+}
+
+// the fused-bias set's two (bgemm_mi355x_tn_bias): `bias` is the bf16 vector of N elements
+static void launch_combine_bias(const float* partial, void* C, const void* bias, int M, int N, int ldc, int splits, bool, hipStream_t stream,
+                                TimingSlot ts) {
+  const CombineGrid cg = combine_grid(M, N);
+  HGEMM_LAUNCH(hgemm_splitk_reduce_bias_kernel, cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)bias, M, N, ldc, splits);
+}
+
+static void launch_reference_tn_bias(const void* A, const void* Bcol, void* C, const void* bias, int M, int N, int K, int lda, int ldb, int ldc,
+                                     bool, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH(hgemm_generic_tn_bias_kernel, grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)Bcol, (__bf16*)C, (const __bf16*)bias, M, N,
+               K, lda, ldb, ldc);
 }
 
 // the b_col_major families' names for their two (hgemm_launch.hpp)
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
-  launch_combine<f16>(partial, C, M, N, ldc, splits, false, stream, ts);
+  launch_combine<f16>(partial, C, nullptr, M, N, ldc, splits, false, stream, ts);
 }
 
 void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int lda, int ldb,
                     int ldc, hipStream_t stream, TimingSlot ts) {
-  launch_reference<f16, false, false>(A, B, C, M, N, K, lda, ldb, ldc, false, stream, ts);
+  launch_reference<f16, false, false>(A, B, C, nullptr, M, N, K, lda, ldb, ldc, false, stream, ts);
 }
 
 // ---- the tables of the three layouts of the transposed-read host path (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the member list: a
-// row is the member's geometry and its launcher in every kernel set of the layout, [TrElem][fp32 C]; `kernels` names the same sets'
-// combine and reference kernel.  A new kernel set is one more cell in the layout's row macro and in its `kernels`.
+// row is the member's geometry and its launcher in every kernel set of the layout, [TrElem][TrKind]; `kernels` names the same sets'
+// combine and reference kernel.  A new kernel set is one more cell in the layout's row macro and in its `kernels`; a cell left out is
+// empty (null launcher, TrKernels{}) and a call for it is refused -- the fused-bias kind of NN and TA.
 // (Inside functions, which both passes read: the device pass instantiates a combine or a reference kernel where it sees its launcher
 // named, and a table of host function pointers at namespace scope would be emitted as a device constant.)
 #define HGEMM_NN_ROW(P, ...)                                                                                \
@@ -304,9 +365,11 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
 #define HGEMM_TA_ROW(P, ...)                                                                                                                 \
   {HGEMM_TR_ENTRY(P, CfgTA, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgTA, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTA, true, __VA_ARGS__)},    \
                                            {&HGEMM_TR_LAUNCHER(CfgTAB, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTAB, true, __VA_ARGS__)}}},
-// TN (family f, hgemm_kernel_tn.hpp): the bf16 set with a 16-bit C alone; every other cell is empty and a call for it is refused
-#define HGEMM_TN_ROW(P, ...) \
-  {HGEMM_TR_ENTRY(P, CfgTNB, __VA_ARGS__), {{nullptr, nullptr}, {&HGEMM_TR_LAUNCHER(CfgTNB, false, __VA_ARGS__), nullptr}}},
+// TN (family f, hgemm_kernel_tn.hpp): the bf16 sets with a 16-bit C, plain and with the fused bias; every other cell is empty and a call
+// for it is refused
+#define HGEMM_TN_ROW(P, ...)                                                                                        \
+  {HGEMM_TR_ENTRY(P, CfgTNB, __VA_ARGS__), {{nullptr, nullptr}, {&HGEMM_TR_LAUNCHER(CfgTNB, false, __VA_ARGS__), nullptr, \
+                                                                 &HGEMM_TN_BIAS_LAUNCHER(CfgTNB, __VA_ARGS__)}}},
 const TrTable& tr_table_nn() {
   static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_NN_ROW, "n")};
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
@@ -325,7 +388,7 @@ const TrTable& tr_table_ta() {
 const TrTable& tr_table_tn() {
   static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TN_ROW, "f")};
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
-                            {{{}, {}}, {{launch_combine<__bf16>, launch_reference_tn<__bf16>}, {}}}};
+                            {{{}, {}}, {{launch_combine<__bf16>, launch_reference_tn<__bf16>}, {}, {launch_combine_bias, launch_reference_tn_bias}}}};
   return t;
 }
 

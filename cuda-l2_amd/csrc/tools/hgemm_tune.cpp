@@ -33,6 +33,8 @@
 //                                                     round-to-round spread (its slowest round minus its median)
 //   hgemm_tune check --layout tn --bf16 [--shapes ...] the bf16 forward product (bgemm_mi355x_launch_tn, family f: B given as b_col_major)
 //   hgemm_tune bench --layout tn --bf16 --shapes ... [--out F.jsonl]
+//   hgemm_tune check --layout tn --bf16 --bias [--shapes ...]   the fused-bias calls (bgemm_mi355x_launch_tn_bias): bf16(S + bias[n])
+//   hgemm_tune bench --layout tn --bf16 --bias --shapes ... [--out F.jsonl]   against the same plan without a bias, "bias_le_plain"
 //                                                     that check first, then per shape interleaved rounds of the planned call, of
 //                                                     bgemm_mi355x_launch_nn with the same member and splits, and -- context -- rocBLAS
 //   hgemm_tune bench --layout nn --shapes ... [--autotune] [--out F.jsonl]
@@ -1086,10 +1088,16 @@ static const TrLayout kLayoutTN = {"tn", "the TN kernels",
                                    nullptr, nullptr, bgemm_mi355x_tn_runs, bgemm_mi355x_launch_tn, bgemm_mi355x_tn,
                                    bgemm_rocblas_tn, true};
 
+// --bias (with --layout tn --bf16): the fused-bias calls, bgemm_mi355x_launch_tn_bias / bgemm_mi355x_tn_bias.  The check's bias is
+// bias[n] = ((n mod 255) - 127) / 2: bf16 values, and with the integer sums S <= K exact in fp32, so the expected C is bf16(S + bias[n]),
+// rounded once.
+static bool g_bias = false;
+static float check_bias(int n) { return (float)((n % 255) - 127) * 0.5f; }
+
 static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
   if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
   int failures = 0, runs = 0;
-  const std::string lay_s = std::string(L.label) + (g_bf16 ? "-bf16" : "");
+  const std::string lay_s = std::string(L.label) + (g_bf16 ? "-bf16" : "") + (g_bias ? "-bias" : "");
   const char* lay = lay_s.c_str();
   const int nc = L.num_configs();
   for (const Shape& sh : shapes) {
@@ -1102,7 +1110,8 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
         int acc = 0;
         for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
         const f16 t16 = (f16)(float)acc;
-        if (g_bf16) truth[(size_t)m * sh.N + n] = bf16_rne((float)acc);
+        if (g_bias) truth[(size_t)m * sh.N + n] = bf16_rne((float)acc + check_bias(n));
+        else if (g_bf16) truth[(size_t)m * sh.N + n] = bf16_rne((float)acc);
         else memcpy(&truth[(size_t)m * sh.N + n], &t16, 2);
       }
     for (int n = 0; n < sh.N; ++n)
@@ -1111,6 +1120,13 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
     HIP_OK(hipMalloc(&s.a, z.a.size() * 2));
     HIP_OK(hipMalloc(&s.b, b_rm.size() * 2));
     HIP_OK(hipMalloc(&s.c, cn * 2));
+    void* d_bias = nullptr;
+    if (g_bias) {
+      std::vector<uint16_t> hb(sh.N);
+      for (int n = 0; n < sh.N; ++n) hb[n] = bf16_rne(check_bias(n));
+      HIP_OK(hipMalloc(&d_bias, hb.size() * 2));
+      HIP_OK(hipMemcpy(d_bias, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+    }
     if (L.a_col_major) {   // a_col_major[k][m] = a[m][k]
       std::vector<f16> a_cm(z.a.size());
       for (int m = 0; m < sh.M; ++m)
@@ -1125,7 +1141,8 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
       const int own = (g_bf16 ? L.runs_bf16 : L.runs)(c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
         HIP_OK(hipMemset(s.c, 0xff, cn * 2));  // NaN pattern: unwritten outputs are caught
-        const int st = (g_bf16 ? L.launch_bf16 : L.launch)(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, nullptr);
+        const int st = g_bias ? bgemm_mi355x_launch_tn_bias(c, splits, s.a, s.b, d_bias, s.c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, nullptr)
+                              : (g_bf16 ? L.launch_bf16 : L.launch)(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, nullptr);
         const hipError_t e = hipDeviceSynchronize();
         ++runs;
         if (st != HGEMM_OK || e != hipSuccess) {
@@ -1150,13 +1167,14 @@ static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
       if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
     }
     free_set(s);
+    if (d_bias) HIP_OK(hipFree(d_bias));
     fflush(stdout);
   }
   printf("check-%s-configs:", lay);
   for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
   printf("\ncheck-%s-forms: 1 1|nt-store 2 5\n", lay);
   printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs%s)\n", lay, runs, failures,
-         g_bf16 ? ", rounded to bf16 once" : "");
+         g_bias ? " plus the bias, rounded to bf16 once" : g_bf16 ? ", rounded to bf16 once" : "");
   return failures ? 1 : 0;
 }
 
@@ -1544,6 +1562,80 @@ static int cmd_bench_tn_bf16(const std::vector<Shape>& shapes, const char* out_p
   return 0;
 }
 
+__global__ void fill_bias_kernel(__bf16* __restrict__ bias, int n) {   // N(0,1)-sized values, a fixed pattern: timing only
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) bias[i] = (__bf16)((float)((i * 37) % 129 - 64) * (1.0f / 32.0f));
+}
+__global__ void add_bias_kernel(__bf16* __restrict__ c, const __bf16* __restrict__ bias, size_t total, int n) {   // the unfused second pass
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    c[i] = (__bf16)((float)c[i] + (float)bias[i % n]);
+}
+
+// bench --layout tn --bf16 --bias: the bias check first, then per shape ONE set of interleaved rounds of the planned bgemm_mi355x_tn_bias
+// call, of bgemm_mi355x_launch_tn with the same member and splits and no bias -- the fused kernel adds 2 BN bytes of loads and 4 FM FN
+// adds per lane to a tile --, and, context only, the path the call replaces: bgemm_mi355x_tn followed by an element-wise bf16 add.  The
+// one condition: fused <= plain within the plain call's own round-to-round spread in this run (its slowest round minus its median):
+// "bias_le_plain".
+static int cmd_bench_tn_bias(const std::vector<Shape>& shapes, const char* out_path) {
+  const TrLayout& L = kLayoutTN;
+  int rc = cmd_check_nn(L, {});
+  if (rc != 0) { fprintf(stderr, "bench --layout tn --bf16 --bias: the check failed, nothing is timed\n"); return rc; }
+  FILE* out = out_path ? fopen(out_path, "w") : stdout;
+  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0));
+  HIP_OK(hipEventCreate(&e1));
+  for (const Shape& sh : shapes) {
+    const size_t a_elems = (size_t)sh.M * sh.K, b_elems = (size_t)sh.K * sh.N, cn = (size_t)sh.M * sh.N;
+    std::vector<Buffers> sets(2);
+    std::vector<__bf16*> ab(sets.size(), nullptr), btb(sets.size(), nullptr), cb(sets.size(), nullptr), bias(sets.size(), nullptr);
+    for (size_t i = 0; i < sets.size(); ++i) {
+      alloc_set(sets[i], sh, 91 + i, true);   // a [M][K] and bt = b_col_major [N][K]
+      HIP_OK(hipMalloc(&ab[i], a_elems * 2));
+      HIP_OK(hipMalloc(&btb[i], b_elems * 2));
+      HIP_OK(hipMalloc(&cb[i], cn * 2));
+      HIP_OK(hipMalloc(&bias[i], (size_t)sh.N * 2));
+      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].a, ab[i], a_elems);
+      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].bt, btb[i], b_elems);
+      fill_bias_kernel<<<64, 256>>>(bias[i], sh.N);
+    }
+    HIP_OK(hipDeviceSynchronize());
+    int cfg = 0, splits = 1;
+    L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
+    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
+    const int add_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+    std::vector<Contender> cs;
+    cs.push_back({"bias", [&](Buffers& b) { return bgemm_mi355x_tn_bias(ab[idx(b)], btb[idx(b)], bias[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
+    cs.push_back({"plain", [&](Buffers& b) { return bgemm_mi355x_launch_tn(cfg, splits, ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, sh.K, sh.K, sh.N, nullptr); }});
+    cs.push_back({"unfused", [&](Buffers& b) {
+                    const int st = bgemm_mi355x_tn(ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr);
+                    add_bias_kernel<<<add_grid, 256>>>(cb[idx(b)], bias[idx(b)], cn, sh.N);
+                    return st;
+                  }});
+    const int rounds = 15;
+    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
+    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
+    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"tn\", \"output\": \"c16_bias\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, "
+                 "\"runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, L.config_name(cfg), splits,
+            bgemm_mi355x_tn_bias_runs(cfg, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N), rounds);
+    for (const Contender& c : cs) {
+      const double us = c.iso_us();
+      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
+    }
+    const double f_us = cs[0].iso_us(), p_us = cs[1].iso_us();
+    const double spread = cs[1].ok && !cs[1].iso.empty() ? *std::max_element(cs[1].iso.begin(), cs[1].iso.end()) - p_us : -1.0;
+    fprintf(out, ", \"plain_spread_us\": %.3f, \"bias_le_plain\": %s}\n", spread, f_us > 0 && p_us > 0 && f_us <= p_us + spread ? "true" : "false");
+    fflush(out);
+    for (size_t i = 0; i < sets.size(); ++i) {
+      free_set(sets[i]);
+      HIP_OK(hipFree(ab[i])); HIP_OK(hipFree(btb[i])); HIP_OK(hipFree(cb[i])); HIP_OK(hipFree(bias[i]));
+    }
+  }
+  HIP_OK(hipEventDestroy(e0));
+  HIP_OK(hipEventDestroy(e1));
+  if (out != stdout) fclose(out);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1570,6 +1662,7 @@ int main(int argc, char** argv) {
     }
     else if (a == "--c32") c32 = true;
     else if (a == "--bf16") g_bf16 = true;
+    else if (a == "--bias") g_bias = true;
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
     else if (a == "--streamk") g_streamk_too = true;
@@ -1624,6 +1717,7 @@ int main(int argc, char** argv) {
     HIP_OK(hipMalloc(&pad, g_pad_alloc_mib << 20));   // (kept until exit)
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
   }
+  if (g_bias && !(g_bf16 && layout_tn)) { fprintf(stderr, "--bias goes with --layout tn --bf16 (bgemm_mi355x_tn_bias)\n"); return 2; }
   if (layout_ta) {   // family a: A given as [K][M] (hgemm_mi355x_launch_ta)
     if (mode == "check") return c32 ? cmd_check_ta_c32(shapes) : cmd_check_nn(kLayoutTA, shapes);
     if (mode == "bench") {
@@ -1649,7 +1743,7 @@ int main(int argc, char** argv) {
     if (mode == "check") return cmd_check_nn(kLayoutTN, shapes);
     if (mode == "bench") {
       if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
-      return cmd_bench_tn_bf16(shapes, out_path);
+      return g_bias ? cmd_bench_tn_bias(shapes, out_path) : cmd_bench_tn_bf16(shapes, out_path);
     }
     fprintf(stderr, "--layout tn --bf16 goes with check or bench\n");
     return 2;

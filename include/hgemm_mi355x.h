@@ -418,6 +418,30 @@ int bgemm_mi355x_tn_plan(int M, int N, int K, int* tn_config, int* splits);
 size_t bgemm_mi355x_tn_plan_workspace_bytes(int tn_config, int splits, int M, int N, int K);
 int bgemm_mi355x_tn_reserve_workspace(int M, int N, int K, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Forward product with a fused bias: Y = X x W^T + b, a linear layer's whole forward in one call.  Operands, layout, strides and scope
+ * are bgemm_mi355x_tn's; `bias` is a bfloat16 device vector of N contiguous elements, read-only, owned by the caller like a and
+ * b_col_major (it must stay valid until the call has run on `stream`).
+ * Replaces bgemm_mi355x_tn followed by an element-wise add -- a second pass that reads and writes all of Y again (4 M N bytes for a
+ * 2 N byte vector) and rounds to bf16 a second time -- or a vendor GEMM with a bias epilogue (hipblasLt's HIPBLASLT_EPILOGUE_BIAS).
+ * Semantics, exactly:  C[m][n] = bf16( fl32( S[m][n] + float(bias[n]) ) ).
+ *   - S is the finished fp32 sum of the product: the accumulator behind the K walk of a plain launch, or the slabs of a two-pass plan
+ *     added in split order.
+ *   - The bias is added last, as ONE fp32 add to the finished sum: it is not the accumulators' initial value and it is not added into
+ *     a slab.
+ *   - The result is rounded once, to nearest even.
+ * No activation and no fp16 form.  bias == NULL: HGEMM_ERR_BAD_ARG (a caller without a bias has bgemm_mi355x_tn).
+ * The kernels (family f's fused-bias epilogue) also want `bias` 16-byte aligned; any other call is answered by the reference kernel
+ * (HGEMM_OK, exact, slow).  The table, ids, names, plan, workspace size and reserve call are bgemm_mi355x_tn_*'s -- the tiles, cuts and
+ * slabs of a bias call are those of the bgemm_mi355x_launch_tn call with the same arguments -- and so are the splits word, the statuses
+ * and the capture behaviour. */
+/* planned, contiguous (lda = ldb = K, ldc = N) */
+int bgemm_mi355x_tn_bias(const void* a, const void* b_col_major, const void* bias, void* c, int M, int N, int K, void* stream);
+int bgemm_mi355x_launch_tn_bias(int tn_config, int splits, const void* a, const void* b_col_major, const void* bias, void* c,
+                                int M, int N, int K, int lda, int ldb, int ldc, void* stream);
+/* 1 when the call (with an aligned bias) runs one of the family's kernels: equal to bgemm_mi355x_tn_runs */
+int bgemm_mi355x_tn_bias_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc);
+
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
 const char* hgemm_mi355x_version(void);
