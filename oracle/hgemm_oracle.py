@@ -14,6 +14,7 @@ Restated rules (reference file:line):
   -max row              summarize_result.py:43-53             lower cuda_l2 speedup of tn/nn
 Parity pinning: see hgemm_oracle.c header and tests/golden/make_golden.py.
 Of this project, not restated: dyadic_inputs / truth_exact and the three wrong-rounding mutants (the rounding tests).
+Likewise bf16_dyadic_inputs / bf16_exact_product and their mutants (the bf16 rounding bars of tests/test_gpu_tn_bars.py).
 """
 from __future__ import annotations
 
@@ -201,6 +202,80 @@ def fp16_partials(a: np.ndarray, b: np.ndarray, cuts) -> np.ndarray:
     for lo, hi in zip(edges, edges[1:]):
         acc += truth_exact(a[:, lo:hi], b[lo:hi]).astype(np.float32)
     return acc.astype(np.float16)
+
+
+# ---- order-exact bfloat16 operands with live mantissa bits (the bf16 rounding bars: tests/test_gpu_tn_bars.py) ------------------
+# numpy has no bfloat16: a bf16 operand is an fp32 array whose low 16 bits are clear, a bf16 result a uint16 array of bit patterns.
+BF16_DYADIC_GRANULARITY = {"A": 2.0 ** -7, "B": 2.0 ** -7, "AB": 2.0 ** -14}
+
+
+def bf16_dyadic_inputs(m: int, n: int, k: int, rng: np.random.Generator, side: str):
+    """dyadic_inputs for bfloat16, whose significand has 7 stored bits: the two lowest of them live in B ("B"), in A ("A") or in both
+    ("AB").  "B": A in {-1, 0, 1}, B = z x (1 + e x 2^-7), z in {0, 1}, e in 0 .. 3.  "A": the mirror, A = s x (1 + f x 2^-7) with
+    the signs kept in A, B in {0, 1}.  "AB": A = s x (1 + f x 2^-7), B = z x (1 + e x 2^-7), products multiples of 2^-14.  All draws
+    uniform.  The sums are exact in fp32 in any order and grouping while sum |a| |b| stays below 2^23 granules: assert_bf16_dyadic
+    asserts that on the operands it is given; no K is promised here.  Returns fp32 arrays of bf16 values."""
+    assert side in BF16_DYADIC_GRANULARITY, side
+    s = rng.integers(-1, 2, size=(m, k)).astype(np.float64)
+    f = rng.integers(0, 4, size=(m, k)) if side in ("A", "AB") else 0
+    z = rng.integers(0, 2, size=(k, n)).astype(np.float64)
+    e = rng.integers(0, 4, size=(k, n)) if side in ("B", "AB") else 0
+    a = (s * (128 + f) / 128.0).astype(np.float32)
+    b = (z * (128 + e) / 128.0).astype(np.float32)
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def is_bf16(x: np.ndarray) -> bool:
+    return x.dtype == np.float32 and not (np.ascontiguousarray(x).view(np.uint32) & 0xFFFF).any()
+
+
+def bf16_dyadic_bits(a: np.ndarray, b: np.ndarray, side: str) -> float:
+    """log2 of the largest sum |a| |b| of an element of C, in granules of the class: the significant bits its partial sums may need."""
+    return float(np.log2((np.abs(a.astype(np.float64)) @ np.abs(b.astype(np.float64))).max() / BF16_DYADIC_GRANULARITY[side]))
+
+
+def assert_bf16_dyadic(a: np.ndarray, b: np.ndarray, side: str) -> None:
+    """The class of bf16_dyadic_inputs and the exactness rule DYADIC_MAX_K rests on, asserted on the actual operands: every product is a
+    whole number of granules, so every partial sum of every order is one, of magnitude <= sum |a| |b| < 2^23 granules: 23 significant bits."""
+    assert is_bf16(a) and is_bf16(b) and a.shape[1] == b.shape[0], "operands must be fp32 arrays of bf16 values"
+    a128, b128 = np.abs(a.astype(np.float64)) * 128.0, b.astype(np.float64) * 128.0
+    top_a, top_b = (131 if side in ("A", "AB") else 128), (131 if side in ("B", "AB") else 128)
+    assert (a128 == np.floor(a128)).all() and ((a128 == 0) | ((a128 >= 128) & (a128 <= top_a))).all(), f"class {side}: A must hold 0 or +-(1 + f / 128), f <= {top_a - 128}"
+    assert (b128 == np.floor(b128)).all() and ((b128 == 0) | ((b128 >= 128) & (b128 <= top_b))).all(), f"class {side}: B must hold 0 or 1 + e / 128, e <= {top_b - 128}"
+    worst = (np.abs(a.astype(np.float64)) @ np.abs(b.astype(np.float64))).max() / BF16_DYADIC_GRANULARITY[side]
+    assert worst < 2.0 ** 23, f"class {side}, K = {a.shape[1]}: a partial sum may need {np.log2(worst):.1f} > 23 significant bits"
+
+
+def bf16_exact_product(a: np.ndarray, b: np.ndarray, side: str) -> np.ndarray:
+    """The exact product as fp32 (the fp64 BLAS product of 23-bit sums is exact in any order; the cast is asserted exact)."""
+    assert_bf16_dyadic(a, b, side)
+    x = a.astype(np.float64) @ b.astype(np.float64)
+    x32 = x.astype(np.float32)
+    assert np.array_equal(x32.astype(np.float64), x), "the exact product is no fp32 matrix"
+    return x32
+
+
+def bf16_roundings(x32: np.ndarray):
+    """An fp32 matrix (finite, inside the bf16 range) as bf16 bit patterns under three roundings: (nearest even, truncation, nearest
+    with ties away from zero).  The first is the right one; the other two are MUTANTS."""
+    u = np.ascontiguousarray(x32, dtype=np.float32).view(np.uint32)
+    keep = u >> 16
+    return ((u + 0x7FFF + (keep & 1)) >> 16).astype(np.uint16), keep.astype(np.uint16), ((u + 0x8000) >> 16).astype(np.uint16)
+
+
+def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
+    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def bf16_partials(a: np.ndarray, b: np.ndarray, side: str, cuts, bias=None) -> np.ndarray:
+    """MUTANT: a split-K whose slabs are held in bf16 -- the exact sum of every K chunk rounded to bf16, the chunks added in fp32 in
+    split order, the bias (if any) added last, the total rounded once more.  Bit patterns."""
+    edges = [0] + [int(c) for c in cuts] + [a.shape[1]]
+    assert all(lo < hi for lo, hi in zip(edges, edges[1:])), edges
+    acc = np.zeros((a.shape[0], b.shape[1]), dtype=np.float32)
+    for lo, hi in zip(edges, edges[1:]):
+        acc += bf16_to_f32(bf16_roundings(bf16_exact_product(a[:, lo:hi], b[lo:hi], side))[0])
+    return bf16_roundings(acc if bias is None else acc + bias[None, :].astype(np.float32))[0]
 
 
 def masked_max_diff(out: np.ndarray, truth: np.ndarray) -> float:

@@ -10,6 +10,8 @@ ones.  S + b then needs at most 12 + 8 = 20 significand bits: exact in fp32, so 
 CPU.  Before any launch the module shows on the CPU that this matrix holds ties to both sides and plain round-ups and differs from what
 each mistake would give: the bias added after the bf16 rounding, added into every slab, taken from the neighbouring column tile.  The bias
 as the accumulators' initial value gives the same bits on integers (every order is exact); the scaled case below tells it apart.
+On integers the twice-rounded bias cannot show at K = 64 (TWICE_ROUNDED_FLOOR[(64, 64, 64)] == 0: every |S| <= 256 is a bf16 value); that
+blind spot is covered by tests/test_gpu_tn_bars.py, whose operands have live mantissa bits (152 elements differ at (64, 64, 64) there).
 
 C lies in [M + 1][ldc] with a sentinel in the pad and the guard row, NaN sits in the operands' padding, the bias vector is followed by a NaN
 guard element, and operands and bias must be bit-unchanged afterwards."""
