@@ -49,7 +49,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1021,547 +1023,251 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
   return 0;
 }
 
-// ---- NN layout (family n, hgemm_kernel_nn.hpp): `check --layout nn`, `bench --layout nn` ------------------------------------------------
-// check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} bit-exact on 0/1 inputs with B ROW-MAJOR; the default
-// shapes hold one tile, ragged M / N, an 8-column sliver, 1 .. 7 K stages, a long K -- and three the kernel does not take
-// (K % 64, N % 8: the reference kernel answers).
-// kLayoutTA: the same check of family a (hgemm_kernel_ta.hpp) -- A handed over as a_col_major [K][M], lda = M; the default shapes add
-// M % 8 != 0 to what the kernel does not take and an 8-row sliver to what it does.
-// One record per transposed-read layout: the family's C ABI, how A is handed over, the words of its output.
-// --bf16: the record's bfloat16 entry points; operands are converted on the host (0 and 1 are bf16 values), the expected 16-bit C is the
-// integer sum rounded to bf16 once.
-static bool g_bf16 = false;
+// ---- The transposed-read variants: `check --layout nn|ta|tn ...`, `bench --layout nn|ta|tn ...` ------------------------------------------
+// Eight variants -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias --, each one record (kVariants)
+// that main resolves once; ONE check (tr_check) and ONE bench driver (tr_bench) serve them all.
+// The check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} (fp32 C: x {store, accumulate}) bit-exact on 0/1 inputs.
+// The NN default shapes hold one tile, ragged M / N, an 8-column sliver, 1 .. 7 K stages, a long K -- and three the kernels do not take
+// (K % 64, N % 8: the reference kernel answers); the TA ones (A handed over as a_col_major [K][M], lda = M) add M % 8 != 0 to what the
+// kernels do not take and an 8-row sliver to what they do.  bf16: operands are converted on the host (0 and 1 are bf16 values), the
+// expected 16-bit C is the integer sum rounded to bf16 once.  fp32 C: exact against the host's integer result, the old C32 integers in
+// +-1000 (store mode starts from a NaN pattern instead).
 static uint16_t bf16_rne(float x) {   // round to nearest even (finite inputs)
   uint32_t u;
   memcpy(&u, &x, 4);
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
-// fp16 values as fp16 or -- --bf16 -- as bf16 bits, ready for upload
-static std::vector<uint16_t> operand_bits(const std::vector<f16>& v) {
+enum Elem { kF16, kBF16 };
+enum Out { kC16, kC32, kC16Bias };   // C as 16-bit elements, as fp32 (stored or accumulated), as bf16 with the fused bias
+// fp16 values as fp16 or as bf16 bits, ready for upload
+static std::vector<uint16_t> operand_bits(const std::vector<f16>& v, Elem elem) {
   std::vector<uint16_t> o(v.size());
   for (size_t i = 0; i < v.size(); ++i) {
-    if (g_bf16) o[i] = bf16_rne((float)v[i]);
+    if (elem == kBF16) o[i] = bf16_rne((float)v[i]);
     else memcpy(&o[i], &v[i], 2);
   }
   return o;
 }
 
+// What a layout's variants share: its words, how A and B are handed over (ldc = N always), its table.
 struct TrLayout {
-  const char* label;            // "nn" / "ta": --layout, the JSON field prefix, the check's lines
+  const char* label;            // "nn" / "ta" / "tn": --layout, the JSON "layout", the stem of the check's labels
   const char* kernels;
   const char* check_shapes;     // the check's default shapes
-  bool a_col_major;             // A handed over as [K][M] with lda = M (else [M][K], lda = K); ldb = ldc = N either way
+  bool a_col_major;             // A handed over as [K][M] with lda = M (else [M][K], lda = K)
+  bool b_col_major;             // B handed over as b_col_major [N][K] with ldb = K (else row-major [K][N], ldb = N)
   int (*num_configs)(void);
   const char* (*config_name)(int);
   int (*plan)(int, int, int, int*, int*);
-  int (*runs)(int, int, int, int, int, int, int);
-  int (*launch)(int, int, const void*, const void*, void*, int, int, int, int, int, int, void*);
-  int (*planned)(const void*, const void*, void*, int, int, int, void*);
-  // the bfloat16 twins (--bf16); table, names and plan are shared
-  int (*runs_bf16)(int, int, int, int, int, int, int);
-  int (*launch_bf16)(int, int, const void*, const void*, void*, int, int, int, int, int, int, void*);
-  int (*planned_bf16)(const void*, const void*, void*, int, int, int, void*);
-  int (*rocblas_bf16)(const void*, const void*, void*, int, int, int, void*);
-  bool b_col_major = false;     // B handed over as b_col_major [N][K] with ldb = K (else row-major [K][N], ldb = N)
+  int (*rocblas_bf16)(const void*, const void*, void*, int, int, int, void*);   // rocBLAS on this layout's operands, bf16 in and out
   int lda(const Shape& sh) const { return a_col_major ? sh.M : sh.K; }
   int ldb(const Shape& sh) const { return b_col_major ? sh.K : sh.N; }
 };
-static const TrLayout kLayoutNN = {"nn", "the NN kernels",
-                                   "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
-                                   "200_136_72,200_100_128,33_17_40",
-                                   false, hgemm_mi355x_nn_num_configs, hgemm_mi355x_nn_config_name, hgemm_mi355x_nn_plan, hgemm_mi355x_nn_runs,
-                                   hgemm_mi355x_launch_nn, hgemm_mi355x_nn_fp32, bgemm_mi355x_nn_runs, bgemm_mi355x_launch_nn, bgemm_mi355x_nn,
-                                   bgemm_rocblas_nn};
+static const char kShapesNN[] = "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
+                                "200_136_72,200_100_128,33_17_40";
+static const TrLayout kLayoutNN = {"nn", "the NN kernels", kShapesNN, false, false,
+                                   hgemm_mi355x_nn_num_configs, hgemm_mi355x_nn_config_name, hgemm_mi355x_nn_plan, bgemm_rocblas_nn};
 static const TrLayout kLayoutTA = {"ta", "the TA kernels",
                                    "64_64_64,8_8_64,72_72_128,200_264_192,136_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
-                                   "200_136_72,200_100_128,100_136_128,33_17_40",
-                                   true, hgemm_mi355x_ta_num_configs, hgemm_mi355x_ta_config_name, hgemm_mi355x_ta_plan, hgemm_mi355x_ta_runs,
-                                   hgemm_mi355x_launch_ta, hgemm_mi355x_ta_fp32, bgemm_mi355x_ta_runs, bgemm_mi355x_launch_ta, bgemm_mi355x_ta,
-                                   bgemm_rocblas_ta};
+                                   "200_136_72,200_100_128,100_136_128,33_17_40", true, false,
+                                   hgemm_mi355x_ta_num_configs, hgemm_mi355x_ta_config_name, hgemm_mi355x_ta_plan, bgemm_rocblas_ta};
+// the bf16 forward product (family f, hgemm_kernel_tn.hpp): a table of its own; M is free, K % 64 and N % 8 go to the reference kernel,
+// so the NN layout's shapes serve
+static const TrLayout kLayoutTN = {"tn", "the TN kernels", kShapesNN, false, true,
+                                   bgemm_mi355x_tn_num_configs, bgemm_mi355x_tn_config_name, bgemm_mi355x_tn_plan, bgemm_rocblas_tn};
 
-// the bf16 forward product (family f, hgemm_kernel_tn.hpp): bf16 entry points alone (--bf16 is required), a table of its own; the
-// default shapes are the NN layout's -- M is free, K % 64 and N % 8 go to the reference kernel
-static const TrLayout kLayoutTN = {"tn", "the TN kernels",
-                                   "64_64_64,1_8_64,65_72_128,200_264_192,130_8_64,96_136_256,96_136_320,96_136_448,512_1024_2048,64_64_8192,"
-                                   "200_136_72,200_100_128,33_17_40",
-                                   false, bgemm_mi355x_tn_num_configs, bgemm_mi355x_tn_config_name, bgemm_mi355x_tn_plan, nullptr,
-                                   nullptr, nullptr, bgemm_mi355x_tn_runs, bgemm_mi355x_launch_tn, bgemm_mi355x_tn,
-                                   bgemm_rocblas_tn, true};
-
-// --bias (with --layout tn --bf16): the fused-bias calls, bgemm_mi355x_launch_tn_bias / bgemm_mi355x_tn_bias.  The check's bias is
-// bias[n] = ((n mod 255) - 127) / 2: bf16 values, and with the integer sums S <= K exact in fp32, so the expected C is bf16(S + bias[n]),
-// rounded once.
-static bool g_bias = false;
-static float check_bias(int n) { return (float)((n % 255) - 127) * 0.5f; }
-
-static int cmd_check_nn(const TrLayout& L, std::vector<Shape> shapes) {
-  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
-  int failures = 0, runs = 0;
-  const std::string lay_s = std::string(L.label) + (g_bf16 ? "-bf16" : "") + (g_bias ? "-bias" : "");
-  const char* lay = lay_s.c_str();
-  const int nc = L.num_configs();
-  for (const Shape& sh : shapes) {
-    const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
-    const size_t cn = (size_t)sh.M * sh.N;
-    std::vector<uint16_t> truth(cn), got(cn);
-    std::vector<f16> b_rm((size_t)sh.K * sh.N);
-    for (int m = 0; m < sh.M; ++m)
-      for (int n = 0; n < sh.N; ++n) {
-        int acc = 0;
-        for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
-        const f16 t16 = (f16)(float)acc;
-        if (g_bias) truth[(size_t)m * sh.N + n] = bf16_rne((float)acc + check_bias(n));
-        else if (g_bf16) truth[(size_t)m * sh.N + n] = bf16_rne((float)acc);
-        else memcpy(&truth[(size_t)m * sh.N + n], &t16, 2);
-      }
-    for (int n = 0; n < sh.N; ++n)
-      for (int k = 0; k < sh.K; ++k) b_rm[(size_t)k * sh.N + n] = z.bt[(size_t)n * sh.K + k];
-    Buffers s;
-    HIP_OK(hipMalloc(&s.a, z.a.size() * 2));
-    HIP_OK(hipMalloc(&s.b, b_rm.size() * 2));
-    HIP_OK(hipMalloc(&s.c, cn * 2));
-    void* d_bias = nullptr;
-    if (g_bias) {
-      std::vector<uint16_t> hb(sh.N);
-      for (int n = 0; n < sh.N; ++n) hb[n] = bf16_rne(check_bias(n));
-      HIP_OK(hipMalloc(&d_bias, hb.size() * 2));
-      HIP_OK(hipMemcpy(d_bias, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
-    }
-    if (L.a_col_major) {   // a_col_major[k][m] = a[m][k]
-      std::vector<f16> a_cm(z.a.size());
-      for (int m = 0; m < sh.M; ++m)
-        for (int k = 0; k < sh.K; ++k) a_cm[(size_t)k * sh.M + m] = z.a[(size_t)m * sh.K + k];
-      HIP_OK(hipMemcpy(s.a, operand_bits(a_cm).data(), a_cm.size() * 2, hipMemcpyHostToDevice));
-    } else {
-      HIP_OK(hipMemcpy(s.a, operand_bits(z.a).data(), z.a.size() * 2, hipMemcpyHostToDevice));
-    }
-    HIP_OK(hipMemcpy(s.b, operand_bits(L.b_col_major ? z.bt : b_rm).data(), b_rm.size() * 2, hipMemcpyHostToDevice));   // (z.bt: [N][K])
-    for (int c = 0; c < nc; ++c) {
-      const char* cname = L.config_name(c);
-      const int own = (g_bf16 ? L.runs_bf16 : L.runs)(c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N);
-      for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
-        HIP_OK(hipMemset(s.c, 0xff, cn * 2));  // NaN pattern: unwritten outputs are caught
-        const int st = g_bias ? bgemm_mi355x_launch_tn_bias(c, splits, s.a, s.b, d_bias, s.c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, nullptr)
-                              : (g_bf16 ? L.launch_bf16 : L.launch)(c, splits, s.a, s.b, s.c, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, nullptr);
-        const hipError_t e = hipDeviceSynchronize();
-        ++runs;
-        if (st != HGEMM_OK || e != hipSuccess) {
-          printf("FAIL %s %d_%d_%d %s s=%d: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
-          ++failures;
-          if (e != hipSuccess) return 3;
-          continue;
-        }
-        HIP_OK(hipMemcpy(got.data(), s.c, cn * 2, hipMemcpyDeviceToHost));
-        size_t bad = 0;
-        for (size_t i = 0; i < cn; ++i)
-          if (memcmp(&got[i], &truth[i], 2) != 0) {
-            if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) printf("   bad m=%zu n=%zu got 0x%04x want 0x%04x\n", i / sh.N, i % sh.N, got[i], truth[i]);
-            ++bad;
-          }
-        if (bad) {
-          printf("FAIL %s %d_%d_%d %s s=%d%s: %zu/%zu elements differ from the exact result\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
-                 (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn);
-          ++failures;
-        }
-      }
-      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
-    }
-    free_set(s);
-    if (d_bias) HIP_OK(hipFree(d_bias));
-    fflush(stdout);
-  }
-  printf("check-%s-configs:", lay);
-  for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
-  printf("\ncheck-%s-forms: 1 1|nt-store 2 5\n", lay);
-  printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs%s)\n", lay, runs, failures,
-         g_bias ? " plus the bias, rounded to bf16 once" : g_bf16 ? ", rounded to bf16 once" : "");
-  return failures ? 1 : 0;
+// One call's operands.  Every variant's entry points sit behind the same two signatures; what a variant has no use for (bias,
+// accumulate) its adapter drops.
+struct TrCall { const void *a, *b, *bias; void* c; int accumulate; };
+template <auto F> static int launch16(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: a 16-bit-C launch
+  return F(cfg, splits, o.a, o.b, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
-
-// What the two bench commands do around their contenders.  The check first (no timing of a kernel that is wrong), then the output file:
-// nullptr (and *rc set) when nothing is to be timed.
-static FILE* tr_bench_open(const TrLayout& L, const char* out_path, int* rc) {
-  *rc = cmd_check_nn(L, {});
-  if (*rc != 0) { fprintf(stderr, "bench --layout %s: the check failed, nothing is timed\n", L.label); return nullptr; }
-  FILE* out = out_path ? fopen(out_path, "w") : stdout;
-  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); *rc = 2; }
-  return out;
+template <auto F> static int launch32(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: an fp32-C launch
+  return F(cfg, splits, o.a, o.b, (float*)o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, o.accumulate, nullptr);
 }
-// one JSON record per shape: the planned member, its splits, whether the family's kernel runs it, then the contenders' times
-static void tr_bench_record(FILE* out, const TrLayout& L, const Shape& sh, int rounds, const std::vector<Contender>& cs) {
-  const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
-  int cfg = 0, splits = 1;
-  L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
-  const int own = L.runs(cfg, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
-  const char* l = L.label;
-  fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"%s\", \"%s_config\": \"%s\", \"%s_splits\": %d, \"%s_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"",
-          sh.M, sh.N, sh.K, l, l, L.config_name(cfg), l, splits, l, own, rounds);
-  for (const Contender& c : cs) {
-    const double us = c.iso_us();
-    fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
-  }
-  fprintf(out, "}\n");
-  fflush(out);
+static int launch_bias(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_bias(cfg, splits, o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
+template <auto F> static int planned16(const TrCall& o, const Shape& sh) { return F(o.a, o.b, o.c, sh.M, sh.N, sh.K, nullptr); }
+template <auto F> static int planned32(const TrCall& o, const Shape& sh) { return F(o.a, o.b, (float*)o.c, sh.M, sh.N, sh.K, o.accumulate, nullptr); }
+static int planned_bias(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_bias(o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, nullptr); }
 
-// bench: the check first, then per shape ONE set of interleaved rounds (time_interleaved) of the
-// planned NN call, the reference kernel on the same operands (what a b-only call ran before the family), hipBLASLt heuristic / autotune
-// _nn, and -- context only -- the shipped TN plan on a pre-built b_col_major.  One JSON record per shape.
-static int cmd_bench_nn(const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
-  int rc = 0;
-  FILE* out = tr_bench_open(kLayoutNN, out_path, &rc);
-  if (!out) return rc;
+// What tr_bench is told about one bench (the descriptions themselves: bench_nn ... bench_tn_bias, below).
+struct TrBench;
+struct BenchDesc {
+  unsigned long long seed0;       // operand set i is filled from seed0 + i
+  void (*warm)(bool autotune);    // the vendor libraries' set-up, once, before anything is allocated or timed
+  void (*shape)(TrBench&);        // per shape: the extra buffers, the contenders in order, the header fields, the verdict
+};
+static void warm_none(bool) {}
+static void warm_rocblas(bool) { hgemm_rocblas_init(); }
+static void warm_hipblaslt(bool autotune) {
   hgemm_hipblaslt_heuristic_init();
   if (autotune) hgemm_hipblaslt_autotune_init();
-  hipEvent_t e0, e1;
-  HIP_OK(hipEventCreate(&e0));
-  HIP_OK(hipEventCreate(&e1));
-  for (const Shape& sh : shapes) {
-    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
-    std::vector<Buffers> sets(2);
-    for (size_t i = 0; i < sets.size(); ++i) alloc_set(sets[i], sh, 77 + i, true);
-    const bool have_at = autotune && hgemm_hipblaslt_autotune_find_best_nn(sh.M, sh.N, sh.K, 0) == HGEMM_OK;   // the search before any timing
-    std::vector<Contender> cs;
-    cs.push_back({"nn", [&](Buffers& b) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
-    cs.push_back({"generic", [&](Buffers& b) { return hgemm_mi355x_launch(HGEMM_CONFIG_GENERIC, 1, 1, b.a, b.b, nullptr, b.c, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N, nullptr); }});
-    cs.push_back({"heur_nn", [&](Buffers& b) { return hgemm_hipblaslt_heuristic_nn(b.a, b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
-    if (have_at) cs.push_back({"auto_nn", [&](Buffers& b) { return hgemm_hipblaslt_autotune_nn(b.a, b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
-    cs.push_back({"tn_shipped", [&](Buffers& b) { return hgemm_mi355x_fp32(b.a, nullptr, b.bt, b.c, sh.M, sh.N, sh.K, nullptr); }});
-    const int rounds = flops > 1.0e11 ? 5 : 15;   // (the reference kernel takes ~0.1 .. 0.5 s per call on the large shapes)
-    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
-    tr_bench_record(out, kLayoutNN, sh, rounds, cs);
-    for (auto& s : sets) free_set(s);
+}
+static void bench_nn(TrBench&), bench_ta(TrBench&), bench_ta_c32(TrBench&), bench_bf16(TrBench&), bench_tn_bf16(TrBench&), bench_tn_bias(TrBench&);
+static const BenchDesc kBenchNN = {77, warm_hipblaslt, bench_nn}, kBenchTA = {91, warm_none, bench_ta}, kBenchTAC32 = {91, warm_none, bench_ta_c32},
+                       kBenchBF16 = {91, warm_rocblas, bench_bf16}, kBenchTN = {91, warm_rocblas, bench_tn_bf16},
+                       kBenchTNBias = {91, warm_none, bench_tn_bias};
+
+struct Variant {
+  const TrLayout* L;
+  Elem elem;
+  Out out;
+  int (*runs)(int cfg, int M, int N, int K, int lda, int ldb, int ldc);   // 1: the family's kernel takes the call
+  int (*launch)(int cfg, int splits, const TrCall&, const Shape&, int lda, int ldb);
+  int (*planned)(const TrCall&, const Shape&);
+  const BenchDesc* bench;
+  std::string words(const char* layout, const char* sep) const {   // "ta-c32-bf16" / "--layout ta --c32 --bf16"
+    return std::string(layout) + L->label + (out == kC32 ? std::string(sep) + "c32" : "") + (elem == kBF16 ? std::string(sep) + "bf16" : "") +
+           (out == kC16Bias ? std::string(sep) + "bias" : "");
   }
-  HIP_OK(hipEventDestroy(e0));
-  HIP_OK(hipEventDestroy(e1));
-  if (out != stdout) fclose(out);
-  return 0;
+  int runs_at(int cfg, const Shape& sh) const { return runs(cfg, sh.M, sh.N, sh.K, L->lda(sh), L->ldb(sh), sh.N); }
+};
+static const Variant kVariants[] = {
+    {&kLayoutNN, kF16, kC16, hgemm_mi355x_nn_runs, launch16<hgemm_mi355x_launch_nn>, planned16<hgemm_mi355x_nn_fp32>, &kBenchNN},
+    {&kLayoutTA, kF16, kC16, hgemm_mi355x_ta_runs, launch16<hgemm_mi355x_launch_ta>, planned16<hgemm_mi355x_ta_fp32>, &kBenchTA},
+    {&kLayoutTA, kF16, kC32, hgemm_mi355x_ta_c32_runs, launch32<hgemm_mi355x_launch_ta_c32>, planned32<hgemm_mi355x_ta_c32>, &kBenchTAC32},
+    {&kLayoutNN, kBF16, kC16, bgemm_mi355x_nn_runs, launch16<bgemm_mi355x_launch_nn>, planned16<bgemm_mi355x_nn>, &kBenchBF16},
+    {&kLayoutTA, kBF16, kC16, bgemm_mi355x_ta_runs, launch16<bgemm_mi355x_launch_ta>, planned16<bgemm_mi355x_ta>, &kBenchBF16},
+    {&kLayoutTA, kBF16, kC32, bgemm_mi355x_ta_c32_runs, launch32<bgemm_mi355x_launch_ta_c32>, planned32<bgemm_mi355x_ta_c32>, &kBenchBF16},
+    {&kLayoutTN, kBF16, kC16, bgemm_mi355x_tn_runs, launch16<bgemm_mi355x_launch_tn>, planned16<bgemm_mi355x_tn>, &kBenchTN},
+    {&kLayoutTN, kBF16, kC16Bias, bgemm_mi355x_tn_bias_runs, launch_bias, planned_bias, &kBenchTNBias},
+};
+// nullptr: no such variant (--layout tn without --bf16 and no --layout at all are the fp16 b_col_major commands)
+static const Variant* resolve_variant(const std::string& layout, bool bf16, bool c32, bool bias) {
+  for (const Variant& v : kVariants)
+    if (layout == v.L->label && (v.elem == kBF16) == bf16 && (v.out == kC32) == c32 && (v.out == kC16Bias) == bias) return &v;
+  return nullptr;
 }
 
-// bench --layout ta: the check first, then per shape ONE set of interleaved rounds of the planned TA call on a_col_major, the planned
-// NN call on a pre-transposed (row-major) A -- context: what the product costs when the transpose is free --, a device-to-device copy
-// of A's bytes followed by that NN call -- no transpose pass can beat a copy, so a lower bound of what a caller without the TA entry
-// points pays --, and rocBLAS on the TA operands.  One JSON record per shape.
-static int cmd_bench_ta(const std::vector<Shape>& shapes, const char* out_path) {
-  int rc = 0;
-  FILE* out = tr_bench_open(kLayoutTA, out_path, &rc);
-  if (!out) return rc;
-  hipEvent_t e0, e1;
-  HIP_OK(hipEventCreate(&e0));
-  HIP_OK(hipEventCreate(&e1));
-  for (const Shape& sh : shapes) {
-    const size_t a_elems = (size_t)sh.M * sh.K;
-    std::vector<Buffers> sets(2);
-    std::vector<f16*> at(sets.size(), nullptr), tmp(sets.size(), nullptr);   // a_col_major and the copy's destination, per set
-    for (size_t i = 0; i < sets.size(); ++i) {
-      alloc_set(sets[i], sh, 91 + i, true);
-      HIP_OK(hipMalloc(&at[i], a_elems * 2));
-      HIP_OK(hipMalloc(&tmp[i], a_elems * 2));
-      transpose_kernel<<<(unsigned)((a_elems + 255) / 256), 256>>>(sets[i].a, at[i], sh.M, sh.K);   // at[k][m] = a[m][k]
-    }
-    HIP_OK(hipDeviceSynchronize());
-    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
-    std::vector<Contender> cs;
-    cs.push_back({"ta", [&](Buffers& b) { return hgemm_mi355x_ta_fp32(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
-    cs.push_back({"nn_pretransposed", [&](Buffers& b) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
-    cs.push_back({"copy_nn", [&](Buffers& b) {
-                    if (hipMemcpyAsync(tmp[idx(b)], b.a, a_elems * 2, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) return (int)HGEMM_ERR_HIP;
-                    return hgemm_mi355x_nn_fp32(tmp[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
-    cs.push_back({"rocblas_ta", [&](Buffers& b) { return hgemm_rocblas_ta(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); }});
-    const int rounds = 15;
-    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
-    tr_bench_record(out, kLayoutTA, sh, rounds, cs);
-    for (size_t i = 0; i < sets.size(); ++i) { free_set(sets[i]); HIP_OK(hipFree(at[i])); HIP_OK(hipFree(tmp[i])); }
+struct DevBufs {   // the device allocations of one scope: freed when it ends, on every way out
+  std::vector<void*> ptrs;
+  DevBufs() = default;
+  DevBufs(const DevBufs&) = delete;
+  DevBufs& operator=(const DevBufs&) = delete;
+  ~DevBufs() { for (void* p : ptrs) (void)hipFree(p); }
+  void* alloc(size_t bytes) {
+    void* p = nullptr;
+    HIP_OK(hipMalloc(&p, bytes));
+    ptrs.push_back(p);
+    return p;
   }
-  HIP_OK(hipEventDestroy(e0));
-  HIP_OK(hipEventDestroy(e1));
-  if (out != stdout) fclose(out);
-  return 0;
+  void* upload(const void* src, size_t bytes) {
+    void* p = alloc(bytes);
+    HIP_OK(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+    return p;
+  }
+};
+
+// The fused-bias check's bias is bias[n] = ((n mod 255) - 127) / 2: bf16 values, and with the integer sums S <= K exact in fp32, so the
+// expected C is bf16(S + bias[n]), rounded once.
+static float check_bias(int n) { return (float)((n % 255) - 127) * 0.5f; }
+static std::vector<f16> transposed(const std::vector<f16>& v, int rows, int cols) {   // [rows][cols] -> [cols][rows]
+  std::vector<f16> t(v.size());
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = v[(size_t)r * cols + c];
+  return t;
 }
 
-// ---- fp32 C of the TA layout (hgemm_mi355x_ta_c32): `check --layout ta --c32`, `bench --layout ta --c32` --------------------------------
-// check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} x {store, accumulate} on the shapes of the TA check, exact
-// against the host's integer result: 0/1 operands, an old C32 of integers in +-1000 (store mode starts from a NaN pattern instead).
-static int cmd_check_ta_c32(std::vector<Shape> shapes) {
-  const TrLayout& L = kLayoutTA;
+static int tr_check(const Variant& V, std::vector<Shape> shapes) {
+  const TrLayout& L = *V.L;
   if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
-  int failures = 0, runs = 0;
+  const bool c32 = V.out == kC32, bias = V.out == kC16Bias;
+  const size_t esz = c32 ? 4 : 2;   // bytes per element of C
+  const std::string lay_s = V.words("", "-");
+  const char* lay = lay_s.c_str();
   const int nc = L.num_configs();
+  int failures = 0, runs = 0;
   for (const Shape& sh : shapes) {
     const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
     const size_t cn = (size_t)sh.M * sh.N;
-    std::vector<float> product(cn), old(cn), got(cn);
-    std::vector<f16> b_rm((size_t)sh.K * sh.N), a_cm(z.a.size());
+    // the expected C as bytes: want[0] what a store leaves, want[1] (fp32 C alone) what accumulating onto `old` leaves
+    std::vector<unsigned char> want[2] = {std::vector<unsigned char>(cn * esz), std::vector<unsigned char>(c32 ? cn * esz : 0)}, got(cn * esz);
+    std::vector<float> old(c32 ? cn : 0);
     uint64_t lcg = 88172645463325252ull + cn;
     for (int m = 0; m < sh.M; ++m)
       for (int n = 0; n < sh.N; ++n) {
         int acc = 0;
         for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
-        product[(size_t)m * sh.N + n] = (float)acc;
-        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-        old[(size_t)m * sh.N + n] = (float)((int)((lcg >> 33) % 2001) - 1000);
+        const size_t i = (size_t)m * sh.N + n;
+        if (c32) {
+          lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+          old[i] = (float)((int)((lcg >> 33) % 2001) - 1000);
+          const float stored = (float)acc, summed = old[i] + stored;   // integers below 2^24: exact
+          memcpy(&want[0][i * 4], &stored, 4);
+          memcpy(&want[1][i * 4], &summed, 4);
+        } else {
+          const f16 t16 = (f16)(float)acc;   // int -> fp32 exact, fp32 -> fp16 round-to-nearest-even
+          const uint16_t tb = bf16_rne((float)acc + (bias ? check_bias(n) : 0.f));
+          memcpy(&want[0][i * 2], V.elem == kBF16 ? (const void*)&tb : (const void*)&t16, 2);
+        }
       }
-    for (int n = 0; n < sh.N; ++n)
-      for (int k = 0; k < sh.K; ++k) b_rm[(size_t)k * sh.N + n] = z.bt[(size_t)n * sh.K + k];
-    for (int m = 0; m < sh.M; ++m)
-      for (int k = 0; k < sh.K; ++k) a_cm[(size_t)k * sh.M + m] = z.a[(size_t)m * sh.K + k];
-    f16 *da = nullptr, *db = nullptr;
-    float* dc = nullptr;
-    HIP_OK(hipMalloc(&da, a_cm.size() * 2));
-    HIP_OK(hipMalloc(&db, b_rm.size() * 2));
-    HIP_OK(hipMalloc(&dc, cn * 4));
-    HIP_OK(hipMemcpy(da, operand_bits(a_cm).data(), a_cm.size() * 2, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(db, operand_bits(b_rm).data(), b_rm.size() * 2, hipMemcpyHostToDevice));
+    DevBufs dev;
+    const std::vector<uint16_t> a_h = operand_bits(L.a_col_major ? transposed(z.a, sh.M, sh.K) : z.a, V.elem);     // (z.a: [M][K])
+    const std::vector<uint16_t> b_h = operand_bits(L.b_col_major ? z.bt : transposed(z.bt, sh.N, sh.K), V.elem);   // (z.bt: [N][K])
+    TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), nullptr, dev.alloc(cn * esz), 0};
+    if (bias) {
+      std::vector<uint16_t> hb(sh.N);
+      for (int n = 0; n < sh.N; ++n) hb[n] = bf16_rne(check_bias(n));
+      call.bias = dev.upload(hb.data(), hb.size() * 2);
+    }
     for (int c = 0; c < nc; ++c) {
       const char* cname = L.config_name(c);
-      const int own = (g_bf16 ? bgemm_mi355x_ta_c32_runs : hgemm_mi355x_ta_c32_runs)(c, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N);
+      const int own = V.runs_at(c, sh);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5})
-        for (int accumulate : {0, 1}) {
-          if (accumulate) HIP_OK(hipMemcpy(dc, old.data(), cn * 4, hipMemcpyHostToDevice));
-          else            HIP_OK(hipMemset(dc, 0xff, cn * 4));   // NaN pattern: store mode must not read it, unwritten outputs are caught
-          const int st = (g_bf16 ? bgemm_mi355x_launch_ta_c32 : hgemm_mi355x_launch_ta_c32)(c, splits, da, db, dc, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N,
-                                                                                            accumulate, nullptr);
+        for (call.accumulate = 0; call.accumulate <= (c32 ? 1 : 0); ++call.accumulate) {
+          if (call.accumulate) HIP_OK(hipMemcpy(call.c, old.data(), cn * esz, hipMemcpyHostToDevice));
+          else                 HIP_OK(hipMemset(call.c, 0xff, cn * esz));   // NaN pattern: a store must not read it, unwritten outputs are caught
+          const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
           const hipError_t e = hipDeviceSynchronize();
           ++runs;
           if (st != HGEMM_OK || e != hipSuccess) {
-            printf("FAIL ta-c32 %d_%d_%d %s s=%d acc=%d: status %d hip %d\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, accumulate, st, (int)e);
+            printf("FAIL %s %d_%d_%d %s s=%d%s: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+                   !c32 ? "" : call.accumulate ? " acc=1" : " acc=0", st, (int)e);
             ++failures;
             if (e != hipSuccess) return 3;
             continue;
           }
-          HIP_OK(hipMemcpy(got.data(), dc, cn * 4, hipMemcpyDeviceToHost));
+          HIP_OK(hipMemcpy(got.data(), call.c, cn * esz, hipMemcpyDeviceToHost));
+          const unsigned char* w = want[call.accumulate].data();
           size_t bad = 0;
-          for (size_t i = 0; i < cn; ++i) {
-            const float want = accumulate ? old[i] + product[i] : product[i];   // integers below 2^24: exact
-            if (memcmp(&got[i], &want, 4) != 0) ++bad;
-          }
+          for (size_t i = 0; i < cn; ++i)
+            if (memcmp(&got[i * esz], &w[i * esz], esz) != 0) {
+              if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) {
+                uint32_t gv = 0, wv = 0;
+                memcpy(&gv, &got[i * esz], esz);
+                memcpy(&wv, &w[i * esz], esz);
+                printf("   bad m=%zu n=%zu got 0x%0*x want 0x%0*x\n", i / sh.N, i % sh.N, (int)esz * 2, gv, (int)esz * 2, wv);
+              }
+              ++bad;
+            }
           if (bad) {
-            printf("FAIL ta-c32 %d_%d_%d %s s=%d%s %s: %zu/%zu elements differ from the exact result\n", sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
-                   (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", accumulate ? "accumulate" : "store", bad, cn);
+            printf("FAIL %s %d_%d_%d %s s=%d%s%s: %zu/%zu elements differ from the exact result\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+                   (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", !c32 ? "" : call.accumulate ? " accumulate" : " store", bad, cn);
             ++failures;
           }
         }
-      if (c == 0) printf("checked ta-c32 %d_%d_%d (%s)\n", sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
+      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
     }
-    HIP_OK(hipFree(da)); HIP_OK(hipFree(db)); HIP_OK(hipFree(dc));
     fflush(stdout);
   }
-  printf("check-ta-c32-forms: 1 1|nt-store 2 5 x store accumulate\n");
-  printf("check ta-c32%s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs and an integer old C32)\n", g_bf16 ? "-bf16" : "", runs, failures);
+  printf("check-%s-configs:", lay);
+  for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
+  printf("\ncheck-%s-forms: 1 1|nt-store 2 5%s\n", lay, c32 ? " x store accumulate" : "");
+  printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs%s)\n", lay, runs, failures,
+         c32 ? " and an integer old C32" : bias ? " plus the bias, rounded to bf16 once" : V.elem == kBF16 ? ", rounded to bf16 once" : "");
   return failures ? 1 : 0;
 }
 
+// ---- bench --layout ...: the check first, then per shape ONE set of interleaved rounds (time_interleaved) of the variant's contenders --
 // what a caller without the fp32-C call runs behind hgemm_mi355x_ta_fp32: main_grad += float(dW16), a plain grid-stride kernel
 __global__ void add_f16_into_f32_kernel(float* __restrict__ c32, const f16* __restrict__ c16, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) c32[i] += (float)c16[i];
 }
-
-// bench --layout ta --c32: the check first, then per shape ONE set of interleaved rounds of the accumulate call, the store call, and the
-// comparator -- hgemm_mi355x_ta_fp32 into an fp16 scratch followed by the elementwise add.  One JSON record per shape; "c32_le_two_step"
-// is the first look's condition (accumulate call <= comparator).
-static int cmd_bench_ta_c32(const std::vector<Shape>& shapes, const char* out_path) {
-  int rc = cmd_check_ta_c32({});
-  if (rc != 0) { fprintf(stderr, "bench --layout ta --c32: the check failed, nothing is timed\n"); return rc; }
-  FILE* out = out_path ? fopen(out_path, "w") : stdout;
-  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
-  hipEvent_t e0, e1;
-  HIP_OK(hipEventCreate(&e0));
-  HIP_OK(hipEventCreate(&e1));
-  for (const Shape& sh : shapes) {
-    const size_t a_elems = (size_t)sh.M * sh.K, cn = (size_t)sh.M * sh.N;
-    std::vector<Buffers> sets(2);
-    std::vector<f16*> at(sets.size(), nullptr);
-    std::vector<float*> c32(sets.size(), nullptr);
-    for (size_t i = 0; i < sets.size(); ++i) {
-      alloc_set(sets[i], sh, 91 + i, true);
-      HIP_OK(hipMalloc(&at[i], a_elems * 2));
-      HIP_OK(hipMalloc(&c32[i], cn * 4));
-      HIP_OK(hipMemset(c32[i], 0, cn * 4));
-      transpose_kernel<<<(unsigned)((a_elems + 255) / 256), 256>>>(sets[i].a, at[i], sh.M, sh.K);   // at[k][m] = a[m][k]
-    }
-    HIP_OK(hipDeviceSynchronize());
-    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
-    const unsigned add_grid = (unsigned)std::min<size_t>((cn + 255) / 256, 256 * 8);
-    std::vector<Contender> cs;
-    cs.push_back({"c32_accumulate", [&](Buffers& b) { return hgemm_mi355x_ta_c32(at[idx(b)], b.b, c32[idx(b)], sh.M, sh.N, sh.K, 1, nullptr); }});
-    cs.push_back({"c32_store", [&](Buffers& b) { return hgemm_mi355x_ta_c32(at[idx(b)], b.b, c32[idx(b)], sh.M, sh.N, sh.K, 0, nullptr); }});
-    cs.push_back({"two_step", [&](Buffers& b) {
-                    const int st = hgemm_mi355x_ta_fp32(at[idx(b)], b.b, b.c, sh.M, sh.N, sh.K, nullptr);
-                    if (st != HGEMM_OK) return st;
-                    add_f16_into_f32_kernel<<<add_grid, 256>>>(c32[idx(b)], b.c, cn);
-                    return hipGetLastError() == hipSuccess ? (int)HGEMM_OK : (int)HGEMM_ERR_HIP; }});
-    const int rounds = 15;
-    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
-    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
-    int cfg = 0, splits = 1;
-    hgemm_mi355x_ta_plan(sh.M, sh.N, sh.K, &cfg, &splits);
-    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"ta\", \"output\": \"c32\", \"ta_config\": \"%s\", \"ta_splits\": %d, \"ta_c32_runs\": %d, \"rounds\": %d, "
-                 "\"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, hgemm_mi355x_ta_config_name(cfg), splits,
-            hgemm_mi355x_ta_c32_runs(cfg, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N), rounds);
-    for (const Contender& c : cs) {
-      const double us = c.iso_us();
-      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
-    }
-    const double acc_us = cs[0].iso_us(), two_us = cs[2].iso_us();
-    fprintf(out, ", \"c32_le_two_step\": %s}\n", acc_us > 0 && two_us > 0 && acc_us <= two_us ? "true" : "false");
-    fflush(out);
-    for (size_t i = 0; i < sets.size(); ++i) { free_set(sets[i]); HIP_OK(hipFree(at[i])); HIP_OK(hipFree(c32[i])); }
-  }
-  HIP_OK(hipEventDestroy(e0));
-  HIP_OK(hipEventDestroy(e1));
-  if (out != stdout) fclose(out);
-  return 0;
-}
-
-// ---- bfloat16 (bgemm_mi355x_nn / _ta / _ta_c32): `bench --layout nn|ta [--c32] --bf16` ---------------------------------------------------
 __global__ void f16_to_bf16_kernel(const f16* __restrict__ in, __bf16* __restrict__ out, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (__bf16)(float)in[i];
 }
-
-// The check first, then per shape ONE set of interleaved rounds of the planned bf16 call, the planned fp16 call -- the same plan on the
-// same shape: the planner does not know the element kind -- on the fp16 N(0,1) operands the bf16 ones were rounded from, and, context
-// only, rocBLAS with bf16 in and out (16-bit C only).  c32: both calls accumulate.  The two calls move the same bytes and issue the same
-// number of MFMAs, so the one condition is bf16 <= fp16 within the fp16 call's own round-to-round spread in this run (its slowest round
-// minus its median): "bf16_le_fp16".
-static int cmd_bench_bf16(const TrLayout& L, bool c32, const std::vector<Shape>& shapes, const char* out_path) {
-  int rc = c32 ? cmd_check_ta_c32({}) : cmd_check_nn(L, {});
-  if (rc != 0) { fprintf(stderr, "bench --layout %s --bf16: the check failed, nothing is timed\n", L.label); return rc; }
-  FILE* out = out_path ? fopen(out_path, "w") : stdout;
-  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
-  hgemm_rocblas_init();
-  hipEvent_t e0, e1;
-  HIP_OK(hipEventCreate(&e0));
-  HIP_OK(hipEventCreate(&e1));
-  for (const Shape& sh : shapes) {
-    const size_t a_elems = (size_t)sh.M * sh.K, b_elems = (size_t)sh.K * sh.N, cn = (size_t)sh.M * sh.N;
-    std::vector<Buffers> sets(2);
-    std::vector<f16*> a16(sets.size(), nullptr);      // A as the layout takes it, fp16 ...
-    std::vector<__bf16*> ab(sets.size(), nullptr), bb(sets.size(), nullptr), cb(sets.size(), nullptr);   // ... and the bf16 operands and C
-    std::vector<float*> c32h(sets.size(), nullptr), c32b(sets.size(), nullptr);
-    for (size_t i = 0; i < sets.size(); ++i) {
-      alloc_set(sets[i], sh, 91 + i, true);
-      HIP_OK(hipMalloc(&ab[i], a_elems * 2));
-      HIP_OK(hipMalloc(&bb[i], b_elems * 2));
-      HIP_OK(hipMalloc(&cb[i], cn * 2));
-      if (L.a_col_major) {
-        HIP_OK(hipMalloc(&a16[i], a_elems * 2));
-        transpose_kernel<<<(unsigned)((a_elems + 255) / 256), 256>>>(sets[i].a, a16[i], sh.M, sh.K);   // a16[k][m] = a[m][k]
-      }
-      const f16* a_src = L.a_col_major ? a16[i] : sets[i].a;
-      f16_to_bf16_kernel<<<2048, 256>>>(a_src, ab[i], a_elems);
-      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].b, bb[i], b_elems);
-      if (c32) {
-        HIP_OK(hipMalloc(&c32h[i], cn * 4));
-        HIP_OK(hipMalloc(&c32b[i], cn * 4));
-        HIP_OK(hipMemset(c32h[i], 0, cn * 4));
-        HIP_OK(hipMemset(c32b[i], 0, cn * 4));
-      }
-    }
-    HIP_OK(hipDeviceSynchronize());
-    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
-    auto a_of = [&](Buffers& b) { return L.a_col_major ? (const void*)a16[idx(b)] : (const void*)b.a; };
-    std::vector<Contender> cs;
-    if (c32) {
-      cs.push_back({"bf16", [&](Buffers& b) { return bgemm_mi355x_ta_c32(ab[idx(b)], bb[idx(b)], c32b[idx(b)], sh.M, sh.N, sh.K, 1, nullptr); }});
-      cs.push_back({"fp16", [&](Buffers& b) { return hgemm_mi355x_ta_c32(a_of(b), b.b, c32h[idx(b)], sh.M, sh.N, sh.K, 1, nullptr); }});
-    } else {
-      cs.push_back({"bf16", [&](Buffers& b) { return L.planned_bf16(ab[idx(b)], bb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
-      cs.push_back({"fp16", [&](Buffers& b) { return L.planned(a_of(b), b.b, b.c, sh.M, sh.N, sh.K, nullptr); }});
-      cs.push_back({"rocblas_bf16", [&](Buffers& b) { return L.rocblas_bf16(ab[idx(b)], bb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
-    }
-    const int rounds = 15;
-    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
-    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
-    int cfg = 0, splits = 1;
-    L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
-    const int own = c32 ? bgemm_mi355x_ta_c32_runs(cfg, sh.M, sh.N, sh.K, sh.M, sh.N, sh.N) : L.runs_bf16(cfg, sh.M, sh.N, sh.K, L.lda(sh), sh.N, sh.N);
-    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"%s\", \"output\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d, "
-                 "\"rounds\": %d, \"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, L.label, c32 ? "c32_accumulate" : "c16", L.config_name(cfg), splits, own, rounds);
-    for (const Contender& c : cs) {
-      const double us = c.iso_us();
-      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
-    }
-    const double b_us = cs[0].iso_us(), h_us = cs[1].iso_us();
-    const double spread = cs[1].ok && !cs[1].iso.empty() ? *std::max_element(cs[1].iso.begin(), cs[1].iso.end()) - h_us : -1.0;
-    fprintf(out, ", \"fp16_spread_us\": %.3f, \"bf16_le_fp16\": %s}\n", spread, b_us > 0 && h_us > 0 && b_us <= h_us + spread ? "true" : "false");
-    fflush(out);
-    for (size_t i = 0; i < sets.size(); ++i) {
-      free_set(sets[i]);
-      HIP_OK(hipFree(ab[i])); HIP_OK(hipFree(bb[i])); HIP_OK(hipFree(cb[i]));
-      if (a16[i]) HIP_OK(hipFree(a16[i]));
-      if (c32h[i]) HIP_OK(hipFree(c32h[i]));
-      if (c32b[i]) HIP_OK(hipFree(c32b[i]));
-    }
-  }
-  HIP_OK(hipEventDestroy(e0));
-  HIP_OK(hipEventDestroy(e1));
-  if (out != stdout) fclose(out);
-  return 0;
-}
-
-// bench --layout tn --bf16: the check first, then per shape ONE set of interleaved rounds of the planned bgemm_mi355x_tn call, of
-// bgemm_mi355x_launch_nn with the same member (the two tables list the same tiles in the same order) and the same splits on the same
-// shape -- the same bytes and MFMAs; ds_read_b128 where family n issues pairs of transposed reads --, and, context only, rocBLAS with
-// bf16 in and out on the tn operands.  The one condition: tn <= nn within the nn call's own round-to-round spread in this run (its slowest
-// round minus its median): "tn_le_nn".
-static int cmd_bench_tn_bf16(const std::vector<Shape>& shapes, const char* out_path) {
-  const TrLayout& L = kLayoutTN;
-  int rc = cmd_check_nn(L, {});
-  if (rc != 0) { fprintf(stderr, "bench --layout tn --bf16: the check failed, nothing is timed\n"); return rc; }
-  FILE* out = out_path ? fopen(out_path, "w") : stdout;
-  if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
-  hgemm_rocblas_init();
-  hipEvent_t e0, e1;
-  HIP_OK(hipEventCreate(&e0));
-  HIP_OK(hipEventCreate(&e1));
-  for (const Shape& sh : shapes) {
-    const size_t a_elems = (size_t)sh.M * sh.K, b_elems = (size_t)sh.K * sh.N, cn = (size_t)sh.M * sh.N;
-    std::vector<Buffers> sets(2);
-    std::vector<__bf16*> ab(sets.size(), nullptr), bb(sets.size(), nullptr), btb(sets.size(), nullptr), cb(sets.size(), nullptr);
-    for (size_t i = 0; i < sets.size(); ++i) {
-      alloc_set(sets[i], sh, 91 + i, true);   // a [M][K], b [K][N] and bt = b_col_major [N][K] of the same B
-      HIP_OK(hipMalloc(&ab[i], a_elems * 2));
-      HIP_OK(hipMalloc(&bb[i], b_elems * 2));
-      HIP_OK(hipMalloc(&btb[i], b_elems * 2));
-      HIP_OK(hipMalloc(&cb[i], cn * 2));
-      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].a, ab[i], a_elems);
-      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].b, bb[i], b_elems);
-      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].bt, btb[i], b_elems);
-    }
-    HIP_OK(hipDeviceSynchronize());
-    int cfg = 0, splits = 1;
-    L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
-    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
-    std::vector<Contender> cs;
-    cs.push_back({"tn", [&](Buffers& b) { return bgemm_mi355x_tn(ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
-    cs.push_back({"nn", [&](Buffers& b) { return bgemm_mi355x_launch_nn(cfg, splits, ab[idx(b)], bb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, sh.K, sh.N, sh.N, nullptr); }});
-    cs.push_back({"rocblas_tn", [&](Buffers& b) { return bgemm_rocblas_tn(ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
-    const int rounds = 15;
-    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
-    const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
-    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"tn\", \"output\": \"c16\", \"elem\": \"bf16\", \"config\": \"%s\", \"nn_config\": \"%s\", \"splits\": %d, "
-                 "\"runs\": %d, \"nn_runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, L.config_name(cfg),
-            hgemm_mi355x_nn_config_name(cfg), splits, L.runs_bf16(cfg, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N),
-            bgemm_mi355x_nn_runs(cfg, sh.M, sh.N, sh.K, sh.K, sh.N, sh.N), rounds);
-    for (const Contender& c : cs) {
-      const double us = c.iso_us();
-      fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
-    }
-    const double t_us = cs[0].iso_us(), n_us = cs[1].iso_us();
-    const double spread = cs[1].ok && !cs[1].iso.empty() ? *std::max_element(cs[1].iso.begin(), cs[1].iso.end()) - n_us : -1.0;
-    fprintf(out, ", \"nn_spread_us\": %.3f, \"tn_le_nn\": %s}\n", spread, t_us > 0 && n_us > 0 && t_us <= n_us + spread ? "true" : "false");
-    fflush(out);
-    for (size_t i = 0; i < sets.size(); ++i) {
-      free_set(sets[i]);
-      HIP_OK(hipFree(ab[i])); HIP_OK(hipFree(bb[i])); HIP_OK(hipFree(btb[i])); HIP_OK(hipFree(cb[i]));
-    }
-  }
-  HIP_OK(hipEventDestroy(e0));
-  HIP_OK(hipEventDestroy(e1));
-  if (out != stdout) fclose(out);
-  return 0;
-}
-
 __global__ void fill_bias_kernel(__bf16* __restrict__ bias, int n) {   // N(0,1)-sized values, a fixed pattern: timing only
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) bias[i] = (__bf16)((float)((i * 37) % 129 - 64) * (1.0f / 32.0f));
 }
@@ -1570,65 +1276,99 @@ __global__ void add_bias_kernel(__bf16* __restrict__ c, const __bf16* __restrict
     c[i] = (__bf16)((float)c[i] + (float)bias[i % n]);
 }
 
-// bench --layout tn --bf16 --bias: the bias check first, then per shape ONE set of interleaved rounds of the planned bgemm_mi355x_tn_bias
-// call, of bgemm_mi355x_launch_tn with the same member and splits and no bias -- the fused kernel adds 2 BN bytes of loads and 4 FM FN
-// adds per lane to a tile --, and, context only, the path the call replaces: bgemm_mi355x_tn followed by an element-wise bf16 add.  The
-// one condition: fused <= plain within the plain call's own round-to-round spread in this run (its slowest round minus its median):
-// "bias_le_plain".
-static int cmd_bench_tn_bias(const std::vector<Shape>& shapes, const char* out_path) {
-  const TrLayout& L = kLayoutTN;
-  int rc = cmd_check_nn(L, {});
-  if (rc != 0) { fprintf(stderr, "bench --layout tn --bf16 --bias: the check failed, nothing is timed\n"); return rc; }
+// One shape of one bench, as its description sees it: the two operand sets (alloc_set: a [M][K], b [K][N], bt = b_col_major [N][K] of the
+// same B, c [M][N]; fp16, N(0,1)), helpers for the further buffers a contender needs -- one per set, freed with this object --, and what
+// the description leaves for the driver: contenders, header fields, rounds, verdict.
+struct TrBench {
+  typedef std::array<void*, 2> PerSet;   // one device pointer per operand set
+  const Variant& V;
+  const Shape sh;
+  const bool autotune;
+  const size_t a_elems, b_elems, cn;
+  std::vector<Buffers> sets;
+  DevBufs dev;
+  int cfg = 0, splits = 1;               // V's plan for sh
+  int rounds = 15;
+  std::vector<Contender> cs;
+  std::string header;                    // the record's fields between "layout" and "rounds"
+  const char* verdict_key = nullptr;     // "<key>": cs[va] <= cs[vb] (+ cs[vb]'s slowest round minus its median, recorded as "<vb's key>_spread_us")
+  int va = 0, vb = 1;
+  bool with_spread = true;
+  TrBench(const Variant& v, const Shape& s, bool at)
+      : V(v), sh(s), autotune(at), a_elems((size_t)s.M * s.K), b_elems((size_t)s.K * s.N), cn((size_t)s.M * s.N), sets(2) {
+    for (size_t i = 0; i < sets.size(); ++i) alloc_set(sets[i], sh, V.bench->seed0 + i, true);
+    V.L->plan(sh.M, sh.N, sh.K, &cfg, &splits);
+  }
+  ~TrBench() { for (Buffers& s : sets) free_set(s); }
+  PerSet alloc(size_t bytes, bool zeroed = false) {
+    PerSet p;
+    for (void*& q : p) {
+      q = dev.alloc(bytes);
+      if (zeroed) HIP_OK(hipMemset(q, 0, bytes));
+    }
+    return p;
+  }
+  PerSet of(f16* Buffers::*member) { return {sets[0].*member, sets[1].*member}; }
+  PerSet a_col_major() {   // [K][M] of each set's a
+    PerSet p = alloc(a_elems * 2);
+    for (size_t i = 0; i < p.size(); ++i) transpose_kernel<<<(unsigned)((a_elems + 255) / 256), 256>>>(sets[i].a, (f16*)p[i], sh.M, sh.K);
+    return p;
+  }
+  PerSet to_bf16(const PerSet& src, size_t n) {
+    PerSet p = alloc(n * 2);
+    for (size_t i = 0; i < p.size(); ++i) f16_to_bf16_kernel<<<2048, 256>>>((const f16*)src[i], (__bf16*)p[i], n);
+    return p;
+  }
+  // contenders are timed in the order they are added (time_interleaved rotates by index); f(set, the set's index into a PerSet)
+  void add(const char* key, std::function<int(Buffers&, size_t)> f) {
+    Buffers* first = sets.data();
+    cs.push_back({key, [first, f](Buffers& b) { return f(b, (size_t)(&b - first)); }});
+  }
+  __attribute__((format(printf, 2, 3))) void head(const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    header = buf;
+  }
+  void verdict(const char* key, int a, int b, bool spread) { verdict_key = key; va = a; vb = b; with_spread = spread; }
+};
+
+static int tr_bench(const Variant& V, const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
+  const int rc = tr_check(V, {});   // no timing of a kernel that is wrong
+  if (rc != 0) { fprintf(stderr, "bench %s: the check failed, nothing is timed\n", V.words("--layout ", " --").c_str()); return rc; }
   FILE* out = out_path ? fopen(out_path, "w") : stdout;
   if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
+  V.bench->warm(autotune);
   hipEvent_t e0, e1;
   HIP_OK(hipEventCreate(&e0));
   HIP_OK(hipEventCreate(&e1));
   for (const Shape& sh : shapes) {
-    const size_t a_elems = (size_t)sh.M * sh.K, b_elems = (size_t)sh.K * sh.N, cn = (size_t)sh.M * sh.N;
-    std::vector<Buffers> sets(2);
-    std::vector<__bf16*> ab(sets.size(), nullptr), btb(sets.size(), nullptr), cb(sets.size(), nullptr), bias(sets.size(), nullptr);
-    for (size_t i = 0; i < sets.size(); ++i) {
-      alloc_set(sets[i], sh, 91 + i, true);   // a [M][K] and bt = b_col_major [N][K]
-      HIP_OK(hipMalloc(&ab[i], a_elems * 2));
-      HIP_OK(hipMalloc(&btb[i], b_elems * 2));
-      HIP_OK(hipMalloc(&cb[i], cn * 2));
-      HIP_OK(hipMalloc(&bias[i], (size_t)sh.N * 2));
-      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].a, ab[i], a_elems);
-      f16_to_bf16_kernel<<<2048, 256>>>(sets[i].bt, btb[i], b_elems);
-      fill_bias_kernel<<<64, 256>>>(bias[i], sh.N);
-    }
+    TrBench B(V, sh, autotune);
+    V.bench->shape(B);
     HIP_OK(hipDeviceSynchronize());
-    int cfg = 0, splits = 1;
-    L.plan(sh.M, sh.N, sh.K, &cfg, &splits);
-    auto idx = [&](Buffers& b) { return (size_t)(&b - sets.data()); };
-    const int add_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
-    std::vector<Contender> cs;
-    cs.push_back({"bias", [&](Buffers& b) { return bgemm_mi355x_tn_bias(ab[idx(b)], btb[idx(b)], bias[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr); }});
-    cs.push_back({"plain", [&](Buffers& b) { return bgemm_mi355x_launch_tn(cfg, splits, ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, sh.K, sh.K, sh.N, nullptr); }});
-    cs.push_back({"unfused", [&](Buffers& b) {
-                    const int st = bgemm_mi355x_tn(ab[idx(b)], btb[idx(b)], cb[idx(b)], sh.M, sh.N, sh.K, nullptr);
-                    add_bias_kernel<<<add_grid, 256>>>(cb[idx(b)], bias[idx(b)], cn, sh.N);
-                    return st;
-                  }});
-    const int rounds = 15;
-    time_interleaved(cs, sets, rounds, 0, 0.0, 1.0, e0, e1);
+    time_interleaved(B.cs, B.sets, B.rounds, 0, 0.0, 1.0, e0, e1);
+    // one JSON record per shape: the description's header fields (plan, whether the family's kernel runs it), then the contenders' times
     const double flops = 2.0 * sh.M * sh.N * (double)sh.K;
-    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"tn\", \"output\": \"c16_bias\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, "
-                 "\"runs\": %d, \"rounds\": %d, \"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, L.config_name(cfg), splits,
-            bgemm_mi355x_tn_bias_runs(cfg, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N), rounds);
-    for (const Contender& c : cs) {
+    fprintf(out, "{\"mnk\": \"%d_%d_%d\", \"layout\": \"%s\", %s, \"rounds\": %d, \"protocol\": \"interleaved\"", sh.M, sh.N, sh.K, V.L->label,
+            B.header.c_str(), B.rounds);
+    for (const Contender& c : B.cs) {
       const double us = c.iso_us();
       fprintf(out, ", \"%s_us\": %.3f, \"%s_tflops\": %.2f", c.key, us, c.key, us > 0 ? flops / us * 1e-6 : -1.0);
     }
-    const double f_us = cs[0].iso_us(), p_us = cs[1].iso_us();
-    const double spread = cs[1].ok && !cs[1].iso.empty() ? *std::max_element(cs[1].iso.begin(), cs[1].iso.end()) - p_us : -1.0;
-    fprintf(out, ", \"plain_spread_us\": %.3f, \"bias_le_plain\": %s}\n", spread, f_us > 0 && p_us > 0 && f_us <= p_us + spread ? "true" : "false");
-    fflush(out);
-    for (size_t i = 0; i < sets.size(); ++i) {
-      free_set(sets[i]);
-      HIP_OK(hipFree(ab[i])); HIP_OK(hipFree(btb[i])); HIP_OK(hipFree(cb[i])); HIP_OK(hipFree(bias[i]));
+    if (B.verdict_key) {
+      const Contender &x = B.cs[B.va], &y = B.cs[B.vb];
+      const double x_us = x.iso_us(), y_us = y.iso_us();
+      double slack = 0.0;
+      if (B.with_spread) {
+        slack = y.ok && !y.iso.empty() ? *std::max_element(y.iso.begin(), y.iso.end()) - y_us : -1.0;
+        fprintf(out, ", \"%s_spread_us\": %.3f", y.key, slack);
+      }
+      fprintf(out, ", \"%s\": %s", B.verdict_key, x_us > 0 && y_us > 0 && x_us <= y_us + slack ? "true" : "false");
     }
+    fprintf(out, "}\n");
+    fflush(out);
   }
   HIP_OK(hipEventDestroy(e0));
   HIP_OK(hipEventDestroy(e1));
@@ -1636,18 +1376,128 @@ static int cmd_bench_tn_bias(const std::vector<Shape>& shapes, const char* out_p
   return 0;
 }
 
+// nn: the planned NN call, the reference kernel on the same operands (what a b-only call ran before the family), hipBLASLt heuristic /
+// autotune _nn, and -- context only -- the shipped TN plan on the pre-built b_col_major.
+static void bench_nn(TrBench& B) {
+  const Shape sh = B.sh;
+  const bool have_at = B.autotune && hgemm_hipblaslt_autotune_find_best_nn(sh.M, sh.N, sh.K, 0) == HGEMM_OK;   // the search before any timing
+  B.add("nn", [=](Buffers& b, size_t) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); });
+  B.add("generic", [=](Buffers& b, size_t) { return hgemm_mi355x_launch(HGEMM_CONFIG_GENERIC, 1, 1, b.a, b.b, nullptr, b.c, sh.M, sh.N, sh.K, sh.K, sh.K, sh.N, nullptr); });
+  B.add("heur_nn", [=](Buffers& b, size_t) { return hgemm_hipblaslt_heuristic_nn(b.a, b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); });
+  if (have_at) B.add("auto_nn", [=](Buffers& b, size_t) { return hgemm_hipblaslt_autotune_nn(b.a, b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); });
+  B.add("tn_shipped", [=](Buffers& b, size_t) { return hgemm_mi355x_fp32(b.a, nullptr, b.bt, b.c, sh.M, sh.N, sh.K, nullptr); });
+  if (2.0 * sh.M * sh.N * (double)sh.K > 1.0e11) B.rounds = 5;   // (the reference kernel takes ~0.1 .. 0.5 s per call on the large shapes)
+  B.head("\"nn_config\": \"%s\", \"nn_splits\": %d, \"nn_runs\": %d", B.V.L->config_name(B.cfg), B.splits, B.V.runs_at(B.cfg, sh));
+}
+
+// ta: the planned TA call on a_col_major, the planned NN call on the row-major A -- context: what the product costs when the transpose is
+// free --, a device-to-device copy of A's bytes followed by that NN call -- no transpose pass can beat a copy, so a lower bound of what a
+// caller without the TA entry points pays --, and rocBLAS on the TA operands.
+static void bench_ta(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t a_bytes = B.a_elems * 2;
+  const TrBench::PerSet at = B.a_col_major(), tmp = B.alloc(a_bytes);
+  B.add("ta", [=](Buffers& b, size_t i) { return hgemm_mi355x_ta_fp32(at[i], b.b, b.c, sh.M, sh.N, sh.K, nullptr); });
+  B.add("nn_pretransposed", [=](Buffers& b, size_t) { return hgemm_mi355x_nn_fp32(b.a, b.b, b.c, sh.M, sh.N, sh.K, nullptr); });
+  B.add("copy_nn", [=](Buffers& b, size_t i) {
+    if (hipMemcpyAsync(tmp[i], b.a, a_bytes, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) return (int)HGEMM_ERR_HIP;
+    return hgemm_mi355x_nn_fp32(tmp[i], b.b, b.c, sh.M, sh.N, sh.K, nullptr);
+  });
+  B.add("rocblas_ta", [=](Buffers& b, size_t i) { return hgemm_rocblas_ta(at[i], b.b, b.c, sh.M, sh.N, sh.K, 0, nullptr); });
+  B.head("\"ta_config\": \"%s\", \"ta_splits\": %d, \"ta_runs\": %d", B.V.L->config_name(B.cfg), B.splits, B.V.runs_at(B.cfg, sh));
+}
+
+// ta --c32: the accumulate call, the store call, and the comparator -- hgemm_mi355x_ta_fp32 into an fp16 scratch followed by the
+// elementwise add.  "c32_le_two_step" is the first look's condition (accumulate call <= comparator).
+static void bench_ta_c32(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const TrBench::PerSet at = B.a_col_major(), c32 = B.alloc(cn * 4, true);
+  const unsigned add_grid = (unsigned)std::min<size_t>((cn + 255) / 256, 256 * 8);
+  B.add("c32_accumulate", [=](Buffers& b, size_t i) { return hgemm_mi355x_ta_c32(at[i], b.b, (float*)c32[i], sh.M, sh.N, sh.K, 1, nullptr); });
+  B.add("c32_store", [=](Buffers& b, size_t i) { return hgemm_mi355x_ta_c32(at[i], b.b, (float*)c32[i], sh.M, sh.N, sh.K, 0, nullptr); });
+  B.add("two_step", [=](Buffers& b, size_t i) {
+    const int st = hgemm_mi355x_ta_fp32(at[i], b.b, b.c, sh.M, sh.N, sh.K, nullptr);
+    if (st != HGEMM_OK) return st;
+    add_f16_into_f32_kernel<<<add_grid, 256>>>((float*)c32[i], b.c, cn);
+    return hipGetLastError() == hipSuccess ? (int)HGEMM_OK : (int)HGEMM_ERR_HIP;
+  });
+  B.head("\"output\": \"c32\", \"ta_config\": \"%s\", \"ta_splits\": %d, \"ta_c32_runs\": %d", B.V.L->config_name(B.cfg), B.splits, B.V.runs_at(B.cfg, sh));
+  B.verdict("c32_le_two_step", 0, 2, false);
+}
+
+// nn|ta [--c32] --bf16: the planned bf16 call, the planned fp16 call -- the same plan on the same shape: the planner does not know the
+// element kind -- on the fp16 N(0,1) operands the bf16 ones were rounded from, and, context only, rocBLAS with bf16 in and out (16-bit C
+// only).  c32: both calls accumulate.  The two calls move the same bytes and issue the same number of MFMAs, so the one condition is
+// bf16 <= fp16 within the fp16 call's own round-to-round spread in this run: "bf16_le_fp16".
+static void bench_bf16(TrBench& B) {
+  const Shape sh = B.sh;
+  const TrLayout* L = B.V.L;
+  const bool c32 = B.V.out == kC32;
+  const Variant *bf = &B.V, *fp = resolve_variant(L->label, false, c32, false);   // (every bf16 variant of nn and ta has its fp16 twin)
+  const TrBench::PerSet a16 = L->a_col_major ? B.a_col_major() : B.of(&Buffers::a);   // A as the layout takes it, fp16
+  const TrBench::PerSet ab = B.to_bf16(a16, B.a_elems), bb = B.to_bf16(B.of(&Buffers::b), B.b_elems);
+  const TrBench::PerSet cb = c32 ? B.alloc(B.cn * 4, true) : B.alloc(B.cn * 2), ch = c32 ? B.alloc(B.cn * 4, true) : B.of(&Buffers::c);
+  B.add("bf16", [=](Buffers&, size_t i) { return bf->planned({ab[i], bb[i], nullptr, cb[i], 1}, sh); });
+  B.add("fp16", [=](Buffers& b, size_t i) { return fp->planned({a16[i], b.b, nullptr, ch[i], 1}, sh); });
+  if (!c32) B.add("rocblas_bf16", [=](Buffers&, size_t i) { return L->rocblas_bf16(ab[i], bb[i], cb[i], sh.M, sh.N, sh.K, nullptr); });
+  B.head("\"output\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", c32 ? "c32_accumulate" : "c16", L->config_name(B.cfg), B.splits,
+         B.V.runs_at(B.cfg, sh));
+  B.verdict("bf16_le_fp16", 0, 1, true);
+}
+
+// tn --bf16: the planned bgemm_mi355x_tn call, bgemm_mi355x_launch_nn with the same member (the two tables list the same tiles in the
+// same order) and the same splits on the same shape -- the same bytes and MFMAs; ds_read_b128 where family n issues pairs of transposed
+// reads --, and, context only, rocBLAS with bf16 in and out on the tn operands.  The one condition: tn <= nn within the nn call's own
+// round-to-round spread in this run: "tn_le_nn".
+static void bench_tn_bf16(TrBench& B) {
+  const Shape sh = B.sh;
+  const int cfg = B.cfg, splits = B.splits, nn_lda = kLayoutNN.lda(sh), nn_ldb = kLayoutNN.ldb(sh);
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), bb = B.to_bf16(B.of(&Buffers::b), B.b_elems),
+                        btb = B.to_bf16(B.of(&Buffers::bt), B.b_elems), cb = B.alloc(B.cn * 2);
+  B.add("tn", [=](Buffers&, size_t i) { return bgemm_mi355x_tn(ab[i], btb[i], cb[i], sh.M, sh.N, sh.K, nullptr); });
+  B.add("nn", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], cb[i], sh.M, sh.N, sh.K, nn_lda, nn_ldb, sh.N, nullptr); });
+  B.add("rocblas_tn", [=](Buffers&, size_t i) { return bgemm_rocblas_tn(ab[i], btb[i], cb[i], sh.M, sh.N, sh.K, nullptr); });
+  B.head("\"output\": \"c16\", \"elem\": \"bf16\", \"config\": \"%s\", \"nn_config\": \"%s\", \"splits\": %d, \"runs\": %d, \"nn_runs\": %d", B.V.L->config_name(cfg),
+         hgemm_mi355x_nn_config_name(cfg), splits, B.V.runs_at(cfg, sh), bgemm_mi355x_nn_runs(cfg, sh.M, sh.N, sh.K, nn_lda, nn_ldb, sh.N));
+  B.verdict("tn_le_nn", 0, 1, true);
+}
+
+// tn --bf16 --bias: the planned bgemm_mi355x_tn_bias call, bgemm_mi355x_launch_tn with the same member and splits and no bias -- the
+// fused kernel adds 2 BN bytes of loads and 4 FM FN adds per lane to a tile --, and, context only, the path the call replaces:
+// bgemm_mi355x_tn followed by an element-wise bf16 add (its launch is not checked: the contender answers with the product's status).
+// The one condition: fused <= plain within the plain call's own round-to-round spread in this run: "bias_le_plain".
+static void bench_tn_bias(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh);
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), btb = B.to_bf16(B.of(&Buffers::bt), B.b_elems), cb = B.alloc(cn * 2),
+                        bias = B.alloc((size_t)sh.N * 2);
+  for (void* p : bias) fill_bias_kernel<<<64, 256>>>((__bf16*)p, sh.N);
+  const int add_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+  B.add("bias", [=](Buffers&, size_t i) { return bgemm_mi355x_tn_bias(ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, nullptr); });
+  B.add("plain", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn(cfg, splits, ab[i], btb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_tn(ab[i], btb[i], cb[i], sh.M, sh.N, sh.K, nullptr);
+    add_bias_kernel<<<add_grid, 256>>>((__bf16*)cb[i], (const __bf16*)bias[i], cn, sh.N);
+    return st;
+  });
+  B.head("\"output\": \"c16_bias\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("bias_le_plain", 0, 1, true);
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
     return 2;
   }
-  std::string mode = argv[1];
+  std::string mode = argv[1], layout;
   std::vector<Shape> shapes;
   const char* out_path = nullptr;
   const char* cfg_name = nullptr;
   double keep = 2.5;
   int max_cand = 12, splits = 1, group = 0, reps = 20;
-  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, layout_nn = false, layout_ta = false, layout_tn = false, c32 = false;
+  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, c32 = false, bf16 = false, bias = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -1656,13 +1506,12 @@ int main(int argc, char** argv) {
     else if (a == "--out") out_path = next();
     else if (a == "--autotune") autotune = true;
     else if (a == "--layout") {
-      const std::string l = next();
-      if (l != "nn" && l != "tn" && l != "ta") { fprintf(stderr, "--layout takes nn, ta or tn\n"); return 2; }
-      layout_nn = l == "nn"; layout_ta = l == "ta"; layout_tn = l == "tn";
+      layout = next();
+      if (layout != "nn" && layout != "tn" && layout != "ta") { fprintf(stderr, "--layout takes nn, ta or tn\n"); return 2; }
     }
     else if (a == "--c32") c32 = true;
-    else if (a == "--bf16") g_bf16 = true;
-    else if (a == "--bias") g_bias = true;
+    else if (a == "--bf16") bf16 = true;
+    else if (a == "--bias") bias = true;
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
     else if (a == "--streamk") g_streamk_too = true;
@@ -1707,6 +1556,17 @@ int main(int argc, char** argv) {
     else if (a == "--fill") g_zero_fill = (std::string(next()) == "zero");
     else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
+  // Which of the transposed-read variants, if any, the flags name -- and every refusal that follows from the flags alone, before a
+  // device is asked for.  nullptr: the fp16 b_col_major commands below (no --layout, or --layout tn without --bf16).
+  if (bias && !(bf16 && layout == "tn")) { fprintf(stderr, "--bias goes with --layout tn --bf16 (bgemm_mi355x_tn_bias)\n"); return 2; }
+  if (c32 && layout != "ta") { fprintf(stderr, "--c32 goes with --layout ta\n"); return 2; }
+  if (bf16 && layout.empty()) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
+  const Variant* variant = resolve_variant(layout, bf16, c32, bias);
+  if (variant && mode != "check" && mode != "bench") {
+    fprintf(stderr, "--layout %s%s goes with check or bench\n", layout.c_str(), variant->L->b_col_major ? " --bf16" : "");
+    return 2;
+  }
+  if (variant && mode == "bench" && shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
     fprintf(stderr, "hgemm_tune: no HIP device visible\n");
@@ -1717,38 +1577,7 @@ int main(int argc, char** argv) {
     HIP_OK(hipMalloc(&pad, g_pad_alloc_mib << 20));   // (kept until exit)
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
   }
-  if (g_bias && !(g_bf16 && layout_tn)) { fprintf(stderr, "--bias goes with --layout tn --bf16 (bgemm_mi355x_tn_bias)\n"); return 2; }
-  if (layout_ta) {   // family a: A given as [K][M] (hgemm_mi355x_launch_ta)
-    if (mode == "check") return c32 ? cmd_check_ta_c32(shapes) : cmd_check_nn(kLayoutTA, shapes);
-    if (mode == "bench") {
-      if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
-      if (g_bf16) return cmd_bench_bf16(kLayoutTA, c32, shapes, out_path);
-      return c32 ? cmd_bench_ta_c32(shapes, out_path) : cmd_bench_ta(shapes, out_path);
-    }
-    fprintf(stderr, "--layout ta goes with check or bench\n");
-    return 2;
-  }
-  if (c32) { fprintf(stderr, "--c32 goes with --layout ta\n"); return 2; }
-  if (layout_nn) {   // family n: B row-major (hgemm_mi355x_launch_nn); the default shapes of the check are cmd_check_nn's
-    if (mode == "check") return cmd_check_nn(kLayoutNN, shapes);
-    if (mode == "bench") {
-      if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
-      if (g_bf16) return cmd_bench_bf16(kLayoutNN, false, shapes, out_path);
-      return cmd_bench_nn(shapes, out_path, autotune);
-    }
-    fprintf(stderr, "--layout nn goes with check or bench\n");
-    return 2;
-  }
-  if (g_bf16 && layout_tn) {   // family f: the bf16 forward product (bgemm_mi355x_launch_tn); without --bf16, tn is the fp16 families below
-    if (mode == "check") return cmd_check_nn(kLayoutTN, shapes);
-    if (mode == "bench") {
-      if (shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
-      return g_bias ? cmd_bench_tn_bias(shapes, out_path) : cmd_bench_tn_bf16(shapes, out_path);
-    }
-    fprintf(stderr, "--layout tn --bf16 goes with check or bench\n");
-    return 2;
-  }
-  if (g_bf16) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
+  if (variant) return mode == "check" ? tr_check(*variant, shapes) : tr_bench(*variant, shapes, out_path, autotune);
   if (mode == "check") {
     if (shapes.empty())
       // (the last two: K tails -- 2104 = 32 x 64 + 56 = 8 x 256 + 56, 728 = 11 x 64 + 24 = 5 x 128 + 88 = 2 x 256 + 216: odd and even
