@@ -48,6 +48,7 @@ LIB_SOURCES = [
     "hgemm_inst_g10.hip",
     "hgemm_inst_g11.hip",
     "hgemm_inst_g12.hip",
+    "hgemm_inst_g13.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -920,6 +920,22 @@ int hgemm_mi355x_launch(int config_id, int splits_arg, int group_m, const void* 
   return HGEMM_OK;
 }
 
+// q256x256_w2x2's one-tile-per-workgroup kernel (hgemm_kernel_sq_one.hpp; switch, counter and selection rule: hgemm_inst_g13.hip)
+int hgemm_mi355x_set_one_item_kernel(int on) { return sq_one_set_enabled(on); }
+
+unsigned long long hgemm_mi355x_one_item_kernel_launches(void) { return sq_one_launch_count(); }
+
+int hgemm_mi355x_one_item_kernel_takes(int config_id, int splits, int group_m, int M, int N, int K, int lda, int ldb, int ldc) {
+  if (M <= 0 || N <= 0 || K <= 0 || config_id >= g_num_kernels || config_id < HGEMM_CONFIG_RAGGED) return HGEMM_ERR_BAD_ARG;
+  const LaunchPlan p = resolve_launch(config_id, splits, group_m, false, true, true, M, N, K, lda, ldb, ldc, 0);
+  if (p.status != HGEMM_OK) return p.status;
+  static const int q256 = hgemm_mi355x_config_by_name("q256x256_w2x2");
+  if (config_id != q256) return 0;
+  for (int i = 0; i < p.n; ++i)   // (the query's C is the null pointer: aligned)
+    if (p.d[i].thunk == THUNK_ENTRY && sq_one_takes(p.d[i].g, p.d[i].grid, p.d[i].epi)) return 1;
+  return 0;
+}
+
 int hgemm_mi355x_set_insitu(int enable) {
   const int old = insitu_enabled() ? 1 : 0;
   g_insitu_mode.store(enable ? 1 : 0);

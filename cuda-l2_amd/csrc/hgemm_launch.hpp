@@ -7,6 +7,8 @@
 
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 namespace hgemm_mi355x {
 
 // One thunk per geometry; `epi` selects the epilogue (EPI_C16 / EPI_SLAB / EPI_FUSED) or, for the classic and the
@@ -81,8 +83,19 @@ void launch_sq_variant(const GemmArgs& g, int grid, hipStream_t stream, int epi,
     HGEMM_LAUNCH((hgemm_tn_sq_kernel<CFG, SP_EPI_NARROW | FLAG>), grid, CFG::THREADS, stream, ts, g);
 }
 
+// q256x256_w2x2's one-tile-per-workgroup kernel (hgemm_kernel_sq_one.hpp), kernel and host side in hgemm_inst_g13.hip: launches it
+// and returns true when the launch is one it takes (sq_one_takes: plain wide epilogue, whole stages of K and at least three, no more
+// items than workgroups, no stagger / phase flags, the switch on), else does nothing.
+bool launch_sq_one(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts);
+bool sq_one_takes(const GemmArgs& g, int grid, int epi);
+int sq_one_set_enabled(int on);                 // the process-wide switch (hgemm_mi355x_set_one_item_kernel); returns the previous value
+unsigned long long sq_one_launch_count();       // launches of the kernel so far
+
 template <class CFG>
 void launch_sq(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if constexpr (std::is_same_v<CFG, CfgSQ<256, 256, 2, 2, 1, 16>>) {
+    if (launch_sq_one(g, grid, stream, epi, ts)) return;
+  }
   if constexpr (CFG::MI == 16) {   // (the 32x32x16 members have no K tail: the host never sends them a K that is not whole stages)
     if (g.K % (BK * CFG::KT) != 0) return launch_sq_variant<CFG, EPI_KTAIL>(g, grid, stream, epi, ts);
     // plan flag HGEMM_PLAN_XCD_STAGGER: whole stages only, the 16x16x32 members only

@@ -493,6 +493,7 @@ static int cmd_check(const std::vector<Shape>& shapes) {
   }
   // what this log covers, machine-readable (tests/test_evidence_consistency.py: a tuner result is only committed beside a
   // check log that names every geometry it times)
+  printf("one-item-kernel: %llu launches (q256x256_w2x2, --one-item 0 sends them to the general kernel)\n", hgemm_mi355x_one_item_kernel_launches());
   printf("check-configs:");
   for (int c = HGEMM_CONFIG_RAGGED; c < nc; ++c) {
     const char* cname = c >= 0 ? hgemm_mi355x_config_name(c) : (c == HGEMM_CONFIG_GENERIC ? "generic" : "ragged");
@@ -1554,6 +1555,9 @@ int main(int argc, char** argv) {
       hgemm_mi355x_set_debug(atoi(next()));
     }
     else if (a == "--fill") g_zero_fill = (std::string(next()) == "zero");
+    // q256x256_w2x2's one-tile-per-workgroup kernel (hgemm_mi355x_set_one_item_kernel): 0 = every launch runs the general kernel,
+    // 1 = the launches it takes run it (the library's default; a -DHGEMM_TIMELINE library needs the 1)
+    else if (a == "--one-item") hgemm_mi355x_set_one_item_kernel(atoi(next()));
     else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
   }
   // Which of the transposed-read variants, if any, the flags name -- and every refusal that follows from the flags alone, before a

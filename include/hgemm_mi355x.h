@@ -521,6 +521,23 @@ int hgemm_mi355x_time_next_launch(void* start_event, void* stop_event);
 /* Waits for stop_event, returns microseconds between the two events (negative on error). */
 double hgemm_mi355x_event_elapsed_us(void* start_event, void* stop_event);
 
+/* ---- the one-tile-per-workgroup kernel of q256x256_w2x2 ---------------------------------------------------------------------
+ * A launch of geometry q256x256_w2x2 in which every workgroup computes at most one output tile (4096^3: 256 tiles on 256
+ * workgroups) runs a kernel of its own, without the persistent item walk and without LDS-DMA behind the last K-step.  It is taken
+ * when ALL of these hold: plain fp16 epilogue (no split-K, no hybrid tail pass, no stream-K) in its wide form (N % 8 == 0,
+ * ldc % 8 == 0, C 16-byte aligned); K % 64 == 0 and K >= 192 (three K-steps: the depth of the kernel's operand streams); work items
+ * <= launched workgroups (at most 256 tiles); none of HGEMM_PLAN_RS_XCD_STAGGER, HGEMM_PLAN_PHASE_OFFSET, HGEMM_PLAN_PHASE_OFFSET4.
+ * Every other launch runs the general kernel.  C is bit-identical either way; plan, config id, flags, workspace are unchanged.
+ *
+ * hgemm_mi355x_set_one_item_kernel(on) is a process-wide switch (default on; off in a -DHGEMM_TIMELINE measurement build) and
+ * returns the previous value, so tests and A/B timing run both kernels from one library.
+ * hgemm_mi355x_one_item_kernel_launches() counts the launches of the kernel since the library was loaded.
+ * hgemm_mi355x_one_item_kernel_takes() answers, without a GPU, whether hgemm_mi355x_launch with these arguments (b_col_major given,
+ * all pointers 16-byte aligned) would run it under the current switch: 1 / 0, negative status for arguments the launch rejects. */
+int hgemm_mi355x_set_one_item_kernel(int on);
+unsigned long long hgemm_mi355x_one_item_kernel_launches(void);
+int hgemm_mi355x_one_item_kernel_takes(int config_id, int splits, int group_m, int M, int N, int K, int lda, int ldb, int ldc);
+
 #ifdef __cplusplus
 }
 #endif
