@@ -26,8 +26,7 @@ unsigned long long sq_one_launch_count() { return g_sq_one_launches.load(); }
 // The launches hgemm_tn_sq_one_kernel takes, of those launch_sq<CfgSQOne> is handed (`g` as resolve_launch made it, C set):
 bool sq_one_takes(const GemmArgs& g, int grid, int epi) {
   if (!g_sq_one_on.load(std::memory_order_relaxed)) return false;
-  const bool wide = ((g.N & 7) == 0) && ((g.ldc & 7) == 0) && ((reinterpret_cast<uintptr_t>(g.C) & 15) == 0);
-  if (epi != EPI_C16 || !wide) return false;                                         // the plain wide fp16 epilogue
+  if (epi != EPI_C16 || !c_takes_wide_stores(g)) return false;                       // the plain wide fp16 epilogue
   if (g.K % (BK * CfgSQOne::KT) != 0 || g.K / BK < SQ_ONE_MIN_STEPS) return false;   // whole stages, at least the streams' depth
   if (g.splits != 1 || g.tail_tiles != 0 || g.items > grid) return false;            // one whole-K work item per workgroup at most
   if (g.flags & (ARG_XCD_STAGGER | ARG_PHASE_OFFSET | ARG_PHASE_OFFSET4)) return false;

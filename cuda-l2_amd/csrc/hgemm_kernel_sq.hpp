@@ -104,6 +104,8 @@ struct CfgSQ : Cfg<BM_, BN_, WM_, WN_, MI_, 2> {
   static constexpr int WGS = (2 * LDS_BYTES <= 160 * 1024) ? 2 : 1;
   static constexpr int AGPRS = WGS == 2 ? Base::FM * Base::FN * ACC : 256;
 };
+// q256x256_w2x2, the headline plan: the member that also has a one-tile-per-workgroup kernel (hgemm_kernel_sq_one.hpp; launch_sq)
+using CfgSQOne = CfgSQ<256, 256, 2, 2, 1, 16>;
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // The slot plan of an interval: which MFMA slot carries which LDS-DMA piece and which trailing fragment read.
@@ -263,7 +265,14 @@ constexpr int kWaitLgkm0 = 0xC07F;   // s_waitcnt lgkmcnt(0) as the builtin's im
 // front of the next interval's MFMAs; (c) the sync point's vmcnt wait sits one gap ahead of the lgkmcnt wait + barrier.  The
 // vendor kernel's loop has the same one-instruction-per-gap shape.
 // Fragment read r of a set: slice r / F reads from src0 / src1, row block r % F.
-template <class CFG, int PHASE>
+// The parts of an interval are compile-time switches; the defaults are the steady state (SQ_K_STEP).  A kernel that writes its
+// last K-steps out (hgemm_kernel_sq_one.hpp) turns off what belongs to tiles that do not exist:
+//   LATE / EARLY  issue the late / early LDS-DMA pieces of the slot plan
+//   VMW           vmcnt count of the sync point's wait = the pieces YOUNGER than the half-tile that must have landed (the stream
+//                 order is A(t+1), B(t+1), A(t+2), B(t+2), ...: two younger half-tiles in the steady state); < 0: no wait
+//   NEXT          a next tile exists: the sync point and the trailing reads (and, in interval B, the leading reads, which belong
+//                 to the next tile; interval A's leading reads are the current tile's slice-1 B fragments and always happen)
+template <class CFG, int PHASE, bool LATE = true, bool EARLY = true, int VMW = CFG::NJA + CFG::NJB, bool NEXT = true>
 __device__ __forceinline__ void sq_interval(const f16x8 (&af)[CFG::NFA], const f16x8 (&bf)[CFG::NFB],
                                             f16x8 (&lead)[PHASE == 0 ? CFG::NFB : CFG::NFA], const char* lead0, const char* lead1,
                                             f16x8 (&trail)[PHASE == 0 ? CFG::NFA : CFG::NFB], const char* trail0, const char* trail1,
@@ -275,13 +284,14 @@ __device__ __forceinline__ void sq_interval(const f16x8 (&af)[CFG::NFA], const f
   constexpr int OP_E = PHASE == 0 ? 1 : 0, OP_L = PHASE == 0 ? 0 : 1;          // operand of the early / late pieces
   constexpr int D_L = PHASE == 0 ? CFG::DA : CFG::DB;                          // late pieces are D_L .. NJ_op - 1 of their half-tile
   constexpr int S = PHASE == 0 ? CFG::P : CFG::Q;
+  constexpr bool LEAD = PHASE == 0 || NEXT;
   // LDS byte address of this wave's first 1-KiB block of the destination stages (M0 = this + a constant per piece)
   const uint32_t lds_l = (uint32_t)(uintptr_t)(lds_void_t*)stage_l + (uint32_t)wave * 1024u;
   const uint32_t lds_e = (uint32_t)(uintptr_t)(lds_void_t*)stage_e + (uint32_t)wave * 1024u;
 #pragma unroll
   for (int n = 0; n < T; ++n) {
     const int u = n / (FM * FN), i = (n / FN) % FM, j = n % FN;   // MFMA k-slice, accumulator tile (i, j)
-    if (n == S) {
+    if (NEXT && n == S) {
       // every fragment read of the region about to be refilled has RETURNED (LDS returns in order, and the leading reads
       // were the last ones issued), and my pieces of the half-tile the trailing reads are about to consume have landed (the
       // vmcnt wait went out one gap earlier; two younger half-tiles may stay in flight)
@@ -290,21 +300,22 @@ __device__ __forceinline__ void sq_interval(const f16x8 (&af)[CFG::NFA], const f
       if (!(HGEMM_SQ_ABL & 1)) sp_sync();
     }
     sp_mfma_mi<CFG::MI>(i * FN + j, bf[u * FN + j], af[u * FM + i]);
-    if (!(HGEMM_SQ_ABL & 16) && n % RS == 0 && n / RS < NLEAD) {
+    if (LEAD && !(HGEMM_SQ_ABL & 16) && n % RS == 0 && n / RS < NLEAD) {
       const int r = n / RS;
       lead[r] = *(const f16x8*)((r / FLEAD ? lead1 : lead0) + (r % FLEAD) * CFG::MI * ROW_BYTES);
     }
     // gap n (behind MFMA n): at most one memory instruction besides a leading read; the M0 write of a piece one gap early
     constexpr SqSlots<CFG, PHASE> tab{};
-    const int l = (HGEMM_SQ_ABL & 8) ? -1 : tab.late[n], l1 = (HGEMM_SQ_ABL & 8) ? -1 : tab.late[n + 1];
-    const int e = (HGEMM_SQ_ABL & 8) ? -1 : tab.early[n], e1 = (HGEMM_SQ_ABL & 8) ? -1 : tab.early[n + 1];
-    const int r = (HGEMM_SQ_ABL & 16) ? -1 : tab.trail[n];
+    constexpr bool late = LATE && !(HGEMM_SQ_ABL & 8), early = EARLY && !(HGEMM_SQ_ABL & 8);
+    const int l = late ? tab.late[n] : -1, l1 = late ? tab.late[n + 1] : -1;
+    const int e = early ? tab.early[n] : -1, e1 = early ? tab.early[n + 1] : -1;
+    const int r = (NEXT && !(HGEMM_SQ_ABL & 16)) ? tab.trail[n] : -1;
     if (l >= 0) { if constexpr (OP_L == 0) sq_piece_load<CFG, 0>(rs_l, voffA, D_L + l, kbyte_l); else sq_piece_load<CFG, 1>(rs_l, voffB, D_L + l, kbyte_l); }
     if (e >= 0) { if constexpr (OP_E == 0) sq_piece_load<CFG, 0>(rs_e, voffA, e, kbyte_e); else sq_piece_load<CFG, 1>(rs_e, voffB, e, kbyte_e); }
     if (r >= 0) trail[r] = *(const f16x8*)((r / FTRAIL ? trail1 : trail0) + (r % FTRAIL) * CFG::MI * ROW_BYTES);
     if (l1 >= 0) sq_piece_m0<CFG, OP_L>(lds_l, D_L + l1, l1 > 0);
     if (e1 >= 0) sq_piece_m0<CFG, OP_E>(lds_e, e1, e1 > 0);
-    if (n == S - 2 && !(HGEMM_SQ_ABL & 2)) wait_vmcnt<CFG::NJA + CFG::NJB>();
+    if constexpr (VMW >= 0) { if (NEXT && n == S - 2 && !(HGEMM_SQ_ABL & 2)) wait_vmcnt<VMW>(); }
     if (n == T - 3) {   // every read of this interval has long returned: from here on the compiler knows it, too
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
@@ -312,6 +323,26 @@ __device__ __forceinline__ void sq_interval(const f16x8 (&af)[CFG::NFA], const f
     }
   }
 }
+
+// ---- what surrounds the K-steps, shared by hgemm_tn_sq_kernel and hgemm_tn_sq_one_kernel (hgemm_kernel_sq_one.hpp) ----------------
+
+#ifdef HGEMM_TIMELINE
+// The measurement build's record of a workgroup (thread 0 writes it).  Words 0..7 (stamps at `tl`): entry, entry (100 MHz clock),
+// pipeline primed, last item's loop start, its last MFMA, its last store issued, everything acknowledged, exit (100 MHz clock);
+// 8: XCC id << 32 | HW_ID; 9: K-steps walked; 10: work items; 11..13 (stamps at `tl_head`): the head split.
+__device__ __forceinline__ void sq_timeline_record(const GemmArgs& g, const char* tl, const char* tl_head, int step, int items, int tid) {
+  if (g.timeline != nullptr && tid == 0) {
+    unsigned long long* out = g.timeline + (size_t)blockIdx.x * HGEMM_TL_WORDS;
+    unsigned hw = 0, xcc = 0;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
+#pragma unroll
+    for (int w = 0; w < 8; ++w) out[w] = hgemm_tl_get(tl, w);
+#pragma unroll
+    for (int w = 0; w < 3; ++w) out[11 + w] = hgemm_tl_get(tl_head, w);
+    out[8] = ((unsigned long long)xcc << 32) | hw; out[9] = (unsigned long long)step; out[10] = (unsigned long long)items;
+  }
+}
+#endif
 #endif  // __HIP_DEVICE_COMPILE__
 
 // One operand's LDS-DMA stream cursor: descriptor of the current work item's tile rows and the K position inside it.
@@ -748,18 +779,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_sq_kernel(const GemmArg
 #ifdef HGEMM_TIMELINE
   HGEMM_TL_STAMP(smem + CFG::LDS_BYTES, 6, tid);
   HGEMM_TL_REALTIME(smem + CFG::LDS_BYTES, 7, tid);
-  if (g.timeline != nullptr && tid == 0) {
-    // words 0..7: entry, entry (100 MHz clock), pipeline primed, last item's loop start, its last MFMA, its last store
-    // issued, everything acknowledged, exit (100 MHz clock); 8: XCC id << 32 | HW_ID; 9: K-steps walked; 10: work items
-    unsigned long long* tl = g.timeline + (size_t)blockIdx.x * HGEMM_TL_WORDS;
-    unsigned hw = 0, xcc = 0;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
-#pragma unroll
-    for (int w = 0; w < 8; ++w) tl[w] = hgemm_tl_get(smem + CFG::LDS_BYTES, w);
-#pragma unroll
-    for (int w = 0; w < 3; ++w) tl[11 + w] = hgemm_tl_get(smem + CFG::LDS_BYTES + 64 + STAGED_BYTES, w);   // 11..13: head split
-    tl[8] = ((unsigned long long)xcc << 32) | hw; tl[9] = (unsigned long long)step; tl[10] = (unsigned long long)walk.count;
-  }
+  sq_timeline_record(g, smem + CFG::LDS_BYTES, smem + CFG::LDS_BYTES + 64 + STAGED_BYTES, step, walk.count, tid);
 #endif
 #endif  // __HIP_DEVICE_COMPILE__
 }

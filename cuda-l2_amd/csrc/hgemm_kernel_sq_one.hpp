@@ -4,8 +4,15 @@
 // hgemm_tn_sq_kernel is the general persistent kernel: its two LDS-DMA streams cross work-item seams (cursors, SQ_LOAD_ITEM), its
 // accumulators are re-zeroed per item, and past the last K-step of the last item its branch-free DMA keeps issuing pieces of a tile
 // nobody consumes.  With one item per workgroup none of that is needed.  This kernel keeps the steady-state K-step (the interval
-// plan SqPlan / SqSlots, the fragment sets, the sync points: sq1_interval below is sq_interval with compile-time switches) and
-// changes what surrounds it:
+// plan SqPlan / SqSlots, the fragment sets, the sync points) and changes what surrounds it.  The interval is the general kernel's
+// text: sq_interval (hgemm_kernel_sq.hpp), whose parts -- late pieces, early pieces, the sync point's vmcnt count, "a next tile
+// exists" -- are compile-time switches that default to the steady state; their meaning and the "younger pieces" rule for the vmcnt
+// count are described there, the HGEMM_SQ_ABL ablations reach this kernel through it, and the HGEMM_TIMELINE record is the shared
+// sq_timeline_record.  What this header holds is its own: the K-step macro that names the switches, the peeled-tail schedule, the
+// kernel's control flow.  (The lane offsets, the descriptors, the prologue and the first fragment reads are the same statements as
+// in hgemm_tn_sq_kernel and still written out in both: as shared functions they moved instructions in this kernel or in the general
+// ones -- DESIGN.md section 4.27.)
+//
 //
 //   1. No item walk.  The tile coordinates and the two descriptors are computed once; a stream position is one scalar byte offset.
 //   2. Peeled tail.  The A stream runs three tiles ahead of the MFMAs and the B stream two, so the last three K-steps are written
@@ -34,61 +41,7 @@
 
 namespace hgemm_mi355x {
 
-using CfgSQOne = CfgSQ<256, 256, 2, 2, 1, 16>;
 constexpr int SQ_ONE_MIN_STEPS = 3;   // K-steps (K = 64 each) the kernel needs: the A stream's depth (see above)
-
-#if defined(__HIP_DEVICE_COMPILE__)
-// sq_interval (hgemm_kernel_sq.hpp) with the parts of an interval as compile-time switches:
-//   LATE / EARLY  issue the late / early LDS-DMA pieces of the slot plan
-//   VMW           vmcnt count of the sync point's wait (pieces younger than the half-tile that must have landed); < 0: no wait
-//   NEXT          a next tile exists: the sync point and the trailing reads (and, in interval B, the leading reads, which belong
-//                 to the next tile; interval A's leading reads are the current tile's slice-1 B fragments and always happen)
-template <class CFG, int PHASE, bool LATE, bool EARLY, int VMW, bool NEXT>
-__device__ __forceinline__ void sq1_interval(const f16x8 (&af)[CFG::NFA], const f16x8 (&bf)[CFG::NFB],
-                                             f16x8 (&lead)[PHASE == 0 ? CFG::NFB : CFG::NFA], const char* lead0, const char* lead1,
-                                             f16x8 (&trail)[PHASE == 0 ? CFG::NFA : CFG::NFB], const char* trail0, const char* trail1,
-                                             int wave, const uint32_t (&voffA)[CFG::PA], const uint32_t (&voffB)[CFG::PB],
-                                             __amdgpu_buffer_rsrc_t rs_l, char* stage_l, uint32_t kbyte_l,
-                                             __amdgpu_buffer_rsrc_t rs_e, char* stage_e, uint32_t kbyte_e) {
-  constexpr int FM = CFG::FM, FN = CFG::FN, T = CFG::T, RS = CFG::RS;
-  constexpr int NLEAD = PHASE == 0 ? CFG::NFB : CFG::NFA, FLEAD = PHASE == 0 ? FN : FM, FTRAIL = PHASE == 0 ? FM : FN;
-  constexpr int OP_E = PHASE == 0 ? 1 : 0, OP_L = PHASE == 0 ? 0 : 1;
-  constexpr int D_L = PHASE == 0 ? CFG::DA : CFG::DB;
-  constexpr int S = PHASE == 0 ? CFG::P : CFG::Q;
-  constexpr bool LEAD = PHASE == 0 || NEXT;
-  const uint32_t lds_l = (uint32_t)(uintptr_t)(lds_void_t*)stage_l + (uint32_t)wave * 1024u;
-  const uint32_t lds_e = (uint32_t)(uintptr_t)(lds_void_t*)stage_e + (uint32_t)wave * 1024u;
-#pragma unroll
-  for (int n = 0; n < T; ++n) {
-    const int u = n / (FM * FN), i = (n / FN) % FM, j = n % FN;
-    if (NEXT && n == S) {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-      sp_sync();
-    }
-    sp_mfma_mi<CFG::MI>(i * FN + j, bf[u * FN + j], af[u * FM + i]);
-    if (LEAD && n % RS == 0 && n / RS < NLEAD) {
-      const int r = n / RS;
-      lead[r] = *(const f16x8*)((r / FLEAD ? lead1 : lead0) + (r % FLEAD) * CFG::MI * ROW_BYTES);
-    }
-    constexpr SqSlots<CFG, PHASE> tab{};
-    const int l = LATE ? tab.late[n] : -1, l1 = LATE ? tab.late[n + 1] : -1;
-    const int e = EARLY ? tab.early[n] : -1, e1 = EARLY ? tab.early[n + 1] : -1;
-    const int r = NEXT ? tab.trail[n] : -1;
-    if (l >= 0) { if constexpr (OP_L == 0) sq_piece_load<CFG, 0>(rs_l, voffA, D_L + l, kbyte_l); else sq_piece_load<CFG, 1>(rs_l, voffB, D_L + l, kbyte_l); }
-    if (e >= 0) { if constexpr (OP_E == 0) sq_piece_load<CFG, 0>(rs_e, voffA, e, kbyte_e); else sq_piece_load<CFG, 1>(rs_e, voffB, e, kbyte_e); }
-    if (r >= 0) trail[r] = *(const f16x8*)((r / FTRAIL ? trail1 : trail0) + (r % FTRAIL) * CFG::MI * ROW_BYTES);
-    if (l1 >= 0) sq_piece_m0<CFG, OP_L>(lds_l, D_L + l1, l1 > 0);
-    if (e1 >= 0) sq_piece_m0<CFG, OP_E>(lds_e, e1, e1 > 0);
-    if constexpr (VMW >= 0) { if (NEXT && n == S - 2) wait_vmcnt<VMW>(); }
-    if (n == T - 3) {
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-#endif  // __HIP_DEVICE_COMPILE__
 
 // Fragment source of interval h (K = 32 half h of the stage image), this lane's row and swizzled chunk (KT = 1, MI = 16)
 #define SQ1_FRAG(STAGE, OPOFF, H) ((STAGE) + (OPOFF) + foff[H])
@@ -99,13 +52,13 @@ __device__ __forceinline__ void sq1_interval(const f16x8 (&af)[CFG::NFA], const 
   do {                                                                                                                  \
     char* st  = smem + (step & 1) * CFG::STAGE_BYTES;                                                                   \
     char* nst = smem + ((step + 1) & 1) * CFG::STAGE_BYTES;                                                             \
-    sq1_interval<CFG, 0, LA, EB, VMP, NEXT>(fX, fU, fV, SQ1_FRAG(st, b_base_off, 1), SQ1_FRAG(st, b_base_off, 1),       \
-                                            ZS, SQ1_FRAG(nst, a_base_off, 1), SQ1_FRAG(nst, a_base_off, 1), wave, voffA, voffB, \
-                                            rsA, st, kbA, rsB, st, kbB);                                                \
+    sq_interval<CFG, 0, LA, EB, VMP, NEXT>(fX, fU, fV, SQ1_FRAG(st, b_base_off, 1), SQ1_FRAG(st, b_base_off, 1),        \
+                                           ZS, SQ1_FRAG(nst, a_base_off, 1), SQ1_FRAG(nst, a_base_off, 1), wave, voffA, voffB, \
+                                           rsA, st, kbA, rsB, st, kbB);                                                 \
     kbA += ROW_BYTES;                                                                                                   \
-    sq1_interval<CFG, 1, LB, EA, VMQ, NEXT>(YS, fV, fX, SQ1_FRAG(nst, a_base_off, 0), SQ1_FRAG(nst, a_base_off, 0),     \
-                                            fU, SQ1_FRAG(nst, b_base_off, 0), SQ1_FRAG(nst, b_base_off, 0), wave, voffA, voffB, \
-                                            rsB, st, kbB, rsA, nst, kbA);                                               \
+    sq_interval<CFG, 1, LB, EA, VMQ, NEXT>(YS, fV, fX, SQ1_FRAG(nst, a_base_off, 0), SQ1_FRAG(nst, a_base_off, 0),      \
+                                           fU, SQ1_FRAG(nst, b_base_off, 0), SQ1_FRAG(nst, b_base_off, 0), wave, voffA, voffB, \
+                                           rsB, st, kbB, rsA, nst, kbA);                                                \
     kbB += ROW_BYTES;                                                                                                   \
     ++step;                                                                                                             \
   } while (0)
@@ -254,16 +207,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_sq_one_kernel(const Gem
   wait_vmcnt<0>();
   HGEMM_TL_STAMP(smem + CFG::LDS_BYTES, 6, tid);
   HGEMM_TL_REALTIME(smem + CFG::LDS_BYTES, 7, tid);
-  if (g.timeline != nullptr && tid == 0) {   // the words of hgemm_tn_sq_kernel's record
-    unsigned long long* tl = g.timeline + (size_t)blockIdx.x * HGEMM_TL_WORDS;
-    unsigned hw = 0, xcc = 0;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw), "=s"(xcc));
-#pragma unroll
-    for (int w = 0; w < 8; ++w) tl[w] = hgemm_tl_get(smem + CFG::LDS_BYTES, w);
-#pragma unroll
-    for (int w = 0; w < 3; ++w) tl[11 + w] = hgemm_tl_get(smem + CFG::LDS_BYTES + 64 + STAGED_BYTES, w);
-    tl[8] = ((unsigned long long)xcc << 32) | hw; tl[9] = (unsigned long long)step; tl[10] = 1ull;
-  }
+  sq_timeline_record(g, smem + CFG::LDS_BYTES, smem + CFG::LDS_BYTES + 64 + STAGED_BYTES, step, 1, tid);
 #endif
 #endif  // __HIP_DEVICE_COMPILE__
 }

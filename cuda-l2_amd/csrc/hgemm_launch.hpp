@@ -56,9 +56,15 @@ void launch_cfg(const GemmArgs& g, int grid, hipStream_t stream, int epi, Timing
     HGEMM_LAUNCH((hgemm_tn_kernel<CFG, EPI_C16>), grid, CFG::THREADS, stream, ts, g);
 }
 
+// The plain fp16 epilogue has a wide form (16-byte stores of eight C elements): every row of C must start 16-byte aligned and
+// hold whole groups of eight.
+inline bool c_takes_wide_stores(const GemmArgs& g) {
+  return ((g.N & 7) == 0) && ((g.ldc & 7) == 0) && ((reinterpret_cast<uintptr_t>(g.C) & 15) == 0);
+}
+
 template <class CFG>
 void launch_sp(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  const bool wide = ((g.N & 7) == 0) && ((g.ldc & 7) == 0) && ((reinterpret_cast<uintptr_t>(g.C) & 15) == 0);
+  const bool wide = c_takes_wide_stores(g);
   if (epi == EPI_FUSED)
     HGEMM_LAUNCH((hgemm_tn_sp_kernel<CFG, SP_EPI_FUSED>), grid, CFG::THREADS, stream, ts, g);
   else if (epi == EPI_SLAB)
@@ -72,7 +78,7 @@ void launch_sp(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingS
 // FLAG = 0, or EPI_KTAIL for the "ktail" variants (whole stages through the pipeline + a direct tail: hgemm_kernel_sq.hpp / _rs.hpp)
 template <class CFG, int FLAG>
 void launch_sq_variant(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  const bool wide = ((g.N & 7) == 0) && ((g.ldc & 7) == 0) && ((reinterpret_cast<uintptr_t>(g.C) & 15) == 0);
+  const bool wide = c_takes_wide_stores(g);
   if (epi == EPI_FUSED)
     HGEMM_LAUNCH((hgemm_tn_sq_kernel<CFG, SP_EPI_FUSED | FLAG>), grid, CFG::THREADS, stream, ts, g);
   else if (epi == EPI_SLAB)
@@ -93,7 +99,7 @@ unsigned long long sq_one_launch_count();       // launches of the kernel so far
 
 template <class CFG>
 void launch_sq(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  if constexpr (std::is_same_v<CFG, CfgSQ<256, 256, 2, 2, 1, 16>>) {
+  if constexpr (std::is_same_v<CFG, CfgSQOne>) {
     if (launch_sq_one(g, grid, stream, epi, ts)) return;
   }
   if constexpr (CFG::MI == 16) {   // (the 32x32x16 members have no K tail: the host never sends them a K that is not whole stages)

@@ -1,11 +1,14 @@
 """Per-kernel fingerprints of the device code (gfx950 ISA as hipcc -S prints it), so a later change to the sources can show
 which kernels' instruction streams it touched -- and therefore which committed measurements still describe the library.
 
-    python tools/isa_fingerprint.py [--csrc DIR --include DIR] > profiles/<name>.json        (no GPU; ~20 s, four hipcc in parallel)
+    python tools/isa_fingerprint.py [--csrc DIR --include DIR] > profiles/<name>.json        (no GPU; ~20 s, one hipcc per unit in parallel)
+    python tools/isa_fingerprint.py --units 13 > profiles/sq_one_isa_fingerprint.json         (the one-tile kernel's unit)
+    python tools/isa_fingerprint.py --units 0 1 2 3 13 --opt -O2 --flag=-DHGEMM_TIMELINE      (another build of the same sources)
 
 A kernel's fingerprint is the sha256 of its function body between the label and s_endpgm with comments, assembler directives
 and basic-block label NUMBERS stripped (labels are numbered per translation unit: adding a kernel renumbers them all).
-tests/test_build_audit.py compares the current sources with profiles/r04_isa_fingerprint_closing_run_library.json.
+tests/test_build_audit.py compares units 0-3 of the current sources with profiles/r0{4,5,6}_isa_fingerprint_*_library.json,
+tests/test_sq_one_build.py unit 13 with profiles/sq_one_isa_fingerprint.json.
 """
 import argparse
 import hashlib
@@ -19,15 +22,17 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parents[1]
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+DEFAULT_UNITS = (0, 1, 2, 3)
 
 
-def compile_groups(csrc: Path, include: Path, opt: str = "-O3") -> str:
-    """hipcc -S --cuda-device-only of the four instantiation units (the flags of tests/test_build_audit.py); returns the text."""
+def compile_groups(csrc: Path, include: Path, opt: str = "-O3", units=DEFAULT_UNITS, flags=()) -> str:
+    """hipcc -S --cuda-device-only of the instantiation units hgemm_inst_g<unit>.hip (the flags of tests/test_build_audit.py, plus
+    `flags`); returns the text."""
     with tempfile.TemporaryDirectory() as tmp:
         procs = []
-        for grp in range(4):
+        for grp in units:
             out = Path(tmp) / f"g{grp}.s"
-            procs.append((out, subprocess.Popen([HIPCC, "--offload-arch=gfx950", opt, "-std=c++17", f"-I{csrc}", f"-I{include}", "-S", "--cuda-device-only",
+            procs.append((out, subprocess.Popen([HIPCC, "--offload-arch=gfx950", opt, "-std=c++17", *flags, f"-I{csrc}", f"-I{include}", "-S", "--cuda-device-only",
                                                  str(csrc / f"hgemm_inst_g{grp}.hip"), "-o", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE)))
         text = ""
         for out, pr in procs:
@@ -56,9 +61,14 @@ def main():
     ap.add_argument("--csrc", default=str(PKG / "csrc"))
     ap.add_argument("--include", default=str(PKG.parent / "include"))
     ap.add_argument("--note", default="")
+    ap.add_argument("--units", type=int, nargs="+", default=list(DEFAULT_UNITS), help="instantiation units hgemm_inst_g<N>.hip (default: 0 1 2 3)")
+    ap.add_argument("--opt", default="-O3", help="optimisation level (default: -O3)")
+    ap.add_argument("--flag", action="append", default=[], help="extra compiler flag, repeatable: --flag=-DHGEMM_TIMELINE")
     a = ap.parse_args()
-    fp = fingerprints(compile_groups(Path(a.csrc), Path(a.include)))
-    json.dump({"note": a.note, "flags": "hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only hgemm_inst_g{0..3}.hip", "kernels": fp}, sys.stdout, indent=1)
+    fp = fingerprints(compile_groups(Path(a.csrc), Path(a.include), a.opt, a.units, a.flag))
+    units = "{" + ",".join(str(u) for u in a.units) + "}" if a.units != list(DEFAULT_UNITS) else "{0..3}"
+    flags = " ".join(["hipcc --offload-arch=gfx950", a.opt, "-std=c++17", *a.flag, "-S --cuda-device-only", f"hgemm_inst_g{units}.hip"])
+    json.dump({"note": a.note, "flags": flags, "kernels": fp}, sys.stdout, indent=1)
     print()
 
 

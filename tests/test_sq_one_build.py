@@ -98,6 +98,21 @@ def test_the_peeled_tail_issues_no_piece_behind_the_last_real_one(one_kernel):
     assert not [c for c in codes[mfma[-1]:] if c.startswith("s_waitcnt vmcnt(0)")], "the kernel waits for its stores"
 
 
+def test_the_kernel_keeps_the_instruction_stream_that_was_measured(one_kernel):
+    """profiles/sq_one_isa_fingerprint.json is unit g13 as the commit that added the kernel compiled it: the kernel of
+    profiles/sq_one_bench_*.jsonl and profiles/sq_one_check_q256x256.log.  Its K-steps are instantiations of sq_interval, shared
+    with every kernel of family q (hgemm_kernel_sq.hpp): a change there shows here as well as in test_build_audit's 348 kernels."""
+    import json
+    import sys
+
+    sys.path.insert(0, str(REPO / "cuda-l2_amd" / "tools"))
+    import isa_fingerprint
+
+    name, *_, text = one_kernel
+    recorded = json.loads((REPO / "profiles" / "sq_one_isa_fingerprint.json").read_text())["kernels"]
+    assert isa_fingerprint.fingerprints(text) == recorded and list(recorded) == [name]
+
+
 @pytest.mark.parametrize("grp", [0, 1, 2, 3])
 def test_the_fingerprinted_units_hold_no_symbol_of_the_kernel(tmp_path_factory, grp):
     if not Path(HIPCC).exists():
