@@ -49,6 +49,7 @@ LIB_SOURCES = [
     "hgemm_inst_g11.hip",
     "hgemm_inst_g12.hip",
     "hgemm_inst_g13.hip",
+    "hgemm_inst_g14.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

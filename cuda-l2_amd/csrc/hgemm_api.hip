@@ -4,6 +4,7 @@
 // (benchmarking_utils.py:23-31), so a lean host path is part of the hot path.
 #include "hgemm_plan.hpp"
 #include "hgemm_kernel_nn.hpp"
+#include "hgemm_act.hpp"
 #include "../../include/hgemm_mi355x.h"
 
 #include <algorithm>
@@ -475,14 +476,23 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // added into what C holds.  ldc counts C's own elements.
 // bias (bgemm_mi355x_tn_bias, family f only): a 16-bit C with a bf16 bias vector fused into the epilogue -- C = T(sum + float(bias[n])), the
 // bias added last and the sum rounded once.  The third output kind: the same tiles, cuts and slabs as the plain 16-bit C.
+// act (bgemm_mi355x_tn_bias_act, with bias only): an activation of hgemm_act.hpp behind the bias add -- C = T(act(sum + float(bias[n]))),
+// applied to the unrounded fp32 value, never to a slab, the result rounded once.  One more kind per activation, TR_C16_BIAS + act; the
+// epilogue ids follow suit, EPI_C16_BIAS + act.
 struct TrOut {
   bool c32, accumulate;
   bool bias = false;
+  int act = 0;   // 0 (none) or HGEMM_ACT_RELU / _GELU / _GELU_TANH = 1 / 2 / 3
   int elem_bytes() const { return c32 ? 4 : 2; }
-  TrKind kind() const { return bias ? TR_C16_BIAS : c32 ? TR_C32 : TR_C16; }   // the kernel set's cell in TrRow / TrTable
+  TrKind kind() const { return bias ? (TrKind)(TR_C16_BIAS + act) : c32 ? TR_C32 : TR_C16; }   // the kernel set's cell in TrRow / TrTable
+  int epi_bias() const { return EPI_C16_BIAS + act; }   // the epilogue id of the plain dispatch and of the combine dispatch of a bias kind
 };
 constexpr TrOut kOutC16{false, false};
 constexpr TrOut kOutC16Bias{false, false, true};
+static_assert(HGEMM_ACT_RELU == ACT_RELU && HGEMM_ACT_GELU == ACT_GELU && HGEMM_ACT_GELU_TANH == ACT_GELU_TANH, "the public ids are hgemm_act.hpp's");
+static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIAS_GELU_TANH + 1 == TR_KINDS, "a kind per activation");
+constexpr bool act_known(int act) { return act == HGEMM_ACT_RELU || act == HGEMM_ACT_GELU || act == HGEMM_ACT_GELU_TANH; }
+constexpr TrOut out_bias_act(int act) { return TrOut{false, false, true, act}; }   // (act_known(act) checked by the caller)
 
 // What the operands and a 16-bit C hold (TrElem): fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements
 // are 2 bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  (TrElem, c32) selects a kernel set and nothing
@@ -528,7 +538,8 @@ const TrLayout kLayoutTN{tr_table_tn(), false, true, TR_BF16};   // the bf16 for
 // out.c32: the same tiles, cuts and slabs; the plain dispatch and the combine carry EPI_C32 (the K slices are the family's EPI_SLAB
 // kernels), the least ldc is still N
 // out.bias: the plan of the plain 16-bit call in everything but the epi of the plain dispatch and of the combine dispatch, EPI_C16_BIAS;
-// the bias pointer is no input (its alignment arrives in `aligned`, as the operands' does)
+// the bias pointer is no input (its alignment arrives in `aligned`, as the operands' does).  out.act: the same again with
+// EPI_C16_BIAS + act in those two dispatches.
 LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
                       unsigned ruled_out) {
   LaunchPlan p;
@@ -541,7 +552,7 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
   // stride of b_col_major (f); ldc >= N
   if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < L.b_row(N, K) || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
   if (!L.t.kernels[elem][out.kind()].reference || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no such kernel set in this layout
-  const int epi_out = out.c32 ? EPI_C32 : out.bias ? EPI_C16_BIAS : EPI_C16;
+  const int epi_out = out.c32 ? EPI_C32 : out.bias ? out.epi_bias() : EPI_C16;
   const TrEntry& e = L.t.rows[config].e;
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -570,7 +581,7 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
     p.form = FORM_SPLITK;
     p.slab_bytes = (size_t)splits * M * N * sizeof(float);
     add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
-    add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : out.bias ? EPI_C16_BIAS : EPI_SLAB);
+    add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : out.bias ? out.epi_bias() : EPI_SLAB);
   } else {
     add(THUNK_ENTRY, g, tiles, epi_out);
   }
@@ -634,7 +645,7 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
     GemmArgs& g = p.d[i].g;
     g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (bf16 travels in the same fields: the kernels of its Cfgs reinterpret)
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
-    if (p.d[i].epi == EPI_C16_BIAS) g.counters = (unsigned*)const_cast<void*>(bias);   // read-only there: the kernel's bf16 bias vector
+    if (out.bias && p.d[i].epi == out.epi_bias()) g.counters = (unsigned*)const_cast<void*>(bias);   // read-only there: the kernel's bf16 bias vector
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
     switch (p.d[i].thunk) {
       case THUNK_ENTRY: launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
@@ -1128,6 +1139,40 @@ int bgemm_mi355x_selfcheck_launch_nn_bias(int nn_config, int splits, int operand
 int bgemm_mi355x_selfcheck_launch_ta_bias(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                           long long out[20]) {
   return tr_selfcheck_launch(kLayoutTA, TR_BF16, kOutC16Bias, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- the forward product with a fused bias and activation, Y = act(X W^T + b) (the kinds TR_C16_BIAS + act): C = bf16(act32(z)),
+// z = fl32(S + float(bias[n])) exactly bgemm_mi355x_tn_bias's value before its rounding; the activation (hgemm_act.hpp) is applied to the
+// unrounded z, never to a slab, and the result is rounded once.  A call resolves to the plan of the bgemm_mi355x_launch_tn call with the
+// same arguments; only the epi id of the plain dispatch and of the combine dispatch differs.  act: HGEMM_ACT_RELU / _GELU / _GELU_TANH,
+// anything else HGEMM_ERR_BAD_ARG (a caller with no activation has bgemm_mi355x_tn_bias).
+int bgemm_mi355x_tn_bias_act_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc) {
+  return tr_runs(kLayoutTN, TR_BF16, out_bias_act(HGEMM_ACT_RELU), tn_config, M, N, K, lda, ldb, ldc);   // (no activation changes the answer)
+}
+int bgemm_mi355x_launch_tn_bias_act(int tn_config, int splits_arg, const void* a, const void* b_col_major, const void* bias, void* c, int M, int N,
+                                    int K, int lda, int ldb, int ldc, int act, void* stream) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutTN, TR_BF16, out_bias_act(act), tn_config, splits_arg, a, b_col_major, bias, c, M, N, K, lda, ldb, ldc, stream);
+}
+int bgemm_mi355x_tn_bias_act(const void* a, const void* b_col_major, const void* bias, void* c, int M, int N, int K, int act, void* stream) {
+  if (!act_known(act) || !bias) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutTN, TR_BF16, out_bias_act(act), a, b_col_major, bias, c, M, N, K, stream);
+}
+// (the output layout of bgemm_mi355x_selfcheck_launch_tn_bias; the NN and TA twins show the refusal)
+int bgemm_mi355x_selfcheck_launch_tn_bias_act(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                              int act, long long out[20]) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, out_bias_act(act), tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_nn_bias_act(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                              int act, long long out[20]) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_bias_act(act), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_ta_bias_act(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                              int act, long long out[20]) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTA, TR_BF16, out_bias_act(act), ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the

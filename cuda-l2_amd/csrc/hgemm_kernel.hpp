@@ -294,10 +294,18 @@ constexpr int EPI_C32    = 4;  // fp32 C (family a): the accumulators stored as 
                                // the float pointer, g.ldc counts fp32 elements
 constexpr int EPI_C16_BIAS = 5;  // bf16 C with a fused bias (family f, bgemm_mi355x_tn_bias): C = bf16(acc + float(bias[n])), the bias added
                                  // last and the sum rounded once; g.counters holds the bias pointer (hgemm_kernel_tn.hpp)
+// bf16 C with a fused bias and activation (family f, bgemm_mi355x_tn_bias_act): C = bf16(act(acc + float(bias[n]))), the activation
+// (hgemm_act.hpp) applied to the unrounded fp32 sum and the result rounded once.  EPI_C16_BIAS + the activation's id, a compile-time
+// property of the kernel.  (Family f takes neither flag below, so its 8 is no EPI_KTAIL.)
+constexpr int EPI_C16_BIAS_RELU = 6, EPI_C16_BIAS_GELU = 7, EPI_C16_BIAS_GELU_TANH = 8;
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.
 constexpr int EPI_KTAIL = 8;
+// (Family f's epilogue id EPI_C16_BIAS_GELU_TANH has the same value.  Ids and flags meet in no template today: family f's kernels and
+// launchers never mask with a flag, and the families that do are never handed family f's ids.  A family that shares a launcher with
+// both has to move one of them first.)
+static_assert(EPI_STREAMK < EPI_KTAIL && EPI_C16_BIAS > EPI_STREAMK, "the flagged families' ids stay below the flag bits; family f's ids are not theirs");
 // Kernel-template flag (family q, round 5): the "kstagger" variant -- the workgroups of XCD x start every work item's K walk at
 // stage x * nk / 8 and wrap (plan flag HGEMM_PLAN_XCD_STAGGER).  A variant of its own for the same reason as EPI_KTAIL.
 constexpr int EPI_KSTAGGER = 16;

@@ -297,12 +297,13 @@ struct TrEntry {
 };
 enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C hold: 2 bytes either way
 // The output kinds of a layout: a 16-bit C, an fp32 C (family a), a 16-bit C with a fused bias (family f: bgemm_mi355x_tn_bias).
-enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_KINDS = 3 };
+// TR_C16_BIAS + a (a = 1, 2, 3: hgemm_act.hpp's ACT_RELU / _GELU / _GELU_TANH): the bias followed by that activation (bgemm_mi355x_tn_bias_act).
+enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_C16_BIAS_GELU = 4, TR_C16_BIAS_GELU_TANH = 5, TR_KINDS = 6 };
 struct TrRow {
   TrEntry e;
   TrLaunch launch[2][TR_KINDS];   // [TrElem][TrKind]
 };
-// `bias`: the bf16 bias vector of the TR_C16_BIAS set (N elements, added last in fp32, the sum rounded once); every other set is handed
+// `bias`: the bf16 bias vector of the TR_C16_BIAS sets (N elements, added last in fp32, the sum rounded once); every other set is handed
 // nullptr and ignores it.
 struct TrKernels {
   void (*combine)(const float* partial, void* c, const void* bias, int M, int N, int ldc, int splits, bool accumulate, hipStream_t, TimingSlot);

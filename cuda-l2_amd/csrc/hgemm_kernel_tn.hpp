@@ -26,9 +26,16 @@
 //     repeated text over a changed loop); families n and a keep their symbols and, as compiled, their instruction streams.
 #pragma once
 
+#include "hgemm_act.hpp"
 #include "hgemm_kernel_nn.hpp"
 
 namespace hgemm_mi355x {
+
+// The epilogues with a bias vector: EPI_C16_BIAS and, with an activation behind the add, EPI_C16_BIAS + ACT_* (hgemm_act.hpp).
+constexpr bool epi_has_bias(int epi) { return epi >= EPI_C16_BIAS && epi <= EPI_C16_BIAS_GELU_TANH; }
+constexpr int epi_act(int epi) { return epi_has_bias(epi) ? epi - EPI_C16_BIAS : ACT_NONE; }
+static_assert(epi_act(EPI_C16_BIAS_RELU) == ACT_RELU && epi_act(EPI_C16_BIAS_GELU) == ACT_GELU && epi_act(EPI_C16_BIAS_GELU_TANH) == ACT_GELU_TANH &&
+              epi_act(EPI_C16_BIAS) == ACT_NONE, "an activation's epilogue id is EPI_C16_BIAS + its ACT_ id");
 
 template <class CFG, int EPI>
 __global__ void hgemm_tn_bf16_kernel(const GemmArgs g);
@@ -43,7 +50,7 @@ struct CfgTNB : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
 };
 
 // GemmArgs as the kernel reads it: A = [M][lda], Bt = b_col_major ([N][ldb], ldb >= K its row stride); tail_tiles = 0, counters = nullptr
-// -- except EPI_C16_BIAS, where counters is the bias vector (const __bf16*, N elements, 16-byte aligned), reinterpreted below as the fp32-C
+// -- except EPI_C16_BIAS and its activation forms, where counters is the bias vector (const __bf16*, N elements, 16-byte aligned), reinterpreted below as the fp32-C
 // kernels reinterpret g.C.
 template <class CFG, int EPI>
 __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmArgs g) {
@@ -53,7 +60,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
   using elem = typename CFG::elem;   // __bf16
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || EPI == EPI_C16_BIAS, "plain, two-pass slab and fused-bias epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || epi_has_bias(EPI), "plain, two-pass slab, fused-bias and fused-bias-activation epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -153,7 +160,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
   // swap of the shared epilogue, which moves finished bf16 values only.
   // The loads are issued HERE, behind the K loop: the loop keeps the EPI_C16 kernel's registers and its counted vmcnt; the price is
   // one L2 round trip per tile in front of the stores.
-  if constexpr (EPI == EPI_C16_BIAS) {
+  if constexpr (epi_has_bias(EPI)) {
     using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
     using bx4 = __attribute__((ext_vector_type(4))) __bf16;
     const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc((void*)g.counters, 0, (uint32_t)g.N * 2u, 0x00020000);
@@ -169,6 +176,29 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
       for (int j = 0; j < FN; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[i][j][e] += (float)bias[j][e];
+  }
+
+  // ---- fused activation (EPI_C16_BIAS + ACT, bgemm_mi355x_tn_bias_act): C = bf16(act(z)), z the unrounded fp32 value above -------------------
+  // act_apply (hgemm_act.hpp) is the text the combine and the reference kernel use; it works on the lane's own pre-swap values, so the
+  // ownership is the bias code's.  A compile-time property of the kernel: no runtime branch, and the kernels without one compile as before.
+  // Register steering, not semantics: the sched_barrier per quad keeps the transcendental's temporaries those of four values, and the empty
+  // asm parks each finished value in an accumulation register.  Without the asm the inlined erf's per-value branch made the compiler hold
+  // all 64 finished values of f128x128_w2x2 in architectural VGPRs: next_free_vgpr 264 against the EPI_C16_BIAS twin's 257 (accum_offset
+  // 200 against 84).  With it every kernel has its twin's figure.  Nothing but tests/test_tn_bias_act_host.py's audit of unit g14 guards
+  // that: after a compiler change the audit fails, and the steering is to be looked at again.
+  if constexpr (epi_act(EPI) != ACT_NONE) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float y = act_apply<epi_act(EPI)>(acc[i][j][e]);
+          asm volatile("" : "+a"(y));   // the finished value waits in an accumulation register for the stores, where the sum was
+          acc[i][j][e] = y;
+        }
+      }
   }
 
   if constexpr (EPI == EPI_SLAB) {
@@ -194,5 +224,19 @@ void launch_tn_bias(const GemmArgs& g, int grid, hipStream_t stream, int epi, Ti
 #define HGEMM_TN_BIAS_INST(...) template void HGEMM_TN_BIAS_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
 #define HGEMM_TN_BIAS_EXTERN(...) extern HGEMM_TN_BIAS_INST(__VA_ARGS__)
 HGEMM_TR_MEMBERS(HGEMM_TN_BIAS_EXTERN, CfgTNB)     // hgemm_inst_g12.hip
+
+// The fused bias+activation sets (bgemm_mi355x_tn_bias_act), one per activation: the member's EPI_C16_BIAS + ACT kernel alone; the K slices
+// of a two-pass form are again the 16-bit set's EPI_SLAB kernels.
+template <class CFG, int ACT>
+void launch_tn_bias_act(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_BIAS + ACT>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_TN_ACT_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_tn_bias_act<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_TN_ACT_INST(...) template void HGEMM_TN_ACT_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TN_ACT_EXTERN(...) extern HGEMM_TN_ACT_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_TN_ACT_EXTERN, ACT_RELU, CfgTNB)        // hgemm_inst_g14.hip
+HGEMM_TR_MEMBERS(HGEMM_TN_ACT_EXTERN, ACT_GELU, CfgTNB)
+HGEMM_TR_MEMBERS(HGEMM_TN_ACT_EXTERN, ACT_GELU_TANH, CfgTNB)
 
 }  // namespace hgemm_mi355x

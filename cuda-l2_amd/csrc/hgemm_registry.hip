@@ -284,6 +284,54 @@ __global__ void __launch_bounds__(256) hgemm_generic_tn_bias_kernel(const __bf16
   }
 }
 
+// The combine of the fused bias+activation calls (bgemm_mi355x_tn_bias_act): hgemm_splitk_reduce_bias_kernel's text -- the slabs in split
+// order, THEN the bias as one fp32 add -- then act_apply<ACT> (hgemm_act.hpp, the kernels' own text) on the unrounded fp32 value, then the
+// one rounding to bf16.  The activation is never applied to a slab.  New symbols: the kernels above keep theirs and their streams.
+template <int ACT>
+__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bias_act_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
+                                                                           const __bf16* __restrict__ bias, int M, int N, int ldc, int splits) {
+  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+  const size_t total4 = ((size_t)M * N) >> 2;
+  const size_t slab   = (size_t)M * N;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = q << 2;
+    const int m = (int)(e / N), n = (int)(e % N);
+    const bx4 b = *(const bx4*)(bias + n);   // in flight with the slab loads
+    f32x4 s = *(const f32x4*)(partial + e);
+    int k = 1;
+    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
+      f32x4 p[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += p[u];
+    }
+    for (; k < splits; ++k) {
+      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
+      s += p;
+    }
+    const bx4 o = {(__bf16)act_apply<ACT>(s[0] + (float)b[0]), (__bf16)act_apply<ACT>(s[1] + (float)b[1]),
+                   (__bf16)act_apply<ACT>(s[2] + (float)b[2]), (__bf16)act_apply<ACT>(s[3] + (float)b[3])};
+    *(bx4*)(C + (size_t)m * ldc + n) = o;
+  }
+}
+
+// The reference kernel of the fused bias+activation calls: hgemm_generic_tn_bias_kernel's fma chain in k order and its fp32 add of
+// float(bias[n]), then act_apply<ACT>, then the one rounding.  Any shape, stride and alignment (bias 2-byte aligned).
+template <int ACT>
+__global__ void __launch_bounds__(256) hgemm_generic_tn_bias_act_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bcol,
+                                                                        __bf16* __restrict__ C, const __bf16* __restrict__ bias, int M, int N,
+                                                                        int K, int lda, int ldb_colmajor, int ldc) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  const float b = (float)bias[n];
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
+    C[(size_t)m * ldc + n] = (__bf16)act_apply<ACT>(s + b);
+  }
+}
+
 // ---- launchers of the combines and the reference kernels, with the signatures of TrKernels (hgemm_kernel_nn.hpp) ----------------------
 // grid and block of a combine: a thread per four outputs
 struct CombineGrid { int grid, threads; };
@@ -342,6 +390,23 @@ static void launch_reference_tn_bias(const void* A, const void* Bcol, void* C, c
                K, lda, ldb, ldc);
 }
 
+// the fused bias+activation sets' two (bgemm_mi355x_tn_bias_act), per activation
+template <int ACT>
+static void launch_combine_bias_act(const float* partial, void* C, const void* bias, int M, int N, int ldc, int splits, bool, hipStream_t stream,
+                                    TimingSlot ts) {
+  const CombineGrid cg = combine_grid(M, N);
+  HGEMM_LAUNCH((hgemm_splitk_reduce_bias_act_kernel<ACT>), cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)bias, M, N, ldc,
+               splits);
+}
+
+template <int ACT>
+static void launch_reference_tn_bias_act(const void* A, const void* Bcol, void* C, const void* bias, int M, int N, int K, int lda, int ldb,
+                                         int ldc, bool, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH((hgemm_generic_tn_bias_act_kernel<ACT>), grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)Bcol, (__bf16*)C,
+               (const __bf16*)bias, M, N, K, lda, ldb, ldc);
+}
+
 // the b_col_major families' names for their two (hgemm_launch.hpp)
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
@@ -356,7 +421,7 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
 // ---- the tables of the three layouts of the transposed-read host path (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the member list: a
 // row is the member's geometry and its launcher in every kernel set of the layout, [TrElem][TrKind]; `kernels` names the same sets'
 // combine and reference kernel.  A new kernel set is one more cell in the layout's row macro and in its `kernels`; a cell left out is
-// empty (null launcher, TrKernels{}) and a call for it is refused -- the fused-bias kind of NN and TA.
+// empty (null launcher, TrKernels{}) and a call for it is refused -- the fused-bias and bias+activation kinds of NN and TA.
 // (Inside functions, which both passes read: the device pass instantiates a combine or a reference kernel where it sees its launcher
 // named, and a table of host function pointers at namespace scope would be emitted as a device constant.)
 #define HGEMM_NN_ROW(P, ...)                                                                                \
@@ -365,11 +430,14 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
 #define HGEMM_TA_ROW(P, ...)                                                                                                                 \
   {HGEMM_TR_ENTRY(P, CfgTA, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgTA, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTA, true, __VA_ARGS__)},    \
                                            {&HGEMM_TR_LAUNCHER(CfgTAB, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTAB, true, __VA_ARGS__)}}},
-// TN (family f, hgemm_kernel_tn.hpp): the bf16 sets with a 16-bit C, plain and with the fused bias; every other cell is empty and a call
-// for it is refused
+// TN (family f, hgemm_kernel_tn.hpp): the bf16 sets with a 16-bit C -- plain, with the fused bias, and with the bias and each activation
+// (TR_C16_BIAS + ACT_*) --; every other cell is empty and a call for it is refused
 #define HGEMM_TN_ROW(P, ...)                                                                                        \
   {HGEMM_TR_ENTRY(P, CfgTNB, __VA_ARGS__), {{nullptr, nullptr}, {&HGEMM_TR_LAUNCHER(CfgTNB, false, __VA_ARGS__), nullptr, \
-                                                                 &HGEMM_TN_BIAS_LAUNCHER(CfgTNB, __VA_ARGS__)}}},
+                                                                 &HGEMM_TN_BIAS_LAUNCHER(CfgTNB, __VA_ARGS__),            \
+                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_RELU, CfgTNB, __VA_ARGS__),   \
+                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_GELU, CfgTNB, __VA_ARGS__),   \
+                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_GELU_TANH, CfgTNB, __VA_ARGS__)}}},
 const TrTable& tr_table_nn() {
   static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_NN_ROW, "n")};
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
@@ -388,7 +456,10 @@ const TrTable& tr_table_ta() {
 const TrTable& tr_table_tn() {
   static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TN_ROW, "f")};
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
-                            {{{}, {}}, {{launch_combine<__bf16>, launch_reference_tn<__bf16>}, {}, {launch_combine_bias, launch_reference_tn_bias}}}};
+                            {{{}, {}}, {{launch_combine<__bf16>, launch_reference_tn<__bf16>}, {}, {launch_combine_bias, launch_reference_tn_bias},
+                                        {launch_combine_bias_act<ACT_RELU>, launch_reference_tn_bias_act<ACT_RELU>},
+                                        {launch_combine_bias_act<ACT_GELU>, launch_reference_tn_bias_act<ACT_GELU>},
+                                        {launch_combine_bias_act<ACT_GELU_TANH>, launch_reference_tn_bias_act<ACT_GELU_TANH>}}}};
   return t;
 }
 

@@ -35,6 +35,10 @@
 //   hgemm_tune bench --layout tn --bf16 --shapes ... [--out F.jsonl]
 //   hgemm_tune check --layout tn --bf16 --bias [--shapes ...]   the fused-bias calls (bgemm_mi355x_launch_tn_bias): bf16(S + bias[n])
 //   hgemm_tune bench --layout tn --bf16 --bias --shapes ... [--out F.jsonl]   against the same plan without a bias, "bias_le_plain"
+//   hgemm_tune check --layout tn --bf16 --bias --act relu|gelu|gelu_tanh [--shapes ...]   the fused bias+activation calls
+//                                                     (bgemm_mi355x_launch_tn_bias_act): ReLU bit for bit, the GELUs inside their bar
+//   hgemm_tune bench --layout tn --bf16 --bias --act A --shapes ... [--out F.jsonl]   against bgemm_mi355x_launch_tn_bias followed by an
+//                                                     element-wise activation kernel, "act_le_unfused"
 //                                                     that check first, then per shape interleaved rounds of the planned call, of
 //                                                     bgemm_mi355x_launch_nn with the same member and splits, and -- context -- rocBLAS
 //   hgemm_tune bench --layout nn --shapes ... [--autotune] [--out F.jsonl]
@@ -68,6 +72,7 @@
 #include <rocm_smi/rocm_smi.h>
 
 #include "../../../include/hgemm_mi355x.h"
+#include "../hgemm_act.hpp"
 
 // Ablation switches exist only in the -DHGEMM_ABLATION build of the library (build.py: HGEMM_LIB_SUFFIX=ablation
 // HGEMM_EXTRA_HIPFLAGS=-DHGEMM_ABLATION); against the shipping library the symbol is absent and --debug refuses.
@@ -1336,8 +1341,10 @@ struct TrBench {
   void verdict(const char* key, int a, int b, bool spread) { verdict_key = key; va = a; vb = b; with_spread = spread; }
 };
 
+static int g_act = 0;   // --act: 0, or HGEMM_ACT_RELU / _GELU / _GELU_TANH (the fused bias+activation calls, below)
+static int act_check(std::vector<Shape> shapes);
 static int tr_bench(const Variant& V, const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
-  const int rc = tr_check(V, {});   // no timing of a kernel that is wrong
+  const int rc = g_act ? act_check({}) : tr_check(V, {});   // no timing of a kernel that is wrong
   if (rc != 0) { fprintf(stderr, "bench %s: the check failed, nothing is timed\n", V.words("--layout ", " --").c_str()); return rc; }
   FILE* out = out_path ? fopen(out_path, "w") : stdout;
   if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
@@ -1487,6 +1494,150 @@ static void bench_tn_bias(TrBench& B) {
   B.verdict("bias_le_plain", 0, 1, true);
 }
 
+// ---- --act relu|gelu|gelu_tanh (with --layout tn --bf16 --bias): the fused bias+activation calls, bgemm_mi355x_tn_bias_act ---------------
+// C = bf16(act(S + bias[n])).  The check's operands are integers in -2 .. 2 with A scaled by 2^-(floor(log2 K) - 2) and a bias of multiples
+// of 2^-8 in [-1, 1]: z = S + bias is exact in fp32 in any order (verified per element) and lies in the activations' live range.  The bars:
+// ReLU bit for bit against (z > 0 ? bf16(z) : +0); both GELUs |C - y*| <= 1/2 ulp_bf16(y*) + 2^-19 |z|, y* the fp64 activation of z.
+static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh"};
+static double act_fp64(double z, int act) {
+  if (act == HGEMM_ACT_RELU) return z > 0 ? z : 0.0;
+  if (act == HGEMM_ACT_GELU) return 0.5 * z * erfc(-z / sqrt(2.0));
+  const double u = sqrt(2.0 / M_PI) * (z + 0.044715 * z * z * z);
+  return z / (1.0 + exp(-2.0 * u));
+}
+static double bf16_value(uint16_t h) {
+  const uint32_t u = (uint32_t)h << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return (double)f;
+}
+static int launch_bias_act(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_bias_act(cfg, splits, o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, g_act, nullptr);
+}
+static int planned_bias_act(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_bias_act(o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, g_act, nullptr); }
+static void bench_tn_bias_act(TrBench&);
+static const BenchDesc kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act};
+// (not in kVariants: resolve_variant answers the flags without --act; main swaps this one in when --act is given)
+static const Variant kVariantTNBiasAct = {&kLayoutTN, kBF16, kC16Bias, bgemm_mi355x_tn_bias_act_runs, launch_bias_act, planned_bias_act, &kBenchTNBiasAct};
+
+static int act_check(std::vector<Shape> shapes) {
+  const Variant& V = kVariantTNBiasAct;
+  const TrLayout& L = *V.L;
+  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
+  const std::string lay_s = V.words("", "-") + "-" + kActNames[g_act];
+  const char* lay = lay_s.c_str();
+  const int nc = L.num_configs();
+  int failures = 0, runs = 0;
+  double worst = 0.0;
+  for (const Shape& sh : shapes) {
+    const size_t cn = (size_t)sh.M * sh.N;
+    int j = 0;
+    while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
+    const double scale = ldexp(1.0, -std::max(j - 2, 0));
+    uint64_t lcg = 0x9E3779B97F4A7C15ull + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
+    auto draw = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (int)((lcg >> 33) % 5) - 2; };
+    std::vector<int8_t> ai((size_t)sh.M * sh.K), wi((size_t)sh.N * sh.K);
+    for (auto& v : ai) v = (int8_t)draw();
+    for (auto& v : wi) v = (int8_t)draw();
+    std::vector<uint16_t> a_h(ai.size()), w_h(wi.size()), b_h(sh.N), got(cn);
+    for (size_t i = 0; i < ai.size(); ++i) a_h[i] = bf16_rne((float)(ai[i] * scale));   // a small integer times a power of two: a bf16 value
+    for (size_t i = 0; i < wi.size(); ++i) w_h[i] = bf16_rne((float)wi[i]);
+    std::vector<double> bias(sh.N), z(cn);
+    for (int n = 0; n < sh.N; ++n) {
+      bias[n] = (double)(((n * 37 + 11) % 513) - 256) / 256.0;   // |q| <= 256: at most 8 significant bits, a bf16 value
+      b_h[n] = bf16_rne((float)bias[n]);
+    }
+    for (int m = 0; m < sh.M; ++m)
+      for (int n = 0; n < sh.N; ++n) {
+        int s = 0;
+        const int8_t *ar = &ai[(size_t)m * sh.K], *wr = &wi[(size_t)n * sh.K];
+        for (int k = 0; k < sh.K; ++k) s += ar[k] * wr[k];
+        const double zz = s * scale + bias[n];
+        if ((double)(float)zz != zz || (double)(float)(s * scale) != s * scale) { fprintf(stderr, "check %s: z is not exact in fp32 at %d_%d_%d\n", lay, sh.M, sh.N, sh.K); return 2; }
+        z[(size_t)m * sh.N + n] = zz;
+      }
+    DevBufs dev;
+    TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(w_h.data(), w_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), dev.alloc(cn * 2), 0};
+    for (int c = 0; c < nc; ++c) {
+      const char* cname = L.config_name(c);
+      const int own = V.runs_at(c, sh);
+      for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
+        HIP_OK(hipMemset(call.c, 0xff, cn * 2));   // NaN pattern: unwritten outputs are caught
+        const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
+        const hipError_t e = hipDeviceSynchronize();
+        ++runs;
+        if (st != HGEMM_OK || e != hipSuccess) {
+          printf("FAIL %s %d_%d_%d %s s=%d: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
+          ++failures;
+          if (e != hipSuccess) return 3;
+          continue;
+        }
+        HIP_OK(hipMemcpy(got.data(), call.c, cn * 2, hipMemcpyDeviceToHost));
+        size_t bad = 0;
+        for (size_t i = 0; i < cn; ++i) {
+          if (g_act == HGEMM_ACT_RELU) {
+            bad += got[i] != (z[i] > 0 ? bf16_rne((float)z[i]) : (uint16_t)0);
+          } else {
+            const double y = act_fp64(z[i], g_act), c16 = bf16_value(got[i]);
+            const double bar = (y != 0 ? ldexp(1.0, (int)floor(log2(fabs(y))) - 8) : 0.0) + ldexp(fabs(z[i]), -19);
+            const double err = fabs(c16 - y);
+            if (!(err <= bar)) ++bad;   // (a NaN fails)
+            else if (bar > 0) worst = std::max(worst, err / bar);
+          }
+        }
+        if (bad) {
+          printf("FAIL %s %d_%d_%d %s s=%d%s: %zu/%zu elements %s\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+                 (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn, g_act == HGEMM_ACT_RELU ? "differ from the exact result" : "outside the bar");
+          ++failures;
+        }
+      }
+      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
+    }
+    fflush(stdout);
+  }
+  printf("check-%s-configs:", lay);
+  for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
+  printf("\ncheck-%s-forms: 1 1|nt-store 2 5\n", lay);
+  if (g_act == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (bit-exact against where(z > 0, bf16(z), +0) of the exact z)\n", lay, runs, failures);
+  else printf("check %s: %d runs, %d failures (every element within 1/2 ulp_bf16(y*) + 2^-19 |z| of the fp64 activation of the exact z; worst %.3f of it)\n",
+              lay, runs, failures, worst);
+  return failures ? 1 : 0;
+}
+
+// the unfused second pass of the contender: an element-wise bf16 activation over all of C, hgemm_act.hpp's text on the value already
+// rounded to bf16
+template <int ACT>
+__global__ void act_bf16_kernel(__bf16* __restrict__ c, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    c[i] = (__bf16)hgemm_mi355x::act_apply<ACT>((float)c[i]);
+}
+
+// tn --bf16 --bias --act A: the planned bgemm_mi355x_tn_bias_act call against the path it replaces -- bgemm_mi355x_launch_tn_bias with the
+// same member and splits followed by the element-wise activation kernel above (its launch is not checked: the contender answers with the
+// product's status) --, and, context only, the plain bias call.  The one condition: fused <= unfused within the unfused path's own
+// round-to-round spread in this run: "act_le_unfused".
+static void bench_tn_bias_act(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = g_act;
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), btb = B.to_bf16(B.of(&Buffers::bt), B.b_elems), cb = B.alloc(cn * 2),
+                        bias = B.alloc((size_t)sh.N * 2);
+  for (void* p : bias) fill_bias_kernel<<<64, 256>>>((__bf16*)p, sh.N);
+  const int act_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+  B.add("act", [=](Buffers&, size_t i) { return bgemm_mi355x_tn_bias_act(ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, act, nullptr); });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
+    if (act == HGEMM_ACT_RELU) act_bf16_kernel<HGEMM_ACT_RELU><<<act_grid, 256>>>((__bf16*)cb[i], cn);
+    else if (act == HGEMM_ACT_GELU) act_bf16_kernel<HGEMM_ACT_GELU><<<act_grid, 256>>>((__bf16*)cb[i], cn);
+    else act_bf16_kernel<HGEMM_ACT_GELU_TANH><<<act_grid, 256>>>((__bf16*)cb[i], cn);
+    return st;
+  });
+  B.add("bias", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
+  B.head("\"output\": \"c16_bias_act\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
+         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("act_le_unfused", 0, 1, true);
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1513,6 +1664,11 @@ int main(int argc, char** argv) {
     else if (a == "--c32") c32 = true;
     else if (a == "--bf16") bf16 = true;
     else if (a == "--bias") bias = true;
+    else if (a == "--act") {
+      const std::string nm = next();
+      for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) g_act = k;
+      if (!g_act) { fprintf(stderr, "--act takes relu, gelu or gelu_tanh\n"); return 2; }
+    }
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
     else if (a == "--streamk") g_streamk_too = true;
@@ -1563,9 +1719,10 @@ int main(int argc, char** argv) {
   // Which of the transposed-read variants, if any, the flags name -- and every refusal that follows from the flags alone, before a
   // device is asked for.  nullptr: the fp16 b_col_major commands below (no --layout, or --layout tn without --bf16).
   if (bias && !(bf16 && layout == "tn")) { fprintf(stderr, "--bias goes with --layout tn --bf16 (bgemm_mi355x_tn_bias)\n"); return 2; }
+  if (g_act && !bias) { fprintf(stderr, "--act goes with --layout tn --bf16 --bias (bgemm_mi355x_tn_bias_act)\n"); return 2; }
   if (c32 && layout != "ta") { fprintf(stderr, "--c32 goes with --layout ta\n"); return 2; }
   if (bf16 && layout.empty()) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
-  const Variant* variant = resolve_variant(layout, bf16, c32, bias);
+  const Variant* variant = g_act ? &kVariantTNBiasAct : resolve_variant(layout, bf16, c32, bias);
   if (variant && mode != "check" && mode != "bench") {
     fprintf(stderr, "--layout %s%s goes with check or bench\n", layout.c_str(), variant->L->b_col_major ? " --bf16" : "");
     return 2;
@@ -1581,7 +1738,7 @@ int main(int argc, char** argv) {
     HIP_OK(hipMalloc(&pad, g_pad_alloc_mib << 20));   // (kept until exit)
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
   }
-  if (variant) return mode == "check" ? tr_check(*variant, shapes) : tr_bench(*variant, shapes, out_path, autotune);
+  if (variant) return mode != "check" ? tr_bench(*variant, shapes, out_path, autotune) : g_act ? act_check(shapes) : tr_check(*variant, shapes);
   if (mode == "check") {
     if (shapes.empty())
       // (the last two: K tails -- 2104 = 32 x 64 + 56 = 8 x 256 + 56, 728 = 11 x 64 + 24 = 5 x 128 + 88 = 2 x 256 + 216: odd and even

@@ -442,6 +442,43 @@ int bgemm_mi355x_launch_tn_bias(int tn_config, int splits, const void* a, const 
 /* 1 when the call (with an aligned bias) runs one of the family's kernels: equal to bgemm_mi355x_tn_runs */
 int bgemm_mi355x_tn_bias_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc);
 
+/* ------------------------------------------------------------------------------------------
+ * Forward product with a fused bias AND activation: Y = act(X x W^T + b), the first half of a transformer MLP in one call.  Operands,
+ * `bias`, layout, strides and scope are bgemm_mi355x_tn_bias's.
+ * Replaces bgemm_mi355x_tn_bias followed by an element-wise activation kernel -- a second launch and a second pass that reads and
+ * writes all of Y again (4 M N bytes), with the activation applied to a value already rounded to bf16 -- or a vendor GEMM with a
+ * bias+ReLU / bias+GELU epilogue.
+ * Semantics, exactly:  z[m][n] = fl32( S[m][n] + float(bias[n]) )   (bgemm_mi355x_tn_bias's value before its rounding)
+ *                      C[m][n] = bf16_rne( act32( z[m][n] ) )
+ *   - S is the finished fp32 sum: the accumulator of a plain launch, or the slabs of a two-pass plan added in split order; the bias
+ *     is added last.
+ *   - The activation is applied to the unrounded sum z, in fp32.  It is never applied to a slab.  The result is rounded once.
+ *   - `act` is one of
+ *       HGEMM_ACT_RELU       y = z if z > 0 or z is NaN, otherwise +0.0f.  -0, -inf and every negative give +0, NaN stays NaN, +inf
+ *                            stays +inf.  An exact function: C is defined bit for bit.
+ *       HGEMM_ACT_GELU       y = 0.5 z (1 + erf(z / sqrt 2)), the erf form (torch's default).
+ *       HGEMM_ACT_GELU_TANH  y = 0.5 z (1 + tanh(sqrt(2 / pi) (z + 0.044715 z^3))), the GPT-2 / BERT form, evaluated as the
+ *                            algebraically equal z / (1 + exp(-2u)).  A large negative finite z (z^3 overflows) gives -0, a large
+ *                            positive z gives z.
+ *     Both GELUs: NaN gives NaN, +inf gives +inf, -inf gives NaN (the formulas' own 0 x inf, as torch has it), z = +-0 gives a zero.
+ *   - The GELU bar: with y* the activation of the exact z evaluated in fp64, every finite element satisfies
+ *       |C - y*| <= 1/2 ulp_bf16(y*) + 2^-19 |z|
+ *     (the second term covers the fp32 evaluation of 1 + erf / 1 + tanh, 16 and 5 ulp in the device math library, times |z| / 2; it
+ *     matters only in the negative tail).  The plain, split and reference forms of one call share one activation text.
+ * act == 0 or any other value: HGEMM_ERR_BAD_ARG (a caller with no activation has bgemm_mi355x_tn_bias).  bias == NULL:
+ * HGEMM_ERR_BAD_ARG -- a layer without a bias passes a zero vector.  No fp16 form, no other layout, no SiLU or gated form.
+ * The table, ids, names, plan, workspace size and reserve call are bgemm_mi355x_tn_*'s: the tiles, cuts, slabs, splits word, statuses
+ * and capture behaviour of a call are those of the bgemm_mi355x_launch_tn call with the same arguments. */
+#define HGEMM_ACT_RELU 1
+#define HGEMM_ACT_GELU 2
+#define HGEMM_ACT_GELU_TANH 3
+/* planned, contiguous (lda = ldb = K, ldc = N) */
+int bgemm_mi355x_tn_bias_act(const void* a, const void* b_col_major, const void* bias, void* c, int M, int N, int K, int act, void* stream);
+int bgemm_mi355x_launch_tn_bias_act(int tn_config, int splits, const void* a, const void* b_col_major, const void* bias, void* c,
+                                    int M, int N, int K, int lda, int ldb, int ldc, int act, void* stream);
+/* 1 when the call (with an aligned bias) runs one of the family's kernels: equal to bgemm_mi355x_tn_runs */
+int bgemm_mi355x_tn_bias_act_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc);
+
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
 const char* hgemm_mi355x_version(void);
