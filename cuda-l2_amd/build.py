@@ -50,6 +50,8 @@ LIB_SOURCES = [
     "hgemm_inst_g12.hip",
     "hgemm_inst_g13.hip",
     "hgemm_inst_g14.hip",
+    "hgemm_inst_g15.hip",
+    "hgemm_inst_g16.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

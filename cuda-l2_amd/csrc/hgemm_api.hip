@@ -479,20 +479,34 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // act (bgemm_mi355x_tn_bias_act, with bias only): an activation of hgemm_act.hpp behind the bias add -- C = T(act(sum + float(bias[n]))),
 // applied to the unrounded fp32 value, never to a slab, the result rounded once.  One more kind per activation, TR_C16_BIAS + act; the
 // epilogue ids follow suit, EPI_C16_BIAS + act.
+// aux (bgemm_mi355x_tn_bias_act_aux, with bias and act only): the rounded pre-activation as a second 16-bit output z_out at row stride ldz,
+// the kinds TR_C16_BIAS_AUX + act and the ids EPI_C16_BIAS_AUX + act.  dact (bgemm_mi355x_nn_dact, family n, no bias): C = T(sum x act'(z)),
+// z a 16-bit INPUT at row stride ldz; the kinds TR_C16_DACT + act, the ids EPI_C16_DACT + act.  Either way the second matrix has C's rules
+// (ldz >= N; ldz % 8 == 0, 16-byte aligned and (BM ldz + N) 2 bytes below 2 GiB, or the reference kernel answers) and changes nothing else
+// of the plan.
 struct TrOut {
   bool c32, accumulate;
   bool bias = false;
   int act = 0;   // 0 (none) or HGEMM_ACT_RELU / _GELU / _GELU_TANH = 1 / 2 / 3
+  bool aux = false, dact = false;
+  int ldz = 0;   // the row stride of z_out (aux) / z (dact); no part of the kind
   int elem_bytes() const { return c32 ? 4 : 2; }
-  TrKind kind() const { return bias ? (TrKind)(TR_C16_BIAS + act) : c32 ? TR_C32 : TR_C16; }   // the kernel set's cell in TrRow / TrTable
-  int epi_bias() const { return EPI_C16_BIAS + act; }   // the epilogue id of the plain dispatch and of the combine dispatch of a bias kind
+  bool has_z() const { return aux || dact; }
+  bool has_epi() const { return bias || dact; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
+  TrKind kind() const {   // the kernel set's cell in TrRow / TrTable
+    return dact ? (TrKind)(TR_C16_DACT + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
+  }
+  int epi_bias() const { return (dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
 };
 constexpr TrOut kOutC16{false, false};
 constexpr TrOut kOutC16Bias{false, false, true};
 static_assert(HGEMM_ACT_RELU == ACT_RELU && HGEMM_ACT_GELU == ACT_GELU && HGEMM_ACT_GELU_TANH == ACT_GELU_TANH, "the public ids are hgemm_act.hpp's");
-static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIAS_GELU_TANH + 1 == TR_KINDS, "a kind per activation");
+static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIAS_AUX == TR_C16_BIAS_GELU_TANH &&
+              TR_C16_DACT == TR_C16_BIAS_AUX + ACT_GELU_TANH && TR_C16_DACT + ACT_GELU_TANH + 1 == TR_KINDS, "a kind per activation, three times");
 constexpr bool act_known(int act) { return act == HGEMM_ACT_RELU || act == HGEMM_ACT_GELU || act == HGEMM_ACT_GELU_TANH; }
 constexpr TrOut out_bias_act(int act) { return TrOut{false, false, true, act}; }   // (act_known(act) checked by the caller)
+constexpr TrOut out_bias_act_aux(int act, int ldz) { return TrOut{false, false, true, act, true, false, ldz}; }
+constexpr TrOut out_dact(int act, int ldz) { return TrOut{false, false, false, act, false, true, ldz}; }
 
 // What the operands and a 16-bit C hold (TrElem): fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements
 // are 2 bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  (TrElem, c32) selects a kernel set and nothing
@@ -550,9 +564,12 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
   };
   // rows must not overlap: lda >= K (n, f) / >= M, the row stride of a_col_major (a); ldb >= N (n, a: B is row-major) / >= K, the row
   // stride of b_col_major (f); ldc >= N
-  if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < L.b_row(N, K) || ldc < N) { p.status = HGEMM_ERR_BAD_ARG; return p; }
-  if (!L.t.kernels[elem][out.kind()].reference || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no such kernel set in this layout
-  const int epi_out = out.c32 ? EPI_C32 : out.bias ? out.epi_bias() : EPI_C16;
+  if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < L.b_row(N, K) || ldc < N || (out.has_z() && out.ldz < N)) {
+    p.status = HGEMM_ERR_BAD_ARG;
+    return p;
+  }
+  if (!L.t.kernels[elem][out.kind()].present() || (out.accumulate && !out.c32)) { p.status = HGEMM_ERR_BAD_ARG; return p; }   // no such kernel set in this layout
+  const int epi_out = out.c32 ? EPI_C32 : out.has_epi() ? out.epi_bias() : EPI_C16;
   const TrEntry& e = L.t.rows[config].e;
   GemmArgs g{};
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
@@ -560,7 +577,8 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
   g.flags = ((splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0) | (out.accumulate ? ARG_ACCUMULATE : 0);
   g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
   const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
-  if (!aligned || !L.path_ok(out, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !L.reach_ok(out, e, M, N, K, lda, ldb, ldc) ||
+  const bool z_ok = !out.has_z() || ((out.ldz & 7) == 0 && ((double)e.bm * out.ldz + N) * 2.0 < 2147483648.0);   // z / z_out: C's rules
+  if (!aligned || !z_ok || !L.path_ok(out, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !L.reach_ok(out, e, M, N, K, lda, ldb, ldc) ||
       tiles > 0x7fffffffL) {
     p.form = FORM_REFERENCE;
     add(THUNK_GENERIC, g, 0, epi_out);
@@ -581,7 +599,7 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
     p.form = FORM_SPLITK;
     p.slab_bytes = (size_t)splits * M * N * sizeof(float);
     add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
-    add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : out.bias ? out.epi_bias() : EPI_SLAB);
+    add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : out.has_epi() ? out.epi_bias() : EPI_SLAB);
   } else {
     add(THUNK_ENTRY, g, tiles, epi_out);
   }
@@ -619,12 +637,15 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 // the reference kernel as an argument and the member's EPI_C16_BIAS kernel in g.counters -- a field the launches of these families leave
 // null; GemmArgs keeps its layout, the kernel reinterprets the pointer (hgemm_kernel_tn.hpp).  The EPI_SLAB dispatch of a split call keeps
 // counters null: store_tile reads a non-null counters as "compact slabs".)
+// (out.aux / out.dact: `z` is the second matrix, required, distinct from c, and joins the alignment rule.  It reaches the combine and the
+// reference kernel as an argument (combine_z / reference_z) and the member's own kernel in fields its non-slab launch leaves idle: z_out in
+// g.partial, z in g.counters, the stride out.ldz in g.tail_first -- tail_tiles stays 0, so the raster map never reads it.)
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
-              int N, int K, int lda, int ldb, int ldc, void* stream) {
+              int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr) {
   DisarmTiming disarm_timing;
-  if (!a || !b || !c || (out.bias && !bias) || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  if (!a || !b || !c || (out.bias && !bias) || (out.has_z() && (!z || z == c)) || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15));
+  const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15)) && !(out.has_z() && ((uintptr_t)z & 15));
   unsigned ruled_out = 0;
   LaunchPlan p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
@@ -646,11 +667,21 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
     g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (bf16 travels in the same fields: the kernels of its Cfgs reinterpret)
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
     if (out.bias && p.d[i].epi == out.epi_bias()) g.counters = (unsigned*)const_cast<void*>(bias);   // read-only there: the kernel's bf16 bias vector
+    if (out.has_z() && p.d[i].thunk == THUNK_ENTRY && p.d[i].epi == out.epi_bias()) {   // the member's own kernel, never a slab kernel
+      if (out.aux) g.partial = (float*)z; else g.counters = (unsigned*)z;              // (read-only in the dact kernels)
+      g.tail_first = out.ldz;
+    }
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
     switch (p.d[i].thunk) {
       case THUNK_ENTRY: launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
-      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, bias, M, N, ldc, g.splits, out.accumulate, s, ts); break;
-      default: kern.reference(a, b, c, bias, M, N, K, lda, ldb, ldc, out.accumulate, s, ts); break;
+      case THUNK_SPLITK_REDUCE:
+        if (out.has_z()) kern.combine_z(g.partial, c, bias, z, M, N, ldc, out.ldz, g.splits, s, ts);
+        else             kern.combine(g.partial, c, bias, M, N, ldc, g.splits, out.accumulate, s, ts);
+        break;
+      default:
+        if (out.has_z()) kern.reference_z(a, b, c, bias, z, M, N, K, lda, ldb, ldc, out.ldz, s, ts);
+        else             kern.reference(a, b, c, bias, M, N, K, lda, ldb, ldc, out.accumulate, s, ts);
+        break;
     }
   }
   hipError_t err = hipGetLastError();
@@ -659,11 +690,12 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
 }
 
 // the planned call on contiguous operands
-int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void* b, const void* bias, void* c, int M, int N, int K, void* stream) {
+int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void* b, const void* bias, void* c, int M, int N, int K, void* stream,
+           void* z = nullptr) {
   if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   int cfg, splits;
   tr_model_plan(L, M, N, K, &cfg, &splits);
-  return tr_launch(L, elem, out, cfg, splits, a, b, bias, c, M, N, K, L.a_row(M, K), L.b_row(N, K), N, stream);
+  return tr_launch(L, elem, out, cfg, splits, a, b, bias, c, M, N, K, L.a_row(M, K), L.b_row(N, K), N, stream, z);
 }
 
 const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.t.count) ? L.t.rows[id].e.name : nullptr; }
@@ -1173,6 +1205,53 @@ int bgemm_mi355x_selfcheck_launch_ta_bias_act(int ta_config, int splits, int ope
                                               int act, long long out[20]) {
   if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
   return tr_selfcheck_launch(kLayoutTA, TR_BF16, out_bias_act(act), ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- the same forward product that also writes the rounded pre-activation (the kinds TR_C16_BIAS_AUX + act): z_out = bf16(z) at row stride
+// ldz and C = bf16(act32(z)) of the unrounded z -- C is bgemm_mi355x_launch_tn_bias_act's and z_out bgemm_mi355x_launch_tn_bias's, bit for
+// bit, for the same arguments and plan.  z_out has C's rules; NULL and z_out == c are HGEMM_ERR_BAD_ARG.
+int bgemm_mi355x_tn_bias_act_aux_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz) {
+  return tr_runs(kLayoutTN, TR_BF16, out_bias_act_aux(HGEMM_ACT_RELU, ldz), tn_config, M, N, K, lda, ldb, ldc);
+}
+int bgemm_mi355x_launch_tn_bias_act_aux(int tn_config, int splits_arg, const void* a, const void* b_col_major, const void* bias, void* c, void* z_out,
+                                        int M, int N, int K, int lda, int ldb, int ldc, int ldz, int act, void* stream) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutTN, TR_BF16, out_bias_act_aux(act, ldz), tn_config, splits_arg, a, b_col_major, bias, c, M, N, K, lda, ldb, ldc, stream, z_out);
+}
+int bgemm_mi355x_tn_bias_act_aux(const void* a, const void* b_col_major, const void* bias, void* c, void* z_out, int M, int N, int K, int act,
+                                 void* stream) {
+  if (!act_known(act) || !bias || !z_out) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutTN, TR_BF16, out_bias_act_aux(act, N), a, b_col_major, bias, c, M, N, K, stream, z_out);
+}
+// (bgemm_mi355x_selfcheck_launch_tn_bias_act's output; operands & 4: a, b, bias, c AND z_out are 16-byte aligned)
+int bgemm_mi355x_selfcheck_launch_tn_bias_act_aux(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                                                  int ruled_out, int act, long long out[20]) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, out_bias_act_aux(act, ldz), tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- the input gradient through the activation, dZ = (dY W) (.) act'(Z) (the kinds TR_C16_DACT + act, family n, bf16): C = bf16(S x
+// dact32(float(z[m][n]))), one fp32 multiply on the finished sum (ReLU: a select) and one rounding; hgemm_act.hpp's dact_mul in the kernel's
+// epilogue, in the combine and in the reference kernel.  A call resolves to the plan of the bgemm_mi355x_launch_nn call with the same
+// arguments; only the epi id of the plain dispatch and of the combine dispatch differs.  z is read-only and has C's rules.
+int bgemm_mi355x_nn_dact_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz) {
+  return tr_runs(kLayoutNN, TR_BF16, out_dact(HGEMM_ACT_RELU, ldz), nn_config, M, N, K, lda, ldb, ldc);
+}
+int bgemm_mi355x_launch_nn_dact(int nn_config, int splits_arg, const void* a, const void* b, const void* z, void* c, int M, int N, int K, int lda,
+                                int ldb, int ldc, int ldz, int act, void* stream) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutNN, TR_BF16, out_dact(act, ldz), nn_config, splits_arg, a, b, nullptr, c, M, N, K, lda, ldb, ldc, stream, const_cast<void*>(z));
+}
+int bgemm_mi355x_nn_dact(const void* a, const void* b, const void* z, void* c, int M, int N, int K, int act, void* stream) {
+  if (!act_known(act) || !z) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutNN, TR_BF16, out_dact(act, N), a, b, nullptr, c, M, N, K, stream, const_cast<void*>(z));
+}
+// (not part of the public header: the byte range of the dact kernels' Z descriptor for the tile at row m0, the kernels' own function)
+unsigned bgemm_mi355x_selfcheck_dact_z_range(int M, int N, int ldz, int m0) { return dact_z_range_bytes(M, N, ldz, m0); }
+int bgemm_mi355x_selfcheck_launch_nn_dact(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                                          int ruled_out, int act, long long out[20]) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_dact(act, ldz), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // Host-side self-check hook (tests/test_host_logic.py; not part of the public header): the raster map of the

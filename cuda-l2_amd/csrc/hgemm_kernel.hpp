@@ -298,6 +298,14 @@ constexpr int EPI_C16_BIAS = 5;  // bf16 C with a fused bias (family f, bgemm_mi
 // (hgemm_act.hpp) applied to the unrounded fp32 sum and the result rounded once.  EPI_C16_BIAS + the activation's id, a compile-time
 // property of the kernel.  (Family f takes neither flag below, so its 8 is no EPI_KTAIL.)
 constexpr int EPI_C16_BIAS_RELU = 6, EPI_C16_BIAS_GELU = 7, EPI_C16_BIAS_GELU_TANH = 8;
+// The same with the rounded pre-activation written as a second output (family f, bgemm_mi355x_tn_bias_act_aux): z_out = bf16(z) and
+// C = bf16(act(z)), z = acc + float(bias[n]) unrounded.  EPI_C16_BIAS_AUX + the activation's id: 9 / 10 / 11.  g.partial holds z_out and
+// g.tail_first its row stride ldz, two fields a non-slab launch of families n and f leaves idle (tail_tiles stays 0).
+constexpr int EPI_C16_BIAS_AUX = 8;
+// bf16 C through an activation's derivative (family n, bgemm_mi355x_nn_dact): C = bf16(acc x act'(float(z[m][n]))), one fp32 multiply on
+// the finished sum (ReLU: a select), rounded once.  EPI_C16_DACT + the activation's id: 12 / 13 / 14.  g.counters holds the read-only bf16
+// z and g.tail_first its row stride ldz.  All below EPI_KSTAGGER; neither family takes a flag.
+constexpr int EPI_C16_DACT = 11;
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

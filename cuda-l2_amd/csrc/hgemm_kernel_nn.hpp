@@ -32,6 +32,7 @@
 //     any form tried and stay in each kernel, on purpose; an edit to one of them is made in all three.
 #pragma once
 
+#include "hgemm_act.hpp"
 #include "hgemm_launch.hpp"
 
 namespace hgemm_mi355x {
@@ -80,6 +81,23 @@ typedef __attribute__((address_space(3))) tr_t lds_tr_t;
 template <class CFG, int EPI>
 __global__ void hgemm_nn_kernel(const GemmArgs g);
 
+// EPI_C16_DACT + ACT_* (hgemm_act.hpp): the bf16 C through the activation's derivative at a saved pre-activation (bgemm_mi355x_nn_dact);
+// the CfgNNB members only.
+constexpr bool epi_is_dact(int epi) { return epi > EPI_C16_DACT && epi <= EPI_C16_DACT + ACT_GELU_TANH; }
+constexpr int epi_dact(int epi) { return epi_is_dact(epi) ? epi - EPI_C16_DACT : ACT_NONE; }
+// The byte range of the Z descriptor of the tile whose first row is m0: from that row to Z's last valid element (M - 1, N - 1), computed in
+// 64 bits and CLAMPED to the descriptor's 32: M is not limited by the host, only a tile's reach is, so a Z of 4 GiB and more is in scope
+// and the distance to its end need not fit.  Where the clamp acts, the matrix goes on for more than 4 GiB behind the tile's first row
+// while the tile's own offsets stay below (BM ldz + N) 2 + 2 BN < 2^32 (host check: the first term below 2 GiB) -- every row of such a
+// tile is a valid row and the range covers all of them; where it does not act, the range ends at the last valid element exactly.
+// (hgemm_api.hip shows it to the CPU tests.)
+__host__ __device__ constexpr uint32_t dact_z_range_bytes(int M, int N, int ldz, int m0) {
+  const unsigned long long bytes = ((unsigned long long)(M - 1 - m0) * (unsigned long long)ldz + (unsigned long long)N) * 2ull;
+  return bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bytes;
+}
+static_assert(dact_z_range_bytes(262144, 8192, 8192, 0) == 0xFFFFFFFFu && dact_z_range_bytes(262144, 8192, 8192, 262016) == (127u * 8192u + 8192u) * 2u &&
+              dact_z_range_bytes(1, 8, 8, 0) == 16u, "a range of 2^32 bytes and more is clamped, not wrapped");
+
 // family n: the classic A image, [BM rows][128 B]
 template <int BM_, int BN_, int WM_, int WN_, int NBUF_>
 struct CfgNN : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
@@ -126,7 +144,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
   using elem = typename CFG::elem;   // f16, or __bf16 (the bgemm_ entry points)
   using ex4 = __attribute__((ext_vector_type(4))) elem;
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB, "plain and two-pass slab epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || (epi_is_dact(EPI) && __is_same(elem, __bf16)), "plain, two-pass slab and (bf16) dact epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -242,6 +260,46 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
     wr = (wr + 1 == NBUF) ? 0 : wr + 1;
   }
 
+  // ---- the activation's derivative (EPI_C16_DACT + ACT, bgemm_mi355x_nn_dact): C = bf16(acc x act'(float(z[m][n]))) ------------------------
+  // g.counters is the saved bf16 pre-activation Z ([M][ldz], read-only; the host puts it there for this epilogue alone, ldz in
+  // g.tail_first: GemmArgs keeps its layout).  tr_mfma(bf, af, acc) leaves lane (row = lane & 15, q = lane >> 4) with
+  // acc[i][j][e] = C[16 i + row][16 j + 4 q + e], so the lane's four z of a fragment are one 8-byte load.  The descriptor starts at the
+  // tile's first row and ENDS AT THE LAST VALID ELEMENT, (M - 1, N - 1): a row at or past M is out of range and reads zeros; a column
+  // group at or past N (N % 8 == 0: wholly inside or wholly behind) reads pad or the next row, inside the range, or zeros behind its end.
+  // Both feed only values the store text never stores.  The offset stays below (BM ldz + N) 2 + 2 BN < 2^32 (host check: below 2 GiB); the
+  // range is dact_z_range_bytes above, clamped where Z goes on for 4 GiB and more behind the tile's first row.
+  // Issued HERE, behind the K loop, as family f's bias loads are: the loop keeps the EPI_C16 kernel's registers and its counted vmcnt.
+  // dact_mul (hgemm_act.hpp) is the combine's and the reference kernel's text: one fp32 multiply on the finished sum, ReLU a select.
+  // The sched_barrier per fragment and the parking asm are hgemm_kernel_tn.hpp's register steering.
+  if constexpr (epi_is_dact(EPI)) {
+    using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+    using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+    const uint32_t ldz = (uint32_t)g.tail_first;
+    const uint32_t z_bytes = dact_z_range_bytes(g.M, g.N, g.tail_first, tc.m0);
+    const __amdgpu_buffer_rsrc_t rsZ =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)g.counters + (size_t)tc.m0 * ldz), 0, z_bytes, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const uint32_t row = (uint32_t)(wave_m * CFG::TM + i * 16 + (lane & 15));
+      bx4 z[FN];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const uint32_t n_z = (uint32_t)(tc.n0 + wave_n * CFG::TN + 16 * j + 4 * (lane >> 4));
+        z[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsZ, (row * ldz + n_z) * 2u, 0, 0));
+      }
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float y = dact_mul<epi_dact(EPI)>(acc[i][j][e], (float)z[j][e]);
+          asm volatile("" : "+a"(y));
+          acc[i][j][e] = y;
+        }
+      }
+    }
+  }
+
   if constexpr (EPI == EPI_SLAB) {
     store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
   } else {
@@ -285,6 +343,21 @@ using TrLaunch = void (*)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
 HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNN, false)    // hgemm_inst_g5.hip
 HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNNB, false)   // hgemm_inst_g8.hip
 
+// The dact sets (bgemm_mi355x_nn_dact), one per activation: the member's EPI_C16_DACT + ACT kernel alone; the K slices of a two-pass
+// form are the bf16 16-bit set's EPI_SLAB kernels, reached through that set's launcher in its own unit.  g.counters of the dact dispatch
+// is Z, g.tail_first its row stride (tr_launch, hgemm_api.hip).
+template <class CFG, int ACT>
+void launch_nn_dact(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_DACT + ACT>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_NN_DACT_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_nn_dact<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_NN_DACT_INST(...) template void HGEMM_NN_DACT_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_NN_DACT_EXTERN(...) extern HGEMM_NN_DACT_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_RELU, CfgNNB)        // hgemm_inst_g16.hip
+HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU, CfgNNB)
+HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU_TANH, CfgNNB)
+
 // A layout's table (hgemm_registry.hip builds both, each by one expansion of the member list: a config id is a position in `rows`; the
 // geometry table of hgemm_configs*.def does not know these families).  A row is the member's geometry and its launcher in every kernel
 // set of the layout; TrKernels is what a set has besides: the combine of the two-pass form and the reference kernel (status 0, exact:
@@ -298,17 +371,25 @@ struct TrEntry {
 enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C hold: 2 bytes either way
 // The output kinds of a layout: a 16-bit C, an fp32 C (family a), a 16-bit C with a fused bias (family f: bgemm_mi355x_tn_bias).
 // TR_C16_BIAS + a (a = 1, 2, 3: hgemm_act.hpp's ACT_RELU / _GELU / _GELU_TANH): the bias followed by that activation (bgemm_mi355x_tn_bias_act).
-enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_C16_BIAS_GELU = 4, TR_C16_BIAS_GELU_TANH = 5, TR_KINDS = 6 };
+// TR_C16_BIAS_AUX + a: the same with the rounded pre-activation as a second output (bgemm_mi355x_tn_bias_act_aux).  TR_C16_DACT + a: a
+// 16-bit C through that activation's derivative at a saved pre-activation (family n: bgemm_mi355x_nn_dact).
+enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_C16_BIAS_GELU = 4, TR_C16_BIAS_GELU_TANH = 5,
+              TR_C16_BIAS_AUX = 5, TR_C16_DACT = 8, TR_KINDS = 12 };
 struct TrRow {
   TrEntry e;
   TrLaunch launch[2][TR_KINDS];   // [TrElem][TrKind]
 };
 // `bias`: the bf16 bias vector of the TR_C16_BIAS sets (N elements, added last in fp32, the sum rounded once); every other set is handed
-// nullptr and ignores it.
+// nullptr and ignores it.  The sets with a second matrix -- TR_C16_BIAS_AUX + a: the output z_out, TR_C16_DACT + a: the input z, `z` with
+// its row stride ldz either way -- have combine_z / reference_z in their place (the other pair is null).
 struct TrKernels {
   void (*combine)(const float* partial, void* c, const void* bias, int M, int N, int ldc, int splits, bool accumulate, hipStream_t, TimingSlot);
   void (*reference)(const void* a, const void* b, void* c, const void* bias, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
                     hipStream_t, TimingSlot);
+  void (*combine_z)(const float* partial, void* c, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits, hipStream_t, TimingSlot);
+  void (*reference_z)(const void* a, const void* b, void* c, const void* bias, void* z, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                      hipStream_t, TimingSlot);
+  bool present() const { return reference || reference_z; }
 };
 struct TrTable {
   const TrRow* rows;

@@ -32,8 +32,12 @@
 namespace hgemm_mi355x {
 
 // The epilogues with a bias vector: EPI_C16_BIAS and, with an activation behind the add, EPI_C16_BIAS + ACT_* (hgemm_act.hpp).
-constexpr bool epi_has_bias(int epi) { return epi >= EPI_C16_BIAS && epi <= EPI_C16_BIAS_GELU_TANH; }
-constexpr int epi_act(int epi) { return epi_has_bias(epi) ? epi - EPI_C16_BIAS : ACT_NONE; }
+// EPI_C16_BIAS_AUX + ACT_*: the activation forms that also write the rounded pre-activation (bgemm_mi355x_tn_bias_act_aux).
+constexpr bool epi_has_aux(int epi) { return epi > EPI_C16_BIAS_AUX && epi <= EPI_C16_BIAS_AUX + ACT_GELU_TANH; }
+constexpr bool epi_has_bias(int epi) { return (epi >= EPI_C16_BIAS && epi <= EPI_C16_BIAS_GELU_TANH) || epi_has_aux(epi); }
+constexpr int epi_act(int epi) { return epi_has_aux(epi) ? epi - EPI_C16_BIAS_AUX : epi_has_bias(epi) ? epi - EPI_C16_BIAS : ACT_NONE; }
+static_assert(epi_act(EPI_C16_BIAS_AUX + ACT_RELU) == ACT_RELU && epi_act(EPI_C16_BIAS_AUX + ACT_GELU_TANH) == ACT_GELU_TANH &&
+              !epi_has_aux(EPI_C16_BIAS_GELU_TANH) && !epi_has_bias(EPI_C16_DACT + ACT_RELU), "the aux ids follow the activation ids");
 static_assert(epi_act(EPI_C16_BIAS_RELU) == ACT_RELU && epi_act(EPI_C16_BIAS_GELU) == ACT_GELU && epi_act(EPI_C16_BIAS_GELU_TANH) == ACT_GELU_TANH &&
               epi_act(EPI_C16_BIAS) == ACT_NONE, "an activation's epilogue id is EPI_C16_BIAS + its ACT_ id");
 
@@ -60,7 +64,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
   using elem = typename CFG::elem;   // __bf16
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || epi_has_bias(EPI), "plain, two-pass slab, fused-bias and fused-bias-activation epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || epi_has_bias(EPI), "plain, two-pass slab, fused-bias, fused-bias-activation and pre-activation-output epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -178,6 +182,18 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
         for (int e = 0; e < 4; ++e) acc[i][j][e] += (float)bias[j][e];
   }
 
+  // ---- the rounded pre-activation as a second output (EPI_C16_BIAS_AUX + ACT, bgemm_mi355x_tn_bias_act_aux): z_out = bf16(z) ----------------
+  // The finished z values go through the shared 16-bit C store text, entered here with z_out (g.partial, reinterpreted) and its row
+  // stride ldz (g.tail_first) in place of C and ldc: the same convert, swap, predicate and 16-byte buffer stores, the NT form included.
+  // acc is only read; the activation below then works on the unrounded z, as in the kernels without this output.
+  if constexpr (epi_has_aux(EPI)) {
+#define HGEMM_TR_STORE_C ((f16*)g.partial)
+#define HGEMM_TR_STORE_LD g.tail_first
+#include "hgemm_tr_store_c16.inc"
+#undef HGEMM_TR_STORE_C
+#undef HGEMM_TR_STORE_LD
+  }
+
   // ---- fused activation (EPI_C16_BIAS + ACT, bgemm_mi355x_tn_bias_act): C = bf16(act(z)), z the unrounded fp32 value above -------------------
   // act_apply (hgemm_act.hpp) is the text the combine and the reference kernel use; it works on the lane's own pre-swap values, so the
   // ownership is the bias code's.  A compile-time property of the kernel: no runtime branch, and the kernels without one compile as before.
@@ -238,5 +254,19 @@ void launch_tn_bias_act(const GemmArgs& g, int grid, hipStream_t stream, int epi
 HGEMM_TR_MEMBERS(HGEMM_TN_ACT_EXTERN, ACT_RELU, CfgTNB)        // hgemm_inst_g14.hip
 HGEMM_TR_MEMBERS(HGEMM_TN_ACT_EXTERN, ACT_GELU, CfgTNB)
 HGEMM_TR_MEMBERS(HGEMM_TN_ACT_EXTERN, ACT_GELU_TANH, CfgTNB)
+
+// The sets that also write the pre-activation (bgemm_mi355x_tn_bias_act_aux), one per activation: the member's EPI_C16_BIAS_AUX + ACT
+// kernel alone, the K slices again the 16-bit set's EPI_SLAB kernels.
+template <class CFG, int ACT>
+void launch_tn_bias_act_aux(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_BIAS_AUX + ACT>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_TN_AUX_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_tn_bias_act_aux<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_TN_AUX_INST(...) template void HGEMM_TN_AUX_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TN_AUX_EXTERN(...) extern HGEMM_TN_AUX_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_TN_AUX_EXTERN, ACT_RELU, CfgTNB)        // hgemm_inst_g15.hip
+HGEMM_TR_MEMBERS(HGEMM_TN_AUX_EXTERN, ACT_GELU, CfgTNB)
+HGEMM_TR_MEMBERS(HGEMM_TN_AUX_EXTERN, ACT_GELU_TANH, CfgTNB)
 
 }  // namespace hgemm_mi355x

@@ -332,6 +332,106 @@ __global__ void __launch_bounds__(256) hgemm_generic_tn_bias_act_kernel(const __
   }
 }
 
+// The combine of bgemm_mi355x_tn_bias_act_aux: hgemm_splitk_reduce_bias_act_kernel's text with a second output -- the slabs in split
+// order, the bias as one fp32 add, then z_out = bf16(z) at stride ldz and C = bf16(act_apply<ACT>(z)) of the UNROUNDED z.  No slab is touched.
+template <int ACT>
+__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bias_act_aux_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
+                                                                               const __bf16* __restrict__ bias, __bf16* __restrict__ Z, int M,
+                                                                               int N, int ldc, int ldz, int splits) {
+  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+  const size_t total4 = ((size_t)M * N) >> 2;
+  const size_t slab   = (size_t)M * N;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = q << 2;
+    const int m = (int)(e / N), n = (int)(e % N);
+    const bx4 b = *(const bx4*)(bias + n);   // in flight with the slab loads
+    f32x4 s = *(const f32x4*)(partial + e);
+    int k = 1;
+    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
+      f32x4 p[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += p[u];
+    }
+    for (; k < splits; ++k) {
+      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
+      s += p;
+    }
+    const float z0 = s[0] + (float)b[0], z1 = s[1] + (float)b[1], z2 = s[2] + (float)b[2], z3 = s[3] + (float)b[3];
+    const bx4 zo = {(__bf16)z0, (__bf16)z1, (__bf16)z2, (__bf16)z3};
+    *(bx4*)(Z + (size_t)m * ldz + n) = zo;
+    const bx4 o = {(__bf16)act_apply<ACT>(z0), (__bf16)act_apply<ACT>(z1), (__bf16)act_apply<ACT>(z2), (__bf16)act_apply<ACT>(z3)};
+    *(bx4*)(C + (size_t)m * ldc + n) = o;
+  }
+}
+
+// The reference kernel of bgemm_mi355x_tn_bias_act_aux: hgemm_generic_tn_bias_act_kernel's chain and add, both outputs from the one z.
+template <int ACT>
+__global__ void __launch_bounds__(256) hgemm_generic_tn_bias_act_aux_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bcol,
+                                                                            __bf16* __restrict__ C, const __bf16* __restrict__ bias,
+                                                                            __bf16* __restrict__ Z, int M, int N, int K, int lda,
+                                                                            int ldb_colmajor, int ldc, int ldz) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  const float b = (float)bias[n];
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
+    const float z = s + b;
+    Z[(size_t)m * ldz + n] = (__bf16)z;
+    C[(size_t)m * ldc + n] = (__bf16)act_apply<ACT>(z);
+  }
+}
+
+// The combine of bgemm_mi355x_nn_dact: the slabs added in split order (hgemm_splitk_reduce_kernel), THEN dact_mul<ACT> (hgemm_act.hpp, the
+// kernels' own text) of the finished sum and float(Z[m][n]) -- one fp32 multiply, ReLU a select --, then the one rounding to bf16.  No
+// slab is multiplied.  (N % 8 == 0, ldz % 8 == 0 and a 16-byte aligned Z on this path: the four z of a quad are one aligned 8-byte load.)
+template <int ACT>
+__global__ void __launch_bounds__(256) hgemm_splitk_reduce_dact_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
+                                                                       const __bf16* __restrict__ Z, int M, int N, int ldc, int ldz,
+                                                                       int splits) {
+  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+  const size_t total4 = ((size_t)M * N) >> 2;
+  const size_t slab   = (size_t)M * N;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = q << 2;
+    const int m = (int)(e / N), n = (int)(e % N);
+    const bx4 z = *(const bx4*)(Z + (size_t)m * ldz + n);   // in flight with the slab loads
+    f32x4 s = *(const f32x4*)(partial + e);
+    int k = 1;
+    for (; k + 8 <= splits; k += 8) {
+      f32x4 p[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += p[u];
+    }
+    for (; k < splits; ++k) {
+      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
+      s += p;
+    }
+    const bx4 o = {(__bf16)dact_mul<ACT>(s[0], (float)z[0]), (__bf16)dact_mul<ACT>(s[1], (float)z[1]),
+                   (__bf16)dact_mul<ACT>(s[2], (float)z[2]), (__bf16)dact_mul<ACT>(s[3], (float)z[3])};
+    *(bx4*)(C + (size_t)m * ldc + n) = o;
+  }
+}
+
+// The reference kernel of bgemm_mi355x_nn_dact: hgemm_generic_kernel's fma chain in k order (B row-major), dact_mul<ACT>, one rounding.
+// Any shape, stride and alignment (Z 2-byte aligned).
+template <int ACT>
+__global__ void __launch_bounds__(256) hgemm_generic_nn_dact_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
+                                                                    __bf16* __restrict__ C, const __bf16* __restrict__ Z, int M, int N, int K,
+                                                                    int lda, int ldb_rowmajor, int ldc, int ldz) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    float s = 0.f;
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
+    C[(size_t)m * ldc + n] = (__bf16)dact_mul<ACT>(s, (float)Z[(size_t)m * ldz + n]);
+  }
+}
+
 // ---- launchers of the combines and the reference kernels, with the signatures of TrKernels (hgemm_kernel_nn.hpp) ----------------------
 // grid and block of a combine: a thread per four outputs
 struct CombineGrid { int grid, threads; };
@@ -407,6 +507,36 @@ static void launch_reference_tn_bias_act(const void* A, const void* Bcol, void* 
                (const __bf16*)bias, M, N, K, lda, ldb, ldc);
 }
 
+// the sets with a second matrix (TrKernels::combine_z / reference_z): bgemm_mi355x_tn_bias_act_aux's z_out, bgemm_mi355x_nn_dact's z
+template <int ACT>
+static void launch_combine_aux(const float* partial, void* C, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits,
+                               hipStream_t stream, TimingSlot ts) {
+  const CombineGrid cg = combine_grid(M, N);
+  HGEMM_LAUNCH((hgemm_splitk_reduce_bias_act_aux_kernel<ACT>), cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)bias,
+               (__bf16*)z, M, N, ldc, ldz, splits);
+}
+template <int ACT>
+static void launch_reference_tn_aux(const void* A, const void* Bcol, void* C, const void* bias, void* z, int M, int N, int K, int lda, int ldb,
+                                    int ldc, int ldz, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH((hgemm_generic_tn_bias_act_aux_kernel<ACT>), grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)Bcol, (__bf16*)C,
+               (const __bf16*)bias, (__bf16*)z, M, N, K, lda, ldb, ldc, ldz);
+}
+template <int ACT>
+static void launch_combine_dact(const float* partial, void* C, const void*, void* z, int M, int N, int ldc, int ldz, int splits,
+                                hipStream_t stream, TimingSlot ts) {
+  const CombineGrid cg = combine_grid(M, N);
+  HGEMM_LAUNCH((hgemm_splitk_reduce_dact_kernel<ACT>), cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)z, M, N, ldc, ldz,
+               splits);
+}
+template <int ACT>
+static void launch_reference_nn_dact(const void* A, const void* B, void* C, const void*, void* z, int M, int N, int K, int lda, int ldb, int ldc,
+                                     int ldz, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
+  HGEMM_LAUNCH((hgemm_generic_nn_dact_kernel<ACT>), grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)B, (__bf16*)C, (const __bf16*)z, M,
+               N, K, lda, ldb, ldc, ldz);
+}
+
 // the b_col_major families' names for their two (hgemm_launch.hpp)
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
@@ -426,23 +556,36 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
 // named, and a table of host function pointers at namespace scope would be emitted as a device constant.)
 #define HGEMM_NN_ROW(P, ...)                                                                                \
   {HGEMM_TR_ENTRY(P, CfgNN, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgNN, false, __VA_ARGS__), nullptr},        \
-                                           {&HGEMM_TR_LAUNCHER(CfgNNB, false, __VA_ARGS__), nullptr}}},
+                                           {&HGEMM_TR_LAUNCHER(CfgNNB, false, __VA_ARGS__), nullptr, nullptr, nullptr, nullptr, nullptr, \
+                                            nullptr, nullptr, nullptr,   /* the bf16 dact sets, TR_C16_DACT + ACT_* */                   \
+                                            &HGEMM_NN_DACT_LAUNCHER(ACT_RELU, CfgNNB, __VA_ARGS__),                                      \
+                                            &HGEMM_NN_DACT_LAUNCHER(ACT_GELU, CfgNNB, __VA_ARGS__),                                      \
+                                            &HGEMM_NN_DACT_LAUNCHER(ACT_GELU_TANH, CfgNNB, __VA_ARGS__)}}},
 #define HGEMM_TA_ROW(P, ...)                                                                                                                 \
   {HGEMM_TR_ENTRY(P, CfgTA, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgTA, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTA, true, __VA_ARGS__)},    \
                                            {&HGEMM_TR_LAUNCHER(CfgTAB, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTAB, true, __VA_ARGS__)}}},
-// TN (family f, hgemm_kernel_tn.hpp): the bf16 sets with a 16-bit C -- plain, with the fused bias, and with the bias and each activation
-// (TR_C16_BIAS + ACT_*) --; every other cell is empty and a call for it is refused
+// TN (family f, hgemm_kernel_tn.hpp): the bf16 sets with a 16-bit C -- plain, with the fused bias, with the bias and each activation
+// (TR_C16_BIAS + ACT_*), and those again with the pre-activation as a second output (TR_C16_BIAS_AUX + ACT_*) --; every other cell is empty and a call for it is refused
 #define HGEMM_TN_ROW(P, ...)                                                                                        \
   {HGEMM_TR_ENTRY(P, CfgTNB, __VA_ARGS__), {{nullptr, nullptr}, {&HGEMM_TR_LAUNCHER(CfgTNB, false, __VA_ARGS__), nullptr, \
                                                                  &HGEMM_TN_BIAS_LAUNCHER(CfgTNB, __VA_ARGS__),            \
                                                                  &HGEMM_TN_ACT_LAUNCHER(ACT_RELU, CfgTNB, __VA_ARGS__),   \
                                                                  &HGEMM_TN_ACT_LAUNCHER(ACT_GELU, CfgTNB, __VA_ARGS__),   \
-                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_GELU_TANH, CfgTNB, __VA_ARGS__)}}},
+                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_GELU_TANH, CfgTNB, __VA_ARGS__), \
+                                                                 &HGEMM_TN_AUX_LAUNCHER(ACT_RELU, CfgTNB, __VA_ARGS__),   \
+                                                                 &HGEMM_TN_AUX_LAUNCHER(ACT_GELU, CfgTNB, __VA_ARGS__),   \
+                                                                 &HGEMM_TN_AUX_LAUNCHER(ACT_GELU_TANH, CfgTNB, __VA_ARGS__)}}},
+// The cells of the rows and of `kernels` are positional: these are the slots the initialisers below count out.
+static_assert(TR_C16_BIAS == 2 && TR_C16_BIAS + ACT_RELU == 3 && TR_C16_BIAS_AUX + ACT_RELU == 6 && TR_C16_DACT + ACT_RELU == 9 &&
+              TR_C16_DACT + ACT_GELU_TANH == 11 && TR_KINDS == 12, "the slots of the positional initialisers of the three tables");
 const TrTable& tr_table_nn() {
   static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_NN_ROW, "n")};
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
                             {{{launch_combine<f16>, launch_reference<f16, false, false>}, {}},
-                             {{launch_combine<__bf16>, launch_reference<__bf16, false, false>}, {}}}};
+                             {{launch_combine<__bf16>, launch_reference<__bf16, false, false>}, {}, {}, {}, {}, {}, {}, {}, {},
+                              {nullptr, nullptr, launch_combine_dact<ACT_RELU>, launch_reference_nn_dact<ACT_RELU>},
+                              {nullptr, nullptr, launch_combine_dact<ACT_GELU>, launch_reference_nn_dact<ACT_GELU>},
+                              {nullptr, nullptr, launch_combine_dact<ACT_GELU_TANH>, launch_reference_nn_dact<ACT_GELU_TANH>}}}};
   return t;
 }
 const TrTable& tr_table_ta() {
@@ -459,7 +602,10 @@ const TrTable& tr_table_tn() {
                             {{{}, {}}, {{launch_combine<__bf16>, launch_reference_tn<__bf16>}, {}, {launch_combine_bias, launch_reference_tn_bias},
                                         {launch_combine_bias_act<ACT_RELU>, launch_reference_tn_bias_act<ACT_RELU>},
                                         {launch_combine_bias_act<ACT_GELU>, launch_reference_tn_bias_act<ACT_GELU>},
-                                        {launch_combine_bias_act<ACT_GELU_TANH>, launch_reference_tn_bias_act<ACT_GELU_TANH>}}}};
+                                        {launch_combine_bias_act<ACT_GELU_TANH>, launch_reference_tn_bias_act<ACT_GELU_TANH>},
+                                        {nullptr, nullptr, launch_combine_aux<ACT_RELU>, launch_reference_tn_aux<ACT_RELU>},
+                                        {nullptr, nullptr, launch_combine_aux<ACT_GELU>, launch_reference_tn_aux<ACT_GELU>},
+                                        {nullptr, nullptr, launch_combine_aux<ACT_GELU_TANH>, launch_reference_tn_aux<ACT_GELU_TANH>}}}};
   return t;
 }
 

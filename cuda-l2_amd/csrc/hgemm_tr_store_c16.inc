@@ -9,8 +9,17 @@
 // the even rows of tile j + 1, after which row q = lane >> 4 owns n = 16 (j + (q & 1)) + 8 (q >> 1) + 0 .. 7 of its C row.  Buffer
 // stores: the non-temporal form is an instruction of its own (two plain C++ stores that differ only in the hint are merged by the
 // optimiser and the hint is lost); the tile's bytes are below 2 GiB from its first row (host check).
+// HGEMM_TR_STORE_C / HGEMM_TR_STORE_LD: the output's base pointer and row stride, g.C and g.ldc unless the including kernel names others
+// (family f's second output, bgemm_mi355x_tn_bias_act_aux, enters the text a second time with z_out and ldz).  A block of its own, so
+// that it can be entered twice.
+#ifndef HGEMM_TR_STORE_C
+#define HGEMM_TR_STORE_C g.C
+#define HGEMM_TR_STORE_LD g.ldc
+#define HGEMM_TR_STORE_DEFAULTS
+#endif
+  {
     using h2 = __attribute__((ext_vector_type(2))) elem;
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(HGEMM_TR_STORE_C + (size_t)tc.m0 * HGEMM_TR_STORE_LD), 0, 0xFFFFFFFFu, 0x00020000);
     const int q = lane >> 4;
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
@@ -25,9 +34,15 @@
         const int n = tc.n0 + wave_n * CFG::TN + 16 * (j + (q & 1)) + 8 * (q >> 1);
         if (tc.m0 + row < g.M && n < g.N) {
           const u32x4 o = {r0[0], r1[0], r0[1], r1[1]};
-          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
+          const uint32_t off = ((uint32_t)row * (uint32_t)HGEMM_TR_STORE_LD + (uint32_t)n) * 2u;
           if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 2);
           else                        __builtin_amdgcn_raw_buffer_store_b128(o, rsC, off, 0, 0);
         }
       }
     }
+  }
+#ifdef HGEMM_TR_STORE_DEFAULTS
+#undef HGEMM_TR_STORE_C
+#undef HGEMM_TR_STORE_LD
+#undef HGEMM_TR_STORE_DEFAULTS
+#endif

@@ -37,6 +37,10 @@
 //   hgemm_tune bench --layout tn --bf16 --bias --shapes ... [--out F.jsonl]   against the same plan without a bias, "bias_le_plain"
 //   hgemm_tune check --layout tn --bf16 --bias --act relu|gelu|gelu_tanh [--shapes ...]   the fused bias+activation calls
 //                                                     (bgemm_mi355x_launch_tn_bias_act): ReLU bit for bit, the GELUs inside their bar
+//   hgemm_tune check|bench --layout tn --bf16 --bias --act A --aux [...]   bgemm_mi355x_tn_bias_act_aux: C to the bars above, z_out = bf16(z)
+//                                                     bit for bit; bench against bgemm_mi355x_launch_tn_bias + an element-wise act(Z) kernel
+//   hgemm_tune check|bench --layout nn --bf16 --dact relu|gelu|gelu_tanh [...]   bgemm_mi355x_nn_dact: ReLU bit for bit, the GELUs inside
+//                                                     1/2 ulp_bf16(S g*) + 2^-19 |S|; bench against bgemm_mi355x_launch_nn + an element-wise kernel
 //   hgemm_tune bench --layout tn --bf16 --bias --act A --shapes ... [--out F.jsonl]   against bgemm_mi355x_launch_tn_bias followed by an
 //                                                     element-wise activation kernel, "act_le_unfused"
 //                                                     that check first, then per shape interleaved rounds of the planned call, of
@@ -1084,7 +1088,7 @@ static const TrLayout kLayoutTN = {"tn", "the TN kernels", kShapesNN, false, tru
 
 // One call's operands.  Every variant's entry points sit behind the same two signatures; what a variant has no use for (bias,
 // accumulate) its adapter drops.
-struct TrCall { const void *a, *b, *bias; void* c; int accumulate; };
+struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; };   // z: z_out of --aux, Z of --dact
 template <auto F> static int launch16(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: a 16-bit-C launch
   return F(cfg, splits, o.a, o.b, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
@@ -1342,9 +1346,12 @@ struct TrBench {
 };
 
 static int g_act = 0;   // --act: 0, or HGEMM_ACT_RELU / _GELU / _GELU_TANH (the fused bias+activation calls, below)
+static bool g_aux = false;   // --aux (with --act): bgemm_mi355x_tn_bias_act_aux, the same call that also writes z_out
+static int g_dact = 0;       // --dact A (with --layout nn --bf16): bgemm_mi355x_nn_dact
 static int act_check(std::vector<Shape> shapes);
+static int dact_check(std::vector<Shape> shapes);
 static int tr_bench(const Variant& V, const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
-  const int rc = g_act ? act_check({}) : tr_check(V, {});   // no timing of a kernel that is wrong
+  const int rc = g_dact ? dact_check({}) : g_act ? act_check({}) : tr_check(V, {});   // no timing of a kernel that is wrong
   if (rc != 0) { fprintf(stderr, "bench %s: the check failed, nothing is timed\n", V.words("--layout ", " --").c_str()); return rc; }
   FILE* out = out_path ? fopen(out_path, "w") : stdout;
   if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
@@ -1520,17 +1527,30 @@ static const BenchDesc kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act};
 // (not in kVariants: resolve_variant answers the flags without --act; main swaps this one in when --act is given)
 static const Variant kVariantTNBiasAct = {&kLayoutTN, kBF16, kC16Bias, bgemm_mi355x_tn_bias_act_runs, launch_bias_act, planned_bias_act, &kBenchTNBiasAct};
 
+// --aux: the same call with the pre-activation as a second output, z_out = bf16(z), held bit for bit next to C's bars
+static int launch_bias_act_aux(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_bias_act_aux(cfg, splits, o.a, o.b, o.bias, o.c, o.z, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, g_act, nullptr);
+}
+static int planned_bias_act_aux(const TrCall& o, const Shape& sh) {
+  return bgemm_mi355x_tn_bias_act_aux(o.a, o.b, o.bias, o.c, o.z, sh.M, sh.N, sh.K, g_act, nullptr);
+}
+static int aux_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_tn_bias_act_aux_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+static void bench_tn_aux(TrBench&);
+static const BenchDesc kBenchTNAux = {91, warm_none, bench_tn_aux};
+static const Variant kVariantTNAux = {&kLayoutTN, kBF16, kC16Bias, aux_runs, launch_bias_act_aux, planned_bias_act_aux, &kBenchTNAux};
+
 static int act_check(std::vector<Shape> shapes) {
-  const Variant& V = kVariantTNBiasAct;
+  const Variant& V = g_aux ? kVariantTNAux : kVariantTNBiasAct;
   const TrLayout& L = *V.L;
   if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
-  const std::string lay_s = V.words("", "-") + "-" + kActNames[g_act];
+  const std::string lay_s = V.words("", "-") + "-" + kActNames[g_act] + (g_aux ? "-aux" : "");
   const char* lay = lay_s.c_str();
   const int nc = L.num_configs();
   int failures = 0, runs = 0;
   double worst = 0.0;
   for (const Shape& sh : shapes) {
     const size_t cn = (size_t)sh.M * sh.N;
+    std::vector<uint16_t> got_z(g_aux ? cn : 0);
     int j = 0;
     while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
     const double scale = ldexp(1.0, -std::max(j - 2, 0));
@@ -1558,11 +1578,13 @@ static int act_check(std::vector<Shape> shapes) {
       }
     DevBufs dev;
     TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(w_h.data(), w_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), dev.alloc(cn * 2), 0};
+    if (g_aux) call.z = dev.alloc(cn * 2);
     for (int c = 0; c < nc; ++c) {
       const char* cname = L.config_name(c);
       const int own = V.runs_at(c, sh);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
         HIP_OK(hipMemset(call.c, 0xff, cn * 2));   // NaN pattern: unwritten outputs are caught
+        if (g_aux) HIP_OK(hipMemset(call.z, 0xff, cn * 2));
         const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
         const hipError_t e = hipDeviceSynchronize();
         ++runs;
@@ -1574,6 +1596,10 @@ static int act_check(std::vector<Shape> shapes) {
         }
         HIP_OK(hipMemcpy(got.data(), call.c, cn * 2, hipMemcpyDeviceToHost));
         size_t bad = 0;
+        if (g_aux) {   // z_out = bf16(z), bit for bit
+          HIP_OK(hipMemcpy(got_z.data(), call.z, cn * 2, hipMemcpyDeviceToHost));
+          for (size_t i = 0; i < cn; ++i) bad += got_z[i] != bf16_rne((float)z[i]);
+        }
         for (size_t i = 0; i < cn; ++i) {
           if (g_act == HGEMM_ACT_RELU) {
             bad += got[i] != (z[i] > 0 ? bf16_rne((float)z[i]) : (uint16_t)0);
@@ -1638,6 +1664,171 @@ static void bench_tn_bias_act(TrBench& B) {
   B.verdict("act_le_unfused", 0, 1, true);
 }
 
+// tn --bf16 --bias --act A --aux: the planned bgemm_mi355x_tn_bias_act_aux call against the sequence it replaces -- bgemm_mi355x_launch_tn_bias
+// with the same member and splits writing Z, then an element-wise kernel that reads Z and writes Y = act(Z) (2 M N bytes read, 2 M N
+// written) --, and, context only, the fused call without the second output.  "aux_le_unfused", within the unfused path's own spread.
+template <int ACT>
+__global__ void act_from_z_kernel(__bf16* __restrict__ y, const __bf16* __restrict__ z, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    y[i] = (__bf16)hgemm_mi355x::act_apply<ACT>((float)z[i]);
+}
+static void bench_tn_aux(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = g_act;
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), btb = B.to_bf16(B.of(&Buffers::bt), B.b_elems), cb = B.alloc(cn * 2),
+                        zb = B.alloc(cn * 2), bias = B.alloc((size_t)sh.N * 2);
+  for (void* p : bias) fill_bias_kernel<<<64, 256>>>((__bf16*)p, sh.N);
+  const int act_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+  B.add("aux", [=](Buffers&, size_t i) { return bgemm_mi355x_tn_bias_act_aux(ab[i], btb[i], bias[i], cb[i], zb[i], sh.M, sh.N, sh.K, act, nullptr); });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], zb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
+    if (act == HGEMM_ACT_RELU) act_from_z_kernel<HGEMM_ACT_RELU><<<act_grid, 256>>>((__bf16*)cb[i], (const __bf16*)zb[i], cn);
+    else if (act == HGEMM_ACT_GELU) act_from_z_kernel<HGEMM_ACT_GELU><<<act_grid, 256>>>((__bf16*)cb[i], (const __bf16*)zb[i], cn);
+    else act_from_z_kernel<HGEMM_ACT_GELU_TANH><<<act_grid, 256>>>((__bf16*)cb[i], (const __bf16*)zb[i], cn);
+    return st;
+  });
+  B.add("act", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn_bias_act(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, act, nullptr); });
+  B.head("\"output\": \"c16_bias_act_aux\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
+         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("aux_le_unfused", 0, 1, true);
+}
+
+// ---- --dact relu|gelu|gelu_tanh (with --layout nn --bf16): bgemm_mi355x_nn_dact, C = bf16(S x act'(float(z))) -----------------------------
+// The check's operands are integers in -2 .. 2 with A scaled by 2^-(floor(log2 K) - 2), so S is exact in fp32 in any order (verified per
+// element); Z is a seeded matrix of multiples of 1/32 in [-4, 4] (bf16 values; both signs, zeros, the range of a negative derivative).  The
+// bars: ReLU bit for bit against (z <= 0 ? +0 : bf16(S)); both GELUs |C - S g*| <= 1/2 ulp_bf16(S g*) + DACT_EPS |S|, g* in fp64.
+static double dact_fp64(double z, int act) {
+  if (act == HGEMM_ACT_RELU) return z <= 0 ? 0.0 : 1.0;
+  if (act == HGEMM_ACT_GELU) return 0.5 * erfc(-z / sqrt(2.0)) + z * exp(-0.5 * z * z) / sqrt(2.0 * M_PI);
+  const double c = sqrt(2.0 / M_PI), s = 1.0 / (1.0 + exp(-2.0 * c * (z + 0.044715 * z * z * z)));
+  return s + z * s * (1.0 - s) * 2.0 * c * (1.0 + 3.0 * 0.044715 * z * z);
+}
+static int launch_dact(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_nn_dact(cfg, splits, o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, g_dact, nullptr);
+}
+static int planned_dact(const TrCall& o, const Shape& sh) { return bgemm_mi355x_nn_dact(o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, g_dact, nullptr); }
+static int dact_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_nn_dact_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+static void bench_nn_dact(TrBench&);
+static const BenchDesc kBenchNNDact = {91, warm_none, bench_nn_dact};
+static const Variant kVariantNNDact = {&kLayoutNN, kBF16, kC16, dact_runs, launch_dact, planned_dact, &kBenchNNDact};
+
+static int dact_check(std::vector<Shape> shapes) {
+  const Variant& V = kVariantNNDact;
+  const TrLayout& L = *V.L;
+  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
+  const std::string lay_s = V.words("", "-") + "-dact-" + kActNames[g_dact];
+  const char* lay = lay_s.c_str();
+  const int nc = L.num_configs();
+  int failures = 0, runs = 0;
+  double worst = 0.0;
+  for (const Shape& sh : shapes) {
+    const size_t cn = (size_t)sh.M * sh.N;
+    int j = 0;
+    while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
+    const double scale = ldexp(1.0, -std::max(j - 2, 0));
+    uint64_t lcg = 0x9E3779B97F4A7C15ull + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
+    auto next = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(lcg >> 33); };
+    std::vector<int8_t> ai((size_t)sh.M * sh.K), bi((size_t)sh.K * sh.N);
+    for (auto& v : ai) v = (int8_t)((int)(next() % 5) - 2);
+    for (auto& v : bi) v = (int8_t)((int)(next() % 5) - 2);
+    std::vector<uint16_t> a_h(ai.size()), b_h(bi.size()), z_h(cn), got(cn);
+    for (size_t i = 0; i < ai.size(); ++i) a_h[i] = bf16_rne((float)(ai[i] * scale));
+    for (size_t i = 0; i < bi.size(); ++i) b_h[i] = bf16_rne((float)bi[i]);
+    std::vector<double> z(cn), s(cn);
+    for (size_t i = 0; i < cn; ++i) {
+      z[i] = (double)((int)(next() % 257) - 128) / 32.0;   // |q| <= 128: at most 8 significant bits, a bf16 value
+      z_h[i] = (i % 29 == 7) ? (uint16_t)0x8000 : bf16_rne((float)z[i]);   // some -0
+      if (i % 29 == 7) z[i] = 0.0;
+    }
+    for (int m = 0; m < sh.M; ++m)
+      for (int n = 0; n < sh.N; ++n) {
+        int acc = 0;
+        for (int k = 0; k < sh.K; ++k) acc += ai[(size_t)m * sh.K + k] * bi[(size_t)k * sh.N + n];
+        const double ss = acc * scale;
+        if ((double)(float)ss != ss) { fprintf(stderr, "check %s: S is not exact in fp32 at %d_%d_%d\n", lay, sh.M, sh.N, sh.K); return 2; }
+        s[(size_t)m * sh.N + n] = ss;
+      }
+    DevBufs dev;
+    TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), nullptr, dev.alloc(cn * 2), 0};
+    call.z = dev.upload(z_h.data(), cn * 2);
+    for (int c = 0; c < nc; ++c) {
+      const char* cname = L.config_name(c);
+      const int own = V.runs_at(c, sh);
+      for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
+        HIP_OK(hipMemset(call.c, 0xff, cn * 2));   // NaN pattern: unwritten outputs are caught
+        const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
+        const hipError_t e = hipDeviceSynchronize();
+        ++runs;
+        if (st != HGEMM_OK || e != hipSuccess) {
+          printf("FAIL %s %d_%d_%d %s s=%d: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
+          ++failures;
+          if (e != hipSuccess) return 3;
+          continue;
+        }
+        HIP_OK(hipMemcpy(got.data(), call.c, cn * 2, hipMemcpyDeviceToHost));
+        size_t bad = 0;
+        for (size_t i = 0; i < cn; ++i) {
+          if (g_dact == HGEMM_ACT_RELU) {
+            bad += got[i] != (z[i] <= 0 ? (uint16_t)0 : bf16_rne((float)s[i]));
+          } else {
+            const double y = s[i] * dact_fp64(z[i], g_dact), c16 = bf16_value(got[i]);
+            const double bar = (y != 0 ? ldexp(1.0, (int)floor(log2(fabs(y))) - 8) : 0.0) + (double)hgemm_mi355x::DACT_EPS * fabs(s[i]);
+            const double err = fabs(c16 - y);
+            if (!(err <= bar)) ++bad;   // (a NaN fails)
+            else if (bar > 0) worst = std::max(worst, err / bar);
+          }
+        }
+        if (bad) {
+          printf("FAIL %s %d_%d_%d %s s=%d%s: %zu/%zu elements %s\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+                 (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn, g_dact == HGEMM_ACT_RELU ? "differ from the exact result" : "outside the bar");
+          ++failures;
+        }
+      }
+      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
+    }
+    fflush(stdout);
+  }
+  if (g_dact == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (bit-exact against where(z <= 0, +0, bf16(S)) of the exact S)\n", lay, runs, failures);
+  else printf("check %s: %d runs, %d failures (every element within 1/2 ulp_bf16(S g*) + 2^-19 |S| of the fp64 product; worst %.3f of it)\n", lay, runs,
+              failures, worst);
+  return failures ? 1 : 0;
+}
+
+// nn --bf16 --dact A: the planned bgemm_mi355x_nn_dact call against the sequence it replaces -- bgemm_mi355x_launch_nn with the same member
+// and splits writing a bf16 dH, then an element-wise kernel that reads dH and Z and writes dZ = dH (.) act'(Z) (6 M N bytes) --, and,
+// context only, the plain NN call.  "dact_le_unfused", within the unfused path's own spread.
+__global__ void fill_z_kernel(__bf16* __restrict__ z, size_t total) {   // a fixed pattern over [-4, 4]: timing only
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    z[i] = (__bf16)((float)((int)((i * 2654435761u) % 257u) - 128) * (1.0f / 32.0f));
+}
+template <int ACT>
+__global__ void dact_elementwise_kernel(__bf16* __restrict__ dz, const __bf16* __restrict__ dh, const __bf16* __restrict__ z, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    dz[i] = (__bf16)hgemm_mi355x::dact_mul<ACT>((float)dh[i], (float)z[i]);
+}
+static void bench_nn_dact(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = g_dact;
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), bb = B.to_bf16(B.of(&Buffers::b), B.b_elems), cb = B.alloc(cn * 2),
+                        hb = B.alloc(cn * 2), zb = B.alloc(cn * 2);
+  const int grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+  for (void* p : zb) fill_z_kernel<<<grid, 256>>>((__bf16*)p, cn);
+  B.add("dact", [=](Buffers&, size_t i) { return bgemm_mi355x_nn_dact(ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, act, nullptr); });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], hb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
+    if (act == HGEMM_ACT_RELU) dact_elementwise_kernel<HGEMM_ACT_RELU><<<grid, 256>>>((__bf16*)cb[i], (const __bf16*)hb[i], (const __bf16*)zb[i], cn);
+    else if (act == HGEMM_ACT_GELU) dact_elementwise_kernel<HGEMM_ACT_GELU><<<grid, 256>>>((__bf16*)cb[i], (const __bf16*)hb[i], (const __bf16*)zb[i], cn);
+    else dact_elementwise_kernel<HGEMM_ACT_GELU_TANH><<<grid, 256>>>((__bf16*)cb[i], (const __bf16*)hb[i], (const __bf16*)zb[i], cn);
+    return st;
+  });
+  B.add("nn", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], hb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
+  B.head("\"output\": \"c16_dact\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
+         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("dact_le_unfused", 0, 1, true);
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -1664,6 +1855,12 @@ int main(int argc, char** argv) {
     else if (a == "--c32") c32 = true;
     else if (a == "--bf16") bf16 = true;
     else if (a == "--bias") bias = true;
+    else if (a == "--aux") g_aux = true;
+    else if (a == "--dact") {
+      const std::string nm = next();
+      for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) g_dact = k;
+      if (!g_dact) { fprintf(stderr, "--dact takes relu, gelu or gelu_tanh\n"); return 2; }
+    }
     else if (a == "--act") {
       const std::string nm = next();
       for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) g_act = k;
@@ -1722,7 +1919,9 @@ int main(int argc, char** argv) {
   if (g_act && !bias) { fprintf(stderr, "--act goes with --layout tn --bf16 --bias (bgemm_mi355x_tn_bias_act)\n"); return 2; }
   if (c32 && layout != "ta") { fprintf(stderr, "--c32 goes with --layout ta\n"); return 2; }
   if (bf16 && layout.empty()) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
-  const Variant* variant = g_act ? &kVariantTNBiasAct : resolve_variant(layout, bf16, c32, bias);
+  if (g_aux && !g_act) { fprintf(stderr, "--aux goes with --layout tn --bf16 --bias --act A (bgemm_mi355x_tn_bias_act_aux)\n"); return 2; }
+  if (g_dact && !(bf16 && layout == "nn" && !g_act)) { fprintf(stderr, "--dact goes with --layout nn --bf16 (bgemm_mi355x_nn_dact)\n"); return 2; }
+  const Variant* variant = g_dact ? &kVariantNNDact : g_aux ? &kVariantTNAux : g_act ? &kVariantTNBiasAct : resolve_variant(layout, bf16, c32, bias);
   if (variant && mode != "check" && mode != "bench") {
     fprintf(stderr, "--layout %s%s goes with check or bench\n", layout.c_str(), variant->L->b_col_major ? " --bf16" : "");
     return 2;
@@ -1738,7 +1937,7 @@ int main(int argc, char** argv) {
     HIP_OK(hipMalloc(&pad, g_pad_alloc_mib << 20));   // (kept until exit)
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
   }
-  if (variant) return mode != "check" ? tr_bench(*variant, shapes, out_path, autotune) : g_act ? act_check(shapes) : tr_check(*variant, shapes);
+  if (variant) return mode != "check" ? tr_bench(*variant, shapes, out_path, autotune) : g_dact ? dact_check(shapes) : g_act ? act_check(shapes) : tr_check(*variant, shapes);
   if (mode == "check") {
     if (shapes.empty())
       // (the last two: K tails -- 2104 = 32 x 64 + 56 = 8 x 256 + 56, 728 = 11 x 64 + 24 = 5 x 128 + 88 = 2 x 256 + 216: odd and even

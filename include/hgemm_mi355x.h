@@ -479,6 +479,73 @@ int bgemm_mi355x_launch_tn_bias_act(int tn_config, int splits, const void* a, co
 /* 1 when the call (with an aligned bias) runs one of the family's kernels: equal to bgemm_mi355x_tn_runs */
 int bgemm_mi355x_tn_bias_act_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc);
 
+/* ------------------------------------------------------------------------------------------
+ * Training forward that also saves the pre-activation: Y = act(X x W^T + b) AND Z = X x W^T + b, both bf16, in one call.  Operands,
+ * `bias`, `act`, layout, strides and scope are bgemm_mi355x_tn_bias_act's; `z_out` is a second bf16 output [M][ldz].
+ * Replaces bgemm_mi355x_tn_bias followed by an element-wise activation kernel, or both GEMMs: the backward pass through the activation
+ * needs z, and the rounded Y does not determine it.  The vendor libraries' GELU_AUX_BIAS epilogue.
+ * Semantics, exactly:  z[m][n]     = fl32( S[m][n] + float(bias[n]) )
+ *                      z_out[m][n] = bf16_rne( z[m][n] )
+ *                      C[m][n]     = bf16_rne( act32( z[m][n] ) )
+ *   - The activation is applied to the UNROUNDED z, as in bgemm_mi355x_tn_bias_act; both outputs are rounded once.
+ *   - Two identities, bit for bit, for the same arguments and plan: C is the C of bgemm_mi355x_launch_tn_bias_act, and z_out is the C
+ *     of bgemm_mi355x_launch_tn_bias.  The plain, two-pass (the combine writes both outputs; no slab is touched) and reference forms
+ *     all hold them.  HGEMM_PLAN_NT_STORE applies to both outputs.
+ * z_out has C's rules: ldz >= N (less: HGEMM_ERR_BAD_ARG); 16-byte aligned, ldz % 8 == 0 and (BM ldz + N) 2 bytes below 2 GiB, or the
+ * reference kernel answers.  z_out == NULL and z_out == c: HGEMM_ERR_BAD_ARG; z_out and C must not overlap.  act and bias: as in
+ * bgemm_mi355x_tn_bias_act.  No fp16 form, no other layout.
+ * The table, ids, names, plan, workspace size and reserve call are bgemm_mi355x_tn_*'s: the tiles, cuts and slabs of a call are those
+ * of the bgemm_mi355x_launch_tn call with the same arguments. */
+/* planned, contiguous (lda = ldb = K, ldc = ldz = N) */
+int bgemm_mi355x_tn_bias_act_aux(const void* a, const void* b_col_major, const void* bias, void* c, void* z_out, int M, int N, int K, int act,
+                                 void* stream);
+int bgemm_mi355x_launch_tn_bias_act_aux(int tn_config, int splits, const void* a, const void* b_col_major, const void* bias, void* c,
+                                        void* z_out, int M, int N, int K, int lda, int ldb, int ldc, int ldz, int act, void* stream);
+/* 1 when the call (with aligned bias and z_out) runs one of the family's kernels: bgemm_mi355x_tn_runs when ldz >= N, ldz % 8 == 0 and
+ * z_out is within reach, otherwise 0 (ldz < N, which the launch refuses, included).  No activation changes the answer. */
+int bgemm_mi355x_tn_bias_act_aux_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz);
+
+/* ------------------------------------------------------------------------------------------
+ * Input gradient through the activation: dZ = (dY x W) (.) act'(Z), the backward of the layer above in one call.  a = dY [M][K],
+ * b = W [K][N] row-major (bgemm_mi355x_nn's operand form), `z` = the saved bf16 pre-activation [M][ldz] (read-only: the z_out of
+ * bgemm_mi355x_tn_bias_act_aux), c = dZ [M][ldc], bf16.
+ * Replaces bgemm_mi355x_nn followed by an element-wise kernel that reads dH and Z and writes dH (.) act'(Z): one more launch, 6 M N
+ * more bytes and a second rounding (dH rounded to bf16 before the multiply).  The vendor libraries' DGELU epilogue.
+ * Semantics, exactly:  zf      = float( z[m][n] )                       (exact: a bf16 value is an fp32 value)
+ *                      C[m][n] = bf16_rne( fl32( S[m][n] x dact32(zf) ) )
+ *   - S is the finished fp32 sum: the accumulator of a plain launch, or the slabs of a two-pass plan added in split order.  The
+ *     multiplication is ONE fp32 multiply on the finished sum, never on a slab; the result is rounded once; no bf16 dH exists.
+ *   - `act` is one of
+ *       HGEMM_ACT_RELU       C = (zf <= 0) ? +0.0f : bf16(S): a select, not a multiply.  -0 and -inf give +0, whatever S holds; a NaN z
+ *                            passes S (torch's threshold_backward).  Defined bit for bit.
+ *       HGEMM_ACT_GELU       g = 1/2 (1 + erf(z / sqrt 2)) + z exp(-z^2 / 2) / sqrt(2 pi)
+ *       HGEMM_ACT_GELU_TANH  g = s + z s (1 - s) 2u', s = 1 / (1 + exp(-2u)), u = sqrt(2 / pi) (z + 0.044715 z^3),
+ *                            u' = sqrt(2 / pi) (1 + 3 x 0.044715 z^2): the derivative of bgemm_mi355x_tn_bias_act's own sigmoid form.
+ *     Both GELUs: g is finite for every finite z -- z is clamped to [-16, 16] first, behind which nothing overflows and outside which
+ *     g is within 2^-180 of its limit; every z >= 16, +inf included, gives exactly 1, every z <= -16, -inf included, gives +0 (so
+ *     C = +-0 or, for a non-finite S, NaN).  A NaN z gives NaN.
+ *   - The GELU bar: with g* the derivative of the given z evaluated in fp64, every element with a finite S satisfies
+ *       |C - S g*(zf)| <= 1/2 ulp_bf16(S g*) + 2^-19 |S|.
+ *     2^-19 is derived, not measured (csrc/hgemm_act.hpp has the full count): the device math library's erff within 16 ulp (32 x 2^-24)
+ *     and expf within 1 ulp, a correctly rounded division, every fp32 product, sum and fmaf within 2^-24 relatively, propagated
+ *     through the formulas with |g| <= 1.13, and the multiply S g itself, give 21.9 x 2^-24 (erf form) and 15.6 x 2^-24 (tanh form),
+ *     both below 32 x 2^-24 = 2^-19.  The plain, split and reference forms of one call share one derivative text.
+ * z has C's rules: ldz >= N (less: HGEMM_ERR_BAD_ARG); 16-byte aligned, ldz % 8 == 0 and (BM ldz + N) 2 bytes below 2 GiB, or the
+ * reference kernel answers.  M is free: a z (and C) of 4 GiB and more is in scope.  The kernels read z through a range that ends at its
+ * last valid element (M - 1, N - 1), or 4 GiB behind a tile's first row where z goes on further than that: no byte behind the last
+ * element is touched and pad columns do not matter.  z == NULL, z == c and any act outside 1..3: HGEMM_ERR_BAD_ARG.
+ * Out of scope: no fp16 form; no TA / TN form; no bias gradient -- the column sum of dZ needs a reduce across workgroups, whose
+ * deterministic form is a change of its own.
+ * The table, ids, names, plan, workspace size and reserve call are hgemm_mi355x_nn_*'s: the tiles, cuts and slabs of a call are those
+ * of the bgemm_mi355x_launch_nn call with the same arguments. */
+/* planned, contiguous (lda = K, ldb = ldc = ldz = N) */
+int bgemm_mi355x_nn_dact(const void* a, const void* b, const void* z, void* c, int M, int N, int K, int act, void* stream);
+int bgemm_mi355x_launch_nn_dact(int nn_config, int splits, const void* a, const void* b, const void* z, void* c, int M, int N, int K,
+                                int lda, int ldb, int ldc, int ldz, int act, void* stream);
+/* 1 when the call (with an aligned z) runs one of the family's kernels: hgemm_mi355x_nn_runs when ldz >= N, ldz % 8 == 0 and z is
+ * within reach, otherwise 0 (ldz < N, which the launch refuses, included).  No activation changes the answer. */
+int bgemm_mi355x_nn_dact_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz);
+
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
 const char* hgemm_mi355x_version(void);
