@@ -52,6 +52,7 @@ LIB_SOURCES = [
     "hgemm_inst_g14.hip",
     "hgemm_inst_g15.hip",
     "hgemm_inst_g16.hip",
+    "hgemm_inst_g17.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -143,7 +143,9 @@ bool mfma_path_ok(const void* a, const void* bt, const void* c, int M, int N, in
 // Host logic only (no HIP call, allocation or lock): the launch issues what it returns, hgemm_mi355x_plan_workspace_bytes reports
 // its request, hgemm_mi355x_selfcheck_launch shows it to the CPU tests.
 enum Form { FORM_REFERENCE, FORM_RAGGED, FORM_STREAMK, FORM_SPLITK, FORM_FUSED, FORM_HYBRID, FORM_PLAIN };
-enum Thunk { THUNK_ENTRY, THUNK_SPLITK_REDUCE, THUNK_TAIL_REDUCE, THUNK_RAGGED, THUNK_GENERIC };
+enum Thunk { THUNK_ENTRY, THUNK_SPLITK_REDUCE, THUNK_TAIL_REDUCE, THUNK_RAGGED, THUNK_GENERIC,
+             // the column sum behind a bgemm_mi355x_nn_dact_dbias call (hgemm_dbias.hpp): row blocks of C to partials, partials to db32, C to db32
+             THUNK_COLSUM_BLOCKED, THUNK_COLSUM_FINISH, THUNK_COLSUM_DIRECT };
 // one dispatch: its arguments (operand pointers, slabs and counters are the launch's to fill in), grid (0: the thunk sizes it),
 // epilogue, and whether it carries the timing hook's start / stop event
 struct Dispatch { int thunk; GemmArgs g; int grid, epi; bool start, stop; };
@@ -151,7 +153,8 @@ struct LaunchPlan {
   int status = HGEMM_OK, form = FORM_PLAIN, n = 0;
   size_t slab_bytes = 0;   // fp32 slab space the form asks for behind the arrival counters (0: no workspace)
   bool counters = false;   // the form uses the arrival counters
-  Dispatch d[3];
+  size_t colsum_off = 0;   // bgemm_mi355x_nn_dact_dbias: where in the slab space the column sum's partials start (behind the K slices' slabs)
+  Dispatch d[5];
 };
 // the selfcheck hooks' view of a plan: out = {form, dispatches, slab bytes, counters}, then per dispatch {thunk, grid, epi, splits,
 // k_chunk, items, start, stop}; returns the plan's status
@@ -484,17 +487,21 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // z a 16-bit INPUT at row stride ldz; the kinds TR_C16_DACT + act, the ids EPI_C16_DACT + act.  Either way the second matrix has C's rules
 // (ldz >= N; ldz % 8 == 0, 16-byte aligned and (BM ldz + N) 2 bytes below 2 GiB, or the reference kernel answers) and changes nothing else
 // of the plan.
+// dbias (bgemm_mi355x_nn_dact_dbias, with dact only): the dact call and db32[n] (+)= sum over m of float(C[m][n]), the kinds
+// TR_C16_DACT_DBIAS + act.  tr_resolve builds the dact call's plan and adds the column sum to it (see there); db_acc is the call's
+// `accumulate`, which is db32's and not C's.
 struct TrOut {
   bool c32, accumulate;
   bool bias = false;
   int act = 0;   // 0 (none) or HGEMM_ACT_RELU / _GELU / _GELU_TANH = 1 / 2 / 3
   bool aux = false, dact = false;
   int ldz = 0;   // the row stride of z_out (aux) / z (dact); no part of the kind
+  bool dbias = false, db_acc = false;
   int elem_bytes() const { return c32 ? 4 : 2; }
   bool has_z() const { return aux || dact; }
   bool has_epi() const { return bias || dact; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
   TrKind kind() const {   // the kernel set's cell in TrRow / TrTable
-    return dact ? (TrKind)(TR_C16_DACT + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
+    return dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
   }
   int epi_bias() const { return (dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
 };
@@ -502,11 +509,13 @@ constexpr TrOut kOutC16{false, false};
 constexpr TrOut kOutC16Bias{false, false, true};
 static_assert(HGEMM_ACT_RELU == ACT_RELU && HGEMM_ACT_GELU == ACT_GELU && HGEMM_ACT_GELU_TANH == ACT_GELU_TANH, "the public ids are hgemm_act.hpp's");
 static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIAS_AUX == TR_C16_BIAS_GELU_TANH &&
-              TR_C16_DACT == TR_C16_BIAS_AUX + ACT_GELU_TANH && TR_C16_DACT + ACT_GELU_TANH + 1 == TR_KINDS, "a kind per activation, three times");
+              TR_C16_DACT == TR_C16_BIAS_AUX + ACT_GELU_TANH && TR_C16_DACT_DBIAS == TR_C16_DACT + ACT_GELU_TANH && TR_C16_DACT_DBIAS + ACT_GELU_TANH + 1 == TR_KINDS,
+              "a kind per activation, four times");
 constexpr bool act_known(int act) { return act == HGEMM_ACT_RELU || act == HGEMM_ACT_GELU || act == HGEMM_ACT_GELU_TANH; }
 constexpr TrOut out_bias_act(int act) { return TrOut{false, false, true, act}; }   // (act_known(act) checked by the caller)
 constexpr TrOut out_bias_act_aux(int act, int ldz) { return TrOut{false, false, true, act, true, false, ldz}; }
 constexpr TrOut out_dact(int act, int ldz) { return TrOut{false, false, false, act, false, true, ldz}; }
+constexpr TrOut out_dact_dbias(int act, int ldz, bool db_acc) { return TrOut{false, false, false, act, false, true, ldz, true, db_acc}; }
 
 // What the operands and a 16-bit C hold (TrElem): fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements
 // are 2 bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  (TrElem, c32) selects a kernel set and nothing
@@ -554,8 +563,8 @@ const TrLayout kLayoutTN{tr_table_tn(), false, true, TR_BF16};   // the bf16 for
 // out.bias: the plan of the plain 16-bit call in everything but the epi of the plain dispatch and of the combine dispatch, EPI_C16_BIAS;
 // the bias pointer is no input (its alignment arrives in `aligned`, as the operands' does).  out.act: the same again with
 // EPI_C16_BIAS + act in those two dispatches.
-LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
-                      unsigned ruled_out) {
+LaunchPlan tr_resolve_gemm(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb,
+                           int ldc, unsigned ruled_out) {
   LaunchPlan p;
   auto add = [&p](int thunk, const GemmArgs& g, long grid, int epi) {
     if (p.n) p.d[p.n - 1].stop = false;
@@ -606,6 +615,41 @@ LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int
   return p;
 }
 
+// out.dbias: the dact call's plan, dispatch for dispatch, and behind it the column sum (hgemm_dbias.hpp).  ruled_out & 1 << FORM_PLAIN: the
+// call got no workspace at all.
+//   plain, with a workspace: the plain dispatch carries EPI_C16_DACT_DBIAS + act -- the member's fused kernel, its tile sums in
+//     P[tiles_m][N] at the start of the slab space -- and THUNK_COLSUM_FINISH adds the tiles_m rows of P into db32;
+//   two-pass: the K slices and the dact combine, then the column sum of the C just written in its own form -- M > COLSUM_DIRECT_ROWS:
+//     THUNK_COLSUM_BLOCKED into partials behind the slabs and THUNK_COLSUM_FINISH, otherwise THUNK_COLSUM_DIRECT;
+//   reference, and plain without a workspace (the dact kernel of bgemm_mi355x_nn_dact itself): THUNK_COLSUM_DIRECT, which needs none.
+// A column-sum dispatch shows epi = EPI_C16_DACT_DBIAS and, in `items`, the partial rows it writes or adds (direct: 0).
+LaunchPlan tr_resolve(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, bool aligned, int M, int N, int K, int lda, int ldb, int ldc,
+                      unsigned ruled_out) {
+  LaunchPlan p = tr_resolve_gemm(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
+  if (!out.dbias || p.status != HGEMM_OK) return p;
+  auto add = [&p](int thunk, GemmArgs g, int rows) {
+    g.items = rows;
+    p.d[p.n - 1].stop = false;
+    p.d[p.n] = Dispatch{thunk, g, 0, EPI_C16_DACT_DBIAS, false, true};
+    ++p.n;
+  };
+  const GemmArgs g = p.d[p.n - 1].g;
+  const bool workspace = !(ruled_out & (1u << FORM_PLAIN));
+  if (p.form == FORM_PLAIN && workspace) {
+    p.d[0].epi = EPI_C16_DACT_DBIAS + out.act;
+    p.slab_bytes = (size_t)g.tiles_m * N * sizeof(float);
+    add(THUNK_COLSUM_FINISH, g, g.tiles_m);
+  } else if (p.form == FORM_SPLITK && M > COLSUM_DIRECT_ROWS) {
+    p.colsum_off = p.slab_bytes;
+    p.slab_bytes += (size_t)colsum_blocks(M) * N * sizeof(float);
+    add(THUNK_COLSUM_BLOCKED, g, colsum_blocks(M));
+    add(THUNK_COLSUM_FINISH, g, colsum_blocks(M));
+  } else {
+    add(THUNK_COLSUM_DIRECT, g, 0);
+  }
+  return p;
+}
+
 // Planner of both families: the largest member whose tiles fill the chip (ties: fewer padded elements, then the taller tile); otherwise
 // the 64 x 64 member with as many two-pass splits as bring tiles x splits up to the CU count -- at most one per K stage, at most 32.
 void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits) {
@@ -641,23 +685,23 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 // reference kernel as an argument (combine_z / reference_z) and the member's own kernel in fields its non-slab launch leaves idle: z_out in
 // g.partial, z in g.counters, the stride out.ldz in g.tail_first -- tail_tiles stays 0, so the raster map never reads it.)
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
-              int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr) {
+              int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr, float* db32 = nullptr) {
   DisarmTiming disarm_timing;
-  if (!a || !b || !c || (out.bias && !bias) || (out.has_z() && (!z || z == c)) || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  if (!a || !b || !c || (out.bias && !bias) || (out.has_z() && (!z || z == c)) || (out.dbias && !db32) || M <= 0 || N <= 0 || K <= 0)
+    return HGEMM_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15)) && !(out.has_z() && ((uintptr_t)z & 15));
   unsigned ruled_out = 0;
   LaunchPlan p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
-  // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit
-  if (p.status == HGEMM_OK && p.slab_bytes) {
+  // no workspace (lent buffer too small, allocation failed, capturing stream): the plan runs unsplit -- and a dbias call, whose plain form
+  // asks for its tile sums' space, then asks once more and without any runs the dact kernel and the direct column sum
+  for (int attempt = 0; attempt < 2 && p.status == HGEMM_OK && p.slab_bytes; ++attempt) {
     const int st = ensure_workspace(p.slab_bytes, s, &slabs, &counters);
-    if (st == HGEMM_ERR_NO_WORKSPACE_INTERNAL) {
-      ruled_out |= 1u << FORM_SPLITK;
-      p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
-    } else if (st != HGEMM_OK) {
-      return st;
-    }
+    if (st == HGEMM_OK) break;
+    if (st != HGEMM_ERR_NO_WORKSPACE_INTERNAL) return st;
+    ruled_out |= (ruled_out & (1u << FORM_SPLITK)) ? 1u << FORM_PLAIN : 1u << FORM_SPLITK;
+    p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   }
   if (p.status != HGEMM_OK) return p.status;
   const TrKernels& kern = L.t.kernels[elem][out.kind()];
@@ -667,13 +711,17 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
     g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (bf16 travels in the same fields: the kernels of its Cfgs reinterpret)
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
     if (out.bias && p.d[i].epi == out.epi_bias()) g.counters = (unsigned*)const_cast<void*>(bias);   // read-only there: the kernel's bf16 bias vector
-    if (out.has_z() && p.d[i].thunk == THUNK_ENTRY && p.d[i].epi == out.epi_bias()) {   // the member's own kernel, never a slab kernel
+    if (out.has_z() && p.d[i].thunk == THUNK_ENTRY &&
+        (p.d[i].epi == out.epi_bias() || (out.dbias && p.d[i].epi == EPI_C16_DACT_DBIAS + out.act))) {   // the member's own kernel, never a slab kernel
       if (out.aux) g.partial = (float*)z; else g.counters = (unsigned*)z;              // (read-only in the dact kernels)
       g.tail_first = out.ldz;
     }
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
     switch (p.d[i].thunk) {
       case THUNK_ENTRY: launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
+      case THUNK_COLSUM_BLOCKED: launch_colsum_blocked(c, slabs + p.colsum_off / sizeof(float), M, N, ldc, s, ts); break;
+      case THUNK_COLSUM_FINISH: launch_colsum_finish(slabs + p.colsum_off / sizeof(float), db32, g.items, N, out.db_acc, s, ts); break;
+      case THUNK_COLSUM_DIRECT: launch_colsum_direct(c, db32, M, N, ldc, out.db_acc, s, ts); break;
       case THUNK_SPLITK_REDUCE:
         if (out.has_z()) kern.combine_z(g.partial, c, bias, z, M, N, ldc, out.ldz, g.splits, s, ts);
         else             kern.combine(g.partial, c, bias, M, N, ldc, g.splits, out.accumulate, s, ts);
@@ -691,11 +739,11 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
 
 // the planned call on contiguous operands
 int tr_run(const TrLayout& L, TrElem elem, TrOut out, const void* a, const void* b, const void* bias, void* c, int M, int N, int K, void* stream,
-           void* z = nullptr) {
+           void* z = nullptr, float* db32 = nullptr) {
   if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
   int cfg, splits;
   tr_model_plan(L, M, N, K, &cfg, &splits);
-  return tr_launch(L, elem, out, cfg, splits, a, b, bias, c, M, N, K, L.a_row(M, K), L.b_row(N, K), N, stream, z);
+  return tr_launch(L, elem, out, cfg, splits, a, b, bias, c, M, N, K, L.a_row(M, K), L.b_row(N, K), N, stream, z, db32);
 }
 
 const char* tr_config_name(const TrLayout& L, int id) { return (id >= 0 && id < L.t.count) ? L.t.rows[id].e.name : nullptr; }
@@ -1246,6 +1294,71 @@ int bgemm_mi355x_nn_dact(const void* a, const void* b, const void* z, void* c, i
   if (!act_known(act) || !z) return HGEMM_ERR_BAD_ARG;
   return tr_run(kLayoutNN, TR_BF16, out_dact(act, N), a, b, nullptr, c, M, N, K, stream, const_cast<void*>(z));
 }
+// ---- the same with the bias gradient (the kinds TR_C16_DACT_DBIAS + act, family n, bf16): C is bgemm_mi355x_launch_nn_dact's C bit for bit
+// and db32[n] (+)= sum over m of float(C[m][n]), the rounded values, in fp32 in an order fixed by the plan (tr_resolve; hgemm_dbias.hpp).
+int bgemm_mi355x_nn_dact_dbias_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz) {
+  return tr_runs(kLayoutNN, TR_BF16, out_dact_dbias(HGEMM_ACT_RELU, ldz, false), nn_config, M, N, K, lda, ldb, ldc);
+}
+int bgemm_mi355x_launch_nn_dact_dbias(int nn_config, int splits_arg, const void* a, const void* b, const void* z, void* c, float* db32, int M, int N,
+                                      int K, int lda, int ldb, int ldc, int ldz, int act, int accumulate, void* stream) {
+  if (!act_known(act) || !db32 || (accumulate != 0 && accumulate != 1)) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutNN, TR_BF16, out_dact_dbias(act, ldz, accumulate == 1), nn_config, splits_arg, a, b, nullptr, c, M, N, K, lda, ldb, ldc, stream,
+                   const_cast<void*>(z), db32);
+}
+int bgemm_mi355x_nn_dact_dbias(const void* a, const void* b, const void* z, void* c, float* db32, int M, int N, int K, int act, int accumulate,
+                               void* stream) {
+  if (!act_known(act) || !z || !db32 || (accumulate != 0 && accumulate != 1)) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutNN, TR_BF16, out_dact_dbias(act, N, accumulate == 1), a, b, nullptr, c, M, N, K, stream, const_cast<void*>(z), db32);
+}
+// what the launch asks ensure_workspace for with this plan on contiguous operands: the counter block, the K slices' slabs of a two-pass
+// plan and the column sum's partials (0: the plan needs none)
+size_t bgemm_mi355x_nn_dact_dbias_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const LaunchPlan p = tr_resolve(kLayoutNN, TR_BF16, out_dact_dbias(HGEMM_ACT_RELU, N, false), nn_config, splits, true, M, N, K, K, N, N, 0);
+  return p.status == HGEMM_OK && p.slab_bytes ? kCounterBytes + p.slab_bytes : 0;
+}
+int bgemm_mi355x_nn_dact_dbias_reserve_workspace(int M, int N, int K, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  int cfg = 0, splits = 1;
+  tr_model_plan(kLayoutNN, M, N, K, &cfg, &splits);
+  const size_t ws = bgemm_mi355x_nn_dact_dbias_plan_workspace_bytes(cfg, splits, M, N, K);
+  if (!ws) return HGEMM_OK;
+  float* slabs = nullptr; unsigned* counters = nullptr;
+  const int rc = ensure_workspace(ws - kCounterBytes, (hipStream_t)stream, &slabs, &counters);
+  return rc == HGEMM_ERR_NO_WORKSPACE_INTERNAL ? HGEMM_ERR_NO_WORKSPACE : rc;
+}
+// (not part of the public header; out = {form, dispatches, slab bytes, counters (0)} and up to five dispatches: 44 words.  ruled_out:
+// 1 << FORM_SPLITK as its siblings, 1 << FORM_PLAIN: no workspace at all)
+int bgemm_mi355x_selfcheck_launch_nn_dact_dbias(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                                                int ruled_out, int act, long long out[44]) {
+  if (!act_known(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_dact_dbias(act, ldz, false), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- the column sum on its own: out32[n] (+)= sum over m of float(x[m][n]), x bf16 [M][ldx] -- the bias gradient of a layer without an
+// activation (db = sum over m of dY) and part 2 of the call above.  M > COLSUM_DIRECT_ROWS and a workspace: row blocks to partials and the
+// finish kernel; otherwise one thread per column (hgemm_dbias.hpp).
+int bgemm_mi355x_colsum_c32(const void* x, float* out32, int M, int N, int ldx, int accumulate, void* stream) {
+  DisarmTiming disarm_timing;
+  if (!x || !out32 || M <= 0 || N <= 0 || ldx < N || (accumulate != 0 && accumulate != 1)) return HGEMM_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = nullptr; unsigned* counters = nullptr;
+  if (M > COLSUM_DIRECT_ROWS) {
+    const int st = ensure_workspace((size_t)colsum_blocks(M) * N * sizeof(float), s, &partial, &counters);
+    if (st != HGEMM_OK && st != HGEMM_ERR_NO_WORKSPACE_INTERNAL) return st;
+    if (st != HGEMM_OK) partial = nullptr;
+  }
+  if (partial) {
+    launch_colsum_blocked(x, partial, M, N, ldx, s, timing_slot(true, false));
+    launch_colsum_finish(partial, out32, colsum_blocks(M), N, accumulate == 1, s, timing_slot(false, true));
+  } else {
+    launch_colsum_direct(x, out32, M, N, ldx, accumulate == 1, s, timing_slot(true, true));
+  }
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
+}
+
 // (not part of the public header: the byte range of the dact kernels' Z descriptor for the tile at row m0, the kernels' own function)
 unsigned bgemm_mi355x_selfcheck_dact_z_range(int M, int N, int ldz, int m0) { return dact_z_range_bytes(M, N, ldz, m0); }
 int bgemm_mi355x_selfcheck_launch_nn_dact(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldz,

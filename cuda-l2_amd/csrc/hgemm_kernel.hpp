@@ -306,6 +306,10 @@ constexpr int EPI_C16_BIAS_AUX = 8;
 // the finished sum (ReLU: a select), rounded once.  EPI_C16_DACT + the activation's id: 12 / 13 / 14.  g.counters holds the read-only bf16
 // z and g.tail_first its row stride ldz.  All below EPI_KSTAGGER; neither family takes a flag.
 constexpr int EPI_C16_DACT = 11;
+// The same with the bias gradient (family n, bgemm_mi355x_nn_dact_dbias): the dact C, bit for bit, and the tile's fp32 column sums of the
+// ROUNDED values to P[tile_m][n] in g.partial (hgemm_dbias.hpp).  EPI_C16_DACT_DBIAS + the activation's id: 33 / 34 / 35.  Ids 15 .. would
+// run into the two flags below; families n and f take neither, and 33 .. 35 have neither bit (8, 16) set, so no id here reads as a flag.
+constexpr int EPI_C16_DACT_DBIAS = 32;
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

@@ -33,6 +33,7 @@
 #pragma once
 
 #include "hgemm_act.hpp"
+#include "hgemm_dbias.hpp"
 #include "hgemm_launch.hpp"
 
 namespace hgemm_mi355x {
@@ -84,7 +85,9 @@ __global__ void hgemm_nn_kernel(const GemmArgs g);
 // EPI_C16_DACT + ACT_* (hgemm_act.hpp): the bf16 C through the activation's derivative at a saved pre-activation (bgemm_mi355x_nn_dact);
 // the CfgNNB members only.
 constexpr bool epi_is_dact(int epi) { return epi > EPI_C16_DACT && epi <= EPI_C16_DACT + ACT_GELU_TANH; }
-constexpr int epi_dact(int epi) { return epi_is_dact(epi) ? epi - EPI_C16_DACT : ACT_NONE; }
+// EPI_C16_DACT_DBIAS + ACT_*: the same C and the tile's column sums (bgemm_mi355x_nn_dact_dbias)
+constexpr bool epi_is_dbias(int epi) { return epi > EPI_C16_DACT_DBIAS && epi <= EPI_C16_DACT_DBIAS + ACT_GELU_TANH; }
+constexpr int epi_dact(int epi) { return epi_is_dact(epi) ? epi - EPI_C16_DACT : epi_is_dbias(epi) ? epi - EPI_C16_DACT_DBIAS : ACT_NONE; }
 // The byte range of the Z descriptor of the tile whose first row is m0: from that row to Z's last valid element (M - 1, N - 1), computed in
 // 64 bits and CLAMPED to the descriptor's 32: M is not limited by the host, only a tile's reach is, so a Z of 4 GiB and more is in scope
 // and the distance to its end need not fit.  Where the clamp acts, the matrix goes on for more than 4 GiB behind the tile's first row
@@ -123,6 +126,18 @@ __device__ __forceinline__ f32x4 tr_mfma(V b, V a, f32x4 c) {
   else                               return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
 }
 
+// the sum over the 16 lanes L & 15 in every one of them: hgemm_dbias.hpp's butterfly, four DPP moves and four adds
+template <int CTRL>
+__device__ __forceinline__ float dbias_dpp_add(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float dbias_row16_sum(float v) {
+  v = dbias_dpp_add<DBIAS_DPP_QUAD_XOR1>(v);
+  v = dbias_dpp_add<DBIAS_DPP_QUAD_XOR2>(v);
+  v = dbias_dpp_add<DBIAS_DPP_HALF_MIRROR>(v);
+  return dbias_dpp_add<DBIAS_DPP_ROW_MIRROR>(v);
+}
+
 // accumulators of a wave tile, zeroed (families n and a; family f keeps the loop in place, see there)
 template <int FM, int FN>
 __device__ __forceinline__ void tr_zero(f32x4 (&acc)[FM][FN]) {
@@ -144,7 +159,8 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
   using elem = typename CFG::elem;   // f16, or __bf16 (the bgemm_ entry points)
   using ex4 = __attribute__((ext_vector_type(4))) elem;
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || (epi_is_dact(EPI) && __is_same(elem, __bf16)), "plain, two-pass slab and (bf16) dact epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || ((epi_is_dact(EPI) || epi_is_dbias(EPI)) && __is_same(elem, __bf16)),
+                "plain, two-pass slab and (bf16) dact / dact + dbias epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -271,7 +287,18 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
   // Issued HERE, behind the K loop, as family f's bias loads are: the loop keeps the EPI_C16 kernel's registers and its counted vmcnt.
   // dact_mul (hgemm_act.hpp) is the combine's and the reference kernel's text: one fp32 multiply on the finished sum, ReLU a select.
   // The sched_barrier per fragment and the parking asm are hgemm_kernel_tn.hpp's register steering.
-  if constexpr (epi_is_dact(EPI)) {
+  // EPI_C16_DACT_DBIAS + ACT (bgemm_mi355x_nn_dact_dbias) is the same text with three additions, steps 1 to 3 of hgemm_dbias.hpp: behind
+  // dact_mul the value is rounded to bf16 and converted back -- exact, so the store text below stores the dact kernel's bits -- and added
+  // into the lane's column accumulator, a row at or past M counting 0; the butterfly; the wave rows through LDS into P (g.partial).
+  if constexpr (epi_is_dact(EPI) || epi_is_dbias(EPI)) {
+    constexpr bool DBIAS = epi_is_dbias(EPI);
+    float col[DBIAS ? FN : 1][4];
+    if constexpr (DBIAS) {
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) col[j][e] = 0.0f;
+    }
     using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
     using bx4 = __attribute__((ext_vector_type(4))) __bf16;
     const uint32_t ldz = (uint32_t)g.tail_first;
@@ -280,7 +307,8 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
         __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)g.counters + (size_t)tc.m0 * ldz), 0, z_bytes, 0x00020000);
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
-      const uint32_t row = (uint32_t)(wave_m * CFG::TM + i * 16 + (lane & 15));
+      const uint32_t row = (uint32_t)dbias_row(wave_m, CFG::TM, i, lane);
+      const bool counts = dbias_row_counts(tc.m0, (int)row, g.M);
       bx4 z[FN];
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
@@ -293,9 +321,35 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float y = dact_mul<epi_dact(EPI)>(acc[i][j][e], (float)z[j][e]);
+          if constexpr (DBIAS) {
+            y = (float)(__bf16)y;
+            col[j][e] += counts ? y : 0.0f;
+          }
           asm volatile("" : "+a"(y));
           acc[i][j][e] = y;
         }
+      }
+    }
+    if constexpr (DBIAS) {
+      float* red = (float*)smem;   // [WM][BN]
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) col[j][e] = dbias_row16_sum(col[j][e]);
+      __syncthreads();             // every wave has read its last stage: the ring is free
+      if ((lane & 15) == 0) {
+#pragma unroll
+        for (int j = 0; j < FN; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) red[wave_m * BN + dbias_col(wave_n, CFG::TN, j, lane, e)] = col[j][e];
+      }
+      __syncthreads();
+      if (tid < BN) {
+        float s = red[tid];
+#pragma unroll
+        for (int w = 1; w < CFG::WM; ++w) s += red[w * BN + tid];
+        const int n = tc.n0 + tid;
+        if (n < g.N) g.partial[(size_t)(tc.m0 / BM) * (size_t)g.N + (size_t)n] = s;
       }
     }
   }
@@ -358,6 +412,21 @@ HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_RELU, CfgNNB)        // hgemm_inst_g1
 HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU, CfgNNB)
 HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU_TANH, CfgNNB)
 
+// The dact + dbias sets (bgemm_mi355x_nn_dact_dbias): the member's EPI_C16_DACT_DBIAS + ACT kernel alone -- g.partial of its dispatch is
+// P[tiles_m][N] --; a dispatch with the plain dact id (the call without a workspace) and the K slices of a two-pass form go to the dact
+// set's launcher in its own unit.
+template <class CFG, int ACT>
+void launch_nn_dbias(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi != EPI_C16_DACT_DBIAS + ACT) return launch_nn_dact<CFG, ACT>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_DACT_DBIAS + ACT>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_NN_DBIAS_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_nn_dbias<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_NN_DBIAS_INST(...) template void HGEMM_NN_DBIAS_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_NN_DBIAS_EXTERN(...) extern HGEMM_NN_DBIAS_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_RELU, CfgNNB)       // hgemm_inst_g17.hip
+HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_GELU, CfgNNB)
+HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_GELU_TANH, CfgNNB)
+
 // A layout's table (hgemm_registry.hip builds both, each by one expansion of the member list: a config id is a position in `rows`; the
 // geometry table of hgemm_configs*.def does not know these families).  A row is the member's geometry and its launcher in every kernel
 // set of the layout; TrKernels is what a set has besides: the combine of the two-pass form and the reference kernel (status 0, exact:
@@ -374,7 +443,7 @@ enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C h
 // TR_C16_BIAS_AUX + a: the same with the rounded pre-activation as a second output (bgemm_mi355x_tn_bias_act_aux).  TR_C16_DACT + a: a
 // 16-bit C through that activation's derivative at a saved pre-activation (family n: bgemm_mi355x_nn_dact).
 enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_C16_BIAS_GELU = 4, TR_C16_BIAS_GELU_TANH = 5,
-              TR_C16_BIAS_AUX = 5, TR_C16_DACT = 8, TR_KINDS = 12 };
+              TR_C16_BIAS_AUX = 5, TR_C16_DACT = 8, TR_C16_DACT_DBIAS = 11, TR_KINDS = 15 };   // TR_C16_DACT_DBIAS + a: dact with the bias gradient
 struct TrRow {
   TrEntry e;
   TrLaunch launch[2][TR_KINDS];   // [TrElem][TrKind]
@@ -391,6 +460,12 @@ struct TrKernels {
                       hipStream_t, TimingSlot);
   bool present() const { return reference || reference_z; }
 };
+// The column sum of a bf16 matrix in fp32 (hgemm_registry.hip; hgemm_dbias.hpp has the forms): out32[n] (+)= sum over m of float(x[m][n]).
+// finish: out32[n] = (accumulate ? out32[n] : 0) + (P[0][n] + P[1][n] + .. + P[rows - 1][n]), the partials of the fused kernels or of
+// colsum_blocked, added in that order, then the one add into the old value.
+void launch_colsum_direct(const void* x, float* out32, int M, int N, int ldx, bool accumulate, hipStream_t, TimingSlot);
+void launch_colsum_blocked(const void* x, float* partial, int M, int N, int ldx, hipStream_t, TimingSlot);
+void launch_colsum_finish(const float* partial, float* out32, int rows, int N, bool accumulate, hipStream_t, TimingSlot);
 struct TrTable {
   const TrRow* rows;
   int count;

@@ -432,6 +432,84 @@ __global__ void __launch_bounds__(256) hgemm_generic_nn_dact_kernel(const __bf16
   }
 }
 
+// ---- the column sum of a bf16 matrix in fp32 (bgemm_mi355x_colsum_c32; part 2 of bgemm_mi355x_nn_dact_dbias's other forms; the finish
+// kernel of its fused form).  hgemm_dbias.hpp states the forms and the order of the adds. --------------------------------------------------
+// direct: a thread per column, the M rows in order; the one add into the old value last
+__global__ void __launch_bounds__(256) hgemm_colsum_direct_kernel(const __bf16* __restrict__ X, float* __restrict__ out, int M, int N, int ldx,
+                                                                  int accumulate) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  float s = (float)X[n];
+  for (int m = 1; m < M; ++m) s += (float)X[(size_t)m * ldx + n];
+  out[n] = accumulate ? out[n] + s : s;
+}
+
+// blocked: blockIdx.y is the row block, blockIdx.x a group of COLSUM_COL_GROUPS x VEC columns; P[blockIdx.y][n] for every n < N
+template <int VEC>
+__global__ void __launch_bounds__(COLSUM_ROW_LANES * COLSUM_COL_GROUPS) hgemm_colsum_blocked_kernel(const __bf16* __restrict__ X,
+                                                                                                   float* __restrict__ P, int M, int N, int ldx) {
+  using bxv = __attribute__((ext_vector_type(VEC))) __bf16;
+  __shared__ float red[COLSUM_ROW_LANES][COLSUM_COL_GROUPS * VEC];
+  const int cg = threadIdx.x % COLSUM_COL_GROUPS, rl = threadIdx.x / COLSUM_COL_GROUPS;
+  const int n = (blockIdx.x * COLSUM_COL_GROUPS + cg) * VEC;
+  const int r0 = blockIdx.y * COLSUM_BLOCK_ROWS, r1 = min(M, r0 + COLSUM_BLOCK_ROWS);
+  float s[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) s[e] = 0.0f;
+  if (n + VEC <= N) {
+    for (int m = r0 + rl; m < r1; m += COLSUM_ROW_LANES) {
+      if constexpr (VEC == 1) {
+        s[0] += (float)X[(size_t)m * ldx + n];
+      } else {
+        const bxv v = *(const bxv*)(X + (size_t)m * ldx + n);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) s[e] += (float)v[e];
+      }
+    }
+  } else if (n < N) {   // (VEC = 8, N % 8 != 0) the ragged last group: element loads of its N - n columns -- a 16-byte load of the last row
+                        // could reach behind x's last element.  Per column the same adds in the same order.
+    for (int m = r0 + rl; m < r1; m += COLSUM_ROW_LANES)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e)
+        if (n + e < N) s[e] += (float)X[(size_t)m * ldx + n + e];
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) red[rl][cg * VEC + e] = s[e];
+  __syncthreads();
+  const int c = threadIdx.x;   // a thread per column of the block's group again, the row lanes in order
+  if (c < COLSUM_COL_GROUPS * VEC) {
+    const int nc = blockIdx.x * COLSUM_COL_GROUPS * VEC + c;
+    float a = red[0][c];
+#pragma unroll
+    for (int r = 1; r < COLSUM_ROW_LANES; ++r) a += red[r][c];
+    if (nc < N) P[(size_t)blockIdx.y * N + nc] = a;
+  }
+}
+
+// finish: the partial rows in order, then the one add into the old value
+__global__ void __launch_bounds__(256) hgemm_colsum_finish_kernel(const float* __restrict__ P, float* __restrict__ out, int rows, int N,
+                                                                  int accumulate) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  float s = P[n];
+  for (int t = 1; t < rows; ++t) s += P[(size_t)t * N + n];
+  out[n] = accumulate ? out[n] + s : s;
+}
+
+void launch_colsum_direct(const void* x, float* out32, int M, int N, int ldx, bool accumulate, hipStream_t stream, TimingSlot ts) {
+  HGEMM_LAUNCH(hgemm_colsum_direct_kernel, (N + 255) / 256, 256, stream, ts, (const __bf16*)x, out32, M, N, ldx, (int)accumulate);
+}
+void launch_colsum_blocked(const void* x, float* partial, int M, int N, int ldx, hipStream_t stream, TimingSlot ts) {
+  const bool vec = (ldx & 7) == 0 && ((uintptr_t)x & 15) == 0;
+  const int cols = COLSUM_COL_GROUPS * (vec ? 8 : 1);
+  const dim3 grid((N + cols - 1) / cols, colsum_blocks(M));
+  if (vec) HGEMM_LAUNCH(hgemm_colsum_blocked_kernel<8>, grid, COLSUM_ROW_LANES * COLSUM_COL_GROUPS, stream, ts, (const __bf16*)x, partial, M, N, ldx);
+  else     HGEMM_LAUNCH(hgemm_colsum_blocked_kernel<1>, grid, COLSUM_ROW_LANES * COLSUM_COL_GROUPS, stream, ts, (const __bf16*)x, partial, M, N, ldx);
+}
+void launch_colsum_finish(const float* partial, float* out32, int rows, int N, bool accumulate, hipStream_t stream, TimingSlot ts) {
+  HGEMM_LAUNCH(hgemm_colsum_finish_kernel, (N + 255) / 256, 256, stream, ts, partial, out32, rows, N, (int)accumulate);
+}
+
 // ---- launchers of the combines and the reference kernels, with the signatures of TrKernels (hgemm_kernel_nn.hpp) ----------------------
 // grid and block of a combine: a thread per four outputs
 struct CombineGrid { int grid, threads; };
@@ -560,7 +638,11 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
                                             nullptr, nullptr, nullptr,   /* the bf16 dact sets, TR_C16_DACT + ACT_* */                   \
                                             &HGEMM_NN_DACT_LAUNCHER(ACT_RELU, CfgNNB, __VA_ARGS__),                                      \
                                             &HGEMM_NN_DACT_LAUNCHER(ACT_GELU, CfgNNB, __VA_ARGS__),                                      \
-                                            &HGEMM_NN_DACT_LAUNCHER(ACT_GELU_TANH, CfgNNB, __VA_ARGS__)}}},
+                                            &HGEMM_NN_DACT_LAUNCHER(ACT_GELU_TANH, CfgNNB, __VA_ARGS__),                                 \
+                                            /* the bf16 dact + dbias sets, TR_C16_DACT_DBIAS + ACT_* */                                  \
+                                            &HGEMM_NN_DBIAS_LAUNCHER(ACT_RELU, CfgNNB, __VA_ARGS__),                                     \
+                                            &HGEMM_NN_DBIAS_LAUNCHER(ACT_GELU, CfgNNB, __VA_ARGS__),                                     \
+                                            &HGEMM_NN_DBIAS_LAUNCHER(ACT_GELU_TANH, CfgNNB, __VA_ARGS__)}}},
 #define HGEMM_TA_ROW(P, ...)                                                                                                                 \
   {HGEMM_TR_ENTRY(P, CfgTA, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgTA, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTA, true, __VA_ARGS__)},    \
                                            {&HGEMM_TR_LAUNCHER(CfgTAB, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTAB, true, __VA_ARGS__)}}},
@@ -577,12 +659,16 @@ void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int
                                                                  &HGEMM_TN_AUX_LAUNCHER(ACT_GELU_TANH, CfgTNB, __VA_ARGS__)}}},
 // The cells of the rows and of `kernels` are positional: these are the slots the initialisers below count out.
 static_assert(TR_C16_BIAS == 2 && TR_C16_BIAS + ACT_RELU == 3 && TR_C16_BIAS_AUX + ACT_RELU == 6 && TR_C16_DACT + ACT_RELU == 9 &&
-              TR_C16_DACT + ACT_GELU_TANH == 11 && TR_KINDS == 12, "the slots of the positional initialisers of the three tables");
+              TR_C16_DACT + ACT_GELU_TANH == 11 && TR_C16_DACT_DBIAS + ACT_RELU == 12 && TR_KINDS == 15, "the slots of the positional initialisers of the three tables");
 const TrTable& tr_table_nn() {
   static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_NN_ROW, "n")};
   static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
                             {{{launch_combine<f16>, launch_reference<f16, false, false>}, {}},
                              {{launch_combine<__bf16>, launch_reference<__bf16, false, false>}, {}, {}, {}, {}, {}, {}, {}, {},
+                              {nullptr, nullptr, launch_combine_dact<ACT_RELU>, launch_reference_nn_dact<ACT_RELU>},
+                              {nullptr, nullptr, launch_combine_dact<ACT_GELU>, launch_reference_nn_dact<ACT_GELU>},
+                              {nullptr, nullptr, launch_combine_dact<ACT_GELU_TANH>, launch_reference_nn_dact<ACT_GELU_TANH>},
+                              // TR_C16_DACT_DBIAS + ACT_*: the dact sets' combine and reference kernel, unchanged; the column sum follows them
                               {nullptr, nullptr, launch_combine_dact<ACT_RELU>, launch_reference_nn_dact<ACT_RELU>},
                               {nullptr, nullptr, launch_combine_dact<ACT_GELU>, launch_reference_nn_dact<ACT_GELU>},
                               {nullptr, nullptr, launch_combine_dact<ACT_GELU_TANH>, launch_reference_nn_dact<ACT_GELU_TANH>}}}};

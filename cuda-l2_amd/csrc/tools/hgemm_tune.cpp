@@ -41,6 +41,10 @@
 //                                                     bit for bit; bench against bgemm_mi355x_launch_tn_bias + an element-wise act(Z) kernel
 //   hgemm_tune check|bench --layout nn --bf16 --dact relu|gelu|gelu_tanh [...]   bgemm_mi355x_nn_dact: ReLU bit for bit, the GELUs inside
 //                                                     1/2 ulp_bf16(S g*) + 2^-19 |S|; bench against bgemm_mi355x_launch_nn + an element-wise kernel
+//   hgemm_tune check|bench --layout nn --bf16 --dact A --dbias [...]   bgemm_mi355x_nn_dact_dbias: C to the bars above and bit for bit the
+//                                                     dact call's, db32 against the fp64 column sum of the C read back -- ReLU bit for bit, the
+//                                                     GELUs inside gamma_(M-1) sum |C| --, accumulate = 1 one fp32 add; bench against
+//                                                     bgemm_mi355x_launch_nn_dact + bgemm_mi355x_colsum_c32 at the same member and splits
 //   hgemm_tune bench --layout tn --bf16 --bias --act A --shapes ... [--out F.jsonl]   against bgemm_mi355x_launch_tn_bias followed by an
 //                                                     element-wise activation kernel, "act_le_unfused"
 //                                                     that check first, then per shape interleaved rounds of the planned call, of
@@ -77,6 +81,7 @@
 
 #include "../../../include/hgemm_mi355x.h"
 #include "../hgemm_act.hpp"
+#include "../hgemm_dbias.hpp"
 
 // Ablation switches exist only in the -DHGEMM_ABLATION build of the library (build.py: HGEMM_LIB_SUFFIX=ablation
 // HGEMM_EXTRA_HIPFLAGS=-DHGEMM_ABLATION); against the shipping library the symbol is absent and --debug refuses.
@@ -1088,7 +1093,7 @@ static const TrLayout kLayoutTN = {"tn", "the TN kernels", kShapesNN, false, tru
 
 // One call's operands.  Every variant's entry points sit behind the same two signatures; what a variant has no use for (bias,
 // accumulate) its adapter drops.
-struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; };   // z: z_out of --aux, Z of --dact
+struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; float* db32 = nullptr; };   // z: z_out of --aux, Z of --dact; db32: --dbias
 template <auto F> static int launch16(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: a 16-bit-C launch
   return F(cfg, splits, o.a, o.b, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
@@ -1348,6 +1353,7 @@ struct TrBench {
 static int g_act = 0;   // --act: 0, or HGEMM_ACT_RELU / _GELU / _GELU_TANH (the fused bias+activation calls, below)
 static bool g_aux = false;   // --aux (with --act): bgemm_mi355x_tn_bias_act_aux, the same call that also writes z_out
 static int g_dact = 0;       // --dact A (with --layout nn --bf16): bgemm_mi355x_nn_dact
+static bool g_dbias = false; // --dbias (with --dact A): bgemm_mi355x_nn_dact_dbias, the same call that also writes db32
 static int act_check(std::vector<Shape> shapes);
 static int dact_check(std::vector<Shape> shapes);
 static int tr_bench(const Variant& V, const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
@@ -1705,23 +1711,32 @@ static double dact_fp64(double z, int act) {
   return s + z * s * (1.0 - s) * 2.0 * c * (1.0 + 3.0 * 0.044715 * z * z);
 }
 static int launch_dact(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  if (g_dbias)
+    return bgemm_mi355x_launch_nn_dact_dbias(cfg, splits, o.a, o.b, o.z, o.c, o.db32, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, g_dact, o.accumulate, nullptr);
   return bgemm_mi355x_launch_nn_dact(cfg, splits, o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, g_dact, nullptr);
 }
-static int planned_dact(const TrCall& o, const Shape& sh) { return bgemm_mi355x_nn_dact(o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, g_dact, nullptr); }
-static int dact_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_nn_dact_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+static int planned_dact(const TrCall& o, const Shape& sh) {
+  if (g_dbias) return bgemm_mi355x_nn_dact_dbias(o.a, o.b, o.z, o.c, o.db32, sh.M, sh.N, sh.K, g_dact, o.accumulate, nullptr);
+  return bgemm_mi355x_nn_dact(o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, g_dact, nullptr);
+}
+static int dact_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) {
+  return g_dbias ? bgemm_mi355x_nn_dact_dbias_runs(cfg, M, N, K, lda, ldb, ldc, N) : bgemm_mi355x_nn_dact_runs(cfg, M, N, K, lda, ldb, ldc, N);
+}
 static void bench_nn_dact(TrBench&);
 static const BenchDesc kBenchNNDact = {91, warm_none, bench_nn_dact};
 static const Variant kVariantNNDact = {&kLayoutNN, kBF16, kC16, dact_runs, launch_dact, planned_dact, &kBenchNNDact};
 
+constexpr int DBIAS_GUARD = 8;               // floats behind db32[N - 1] that must keep DBIAS_SENTINEL
+constexpr float DBIAS_SENTINEL = -12345.625f;
 static int dact_check(std::vector<Shape> shapes) {
   const Variant& V = kVariantNNDact;
   const TrLayout& L = *V.L;
   if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
-  const std::string lay_s = V.words("", "-") + "-dact-" + kActNames[g_dact];
+  const std::string lay_s = V.words("", "-") + "-dact-" + kActNames[g_dact] + (g_dbias ? "-dbias" : "");
   const char* lay = lay_s.c_str();
   const int nc = L.num_configs();
   int failures = 0, runs = 0;
-  double worst = 0.0;
+  double worst = 0.0, worst_db = 0.0;
   for (const Shape& sh : shapes) {
     const size_t cn = (size_t)sh.M * sh.N;
     int j = 0;
@@ -1752,11 +1767,20 @@ static int dact_check(std::vector<Shape> shapes) {
     DevBufs dev;
     TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), nullptr, dev.alloc(cn * 2), 0};
     call.z = dev.upload(z_h.data(), cn * 2);
+    // --dbias: db32 of N floats from a NaN prefill with DBIAS_GUARD sentinels behind it, and a second C for the dact call at the same plan
+    std::vector<float> db_fill(sh.N + DBIAS_GUARD, std::nanf("")), db_got(sh.N + DBIAS_GUARD), db_old(sh.N + DBIAS_GUARD), db_acc(sh.N + DBIAS_GUARD);
+    std::vector<uint16_t> dact_c(g_dbias ? cn : 0);
+    void* c_dact = g_dbias ? dev.alloc(cn * 2) : nullptr;
+    for (int n = 0; n < DBIAS_GUARD; ++n) db_fill[sh.N + n] = DBIAS_SENTINEL;
+    db_old = db_fill;
+    for (int n = 0; n < sh.N; ++n) db_old[n] = (float)((n * 37) % 129 - 64) * 0.3f;
+    if (g_dbias) call.db32 = (float*)dev.alloc(db_fill.size() * 4);
     for (int c = 0; c < nc; ++c) {
       const char* cname = L.config_name(c);
       const int own = V.runs_at(c, sh);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
         HIP_OK(hipMemset(call.c, 0xff, cn * 2));   // NaN pattern: unwritten outputs are caught
+        if (g_dbias) HIP_OK(hipMemcpy(call.db32, db_fill.data(), db_fill.size() * 4, hipMemcpyHostToDevice));
         const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
         const hipError_t e = hipDeviceSynchronize();
         ++runs;
@@ -1784,11 +1808,53 @@ static int dact_check(std::vector<Shape> shapes) {
                  (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn, g_dact == HGEMM_ACT_RELU ? "differ from the exact result" : "outside the bar");
           ++failures;
         }
+        if (!g_dbias) continue;
+        // C is the dact call's bit for bit; db32 is the column sum of the C read back, taken in fp64 -- ReLU: every C is a multiple of `scale`
+        // and every column sum exact in fp32 in any order (verified), so bit for bit; the GELUs: inside gamma_(M-1) sum |C|, the bound of an
+        // M-term fp32 sum in any order (hgemm_dbias.hpp) --; nothing behind db32[N - 1] is written; accumulate = 1 is fl32(old + s)
+        HIP_OK(hipMemcpy(db_got.data(), call.db32, db_got.size() * 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemset(c_dact, 0xff, cn * 2));
+        const int st_d = bgemm_mi355x_launch_nn_dact(c, splits, call.a, call.b, call.z, c_dact, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, sh.N, g_dact, nullptr);
+        HIP_OK(hipMemcpy(call.db32, db_old.data(), db_old.size() * 4, hipMemcpyHostToDevice));
+        call.accumulate = 1;
+        const int st_a = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
+        call.accumulate = 0;
+        const hipError_t e_d = hipDeviceSynchronize();
+        if (e_d != hipSuccess) { printf("FAIL %s %d_%d_%d %s s=%d: hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, (int)e_d); return 3; }
+        HIP_OK(hipMemcpy(dact_c.data(), c_dact, cn * 2, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(db_acc.data(), call.db32, db_acc.size() * 4, hipMemcpyDeviceToHost));
+        size_t c_differs = 0, db_bad = 0, acc_bad = 0, guard_bad = 0;
+        for (size_t i = 0; i < cn; ++i) c_differs += got[i] != dact_c[i];
+        for (int n = 0; n < DBIAS_GUARD; ++n) guard_bad += (db_got[sh.N + n] != DBIAS_SENTINEL) + (db_acc[sh.N + n] != DBIAS_SENTINEL);
+        for (int n = 0; n < sh.N; ++n) {
+          double sum = 0.0, mag = 0.0;
+          for (int m = 0; m < sh.M; ++m) { const double v = bf16_value(got[(size_t)m * sh.N + n]); sum += v; mag += fabs(v); }
+          if (g_dact == HGEMM_ACT_RELU) {
+            if ((double)(float)sum != sum) { fprintf(stderr, "check %s: a column sum is not exact in fp32 at %d_%d_%d\n", lay, sh.M, sh.N, sh.K); return 2; }
+            const float want = (float)sum;
+            db_bad += memcmp(&want, &db_got[n], 4) != 0;
+          } else {
+            const double bar = hgemm_mi355x::colsum_gamma(sh.M) * mag, err = fabs((double)db_got[n] - sum);
+            if (!(err <= bar)) ++db_bad;   // (a NaN fails)
+            else if (bar > 0) worst_db = std::max(worst_db, err / bar);
+          }
+          const float want_acc = db_old[n] + db_got[n];
+          acc_bad += memcmp(&want_acc, &db_acc[n], 4) != 0;
+        }
+        if (st_d != HGEMM_OK || st_a != HGEMM_OK || c_differs || db_bad || acc_bad || guard_bad) {
+          printf("FAIL %s %d_%d_%d %s s=%d%s: status %d %d, %zu/%zu elements of C differ from the dact call's, %zu/%d columns of db32 %s, %zu not fl32(old + s), "
+                 "%zu guard floats written\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", st_d, st_a,
+                 c_differs, cn, db_bad, sh.N, g_dact == HGEMM_ACT_RELU ? "differ from the exact sum" : "outside the bar", acc_bad, guard_bad);
+          ++failures;
+        }
       }
       if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
     }
     fflush(stdout);
   }
+  if (g_dbias && g_dact == HGEMM_ACT_RELU) printf("check-%s-db32: bit-exact against the fp64 column sum of the C read back; C the dact call's bit for bit\n", lay);
+  else if (g_dbias) printf("check-%s-db32: every column within gamma_(M-1) sum |C| of the fp64 column sum of the C read back (worst %.3f of it); "
+                           "C the dact call's bit for bit\n", lay, worst_db);
   if (g_dact == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (bit-exact against where(z <= 0, +0, bf16(S)) of the exact S)\n", lay, runs, failures);
   else printf("check %s: %d runs, %d failures (every element within 1/2 ulp_bf16(S g*) + 2^-19 |S| of the fp64 product; worst %.3f of it)\n", lay, runs,
               failures, worst);
@@ -1807,6 +1873,9 @@ __global__ void dact_elementwise_kernel(__bf16* __restrict__ dz, const __bf16* _
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
     dz[i] = (__bf16)hgemm_mi355x::dact_mul<ACT>((float)dh[i], (float)z[i]);
 }
+// nn --bf16 --dact A --dbias: bgemm_mi355x_launch_nn_dact_dbias at the plan against the sequence it replaces -- bgemm_mi355x_launch_nn_dact with
+// the same member and splits, then bgemm_mi355x_colsum_c32 over the dZ just written (one more launch, 2 M N more bytes read) --, and,
+// context only, the dact call alone.  "dbias_le_unfused", within the unfused path's own spread.
 static void bench_nn_dact(TrBench& B) {
   const Shape sh = B.sh;
   const size_t cn = B.cn;
@@ -1815,6 +1884,21 @@ static void bench_nn_dact(TrBench& B) {
                         hb = B.alloc(cn * 2), zb = B.alloc(cn * 2);
   const int grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
   for (void* p : zb) fill_z_kernel<<<grid, 256>>>((__bf16*)p, cn);
+  if (g_dbias) {
+    const TrBench::PerSet db = B.alloc((size_t)sh.N * 4, true);
+    B.add("dbias", [=](Buffers&, size_t i) {
+      return bgemm_mi355x_launch_nn_dact_dbias(cfg, splits, ab[i], bb[i], zb[i], cb[i], (float*)db[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, 0, nullptr);
+    });
+    B.add("unfused", [=](Buffers&, size_t i) {
+      const int st = bgemm_mi355x_launch_nn_dact(cfg, splits, ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, nullptr);
+      return st != HGEMM_OK ? st : bgemm_mi355x_colsum_c32(cb[i], (float*)db[i], sh.M, sh.N, sh.N, 0, nullptr);
+    });
+    B.add("dact", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn_dact(cfg, splits, ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, nullptr); });
+    B.head("\"output\": \"c16_dact_dbias\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
+           B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+    B.verdict("dbias_le_unfused", 0, 1, true);
+    return;
+  }
   B.add("dact", [=](Buffers&, size_t i) { return bgemm_mi355x_nn_dact(ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, act, nullptr); });
   B.add("unfused", [=](Buffers&, size_t i) {
     const int st = bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], hb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
@@ -1861,6 +1945,7 @@ int main(int argc, char** argv) {
       for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) g_dact = k;
       if (!g_dact) { fprintf(stderr, "--dact takes relu, gelu or gelu_tanh\n"); return 2; }
     }
+    else if (a == "--dbias") g_dbias = true;
     else if (a == "--act") {
       const std::string nm = next();
       for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) g_act = k;
@@ -1921,6 +2006,7 @@ int main(int argc, char** argv) {
   if (bf16 && layout.empty()) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
   if (g_aux && !g_act) { fprintf(stderr, "--aux goes with --layout tn --bf16 --bias --act A (bgemm_mi355x_tn_bias_act_aux)\n"); return 2; }
   if (g_dact && !(bf16 && layout == "nn" && !g_act)) { fprintf(stderr, "--dact goes with --layout nn --bf16 (bgemm_mi355x_nn_dact)\n"); return 2; }
+  if (g_dbias && !g_dact) { fprintf(stderr, "--dbias goes with --layout nn --bf16 --dact A (bgemm_mi355x_nn_dact_dbias)\n"); return 2; }
   const Variant* variant = g_dact ? &kVariantNNDact : g_aux ? &kVariantTNAux : g_act ? &kVariantTNBiasAct : resolve_variant(layout, bf16, c32, bias);
   if (variant && mode != "check" && mode != "bench") {
     fprintf(stderr, "--layout %s%s goes with check or bench\n", layout.c_str(), variant->L->b_col_major ? " --bf16" : "");

@@ -534,8 +534,8 @@ int bgemm_mi355x_tn_bias_act_aux_runs(int tn_config, int M, int N, int K, int ld
  * reference kernel answers.  M is free: a z (and C) of 4 GiB and more is in scope.  The kernels read z through a range that ends at its
  * last valid element (M - 1, N - 1), or 4 GiB behind a tile's first row where z goes on further than that: no byte behind the last
  * element is touched and pad columns do not matter.  z == NULL, z == c and any act outside 1..3: HGEMM_ERR_BAD_ARG.
- * Out of scope: no fp16 form; no TA / TN form; no bias gradient -- the column sum of dZ needs a reduce across workgroups, whose
- * deterministic form is a change of its own.
+ * Out of scope: no fp16 form; no TA / TN form; no bias gradient -- this call writes dZ alone; bgemm_mi355x_nn_dact_dbias below is the
+ * same call with the column sum of dZ, reduced across workgroups in a fixed order.
  * The table, ids, names, plan, workspace size and reserve call are hgemm_mi355x_nn_*'s: the tiles, cuts and slabs of a call are those
  * of the bgemm_mi355x_launch_nn call with the same arguments. */
 /* planned, contiguous (lda = K, ldb = ldc = ldz = N) */
@@ -545,6 +545,52 @@ int bgemm_mi355x_launch_nn_dact(int nn_config, int splits, const void* a, const 
 /* 1 when the call (with an aligned z) runs one of the family's kernels: hgemm_mi355x_nn_runs when ldz >= N, ldz % 8 == 0 and z is
  * within reach, otherwise 0 (ldz < N, which the launch refuses, included).  No activation changes the answer. */
 int bgemm_mi355x_nn_dact_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz);
+
+/* ------------------------------------------------------------------------------------------
+ * The same with the bias gradient: dZ as above and db = the column sum of dZ, in one call.  Replaces a framework reduction over dZ behind
+ * bgemm_mi355x_nn_dact: one more launch, 2 M N more bytes, and an order of summation that is not this library's.
+ * Semantics, exactly:
+ *   - C[m][n] is the C of bgemm_mi355x_launch_nn_dact for the same arguments and plan, bit for bit.
+ *   - s[n] = sum over m < M of float( C[m][n] ): the sum of the ROUNDED bf16 values the call stores -- db matches the dZ the dW GEMM
+ *     (bgemm_mi355x_ta_c32) will read --, taken in fp32.  The order is fixed for a given (plan, strides, alignment, workspace present or
+ *     not): two identical calls give identical bits, and HGEMM_PLAN_NT_STORE does not change the bits.  A row at or past M counts 0.
+ *   - accumulate == 0: db32[n] = s[n]; the old contents are never read and may be NaN.
+ *     accumulate == 1: db32[n] = fl32( old + s[n] ), one fp32 add, as in hgemm_mi355x_ta_c32.
+ *     Any other value: HGEMM_ERR_BAD_ARG.
+ *   - db32 holds N contiguous floats; db32 == NULL: HGEMM_ERR_BAD_ARG; 4-byte alignment is enough; nothing behind db32[N-1] is written.
+ *   - The bar of the sum: |s[n] - sum_m C[m][n]| <= gamma_{M-1} sum_m |C[m][n]|, gamma_k = k u / (1 - k u), u = 2^-24: the standard
+ *     bound of an M-term fp32 sum in any order, derived, not measured (csrc/hgemm_dbias.hpp).  Where every partial sum is exact in fp32
+ *     (integer data), s is exact.
+ * Everything else is bgemm_mi355x_nn_dact's: act, z, ldz, strides, scope, statuses, table, plan and refusals, the reference form, M free.
+ * How a call runs (the order of the sum follows from it):
+ *   - plain plan: the member's kernel sums its finished, rounded tile by column in its epilogue -- per lane over its fragments, a fixed
+ *     butterfly over the 16 rows of a fragment, the wave rows through LDS in order -- and writes tiles_m x N fp32 partials to the stream's
+ *     workspace; a second small kernel adds them over tile_m = 0 .. tiles_m - 1 in that order and writes or adds into db32.
+ *   - two-pass plan: the K slices and the dact combine unchanged, then bgemm_mi355x_colsum_c32's sum of the C just written.
+ *   - reference form (misaligned pointer, ldz % 8 != 0, ...): the reference dact kernel, then the direct column sum of C.
+ *   - no workspace (a capturing stream without a reserve, a lent buffer too small): still HGEMM_OK and a correct db -- the dact kernel of
+ *     bgemm_mi355x_nn_dact, unsplit, then the direct column sum, which needs none.  Nothing is allocated during capture.
+ * Workspace: counters + tiles_m x N x 4 bytes (plain), + the slabs and the sum's partials (two-pass); _plan_workspace_bytes reports what
+ * a launch with that plan on contiguous operands asks for, _reserve_workspace sizes the stream's workspace for the planned call.
+ * Out of scope: no fp16 form, no other layout, no bf16 db, no db inside the dW kernel or the two-pass combine. */
+/* planned, contiguous (lda = K, ldb = ldc = ldz = N) */
+int bgemm_mi355x_nn_dact_dbias(const void* a, const void* b, const void* z, void* c, float* db32, int M, int N, int K, int act,
+                               int accumulate, void* stream);
+int bgemm_mi355x_launch_nn_dact_dbias(int nn_config, int splits, const void* a, const void* b, const void* z, void* c, float* db32, int M,
+                                      int N, int K, int lda, int ldb, int ldc, int ldz, int act, int accumulate, void* stream);
+/* bgemm_mi355x_nn_dact_runs: the bias gradient changes no scope */
+int bgemm_mi355x_nn_dact_dbias_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz);
+size_t bgemm_mi355x_nn_dact_dbias_plan_workspace_bytes(int nn_config, int splits, int M, int N, int K);
+int bgemm_mi355x_nn_dact_dbias_reserve_workspace(int M, int N, int K, void* stream);
+
+/* The column sum on its own: out32[n] (+)= sum over m < M of float( x[m][n] ), x a bf16 matrix [M][ldx].  The bias gradient of a layer
+ * without an activation (db = sum over m of dY), and what the call above falls back to.  Any M, N >= 1; ldx >= N (less:
+ * HGEMM_ERR_BAD_ARG); x == NULL, out32 == NULL and accumulate outside 0 / 1: HGEMM_ERR_BAD_ARG.  accumulate as above; out32 holds N floats.
+ * fp32 throughout, deterministic per (M, N, ldx, alignment, workspace present or not), the bar above.  M > 256 and a workspace: row blocks
+ * of 256 rows to fp32 partials in the stream's workspace -- 16-byte loads where ldx % 8 == 0 and x is 16-byte aligned (the last N % 8 columns
+ * by 2-byte loads), 2-byte loads otherwise; the same adds in the same order either way --, then the finish kernel of the call above.  Otherwise, and without a workspace: one thread per column walks the M
+ * rows in order. */
+int bgemm_mi355x_colsum_c32(const void* x, float* out32, int M, int N, int ldx, int accumulate, void* stream);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
