@@ -682,7 +682,7 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 // null; GemmArgs keeps its layout, the kernel reinterprets the pointer (hgemm_kernel_tn.hpp).  The EPI_SLAB dispatch of a split call keeps
 // counters null: store_tile reads a non-null counters as "compact slabs".)
 // (out.aux / out.dact: `z` is the second matrix, required, distinct from c, and joins the alignment rule.  It reaches the combine and the
-// reference kernel as an argument (combine_z / reference_z) and the member's own kernel in fields its non-slab launch leaves idle: z_out in
+// reference kernel as an argument and the member's own kernel in fields its non-slab launch leaves idle: z_out in
 // g.partial, z in g.counters, the stride out.ldz in g.tail_first -- tail_tiles stays 0, so the raster map never reads it.)
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
               int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr, float* db32 = nullptr) {
@@ -722,14 +722,8 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
       case THUNK_COLSUM_BLOCKED: launch_colsum_blocked(c, slabs + p.colsum_off / sizeof(float), M, N, ldc, s, ts); break;
       case THUNK_COLSUM_FINISH: launch_colsum_finish(slabs + p.colsum_off / sizeof(float), db32, g.items, N, out.db_acc, s, ts); break;
       case THUNK_COLSUM_DIRECT: launch_colsum_direct(c, db32, M, N, ldc, out.db_acc, s, ts); break;
-      case THUNK_SPLITK_REDUCE:
-        if (out.has_z()) kern.combine_z(g.partial, c, bias, z, M, N, ldc, out.ldz, g.splits, s, ts);
-        else             kern.combine(g.partial, c, bias, M, N, ldc, g.splits, out.accumulate, s, ts);
-        break;
-      default:
-        if (out.has_z()) kern.reference_z(a, b, c, bias, z, M, N, K, lda, ldb, ldc, out.ldz, s, ts);
-        else             kern.reference(a, b, c, bias, M, N, K, lda, ldb, ldc, out.accumulate, s, ts);
-        break;
+      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, bias, z, M, N, ldc, out.ldz, g.splits, out.accumulate, s, ts); break;
+      default: kern.reference(a, b, c, bias, z, M, N, K, lda, ldb, ldc, out.ldz, out.accumulate, s, ts); break;
     }
   }
   hipError_t err = hipGetLastError();

@@ -449,16 +449,14 @@ struct TrRow {
   TrLaunch launch[2][TR_KINDS];   // [TrElem][TrKind]
 };
 // `bias`: the bf16 bias vector of the TR_C16_BIAS sets (N elements, added last in fp32, the sum rounded once); every other set is handed
-// nullptr and ignores it.  The sets with a second matrix -- TR_C16_BIAS_AUX + a: the output z_out, TR_C16_DACT + a: the input z, `z` with
-// its row stride ldz either way -- have combine_z / reference_z in their place (the other pair is null).
+// nullptr and ignores it.  `z` with its row stride ldz: the second matrix -- TR_C16_BIAS_AUX + a: the output z_out, TR_C16_DACT + a: the
+// input z --; every other set is handed nullptr / 0 and ignores them, as a set with a 16-bit C ignores `accumulate`.
 struct TrKernels {
-  void (*combine)(const float* partial, void* c, const void* bias, int M, int N, int ldc, int splits, bool accumulate, hipStream_t, TimingSlot);
-  void (*reference)(const void* a, const void* b, void* c, const void* bias, int M, int N, int K, int lda, int ldb, int ldc, bool accumulate,
-                    hipStream_t, TimingSlot);
-  void (*combine_z)(const float* partial, void* c, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits, hipStream_t, TimingSlot);
-  void (*reference_z)(const void* a, const void* b, void* c, const void* bias, void* z, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
-                      hipStream_t, TimingSlot);
-  bool present() const { return reference || reference_z; }
+  void (*combine)(const float* partial, void* c, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits, bool accumulate,
+                  hipStream_t, TimingSlot);
+  void (*reference)(const void* a, const void* b, void* c, const void* bias, void* z, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                    bool accumulate, hipStream_t, TimingSlot);
+  bool present() const { return reference; }
 };
 // The column sum of a bf16 matrix in fp32 (hgemm_registry.hip; hgemm_dbias.hpp has the forms): out32[n] (+)= sum over m of float(x[m][n]).
 // finish: out32[n] = (accumulate ? out32[n] : 0) + (P[0][n] + P[1][n] + .. + P[rows - 1][n]), the partials of the fused kernels or of

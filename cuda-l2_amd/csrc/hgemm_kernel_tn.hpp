@@ -20,7 +20,7 @@
 //   * Scope (the host sends anything else to the reference kernel): K % 64 == 0, N % 8 == 0 (C's 16-byte stores; M is free),
 //     lda / ldb / ldc multiples of 8, 16-byte aligned pointers, (BM lda + K) 2, (BN ldb + K) 2 and (BM ldc + N) 2 bytes below 2 GiB.
 //   * Epilogues: family n's: bf16 C (each accumulator rounded once by v_cvt_pk_bf16_f32, v_permlane16_swap, 16-byte buffer stores, the
-//     plain and the non-temporal store an instruction each) and the two-pass split-K slab (hgemm_splitk_reduce_kernel<__bf16> combines).
+//     plain and the non-temporal store an instruction each) and the two-pass split-K slab (hgemm_splitk_reduce_kernel<OutC16<__bf16>> combines).
 //   * Shared with family n: CfgTR, tr_mfma, launch_tr, the member list and its macros, the table types and the 16-bit C epilogue
 //     (hgemm_tr_store_c16.inc).  The preamble, the images and the ring are family n's text a third time, on purpose (a
 //     repeated text over a changed loop); families n and a keep their symbols and, as compiled, their instruction streams.

@@ -101,20 +101,112 @@ const KernelEntry g_kernel_table[] = {
 const int g_num_kernels = (int)(sizeof(g_kernel_table) / sizeof(g_kernel_table[0]));
 #endif  // !__HIP_DEVICE_COMPILE__
 
-// Split-K combine: C[m][n] = T( sum_s partial[s][m][n] ), fp32 adds in split order, the sum rounded to T once -- fp16 (the b_col_major
-// families and the fp16 calls of the transposed-read layouts) or bf16 (bgemm_mi355x_nn / _ta: round to nearest even).  Slabs are fp32
-// whatever the operands were.
-// (deterministic, unlike the reference's atomicAdd split-K, a100_F32F16F16F32/64_256_16384.cu:149-152).
+// ---- the output kinds of the two helper kernels -----------------------------------------------------------------------------------------
+// A kernel set (hgemm_kernel_nn.hpp: TrKind) has, besides its member kernels, the combine of its two-pass form and a reference kernel.  Both
+// end the same way: a finished fp32 sum S[m][n] becomes the kind's output(s).  A kind states that ONCE, as a policy: its pointers and
+// strides, what it reads early -- early<V>(at), issued in front of the sum so that the read is in flight with the loads that feed it --
+// and what it stores from the sum, store<V>(at, S, early).  V = 4 consecutive n in the combine, whose calls are aligned as a row of C is
+// (N % 8 == 0, 16-byte aligned pointers, strides that keep rows aligned: a quad is one vector access), V = 1 in the reference kernel, which
+// takes any shape, stride and alignment.  act_apply / dact_mul (hgemm_act.hpp) are the member kernels' own texts.
+// `at` is where the V outputs lie, m() and n(): the reference kernel's thread knows both; the combine's thread owns quad e / 4 of the M x N
+// outputs and divides only where the kind asks.  (Dividing in the kernel, in front of the call, cost hgemm_splitk_reduce_kernel<OutC16<f16>>
+// ten VGPRs: the quotient of a kind that reads nothing early was carried through the slab loop.)
+struct ElemPos { int row, col; __device__ int m() const { return row; } __device__ int n() const { return col; } };
+struct QuadPos { size_t e; int N; __device__ int m() const { return (int)(e / N); } __device__ int n() const { return (int)(e % N); } };
+template <class T, int V>
+using vec_t = T __attribute__((ext_vector_type(V)));
+struct OutArgs { void* c; const void* bias; void* z; int ldc, ldz; bool accumulate; };   // what TrKernels' launchers are handed (host)
+
+template <class T, int V>
+__device__ __forceinline__ vec_t<T, V> out_load(const T* p) { return *(const vec_t<T, V>*)p; }
+template <int V, class T>
+__device__ __forceinline__ void out_store(T* p, vec_t<float, V> v) {   // each element converted to T once: round to nearest even
+  vec_t<T, V> o;
+#pragma unroll
+  for (int i = 0; i < V; ++i) o[i] = (T)v[i];
+  *(vec_t<T, V>*)p = o;
+}
+
+// a 16-bit C of type T (f16, or __bf16: the bgemm_ calls): C = T(S)
 template <class T>
-__global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* __restrict__ partial,
-                                                                  T* __restrict__ C, int M, int N,
-                                                                  int ldc, int splits) {
-  using Tx4 = __attribute__((ext_vector_type(4))) T;
-  const size_t total4 = ((size_t)M * N) >> 2;  // N % 4 == 0 on this path
+struct OutC16 {
+  T* C; int ldc;
+  static OutC16 make(const OutArgs& o) { return {(T*)o.c, o.ldc}; }
+  template <int V, class At> __device__ int early(At) const { return 0; }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, int) const { out_store<V>(C + (size_t)at.m() * ldc + at.n(), s); }
+};
+// the fp32 C (hgemm_mi355x_ta_c32, bgemm_mi355x_ta_c32): C32 = accumulate ? C32 + S : S -- the shape of the unsplit result, old + fl(sum);
+// C32 is read only with `accumulate`, ldc counts fp32 elements
+struct OutC32 {
+  float* C; int ldc, accumulate;
+  static OutC32 make(const OutArgs& o) { return {(float*)o.c, o.ldc, o.accumulate ? 1 : 0}; }
+  template <int V, class At> __device__ vec_t<float, V> early(At at) const {
+    vec_t<float, V> old = 0.f;
+    if (accumulate) old = out_load<float, V>(C + (size_t)at.m() * ldc + at.n());
+    return old;
+  }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, vec_t<float, V> old) const {
+    *(vec_t<float, V>*)(C + (size_t)at.m() * ldc + at.n()) = accumulate ? old + s : s;
+  }
+};
+// the fused bias (bgemm_mi355x_tn_bias, ACT_NONE) and bias + activation (bgemm_mi355x_tn_bias_act): z = S + float(bias[n]) as one fp32 add,
+// C = bf16(act_apply<ACT>(z)) of the unrounded z
+template <int ACT>
+__device__ __forceinline__ float out_act(float z) {
+  if constexpr (ACT == ACT_NONE) return z;
+  else return act_apply<ACT>(z);
+}
+template <int ACT>
+struct OutBias {
+  __bf16* C; const __bf16* bias; int ldc;
+  static OutBias make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.bias, o.ldc}; }
+  template <int V, class At> __device__ vec_t<__bf16, V> early(At at) const { return out_load<__bf16, V>(bias + at.n()); }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, vec_t<__bf16, V> b) const {
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] = out_act<ACT>(s[i] + (float)b[i]);
+    out_store<V>(C + (size_t)at.m() * ldc + at.n(), s);
+  }
+};
+// the same with the pre-activation as a second output (bgemm_mi355x_tn_bias_act_aux): z_out = bf16(z) at stride ldz, both from the one z
+template <int ACT>
+struct OutBiasAux {
+  __bf16* C; const __bf16* bias; __bf16* Z; int ldc, ldz;
+  static OutBiasAux make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.bias, (__bf16*)o.z, o.ldc, o.ldz}; }
+  template <int V, class At> __device__ vec_t<__bf16, V> early(At at) const { return out_load<__bf16, V>(bias + at.n()); }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, vec_t<__bf16, V> b) const {
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] += (float)b[i];
+    out_store<V>(Z + (size_t)at.m() * ldz + at.n(), s);
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] = act_apply<ACT>(s[i]);
+    out_store<V>(C + (size_t)at.m() * ldc + at.n(), s);
+  }
+};
+// the activation's derivative at a saved pre-activation (bgemm_mi355x_nn_dact, and the C of _nn_dact_dbias): C = bf16(dact_mul<ACT>(S,
+// float(Z[m][n]))) -- one fp32 multiply on the finished sum, ReLU a select; Z is read-only, at stride ldz
+template <int ACT>
+struct OutDact {
+  __bf16* C; const __bf16* Z; int ldc, ldz;
+  static OutDact make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.z, o.ldc, o.ldz}; }
+  template <int V, class At> __device__ vec_t<__bf16, V> early(At at) const { return out_load<__bf16, V>(Z + (size_t)at.m() * ldz + at.n()); }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, vec_t<__bf16, V> z) const {
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] = dact_mul<ACT>(s[i], (float)z[i]);
+    out_store<V>(C + (size_t)at.m() * ldc + at.n(), s);
+  }
+};
+
+// Split-K combine of every kind: S = p[0] + p[1] + ... + p[S-1], fp32 adds in split order and one fixed order per plan, THEN the kind's
+// store.  Nothing is ever applied to a slab; slabs are fp32 whatever the operands were.  (N % 4 == 0 on this path.)
+// (deterministic, unlike the reference's atomicAdd split-K, a100_F32F16F16F32/64_256_16384.cu:149-152).
+template <class Out>
+__global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* __restrict__ partial, const Out out, int M, int N, int splits) {
+  const size_t total4 = ((size_t)M * N) >> 2;
   const size_t slab   = (size_t)M * N;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4;
-       q += (size_t)gridDim.x * blockDim.x) {
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
     const size_t e = q << 2;
+    const QuadPos at{e, N};
+    const auto early = out.template early<4>(at);   // in flight with the slab loads
     f32x4 s = *(const f32x4*)(partial + e);
     int k = 1;
     // eight slabs' loads in flight per thread, added in split order: with tiny M*N this kernel is a
@@ -130,16 +222,14 @@ __global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* _
       const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
       s += p;
     }
-    const int m = (int)(e / N), n = (int)(e % N);
-    Tx4 o = {(T)s[0], (T)s[1], (T)s[2], (T)s[3]};
-    *(Tx4*)(C + (size_t)m * ldc + n) = o;
+    out.template store<4>(at, s, early);
   }
 }
 
-// The combine of the fp32-C calls (hgemm_mi355x_ta_c32, bgemm_mi355x_ta_c32): t = p[0] + p[1] + ... + p[S-1] in split order, then
-// C32 = accumulate ? C32 + t : t -- the shape of the unsplit result, old + fl(sum), and one fixed order per plan.  C32 is read only
-// with `accumulate`; rows are ldc fp32 elements apart and the pad between N and ldc is never touched.  (N % 4 == 0, ldc % 4 == 0 and
-// a 16-byte aligned C32 on this path.)
+// The combine of the fp32-C calls keeps a text of its own: as hgemm_splitk_reduce_kernel<OutC32> it measured slower than this one on an
+// MI355X (tuning/combine_refactor_mi355x.jsonl: 64 x 64 outputs, 32 splits), the only kind that did.  The same sum in split order, then
+// OutC32's rule: C32 = accumulate ? C32 + t : t, C32 read only with `accumulate`, the pad between N and ldc never touched.  (N % 4 == 0,
+// ldc % 4 == 0 and a 16-byte aligned C32 on this path.)  The reference kernel of these calls is the shared one, with OutC32.
 __global__ void __launch_bounds__(256) hgemm_splitk_reduce_c32_kernel(const float* __restrict__ partial, float* __restrict__ C32, int M,
                                                                       int N, int ldc, int splits, int accumulate) {
   const size_t total4 = ((size_t)M * N) >> 2;
@@ -189,246 +279,29 @@ __global__ void __launch_bounds__(256) hgemm_tail_reduce_kernel(const GemmArgs g
   }
 }
 
-// Any-shape / any-alignment fallback (one output per thread, an fmaf chain in k order, fp32 accumulate, rounded to T once).
-// Correctness net for shapes the MFMA paths do not accept (K % 8 != 0, unaligned views); never tuned.  The reference kernel of every
-// 16-bit call: <f16, false> the b_col_major families' and the NN layout's, A_COL the TA layout's (hgemm_kernel_ta.hpp: A given as
-// a_col_major, read as A[k * lda + m] -- same sum order, so the same bits on the transposed operand), T = __bf16 the bgemm_ calls'.
-template <class T, bool A_COL>
-__global__ void __launch_bounds__(256) hgemm_generic_kernel(const T* __restrict__ A,
-                                                            const T* __restrict__ B,
-                                                            T* __restrict__ C, int M, int N, int K,
-                                                            int lda, int ldb_rowmajor, int ldc) {
+// Any-shape / any-alignment fallback of every kind (one output per thread, an fmaf chain in k order, fp32 accumulate, then the kind's store
+// of the finished sum).  Correctness net for shapes the MFMA paths do not accept (K % 8 != 0, unaligned views); never tuned.  Operands<T,
+// A_COL, B_COL> is how the two operands lie: A as [M][lda] or -- A_COL, the TA layout (hgemm_kernel_ta.hpp) -- a_col_major, read as
+// A[k * lda + m]; B row-major [K][ldb] or -- B_COL, the TN layout (hgemm_kernel_tn.hpp) -- b_col_major, read as B[n * ldb + k].  The sum
+// order is the same in all of them, so the same bits on a transposed operand.  <f16, false, false> with OutC16<f16> is the b_col_major
+// families' reference kernel (launch_generic).
+template <class T_, bool A_COL, bool B_COL>
+struct Operands {
+  using T = T_;
+  static __device__ size_t a(int m, int k, int lda) { return A_COL ? (size_t)k * lda + m : (size_t)m * lda + k; }
+  static __device__ size_t b(int k, int n, int ldb) { return B_COL ? (size_t)n * ldb + k : (size_t)k * ldb + n; }
+};
+template <class Ops, class Out>
+__global__ void __launch_bounds__(256) hgemm_generic_kernel(const typename Ops::T* __restrict__ A, const typename Ops::T* __restrict__ B,
+                                                            const Out out, int M, int N, int K, int lda, int ldb) {
   const int n = blockIdx.x * 64 + (threadIdx.x & 63);
   if (n >= N) return;
   // grid-stride over M: gridDim.y is capped at 65535 (M > 262140 used to fail the launch)
   for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
+    const auto early = out.template early<1>(ElemPos{m, n});
     float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[A_COL ? (size_t)k * lda + m : (size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    C[(size_t)m * ldc + n] = (T)s;
-  }
-}
-
-// The reference kernel of the TN layout (bgemm_mi355x_tn, hgemm_kernel_tn.hpp): B given as b_col_major, read as B[n * ldb + k] -- the same
-// one output per thread, the same fma chain in k order and the one rounding to T.  A kernel of its own: hgemm_generic_kernel keeps its
-// template arguments, and with them the symbols of its instances.
-template <class T>
-__global__ void __launch_bounds__(256) hgemm_generic_tn_kernel(const T* __restrict__ A, const T* __restrict__ Bcol, T* __restrict__ C, int M,
-                                                               int N, int K, int lda, int ldb_colmajor, int ldc) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
-    C[(size_t)m * ldc + n] = (T)s;
-  }
-}
-
-// The reference kernel of the fp32-C calls: the same fma chain in k order, then C32 = accumulate ? C32 + s : s (no rounding).
-template <class T, bool A_COL>
-__global__ void __launch_bounds__(256) hgemm_generic_c32_kernel(const T* __restrict__ A, const T* __restrict__ B,
-                                                                float* __restrict__ C32, int M, int N, int K, int lda,
-                                                                int ldb_rowmajor, int ldc, int accumulate) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[A_COL ? (size_t)k * lda + m : (size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    float* out = C32 + (size_t)m * ldc + n;
-    *out = accumulate ? *out + s : s;
-  }
-}
-
-// The combine of the fused-bias calls (bgemm_mi355x_tn_bias): s = p[0] + p[1] + ... + p[S-1] in split order, as hgemm_splitk_reduce_kernel
-// adds them, THEN s + float(bias[n]) as one fp32 add, then the one rounding to bf16 (nearest even).  The bias is not added into a slab.
-// A kernel of its own: hgemm_splitk_reduce_kernel keeps its symbols and streams.  (N % 8 == 0 and a 16-byte aligned bias on this path, so
-// the four bias values of a quad are one aligned 8-byte load inside the vector.)
-__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bias_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
-                                                                       const __bf16* __restrict__ bias, int M, int N, int ldc, int splits) {
-  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
-  const size_t total4 = ((size_t)M * N) >> 2;
-  const size_t slab   = (size_t)M * N;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
-    const size_t e = q << 2;
-    const int m = (int)(e / N), n = (int)(e % N);
-    const bx4 b = *(const bx4*)(bias + n);   // in flight with the slab loads
-    f32x4 s = *(const f32x4*)(partial + e);
-    int k = 1;
-    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
-      f32x4 p[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += p[u];
-    }
-    for (; k < splits; ++k) {
-      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
-      s += p;
-    }
-    const bx4 o = {(__bf16)(s[0] + (float)b[0]), (__bf16)(s[1] + (float)b[1]), (__bf16)(s[2] + (float)b[2]), (__bf16)(s[3] + (float)b[3])};
-    *(bx4*)(C + (size_t)m * ldc + n) = o;
-  }
-}
-
-// The reference kernel of the fused-bias calls: hgemm_generic_tn_kernel's one output per thread and its fma chain in k order, then the
-// fp32 add of float(bias[n]) to the finished sum, then the one rounding.  Any shape, stride and alignment (bias 2-byte aligned).
-__global__ void __launch_bounds__(256) hgemm_generic_tn_bias_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bcol,
-                                                                    __bf16* __restrict__ C, const __bf16* __restrict__ bias, int M, int N,
-                                                                    int K, int lda, int ldb_colmajor, int ldc) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  const float b = (float)bias[n];
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
-    C[(size_t)m * ldc + n] = (__bf16)(s + b);
-  }
-}
-
-// The combine of the fused bias+activation calls (bgemm_mi355x_tn_bias_act): hgemm_splitk_reduce_bias_kernel's text -- the slabs in split
-// order, THEN the bias as one fp32 add -- then act_apply<ACT> (hgemm_act.hpp, the kernels' own text) on the unrounded fp32 value, then the
-// one rounding to bf16.  The activation is never applied to a slab.  New symbols: the kernels above keep theirs and their streams.
-template <int ACT>
-__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bias_act_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
-                                                                           const __bf16* __restrict__ bias, int M, int N, int ldc, int splits) {
-  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
-  const size_t total4 = ((size_t)M * N) >> 2;
-  const size_t slab   = (size_t)M * N;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
-    const size_t e = q << 2;
-    const int m = (int)(e / N), n = (int)(e % N);
-    const bx4 b = *(const bx4*)(bias + n);   // in flight with the slab loads
-    f32x4 s = *(const f32x4*)(partial + e);
-    int k = 1;
-    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
-      f32x4 p[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += p[u];
-    }
-    for (; k < splits; ++k) {
-      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
-      s += p;
-    }
-    const bx4 o = {(__bf16)act_apply<ACT>(s[0] + (float)b[0]), (__bf16)act_apply<ACT>(s[1] + (float)b[1]),
-                   (__bf16)act_apply<ACT>(s[2] + (float)b[2]), (__bf16)act_apply<ACT>(s[3] + (float)b[3])};
-    *(bx4*)(C + (size_t)m * ldc + n) = o;
-  }
-}
-
-// The reference kernel of the fused bias+activation calls: hgemm_generic_tn_bias_kernel's fma chain in k order and its fp32 add of
-// float(bias[n]), then act_apply<ACT>, then the one rounding.  Any shape, stride and alignment (bias 2-byte aligned).
-template <int ACT>
-__global__ void __launch_bounds__(256) hgemm_generic_tn_bias_act_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bcol,
-                                                                        __bf16* __restrict__ C, const __bf16* __restrict__ bias, int M, int N,
-                                                                        int K, int lda, int ldb_colmajor, int ldc) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  const float b = (float)bias[n];
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
-    C[(size_t)m * ldc + n] = (__bf16)act_apply<ACT>(s + b);
-  }
-}
-
-// The combine of bgemm_mi355x_tn_bias_act_aux: hgemm_splitk_reduce_bias_act_kernel's text with a second output -- the slabs in split
-// order, the bias as one fp32 add, then z_out = bf16(z) at stride ldz and C = bf16(act_apply<ACT>(z)) of the UNROUNDED z.  No slab is touched.
-template <int ACT>
-__global__ void __launch_bounds__(256) hgemm_splitk_reduce_bias_act_aux_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
-                                                                               const __bf16* __restrict__ bias, __bf16* __restrict__ Z, int M,
-                                                                               int N, int ldc, int ldz, int splits) {
-  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
-  const size_t total4 = ((size_t)M * N) >> 2;
-  const size_t slab   = (size_t)M * N;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
-    const size_t e = q << 2;
-    const int m = (int)(e / N), n = (int)(e % N);
-    const bx4 b = *(const bx4*)(bias + n);   // in flight with the slab loads
-    f32x4 s = *(const f32x4*)(partial + e);
-    int k = 1;
-    for (; k + 8 <= splits; k += 8) {   // eight slabs' loads in flight per thread, added in split order (hgemm_splitk_reduce_kernel)
-      f32x4 p[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += p[u];
-    }
-    for (; k < splits; ++k) {
-      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
-      s += p;
-    }
-    const float z0 = s[0] + (float)b[0], z1 = s[1] + (float)b[1], z2 = s[2] + (float)b[2], z3 = s[3] + (float)b[3];
-    const bx4 zo = {(__bf16)z0, (__bf16)z1, (__bf16)z2, (__bf16)z3};
-    *(bx4*)(Z + (size_t)m * ldz + n) = zo;
-    const bx4 o = {(__bf16)act_apply<ACT>(z0), (__bf16)act_apply<ACT>(z1), (__bf16)act_apply<ACT>(z2), (__bf16)act_apply<ACT>(z3)};
-    *(bx4*)(C + (size_t)m * ldc + n) = o;
-  }
-}
-
-// The reference kernel of bgemm_mi355x_tn_bias_act_aux: hgemm_generic_tn_bias_act_kernel's chain and add, both outputs from the one z.
-template <int ACT>
-__global__ void __launch_bounds__(256) hgemm_generic_tn_bias_act_aux_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bcol,
-                                                                            __bf16* __restrict__ C, const __bf16* __restrict__ bias,
-                                                                            __bf16* __restrict__ Z, int M, int N, int K, int lda,
-                                                                            int ldb_colmajor, int ldc, int ldz) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  const float b = (float)bias[n];
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)Bcol[(size_t)n * ldb_colmajor + k], s);
-    const float z = s + b;
-    Z[(size_t)m * ldz + n] = (__bf16)z;
-    C[(size_t)m * ldc + n] = (__bf16)act_apply<ACT>(z);
-  }
-}
-
-// The combine of bgemm_mi355x_nn_dact: the slabs added in split order (hgemm_splitk_reduce_kernel), THEN dact_mul<ACT> (hgemm_act.hpp, the
-// kernels' own text) of the finished sum and float(Z[m][n]) -- one fp32 multiply, ReLU a select --, then the one rounding to bf16.  No
-// slab is multiplied.  (N % 8 == 0, ldz % 8 == 0 and a 16-byte aligned Z on this path: the four z of a quad are one aligned 8-byte load.)
-template <int ACT>
-__global__ void __launch_bounds__(256) hgemm_splitk_reduce_dact_kernel(const float* __restrict__ partial, __bf16* __restrict__ C,
-                                                                       const __bf16* __restrict__ Z, int M, int N, int ldc, int ldz,
-                                                                       int splits) {
-  using bx4 = __attribute__((ext_vector_type(4))) __bf16;
-  const size_t total4 = ((size_t)M * N) >> 2;
-  const size_t slab   = (size_t)M * N;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total4; q += (size_t)gridDim.x * blockDim.x) {
-    const size_t e = q << 2;
-    const int m = (int)(e / N), n = (int)(e % N);
-    const bx4 z = *(const bx4*)(Z + (size_t)m * ldz + n);   // in flight with the slab loads
-    f32x4 s = *(const f32x4*)(partial + e);
-    int k = 1;
-    for (; k + 8 <= splits; k += 8) {
-      f32x4 p[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) p[u] = *(const f32x4*)(partial + (size_t)(k + u) * slab + e);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += p[u];
-    }
-    for (; k < splits; ++k) {
-      const f32x4 p = *(const f32x4*)(partial + (size_t)k * slab + e);
-      s += p;
-    }
-    const bx4 o = {(__bf16)dact_mul<ACT>(s[0], (float)z[0]), (__bf16)dact_mul<ACT>(s[1], (float)z[1]),
-                   (__bf16)dact_mul<ACT>(s[2], (float)z[2]), (__bf16)dact_mul<ACT>(s[3], (float)z[3])};
-    *(bx4*)(C + (size_t)m * ldc + n) = o;
-  }
-}
-
-// The reference kernel of bgemm_mi355x_nn_dact: hgemm_generic_kernel's fma chain in k order (B row-major), dact_mul<ACT>, one rounding.
-// Any shape, stride and alignment (Z 2-byte aligned).
-template <int ACT>
-__global__ void __launch_bounds__(256) hgemm_generic_nn_dact_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
-                                                                    __bf16* __restrict__ C, const __bf16* __restrict__ Z, int M, int N, int K,
-                                                                    int lda, int ldb_rowmajor, int ldc, int ldz) {
-  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
-  if (n >= N) return;
-  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < M; m += gridDim.y * 4) {
-    float s = 0.f;
-    for (int k = 0; k < K; ++k) s = fmaf((float)A[(size_t)m * lda + k], (float)B[(size_t)k * ldb_rowmajor + n], s);
-    C[(size_t)m * ldc + n] = (__bf16)dact_mul<ACT>(s, (float)Z[(size_t)m * ldz + n]);
+    for (int k = 0; k < K; ++k) s = fmaf((float)A[Ops::a(m, k, lda)], (float)B[Ops::b(k, n, ldb)], s);
+    out.template store<1>(ElemPos{m, n}, vec_t<float, 1>(s), early);
   }
 }
 
@@ -523,176 +396,142 @@ static CombineGrid combine_grid(int M, int N) {
   return {grid, threads};
 }
 
-template <class T>
-static void launch_combine(const float* partial, void* C, const void*, int M, int N, int ldc, int splits, bool, hipStream_t stream, TimingSlot ts) {
+template <class Out>
+static void launch_combine(const float* partial, void* c, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits, bool accumulate,
+                           hipStream_t stream, TimingSlot ts) {
   const CombineGrid cg = combine_grid(M, N);
-  HGEMM_LAUNCH((hgemm_splitk_reduce_kernel<T>), cg.grid, cg.threads, stream, ts, partial, (T*)C, M, N, ldc, splits);
+  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate});
+  HGEMM_LAUNCH((hgemm_splitk_reduce_kernel<Out>), cg.grid, cg.threads, stream, ts, partial, out, M, N, splits);
 }
-
-// ldc in fp32 elements; accumulate: C32 += the sum, otherwise C32 is never read
-static void launch_combine_c32(const float* partial, void* C32, const void*, int M, int N, int ldc, int splits, bool accumulate,
-                               hipStream_t stream, TimingSlot ts) {
+// the fp32-C kind's combine is the kernel that kept its text (see there)
+template <>
+void launch_combine<OutC32>(const float* partial, void* c, const void*, void*, int M, int N, int ldc, int, int splits, bool accumulate,
+                            hipStream_t stream, TimingSlot ts) {
   const CombineGrid cg = combine_grid(M, N);
-  HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, cg.grid, cg.threads, stream, ts, partial, (float*)C32, M, N, ldc, splits, accumulate ? 1 : 0);
+  HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, cg.grid, cg.threads, stream, ts, partial, (float*)c, M, N, ldc, splits, accumulate ? 1 : 0);
 }
 
-template <class T, bool A_COL, bool C32>
-static void launch_reference(const void* A, const void* B, void* C, const void*, int M, int N, int K, int lda, int ldb, int ldc,
-                             bool accumulate, hipStream_t stream, TimingSlot ts) {
+template <class Ops, class Out>
+static void launch_reference(const void* A, const void* B, void* c, const void* bias, void* z, int M, int N, int K, int lda, int ldb, int ldc,
+                             int ldz, bool accumulate, hipStream_t stream, TimingSlot ts) {
+  using T = typename Ops::T;
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  if constexpr (C32)
-    HGEMM_LAUNCH((hgemm_generic_c32_kernel<T, A_COL>), grid, 256, stream, ts, (const T*)A, (const T*)B, (float*)C, M, N, K, lda, ldb, ldc,
-                 accumulate ? 1 : 0);
-  else
-    HGEMM_LAUNCH((hgemm_generic_kernel<T, A_COL>), grid, 256, stream, ts, (const T*)A, (const T*)B, (T*)C, M, N, K, lda, ldb, ldc);
-}
-
-template <class T>
-static void launch_reference_tn(const void* A, const void* Bcol, void* C, const void*, int M, int N, int K, int lda, int ldb, int ldc, bool,
-                                hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH((hgemm_generic_tn_kernel<T>), grid, 256, stream, ts, (const T*)A, (const T*)Bcol, (T*)C, M, N, K, lda, ldb, ldc);
-}
-
-// the fused-bias set's two (bgemm_mi355x_tn_bias): `bias` is the bf16 vector of N elements
-static void launch_combine_bias(const float* partial, void* C, const void* bias, int M, int N, int ldc, int splits, bool, hipStream_t stream,
-                                TimingSlot ts) {
-  const CombineGrid cg = combine_grid(M, N);
-  HGEMM_LAUNCH(hgemm_splitk_reduce_bias_kernel, cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)bias, M, N, ldc, splits);
-}
-
-static void launch_reference_tn_bias(const void* A, const void* Bcol, void* C, const void* bias, int M, int N, int K, int lda, int ldb, int ldc,
-                                     bool, hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH(hgemm_generic_tn_bias_kernel, grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)Bcol, (__bf16*)C, (const __bf16*)bias, M, N,
-               K, lda, ldb, ldc);
-}
-
-// the fused bias+activation sets' two (bgemm_mi355x_tn_bias_act), per activation
-template <int ACT>
-static void launch_combine_bias_act(const float* partial, void* C, const void* bias, int M, int N, int ldc, int splits, bool, hipStream_t stream,
-                                    TimingSlot ts) {
-  const CombineGrid cg = combine_grid(M, N);
-  HGEMM_LAUNCH((hgemm_splitk_reduce_bias_act_kernel<ACT>), cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)bias, M, N, ldc,
-               splits);
-}
-
-template <int ACT>
-static void launch_reference_tn_bias_act(const void* A, const void* Bcol, void* C, const void* bias, int M, int N, int K, int lda, int ldb,
-                                         int ldc, bool, hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH((hgemm_generic_tn_bias_act_kernel<ACT>), grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)Bcol, (__bf16*)C,
-               (const __bf16*)bias, M, N, K, lda, ldb, ldc);
-}
-
-// the sets with a second matrix (TrKernels::combine_z / reference_z): bgemm_mi355x_tn_bias_act_aux's z_out, bgemm_mi355x_nn_dact's z
-template <int ACT>
-static void launch_combine_aux(const float* partial, void* C, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits,
-                               hipStream_t stream, TimingSlot ts) {
-  const CombineGrid cg = combine_grid(M, N);
-  HGEMM_LAUNCH((hgemm_splitk_reduce_bias_act_aux_kernel<ACT>), cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)bias,
-               (__bf16*)z, M, N, ldc, ldz, splits);
-}
-template <int ACT>
-static void launch_reference_tn_aux(const void* A, const void* Bcol, void* C, const void* bias, void* z, int M, int N, int K, int lda, int ldb,
-                                    int ldc, int ldz, hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH((hgemm_generic_tn_bias_act_aux_kernel<ACT>), grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)Bcol, (__bf16*)C,
-               (const __bf16*)bias, (__bf16*)z, M, N, K, lda, ldb, ldc, ldz);
-}
-template <int ACT>
-static void launch_combine_dact(const float* partial, void* C, const void*, void* z, int M, int N, int ldc, int ldz, int splits,
-                                hipStream_t stream, TimingSlot ts) {
-  const CombineGrid cg = combine_grid(M, N);
-  HGEMM_LAUNCH((hgemm_splitk_reduce_dact_kernel<ACT>), cg.grid, cg.threads, stream, ts, partial, (__bf16*)C, (const __bf16*)z, M, N, ldc, ldz,
-               splits);
-}
-template <int ACT>
-static void launch_reference_nn_dact(const void* A, const void* B, void* C, const void*, void* z, int M, int N, int K, int lda, int ldb, int ldc,
-                                     int ldz, hipStream_t stream, TimingSlot ts) {
-  dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  HGEMM_LAUNCH((hgemm_generic_nn_dact_kernel<ACT>), grid, 256, stream, ts, (const __bf16*)A, (const __bf16*)B, (__bf16*)C, (const __bf16*)z, M,
-               N, K, lda, ldb, ldc, ldz);
+  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate});
+  HGEMM_LAUNCH((hgemm_generic_kernel<Ops, Out>), grid, 256, stream, ts, (const T*)A, (const T*)B, out, M, N, K, lda, ldb);
 }
 
 // the b_col_major families' names for their two (hgemm_launch.hpp)
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
-  launch_combine<f16>(partial, C, nullptr, M, N, ldc, splits, false, stream, ts);
+  launch_combine<OutC16<f16>>(partial, C, nullptr, nullptr, M, N, ldc, 0, splits, false, stream, ts);
 }
 
 void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int lda, int ldb,
                     int ldc, hipStream_t stream, TimingSlot ts) {
-  launch_reference<f16, false, false>(A, B, C, nullptr, M, N, K, lda, ldb, ldc, false, stream, ts);
+  launch_reference<Operands<f16, false, false>, OutC16<f16>>(A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, false, stream, ts);
 }
 
-// ---- the tables of the three layouts of the transposed-read host path (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the member list: a
-// row is the member's geometry and its launcher in every kernel set of the layout, [TrElem][TrKind]; `kernels` names the same sets'
-// combine and reference kernel.  A new kernel set is one more cell in the layout's row macro and in its `kernels`; a cell left out is
-// empty (null launcher, TrKernels{}) and a call for it is refused -- the fused-bias and bias+activation kinds of NN and TA.
+// ---- the tables of the three layouts of the transposed-read host path (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the
+// member list: a row is the member's geometry and its launcher in every kernel set of the layout, `kernels` names the same sets' combine
+// and reference kernel, both filled by [TrElem][TrKind] index.  A new kernel set is one cell in the layout's row builder and one in its
+// `kernels`; a cell that is not assigned is empty (null launcher, TrKernels{}) and a call for it is refused -- the fused-bias kinds of NN
+// and TA, say.
 // (Inside functions, which both passes read: the device pass instantiates a combine or a reference kernel where it sees its launcher
 // named, and a table of host function pointers at namespace scope would be emitted as a device constant.)
-#define HGEMM_NN_ROW(P, ...)                                                                                \
-  {HGEMM_TR_ENTRY(P, CfgNN, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgNN, false, __VA_ARGS__), nullptr},        \
-                                           {&HGEMM_TR_LAUNCHER(CfgNNB, false, __VA_ARGS__), nullptr, nullptr, nullptr, nullptr, nullptr, \
-                                            nullptr, nullptr, nullptr,   /* the bf16 dact sets, TR_C16_DACT + ACT_* */                   \
-                                            &HGEMM_NN_DACT_LAUNCHER(ACT_RELU, CfgNNB, __VA_ARGS__),                                      \
-                                            &HGEMM_NN_DACT_LAUNCHER(ACT_GELU, CfgNNB, __VA_ARGS__),                                      \
-                                            &HGEMM_NN_DACT_LAUNCHER(ACT_GELU_TANH, CfgNNB, __VA_ARGS__),                                 \
-                                            /* the bf16 dact + dbias sets, TR_C16_DACT_DBIAS + ACT_* */                                  \
-                                            &HGEMM_NN_DBIAS_LAUNCHER(ACT_RELU, CfgNNB, __VA_ARGS__),                                     \
-                                            &HGEMM_NN_DBIAS_LAUNCHER(ACT_GELU, CfgNNB, __VA_ARGS__),                                     \
-                                            &HGEMM_NN_DBIAS_LAUNCHER(ACT_GELU_TANH, CfgNNB, __VA_ARGS__)}}},
-#define HGEMM_TA_ROW(P, ...)                                                                                                                 \
-  {HGEMM_TR_ENTRY(P, CfgTA, __VA_ARGS__), {{&HGEMM_TR_LAUNCHER(CfgTA, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTA, true, __VA_ARGS__)},    \
-                                           {&HGEMM_TR_LAUNCHER(CfgTAB, false, __VA_ARGS__), &HGEMM_TR_LAUNCHER(CfgTAB, true, __VA_ARGS__)}}},
-// TN (family f, hgemm_kernel_tn.hpp): the bf16 sets with a 16-bit C -- plain, with the fused bias, with the bias and each activation
-// (TR_C16_BIAS + ACT_*), and those again with the pre-activation as a second output (TR_C16_BIAS_AUX + ACT_*) --; every other cell is empty and a call for it is refused
-#define HGEMM_TN_ROW(P, ...)                                                                                        \
-  {HGEMM_TR_ENTRY(P, CfgTNB, __VA_ARGS__), {{nullptr, nullptr}, {&HGEMM_TR_LAUNCHER(CfgTNB, false, __VA_ARGS__), nullptr, \
-                                                                 &HGEMM_TN_BIAS_LAUNCHER(CfgTNB, __VA_ARGS__),            \
-                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_RELU, CfgTNB, __VA_ARGS__),   \
-                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_GELU, CfgTNB, __VA_ARGS__),   \
-                                                                 &HGEMM_TN_ACT_LAUNCHER(ACT_GELU_TANH, CfgTNB, __VA_ARGS__), \
-                                                                 &HGEMM_TN_AUX_LAUNCHER(ACT_RELU, CfgTNB, __VA_ARGS__),   \
-                                                                 &HGEMM_TN_AUX_LAUNCHER(ACT_GELU, CfgTNB, __VA_ARGS__),   \
-                                                                 &HGEMM_TN_AUX_LAUNCHER(ACT_GELU_TANH, CfgTNB, __VA_ARGS__)}}},
-// The cells of the rows and of `kernels` are positional: these are the slots the initialisers below count out.
-static_assert(TR_C16_BIAS == 2 && TR_C16_BIAS + ACT_RELU == 3 && TR_C16_BIAS_AUX + ACT_RELU == 6 && TR_C16_DACT + ACT_RELU == 9 &&
-              TR_C16_DACT + ACT_GELU_TANH == 11 && TR_C16_DACT_DBIAS + ACT_RELU == 12 && TR_KINDS == 15, "the slots of the positional initialisers of the three tables");
+template <class Ops, class Out>
+static TrKernels tr_kernels() { return {launch_combine<Out>, launch_reference<Ops, Out>}; }
+
+// G: the member's BM, BN, WM, WN, NBUF (HGEMM_TR_MEMBERS)
+template <int... G>
+static TrRow nn_row(TrEntry e) {
+  using F = CfgNN<G...>;
+  using B = CfgNNB<G...>;
+  TrRow r{e, {}};
+  r.launch[TR_F16][TR_C16] = &launch_tr<F, false>;
+  r.launch[TR_BF16][TR_C16] = &launch_tr<B, false>;
+  r.launch[TR_BF16][TR_C16_DACT + ACT_RELU] = &launch_nn_dact<B, ACT_RELU>;
+  r.launch[TR_BF16][TR_C16_DACT + ACT_GELU] = &launch_nn_dact<B, ACT_GELU>;
+  r.launch[TR_BF16][TR_C16_DACT + ACT_GELU_TANH] = &launch_nn_dact<B, ACT_GELU_TANH>;
+  r.launch[TR_BF16][TR_C16_DACT_DBIAS + ACT_RELU] = &launch_nn_dbias<B, ACT_RELU>;
+  r.launch[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU] = &launch_nn_dbias<B, ACT_GELU>;
+  r.launch[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU_TANH] = &launch_nn_dbias<B, ACT_GELU_TANH>;
+  return r;
+}
+template <int... G>
+static TrRow ta_row(TrEntry e) {
+  TrRow r{e, {}};
+  r.launch[TR_F16][TR_C16] = &launch_tr<CfgTA<G...>, false>;
+  r.launch[TR_F16][TR_C32] = &launch_tr<CfgTA<G...>, true>;
+  r.launch[TR_BF16][TR_C16] = &launch_tr<CfgTAB<G...>, false>;
+  r.launch[TR_BF16][TR_C32] = &launch_tr<CfgTAB<G...>, true>;
+  return r;
+}
+// TN (family f, hgemm_kernel_tn.hpp): bf16 sets with a 16-bit C only
+template <int... G>
+static TrRow tn_row(TrEntry e) {
+  using B = CfgTNB<G...>;
+  TrRow r{e, {}};
+  r.launch[TR_BF16][TR_C16] = &launch_tr<B, false>;
+  r.launch[TR_BF16][TR_C16_BIAS] = &launch_tn_bias<B>;
+  r.launch[TR_BF16][TR_C16_BIAS + ACT_RELU] = &launch_tn_bias_act<B, ACT_RELU>;
+  r.launch[TR_BF16][TR_C16_BIAS + ACT_GELU] = &launch_tn_bias_act<B, ACT_GELU>;
+  r.launch[TR_BF16][TR_C16_BIAS + ACT_GELU_TANH] = &launch_tn_bias_act<B, ACT_GELU_TANH>;
+  r.launch[TR_BF16][TR_C16_BIAS_AUX + ACT_RELU] = &launch_tn_bias_act_aux<B, ACT_RELU>;
+  r.launch[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU] = &launch_tn_bias_act_aux<B, ACT_GELU>;
+  r.launch[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU_TANH] = &launch_tn_bias_act_aux<B, ACT_GELU_TANH>;
+  return r;
+}
+#define HGEMM_TR_ROW(ROW, P, CFG, ...) ROW<__VA_ARGS__>(HGEMM_TR_ENTRY(P, CFG, __VA_ARGS__)),
+
 const TrTable& tr_table_nn() {
-  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_NN_ROW, "n")};
-  static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
-                            {{{launch_combine<f16>, launch_reference<f16, false, false>}, {}},
-                             {{launch_combine<__bf16>, launch_reference<__bf16, false, false>}, {}, {}, {}, {}, {}, {}, {}, {},
-                              {nullptr, nullptr, launch_combine_dact<ACT_RELU>, launch_reference_nn_dact<ACT_RELU>},
-                              {nullptr, nullptr, launch_combine_dact<ACT_GELU>, launch_reference_nn_dact<ACT_GELU>},
-                              {nullptr, nullptr, launch_combine_dact<ACT_GELU_TANH>, launch_reference_nn_dact<ACT_GELU_TANH>},
-                              // TR_C16_DACT_DBIAS + ACT_*: the dact sets' combine and reference kernel, unchanged; the column sum follows them
-                              {nullptr, nullptr, launch_combine_dact<ACT_RELU>, launch_reference_nn_dact<ACT_RELU>},
-                              {nullptr, nullptr, launch_combine_dact<ACT_GELU>, launch_reference_nn_dact<ACT_GELU>},
-                              {nullptr, nullptr, launch_combine_dact<ACT_GELU_TANH>, launch_reference_nn_dact<ACT_GELU_TANH>}}}};
-  return t;
+  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TR_ROW, nn_row, "n", CfgNN)};
+  static const TrTable table = [] {
+    using F = Operands<f16, false, false>;
+    using B = Operands<__bf16, false, false>;
+    TrTable t{rows, (int)(sizeof(rows) / sizeof(rows[0])), {}};
+    t.kernels[TR_F16][TR_C16] = tr_kernels<F, OutC16<f16>>();
+    t.kernels[TR_BF16][TR_C16] = tr_kernels<B, OutC16<__bf16>>();
+    t.kernels[TR_BF16][TR_C16_DACT + ACT_RELU] = tr_kernels<B, OutDact<ACT_RELU>>();
+    t.kernels[TR_BF16][TR_C16_DACT + ACT_GELU] = tr_kernels<B, OutDact<ACT_GELU>>();
+    t.kernels[TR_BF16][TR_C16_DACT + ACT_GELU_TANH] = tr_kernels<B, OutDact<ACT_GELU_TANH>>();
+    // the dact sets' combine and reference kernel, unchanged; the column sum follows them
+    t.kernels[TR_BF16][TR_C16_DACT_DBIAS + ACT_RELU] = tr_kernels<B, OutDact<ACT_RELU>>();
+    t.kernels[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU] = tr_kernels<B, OutDact<ACT_GELU>>();
+    t.kernels[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU_TANH] = tr_kernels<B, OutDact<ACT_GELU_TANH>>();
+    return t;
+  }();
+  return table;
 }
 const TrTable& tr_table_ta() {
-  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TA_ROW, "a")};
-  static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
-                            {{{launch_combine<f16>, launch_reference<f16, true, false>}, {launch_combine_c32, launch_reference<f16, true, true>}},
-                             {{launch_combine<__bf16>, launch_reference<__bf16, true, false>}, {launch_combine_c32, launch_reference<__bf16, true, true>}}}};
-  return t;
+  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TR_ROW, ta_row, "a", CfgTA)};
+  static const TrTable table = [] {
+    using F = Operands<f16, true, false>;
+    using B = Operands<__bf16, true, false>;
+    TrTable t{rows, (int)(sizeof(rows) / sizeof(rows[0])), {}};
+    t.kernels[TR_F16][TR_C16] = tr_kernels<F, OutC16<f16>>();
+    t.kernels[TR_F16][TR_C32] = tr_kernels<F, OutC32>();
+    t.kernels[TR_BF16][TR_C16] = tr_kernels<B, OutC16<__bf16>>();
+    t.kernels[TR_BF16][TR_C32] = tr_kernels<B, OutC32>();
+    return t;
+  }();
+  return table;
 }
-
 const TrTable& tr_table_tn() {
-  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TN_ROW, "f")};
-  static const TrTable t = {rows, (int)(sizeof(rows) / sizeof(rows[0])),
-                            {{{}, {}}, {{launch_combine<__bf16>, launch_reference_tn<__bf16>}, {}, {launch_combine_bias, launch_reference_tn_bias},
-                                        {launch_combine_bias_act<ACT_RELU>, launch_reference_tn_bias_act<ACT_RELU>},
-                                        {launch_combine_bias_act<ACT_GELU>, launch_reference_tn_bias_act<ACT_GELU>},
-                                        {launch_combine_bias_act<ACT_GELU_TANH>, launch_reference_tn_bias_act<ACT_GELU_TANH>},
-                                        {nullptr, nullptr, launch_combine_aux<ACT_RELU>, launch_reference_tn_aux<ACT_RELU>},
-                                        {nullptr, nullptr, launch_combine_aux<ACT_GELU>, launch_reference_tn_aux<ACT_GELU>},
-                                        {nullptr, nullptr, launch_combine_aux<ACT_GELU_TANH>, launch_reference_tn_aux<ACT_GELU_TANH>}}}};
-  return t;
+  static const TrRow rows[] = {HGEMM_TR_MEMBERS(HGEMM_TR_ROW, tn_row, "f", CfgTNB)};
+  static const TrTable table = [] {
+    using B = Operands<__bf16, false, true>;
+    TrTable t{rows, (int)(sizeof(rows) / sizeof(rows[0])), {}};
+    t.kernels[TR_BF16][TR_C16] = tr_kernels<B, OutC16<__bf16>>();
+    t.kernels[TR_BF16][TR_C16_BIAS] = tr_kernels<B, OutBias<ACT_NONE>>();
+    t.kernels[TR_BF16][TR_C16_BIAS + ACT_RELU] = tr_kernels<B, OutBias<ACT_RELU>>();
+    t.kernels[TR_BF16][TR_C16_BIAS + ACT_GELU] = tr_kernels<B, OutBias<ACT_GELU>>();
+    t.kernels[TR_BF16][TR_C16_BIAS + ACT_GELU_TANH] = tr_kernels<B, OutBias<ACT_GELU_TANH>>();
+    t.kernels[TR_BF16][TR_C16_BIAS_AUX + ACT_RELU] = tr_kernels<B, OutBiasAux<ACT_RELU>>();
+    t.kernels[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU] = tr_kernels<B, OutBiasAux<ACT_GELU>>();
+    t.kernels[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU_TANH] = tr_kernels<B, OutBiasAux<ACT_GELU_TANH>>();
+    return t;
+  }();
+  return table;
 }
 
 void launch_tail_reduce(const GemmArgs& g, int BM, int BN, hipStream_t stream, TimingSlot ts) {

@@ -386,3 +386,19 @@ def test_one_layer_aux_forward_dact_dbias_and_the_weight_gradient(g, L, members,
         if act == RELU:
             assert torch.equal(dw[r].cpu(), db[:n].cpu())
     assert bwd.operands_intact()
+
+
+def test_the_combine_and_the_reference_kernel_on_dyadic_operands(g, L):
+    """The two helper kernels of the three dact + dbias sets (C and db32) (hgemm_registry.hip), on order-exact dyadic operands (gpu_common.HelperKernelSet): the 64 x 64 member,
+    M = N = 64, ldc = 72, ldz = 80 -- K = 128 in 2 splits runs the combine's remainder loop only, K = 704 in 11 splits one unrolled block of eight and
+    two remainder slabs --, the split call against the unsplit and the reference-kernel call bit for bit; then M = 5, N = 12, K = 24 on padded
+    strides, which only the reference kernel takes, against the member kernel on the zero-padded operands bit for bit.  db32 bit for bit where its sums are exact (ReLU, and split against reference: one kernel on one C), otherwise inside (M - 1) 2^-24 sum |C|."""
+    def one(act):
+        return g.HelperKernelSet(lambda cfg, word, p, d, acc: L.bgemm_mi355x_launch_nn_dact_dbias(cfg, word, p["a"], p["b"], p["z"], p["c"], p["db"], *d, act, 0, g.stream()),
+                                 lambda cfg, word, d, aligned, acc: decision(L, cfg, word, act, *d[:3], d[3:6], d[6], aligned), torch.bfloat16, z="in",
+                                 db=True, db_exact=act == RELU)
+    sets = [one(act) for act in ACTS]
+    for s in sets:
+        s.check_combine(128, 2, 9181)
+        s.check_combine(704, 11, 9181 + 1)
+        s.check_reference(9181 + 2)

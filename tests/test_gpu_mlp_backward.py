@@ -471,3 +471,23 @@ def test_print_the_worst_ratios(evidence):
     for key in sorted(WORST):
         print("worst ratio", *key, f"{WORST[key]:.3f}")
     assert all(v <= 1.0 for v in WORST.values())                  # (each test has asserted its own rows; run alone, the table is empty)
+
+
+def test_the_combine_and_the_reference_kernel_on_dyadic_operands(g, L):
+    """The two helper kernels of the three aux sets (C and z_out) and the three dact sets (hgemm_registry.hip), on order-exact dyadic operands (gpu_common.HelperKernelSet): the 64 x 64 member,
+    M = N = 64, ldc = 72, ldz = 80 -- K = 128 in 2 splits runs the combine's remainder loop only, K = 704 in 11 splits one unrolled block of eight and
+    two remainder slabs --, the split call against the unsplit and the reference-kernel call bit for bit; then M = 5, N = 12, K = 24 on padded
+    strides, which only the reference kernel takes, against the member kernel on the zero-padded operands bit for bit."""
+    def aux(act):
+        return g.HelperKernelSet(lambda cfg, word, p, d, acc: L.bgemm_mi355x_launch_tn_bias_act_aux(cfg, word, p["a"], p["b"], p["bias"], p["c"], p["z"], *d, act, g.stream()),
+                                 lambda cfg, word, d, aligned, acc: decision(L, AUX_HOOK, cfg, word, act, *d[:3], d[3:6], d[6], aligned), torch.bfloat16,
+                                 b_col=True, bias=True, z="out")
+
+    def dact(act):
+        return g.HelperKernelSet(lambda cfg, word, p, d, acc: L.bgemm_mi355x_launch_nn_dact(cfg, word, p["a"], p["b"], p["z"], p["c"], *d, act, g.stream()),
+                                 lambda cfg, word, d, aligned, acc: decision(L, DACT_HOOK, cfg, word, act, *d[:3], d[3:6], d[6], aligned), torch.bfloat16, z="in")
+    sets = [aux(act) for act in ACTS] + [dact(act) for act in ACTS]
+    for s in sets:
+        s.check_combine(128, 2, 9171)
+        s.check_combine(704, 11, 9171 + 1)
+        s.check_reference(9171 + 2)

@@ -447,3 +447,16 @@ def test_the_rocblas_ta_baseline_agrees_with_the_oracle(g, L, oracle):
         assert st == 0, L.hgemm_mi355x_strerror(st)
         torch.cuda.synchronize()
         assert np.array_equal(bits(c.cpu().numpy()), bits(truth)), (acc, int((bits(c.cpu().numpy()) != bits(truth)).sum()))
+
+
+def test_the_combine_and_the_reference_kernel_on_dyadic_operands(g, L):
+    """The two helper kernels of the fp16 TA set (hgemm_registry.hip), on order-exact dyadic operands (gpu_common.HelperKernelSet): the 64 x 64 member,
+    M = N = 64, ldc = 72 -- K = 128 in 2 splits runs the combine's remainder loop only, K = 704 in 11 splits one unrolled block of eight and
+    two remainder slabs --, the split call against the unsplit and the reference-kernel call bit for bit; then M = 5, N = 12, K = 24 on padded
+    strides, which only the reference kernel takes, against the member kernel on the zero-padded operands bit for bit."""
+    sets = [g.HelperKernelSet(lambda cfg, word, p, d, acc: L.hgemm_mi355x_launch_ta(cfg, word, p["a"], p["b"], p["c"], *d[:6], g.stream()),
+                              lambda cfg, word, d, aligned, acc: decision(L, cfg, word, *d[:3], d[3:6], aligned), torch.float16, a_col=True)]
+    for s in sets:
+        s.check_combine(128, 2, 9111)
+        s.check_combine(704, 11, 9111 + 1)
+        s.check_reference(9111 + 2)

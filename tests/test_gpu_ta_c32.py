@@ -420,3 +420,17 @@ def test_the_planned_accumulate_call_captures_through_its_split_plan_after_the_r
         rc = L.hgemm_mi355x_ta_c32(case.at.data_ptr(), case.bd.data_ptr(), buf.data_ptr(), m, n, k, 1, torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     assert replays_exactly(case, graph, buf) == []
+
+
+def test_the_combine_and_the_reference_kernel_on_dyadic_operands(g, L):
+    """The two helper kernels of the fp16 TA set with an fp32 C (hgemm_registry.hip), on order-exact dyadic operands (gpu_common.HelperKernelSet): the 64 x 64 member,
+    M = N = 64, ldc = 72 -- K = 128 in 2 splits runs the combine's remainder loop only, K = 704 in 11 splits one unrolled block of eight and
+    two remainder slabs --, the split call against the unsplit and the reference-kernel call bit for bit; then M = 5, N = 12, K = 24 on padded
+    strides, which only the reference kernel takes, against the member kernel on the zero-padded operands bit for bit, accumulate = 0 and accumulate = 1 on a non-zero C32."""
+    sets = [g.HelperKernelSet(lambda cfg, word, p, d, acc: L.hgemm_mi355x_launch_ta_c32(cfg, word, p["a"], p["b"], p["c"], *d[:6], acc, g.stream()),
+                              lambda cfg, word, d, aligned, acc: decision(L, cfg, word, *d[:3], d[3:6], aligned, acc), torch.float16, a_col=True,
+                              c32=True, accs=(0, 1))]
+    for s in sets:
+        s.check_combine(128, 2, 9121)
+        s.check_combine(704, 11, 9121 + 1)
+        s.check_reference(9121 + 2)

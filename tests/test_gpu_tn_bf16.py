@@ -372,3 +372,16 @@ def test_a_split_call_captured_without_a_workspace_runs_unsplit_and_split_after_
         graph.replay()
         case.check(buf, f"replay, reserved={reserve}")
     assert case.operands_intact()
+
+
+def test_the_combine_and_the_reference_kernel_on_dyadic_operands(g, L):
+    """The two helper kernels of the bf16 TN set (hgemm_registry.hip), on order-exact dyadic operands (gpu_common.HelperKernelSet): the 64 x 64 member,
+    M = N = 64, ldc = 72 -- K = 128 in 2 splits runs the combine's remainder loop only, K = 704 in 11 splits one unrolled block of eight and
+    two remainder slabs --, the split call against the unsplit and the reference-kernel call bit for bit; then M = 5, N = 12, K = 24 on padded
+    strides, which only the reference kernel takes, against the member kernel on the zero-padded operands bit for bit."""
+    sets = [g.HelperKernelSet(lambda cfg, word, p, d, acc: L.bgemm_mi355x_launch_tn(cfg, word, p["a"], p["b"], p["c"], *d[:6], g.stream()),
+                              lambda cfg, word, d, aligned, acc: decision(L, cfg, word, *d[:3], d[3:6], aligned), torch.bfloat16, b_col=True)]
+    for s in sets:
+        s.check_combine(128, 2, 9141)
+        s.check_combine(704, 11, 9141 + 1)
+        s.check_reference(9141 + 2)

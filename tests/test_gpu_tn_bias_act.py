@@ -491,3 +491,18 @@ def test_print_the_worst_ratios(evidence):
     # two GELUs x (four members x four forms + the reference kernel): an empty or partial table -- this test run alone -- fails
     assert len(WORST) == 2 * (4 * len(FORMS) + 1), f"{len(WORST)} rows: run the whole file, the sweep and the forms test fill the table"
     assert all(v <= 1.0 for v in WORST.values())
+
+
+def test_the_combine_and_the_reference_kernel_on_dyadic_operands(g, L):
+    """The two helper kernels of the three bias+activation sets (hgemm_registry.hip), on order-exact dyadic operands (gpu_common.HelperKernelSet): the 64 x 64 member,
+    M = N = 64, ldc = 72 -- K = 128 in 2 splits runs the combine's remainder loop only, K = 704 in 11 splits one unrolled block of eight and
+    two remainder slabs --, the split call against the unsplit and the reference-kernel call bit for bit; then M = 5, N = 12, K = 24 on padded
+    strides, which only the reference kernel takes, against the member kernel on the zero-padded operands bit for bit."""
+    def one(act):
+        return g.HelperKernelSet(lambda cfg, word, p, d, acc: L.bgemm_mi355x_launch_tn_bias_act(cfg, word, p["a"], p["b"], p["bias"], p["c"], *d[:6], act, g.stream()),
+                                 lambda cfg, word, d, aligned, acc: decision(L, cfg, word, act, *d[:3], d[3:6], aligned), torch.bfloat16, b_col=True, bias=True)
+    sets = [one(act) for act in ACTS]
+    for s in sets:
+        s.check_combine(128, 2, 9161)
+        s.check_combine(704, 11, 9161 + 1)
+        s.check_reference(9161 + 2)

@@ -487,3 +487,20 @@ def test_a_split_call_captured_without_a_workspace_runs_unsplit_and_split_after_
             graph.replay()
             case.check(buf, case.product16, f"replay {r}, reserved={reserve}")
     assert case.operands_intact()
+
+
+def test_the_combine_and_the_reference_kernel_on_dyadic_operands(g, L):
+    """The two helper kernels of the bf16 NN and TA sets, 16-bit and fp32 C (hgemm_registry.hip), on order-exact dyadic operands (gpu_common.HelperKernelSet): the 64 x 64 member,
+    M = N = 64, ldc = 72 -- K = 128 in 2 splits runs the combine's remainder loop only, K = 704 in 11 splits one unrolled block of eight and
+    two remainder slabs --, the split call against the unsplit and the reference-kernel call bit for bit; then M = 5, N = 12, K = 24 on padded
+    strides, which only the reference kernel takes, against the member kernel on the zero-padded operands bit for bit, the fp32 C with accumulate = 0 and accumulate = 1 on a non-zero C32."""
+    def one(kind, fn, **kw):
+        c32 = kind == "c32"
+        return g.HelperKernelSet(lambda cfg, word, p, d, acc: fn(cfg, word, p["a"], p["b"], p["c"], *d[:6], *([acc] if c32 else []), g.stream()),
+                                 lambda cfg, word, d, aligned, acc: decision(L, kind, cfg, word, *d[:3], d[3:6], aligned, acc), torch.bfloat16, **kw)
+    sets = [one("nn", L.bgemm_mi355x_launch_nn), one("ta", L.bgemm_mi355x_launch_ta, a_col=True),
+            one("c32", L.bgemm_mi355x_launch_ta_c32, a_col=True, c32=True, accs=(0, 1))]
+    for s in sets:
+        s.check_combine(128, 2, 9131)
+        s.check_combine(704, 11, 9131 + 1)
+        s.check_reference(9131 + 2)
