@@ -75,6 +75,7 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <rocm_smi/rocm_smi.h>
@@ -1039,21 +1040,34 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
 }
 
 // ---- The transposed-read variants: `check --layout nn|ta|tn ...`, `bench --layout nn|ta|tn ...` ------------------------------------------
-// Eight variants -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias --, each one record (kVariants)
-// that main resolves once; ONE check (tr_check) and ONE bench driver (tr_bench) serve them all.
-// The check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} (fp32 C: x {store, accumulate}) bit-exact on 0/1 inputs.
+// Twelve call kinds -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias, tn --bf16 --bias --act A,
+// ... --act A --aux, nn --bf16 --dact A, ... --dact A --dbias --, each one row of kVariants that main resolves once from the flags; the
+// activation A is a run-time value of the call (TrCall::act), not of the row.  ONE check (tr_check) and ONE bench driver (tr_bench) serve
+// them all; a row names what differs: its operand scheme, its judge of one finished run, its closing sentence, its bench description.
+// The check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} (fp32 C: x {store, accumulate}) from NaN-filled outputs.
 // The NN default shapes hold one tile, ragged M / N, an 8-column sliver, 1 .. 7 K stages, a long K -- and three the kernels do not take
 // (K % 64, N % 8: the reference kernel answers); the TA ones (A handed over as a_col_major [K][M], lda = M) add M % 8 != 0 to what the
-// kernels do not take and an 8-row sliver to what they do.  bf16: operands are converted on the host (0 and 1 are bf16 values), the
-// expected 16-bit C is the integer sum rounded to bf16 once.  fp32 C: exact against the host's integer result, the old C32 integers in
-// +-1000 (store mode starts from a NaN pattern instead).
+// kernels do not take and an 8-row sliver to what they do.  Two operand schemes.  operands_zero_one (c16 / c32 / bias): 0/1 inputs, C
+// bit-exact.  bf16: operands are converted on the host (0 and 1 are bf16 values), the expected 16-bit C is the integer sum (plus the
+// bias) rounded to bf16 once.  fp32 C: exact against the host's integer result, the old C32 integers in +-1000.  operands_small_int (the
+// activation kinds): integers in -2 .. 2, A scaled by a power of two, so the sum is exact in fp32 in any order (verified per element)
+// and lies in the activations' live range; ReLU is held bit for bit, the GELUs to a bar (within_gelu_bar).
 static uint16_t bf16_rne(float x) {   // round to nearest even (finite inputs)
   uint32_t u;
   memcpy(&u, &x, 4);
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 enum Elem { kF16, kBF16 };
-enum Out { kC16, kC32, kC16Bias };   // C as 16-bit elements, as fp32 (stored or accumulated), as bf16 with the fused bias
+// An output kind, as TrOut in hgemm_api.hip and the registry's OutC16 / OutC32 / OutBias / OutBiasAux / OutDact describe it.
+// c32: C is fp32, stored or accumulated onto (else 16-bit elements); bias: the call takes bias[N]; db32: it also writes the column sum
+// db32[N]; act: it takes an activation.
+enum ZRole { kZNone, kZRead, kZWritten };   // no z; Z is an input (dact); z_out is a second output (aux)
+struct OutKind { bool c32, bias; ZRole z; bool db32, act; };
+static const OutKind kOutC16 = {false, false, kZNone, false, false}, kOutC32 = {true, false, kZNone, false, false},
+                     kOutBias = {false, true, kZNone, false, false}, kOutBiasAct = {false, true, kZNone, false, true},
+                     kOutBiasAux = {false, true, kZWritten, false, true}, kOutDact = {false, false, kZRead, false, true},
+                     kOutDactDbias = {false, false, kZRead, true, true};
+static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh"};
 // fp16 values as fp16 or as bf16 bits, ready for upload
 static std::vector<uint16_t> operand_bits(const std::vector<f16>& v, Elem elem) {
   std::vector<uint16_t> o(v.size());
@@ -1092,8 +1106,8 @@ static const TrLayout kLayoutTN = {"tn", "the TN kernels", kShapesNN, false, tru
                                    bgemm_mi355x_tn_num_configs, bgemm_mi355x_tn_config_name, bgemm_mi355x_tn_plan, bgemm_rocblas_tn};
 
 // One call's operands.  Every variant's entry points sit behind the same two signatures; what a variant has no use for (bias,
-// accumulate) its adapter drops.
-struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; float* db32 = nullptr; };   // z: z_out of --aux, Z of --dact; db32: --dbias
+// accumulate, z, db32, act) its adapter drops.  z: z_out of --aux, Z of --dact; act: HGEMM_ACT_RELU / _GELU / _GELU_TANH
+struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; float* db32 = nullptr; int act = 0; };
 template <auto F> static int launch16(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: a 16-bit-C launch
   return F(cfg, splits, o.a, o.b, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
@@ -1106,8 +1120,29 @@ static int launch_bias(int cfg, int splits, const TrCall& o, const Shape& sh, in
 template <auto F> static int planned16(const TrCall& o, const Shape& sh) { return F(o.a, o.b, o.c, sh.M, sh.N, sh.K, nullptr); }
 template <auto F> static int planned32(const TrCall& o, const Shape& sh) { return F(o.a, o.b, (float*)o.c, sh.M, sh.N, sh.K, o.accumulate, nullptr); }
 static int planned_bias(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_bias(o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, nullptr); }
+// the fused bias+activation calls (bgemm_mi355x_tn_bias_act), and --aux: the same call with the pre-activation as a second output
+static int launch_bias_act(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_bias_act(cfg, splits, o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, o.act, nullptr);
+}
+static int planned_bias_act(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_bias_act(o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, o.act, nullptr); }
+static int launch_bias_act_aux(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_bias_act_aux(cfg, splits, o.a, o.b, o.bias, o.c, o.z, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, o.act, nullptr);
+}
+static int planned_bias_act_aux(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_bias_act_aux(o.a, o.b, o.bias, o.c, o.z, sh.M, sh.N, sh.K, o.act, nullptr); }
+static int aux_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_tn_bias_act_aux_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+// the activation's derivative at a saved Z (bgemm_mi355x_nn_dact), and --dbias: the same call that also writes db32 (ldz = N throughout)
+static int launch_dact(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_nn_dact(cfg, splits, o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, o.act, nullptr);
+}
+static int planned_dact(const TrCall& o, const Shape& sh) { return bgemm_mi355x_nn_dact(o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, o.act, nullptr); }
+static int dact_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_nn_dact_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+static int launch_dact_dbias(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_nn_dact_dbias(cfg, splits, o.a, o.b, o.z, o.c, o.db32, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, o.act, o.accumulate, nullptr);
+}
+static int planned_dact_dbias(const TrCall& o, const Shape& sh) { return bgemm_mi355x_nn_dact_dbias(o.a, o.b, o.z, o.c, o.db32, sh.M, sh.N, sh.K, o.act, o.accumulate, nullptr); }
+static int dact_dbias_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_nn_dact_dbias_runs(cfg, M, N, K, lda, ldb, ldc, N); }
 
-// What tr_bench is told about one bench (the descriptions themselves: bench_nn ... bench_tn_bias, below).
+// What tr_bench is told about one bench (the descriptions themselves: bench_nn ... bench_nn_dact_dbias, below).
 struct TrBench;
 struct BenchDesc {
   unsigned long long seed0;       // operand set i is filled from seed0 + i
@@ -1120,39 +1155,71 @@ static void warm_hipblaslt(bool autotune) {
   hgemm_hipblaslt_heuristic_init();
   if (autotune) hgemm_hipblaslt_autotune_init();
 }
-static void bench_nn(TrBench&), bench_ta(TrBench&), bench_ta_c32(TrBench&), bench_bf16(TrBench&), bench_tn_bf16(TrBench&), bench_tn_bias(TrBench&);
+static void bench_nn(TrBench&), bench_ta(TrBench&), bench_ta_c32(TrBench&), bench_bf16(TrBench&), bench_tn_bf16(TrBench&), bench_tn_bias(TrBench&),
+    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&);
 static const BenchDesc kBenchNN = {77, warm_hipblaslt, bench_nn}, kBenchTA = {91, warm_none, bench_ta}, kBenchTAC32 = {91, warm_none, bench_ta_c32},
-                       kBenchBF16 = {91, warm_rocblas, bench_bf16}, kBenchTN = {91, warm_rocblas, bench_tn_bf16},
-                       kBenchTNBias = {91, warm_none, bench_tn_bias};
+                       kBenchBF16 = {91, warm_rocblas, bench_bf16}, kBenchTN = {91, warm_rocblas, bench_tn_bf16}, kBenchTNBias = {91, warm_none, bench_tn_bias},
+                       kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act}, kBenchTNAux = {91, warm_none, bench_tn_aux},
+                       kBenchNNDact = {91, warm_none, bench_nn_dact}, kBenchNNDactDbias = {91, warm_none, bench_nn_dact_dbias};
+
+// What tr_check is told about one kind (the functions themselves: below, above tr_check).
+struct Check;
+struct CheckDesc {
+  int (*operands)(Check&);        // per shape: the host operands and the exact host result; 0, or the exit status of a refusal
+  int (*judge)(Check&);           // per finished run: compares, reports through Check::report; 0, or the exit status that ends the check
+  void (*summary)(const Check&);  // the closing line(s)
+};
+static int operands_zero_one(Check&), operands_small_int(Check&), judge_exact(Check&), judge_act(Check&), judge_dbias(Check&);
+static void summary_exact(const Check&), summary_act(const Check&);
+static const CheckDesc kCheckExact = {operands_zero_one, judge_exact, summary_exact}, kCheckAct = {operands_small_int, judge_act, summary_act},
+                       kCheckDbias = {operands_small_int, judge_dbias, summary_act};
 
 struct Variant {
   const TrLayout* L;
   Elem elem;
-  Out out;
+  const OutKind* out;
   int (*runs)(int cfg, int M, int N, int K, int lda, int ldb, int ldc);   // 1: the family's kernel takes the call
   int (*launch)(int cfg, int splits, const TrCall&, const Shape&, int lda, int ldb);
   int (*planned)(const TrCall&, const Shape&);
+  const CheckDesc* check;
   const BenchDesc* bench;
-  std::string words(const char* layout, const char* sep) const {   // "ta-c32-bf16" / "--layout ta --c32 --bf16"
-    return std::string(layout) + L->label + (out == kC32 ? std::string(sep) + "c32" : "") + (elem == kBF16 ? std::string(sep) + "bf16" : "") +
-           (out == kC16Bias ? std::string(sep) + "bias" : "");
+  // "ta-c32-bf16" / "--layout ta --c32 --bf16"; with an activation the check's label, "tn-bf16-bias-gelu-aux" / "nn-bf16-dact-relu-dbias"
+  std::string words(const char* layout, const char* sep, int act = 0) const {
+    std::string w = std::string(layout) + L->label + (out->c32 ? std::string(sep) + "c32" : "") + (elem == kBF16 ? std::string(sep) + "bf16" : "") +
+                    (out->bias ? std::string(sep) + "bias" : "");
+    if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
+                  (out->db32 ? std::string(sep) + "dbias" : "");
+    return w;
   }
   int runs_at(int cfg, const Shape& sh) const { return runs(cfg, sh.M, sh.N, sh.K, L->lda(sh), L->ldb(sh), sh.N); }
 };
 static const Variant kVariants[] = {
-    {&kLayoutNN, kF16, kC16, hgemm_mi355x_nn_runs, launch16<hgemm_mi355x_launch_nn>, planned16<hgemm_mi355x_nn_fp32>, &kBenchNN},
-    {&kLayoutTA, kF16, kC16, hgemm_mi355x_ta_runs, launch16<hgemm_mi355x_launch_ta>, planned16<hgemm_mi355x_ta_fp32>, &kBenchTA},
-    {&kLayoutTA, kF16, kC32, hgemm_mi355x_ta_c32_runs, launch32<hgemm_mi355x_launch_ta_c32>, planned32<hgemm_mi355x_ta_c32>, &kBenchTAC32},
-    {&kLayoutNN, kBF16, kC16, bgemm_mi355x_nn_runs, launch16<bgemm_mi355x_launch_nn>, planned16<bgemm_mi355x_nn>, &kBenchBF16},
-    {&kLayoutTA, kBF16, kC16, bgemm_mi355x_ta_runs, launch16<bgemm_mi355x_launch_ta>, planned16<bgemm_mi355x_ta>, &kBenchBF16},
-    {&kLayoutTA, kBF16, kC32, bgemm_mi355x_ta_c32_runs, launch32<bgemm_mi355x_launch_ta_c32>, planned32<bgemm_mi355x_ta_c32>, &kBenchBF16},
-    {&kLayoutTN, kBF16, kC16, bgemm_mi355x_tn_runs, launch16<bgemm_mi355x_launch_tn>, planned16<bgemm_mi355x_tn>, &kBenchTN},
-    {&kLayoutTN, kBF16, kC16Bias, bgemm_mi355x_tn_bias_runs, launch_bias, planned_bias, &kBenchTNBias},
+    {&kLayoutNN, kF16, &kOutC16, hgemm_mi355x_nn_runs, launch16<hgemm_mi355x_launch_nn>, planned16<hgemm_mi355x_nn_fp32>, &kCheckExact, &kBenchNN},
+    {&kLayoutTA, kF16, &kOutC16, hgemm_mi355x_ta_runs, launch16<hgemm_mi355x_launch_ta>, planned16<hgemm_mi355x_ta_fp32>, &kCheckExact, &kBenchTA},
+    {&kLayoutTA, kF16, &kOutC32, hgemm_mi355x_ta_c32_runs, launch32<hgemm_mi355x_launch_ta_c32>, planned32<hgemm_mi355x_ta_c32>, &kCheckExact, &kBenchTAC32},
+    {&kLayoutNN, kBF16, &kOutC16, bgemm_mi355x_nn_runs, launch16<bgemm_mi355x_launch_nn>, planned16<bgemm_mi355x_nn>, &kCheckExact, &kBenchBF16},
+    {&kLayoutTA, kBF16, &kOutC16, bgemm_mi355x_ta_runs, launch16<bgemm_mi355x_launch_ta>, planned16<bgemm_mi355x_ta>, &kCheckExact, &kBenchBF16},
+    {&kLayoutTA, kBF16, &kOutC32, bgemm_mi355x_ta_c32_runs, launch32<bgemm_mi355x_launch_ta_c32>, planned32<bgemm_mi355x_ta_c32>, &kCheckExact, &kBenchBF16},
+    {&kLayoutTN, kBF16, &kOutC16, bgemm_mi355x_tn_runs, launch16<bgemm_mi355x_launch_tn>, planned16<bgemm_mi355x_tn>, &kCheckExact, &kBenchTN},
+    {&kLayoutTN, kBF16, &kOutBias, bgemm_mi355x_tn_bias_runs, launch_bias, planned_bias, &kCheckExact, &kBenchTNBias},
+    {&kLayoutTN, kBF16, &kOutBiasAct, bgemm_mi355x_tn_bias_act_runs, launch_bias_act, planned_bias_act, &kCheckAct, &kBenchTNBiasAct},
+    {&kLayoutTN, kBF16, &kOutBiasAux, aux_runs, launch_bias_act_aux, planned_bias_act_aux, &kCheckAct, &kBenchTNAux},
+    {&kLayoutNN, kBF16, &kOutDact, dact_runs, launch_dact, planned_dact, &kCheckAct, &kBenchNNDact},
+    {&kLayoutNN, kBF16, &kOutDactDbias, dact_dbias_runs, launch_dact_dbias, planned_dact_dbias, &kCheckDbias, &kBenchNNDactDbias},
+};
+// What the command line says of the call; act, dact: 0, or the A of --act A / --dact A as HGEMM_ACT_RELU / _GELU / _GELU_TANH.
+struct TrFlags {
+  std::string layout;
+  bool bf16 = false, c32 = false, bias = false, aux = false, dbias = false;
+  int act = 0, dact = 0;
+  int activation() const { return act ? act : dact; }
 };
 // nullptr: no such variant (--layout tn without --bf16 and no --layout at all are the fp16 b_col_major commands)
-static const Variant* resolve_variant(const std::string& layout, bool bf16, bool c32, bool bias) {
+static const Variant* resolve_variant(const TrFlags& f) {
   for (const Variant& v : kVariants)
-    if (layout == v.L->label && (v.elem == kBF16) == bf16 && (v.out == kC32) == c32 && (v.out == kC16Bias) == bias) return &v;
+    if (f.layout == v.L->label && (v.elem == kBF16) == f.bf16 && v.out->c32 == f.c32 && v.out->bias == f.bias && v.out->db32 == f.dbias &&
+        v.out->z == (f.dact ? kZRead : f.aux ? kZWritten : kZNone) && v.out->act == (f.activation() != 0))
+      return &v;
   return nullptr;
 }
 
@@ -1178,101 +1245,319 @@ struct DevBufs {   // the device allocations of one scope: freed when it ends, o
 // The fused-bias check's bias is bias[n] = ((n mod 255) - 127) / 2: bf16 values, and with the integer sums S <= K exact in fp32, so the
 // expected C is bf16(S + bias[n]), rounded once.
 static float check_bias(int n) { return (float)((n % 255) - 127) * 0.5f; }
-static std::vector<f16> transposed(const std::vector<f16>& v, int rows, int cols) {   // [rows][cols] -> [cols][rows]
-  std::vector<f16> t(v.size());
+template <class T> static std::vector<T> transposed(const std::vector<T>& v, int rows, int cols) {   // [rows][cols] -> [cols][rows]
+  std::vector<T> t(v.size());
   for (int r = 0; r < rows; ++r)
     for (int c = 0; c < cols; ++c) t[(size_t)c * rows + r] = v[(size_t)r * cols + c];
   return t;
 }
 
-static int tr_check(const Variant& V, std::vector<Shape> shapes) {
-  const TrLayout& L = *V.L;
-  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
-  const bool c32 = V.out == kC32, bias = V.out == kC16Bias;
-  const size_t esz = c32 ? 4 : 2;   // bytes per element of C
-  const std::string lay_s = V.words("", "-");
-  const char* lay = lay_s.c_str();
-  const int nc = L.num_configs();
+constexpr int DBIAS_GUARD = 8;               // floats behind db32[N - 1] that must keep DBIAS_SENTINEL
+constexpr float DBIAS_SENTINEL = -12345.625f;
+// db32 as a run finds it: N floats -- NaN, or with `old` a fixed pattern to accumulate onto -- and the sentinels behind them
+static std::vector<float> dbias_prefill(int N, bool old) {
+  std::vector<float> v(N + DBIAS_GUARD, std::nanf(""));
+  for (int n = 0; n < N && old; ++n) v[n] = (float)((n * 37) % 129 - 64) * 0.3f;
+  for (int n = 0; n < DBIAS_GUARD; ++n) v[N + n] = DBIAS_SENTINEL;
+  return v;
+}
+
+// One check as its kind's functions (CheckDesc) see it: the tallies, the shape at hand with what `operands` made of it, the run at hand.
+struct Check {
+  const Variant& V;
+  const int act;
+  const std::string lay;                  // the label of every line: V's words and the activation
   int failures = 0, runs = 0;
-  for (const Shape& sh : shapes) {
-    const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
-    const size_t cn = (size_t)sh.M * sh.N;
-    // the expected C as bytes: want[0] what a store leaves, want[1] (fp32 C alone) what accumulating onto `old` leaves
-    std::vector<unsigned char> want[2] = {std::vector<unsigned char>(cn * esz), std::vector<unsigned char>(c32 ? cn * esz : 0)}, got(cn * esz);
-    std::vector<float> old(c32 ? cn : 0);
-    uint64_t lcg = 88172645463325252ull + cn;
-    for (int m = 0; m < sh.M; ++m)
-      for (int n = 0; n < sh.N; ++n) {
-        int acc = 0;
-        for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
-        const size_t i = (size_t)m * sh.N + n;
-        if (c32) {
-          lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-          old[i] = (float)((int)((lcg >> 33) % 2001) - 1000);
-          const float stored = (float)acc, summed = old[i] + stored;   // integers below 2^24: exact
-          memcpy(&want[0][i * 4], &stored, 4);
-          memcpy(&want[1][i * 4], &summed, 4);
-        } else {
-          const f16 t16 = (f16)(float)acc;   // int -> fp32 exact, fp32 -> fp16 round-to-nearest-even
-          const uint16_t tb = bf16_rne((float)acc + (bias ? check_bias(n) : 0.f));
-          memcpy(&want[0][i * 2], V.elem == kBF16 ? (const void*)&tb : (const void*)&t16, 2);
-        }
+  double worst = 0.0, worst_db = 0.0;     // the GELU bars: the largest err / bar that passed, of C and of db32
+  Shape sh = {};
+  size_t cn = 0;                          // M N
+  struct Host {
+    std::vector<uint16_t> a, b, bias, z;  // the bits to upload, A and B as the layout takes them; z [M][N]: Z of a dact call, of an aux call what z_out must hold
+    std::vector<unsigned char> want[2];   // operands_zero_one: the expected C as bytes: [0] what a store leaves, [1] (fp32 C alone) what accumulating onto `old` leaves
+    std::vector<float> old;
+    std::vector<uint16_t> relu;           // operands_small_int: ReLU's exact C,
+    std::vector<double> y, eps;           //   the GELUs' fp64 target y* and the second term of their bar
+  } h;
+  TrCall call = {};
+  int cfg = 0, splits = 1;
+  const char* cname = "";
+  std::vector<unsigned char> got;         // C read back
+  void report(size_t bad) {               // the run's elements outside its bar
+    if (!bad) return;
+    printf("FAIL %s %d_%d_%d %s s=%d%s%s: %zu/%zu elements %s\n", lay.c_str(), sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
+           (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", !V.out->c32 ? "" : call.accumulate ? " accumulate" : " store", bad, cn,
+           V.out->act && act != HGEMM_ACT_RELU ? "outside the bar" : "differ from the exact result");
+    ++failures;
+  }
+};
+
+static int operands_zero_one(Check& K) {
+  const Variant& V = K.V;
+  const Shape& sh = K.sh;
+  const bool c32 = V.out->c32, bias = V.out->bias;
+  const size_t esz = c32 ? 4 : 2, cn = K.cn;
+  const ZeroOne z = make_zero_one(sh, 4321 + sh.M + sh.N * 3 + sh.K * 7);
+  K.h.want[0].resize(cn * esz);
+  K.h.want[1].resize(c32 ? cn * esz : 0);
+  K.h.old.resize(c32 ? cn : 0);
+  uint64_t lcg = 88172645463325252ull + cn;
+  for (int m = 0; m < sh.M; ++m)
+    for (int n = 0; n < sh.N; ++n) {
+      int acc = 0;
+      for (int w = 0; w < z.words; ++w) acc += __builtin_popcountll(z.abits[(size_t)m * z.words + w] & z.bbits[(size_t)n * z.words + w]);
+      const size_t i = (size_t)m * sh.N + n;
+      if (c32) {
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        K.h.old[i] = (float)((int)((lcg >> 33) % 2001) - 1000);
+        const float stored = (float)acc, summed = K.h.old[i] + stored;   // integers below 2^24: exact
+        memcpy(&K.h.want[0][i * 4], &stored, 4);
+        memcpy(&K.h.want[1][i * 4], &summed, 4);
+      } else {
+        const f16 t16 = (f16)(float)acc;   // int -> fp32 exact, fp32 -> fp16 round-to-nearest-even
+        const uint16_t tb = bf16_rne((float)acc + (bias ? check_bias(n) : 0.f));
+        memcpy(&K.h.want[0][i * 2], V.elem == kBF16 ? (const void*)&tb : (const void*)&t16, 2);
       }
-    DevBufs dev;
-    const std::vector<uint16_t> a_h = operand_bits(L.a_col_major ? transposed(z.a, sh.M, sh.K) : z.a, V.elem);     // (z.a: [M][K])
-    const std::vector<uint16_t> b_h = operand_bits(L.b_col_major ? z.bt : transposed(z.bt, sh.N, sh.K), V.elem);   // (z.bt: [N][K])
-    TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), nullptr, dev.alloc(cn * esz), 0};
-    if (bias) {
-      std::vector<uint16_t> hb(sh.N);
-      for (int n = 0; n < sh.N; ++n) hb[n] = bf16_rne(check_bias(n));
-      call.bias = dev.upload(hb.data(), hb.size() * 2);
     }
+  K.h.a = operand_bits(V.L->a_col_major ? transposed(z.a, sh.M, sh.K) : z.a, V.elem);   // (z.a: [M][K])
+  K.h.b = operand_bits(V.L->b_col_major ? z.bt : transposed(z.bt, sh.N, sh.K), V.elem);   // (z.bt: [N][K])
+  for (int n = 0; n < sh.N && bias; ++n) K.h.bias.push_back(bf16_rne(check_bias(n)));
+  return 0;
+}
+static int judge_exact(Check& K) {   // bit for bit
+  const size_t esz = K.V.out->c32 ? 4 : 2;
+  const unsigned char* w = K.h.want[K.call.accumulate].data();
+  size_t bad = 0;
+  for (size_t i = 0; i < K.cn; ++i)
+    if (memcmp(&K.got[i * esz], &w[i * esz], esz) != 0) {
+      if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) {
+        uint32_t gv = 0, wv = 0;
+        memcpy(&gv, &K.got[i * esz], esz);
+        memcpy(&wv, &w[i * esz], esz);
+        printf("   bad m=%zu n=%zu got 0x%0*x want 0x%0*x\n", i / K.sh.N, i % K.sh.N, (int)esz * 2, gv, (int)esz * 2, wv);
+      }
+      ++bad;
+    }
+  K.report(bad);
+  return 0;
+}
+static void summary_exact(const Check& K) {
+  printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs%s)\n", K.lay.c_str(), K.runs, K.failures,
+         K.V.out->c32 ? " and an integer old C32" : K.V.out->bias ? " plus the bias, rounded to bf16 once" : K.V.elem == kBF16 ? ", rounded to bf16 once" : "");
+}
+
+// ---- The activation kinds' check ------------------------------------------------------------------------------------------------------------
+// --act A (with --layout tn --bf16 --bias; bgemm_mi355x_tn_bias_act): C = bf16(act(S + bias[n])).  A bias of multiples of 2^-8 in [-1, 1]:
+// z = S + bias is exact in fp32 in any order.  The bars: ReLU bit for bit against (z > 0 ? bf16(z) : +0); both GELUs
+// |C - y*| <= 1/2 ulp_bf16(y*) + 2^-19 |z|, y* the fp64 activation of z.  --aux: z_out = bf16(z), held bit for bit next to C's bars.
+// --dact A (with --layout nn --bf16; bgemm_mi355x_nn_dact): C = bf16(S x act'(float(z))).  Z is a seeded matrix of multiples of 1/32 in
+// [-4, 4] (bf16 values; both signs, zeros, some -0, the range of a negative derivative).  The bars: ReLU bit for bit against
+// (z <= 0 ? +0 : bf16(S)); both GELUs |C - S g*| <= 1/2 ulp_bf16(S g*) + DACT_EPS |S|, g* in fp64.
+static double act_fp64(double z, int act) {
+  if (act == HGEMM_ACT_RELU) return z > 0 ? z : 0.0;
+  if (act == HGEMM_ACT_GELU) return 0.5 * z * erfc(-z / sqrt(2.0));
+  const double u = sqrt(2.0 / M_PI) * (z + 0.044715 * z * z * z);
+  return z / (1.0 + exp(-2.0 * u));
+}
+static double dact_fp64(double z, int act) {
+  if (act == HGEMM_ACT_RELU) return z <= 0 ? 0.0 : 1.0;
+  if (act == HGEMM_ACT_GELU) return 0.5 * erfc(-z / sqrt(2.0)) + z * exp(-0.5 * z * z) / sqrt(2.0 * M_PI);
+  const double c = sqrt(2.0 / M_PI), s = 1.0 / (1.0 + exp(-2.0 * c * (z + 0.044715 * z * z * z)));
+  return s + z * s * (1.0 - s) * 2.0 * c * (1.0 + 3.0 * 0.044715 * z * z);
+}
+static double bf16_value(uint16_t h) {
+  const uint32_t u = (uint32_t)h << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return (double)f;
+}
+// Integers in -2 .. 2, A scaled by 2^-(floor(log2 K) - 2); drawn in the order A, B (as the layout hands it over), for a dact call then Z.
+static int operands_small_int(Check& K) {
+  const Shape& sh = K.sh;
+  const size_t cn = K.cn;
+  const bool dact = K.V.out->z == kZRead;
+  int j = 0;
+  while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
+  const double scale = ldexp(1.0, -std::max(j - 2, 0));
+  uint64_t lcg = 0x9E3779B97F4A7C15ull + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
+  auto next = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(lcg >> 33); };
+  std::vector<int8_t> ai((size_t)sh.M * sh.K), bi((size_t)sh.K * sh.N);
+  for (auto& v : ai) v = (int8_t)((int)(next() % 5) - 2);
+  for (auto& v : bi) v = (int8_t)((int)(next() % 5) - 2);
+  for (int8_t v : ai) K.h.a.push_back(bf16_rne((float)(v * scale)));   // a small integer times a power of two: a bf16 value
+  for (int8_t v : bi) K.h.b.push_back(bf16_rne((float)v));
+  std::vector<double> bias(sh.N, 0.0), z(dact ? cn : 0);
+  for (int n = 0; n < sh.N && K.V.out->bias; ++n) {
+    bias[n] = (double)(((n * 37 + 11) % 513) - 256) / 256.0;   // |q| <= 256: at most 8 significant bits, a bf16 value
+    K.h.bias.push_back(bf16_rne((float)bias[n]));
+  }
+  K.h.z.resize(cn), K.h.relu.resize(cn), K.h.y.resize(cn), K.h.eps.resize(cn);
+  for (size_t i = 0; i < z.size(); ++i) {
+    z[i] = (double)((int)(next() % 257) - 128) / 32.0;   // |q| <= 128: at most 8 significant bits, a bf16 value
+    K.h.z[i] = (i % 29 == 7) ? (uint16_t)0x8000 : bf16_rne((float)z[i]);   // some -0
+    if (i % 29 == 7) z[i] = 0.0;
+  }
+  const std::vector<int8_t> bt = K.V.L->b_col_major ? bi : transposed(bi, sh.K, sh.N);   // [N][K]
+  for (int m = 0; m < sh.M; ++m)
+    for (int n = 0; n < sh.N; ++n) {
+      int acc = 0;
+      const int8_t *ar = &ai[(size_t)m * sh.K], *br = &bt[(size_t)n * sh.K];
+      for (int k = 0; k < sh.K; ++k) acc += ar[k] * br[k];
+      const double s = acc * scale, t = s + bias[n];   // t: the pre-activation of an act call
+      if ((double)(float)t != t || (double)(float)s != s) {
+        fprintf(stderr, "check %s: %s is not exact in fp32 at %d_%d_%d\n", K.lay.c_str(), dact ? "S" : "z", sh.M, sh.N, sh.K);
+        return 2;
+      }
+      const size_t i = (size_t)m * sh.N + n;
+      if (dact) {
+        K.h.relu[i] = z[i] <= 0 ? (uint16_t)0 : bf16_rne((float)s);
+        K.h.y[i] = s * dact_fp64(z[i], K.act), K.h.eps[i] = (double)hgemm_mi355x::DACT_EPS * fabs(s);
+      } else {
+        K.h.z[i] = bf16_rne((float)t);
+        K.h.relu[i] = t > 0 ? K.h.z[i] : (uint16_t)0;
+        K.h.y[i] = act_fp64(t, K.act), K.h.eps[i] = ldexp(fabs(t), -19);
+      }
+    }
+  return 0;
+}
+// The GELU bar of one element: |c - y| <= 1/2 ulp_bf16(y) + eps (a NaN fails); `worst` keeps the largest err / bar that passed.
+static bool within_gelu_bar(uint16_t c, double y, double eps, double& worst) {
+  const double bar = (y != 0 ? ldexp(1.0, (int)floor(log2(fabs(y))) - 8) : 0.0) + eps, err = fabs(bf16_value(c) - y);
+  if (!(err <= bar)) return false;
+  if (bar > 0) worst = std::max(worst, err / bar);
+  return true;
+}
+static int judge_act(Check& K) {   // act, aux, dact; the C of dbias
+  const uint16_t* got = (const uint16_t*)K.got.data();
+  size_t bad = 0;
+  if (K.V.out->z == kZWritten) {   // z_out = bf16(z), bit for bit
+    std::vector<uint16_t> got_z(K.cn);
+    HIP_OK(hipMemcpy(got_z.data(), K.call.z, K.cn * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < K.cn; ++i) bad += got_z[i] != K.h.z[i];
+  }
+  for (size_t i = 0; i < K.cn; ++i) bad += K.act == HGEMM_ACT_RELU ? got[i] != K.h.relu[i] : !within_gelu_bar(got[i], K.h.y[i], K.h.eps[i], K.worst);
+  K.report(bad);
+  return 0;
+}
+// --dbias: C by the dact bars, then: C is the dact call's at the same plan bit for bit; db32 is the column sum of the C read back, taken in
+// fp64 -- ReLU: every C is a multiple of `scale` and every column sum exact in fp32 in any order (verified), so bit for bit; the GELUs:
+// inside gamma_(M-1) sum |C|, the bound of an M-term fp32 sum in any order (hgemm_dbias.hpp) --; nothing behind db32[N - 1] is written;
+// accumulate = 1 is fl32(old + s).  (Two more launches, not counted as runs.)
+static int judge_dbias(Check& K) {
+  judge_act(K);
+  const Shape& sh = K.sh;
+  const size_t cn = K.cn;
+  const int lda = K.V.L->lda(sh), ldb = K.V.L->ldb(sh);
+  const char* lay = K.lay.c_str();
+  const uint16_t* got = (const uint16_t*)K.got.data();
+  const std::vector<float> db_old = dbias_prefill(sh.N, true);
+  std::vector<float> db_got(db_old.size()), db_acc(db_old.size());
+  std::vector<uint16_t> dact_c(cn);
+  DevBufs dev;
+  TrCall twin = K.call;   // the dact call on the same operands, into a C of its own
+  twin.c = dev.alloc(cn * 2);
+  HIP_OK(hipMemcpy(db_got.data(), K.call.db32, db_got.size() * 4, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemset(twin.c, 0xff, cn * 2));
+  const int st_d = launch_dact(K.cfg, K.splits, twin, sh, lda, ldb);
+  HIP_OK(hipMemcpy(K.call.db32, db_old.data(), db_old.size() * 4, hipMemcpyHostToDevice));
+  K.call.accumulate = 1;
+  const int st_a = K.V.launch(K.cfg, K.splits, K.call, sh, lda, ldb);
+  K.call.accumulate = 0;
+  const hipError_t e_d = hipDeviceSynchronize();
+  if (e_d != hipSuccess) { printf("FAIL %s %d_%d_%d %s s=%d: hip %d\n", lay, sh.M, sh.N, sh.K, K.cname, K.splits & HGEMM_SPLITK_MASK, (int)e_d); return 3; }
+  HIP_OK(hipMemcpy(dact_c.data(), twin.c, cn * 2, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(db_acc.data(), K.call.db32, db_acc.size() * 4, hipMemcpyDeviceToHost));
+  size_t c_differs = 0, db_bad = 0, acc_bad = 0, guard_bad = 0;
+  for (size_t i = 0; i < cn; ++i) c_differs += got[i] != dact_c[i];
+  for (int n = 0; n < DBIAS_GUARD; ++n) guard_bad += (db_got[sh.N + n] != DBIAS_SENTINEL) + (db_acc[sh.N + n] != DBIAS_SENTINEL);
+  for (int n = 0; n < sh.N; ++n) {
+    double sum = 0.0, mag = 0.0;
+    for (int m = 0; m < sh.M; ++m) { const double v = bf16_value(got[(size_t)m * sh.N + n]); sum += v; mag += fabs(v); }
+    if (K.act == HGEMM_ACT_RELU) {
+      if ((double)(float)sum != sum) { fprintf(stderr, "check %s: a column sum is not exact in fp32 at %d_%d_%d\n", lay, sh.M, sh.N, sh.K); return 2; }
+      const float want = (float)sum;
+      db_bad += memcmp(&want, &db_got[n], 4) != 0;
+    } else {
+      const double bar = hgemm_mi355x::colsum_gamma(sh.M) * mag, err = fabs((double)db_got[n] - sum);
+      if (!(err <= bar)) ++db_bad;   // (a NaN fails)
+      else if (bar > 0) K.worst_db = std::max(K.worst_db, err / bar);
+    }
+    const float want_acc = db_old[n] + db_got[n];
+    acc_bad += memcmp(&want_acc, &db_acc[n], 4) != 0;
+  }
+  if (st_d != HGEMM_OK || st_a != HGEMM_OK || c_differs || db_bad || acc_bad || guard_bad) {
+    printf("FAIL %s %d_%d_%d %s s=%d%s: status %d %d, %zu/%zu elements of C differ from the dact call's, %zu/%d columns of db32 %s, %zu not fl32(old + s), "
+           "%zu guard floats written\n", lay, sh.M, sh.N, sh.K, K.cname, K.splits & HGEMM_SPLITK_MASK, (K.splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", st_d, st_a,
+           c_differs, cn, db_bad, sh.N, K.act == HGEMM_ACT_RELU ? "differ from the exact sum" : "outside the bar", acc_bad, guard_bad);
+    ++K.failures;
+  }
+  return 0;
+}
+static void summary_act(const Check& K) {
+  const char* lay = K.lay.c_str();
+  const bool relu = K.act == HGEMM_ACT_RELU, dact = K.V.out->z == kZRead;
+  if (K.V.out->db32 && relu) printf("check-%s-db32: bit-exact against the fp64 column sum of the C read back; C the dact call's bit for bit\n", lay);
+  else if (K.V.out->db32) printf("check-%s-db32: every column within gamma_(M-1) sum |C| of the fp64 column sum of the C read back (worst %.3f of it); "
+                                 "C the dact call's bit for bit\n", lay, K.worst_db);
+  if (relu) printf("check %s: %d runs, %d failures (bit-exact against %s)\n", lay, K.runs, K.failures,
+                   dact ? "where(z <= 0, +0, bf16(S)) of the exact S" : "where(z > 0, bf16(z), +0) of the exact z");
+  else printf("check %s: %d runs, %d failures (every element within %s; worst %.3f of it)\n", lay, K.runs, K.failures,
+              dact ? "1/2 ulp_bf16(S g*) + 2^-19 |S| of the fp64 product" : "1/2 ulp_bf16(y*) + 2^-19 |z| of the fp64 activation of the exact z", K.worst);
+}
+
+static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
+  const TrLayout& L = *V.L;
+  const OutKind& O = *V.out;
+  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
+  const size_t esz = O.c32 ? 4 : 2;   // bytes per element of C
+  Check K = {V, act, V.words("", "-", act)};
+  const char* lay = K.lay.c_str();
+  const int nc = L.num_configs();
+  for (const Shape& sh : shapes) {
+    const size_t cn = (size_t)sh.M * sh.N;
+    K.sh = sh, K.cn = cn, K.h = {};
+    if (const int refused = V.check->operands(K)) return refused;
+    DevBufs dev;
+    TrCall& call = K.call;
+    call = {dev.upload(K.h.a.data(), K.h.a.size() * 2), dev.upload(K.h.b.data(), K.h.b.size() * 2),
+            O.bias ? dev.upload(K.h.bias.data(), K.h.bias.size() * 2) : nullptr, dev.alloc(cn * esz), 0,
+            O.z == kZRead ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : nullptr,
+            O.db32 ? (float*)dev.alloc((sh.N + DBIAS_GUARD) * sizeof(float)) : nullptr, act};
+    K.got.resize(cn * esz);
     for (int c = 0; c < nc; ++c) {
-      const char* cname = L.config_name(c);
+      K.cfg = c;
+      K.cname = L.config_name(c);
       const int own = V.runs_at(c, sh);
       for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5})
-        for (call.accumulate = 0; call.accumulate <= (c32 ? 1 : 0); ++call.accumulate) {
-          if (call.accumulate) HIP_OK(hipMemcpy(call.c, old.data(), cn * esz, hipMemcpyHostToDevice));
+        for (call.accumulate = 0; call.accumulate <= (O.c32 ? 1 : 0); ++call.accumulate) {
+          K.splits = splits;
+          if (call.accumulate) HIP_OK(hipMemcpy(call.c, K.h.old.data(), cn * esz, hipMemcpyHostToDevice));
           else                 HIP_OK(hipMemset(call.c, 0xff, cn * esz));   // NaN pattern: a store must not read it, unwritten outputs are caught
+          if (O.z == kZWritten) HIP_OK(hipMemset(call.z, 0xff, cn * 2));
+          if (O.db32) HIP_OK(hipMemcpy(call.db32, dbias_prefill(sh.N, false).data(), (sh.N + DBIAS_GUARD) * sizeof(float), hipMemcpyHostToDevice));
           const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
           const hipError_t e = hipDeviceSynchronize();
-          ++runs;
+          ++K.runs;
           if (st != HGEMM_OK || e != hipSuccess) {
-            printf("FAIL %s %d_%d_%d %s s=%d%s: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
-                   !c32 ? "" : call.accumulate ? " acc=1" : " acc=0", st, (int)e);
-            ++failures;
+            printf("FAIL %s %d_%d_%d %s s=%d%s: status %d hip %d\n", lay, sh.M, sh.N, sh.K, K.cname, splits & HGEMM_SPLITK_MASK,
+                   !O.c32 ? "" : call.accumulate ? " acc=1" : " acc=0", st, (int)e);
+            ++K.failures;
             if (e != hipSuccess) return 3;
             continue;
           }
-          HIP_OK(hipMemcpy(got.data(), call.c, cn * esz, hipMemcpyDeviceToHost));
-          const unsigned char* w = want[call.accumulate].data();
-          size_t bad = 0;
-          for (size_t i = 0; i < cn; ++i)
-            if (memcmp(&got[i * esz], &w[i * esz], esz) != 0) {
-              if (bad < 8 && getenv("HGEMM_CHECK_VERBOSE")) {
-                uint32_t gv = 0, wv = 0;
-                memcpy(&gv, &got[i * esz], esz);
-                memcpy(&wv, &w[i * esz], esz);
-                printf("   bad m=%zu n=%zu got 0x%0*x want 0x%0*x\n", i / sh.N, i % sh.N, (int)esz * 2, gv, (int)esz * 2, wv);
-              }
-              ++bad;
-            }
-          if (bad) {
-            printf("FAIL %s %d_%d_%d %s s=%d%s%s: %zu/%zu elements differ from the exact result\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
-                   (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", !c32 ? "" : call.accumulate ? " accumulate" : " store", bad, cn);
-            ++failures;
-          }
+          HIP_OK(hipMemcpy(K.got.data(), call.c, cn * esz, hipMemcpyDeviceToHost));
+          if (const int ended = V.check->judge(K)) return ended;
         }
       if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
     }
     fflush(stdout);
   }
-  printf("check-%s-configs:", lay);
-  for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
-  printf("\ncheck-%s-forms: 1 1|nt-store 2 5%s\n", lay, c32 ? " x store accumulate" : "");
-  printf("check %s: %d runs, %d failures (bit-exact against the exact integer result of 0/1 inputs%s)\n", lay, runs, failures,
-         c32 ? " and an integer old C32" : bias ? " plus the bias, rounded to bf16 once" : V.elem == kBF16 ? ", rounded to bf16 once" : "");
-  return failures ? 1 : 0;
+  if (O.z != kZRead) {   // (the dact kinds' check has never printed the two footers; its output is kept byte for byte)
+    printf("check-%s-configs:", lay);
+    for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
+    printf("\ncheck-%s-forms: 1 1|nt-store 2 5%s\n", lay, O.c32 ? " x store accumulate" : "");
+  }
+  V.check->summary(K);
+  return K.failures ? 1 : 0;
 }
 
 // ---- bench --layout ...: the check first, then per shape ONE set of interleaved rounds (time_interleaved) of the variant's contenders --
@@ -1298,6 +1583,7 @@ struct TrBench {
   typedef std::array<void*, 2> PerSet;   // one device pointer per operand set
   const Variant& V;
   const Shape sh;
+  const int act;                         // the call's activation (HGEMM_ACT_*), 0 where the kind takes none
   const bool autotune;
   const size_t a_elems, b_elems, cn;
   std::vector<Buffers> sets;
@@ -1309,8 +1595,8 @@ struct TrBench {
   const char* verdict_key = nullptr;     // "<key>": cs[va] <= cs[vb] (+ cs[vb]'s slowest round minus its median, recorded as "<vb's key>_spread_us")
   int va = 0, vb = 1;
   bool with_spread = true;
-  TrBench(const Variant& v, const Shape& s, bool at)
-      : V(v), sh(s), autotune(at), a_elems((size_t)s.M * s.K), b_elems((size_t)s.K * s.N), cn((size_t)s.M * s.N), sets(2) {
+  TrBench(const Variant& v, int activation, const Shape& s, bool at)
+      : V(v), sh(s), act(activation), autotune(at), a_elems((size_t)s.M * s.K), b_elems((size_t)s.K * s.N), cn((size_t)s.M * s.N), sets(2) {
     for (size_t i = 0; i < sets.size(); ++i) alloc_set(sets[i], sh, V.bench->seed0 + i, true);
     V.L->plan(sh.M, sh.N, sh.K, &cfg, &splits);
   }
@@ -1350,14 +1636,8 @@ struct TrBench {
   void verdict(const char* key, int a, int b, bool spread) { verdict_key = key; va = a; vb = b; with_spread = spread; }
 };
 
-static int g_act = 0;   // --act: 0, or HGEMM_ACT_RELU / _GELU / _GELU_TANH (the fused bias+activation calls, below)
-static bool g_aux = false;   // --aux (with --act): bgemm_mi355x_tn_bias_act_aux, the same call that also writes z_out
-static int g_dact = 0;       // --dact A (with --layout nn --bf16): bgemm_mi355x_nn_dact
-static bool g_dbias = false; // --dbias (with --dact A): bgemm_mi355x_nn_dact_dbias, the same call that also writes db32
-static int act_check(std::vector<Shape> shapes);
-static int dact_check(std::vector<Shape> shapes);
-static int tr_bench(const Variant& V, const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
-  const int rc = g_dact ? dact_check({}) : g_act ? act_check({}) : tr_check(V, {});   // no timing of a kernel that is wrong
+static int tr_bench(const Variant& V, int act, const std::vector<Shape>& shapes, const char* out_path, bool autotune) {
+  const int rc = tr_check(V, act, {});   // no timing of a kernel that is wrong
   if (rc != 0) { fprintf(stderr, "bench %s: the check failed, nothing is timed\n", V.words("--layout ", " --").c_str()); return rc; }
   FILE* out = out_path ? fopen(out_path, "w") : stdout;
   if (!out) { fprintf(stderr, "cannot open %s\n", out_path); return 2; }
@@ -1366,7 +1646,7 @@ static int tr_bench(const Variant& V, const std::vector<Shape>& shapes, const ch
   HIP_OK(hipEventCreate(&e0));
   HIP_OK(hipEventCreate(&e1));
   for (const Shape& sh : shapes) {
-    TrBench B(V, sh, autotune);
+    TrBench B(V, act, sh, autotune);
     V.bench->shape(B);
     HIP_OK(hipDeviceSynchronize());
     time_interleaved(B.cs, B.sets, B.rounds, 0, 0.0, 1.0, e0, e1);
@@ -1454,8 +1734,8 @@ static void bench_ta_c32(TrBench& B) {
 static void bench_bf16(TrBench& B) {
   const Shape sh = B.sh;
   const TrLayout* L = B.V.L;
-  const bool c32 = B.V.out == kC32;
-  const Variant *bf = &B.V, *fp = resolve_variant(L->label, false, c32, false);   // (every bf16 variant of nn and ta has its fp16 twin)
+  const bool c32 = B.V.out->c32;
+  const Variant *bf = &B.V, *fp = resolve_variant({L->label, false, c32});   // (every bf16 variant of nn and ta has its fp16 twin)
   const TrBench::PerSet a16 = L->a_col_major ? B.a_col_major() : B.of(&Buffers::a);   // A as the layout takes it, fp16
   const TrBench::PerSet ab = B.to_bf16(a16, B.a_elems), bb = B.to_bf16(B.of(&Buffers::b), B.b_elems);
   const TrBench::PerSet cb = c32 ? B.alloc(B.cn * 4, true) : B.alloc(B.cn * 2), ch = c32 ? B.alloc(B.cn * 4, true) : B.of(&Buffers::c);
@@ -1484,6 +1764,25 @@ static void bench_tn_bf16(TrBench& B) {
   B.verdict("tn_le_nn", 0, 1, true);
 }
 
+// What the three tn --bf16 --bias benches share: each set's bf16 A and b_col_major B, a C, the filled bias.
+struct TnBiasBufs { TrBench::PerSet ab, btb, cb, bias; };
+static TnBiasBufs tn_bias_bufs(TrBench& B) {
+  const TnBiasBufs t = {B.to_bf16(B.of(&Buffers::a), B.a_elems), B.to_bf16(B.of(&Buffers::bt), B.b_elems), B.alloc(B.cn * 2), B.alloc((size_t)B.sh.N * 2)};
+  for (void* p : t.bias) fill_bias_kernel<<<64, 256>>>((__bf16*)p, B.sh.N);
+  return t;
+}
+static int elementwise_grid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 8192); }   // blocks of 256 for a grid-stride kernel
+// The one place a run-time activation becomes a template argument: f(std::integral_constant<int, ACT>()), for <<<>>> of an <ACT> kernel.
+template <class F> static void with_act(int act, F&& f) {
+  if (act == HGEMM_ACT_RELU) f(std::integral_constant<int, HGEMM_ACT_RELU>());
+  else if (act == HGEMM_ACT_GELU) f(std::integral_constant<int, HGEMM_ACT_GELU>());
+  else f(std::integral_constant<int, HGEMM_ACT_GELU_TANH>());
+}
+static void head_act(TrBench& B, const char* output) {   // the header fields of the activation kinds' records
+  B.head("\"output\": \"%s\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", output, kActNames[B.act],
+         B.V.L->config_name(B.cfg), B.splits, B.V.runs_at(B.cfg, B.sh));
+}
+
 // tn --bf16 --bias: the planned bgemm_mi355x_tn_bias call, bgemm_mi355x_launch_tn with the same member and splits and no bias -- the
 // fused kernel adds 2 BN bytes of loads and 4 FM FN adds per lane to a tile --, and, context only, the path the call replaces:
 // bgemm_mi355x_tn followed by an element-wise bf16 add (its launch is not checked: the contender answers with the product's status).
@@ -1491,11 +1790,9 @@ static void bench_tn_bf16(TrBench& B) {
 static void bench_tn_bias(TrBench& B) {
   const Shape sh = B.sh;
   const size_t cn = B.cn;
-  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh);
-  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), btb = B.to_bf16(B.of(&Buffers::bt), B.b_elems), cb = B.alloc(cn * 2),
-                        bias = B.alloc((size_t)sh.N * 2);
-  for (void* p : bias) fill_bias_kernel<<<64, 256>>>((__bf16*)p, sh.N);
-  const int add_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), add_grid = elementwise_grid(cn);
+  const TnBiasBufs t = tn_bias_bufs(B);
+  const TrBench::PerSet ab = t.ab, btb = t.btb, cb = t.cb, bias = t.bias;
   B.add("bias", [=](Buffers&, size_t i) { return bgemm_mi355x_tn_bias(ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, nullptr); });
   B.add("plain", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn(cfg, splits, ab[i], btb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
   B.add("unfused", [=](Buffers&, size_t i) {
@@ -1505,135 +1802,6 @@ static void bench_tn_bias(TrBench& B) {
   });
   B.head("\"output\": \"c16_bias\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
   B.verdict("bias_le_plain", 0, 1, true);
-}
-
-// ---- --act relu|gelu|gelu_tanh (with --layout tn --bf16 --bias): the fused bias+activation calls, bgemm_mi355x_tn_bias_act ---------------
-// C = bf16(act(S + bias[n])).  The check's operands are integers in -2 .. 2 with A scaled by 2^-(floor(log2 K) - 2) and a bias of multiples
-// of 2^-8 in [-1, 1]: z = S + bias is exact in fp32 in any order (verified per element) and lies in the activations' live range.  The bars:
-// ReLU bit for bit against (z > 0 ? bf16(z) : +0); both GELUs |C - y*| <= 1/2 ulp_bf16(y*) + 2^-19 |z|, y* the fp64 activation of z.
-static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh"};
-static double act_fp64(double z, int act) {
-  if (act == HGEMM_ACT_RELU) return z > 0 ? z : 0.0;
-  if (act == HGEMM_ACT_GELU) return 0.5 * z * erfc(-z / sqrt(2.0));
-  const double u = sqrt(2.0 / M_PI) * (z + 0.044715 * z * z * z);
-  return z / (1.0 + exp(-2.0 * u));
-}
-static double bf16_value(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return (double)f;
-}
-static int launch_bias_act(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
-  return bgemm_mi355x_launch_tn_bias_act(cfg, splits, o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, g_act, nullptr);
-}
-static int planned_bias_act(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_bias_act(o.a, o.b, o.bias, o.c, sh.M, sh.N, sh.K, g_act, nullptr); }
-static void bench_tn_bias_act(TrBench&);
-static const BenchDesc kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act};
-// (not in kVariants: resolve_variant answers the flags without --act; main swaps this one in when --act is given)
-static const Variant kVariantTNBiasAct = {&kLayoutTN, kBF16, kC16Bias, bgemm_mi355x_tn_bias_act_runs, launch_bias_act, planned_bias_act, &kBenchTNBiasAct};
-
-// --aux: the same call with the pre-activation as a second output, z_out = bf16(z), held bit for bit next to C's bars
-static int launch_bias_act_aux(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
-  return bgemm_mi355x_launch_tn_bias_act_aux(cfg, splits, o.a, o.b, o.bias, o.c, o.z, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, g_act, nullptr);
-}
-static int planned_bias_act_aux(const TrCall& o, const Shape& sh) {
-  return bgemm_mi355x_tn_bias_act_aux(o.a, o.b, o.bias, o.c, o.z, sh.M, sh.N, sh.K, g_act, nullptr);
-}
-static int aux_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_tn_bias_act_aux_runs(cfg, M, N, K, lda, ldb, ldc, N); }
-static void bench_tn_aux(TrBench&);
-static const BenchDesc kBenchTNAux = {91, warm_none, bench_tn_aux};
-static const Variant kVariantTNAux = {&kLayoutTN, kBF16, kC16Bias, aux_runs, launch_bias_act_aux, planned_bias_act_aux, &kBenchTNAux};
-
-static int act_check(std::vector<Shape> shapes) {
-  const Variant& V = g_aux ? kVariantTNAux : kVariantTNBiasAct;
-  const TrLayout& L = *V.L;
-  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
-  const std::string lay_s = V.words("", "-") + "-" + kActNames[g_act] + (g_aux ? "-aux" : "");
-  const char* lay = lay_s.c_str();
-  const int nc = L.num_configs();
-  int failures = 0, runs = 0;
-  double worst = 0.0;
-  for (const Shape& sh : shapes) {
-    const size_t cn = (size_t)sh.M * sh.N;
-    std::vector<uint16_t> got_z(g_aux ? cn : 0);
-    int j = 0;
-    while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
-    const double scale = ldexp(1.0, -std::max(j - 2, 0));
-    uint64_t lcg = 0x9E3779B97F4A7C15ull + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
-    auto draw = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (int)((lcg >> 33) % 5) - 2; };
-    std::vector<int8_t> ai((size_t)sh.M * sh.K), wi((size_t)sh.N * sh.K);
-    for (auto& v : ai) v = (int8_t)draw();
-    for (auto& v : wi) v = (int8_t)draw();
-    std::vector<uint16_t> a_h(ai.size()), w_h(wi.size()), b_h(sh.N), got(cn);
-    for (size_t i = 0; i < ai.size(); ++i) a_h[i] = bf16_rne((float)(ai[i] * scale));   // a small integer times a power of two: a bf16 value
-    for (size_t i = 0; i < wi.size(); ++i) w_h[i] = bf16_rne((float)wi[i]);
-    std::vector<double> bias(sh.N), z(cn);
-    for (int n = 0; n < sh.N; ++n) {
-      bias[n] = (double)(((n * 37 + 11) % 513) - 256) / 256.0;   // |q| <= 256: at most 8 significant bits, a bf16 value
-      b_h[n] = bf16_rne((float)bias[n]);
-    }
-    for (int m = 0; m < sh.M; ++m)
-      for (int n = 0; n < sh.N; ++n) {
-        int s = 0;
-        const int8_t *ar = &ai[(size_t)m * sh.K], *wr = &wi[(size_t)n * sh.K];
-        for (int k = 0; k < sh.K; ++k) s += ar[k] * wr[k];
-        const double zz = s * scale + bias[n];
-        if ((double)(float)zz != zz || (double)(float)(s * scale) != s * scale) { fprintf(stderr, "check %s: z is not exact in fp32 at %d_%d_%d\n", lay, sh.M, sh.N, sh.K); return 2; }
-        z[(size_t)m * sh.N + n] = zz;
-      }
-    DevBufs dev;
-    TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(w_h.data(), w_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), dev.alloc(cn * 2), 0};
-    if (g_aux) call.z = dev.alloc(cn * 2);
-    for (int c = 0; c < nc; ++c) {
-      const char* cname = L.config_name(c);
-      const int own = V.runs_at(c, sh);
-      for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
-        HIP_OK(hipMemset(call.c, 0xff, cn * 2));   // NaN pattern: unwritten outputs are caught
-        if (g_aux) HIP_OK(hipMemset(call.z, 0xff, cn * 2));
-        const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
-        const hipError_t e = hipDeviceSynchronize();
-        ++runs;
-        if (st != HGEMM_OK || e != hipSuccess) {
-          printf("FAIL %s %d_%d_%d %s s=%d: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
-          ++failures;
-          if (e != hipSuccess) return 3;
-          continue;
-        }
-        HIP_OK(hipMemcpy(got.data(), call.c, cn * 2, hipMemcpyDeviceToHost));
-        size_t bad = 0;
-        if (g_aux) {   // z_out = bf16(z), bit for bit
-          HIP_OK(hipMemcpy(got_z.data(), call.z, cn * 2, hipMemcpyDeviceToHost));
-          for (size_t i = 0; i < cn; ++i) bad += got_z[i] != bf16_rne((float)z[i]);
-        }
-        for (size_t i = 0; i < cn; ++i) {
-          if (g_act == HGEMM_ACT_RELU) {
-            bad += got[i] != (z[i] > 0 ? bf16_rne((float)z[i]) : (uint16_t)0);
-          } else {
-            const double y = act_fp64(z[i], g_act), c16 = bf16_value(got[i]);
-            const double bar = (y != 0 ? ldexp(1.0, (int)floor(log2(fabs(y))) - 8) : 0.0) + ldexp(fabs(z[i]), -19);
-            const double err = fabs(c16 - y);
-            if (!(err <= bar)) ++bad;   // (a NaN fails)
-            else if (bar > 0) worst = std::max(worst, err / bar);
-          }
-        }
-        if (bad) {
-          printf("FAIL %s %d_%d_%d %s s=%d%s: %zu/%zu elements %s\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
-                 (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn, g_act == HGEMM_ACT_RELU ? "differ from the exact result" : "outside the bar");
-          ++failures;
-        }
-      }
-      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
-    }
-    fflush(stdout);
-  }
-  printf("check-%s-configs:", lay);
-  for (int c = 0; c < nc; ++c) printf(" %s", L.config_name(c));
-  printf("\ncheck-%s-forms: 1 1|nt-store 2 5\n", lay);
-  if (g_act == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (bit-exact against where(z > 0, bf16(z), +0) of the exact z)\n", lay, runs, failures);
-  else printf("check %s: %d runs, %d failures (every element within 1/2 ulp_bf16(y*) + 2^-19 |z| of the fp64 activation of the exact z; worst %.3f of it)\n",
-              lay, runs, failures, worst);
-  return failures ? 1 : 0;
 }
 
 // the unfused second pass of the contender: an element-wise bf16 activation over all of C, hgemm_act.hpp's text on the value already
@@ -1651,22 +1819,17 @@ __global__ void act_bf16_kernel(__bf16* __restrict__ c, size_t total) {
 static void bench_tn_bias_act(TrBench& B) {
   const Shape sh = B.sh;
   const size_t cn = B.cn;
-  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = g_act;
-  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), btb = B.to_bf16(B.of(&Buffers::bt), B.b_elems), cb = B.alloc(cn * 2),
-                        bias = B.alloc((size_t)sh.N * 2);
-  for (void* p : bias) fill_bias_kernel<<<64, 256>>>((__bf16*)p, sh.N);
-  const int act_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = B.act, act_grid = elementwise_grid(cn);
+  const TnBiasBufs t = tn_bias_bufs(B);
+  const TrBench::PerSet ab = t.ab, btb = t.btb, cb = t.cb, bias = t.bias;
   B.add("act", [=](Buffers&, size_t i) { return bgemm_mi355x_tn_bias_act(ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, act, nullptr); });
   B.add("unfused", [=](Buffers&, size_t i) {
     const int st = bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
-    if (act == HGEMM_ACT_RELU) act_bf16_kernel<HGEMM_ACT_RELU><<<act_grid, 256>>>((__bf16*)cb[i], cn);
-    else if (act == HGEMM_ACT_GELU) act_bf16_kernel<HGEMM_ACT_GELU><<<act_grid, 256>>>((__bf16*)cb[i], cn);
-    else act_bf16_kernel<HGEMM_ACT_GELU_TANH><<<act_grid, 256>>>((__bf16*)cb[i], cn);
+    with_act(act, [&](auto A) { act_bf16_kernel<decltype(A)::value><<<act_grid, 256>>>((__bf16*)cb[i], cn); });
     return st;
   });
   B.add("bias", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
-  B.head("\"output\": \"c16_bias_act\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
-         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  head_act(B, "c16_bias_act");
   B.verdict("act_le_unfused", 0, 1, true);
 }
 
@@ -1681,236 +1844,75 @@ __global__ void act_from_z_kernel(__bf16* __restrict__ y, const __bf16* __restri
 static void bench_tn_aux(TrBench& B) {
   const Shape sh = B.sh;
   const size_t cn = B.cn;
-  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = g_act;
-  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), btb = B.to_bf16(B.of(&Buffers::bt), B.b_elems), cb = B.alloc(cn * 2),
-                        zb = B.alloc(cn * 2), bias = B.alloc((size_t)sh.N * 2);
-  for (void* p : bias) fill_bias_kernel<<<64, 256>>>((__bf16*)p, sh.N);
-  const int act_grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = B.act, act_grid = elementwise_grid(cn);
+  const TnBiasBufs t = tn_bias_bufs(B);
+  const TrBench::PerSet ab = t.ab, btb = t.btb, cb = t.cb, bias = t.bias, zb = B.alloc(cn * 2);
   B.add("aux", [=](Buffers&, size_t i) { return bgemm_mi355x_tn_bias_act_aux(ab[i], btb[i], bias[i], cb[i], zb[i], sh.M, sh.N, sh.K, act, nullptr); });
   B.add("unfused", [=](Buffers&, size_t i) {
     const int st = bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], zb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
-    if (act == HGEMM_ACT_RELU) act_from_z_kernel<HGEMM_ACT_RELU><<<act_grid, 256>>>((__bf16*)cb[i], (const __bf16*)zb[i], cn);
-    else if (act == HGEMM_ACT_GELU) act_from_z_kernel<HGEMM_ACT_GELU><<<act_grid, 256>>>((__bf16*)cb[i], (const __bf16*)zb[i], cn);
-    else act_from_z_kernel<HGEMM_ACT_GELU_TANH><<<act_grid, 256>>>((__bf16*)cb[i], (const __bf16*)zb[i], cn);
+    with_act(act, [&](auto A) { act_from_z_kernel<decltype(A)::value><<<act_grid, 256>>>((__bf16*)cb[i], (const __bf16*)zb[i], cn); });
     return st;
   });
   B.add("act", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn_bias_act(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, act, nullptr); });
-  B.head("\"output\": \"c16_bias_act_aux\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
-         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  head_act(B, "c16_bias_act_aux");
   B.verdict("aux_le_unfused", 0, 1, true);
 }
 
-// ---- --dact relu|gelu|gelu_tanh (with --layout nn --bf16): bgemm_mi355x_nn_dact, C = bf16(S x act'(float(z))) -----------------------------
-// The check's operands are integers in -2 .. 2 with A scaled by 2^-(floor(log2 K) - 2), so S is exact in fp32 in any order (verified per
-// element); Z is a seeded matrix of multiples of 1/32 in [-4, 4] (bf16 values; both signs, zeros, the range of a negative derivative).  The
-// bars: ReLU bit for bit against (z <= 0 ? +0 : bf16(S)); both GELUs |C - S g*| <= 1/2 ulp_bf16(S g*) + DACT_EPS |S|, g* in fp64.
-static double dact_fp64(double z, int act) {
-  if (act == HGEMM_ACT_RELU) return z <= 0 ? 0.0 : 1.0;
-  if (act == HGEMM_ACT_GELU) return 0.5 * erfc(-z / sqrt(2.0)) + z * exp(-0.5 * z * z) / sqrt(2.0 * M_PI);
-  const double c = sqrt(2.0 / M_PI), s = 1.0 / (1.0 + exp(-2.0 * c * (z + 0.044715 * z * z * z)));
-  return s + z * s * (1.0 - s) * 2.0 * c * (1.0 + 3.0 * 0.044715 * z * z);
+// What the two nn --bf16 --dact benches share: each set's bf16 A and B, a C, a Z filled with a fixed pattern over [-4, 4] (timing only).
+__global__ void fill_z_kernel(__bf16* __restrict__ z, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    z[i] = (__bf16)((float)((int)((i * 2654435761u) % 257u) - 128) * (1.0f / 32.0f));
 }
-static int launch_dact(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
-  if (g_dbias)
-    return bgemm_mi355x_launch_nn_dact_dbias(cfg, splits, o.a, o.b, o.z, o.c, o.db32, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, g_dact, o.accumulate, nullptr);
-  return bgemm_mi355x_launch_nn_dact(cfg, splits, o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, g_dact, nullptr);
-}
-static int planned_dact(const TrCall& o, const Shape& sh) {
-  if (g_dbias) return bgemm_mi355x_nn_dact_dbias(o.a, o.b, o.z, o.c, o.db32, sh.M, sh.N, sh.K, g_dact, o.accumulate, nullptr);
-  return bgemm_mi355x_nn_dact(o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, g_dact, nullptr);
-}
-static int dact_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) {
-  return g_dbias ? bgemm_mi355x_nn_dact_dbias_runs(cfg, M, N, K, lda, ldb, ldc, N) : bgemm_mi355x_nn_dact_runs(cfg, M, N, K, lda, ldb, ldc, N);
-}
-static void bench_nn_dact(TrBench&);
-static const BenchDesc kBenchNNDact = {91, warm_none, bench_nn_dact};
-static const Variant kVariantNNDact = {&kLayoutNN, kBF16, kC16, dact_runs, launch_dact, planned_dact, &kBenchNNDact};
-
-constexpr int DBIAS_GUARD = 8;               // floats behind db32[N - 1] that must keep DBIAS_SENTINEL
-constexpr float DBIAS_SENTINEL = -12345.625f;
-static int dact_check(std::vector<Shape> shapes) {
-  const Variant& V = kVariantNNDact;
-  const TrLayout& L = *V.L;
-  if (shapes.empty()) shapes = parse_shapes(L.check_shapes);
-  const std::string lay_s = V.words("", "-") + "-dact-" + kActNames[g_dact] + (g_dbias ? "-dbias" : "");
-  const char* lay = lay_s.c_str();
-  const int nc = L.num_configs();
-  int failures = 0, runs = 0;
-  double worst = 0.0, worst_db = 0.0;
-  for (const Shape& sh : shapes) {
-    const size_t cn = (size_t)sh.M * sh.N;
-    int j = 0;
-    while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
-    const double scale = ldexp(1.0, -std::max(j - 2, 0));
-    uint64_t lcg = 0x9E3779B97F4A7C15ull + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
-    auto next = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(lcg >> 33); };
-    std::vector<int8_t> ai((size_t)sh.M * sh.K), bi((size_t)sh.K * sh.N);
-    for (auto& v : ai) v = (int8_t)((int)(next() % 5) - 2);
-    for (auto& v : bi) v = (int8_t)((int)(next() % 5) - 2);
-    std::vector<uint16_t> a_h(ai.size()), b_h(bi.size()), z_h(cn), got(cn);
-    for (size_t i = 0; i < ai.size(); ++i) a_h[i] = bf16_rne((float)(ai[i] * scale));
-    for (size_t i = 0; i < bi.size(); ++i) b_h[i] = bf16_rne((float)bi[i]);
-    std::vector<double> z(cn), s(cn);
-    for (size_t i = 0; i < cn; ++i) {
-      z[i] = (double)((int)(next() % 257) - 128) / 32.0;   // |q| <= 128: at most 8 significant bits, a bf16 value
-      z_h[i] = (i % 29 == 7) ? (uint16_t)0x8000 : bf16_rne((float)z[i]);   // some -0
-      if (i % 29 == 7) z[i] = 0.0;
-    }
-    for (int m = 0; m < sh.M; ++m)
-      for (int n = 0; n < sh.N; ++n) {
-        int acc = 0;
-        for (int k = 0; k < sh.K; ++k) acc += ai[(size_t)m * sh.K + k] * bi[(size_t)k * sh.N + n];
-        const double ss = acc * scale;
-        if ((double)(float)ss != ss) { fprintf(stderr, "check %s: S is not exact in fp32 at %d_%d_%d\n", lay, sh.M, sh.N, sh.K); return 2; }
-        s[(size_t)m * sh.N + n] = ss;
-      }
-    DevBufs dev;
-    TrCall call = {dev.upload(a_h.data(), a_h.size() * 2), dev.upload(b_h.data(), b_h.size() * 2), nullptr, dev.alloc(cn * 2), 0};
-    call.z = dev.upload(z_h.data(), cn * 2);
-    // --dbias: db32 of N floats from a NaN prefill with DBIAS_GUARD sentinels behind it, and a second C for the dact call at the same plan
-    std::vector<float> db_fill(sh.N + DBIAS_GUARD, std::nanf("")), db_got(sh.N + DBIAS_GUARD), db_old(sh.N + DBIAS_GUARD), db_acc(sh.N + DBIAS_GUARD);
-    std::vector<uint16_t> dact_c(g_dbias ? cn : 0);
-    void* c_dact = g_dbias ? dev.alloc(cn * 2) : nullptr;
-    for (int n = 0; n < DBIAS_GUARD; ++n) db_fill[sh.N + n] = DBIAS_SENTINEL;
-    db_old = db_fill;
-    for (int n = 0; n < sh.N; ++n) db_old[n] = (float)((n * 37) % 129 - 64) * 0.3f;
-    if (g_dbias) call.db32 = (float*)dev.alloc(db_fill.size() * 4);
-    for (int c = 0; c < nc; ++c) {
-      const char* cname = L.config_name(c);
-      const int own = V.runs_at(c, sh);
-      for (int splits : {1, 1 | HGEMM_PLAN_NT_STORE, 2, 5}) {
-        HIP_OK(hipMemset(call.c, 0xff, cn * 2));   // NaN pattern: unwritten outputs are caught
-        if (g_dbias) HIP_OK(hipMemcpy(call.db32, db_fill.data(), db_fill.size() * 4, hipMemcpyHostToDevice));
-        const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
-        const hipError_t e = hipDeviceSynchronize();
-        ++runs;
-        if (st != HGEMM_OK || e != hipSuccess) {
-          printf("FAIL %s %d_%d_%d %s s=%d: status %d hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, st, (int)e);
-          ++failures;
-          if (e != hipSuccess) return 3;
-          continue;
-        }
-        HIP_OK(hipMemcpy(got.data(), call.c, cn * 2, hipMemcpyDeviceToHost));
-        size_t bad = 0;
-        for (size_t i = 0; i < cn; ++i) {
-          if (g_dact == HGEMM_ACT_RELU) {
-            bad += got[i] != (z[i] <= 0 ? (uint16_t)0 : bf16_rne((float)s[i]));
-          } else {
-            const double y = s[i] * dact_fp64(z[i], g_dact), c16 = bf16_value(got[i]);
-            const double bar = (y != 0 ? ldexp(1.0, (int)floor(log2(fabs(y))) - 8) : 0.0) + (double)hgemm_mi355x::DACT_EPS * fabs(s[i]);
-            const double err = fabs(c16 - y);
-            if (!(err <= bar)) ++bad;   // (a NaN fails)
-            else if (bar > 0) worst = std::max(worst, err / bar);
-          }
-        }
-        if (bad) {
-          printf("FAIL %s %d_%d_%d %s s=%d%s: %zu/%zu elements %s\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK,
-                 (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad, cn, g_dact == HGEMM_ACT_RELU ? "differ from the exact result" : "outside the bar");
-          ++failures;
-        }
-        if (!g_dbias) continue;
-        // C is the dact call's bit for bit; db32 is the column sum of the C read back, taken in fp64 -- ReLU: every C is a multiple of `scale`
-        // and every column sum exact in fp32 in any order (verified), so bit for bit; the GELUs: inside gamma_(M-1) sum |C|, the bound of an
-        // M-term fp32 sum in any order (hgemm_dbias.hpp) --; nothing behind db32[N - 1] is written; accumulate = 1 is fl32(old + s)
-        HIP_OK(hipMemcpy(db_got.data(), call.db32, db_got.size() * 4, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemset(c_dact, 0xff, cn * 2));
-        const int st_d = bgemm_mi355x_launch_nn_dact(c, splits, call.a, call.b, call.z, c_dact, sh.M, sh.N, sh.K, L.lda(sh), L.ldb(sh), sh.N, sh.N, g_dact, nullptr);
-        HIP_OK(hipMemcpy(call.db32, db_old.data(), db_old.size() * 4, hipMemcpyHostToDevice));
-        call.accumulate = 1;
-        const int st_a = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
-        call.accumulate = 0;
-        const hipError_t e_d = hipDeviceSynchronize();
-        if (e_d != hipSuccess) { printf("FAIL %s %d_%d_%d %s s=%d: hip %d\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, (int)e_d); return 3; }
-        HIP_OK(hipMemcpy(dact_c.data(), c_dact, cn * 2, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(db_acc.data(), call.db32, db_acc.size() * 4, hipMemcpyDeviceToHost));
-        size_t c_differs = 0, db_bad = 0, acc_bad = 0, guard_bad = 0;
-        for (size_t i = 0; i < cn; ++i) c_differs += got[i] != dact_c[i];
-        for (int n = 0; n < DBIAS_GUARD; ++n) guard_bad += (db_got[sh.N + n] != DBIAS_SENTINEL) + (db_acc[sh.N + n] != DBIAS_SENTINEL);
-        for (int n = 0; n < sh.N; ++n) {
-          double sum = 0.0, mag = 0.0;
-          for (int m = 0; m < sh.M; ++m) { const double v = bf16_value(got[(size_t)m * sh.N + n]); sum += v; mag += fabs(v); }
-          if (g_dact == HGEMM_ACT_RELU) {
-            if ((double)(float)sum != sum) { fprintf(stderr, "check %s: a column sum is not exact in fp32 at %d_%d_%d\n", lay, sh.M, sh.N, sh.K); return 2; }
-            const float want = (float)sum;
-            db_bad += memcmp(&want, &db_got[n], 4) != 0;
-          } else {
-            const double bar = hgemm_mi355x::colsum_gamma(sh.M) * mag, err = fabs((double)db_got[n] - sum);
-            if (!(err <= bar)) ++db_bad;   // (a NaN fails)
-            else if (bar > 0) worst_db = std::max(worst_db, err / bar);
-          }
-          const float want_acc = db_old[n] + db_got[n];
-          acc_bad += memcmp(&want_acc, &db_acc[n], 4) != 0;
-        }
-        if (st_d != HGEMM_OK || st_a != HGEMM_OK || c_differs || db_bad || acc_bad || guard_bad) {
-          printf("FAIL %s %d_%d_%d %s s=%d%s: status %d %d, %zu/%zu elements of C differ from the dact call's, %zu/%d columns of db32 %s, %zu not fl32(old + s), "
-                 "%zu guard floats written\n", lay, sh.M, sh.N, sh.K, cname, splits & HGEMM_SPLITK_MASK, (splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", st_d, st_a,
-                 c_differs, cn, db_bad, sh.N, g_dact == HGEMM_ACT_RELU ? "differ from the exact sum" : "outside the bar", acc_bad, guard_bad);
-          ++failures;
-        }
-      }
-      if (c == 0) printf("checked %s %d_%d_%d (%s)\n", lay, sh.M, sh.N, sh.K, own ? L.kernels : "outside their scope: the reference kernel");
-    }
-    fflush(stdout);
-  }
-  if (g_dbias && g_dact == HGEMM_ACT_RELU) printf("check-%s-db32: bit-exact against the fp64 column sum of the C read back; C the dact call's bit for bit\n", lay);
-  else if (g_dbias) printf("check-%s-db32: every column within gamma_(M-1) sum |C| of the fp64 column sum of the C read back (worst %.3f of it); "
-                           "C the dact call's bit for bit\n", lay, worst_db);
-  if (g_dact == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (bit-exact against where(z <= 0, +0, bf16(S)) of the exact S)\n", lay, runs, failures);
-  else printf("check %s: %d runs, %d failures (every element within 1/2 ulp_bf16(S g*) + 2^-19 |S| of the fp64 product; worst %.3f of it)\n", lay, runs,
-              failures, worst);
-  return failures ? 1 : 0;
+struct NnDactBufs { TrBench::PerSet ab, bb, cb, zb; };
+static NnDactBufs nn_dact_bufs(TrBench& B) {
+  const NnDactBufs t = {B.to_bf16(B.of(&Buffers::a), B.a_elems), B.to_bf16(B.of(&Buffers::b), B.b_elems), B.alloc(B.cn * 2), B.alloc(B.cn * 2)};
+  for (void* p : t.zb) fill_z_kernel<<<elementwise_grid(B.cn), 256>>>((__bf16*)p, B.cn);
+  return t;
 }
 
 // nn --bf16 --dact A: the planned bgemm_mi355x_nn_dact call against the sequence it replaces -- bgemm_mi355x_launch_nn with the same member
 // and splits writing a bf16 dH, then an element-wise kernel that reads dH and Z and writes dZ = dH (.) act'(Z) (6 M N bytes) --, and,
 // context only, the plain NN call.  "dact_le_unfused", within the unfused path's own spread.
-__global__ void fill_z_kernel(__bf16* __restrict__ z, size_t total) {   // a fixed pattern over [-4, 4]: timing only
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
-    z[i] = (__bf16)((float)((int)((i * 2654435761u) % 257u) - 128) * (1.0f / 32.0f));
-}
 template <int ACT>
 __global__ void dact_elementwise_kernel(__bf16* __restrict__ dz, const __bf16* __restrict__ dh, const __bf16* __restrict__ z, size_t total) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
     dz[i] = (__bf16)hgemm_mi355x::dact_mul<ACT>((float)dh[i], (float)z[i]);
 }
-// nn --bf16 --dact A --dbias: bgemm_mi355x_launch_nn_dact_dbias at the plan against the sequence it replaces -- bgemm_mi355x_launch_nn_dact with
-// the same member and splits, then bgemm_mi355x_colsum_c32 over the dZ just written (one more launch, 2 M N more bytes read) --, and,
-// context only, the dact call alone.  "dbias_le_unfused", within the unfused path's own spread.
 static void bench_nn_dact(TrBench& B) {
   const Shape sh = B.sh;
   const size_t cn = B.cn;
-  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = g_dact;
-  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), bb = B.to_bf16(B.of(&Buffers::b), B.b_elems), cb = B.alloc(cn * 2),
-                        hb = B.alloc(cn * 2), zb = B.alloc(cn * 2);
-  const int grid = (int)std::min<size_t>((cn + 255) / 256, 8192);
-  for (void* p : zb) fill_z_kernel<<<grid, 256>>>((__bf16*)p, cn);
-  if (g_dbias) {
-    const TrBench::PerSet db = B.alloc((size_t)sh.N * 4, true);
-    B.add("dbias", [=](Buffers&, size_t i) {
-      return bgemm_mi355x_launch_nn_dact_dbias(cfg, splits, ab[i], bb[i], zb[i], cb[i], (float*)db[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, 0, nullptr);
-    });
-    B.add("unfused", [=](Buffers&, size_t i) {
-      const int st = bgemm_mi355x_launch_nn_dact(cfg, splits, ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, nullptr);
-      return st != HGEMM_OK ? st : bgemm_mi355x_colsum_c32(cb[i], (float*)db[i], sh.M, sh.N, sh.N, 0, nullptr);
-    });
-    B.add("dact", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn_dact(cfg, splits, ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, nullptr); });
-    B.head("\"output\": \"c16_dact_dbias\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
-           B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
-    B.verdict("dbias_le_unfused", 0, 1, true);
-    return;
-  }
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = B.act, grid = elementwise_grid(cn);
+  const NnDactBufs t = nn_dact_bufs(B);
+  const TrBench::PerSet ab = t.ab, bb = t.bb, cb = t.cb, zb = t.zb, hb = B.alloc(cn * 2);
   B.add("dact", [=](Buffers&, size_t i) { return bgemm_mi355x_nn_dact(ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, act, nullptr); });
   B.add("unfused", [=](Buffers&, size_t i) {
     const int st = bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], hb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
-    if (act == HGEMM_ACT_RELU) dact_elementwise_kernel<HGEMM_ACT_RELU><<<grid, 256>>>((__bf16*)cb[i], (const __bf16*)hb[i], (const __bf16*)zb[i], cn);
-    else if (act == HGEMM_ACT_GELU) dact_elementwise_kernel<HGEMM_ACT_GELU><<<grid, 256>>>((__bf16*)cb[i], (const __bf16*)hb[i], (const __bf16*)zb[i], cn);
-    else dact_elementwise_kernel<HGEMM_ACT_GELU_TANH><<<grid, 256>>>((__bf16*)cb[i], (const __bf16*)hb[i], (const __bf16*)zb[i], cn);
+    with_act(act, [&](auto A) { dact_elementwise_kernel<decltype(A)::value><<<grid, 256>>>((__bf16*)cb[i], (const __bf16*)hb[i], (const __bf16*)zb[i], cn); });
     return st;
   });
   B.add("nn", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], hb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
-  B.head("\"output\": \"c16_dact\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
-         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  head_act(B, "c16_dact");
   B.verdict("dact_le_unfused", 0, 1, true);
+}
+
+// nn --bf16 --dact A --dbias: bgemm_mi355x_launch_nn_dact_dbias at the plan against the sequence it replaces -- bgemm_mi355x_launch_nn_dact with
+// the same member and splits, then bgemm_mi355x_colsum_c32 over the dZ just written (one more launch, 2 M N more bytes read) --, and,
+// context only, the dact call alone.  "dbias_le_unfused", within the unfused path's own spread.
+static void bench_nn_dact_dbias(TrBench& B) {
+  const Shape sh = B.sh;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = B.act;
+  const NnDactBufs t = nn_dact_bufs(B);
+  const TrBench::PerSet ab = t.ab, bb = t.bb, cb = t.cb, zb = t.zb, db = B.alloc((size_t)sh.N * 4, true);
+  B.add("dbias", [=](Buffers&, size_t i) {
+    return bgemm_mi355x_launch_nn_dact_dbias(cfg, splits, ab[i], bb[i], zb[i], cb[i], (float*)db[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, 0, nullptr);
+  });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_nn_dact(cfg, splits, ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, nullptr);
+    return st != HGEMM_OK ? st : bgemm_mi355x_colsum_c32(cb[i], (float*)db[i], sh.M, sh.N, sh.N, 0, nullptr);
+  });
+  B.add("dact", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn_dact(cfg, splits, ab[i], bb[i], zb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, nullptr); });
+  head_act(B, "c16_dact_dbias");
+  B.verdict("dbias_le_unfused", 0, 1, true);
 }
 
 int main(int argc, char** argv) {
@@ -1918,13 +1920,14 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
     return 2;
   }
-  std::string mode = argv[1], layout;
+  std::string mode = argv[1];
+  TrFlags tr;   // --layout, --bf16, --c32, --bias, --act, --aux, --dact, --dbias
   std::vector<Shape> shapes;
   const char* out_path = nullptr;
   const char* cfg_name = nullptr;
   double keep = 2.5;
   int max_cand = 12, splits = 1, group = 0, reps = 20;
-  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false, c32 = false, bf16 = false, bias = false;
+  bool baselines = false, use_lib = false, sweep_group = false, autotune = false, isolated = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -1933,23 +1936,19 @@ int main(int argc, char** argv) {
     else if (a == "--out") out_path = next();
     else if (a == "--autotune") autotune = true;
     else if (a == "--layout") {
-      layout = next();
-      if (layout != "nn" && layout != "tn" && layout != "ta") { fprintf(stderr, "--layout takes nn, ta or tn\n"); return 2; }
+      tr.layout = next();
+      if (tr.layout != "nn" && tr.layout != "tn" && tr.layout != "ta") { fprintf(stderr, "--layout takes nn, ta or tn\n"); return 2; }
     }
-    else if (a == "--c32") c32 = true;
-    else if (a == "--bf16") bf16 = true;
-    else if (a == "--bias") bias = true;
-    else if (a == "--aux") g_aux = true;
-    else if (a == "--dact") {
+    else if (a == "--c32") tr.c32 = true;
+    else if (a == "--bf16") tr.bf16 = true;
+    else if (a == "--bias") tr.bias = true;
+    else if (a == "--aux") tr.aux = true;
+    else if (a == "--dbias") tr.dbias = true;
+    else if (a == "--act" || a == "--dact") {
+      int& which = a == "--act" ? tr.act : tr.dact;
       const std::string nm = next();
-      for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) g_dact = k;
-      if (!g_dact) { fprintf(stderr, "--dact takes relu, gelu or gelu_tanh\n"); return 2; }
-    }
-    else if (a == "--dbias") g_dbias = true;
-    else if (a == "--act") {
-      const std::string nm = next();
-      for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) g_act = k;
-      if (!g_act) { fprintf(stderr, "--act takes relu, gelu or gelu_tanh\n"); return 2; }
+      for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) which = k;
+      if (!which) { fprintf(stderr, "%s takes relu, gelu or gelu_tanh\n", a.c_str()); return 2; }
     }
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
@@ -2000,16 +1999,16 @@ int main(int argc, char** argv) {
   }
   // Which of the transposed-read variants, if any, the flags name -- and every refusal that follows from the flags alone, before a
   // device is asked for.  nullptr: the fp16 b_col_major commands below (no --layout, or --layout tn without --bf16).
-  if (bias && !(bf16 && layout == "tn")) { fprintf(stderr, "--bias goes with --layout tn --bf16 (bgemm_mi355x_tn_bias)\n"); return 2; }
-  if (g_act && !bias) { fprintf(stderr, "--act goes with --layout tn --bf16 --bias (bgemm_mi355x_tn_bias_act)\n"); return 2; }
-  if (c32 && layout != "ta") { fprintf(stderr, "--c32 goes with --layout ta\n"); return 2; }
-  if (bf16 && layout.empty()) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
-  if (g_aux && !g_act) { fprintf(stderr, "--aux goes with --layout tn --bf16 --bias --act A (bgemm_mi355x_tn_bias_act_aux)\n"); return 2; }
-  if (g_dact && !(bf16 && layout == "nn" && !g_act)) { fprintf(stderr, "--dact goes with --layout nn --bf16 (bgemm_mi355x_nn_dact)\n"); return 2; }
-  if (g_dbias && !g_dact) { fprintf(stderr, "--dbias goes with --layout nn --bf16 --dact A (bgemm_mi355x_nn_dact_dbias)\n"); return 2; }
-  const Variant* variant = g_dact ? &kVariantNNDact : g_aux ? &kVariantTNAux : g_act ? &kVariantTNBiasAct : resolve_variant(layout, bf16, c32, bias);
+  if (tr.bias && !(tr.bf16 && tr.layout == "tn")) { fprintf(stderr, "--bias goes with --layout tn --bf16 (bgemm_mi355x_tn_bias)\n"); return 2; }
+  if (tr.act && !tr.bias) { fprintf(stderr, "--act goes with --layout tn --bf16 --bias (bgemm_mi355x_tn_bias_act)\n"); return 2; }
+  if (tr.c32 && tr.layout != "ta") { fprintf(stderr, "--c32 goes with --layout ta\n"); return 2; }
+  if (tr.bf16 && tr.layout.empty()) { fprintf(stderr, "--bf16 goes with --layout nn, ta or tn (the fp16 b_col_major families have no bf16 form)\n"); return 2; }
+  if (tr.aux && !tr.act) { fprintf(stderr, "--aux goes with --layout tn --bf16 --bias --act A (bgemm_mi355x_tn_bias_act_aux)\n"); return 2; }
+  if (tr.dact && !(tr.bf16 && tr.layout == "nn" && !tr.act)) { fprintf(stderr, "--dact goes with --layout nn --bf16 (bgemm_mi355x_nn_dact)\n"); return 2; }
+  if (tr.dbias && !tr.dact) { fprintf(stderr, "--dbias goes with --layout nn --bf16 --dact A (bgemm_mi355x_nn_dact_dbias)\n"); return 2; }
+  const Variant* variant = resolve_variant(tr);
   if (variant && mode != "check" && mode != "bench") {
-    fprintf(stderr, "--layout %s%s goes with check or bench\n", layout.c_str(), variant->L->b_col_major ? " --bf16" : "");
+    fprintf(stderr, "--layout %s%s goes with check or bench\n", tr.layout.c_str(), variant->L->b_col_major ? " --bf16" : "");
     return 2;
   }
   if (variant && mode == "bench" && shapes.empty()) { fprintf(stderr, "bench needs --shape\n"); return 2; }
@@ -2023,7 +2022,7 @@ int main(int argc, char** argv) {
     HIP_OK(hipMalloc(&pad, g_pad_alloc_mib << 20));   // (kept until exit)
     HIP_OK(hipMemset(pad, 1, g_pad_alloc_mib << 20));
   }
-  if (variant) return mode != "check" ? tr_bench(*variant, shapes, out_path, autotune) : g_dact ? dact_check(shapes) : g_act ? act_check(shapes) : tr_check(*variant, shapes);
+  if (variant) return mode == "check" ? tr_check(*variant, tr.activation(), shapes) : tr_bench(*variant, tr.activation(), shapes, out_path, autotune);
   if (mode == "check") {
     if (shapes.empty())
       // (the last two: K tails -- 2104 = 32 x 64 + 56 = 8 x 256 + 56, 728 = 11 x 64 + 24 = 5 x 128 + 88 = 2 x 256 + 216: odd and even

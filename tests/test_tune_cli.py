@@ -1,4 +1,5 @@
-"""CPU tests of hgemm_tune's command line for the transposed-read variants (--layout nn|ta|tn with --bf16, --c32, --bias): which
+"""CPU tests of hgemm_tune's command line for the transposed-read variants (--layout nn|ta|tn with --bf16, --c32, --bias, --act A,
+--aux, --dact A, --dbias): which
 variant the flags resolve to is decided before a device is asked for, so every refusal -- its exact stderr line, exit status 2 -- shows
 on a machine without a GPU, where a command line the tool accepts ends with "no HIP device visible" and status 3 instead."""
 import subprocess
@@ -20,9 +21,18 @@ REFUSED = [
     ("bench --layout nn", NO_SHAPE),
     ("bench --layout ta --c32", NO_SHAPE),
     ("bench --layout tn --bf16 --bias", NO_SHAPE),
+    ("check --layout tn --bf16 --act relu", "--act goes with --layout tn --bf16 --bias (bgemm_mi355x_tn_bias_act)"),
+    ("check --layout tn --bf16 --bias --aux", "--aux goes with --layout tn --bf16 --bias --act A (bgemm_mi355x_tn_bias_act_aux)"),
+    ("check --layout ta --bf16 --dact gelu", "--dact goes with --layout nn --bf16 (bgemm_mi355x_nn_dact)"),
+    ("check --layout nn --bf16 --dbias", "--dbias goes with --layout nn --bf16 --dact A (bgemm_mi355x_nn_dact_dbias)"),
+    ("bench --layout nn --bf16 --dact relu", NO_SHAPE),
 ]
+ACTS = ("relu", "gelu", "gelu_tanh")
+# the activation kinds: four call kinds, the activation a value of the call
+ACT_VARIANTS = [flags.format(a) for flags in ("--layout tn --bf16 --bias --act {}", "--layout tn --bf16 --bias --act {} --aux",
+                                              "--layout nn --bf16 --dact {}", "--layout nn --bf16 --dact {} --dbias") for a in ACTS]
 VARIANTS = ["--layout nn", "--layout ta", "--layout ta --c32", "--layout nn --bf16", "--layout ta --bf16", "--layout ta --c32 --bf16",
-            "--layout tn --bf16", "--layout tn --bf16 --bias"]
+            "--layout tn --bf16", "--layout tn --bf16 --bias", *ACT_VARIANTS]
 
 
 @pytest.fixture(scope="module")
