@@ -14,6 +14,10 @@
 //                       where z^3 overflows, gives u = -inf, exp = +inf and y = -0; a large positive z gives exp = 0 and y = z.
 //   Both GELUs: NaN gives NaN, +inf gives +inf, -inf gives NaN (0 x inf and inf / inf, as the formulas have it: no select is spent),
 //   +-0 gives a zero.
+//   HGEMM_ACT_SILU      y = z / (1 + exp(-z)), the gated calls only (bgemm_mi355x_tn_gated; every other call refuses the id).  NaN gives NaN,
+//                       +inf gives +inf (exp = 0), -inf gives NaN (inf / inf), a large negative finite z gives exp = +inf and y = -0, +-0
+//                       gives a zero of its sign.  expf within 1 ulp, one add and one correctly rounded division: within 4 x 2^-24 |y| of
+//                       the exact value, so within 2^-22 |z| (|silu(z)| <= |z|).
 #pragma once
 
 #include <math.h>
@@ -32,22 +36,24 @@
 namespace hgemm_mi355x {
 
 // the public constants' values (include/hgemm_mi355x.h: HGEMM_ACT_RELU / _GELU / _GELU_TANH)
-constexpr int ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_GELU_TANH = 3;
+constexpr int ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_GELU_TANH = 3, ACT_SILU = 4;
 
 template <int ACT>
 HGEMM_ACT_HD float act_apply(float z) {
   HGEMM_ACT_NO_CONTRACT
-  static_assert(ACT == ACT_RELU || ACT == ACT_GELU || ACT == ACT_GELU_TANH, "relu, gelu (erf), gelu (tanh)");
+  static_assert(ACT == ACT_RELU || ACT == ACT_GELU || ACT == ACT_GELU_TANH || ACT == ACT_SILU, "relu, gelu (erf), gelu (tanh), silu");
   if (ACT == ACT_RELU) {
     return (z > 0.0f || z != z) ? z : 0.0f;
   } else if (ACT == ACT_GELU) {
     const float t = 1.0f + erff(z * 0.70710678118654752440f);   // in [0, 2]
     return (0.5f * z) * t;
-  } else {
+  } else if (ACT == ACT_GELU_TANH) {
     const float z3 = (z * z) * z;
     const float inner = fmaf(0.044715f, z3, z);                  // z + 0.044715 z^3
     const float e = expf(-1.5957691216057307117f * inner);       // exp(-2u), -2 sqrt(2 / pi)
     return z / (1.0f + e);
+  } else {
+    return z / (1.0f + expf(-z));
   }
 }
 

@@ -490,6 +490,9 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // dbias (bgemm_mi355x_nn_dact_dbias, with dact only): the dact call and db32[n] (+)= sum over m of float(C[m][n]), the kinds
 // TR_C16_DACT_DBIAS + act.  tr_resolve builds the dact call's plan and adds the column sum to it (see there); db_acc is the call's
 // `accumulate`, which is db32's and not C's.
+// gated (bgemm_mi355x_tn_gated, family f only): C = T(act(sum_g + bias_g[n]) x (sum_u + bias_u[n])) over two weights of N rows each, the kinds
+// TR_C16_GATED + act (HGEMM_ACT_SILU included) and the ids EPI_C16_GATED + act.  N is the OUTPUT width; tiles, cuts, slabs and workspace are
+// those of the plain product of width 2 N (a member's tile is BM x BN / 2 outputs; hgemm_gated.hpp has the slab).  Either bias may be null.
 struct TrOut {
   bool c32, accumulate;
   bool bias = false;
@@ -497,13 +500,14 @@ struct TrOut {
   bool aux = false, dact = false;
   int ldz = 0;   // the row stride of z_out (aux) / z (dact); no part of the kind
   bool dbias = false, db_acc = false;
+  bool gated = false;
   int elem_bytes() const { return c32 ? 4 : 2; }
   bool has_z() const { return aux || dact; }
-  bool has_epi() const { return bias || dact; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
+  bool has_epi() const { return bias || dact || gated; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
   TrKind kind() const {   // the kernel set's cell in TrRow / TrTable
-    return dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
+    return gated ? (TrKind)(TR_C16_GATED + act) : dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
   }
-  int epi_bias() const { return (dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
+  int epi_bias() const { return (gated ? EPI_C16_GATED : dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
 };
 constexpr TrOut kOutC16{false, false};
 constexpr TrOut kOutC16Bias{false, false, true};
@@ -512,6 +516,10 @@ static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIA
               TR_C16_DACT == TR_C16_BIAS_AUX + ACT_GELU_TANH && TR_C16_DACT_DBIAS == TR_C16_DACT + ACT_GELU_TANH && TR_C16_DACT_DBIAS + ACT_GELU_TANH + 1 == TR_KINDS,
               "a kind per activation, four times");
 constexpr bool act_known(int act) { return act == HGEMM_ACT_RELU || act == HGEMM_ACT_GELU || act == HGEMM_ACT_GELU_TANH; }
+static_assert(HGEMM_ACT_SILU == ACT_SILU && TR_C16_GATED + 1 == TR_KINDS && TR_C16_GATED + ACT_SILU + 1 == TR_KINDS_ALL && !act_known(HGEMM_ACT_SILU),
+              "the gated kinds follow; SiLU is theirs alone");
+constexpr bool act_known_gated(int act) { return act_known(act) || act == HGEMM_ACT_SILU; }
+constexpr TrOut out_gated(int act) { return TrOut{false, false, false, act, false, false, 0, false, false, true}; }   // (act_known_gated(act) checked by the caller)
 constexpr TrOut out_bias_act(int act) { return TrOut{false, false, true, act}; }   // (act_known(act) checked by the caller)
 constexpr TrOut out_bias_act_aux(int act, int ldz) { return TrOut{false, false, true, act, true, false, ldz}; }
 constexpr TrOut out_dact(int act, int ldz) { return TrOut{false, false, false, act, false, true, ldz}; }
@@ -548,7 +556,8 @@ struct TrLayout {
   // from a tile's first row
   bool reach_ok(TrOut out, const TrEntry& e, int M, int N, int K, int lda, int ldb, int ldc) const {
     const double a_bytes = a_col_major ? (double)(K - 1) * lda * 2.0 + M * 2.0 : (double)e.bm * lda * 2.0 + K * 2.0;
-    const double b_bytes = b_col_major ? (double)e.bn * ldb * 2.0 + K * 2.0 : (double)(K - 1) * ldb * 2.0 + N * 2.0;
+    // (a gated tile holds BN / 2 rows of each weight)
+    const double b_bytes = b_col_major ? (double)(out.gated ? e.bn / 2 : e.bn) * ldb * 2.0 + K * 2.0 : (double)(K - 1) * ldb * 2.0 + N * 2.0;
     const double c_bytes = ((double)e.bm * ldc + N) * out.elem_bytes();
     return a_bytes < 2147483648.0 && b_bytes < 2147483648.0 && c_bytes < 2147483648.0;
   }
@@ -573,7 +582,8 @@ LaunchPlan tr_resolve_gemm(const TrLayout& L, TrElem elem, TrOut out, int config
   };
   // rows must not overlap: lda >= K (n, f) / >= M, the row stride of a_col_major (a); ldb >= N (n, a: B is row-major) / >= K, the row
   // stride of b_col_major (f); ldc >= N
-  if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < L.b_row(N, K) || ldc < N || (out.has_z() && out.ldz < N)) {
+  if (config < 0 || config >= L.t.count || lda < L.a_row(M, K) || ldb < L.b_row(N, K) || ldc < N || (out.has_z() && out.ldz < N) ||
+      (out.gated && N >= (1 << 30))) {   // (2 N is an int)
     p.status = HGEMM_ERR_BAD_ARG;
     return p;
   }
@@ -585,7 +595,9 @@ LaunchPlan tr_resolve_gemm(const TrLayout& L, TrElem elem, TrOut out, int config
   g.k_chunk = K; g.splits = g.tiles_m = g.tiles_n = g.group_m = g.items = 1;
   g.flags = ((splits_arg & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0) | (out.accumulate ? ARG_ACCUMULATE : 0);
   g.sk = StreamK{1, 0, 0, 1, FastDiv{0u, 0u, 0u}};
-  const long tiles = (long)((M + e.bm - 1) / e.bm) * ((N + e.bn - 1) / e.bn);
+  // out.gated: g.N stays the OUTPUT width (what the kernels clamp and predicate with); the tiles and the slabs are the product's, 2 N wide
+  const int NP = out.gated ? 2 * N : N;
+  const long tiles = (long)((M + e.bm - 1) / e.bm) * ((NP + e.bn - 1) / e.bn);
   const bool z_ok = !out.has_z() || ((out.ldz & 7) == 0 && ((double)e.bm * out.ldz + N) * 2.0 < 2147483648.0);   // z / z_out: C's rules
   if (!aligned || !z_ok || !L.path_ok(out, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc) || !L.reach_ok(out, e, M, N, K, lda, ldb, ldc) ||
       tiles > 0x7fffffffL) {
@@ -593,7 +605,7 @@ LaunchPlan tr_resolve_gemm(const TrLayout& L, TrElem elem, TrOut out, int config
     add(THUNK_GENERIC, g, 0, epi_out);
     return p;
   }
-  g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (N + e.bn - 1) / e.bn;
+  g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (NP + e.bn - 1) / e.bn;
   g.group_m = std::min(g.tiles_m, 8);
   // at most one split per stage, no empty split (the arithmetic of split_k); the single-launch and stream-K words have no kernel
   // here: their split count runs as the two-pass form / the plain launch
@@ -606,7 +618,7 @@ LaunchPlan tr_resolve_gemm(const TrLayout& L, TrElem elem, TrOut out, int config
   set_raster_div(g);
   if (splits > 1) {
     p.form = FORM_SPLITK;
-    p.slab_bytes = (size_t)splits * M * N * sizeof(float);
+    p.slab_bytes = (size_t)splits * M * NP * sizeof(float);
     add(THUNK_ENTRY, g, tiles * splits, EPI_SLAB);
     add(THUNK_SPLITK_REDUCE, g, 0, out.c32 ? EPI_C32 : out.has_epi() ? out.epi_bias() : EPI_SLAB);
   } else {
@@ -685,12 +697,14 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 // reference kernel as an argument and the member's own kernel in fields its non-slab launch leaves idle: z_out in
 // g.partial, z in g.counters, the stride out.ldz in g.tail_first -- tail_tiles stays 0, so the raster map never reads it.)
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
-              int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr, float* db32 = nullptr) {
+              int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr, float* db32 = nullptr, const void* b2 = nullptr,
+              const void* bias2 = nullptr) {
   DisarmTiming disarm_timing;
-  if (!a || !b || !c || (out.bias && !bias) || (out.has_z() && (!z || z == c)) || (out.dbias && !db32) || M <= 0 || N <= 0 || K <= 0)
+  if (!a || !b || !c || (out.bias && !bias) || (out.gated && !b2) || (out.has_z() && (!z || z == c)) || (out.dbias && !db32) || M <= 0 || N <= 0 || K <= 0)
     return HGEMM_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15)) && !(out.has_z() && ((uintptr_t)z & 15));
+  const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15)) && !(out.has_z() && ((uintptr_t)z & 15)) &&
+                       !(out.gated && (((uintptr_t)b2 | (uintptr_t)bias | (uintptr_t)bias2) & 15));   // (a null bias is aligned)
   unsigned ruled_out = 0;
   LaunchPlan p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
@@ -718,12 +732,21 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
     }
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
     switch (p.d[i].thunk) {
-      case THUNK_ENTRY: launch(g, p.d[i].grid, s, p.d[i].epi, ts); break;
+      case THUNK_ENTRY:
+        if (out.gated) {   // the gated sets' launchers are handed a GatedArgs (hgemm_kernel_tn_gated.hpp)
+          GatedArgs ga;
+          static_cast<GemmArgs&>(ga) = g;
+          ga.Bu = (const __bf16*)b2; ga.bias_g = (const __bf16*)bias; ga.bias_u = (const __bf16*)bias2;
+          launch(ga, p.d[i].grid, s, p.d[i].epi, ts);
+        } else {
+          launch(g, p.d[i].grid, s, p.d[i].epi, ts);
+        }
+        break;
       case THUNK_COLSUM_BLOCKED: launch_colsum_blocked(c, slabs + p.colsum_off / sizeof(float), M, N, ldc, s, ts); break;
       case THUNK_COLSUM_FINISH: launch_colsum_finish(slabs + p.colsum_off / sizeof(float), db32, g.items, N, out.db_acc, s, ts); break;
       case THUNK_COLSUM_DIRECT: launch_colsum_direct(c, db32, M, N, ldc, out.db_acc, s, ts); break;
-      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, bias, z, M, N, ldc, out.ldz, g.splits, out.accumulate, s, ts); break;
-      default: kern.reference(a, b, c, bias, z, M, N, K, lda, ldb, ldc, out.ldz, out.accumulate, s, ts); break;
+      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, bias, bias2, z, M, N, ldc, out.ldz, g.splits, out.accumulate, s, ts); break;
+      default: kern.reference(a, b, b2, c, bias, bias2, z, M, N, K, lda, ldb, ldc, out.ldz, out.accumulate, s, ts); break;
     }
   }
   hipError_t err = hipGetLastError();
@@ -1213,6 +1236,43 @@ int bgemm_mi355x_selfcheck_launch_nn_bias(int nn_config, int splits, int operand
 int bgemm_mi355x_selfcheck_launch_ta_bias(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
                                           long long out[20]) {
   return tr_selfcheck_launch(kLayoutTA, TR_BF16, kOutC16Bias, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- the gated forward product, H = act(X Wg^T + bg) (.) (X Wu^T + bu) (the kinds TR_C16_GATED + act): the work of the TN product of width
+// 2 N, so the planned call asks bgemm_mi355x_tn_plan(M, 2 N, K) and the workspace is that product's; N is the output width everywhere else.
+// act: HGEMM_ACT_RELU / _GELU / _GELU_TANH / _SILU, anything else HGEMM_ERR_BAD_ARG.  Either bias may be NULL: +0.0.
+int bgemm_mi355x_tn_gated_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc) {
+  return tr_runs(kLayoutTN, TR_BF16, out_gated(HGEMM_ACT_RELU), tn_config, M, N, K, lda, ldb, ldc);   // (no activation changes the answer)
+}
+int bgemm_mi355x_launch_tn_gated(int tn_config, int splits_arg, const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g,
+                                 const void* bias_u, void* c, int M, int N, int K, int lda, int ldb, int ldc, int act, void* stream) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutTN, TR_BF16, out_gated(act), tn_config, splits_arg, a, wg_col_major, bias_g, c, M, N, K, lda, ldb, ldc, stream, nullptr, nullptr,
+                   wu_col_major, bias_u);
+}
+int bgemm_mi355x_tn_gated(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c, int M,
+                          int N, int K, int act, void* stream) {
+  if (!act_known_gated(act) || M <= 0 || N <= 0 || K <= 0 || N >= (1 << 30)) return HGEMM_ERR_BAD_ARG;   // (2 N is an int)
+  int cfg, splits;
+  tr_model_plan(kLayoutTN, M, 2 * N, K, &cfg, &splits);
+  return bgemm_mi355x_launch_tn_gated(cfg, splits, a, wg_col_major, wu_col_major, bias_g, bias_u, c, M, N, K, K, K, N, act, stream);
+}
+// (bgemm_mi355x_selfcheck_launch_tn_bias_act's output; operands & 4: a, both weights, c and every non-NULL bias are 16-byte aligned.  The NN
+// and TA twins show the refusal.)
+int bgemm_mi355x_selfcheck_launch_tn_gated(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                           int act, long long out[20]) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, out_gated(act), tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_nn_gated(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                           int act, long long out[20]) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_gated(act), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_ta_gated(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ruled_out,
+                                           int act, long long out[20]) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTA, TR_BF16, out_gated(act), ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
 // ---- the forward product with a fused bias and activation, Y = act(X W^T + b) (the kinds TR_C16_BIAS + act): C = bf16(act32(z)),

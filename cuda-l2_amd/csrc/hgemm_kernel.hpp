@@ -310,6 +310,10 @@ constexpr int EPI_C16_DACT = 11;
 // ROUNDED values to P[tile_m][n] in g.partial (hgemm_dbias.hpp).  EPI_C16_DACT_DBIAS + the activation's id: 33 / 34 / 35.  Ids 15 .. would
 // run into the two flags below; families n and f take neither, and 33 .. 35 have neither bit (8, 16) set, so no id here reads as a flag.
 constexpr int EPI_C16_DACT_DBIAS = 32;
+// The gated forward product (family f, bgemm_mi355x_tn_gated): C = bf16(act(acc_g + bias_g[n]) x (acc_u + bias_u[n])), two accumulators of one
+// lane, one product, rounded once (hgemm_kernel_tn_gated.hpp).  EPI_C16_GATED + the activation's id, HGEMM_ACT_SILU = 4 included: 65 .. 68,
+// again with neither flag bit (8, 16) set.  The id of a plan's dispatch; the kernels take the activation itself as their parameter.
+constexpr int EPI_C16_GATED = 64;
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

@@ -381,6 +381,15 @@ void launch_tr(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingS
   }
 }
 using TrLaunch = void (*)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+// What a launcher of the gated sets (hgemm_kernel_tn_gated.hpp) is handed through that signature: the launch's GemmArgs (A = X, Bt = Wg,
+// C, partial = the slabs, N = the OUTPUT width, tiles_n = ceil(N / (BN / 2))) and behind it the second weight and the two bias vectors
+// (either may be null).  tr_launch (hgemm_api.hip) builds one and passes it as its base; the launcher casts back.  GemmArgs itself keeps
+// its size and every kernarg offset.
+struct GatedArgs : GemmArgs {
+  const __bf16* Bu;
+  const __bf16* bias_g;
+  const __bf16* bias_u;
+};
 
 // The members of both families, smallest tile first, and what is made of them: X(args ..., BM, BN, WM, WN, NBUF) per member.
 //   HGEMM_TR_INST(CFG, C32)    a unit's one line: the explicit instantiation of a kernel set's launchers, and with them its kernels
@@ -443,19 +452,24 @@ enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C h
 // TR_C16_BIAS_AUX + a: the same with the rounded pre-activation as a second output (bgemm_mi355x_tn_bias_act_aux).  TR_C16_DACT + a: a
 // 16-bit C through that activation's derivative at a saved pre-activation (family n: bgemm_mi355x_nn_dact).
 enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_C16_BIAS_GELU = 4, TR_C16_BIAS_GELU_TANH = 5,
-              TR_C16_BIAS_AUX = 5, TR_C16_DACT = 8, TR_C16_DACT_DBIAS = 11, TR_KINDS = 15 };   // TR_C16_DACT_DBIAS + a: dact with the bias gradient
+              TR_C16_BIAS_AUX = 5, TR_C16_DACT = 8, TR_C16_DACT_DBIAS = 11, TR_KINDS = 15,   // TR_C16_DACT_DBIAS + a: dact with the bias gradient
+              // TR_C16_GATED + a (a = 1 .. 4, ACT_SILU included): the gated product (family f: bgemm_mi355x_tn_gated).  TR_KINDS keeps counting
+              // the kinds with one sum per output; the tables hold TR_KINDS_ALL cells.
+              TR_C16_GATED = 14, TR_KINDS_ALL = 19 };
 struct TrRow {
   TrEntry e;
-  TrLaunch launch[2][TR_KINDS];   // [TrElem][TrKind]
+  TrLaunch launch[2][TR_KINDS_ALL];   // [TrElem][TrKind]
 };
 // `bias`: the bf16 bias vector of the TR_C16_BIAS sets (N elements, added last in fp32, the sum rounded once); every other set is handed
 // nullptr and ignores it.  `z` with its row stride ldz: the second matrix -- TR_C16_BIAS_AUX + a: the output z_out, TR_C16_DACT + a: the
-// input z --; every other set is handed nullptr / 0 and ignores them, as a set with a 16-bit C ignores `accumulate`.
+// input z --; every other set is handed nullptr / 0 and ignores them, as a set with a 16-bit C ignores `accumulate`.  `b2` and `bias2`: the
+// second weight and its bias vector of the TR_C16_GATED sets, whose `b` / `bias` are the gate's (either bias may be null there: +0.0); every
+// other set is handed nullptr and ignores them.  The slabs of a gated set are [splits][M][2 N] (hgemm_gated.hpp).
 struct TrKernels {
-  void (*combine)(const float* partial, void* c, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits, bool accumulate,
-                  hipStream_t, TimingSlot);
-  void (*reference)(const void* a, const void* b, void* c, const void* bias, void* z, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
-                    bool accumulate, hipStream_t, TimingSlot);
+  void (*combine)(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
+                  bool accumulate, hipStream_t, TimingSlot);
+  void (*reference)(const void* a, const void* b, const void* b2, void* c, const void* bias, const void* bias2, void* z, int M, int N, int K, int lda,
+                    int ldb, int ldc, int ldz, bool accumulate, hipStream_t, TimingSlot);
   bool present() const { return reference; }
 };
 // The column sum of a bf16 matrix in fp32 (hgemm_registry.hip; hgemm_dbias.hpp has the forms): out32[n] (+)= sum over m of float(x[m][n]).
@@ -467,7 +481,7 @@ void launch_colsum_finish(const float* partial, float* out32, int rows, int N, b
 struct TrTable {
   const TrRow* rows;
   int count;
-  TrKernels kernels[2][TR_KINDS];   // [TrElem][TrKind]
+  TrKernels kernels[2][TR_KINDS_ALL];   // [TrElem][TrKind]
 };
 const TrTable& tr_table_nn();
 const TrTable& tr_table_ta();

@@ -3,6 +3,7 @@
 #include "hgemm_kernel_rg.hpp"
 #include "hgemm_kernel_ta.hpp"
 #include "hgemm_kernel_tn.hpp"
+#include "hgemm_kernel_tn_gated.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -115,7 +116,7 @@ struct ElemPos { int row, col; __device__ int m() const { return row; } __device
 struct QuadPos { size_t e; int N; __device__ int m() const { return (int)(e / N); } __device__ int n() const { return (int)(e % N); } };
 template <class T, int V>
 using vec_t = T __attribute__((ext_vector_type(V)));
-struct OutArgs { void* c; const void* bias; void* z; int ldc, ldz; bool accumulate; };   // what TrKernels' launchers are handed (host)
+struct OutArgs { void* c; const void* bias; void* z; int ldc, ldz; bool accumulate; const void* b2; const void* bias2; };   // what TrKernels' launchers are handed (host)
 
 template <class T, int V>
 __device__ __forceinline__ vec_t<T, V> out_load(const T* p) { return *(const vec_t<T, V>*)p; }
@@ -130,6 +131,7 @@ __device__ __forceinline__ void out_store(T* p, vec_t<float, V> v) {   // each e
 // a 16-bit C of type T (f16, or __bf16: the bgemm_ calls): C = T(S)
 template <class T>
 struct OutC16 {
+  static constexpr int SUMS = 1;   // fp32 sums per output (2: the gated kind)
   T* C; int ldc;
   static OutC16 make(const OutArgs& o) { return {(T*)o.c, o.ldc}; }
   template <int V, class At> __device__ int early(At) const { return 0; }
@@ -138,6 +140,7 @@ struct OutC16 {
 // the fp32 C (hgemm_mi355x_ta_c32, bgemm_mi355x_ta_c32): C32 = accumulate ? C32 + S : S -- the shape of the unsplit result, old + fl(sum);
 // C32 is read only with `accumulate`, ldc counts fp32 elements
 struct OutC32 {
+  static constexpr int SUMS = 1;
   float* C; int ldc, accumulate;
   static OutC32 make(const OutArgs& o) { return {(float*)o.c, o.ldc, o.accumulate ? 1 : 0}; }
   template <int V, class At> __device__ vec_t<float, V> early(At at) const {
@@ -158,6 +161,7 @@ __device__ __forceinline__ float out_act(float z) {
 }
 template <int ACT>
 struct OutBias {
+  static constexpr int SUMS = 1;
   __bf16* C; const __bf16* bias; int ldc;
   static OutBias make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.bias, o.ldc}; }
   template <int V, class At> __device__ vec_t<__bf16, V> early(At at) const { return out_load<__bf16, V>(bias + at.n()); }
@@ -170,6 +174,7 @@ struct OutBias {
 // the same with the pre-activation as a second output (bgemm_mi355x_tn_bias_act_aux): z_out = bf16(z) at stride ldz, both from the one z
 template <int ACT>
 struct OutBiasAux {
+  static constexpr int SUMS = 1;
   __bf16* C; const __bf16* bias; __bf16* Z; int ldc, ldz;
   static OutBiasAux make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.bias, (__bf16*)o.z, o.ldc, o.ldz}; }
   template <int V, class At> __device__ vec_t<__bf16, V> early(At at) const { return out_load<__bf16, V>(bias + at.n()); }
@@ -186,6 +191,7 @@ struct OutBiasAux {
 // float(Z[m][n]))) -- one fp32 multiply on the finished sum, ReLU a select; Z is read-only, at stride ldz
 template <int ACT>
 struct OutDact {
+  static constexpr int SUMS = 1;
   __bf16* C; const __bf16* Z; int ldc, ldz;
   static OutDact make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.z, o.ldc, o.ldz}; }
   template <int V, class At> __device__ vec_t<__bf16, V> early(At at) const { return out_load<__bf16, V>(Z + (size_t)at.m() * ldz + at.n()); }
@@ -193,6 +199,29 @@ struct OutDact {
 #pragma unroll
     for (int i = 0; i < V; ++i) s[i] = dact_mul<ACT>(s[i], (float)z[i]);
     out_store<V>(C + (size_t)at.m() * ldc + at.n(), s);
+  }
+};
+// the gated kind (bgemm_mi355x_tn_gated): TWO finished sums per output, Sg = X Wg^T and Su = X Wu^T; g = Sg + float(bias_g[n]) and
+// u = Su + float(bias_u[n]) one fp32 add each, C = bf16(act_apply<ACT>(g) * u), one product and one rounding (hgemm_gated.hpp).  A null
+// bias vector counts as +0.0, added like any other: the bits of a zero-filled vector.  Wu is the reference kernel's second B operand; it
+// travels here, with the kind's other pointers, so that the kernel's argument list stays the one every other kind compiles with.
+template <int V> struct GatedBias { vec_t<__bf16, V> g, u; };
+template <int ACT>
+struct OutGated {
+  static constexpr int SUMS = 2;
+  __bf16* C; const __bf16* Wu; const __bf16* bias_g; const __bf16* bias_u; int ldc;
+  static OutGated make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.b2, (const __bf16*)o.bias, (const __bf16*)o.bias2, o.ldc}; }
+  template <int V, class At> __device__ GatedBias<V> early(At at) const {
+    GatedBias<V> b;
+    b.g = (__bf16)0.0f; b.u = (__bf16)0.0f;
+    if (bias_g) b.g = out_load<__bf16, V>(bias_g + at.n());
+    if (bias_u) b.u = out_load<__bf16, V>(bias_u + at.n());
+    return b;
+  }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> sg, vec_t<float, V> su, GatedBias<V> b) const {
+#pragma unroll
+    for (int i = 0; i < V; ++i) sg[i] = gated_mul(act_apply<ACT>(sg[i] + (float)b.g[i]), su[i] + (float)b.u[i]);
+    out_store<V>(C + (size_t)at.m() * ldc + at.n(), sg);
   }
 };
 
@@ -207,6 +236,18 @@ __global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* _
     const size_t e = q << 2;
     const QuadPos at{e, N};
     const auto early = out.template early<4>(at);   // in flight with the slab loads
+    if constexpr (Out::SUMS == 2) {
+      // the gated kind: a slab is [M][2 N], row m holding its N gate sums and then its N up sums (gated_slab_index); both columns of an
+      // output added over the splits in split order, then the kind's store of the two finished sums
+      const int m = at.m(), n = at.n();
+      f32x4 sg = *(const f32x4*)(partial + gated_slab_index(M, N, 0, m, n, 0));
+      f32x4 su = *(const f32x4*)(partial + gated_slab_index(M, N, 0, m, n, 1));
+      for (int k = 1; k < splits; ++k) {
+        sg += *(const f32x4*)(partial + gated_slab_index(M, N, k, m, n, 0));
+        su += *(const f32x4*)(partial + gated_slab_index(M, N, k, m, n, 1));
+      }
+      out.template store<4>(at, sg, su, early);
+    } else {
     f32x4 s = *(const f32x4*)(partial + e);
     int k = 1;
     // eight slabs' loads in flight per thread, added in split order: with tiny M*N this kernel is a
@@ -223,6 +264,7 @@ __global__ void __launch_bounds__(256) hgemm_splitk_reduce_kernel(const float* _
       s += p;
     }
     out.template store<4>(at, s, early);
+    }
   }
 }
 
@@ -301,7 +343,13 @@ __global__ void __launch_bounds__(256) hgemm_generic_kernel(const typename Ops::
     const auto early = out.template early<1>(ElemPos{m, n});
     float s = 0.f;
     for (int k = 0; k < K; ++k) s = fmaf((float)A[Ops::a(m, k, lda)], (float)B[Ops::b(k, n, ldb)], s);
+    if constexpr (Out::SUMS == 2) {   // the gated kind: a second chain in k order over the kind's second weight, then its store of both sums
+      float u = 0.f;
+      for (int k = 0; k < K; ++k) u = fmaf((float)A[Ops::a(m, k, lda)], (float)out.Wu[Ops::b(k, n, ldb)], u);
+      out.template store<1>(ElemPos{m, n}, vec_t<float, 1>(s), vec_t<float, 1>(u), early);
+    } else {
     out.template store<1>(ElemPos{m, n}, vec_t<float, 1>(s), early);
+    }
   }
 }
 
@@ -397,38 +445,38 @@ static CombineGrid combine_grid(int M, int N) {
 }
 
 template <class Out>
-static void launch_combine(const float* partial, void* c, const void* bias, void* z, int M, int N, int ldc, int ldz, int splits, bool accumulate,
-                           hipStream_t stream, TimingSlot ts) {
+static void launch_combine(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
+                           bool accumulate, hipStream_t stream, TimingSlot ts) {
   const CombineGrid cg = combine_grid(M, N);
-  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate});
+  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate, nullptr, bias2});
   HGEMM_LAUNCH((hgemm_splitk_reduce_kernel<Out>), cg.grid, cg.threads, stream, ts, partial, out, M, N, splits);
 }
 // the fp32-C kind's combine is the kernel that kept its text (see there)
 template <>
-void launch_combine<OutC32>(const float* partial, void* c, const void*, void*, int M, int N, int ldc, int, int splits, bool accumulate,
+void launch_combine<OutC32>(const float* partial, void* c, const void*, const void*, void*, int M, int N, int ldc, int, int splits, bool accumulate,
                             hipStream_t stream, TimingSlot ts) {
   const CombineGrid cg = combine_grid(M, N);
   HGEMM_LAUNCH(hgemm_splitk_reduce_c32_kernel, cg.grid, cg.threads, stream, ts, partial, (float*)c, M, N, ldc, splits, accumulate ? 1 : 0);
 }
 
 template <class Ops, class Out>
-static void launch_reference(const void* A, const void* B, void* c, const void* bias, void* z, int M, int N, int K, int lda, int ldb, int ldc,
-                             int ldz, bool accumulate, hipStream_t stream, TimingSlot ts) {
+static void launch_reference(const void* A, const void* B, const void* B2, void* c, const void* bias, const void* bias2, void* z, int M, int N, int K,
+                             int lda, int ldb, int ldc, int ldz, bool accumulate, hipStream_t stream, TimingSlot ts) {
   using T = typename Ops::T;
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate});
+  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate, B2, bias2});
   HGEMM_LAUNCH((hgemm_generic_kernel<Ops, Out>), grid, 256, stream, ts, (const T*)A, (const T*)B, out, M, N, K, lda, ldb);
 }
 
 // the b_col_major families' names for their two (hgemm_launch.hpp)
 void launch_splitk_reduce(const float* partial, f16* C, int M, int N, int ldc, int splits,
                           hipStream_t stream, TimingSlot ts) {
-  launch_combine<OutC16<f16>>(partial, C, nullptr, nullptr, M, N, ldc, 0, splits, false, stream, ts);
+  launch_combine<OutC16<f16>>(partial, C, nullptr, nullptr, nullptr, M, N, ldc, 0, splits, false, stream, ts);
 }
 
 void launch_generic(const f16* A, const f16* B, f16* C, int M, int N, int K, int lda, int ldb,
                     int ldc, hipStream_t stream, TimingSlot ts) {
-  launch_reference<Operands<f16, false, false>, OutC16<f16>>(A, B, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, false, stream, ts);
+  launch_reference<Operands<f16, false, false>, OutC16<f16>>(A, B, nullptr, C, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, false, stream, ts);
 }
 
 // ---- the tables of the three layouts of the transposed-read host path (hgemm_kernel_nn.hpp: TrTable), each built by ONE expansion of the
@@ -479,6 +527,10 @@ static TrRow tn_row(TrEntry e) {
   r.launch[TR_BF16][TR_C16_BIAS_AUX + ACT_RELU] = &launch_tn_bias_act_aux<B, ACT_RELU>;
   r.launch[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU] = &launch_tn_bias_act_aux<B, ACT_GELU>;
   r.launch[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU_TANH] = &launch_tn_bias_act_aux<B, ACT_GELU_TANH>;
+  r.launch[TR_BF16][TR_C16_GATED + ACT_RELU] = &launch_tn_gated<B, ACT_RELU>;
+  r.launch[TR_BF16][TR_C16_GATED + ACT_GELU] = &launch_tn_gated<B, ACT_GELU>;
+  r.launch[TR_BF16][TR_C16_GATED + ACT_GELU_TANH] = &launch_tn_gated<B, ACT_GELU_TANH>;
+  r.launch[TR_BF16][TR_C16_GATED + ACT_SILU] = &launch_tn_gated<B, ACT_SILU>;
   return r;
 }
 #define HGEMM_TR_ROW(ROW, P, CFG, ...) ROW<__VA_ARGS__>(HGEMM_TR_ENTRY(P, CFG, __VA_ARGS__)),
@@ -529,6 +581,10 @@ const TrTable& tr_table_tn() {
     t.kernels[TR_BF16][TR_C16_BIAS_AUX + ACT_RELU] = tr_kernels<B, OutBiasAux<ACT_RELU>>();
     t.kernels[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU] = tr_kernels<B, OutBiasAux<ACT_GELU>>();
     t.kernels[TR_BF16][TR_C16_BIAS_AUX + ACT_GELU_TANH] = tr_kernels<B, OutBiasAux<ACT_GELU_TANH>>();
+    t.kernels[TR_BF16][TR_C16_GATED + ACT_RELU] = tr_kernels<B, OutGated<ACT_RELU>>();
+    t.kernels[TR_BF16][TR_C16_GATED + ACT_GELU] = tr_kernels<B, OutGated<ACT_GELU>>();
+    t.kernels[TR_BF16][TR_C16_GATED + ACT_GELU_TANH] = tr_kernels<B, OutGated<ACT_GELU_TANH>>();
+    t.kernels[TR_BF16][TR_C16_GATED + ACT_SILU] = tr_kernels<B, OutGated<ACT_SILU>>();
     return t;
   }();
   return table;

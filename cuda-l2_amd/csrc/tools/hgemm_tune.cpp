@@ -83,6 +83,7 @@
 #include "../../../include/hgemm_mi355x.h"
 #include "../hgemm_act.hpp"
 #include "../hgemm_dbias.hpp"
+#include "../hgemm_gated.hpp"
 
 // Ablation switches exist only in the -DHGEMM_ABLATION build of the library (build.py: HGEMM_LIB_SUFFIX=ablation
 // HGEMM_EXTRA_HIPFLAGS=-DHGEMM_ABLATION); against the shipping library the symbol is absent and --debug refuses.
@@ -1062,12 +1063,12 @@ enum Elem { kF16, kBF16 };
 // c32: C is fp32, stored or accumulated onto (else 16-bit elements); bias: the call takes bias[N]; db32: it also writes the column sum
 // db32[N]; act: it takes an activation.
 enum ZRole { kZNone, kZRead, kZWritten };   // no z; Z is an input (dact); z_out is a second output (aux)
-struct OutKind { bool c32, bias; ZRole z; bool db32, act; };
+struct OutKind { bool c32, bias; ZRole z; bool db32, act; bool gated = false; };   // gated: two weights, two biases (bgemm_mi355x_tn_gated)
 static const OutKind kOutC16 = {false, false, kZNone, false, false}, kOutC32 = {true, false, kZNone, false, false},
                      kOutBias = {false, true, kZNone, false, false}, kOutBiasAct = {false, true, kZNone, false, true},
                      kOutBiasAux = {false, true, kZWritten, false, true}, kOutDact = {false, false, kZRead, false, true},
-                     kOutDactDbias = {false, false, kZRead, true, true};
-static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh"};
+                     kOutDactDbias = {false, false, kZRead, true, true}, kOutGated = {false, false, kZNone, false, true, true};
+static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh", "silu"};   // silu: --gated alone
 // fp16 values as fp16 or as bf16 bits, ready for upload
 static std::vector<uint16_t> operand_bits(const std::vector<f16>& v, Elem elem) {
   std::vector<uint16_t> o(v.size());
@@ -1107,7 +1108,8 @@ static const TrLayout kLayoutTN = {"tn", "the TN kernels", kShapesNN, false, tru
 
 // One call's operands.  Every variant's entry points sit behind the same two signatures; what a variant has no use for (bias,
 // accumulate, z, db32, act) its adapter drops.  z: z_out of --aux, Z of --dact; act: HGEMM_ACT_RELU / _GELU / _GELU_TANH
-struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; float* db32 = nullptr; int act = 0; };
+struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; float* db32 = nullptr; int act = 0;
+                const void *b2 = nullptr, *bias2 = nullptr; };   // b2, bias2: Wu and bias_u of a gated call, whose b and bias are the gate's
 template <auto F> static int launch16(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: a 16-bit-C launch
   return F(cfg, splits, o.a, o.b, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
@@ -1142,6 +1144,12 @@ static int launch_dact_dbias(int cfg, int splits, const TrCall& o, const Shape& 
 static int planned_dact_dbias(const TrCall& o, const Shape& sh) { return bgemm_mi355x_nn_dact_dbias(o.a, o.b, o.z, o.c, o.db32, sh.M, sh.N, sh.K, o.act, o.accumulate, nullptr); }
 static int dact_dbias_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_nn_dact_dbias_runs(cfg, M, N, K, lda, ldb, ldc, N); }
 
+// the gated forward product (bgemm_mi355x_tn_gated): sh.N is the OUTPUT width, both weights [N][K]
+static int launch_gated(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_gated(cfg, splits, o.a, o.b, o.b2, o.bias, o.bias2, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, o.act, nullptr);
+}
+static int planned_gated(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_gated(o.a, o.b, o.b2, o.bias, o.bias2, o.c, sh.M, sh.N, sh.K, o.act, nullptr); }
+
 // What tr_bench is told about one bench (the descriptions themselves: bench_nn ... bench_nn_dact_dbias, below).
 struct TrBench;
 struct BenchDesc {
@@ -1156,11 +1164,12 @@ static void warm_hipblaslt(bool autotune) {
   if (autotune) hgemm_hipblaslt_autotune_init();
 }
 static void bench_nn(TrBench&), bench_ta(TrBench&), bench_ta_c32(TrBench&), bench_bf16(TrBench&), bench_tn_bf16(TrBench&), bench_tn_bias(TrBench&),
-    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&);
+    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&), bench_tn_gated(TrBench&);
 static const BenchDesc kBenchNN = {77, warm_hipblaslt, bench_nn}, kBenchTA = {91, warm_none, bench_ta}, kBenchTAC32 = {91, warm_none, bench_ta_c32},
                        kBenchBF16 = {91, warm_rocblas, bench_bf16}, kBenchTN = {91, warm_rocblas, bench_tn_bf16}, kBenchTNBias = {91, warm_none, bench_tn_bias},
                        kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act}, kBenchTNAux = {91, warm_none, bench_tn_aux},
-                       kBenchNNDact = {91, warm_none, bench_nn_dact}, kBenchNNDactDbias = {91, warm_none, bench_nn_dact_dbias};
+                       kBenchNNDact = {91, warm_none, bench_nn_dact}, kBenchNNDactDbias = {91, warm_none, bench_nn_dact_dbias},
+                       kBenchTNGated = {91, warm_none, bench_tn_gated};
 
 // What tr_check is told about one kind (the functions themselves: below, above tr_check).
 struct Check;
@@ -1169,10 +1178,10 @@ struct CheckDesc {
   int (*judge)(Check&);           // per finished run: compares, reports through Check::report; 0, or the exit status that ends the check
   void (*summary)(const Check&);  // the closing line(s)
 };
-static int operands_zero_one(Check&), operands_small_int(Check&), judge_exact(Check&), judge_act(Check&), judge_dbias(Check&);
-static void summary_exact(const Check&), summary_act(const Check&);
+static int operands_zero_one(Check&), operands_small_int(Check&), operands_gated(Check&), judge_exact(Check&), judge_act(Check&), judge_dbias(Check&), judge_gated(Check&);
+static void summary_exact(const Check&), summary_act(const Check&), summary_gated(const Check&);
 static const CheckDesc kCheckExact = {operands_zero_one, judge_exact, summary_exact}, kCheckAct = {operands_small_int, judge_act, summary_act},
-                       kCheckDbias = {operands_small_int, judge_dbias, summary_act};
+                       kCheckDbias = {operands_small_int, judge_dbias, summary_act}, kCheckGated = {operands_gated, judge_gated, summary_gated};
 
 struct Variant {
   const TrLayout* L;
@@ -1187,7 +1196,7 @@ struct Variant {
   std::string words(const char* layout, const char* sep, int act = 0) const {
     std::string w = std::string(layout) + L->label + (out->c32 ? std::string(sep) + "c32" : "") + (elem == kBF16 ? std::string(sep) + "bf16" : "") +
                     (out->bias ? std::string(sep) + "bias" : "");
-    if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
+    if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : out->gated ? std::string(sep) + "gated" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
                   (out->db32 ? std::string(sep) + "dbias" : "");
     return w;
   }
@@ -1206,19 +1215,21 @@ static const Variant kVariants[] = {
     {&kLayoutTN, kBF16, &kOutBiasAux, aux_runs, launch_bias_act_aux, planned_bias_act_aux, &kCheckAct, &kBenchTNAux},
     {&kLayoutNN, kBF16, &kOutDact, dact_runs, launch_dact, planned_dact, &kCheckAct, &kBenchNNDact},
     {&kLayoutNN, kBF16, &kOutDactDbias, dact_dbias_runs, launch_dact_dbias, planned_dact_dbias, &kCheckDbias, &kBenchNNDactDbias},
+    {&kLayoutTN, kBF16, &kOutGated, bgemm_mi355x_tn_gated_runs, launch_gated, planned_gated, &kCheckGated, &kBenchTNGated},
 };
 // What the command line says of the call; act, dact: 0, or the A of --act A / --dact A as HGEMM_ACT_RELU / _GELU / _GELU_TANH.
 struct TrFlags {
   std::string layout;
   bool bf16 = false, c32 = false, bias = false, aux = false, dbias = false;
-  int act = 0, dact = 0;
-  int activation() const { return act ? act : dact; }
+  int act = 0, dact = 0, gated = 0;
+  int activation() const { return act ? act : dact ? dact : gated; }
 };
 // nullptr: no such variant (--layout tn without --bf16 and no --layout at all are the fp16 b_col_major commands)
 static const Variant* resolve_variant(const TrFlags& f) {
   for (const Variant& v : kVariants)
     if (f.layout == v.L->label && (v.elem == kBF16) == f.bf16 && v.out->c32 == f.c32 && v.out->bias == f.bias && v.out->db32 == f.dbias &&
-        v.out->z == (f.dact ? kZRead : f.aux ? kZWritten : kZNone) && v.out->act == (f.activation() != 0))
+        v.out->z == (f.dact ? kZRead : f.aux ? kZWritten : kZNone) && v.out->act == (f.activation() != 0) && v.out->gated == (f.gated != 0) &&
+        !(f.gated && (f.act || f.dact)))
       return &v;
   return nullptr;
 }
@@ -1272,6 +1283,7 @@ struct Check {
   Shape sh = {};
   size_t cn = 0;                          // M N
   struct Host {
+    std::vector<uint16_t> b2, bias2;      // operands_gated: Wu [N][K] and bias_u (b and bias are the gate's)
     std::vector<uint16_t> a, b, bias, z;  // the bits to upload, A and B as the layout takes them; z [M][N]: Z of a dact call, of an aux call what z_out must hold
     std::vector<unsigned char> want[2];   // operands_zero_one: the expected C as bytes: [0] what a store leaves, [1] (fp32 C alone) what accumulating onto `old` leaves
     std::vector<float> old;
@@ -1355,6 +1367,7 @@ static void summary_exact(const Check& K) {
 static double act_fp64(double z, int act) {
   if (act == HGEMM_ACT_RELU) return z > 0 ? z : 0.0;
   if (act == HGEMM_ACT_GELU) return 0.5 * z * erfc(-z / sqrt(2.0));
+  if (act == HGEMM_ACT_SILU) return z / (1.0 + exp(-z));
   const double u = sqrt(2.0 / M_PI) * (z + 0.044715 * z * z * z);
   return z / (1.0 + exp(-2.0 * u));
 }
@@ -1504,6 +1517,71 @@ static void summary_act(const Check& K) {
               dact ? "1/2 ulp_bf16(S g*) + 2^-19 |S| of the fp64 product" : "1/2 ulp_bf16(y*) + 2^-19 |z| of the fp64 activation of the exact z", K.worst);
 }
 
+// ---- The gated kind's check (--gated A with --layout tn --bf16; bgemm_mi355x_tn_gated) --------------------------------------------------------
+// C = bf16(act(Sg + bias_g[n]) x (Su + bias_u[n])), sh.N the output width.  Wg and Wu independent integers in -2 .. 2, A scaled as in
+// operands_small_int, two bias vectors of multiples of 2^-8 in [-1, 1]: g and u are exact in fp32 in any order (verified per element).
+// The bars: ReLU bit for bit against bf16(fl32(relu(g) u)); the other three |C - y*| <= 1/2 ulp_bf16(y*) + GATED_ACT_EPS |g| |u| +
+// GATED_MUL_EPS |y*|, y* = act*(g) u in fp64 (hgemm_gated.hpp).  C is followed by GATED_GUARD sentinel bytes that no run may change.
+constexpr size_t GATED_GUARD = 64;
+constexpr int GATED_SENTINEL = 0x5a;
+static int operands_gated(Check& K) {
+  const Shape& sh = K.sh;
+  int j = 0;
+  while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
+  const double scale = ldexp(1.0, -std::max(j - 2, 0));
+  uint64_t lcg = 0xD1B54A32D192ED03ull + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
+  auto next = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(lcg >> 33); };
+  std::vector<int8_t> ai((size_t)sh.M * sh.K), gi((size_t)sh.N * sh.K), ui((size_t)sh.N * sh.K);   // A [M][K], Wg and Wu [N][K]
+  for (auto& v : ai) v = (int8_t)((int)(next() % 5) - 2);
+  for (auto& v : gi) v = (int8_t)((int)(next() % 5) - 2);
+  for (auto& v : ui) v = (int8_t)((int)(next() % 5) - 2);
+  for (int8_t v : ai) K.h.a.push_back(bf16_rne((float)(v * scale)));
+  for (int8_t v : gi) K.h.b.push_back(bf16_rne((float)v));
+  for (int8_t v : ui) K.h.b2.push_back(bf16_rne((float)v));
+  std::vector<double> bg(sh.N), bu(sh.N);
+  for (int n = 0; n < sh.N; ++n) {
+    bg[n] = (double)(((n * 37 + 11) % 513) - 256) / 256.0;   // |q| <= 256: at most 8 significant bits, a bf16 value
+    bu[n] = (double)(((n * 101 + 300) % 513) - 256) / 256.0;
+    K.h.bias.push_back(bf16_rne((float)bg[n]));
+    K.h.bias2.push_back(bf16_rne((float)bu[n]));
+  }
+  K.h.relu.resize(K.cn), K.h.y.resize(K.cn), K.h.eps.resize(K.cn);
+  for (int m = 0; m < sh.M; ++m)
+    for (int n = 0; n < sh.N; ++n) {
+      int sg = 0, su = 0;
+      const int8_t *ar = &ai[(size_t)m * sh.K], *gr = &gi[(size_t)n * sh.K], *ur = &ui[(size_t)n * sh.K];
+      for (int k = 0; k < sh.K; ++k) sg += ar[k] * gr[k], su += ar[k] * ur[k];
+      const double g = sg * scale + bg[n], u = su * scale + bu[n];
+      if ((double)(float)g != g || (double)(float)u != u || (double)(float)(sg * scale) != sg * scale || (double)(float)(su * scale) != su * scale) {
+        fprintf(stderr, "check %s: g or u is not exact in fp32 at %d_%d_%d\n", K.lay.c_str(), sh.M, sh.N, sh.K);
+        return 2;
+      }
+      const size_t i = (size_t)m * sh.N + n;
+      const float gf = (float)g, uf = (float)u;
+      K.h.relu[i] = bf16_rne(hgemm_mi355x::gated_mul(gf > 0 ? gf : 0.0f, uf));
+      K.h.y[i] = act_fp64(g, K.act) * u;
+      K.h.eps[i] = hgemm_mi355x::GATED_ACT_EPS * fabs(g) * fabs(u) + hgemm_mi355x::GATED_MUL_EPS * fabs(K.h.y[i]);
+    }
+  return 0;
+}
+static int judge_gated(Check& K) {   // C by judge_act's two rules, then the sentinels behind C
+  judge_act(K);
+  unsigned char guard[GATED_GUARD];
+  HIP_OK(hipMemcpy(guard, (const unsigned char*)K.call.c + K.cn * 2, GATED_GUARD, hipMemcpyDeviceToHost));
+  size_t changed = 0;
+  for (unsigned char g : guard) changed += g != GATED_SENTINEL;
+  if (changed) {
+    printf("FAIL %s %d_%d_%d %s s=%d: %zu sentinel bytes behind C changed\n", K.lay.c_str(), K.sh.M, K.sh.N, K.sh.K, K.cname, K.splits & HGEMM_SPLITK_MASK, changed);
+    ++K.failures;
+  }
+  return 0;
+}
+static void summary_gated(const Check& K) {
+  if (K.act == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (bit-exact against bf16(relu(g) u) of the exact g and u)\n", K.lay.c_str(), K.runs, K.failures);
+  else printf("check %s: %d runs, %d failures (every element within 1/2 ulp_bf16(y*) + 2^-19 |g| |u| + 2^-23 |y*| of the fp64 value of the exact g and u; worst %.3f of it)\n",
+              K.lay.c_str(), K.runs, K.failures, K.worst);
+}
+
 static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
   const TrLayout& L = *V.L;
   const OutKind& O = *V.out;
@@ -1519,9 +1597,13 @@ static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
     DevBufs dev;
     TrCall& call = K.call;
     call = {dev.upload(K.h.a.data(), K.h.a.size() * 2), dev.upload(K.h.b.data(), K.h.b.size() * 2),
-            O.bias ? dev.upload(K.h.bias.data(), K.h.bias.size() * 2) : nullptr, dev.alloc(cn * esz), 0,
+            O.bias || O.gated ? dev.upload(K.h.bias.data(), K.h.bias.size() * 2) : nullptr, dev.alloc(cn * esz + (O.gated ? GATED_GUARD : 0)), 0,
             O.z == kZRead ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : nullptr,
             O.db32 ? (float*)dev.alloc((sh.N + DBIAS_GUARD) * sizeof(float)) : nullptr, act};
+    if (O.gated) {
+      call.b2 = dev.upload(K.h.b2.data(), K.h.b2.size() * 2), call.bias2 = dev.upload(K.h.bias2.data(), K.h.bias2.size() * 2);
+      HIP_OK(hipMemset((unsigned char*)call.c + cn * esz, GATED_SENTINEL, GATED_GUARD));
+    }
     K.got.resize(cn * esz);
     for (int c = 0; c < nc; ++c) {
       K.cfg = c;
@@ -1778,6 +1860,10 @@ template <class F> static void with_act(int act, F&& f) {
   else if (act == HGEMM_ACT_GELU) f(std::integral_constant<int, HGEMM_ACT_GELU>());
   else f(std::integral_constant<int, HGEMM_ACT_GELU_TANH>());
 }
+template <class F> static void with_gated_act(int act, F&& f) {   // the gated kind's: SiLU too, which the derivative kernels do not have
+  if (act == HGEMM_ACT_SILU) f(std::integral_constant<int, HGEMM_ACT_SILU>());
+  else with_act(act, f);
+}
 static void head_act(TrBench& B, const char* output) {   // the header fields of the activation kinds' records
   B.head("\"output\": \"%s\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", output, kActNames[B.act],
          B.V.L->config_name(B.cfg), B.splits, B.V.runs_at(B.cfg, B.sh));
@@ -1810,6 +1896,49 @@ template <int ACT>
 __global__ void act_bf16_kernel(__bf16* __restrict__ c, size_t total) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
     c[i] = (__bf16)hgemm_mi355x::act_apply<ACT>((float)c[i]);
+}
+
+// the unfused second pass of the gated contender: H[m][n] = bf16(act(float(GU[m][n])) x float(GU[m][N + n])) over the bf16 [M][2 N] product
+// of the stacked weight, hgemm_act.hpp's text on values already rounded to bf16
+template <int ACT>
+__global__ void gate_bf16_kernel(const __bf16* __restrict__ gu, __bf16* __restrict__ h, size_t total, int n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t m = i / n, c = i % n;
+    h[i] = (__bf16)(hgemm_mi355x::act_apply<ACT>((float)gu[m * 2 * n + c]) * (float)gu[m * 2 * n + n + c]);
+  }
+}
+// tn --bf16 --gated A: bgemm_mi355x_launch_tn_gated at the plan of the product of width 2 N against the path it replaces at the SAME member
+// and splits -- bgemm_mi355x_launch_tn on the stacked [2 N][K] weight into a bf16 [M][2 N] scratch, then the element-wise kernel above (its
+// launch is not checked: the contender answers with the product's status) --, and, context only, that product alone.  Both halves of the
+// stacked weight hold the set's B (timing only).  The one condition: fused <= unfused within the unfused path's own round-to-round spread
+// in this run: "gated_le_unfused".  (The record's TFLOP/s count 2 M N K with N the output width: half of the product's flops.)
+static void bench_tn_gated(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  int cfg = 0, splits = 1;
+  bgemm_mi355x_tn_plan(sh.M, 2 * sh.N, sh.K, &cfg, &splits);
+  B.cfg = cfg, B.splits = splits;
+  const int lda = sh.K, ldb = sh.K, act = B.act, gate_grid = elementwise_grid(cn);
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), half = B.to_bf16(B.of(&Buffers::bt), B.b_elems), w = B.alloc(2 * B.b_elems * 2),
+                        gu = B.alloc(2 * cn * 2), cb = B.alloc(cn * 2), bias = B.alloc((size_t)2 * sh.N * 2);
+  for (size_t i = 0; i < w.size(); ++i) {
+    HIP_OK(hipMemcpy(w[i], half[i], B.b_elems * 2, hipMemcpyDeviceToDevice));
+    HIP_OK(hipMemcpy((char*)w[i] + B.b_elems * 2, half[i], B.b_elems * 2, hipMemcpyDeviceToDevice));
+    fill_bias_kernel<<<64, 256>>>((__bf16*)bias[i], 2 * sh.N);
+  }
+  B.add("gated", [=](Buffers&, size_t i) {
+    return bgemm_mi355x_launch_tn_gated(cfg, splits, ab[i], w[i], (const char*)w[i] + (size_t)sh.N * sh.K * 2, bias[i], (const char*)bias[i] + (size_t)sh.N * 2, cb[i],
+                                        sh.M, sh.N, sh.K, lda, ldb, sh.N, act, nullptr);
+  });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_tn(cfg, splits, ab[i], w[i], gu[i], sh.M, 2 * sh.N, sh.K, lda, ldb, 2 * sh.N, nullptr);
+    with_gated_act(act, [&](auto A) { gate_bf16_kernel<decltype(A)::value><<<gate_grid, 256>>>((const __bf16*)gu[i], (__bf16*)cb[i], cn, sh.N); });
+    return st;
+  });
+  B.add("product_2n", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn(cfg, splits, ab[i], w[i], gu[i], sh.M, 2 * sh.N, sh.K, lda, ldb, 2 * sh.N, nullptr); });
+  B.head("\"output\": \"c16_gated\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
+         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("gated_le_unfused", 0, 1, true);
 }
 
 // tn --bf16 --bias --act A: the planned bgemm_mi355x_tn_bias_act call against the path it replaces -- bgemm_mi355x_launch_tn_bias with the
@@ -1949,6 +2078,11 @@ int main(int argc, char** argv) {
       const std::string nm = next();
       for (int k = 1; k <= 3; ++k) if (nm == kActNames[k]) which = k;
       if (!which) { fprintf(stderr, "%s takes relu, gelu or gelu_tanh\n", a.c_str()); return 2; }
+    }
+    else if (a == "--gated") {
+      const std::string nm = next();
+      for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.gated = k;
+      if (!tr.gated) { fprintf(stderr, "--gated takes relu, gelu, gelu_tanh or silu\n"); return 2; }
     }
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;

@@ -466,7 +466,8 @@ int bgemm_mi355x_tn_bias_runs(int tn_config, int M, int N, int K, int lda, int l
  *     (the second term covers the fp32 evaluation of 1 + erf / 1 + tanh, 16 and 5 ulp in the device math library, times |z| / 2; it
  *     matters only in the negative tail).  The plain, split and reference forms of one call share one activation text.
  * act == 0 or any other value: HGEMM_ERR_BAD_ARG (a caller with no activation has bgemm_mi355x_tn_bias).  bias == NULL:
- * HGEMM_ERR_BAD_ARG -- a layer without a bias passes a zero vector.  No fp16 form, no other layout, no SiLU or gated form.
+ * HGEMM_ERR_BAD_ARG -- a layer without a bias passes a zero vector.  No fp16 form, no other layout; HGEMM_ACT_SILU is refused here --
+ * SiLU and the gated forms (SwiGLU, GeGLU, ReGLU) are bgemm_mi355x_tn_gated, below.
  * The table, ids, names, plan, workspace size and reserve call are bgemm_mi355x_tn_*'s: the tiles, cuts, slabs, splits word, statuses
  * and capture behaviour of a call are those of the bgemm_mi355x_launch_tn call with the same arguments. */
 #define HGEMM_ACT_RELU 1
@@ -478,6 +479,43 @@ int bgemm_mi355x_launch_tn_bias_act(int tn_config, int splits, const void* a, co
                                     int M, int N, int K, int lda, int ldb, int ldc, int act, void* stream);
 /* 1 when the call (with an aligned bias) runs one of the family's kernels: equal to bgemm_mi355x_tn_runs */
 int bgemm_mi355x_tn_bias_act_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc);
+
+/* ------------------------------------------------------------------------------------------
+ * Gated forward product: H = act(X x Wg^T + bg) (.) (X x Wu^T + bu), the first half of a SwiGLU / GeGLU / ReGLU MLP (Llama, Mistral,
+ * Qwen, Gemma, PaLM) in one call.  a = X [M][lda]; wg_col_major and wu_col_major are each [N][ldb] with K contiguous, N the OUTPUT width,
+ * one ldb for both; a fused [2N][K] gate_up weight is passed as wu = wg + N ldb, and wg == wu is allowed (both are only read).  c = H,
+ * bf16 [M][ldc], overlapping no input.
+ * Replaces two bgemm_mi355x_tn_bias* calls, each rounding to bf16, and an element-wise kernel -- or one bgemm_mi355x_tn on the stacked
+ * weight and an element-wise kernel that reads 2 M 2N bytes back and writes M N 2 more; either way the activation sees a rounded value.
+ * Semantics, exactly:  g[m][n] = fl32( Sg[m][n] + float(bias_g[n]) )      Sg = X x Wg^T, the finished fp32 sum
+ *                      u[m][n] = fl32( Su[m][n] + float(bias_u[n]) )      Su = X x Wu^T
+ *                      C[m][n] = bf16_rne( fl32( act32(g[m][n]) x u[m][n] ) )
+ *   - A finished sum is the accumulator of a plain launch, or the slabs of a two-pass plan added in split order.  Bias, activation and
+ *     gate are applied once, to finished sums, never to a slab.  One bf16 rounding.
+ *   - `act` is HGEMM_ACT_RELU, HGEMM_ACT_GELU, HGEMM_ACT_GELU_TANH (as above) or
+ *       HGEMM_ACT_SILU       y = z / (1 + exp(-z)).  NaN gives NaN, +inf gives +inf, -inf gives NaN (inf / inf), a large negative finite
+ *                            z gives -0, z = +-0 gives a zero.
+ *     Any other value: HGEMM_ERR_BAD_ARG.  HGEMM_ACT_SILU is accepted by the gated calls alone.
+ *   - bias_g == NULL or bias_u == NULL (each on its own) means a vector of +0.0: the result is that of a zero-filled vector, bit for bit.
+ *   - The bar: with y* = act*(g) u in fp64 on the exact g and u, every finite element satisfies
+ *       |C - y*| <= 1/2 ulp_bf16(y*) + 2^-19 |g| |u| + 2^-23 |y*|
+ *     (the activation's fp32 evaluation, the fp32 product, the one rounding).  With HGEMM_ACT_RELU C is defined bit for bit.
+ * The call does the work of a TN product of width 2N: the planned call takes its member and splits from bgemm_mi355x_tn_plan(M, 2N, K);
+ * workspace size and reserve are bgemm_mi355x_tn_plan_workspace_bytes(cfg, splits, M, 2N, K) and bgemm_mi355x_tn_reserve_workspace(M, 2N,
+ * K, stream).  Ids, names, the splits word, HGEMM_PLAN_NT_STORE, statuses, the capture rules and the no-workspace fallback during capture
+ * (unsplit, HGEMM_OK, nothing allocated) are bgemm_mi355x_launch_tn's.  A member's tile is BM rows by BN / 2 output columns.
+ * Scope of the kernels: K % 64 == 0, N % 8 == 0, lda / ldb / ldc multiples of 8, a, both weights, c and any non-NULL bias 16-byte
+ * aligned, (BM lda + K) 2, (BN / 2 ldb + K) 2 for each weight and (BM ldc + N) 2 bytes below 2 GiB.  Everything else is answered by the
+ * reference kernel (status 0, the same semantics).  NULL a, wg, wu or c, N >= 2^30: HGEMM_ERR_BAD_ARG.  No fp16 form, no other layout. */
+#define HGEMM_ACT_SILU 4   /* the gated calls only */
+/* planned, contiguous (lda = ldb = K, ldc = N) */
+int bgemm_mi355x_tn_gated(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c,
+                          int M, int N, int K, int act, void* stream);
+int bgemm_mi355x_launch_tn_gated(int tn_config, int splits, const void* a, const void* wg_col_major, const void* wu_col_major,
+                                 const void* bias_g, const void* bias_u, void* c, int M, int N, int K, int lda, int ldb, int ldc, int act,
+                                 void* stream);
+/* 1 when the call (with aligned operands) runs one of the family's kernels */
+int bgemm_mi355x_tn_gated_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc);
 
 /* ------------------------------------------------------------------------------------------
  * Training forward that also saves the pre-activation: Y = act(X x W^T + b) AND Z = X x W^T + b, both bf16, in one call.  Operands,
