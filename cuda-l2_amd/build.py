@@ -54,6 +54,7 @@ LIB_SOURCES = [
     "hgemm_inst_g16.hip",
     "hgemm_inst_g17.hip",
     "hgemm_inst_g18.hip",
+    "hgemm_inst_g19.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -1,7 +1,8 @@
 // The activations of the fused bias+activation calls (bgemm_mi355x_tn_bias_act): ONE text, used by family f's epilogue
 // (hgemm_kernel_tn.hpp), by the split-K combine and by the reference kernel (hgemm_registry.hip), and by a CPU program
 // (tests/test_tn_bias_act_host.py builds one with the host compiler).  act_apply<ACT>(z) maps the unrounded fp32 z = S + float(bias[n]) to
-// the fp32 value that is then rounded to bf16 once.  Below it the derivatives of the same three, dact_apply / dact_mul (bgemm_mi355x_nn_dact).
+// the fp32 value that is then rounded to bf16 once.  Below it the derivatives, dact_apply / dact_mul (bgemm_mi355x_nn_dact; SiLU's for
+// bgemm_mi355x_nn_dgated alone).
 //
 // Written so that the result does not depend on the caller: contraction is off inside each function, a fused operation is an explicit
 // fmaf, and erff / expf are the math library's.  No HIP construct besides the two function attributes, which are empty for a host compiler
@@ -14,7 +15,7 @@
 //                       where z^3 overflows, gives u = -inf, exp = +inf and y = -0; a large positive z gives exp = 0 and y = z.
 //   Both GELUs: NaN gives NaN, +inf gives +inf, -inf gives NaN (0 x inf and inf / inf, as the formulas have it: no select is spent),
 //   +-0 gives a zero.
-//   HGEMM_ACT_SILU      y = z / (1 + exp(-z)), the gated calls only (bgemm_mi355x_tn_gated; every other call refuses the id).  NaN gives NaN,
+//   HGEMM_ACT_SILU      y = z / (1 + exp(-z)), the gated calls only (bgemm_mi355x_tn_gated, bgemm_mi355x_nn_dgated; every other call refuses the id).  NaN gives NaN,
 //                       +inf gives +inf (exp = 0), -inf gives NaN (inf / inf), a large negative finite z gives exp = +inf and y = -0, +-0
 //                       gives a zero of its sign.  expf within 1 ulp, one add and one correctly rounded division: within 4 x 2^-24 |y| of
 //                       the exact value, so within 2^-22 |z| (|silu(z)| <= |z|).
@@ -82,14 +83,28 @@ HGEMM_ACT_HD float act_apply(float z) {
 //     s(a): s(a) s(-a) (5 h x + 2 h) + 2 h s(a) <= 0.224 x 5 h + 0.5 h + 2 h = 3.6 h (t sig(t) sig(-t) <= 0.224); s(-a) = e s(a):
 //     sig(-t) t <= 0.279, 0.279 x 5 h + 0.5 x 5 h = 3.9 h.  p = s(a) s(-a) relatively 10 h x + 10 h, 2u' 4 h, the two products 2 h:
 //     T = a p 2u' carries (10 x + 16) h relatively, and T (10 x + 16) <= 8.6 over a >= 0 (its maximum, 8.54, lies at a = 1.29), so 8.6 h.  The last sum 2 h, the multiply S g 1.13 h.  Sum 15.6 h < 2^-19.
+//   HGEMM_ACT_SILU      g = s + z s (1 - s), s = 1 / (1 + exp(-z)) (the gated backward call only, bgemm_mi355x_nn_dgated; |g| <= 1.0999).
+//                       Written as the tanh form is, on a = |z|: e = exp(-a) <= 1, sp = s(a) = 1 / (1 + e), sm = s(-a) = e sp,
+//                       t = a (sp sm) >= 0 (even in z), g = z < 0 ? sm - t : sp + t.  a is clamped to DACT_SILU_CLAMP = 128 and not to 16:
+//                       at a = 16 the function is still 1.9 x 10^-6 = 32 h from its limit.  exp(-128) = 2.6 x 10^-56 lies 31 binades below
+//                       half the least denormal, so expf gives exactly 0 there, sp = 1, sm = t = +0 (a is finite: no 0 x inf): every
+//                       z >= 128, +inf included, gives exactly 1, every z <= -128, -inf included, +0 (the function is within 2^-177 of
+//                       the limit), NaN gives NaN, +-0 gives 1/2.
+//   silu form.  a is exact.  e = expf(-a): 2 h relatively.  sp: e's error enters with weight e / (1 + e) = sm <= 1/2, so h; the sum and the
+//     division h each: 3 h relatively, sp <= 1.  sm = e sp: 2 h + 3 h + h = 6 h relatively of a value <= 1/2: 3 h.  p = sp sm: 3 h + 6 h + h =
+//     10 h relatively, t = a p 11 h, t <= 0.224 (a sig(a) sig(-a), its maximum at a = 1.54): 2.5 h.  The last sum: sm or sp 3 h, t 2.5 h, its
+//     rounding 1.1 h: 6.6 h.  The multiply S g 1.1 h.  Sum 7.7 h < 2^-19.
 // The bar of the call: |C - S g*(z)| <= 1/2 ulp_bf16(S g*) + DACT_EPS |S|, g* the derivative in fp64.
+// The gated backward call multiplies v = fl32(S u) by g (hgemm_dgated.hpp): v carries h relatively, |g| h more against |S u|, at most 1.13 h:
+// 23.0 h (erf), 16.7 h (tanh), 8.8 h (silu), all below 32 h: the same eps against |S u|.
 constexpr int DACT_EPS_LOG2 = -19;
 constexpr float DACT_EPS = 0x1p-19f;
+constexpr float DACT_SILU_CLAMP = 128.0f;
 
 template <int ACT>
 HGEMM_ACT_HD float dact_apply(float z) {
   HGEMM_ACT_NO_CONTRACT
-  static_assert(ACT == ACT_RELU || ACT == ACT_GELU || ACT == ACT_GELU_TANH, "relu, gelu (erf), gelu (tanh)");
+  static_assert(ACT == ACT_RELU || ACT == ACT_GELU || ACT == ACT_GELU_TANH || ACT == ACT_SILU, "relu, gelu (erf), gelu (tanh), silu");
   if (ACT == ACT_RELU) {
     return (z <= 0.0f) ? 0.0f : 1.0f;
   } else if (ACT == ACT_GELU) {
@@ -97,6 +112,14 @@ HGEMM_ACT_HD float dact_apply(float z) {
     const float t = 1.0f + erff(zc * 0.70710678118654752440f);        // in [0, 2]
     const float e = expf(-0.5f * (zc * zc));                          // 0 from |zc| = 13.3 on
     return fmaf(zc * 0.39894228040143267794f, e, 0.5f * t);           // 1 / sqrt(2 pi)
+  } else if (ACT == ACT_SILU) {
+    float a = z < 0.0f ? -z : z;
+    a = a > DACT_SILU_CLAMP ? DACT_SILU_CLAMP : a;                    // (a NaN fails the test and stays)
+    const float e = expf(-a);                                         // in [0, 1], exactly 0 at the clamp
+    const float sp = 1.0f / (1.0f + e);                               // s(a) in [1/2, 1]
+    const float sm = e * sp;                                          // s(-a) = 1 - s(a)
+    const float t = a * (sp * sm);                                    // |z| s (1 - s) >= 0
+    return z < 0.0f ? sm - t : sp + t;
   } else {
     float a = z < 0.0f ? -z : z;
     a = a > 16.0f ? 16.0f : a;

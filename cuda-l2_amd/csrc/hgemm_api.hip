@@ -493,6 +493,9 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // gated (bgemm_mi355x_tn_gated, family f only): C = T(act(sum_g + bias_g[n]) x (sum_u + bias_u[n])) over two weights of N rows each, the kinds
 // TR_C16_GATED + act (HGEMM_ACT_SILU included) and the ids EPI_C16_GATED + act.  N is the OUTPUT width; tiles, cuts, slabs and workspace are
 // those of the plain product of width 2 N (a member's tile is BM x BN / 2 outputs; hgemm_gated.hpp has the slab).  Either bias may be null.
+// dgated (bgemm_mi355x_nn_dgated, family n only, with dact): the gated layer's input gradient -- two saved 16-bit inputs g (= z) and u at ldz,
+// two 16-bit outputs dg (= c) and du at ldc, hgemm_dgated.hpp's dgated_store on the finished sum --, the kinds TR_C16_DGATED + act
+// (HGEMM_ACT_SILU included) and the ids EPI_C16_DGATED + act.  The dact call's plan in everything but those ids.
 struct TrOut {
   bool c32, accumulate;
   bool bias = false;
@@ -501,13 +504,14 @@ struct TrOut {
   int ldz = 0;   // the row stride of z_out (aux) / z (dact); no part of the kind
   bool dbias = false, db_acc = false;
   bool gated = false;
+  bool dgated = false;   // with dact: two saved matrices in (z = g, and u) and two outputs (c = dg, and du); the dact call's plan
   int elem_bytes() const { return c32 ? 4 : 2; }
   bool has_z() const { return aux || dact; }
   bool has_epi() const { return bias || dact || gated; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
   TrKind kind() const {   // the kernel set's cell in TrRow / TrTable
-    return gated ? (TrKind)(TR_C16_GATED + act) : dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
+    return dgated ? (TrKind)(TR_C16_DGATED + act) : gated ? (TrKind)(TR_C16_GATED + act) : dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
   }
-  int epi_bias() const { return (gated ? EPI_C16_GATED : dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
+  int epi_bias() const { return (dgated ? EPI_C16_DGATED : gated ? EPI_C16_GATED : dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
 };
 constexpr TrOut kOutC16{false, false};
 constexpr TrOut kOutC16Bias{false, false, true};
@@ -516,14 +520,17 @@ static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIA
               TR_C16_DACT == TR_C16_BIAS_AUX + ACT_GELU_TANH && TR_C16_DACT_DBIAS == TR_C16_DACT + ACT_GELU_TANH && TR_C16_DACT_DBIAS + ACT_GELU_TANH + 1 == TR_KINDS,
               "a kind per activation, four times");
 constexpr bool act_known(int act) { return act == HGEMM_ACT_RELU || act == HGEMM_ACT_GELU || act == HGEMM_ACT_GELU_TANH; }
-static_assert(HGEMM_ACT_SILU == ACT_SILU && TR_C16_GATED + 1 == TR_KINDS && TR_C16_GATED + ACT_SILU + 1 == TR_KINDS_ALL && !act_known(HGEMM_ACT_SILU),
-              "the gated kinds follow; SiLU is theirs alone");
+static_assert(HGEMM_ACT_SILU == ACT_SILU && TR_C16_GATED + 1 == TR_KINDS && TR_C16_GATED + ACT_SILU == TR_C16_DGATED &&
+              TR_C16_DGATED + ACT_SILU + 1 == TR_KINDS_ALL && !act_known(HGEMM_ACT_SILU),
+              "the gated kinds and the dgated kinds follow; SiLU is theirs alone");
 constexpr bool act_known_gated(int act) { return act_known(act) || act == HGEMM_ACT_SILU; }
 constexpr TrOut out_gated(int act) { return TrOut{false, false, false, act, false, false, 0, false, false, true}; }   // (act_known_gated(act) checked by the caller)
 constexpr TrOut out_bias_act(int act) { return TrOut{false, false, true, act}; }   // (act_known(act) checked by the caller)
 constexpr TrOut out_bias_act_aux(int act, int ldz) { return TrOut{false, false, true, act, true, false, ldz}; }
 constexpr TrOut out_dact(int act, int ldz) { return TrOut{false, false, false, act, false, true, ldz}; }
 constexpr TrOut out_dact_dbias(int act, int ldz, bool db_acc) { return TrOut{false, false, false, act, false, true, ldz, true, db_acc}; }
+// (act_known_gated(act) checked by the caller.)  A dact call in every rule and in its plan: z is g, ldz the stride of g and of u alike
+constexpr TrOut out_dgated(int act, int ldz) { return TrOut{false, false, false, act, false, true, ldz, false, false, false, true}; }
 
 // What the operands and a 16-bit C hold (TrElem): fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements
 // are 2 bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  (TrElem, c32) selects a kernel set and nothing
@@ -696,15 +703,20 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 // (out.aux / out.dact: `z` is the second matrix, required, distinct from c, and joins the alignment rule.  It reaches the combine and the
 // reference kernel as an argument and the member's own kernel in fields its non-slab launch leaves idle: z_out in
 // g.partial, z in g.counters, the stride out.ldz in g.tail_first -- tail_tiles stays 0, so the raster map never reads it.)
+// (out.dgated: z = g as in a dact call; the second input u travels as `bias` and the second output du as `bias2`, both required, with z's
+// and c's rules; no output may be the other output or an input.  They reach the combine and the reference kernel under those names and the
+// member's kernel behind its GemmArgs, in a DgatedArgs (hgemm_kernel_nn.hpp).)
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
               int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr, float* db32 = nullptr, const void* b2 = nullptr,
               const void* bias2 = nullptr) {
   DisarmTiming disarm_timing;
   if (!a || !b || !c || (out.bias && !bias) || (out.gated && !b2) || (out.has_z() && (!z || z == c)) || (out.dbias && !db32) || M <= 0 || N <= 0 || K <= 0)
     return HGEMM_ERR_BAD_ARG;
+  if (out.dgated && (!bias || !bias2 || bias2 == c || bias2 == z || bias2 == bias || c == bias)) return HGEMM_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15)) && !(out.has_z() && ((uintptr_t)z & 15)) &&
-                       !(out.gated && (((uintptr_t)b2 | (uintptr_t)bias | (uintptr_t)bias2) & 15));   // (a null bias is aligned)
+                       !(out.gated && (((uintptr_t)b2 | (uintptr_t)bias | (uintptr_t)bias2) & 15)) &&   // (a null bias is aligned)
+                       !(out.dgated && (((uintptr_t)bias | (uintptr_t)bias2) & 15));
   unsigned ruled_out = 0;
   LaunchPlan p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
@@ -738,6 +750,11 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
           static_cast<GemmArgs&>(ga) = g;
           ga.Bu = (const __bf16*)b2; ga.bias_g = (const __bf16*)bias; ga.bias_u = (const __bf16*)bias2;
           launch(ga, p.d[i].grid, s, p.d[i].epi, ts);
+        } else if (out.dgated) {   // the dgated sets' launchers are handed a DgatedArgs (hgemm_kernel_nn.hpp)
+          DgatedArgs da;
+          static_cast<GemmArgs&>(da) = g;
+          da.U = (const __bf16*)bias; da.dU = (__bf16*)const_cast<void*>(bias2);
+          launch(da, p.d[i].grid, s, p.d[i].epi, ts);
         } else {
           launch(g, p.d[i].grid, s, p.d[i].epi, ts);
         }
@@ -1347,6 +1364,30 @@ int bgemm_mi355x_launch_nn_dact(int nn_config, int splits_arg, const void* a, co
 int bgemm_mi355x_nn_dact(const void* a, const void* b, const void* z, void* c, int M, int N, int K, int act, void* stream) {
   if (!act_known(act) || !z) return HGEMM_ERR_BAD_ARG;
   return tr_run(kLayoutNN, TR_BF16, out_dact(act, N), a, b, nullptr, c, M, N, K, stream, const_cast<void*>(z));
+}
+// ---- the gated MLP's input gradient, dG = (dY Wd) (.) U (.) act'(G) and dU = act(G) (.) (dY Wd) (the kinds TR_C16_DGATED + act, family n,
+// bf16, HGEMM_ACT_SILU included): hgemm_dgated.hpp's dgated_store on the finished sum in the kernel's epilogue, in the combine and in the
+// reference kernel.  A call resolves to the plan of the bgemm_mi355x_launch_nn_dact call with the same arguments (z = g).
+int bgemm_mi355x_nn_dgated_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldz, int ldc) {
+  return tr_runs(kLayoutNN, TR_BF16, out_dgated(HGEMM_ACT_RELU, ldz), nn_config, M, N, K, lda, ldb, ldc);
+}
+int bgemm_mi355x_launch_nn_dgated(int nn_config, int splits_arg, const void* a, const void* b, const void* g, const void* u, void* dg, void* du, int M,
+                                  int N, int K, int lda, int ldb, int ldz, int ldc, int act, void* stream) {
+  if (!act_known_gated(act) || !g || !u || !dg || !du) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutNN, TR_BF16, out_dgated(act, ldz), nn_config, splits_arg, a, b, u, dg, M, N, K, lda, ldb, ldc, stream, const_cast<void*>(g), nullptr,
+                   nullptr, du);
+}
+int bgemm_mi355x_nn_dgated(const void* a, const void* b, const void* g, const void* u, void* dg, void* du, int M, int N, int K, int act, void* stream) {
+  if (M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  int cfg, splits;
+  tr_model_plan(kLayoutNN, M, N, K, &cfg, &splits);
+  return bgemm_mi355x_launch_nn_dgated(cfg, splits, a, b, g, u, dg, du, M, N, K, K, N, N, N, act, stream);
+}
+// (not part of the public header)
+int bgemm_mi355x_selfcheck_launch_nn_dgated(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldz, int ldc,
+                                            int ruled_out, int act, long long out[20]) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_dgated(act, ldz), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 // ---- the same with the bias gradient (the kinds TR_C16_DACT_DBIAS + act, family n, bf16): C is bgemm_mi355x_launch_nn_dact's C bit for bit
 // and db32[n] (+)= sum over m of float(C[m][n]), the rounded values, in fp32 in an order fixed by the plan (tr_resolve; hgemm_dbias.hpp).

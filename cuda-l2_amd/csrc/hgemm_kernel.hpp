@@ -314,6 +314,9 @@ constexpr int EPI_C16_DACT_DBIAS = 32;
 // lane, one product, rounded once (hgemm_kernel_tn_gated.hpp).  EPI_C16_GATED + the activation's id, HGEMM_ACT_SILU = 4 included: 65 .. 68,
 // again with neither flag bit (8, 16) set.  The id of a plan's dispatch; the kernels take the activation itself as their parameter.
 constexpr int EPI_C16_GATED = 64;
+// The gated MLP's input gradient (family n, bgemm_mi355x_nn_dgated): dU = bf16(act(g) x acc), dG = bf16(acc x u x act'(g)), g and u the saved
+// bf16 pre-activations (hgemm_dgated.hpp).  EPI_C16_DGATED + the activation's id, HGEMM_ACT_SILU included: 97 .. 100, neither flag bit set.
+constexpr int EPI_C16_DGATED = 96;
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

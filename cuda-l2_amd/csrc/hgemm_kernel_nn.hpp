@@ -30,10 +30,15 @@
 //     included by the three kernels) and, for n and a, the accumulator zeroing (tr_zero).  The bar: every kernel's instruction stream,
 //     register counts, LDS and scratch as they were.  The preamble, the ring and the operand images did not meet it in
 //     any form tried and stay in each kernel, on purpose; an edit to one of them is made in all three.
-#pragma once
+// This header includes ITSELF: the device text of the family's kernel stands at the end of the file, behind the include guard, under
+// HGEMM_NN_KERNEL_TEXT, and each of the two entry points (hgemm_nn_kernel, hgemm_nn_dgated_kernel) includes the file once more with that
+// macro set -- the guard skips everything but the text.  Hence a guard and no `#pragma once`.
+#ifndef HGEMM_KERNEL_NN_HPP
+#define HGEMM_KERNEL_NN_HPP
 
 #include "hgemm_act.hpp"
 #include "hgemm_dbias.hpp"
+#include "hgemm_dgated.hpp"
 #include "hgemm_launch.hpp"
 
 namespace hgemm_mi355x {
@@ -88,6 +93,10 @@ constexpr bool epi_is_dact(int epi) { return epi > EPI_C16_DACT && epi <= EPI_C1
 // EPI_C16_DACT_DBIAS + ACT_*: the same C and the tile's column sums (bgemm_mi355x_nn_dact_dbias)
 constexpr bool epi_is_dbias(int epi) { return epi > EPI_C16_DACT_DBIAS && epi <= EPI_C16_DACT_DBIAS + ACT_GELU_TANH; }
 constexpr int epi_dact(int epi) { return epi_is_dact(epi) ? epi - EPI_C16_DACT : epi_is_dbias(epi) ? epi - EPI_C16_DACT_DBIAS : ACT_NONE; }
+// EPI_C16_DGATED + ACT_* (ACT_SILU included): the gated MLP's input gradient, two saved pre-activations in and two bf16 matrices out
+// (bgemm_mi355x_nn_dgated, hgemm_dgated.hpp); the CfgNNB members only, through hgemm_nn_dgated_kernel below.
+constexpr bool epi_is_dgated(int epi) { return epi > EPI_C16_DGATED && epi <= EPI_C16_DGATED + ACT_SILU; }
+constexpr int epi_dgated(int epi) { return epi_is_dgated(epi) ? epi - EPI_C16_DGATED : ACT_NONE; }
 // The byte range of the Z descriptor of the tile whose first row is m0: from that row to Z's last valid element (M - 1, N - 1), computed in
 // 64 bits and CLAMPED to the descriptor's 32: M is not limited by the host, only a tile's reach is, so a Z of 4 GiB and more is in scope
 // and the distance to its end need not fit.  Where the clamp acts, the matrix goes on for more than 4 GiB behind the tile's first row
@@ -149,18 +158,201 @@ __device__ __forceinline__ void tr_zero(f32x4 (&acc)[FM][FN]) {
       for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.0f;
 }
 
+// What a dgated kernel is handed: the launch's GemmArgs -- A = dY, Bt = Wd, C = dG, counters = G, tail_first = ldz, as a dact launch carries
+// its Z -- and behind it the second input and the second output, the way GatedArgs (below) carries a second weight.  GemmArgs itself keeps its
+// size and every kernarg offset.  nn_dgated_u / _du: what the kernel text reads them through; the GemmArgs overloads are never called (the
+// text names them under `if constexpr (epi_is_dgated(EPI))` alone) and let the one text compile for both entry points.
+struct DgatedArgs : GemmArgs {
+  const __bf16* U;
+  __bf16* dU;
+};
+__device__ __forceinline__ const __bf16* nn_dgated_u(const GemmArgs&) { return nullptr; }
+__device__ __forceinline__ __bf16* nn_dgated_du(const GemmArgs&) { return nullptr; }
+__device__ __forceinline__ const __bf16* nn_dgated_u(const DgatedArgs& g) { return g.U; }
+__device__ __forceinline__ __bf16* nn_dgated_du(const DgatedArgs& g) { return g.dU; }
+
 // GemmArgs as the kernel reads it: Bt = the ROW-MAJOR B ([K][ldb]), ldb >= N its row stride; tail_tiles = 0, counters = nullptr.
 template <class CFG, int EPI>
 __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g) {
   prefetch_kernargs<sizeof(GemmArgs)>();
 #if defined(__HIP_DEVICE_COMPILE__)
+#define HGEMM_NN_KERNEL_TEXT
+#include "hgemm_kernel_nn.hpp"   // the kernel text at the end of this file
+#undef HGEMM_NN_KERNEL_TEXT
+#endif  // __HIP_DEVICE_COMPILE__
+}
+// the same text behind a DgatedArgs: the EPI_C16_DGATED + ACT kernels (hgemm_inst_g19.hip)
+template <class CFG, int EPI>
+__global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_dgated_kernel(const DgatedArgs g) {
+  static_assert(epi_is_dgated(EPI), "the dgated epilogues alone");
+  prefetch_kernargs<sizeof(DgatedArgs)>();
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HGEMM_NN_KERNEL_TEXT
+#include "hgemm_kernel_nn.hpp"   // the kernel text at the end of this file
+#undef HGEMM_NN_KERNEL_TEXT
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
+// ---- host side of both transposed-read families (family a builds on it) -----------------------------------------------------------
+// A kernel set is one (element, output) of a layout: CfgNN / CfgNNB / CfgTA / CfgTAB, with a 16-bit C or -- C32 -- the fp32 C.  Each
+// set is instantiated in a unit of its own (hgemm_inst_g5.hip .. g10.hip).
+//
+// The one launcher: member CFG's kernel of epilogue `epi`.  The 16-bit set has the EPI_C16 and EPI_SLAB kernels.  The fp32-C set has
+// the EPI_C32 kernel alone: the K slices of its two-pass form are the 16-bit set's EPI_SLAB kernels (slabs are fp32 either way), reached
+// through that set's launcher in its own unit -- the extern declarations below keep it from being instantiated a second time.
+template <class CFG, bool C32>
+void launch_tr(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if constexpr (C32) {
+    if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+    HGEMM_LAUNCH((CFG::template kernel<EPI_C32>()), grid, CFG::THREADS, stream, ts, g);
+  } else if (epi == EPI_SLAB) {
+    HGEMM_LAUNCH((CFG::template kernel<EPI_SLAB>()), grid, CFG::THREADS, stream, ts, g);
+  } else {
+    HGEMM_LAUNCH((CFG::template kernel<EPI_C16>()), grid, CFG::THREADS, stream, ts, g);
+  }
+}
+using TrLaunch = void (*)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+// What a launcher of the gated sets (hgemm_kernel_tn_gated.hpp) is handed through that signature: the launch's GemmArgs (A = X, Bt = Wg,
+// C, partial = the slabs, N = the OUTPUT width, tiles_n = ceil(N / (BN / 2))) and behind it the second weight and the two bias vectors
+// (either may be null).  tr_launch (hgemm_api.hip) builds one and passes it as its base; the launcher casts back.  GemmArgs itself keeps
+// its size and every kernarg offset.
+struct GatedArgs : GemmArgs {
+  const __bf16* Bu;
+  const __bf16* bias_g;
+  const __bf16* bias_u;
+};
+
+// The members of both families, smallest tile first, and what is made of them: X(args ..., BM, BN, WM, WN, NBUF) per member.
+//   HGEMM_TR_INST(CFG, C32)    a unit's one line: the explicit instantiation of a kernel set's launchers, and with them its kernels
+//   HGEMM_TR_EXTERN(CFG, C32)  everyone else's view of the set: no unit but the set's own instantiates a launcher or a kernel
+//   HGEMM_TR_ENTRY(P, CFG)     the member's geometry row, named P<BM>x<BN>_w<WM>x<WN>
+#define HGEMM_TR_MEMBERS(X, ...) \
+  X(__VA_ARGS__, 64, 64, 2, 2, 4) X(__VA_ARGS__, 128, 64, 2, 2, 3) X(__VA_ARGS__, 64, 128, 2, 2, 3) X(__VA_ARGS__, 128, 128, 2, 2, 3)
+#define HGEMM_TR_LAUNCHER(CFG, C32, BM, BN, WM, WN, NB) launch_tr<CFG<BM, BN, WM, WN, NB>, C32>
+#define HGEMM_TR_INST(...) template void HGEMM_TR_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TR_EXTERN(...) extern HGEMM_TR_INST(__VA_ARGS__)
+#define HGEMM_TR_ENTRY(P, CFG, BM, BN, WM, WN, NB) \
+  {P #BM "x" #BN "_w" #WM "x" #WN, BM, BN, WM, WN, NB, CFG<BM, BN, WM, WN, NB>::THREADS, CFG<BM, BN, WM, WN, NB>::LDS_BYTES}
+
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNN, false)    // hgemm_inst_g5.hip
+HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNNB, false)   // hgemm_inst_g8.hip
+
+// The dact sets (bgemm_mi355x_nn_dact), one per activation: the member's EPI_C16_DACT + ACT kernel alone; the K slices of a two-pass
+// form are the bf16 16-bit set's EPI_SLAB kernels, reached through that set's launcher in its own unit.  g.counters of the dact dispatch
+// is Z, g.tail_first its row stride (tr_launch, hgemm_api.hip).
+template <class CFG, int ACT>
+void launch_nn_dact(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_DACT + ACT>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_NN_DACT_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_nn_dact<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_NN_DACT_INST(...) template void HGEMM_NN_DACT_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_NN_DACT_EXTERN(...) extern HGEMM_NN_DACT_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_RELU, CfgNNB)        // hgemm_inst_g16.hip
+HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU, CfgNNB)
+HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU_TANH, CfgNNB)
+
+// The dact + dbias sets (bgemm_mi355x_nn_dact_dbias): the member's EPI_C16_DACT_DBIAS + ACT kernel alone -- g.partial of its dispatch is
+// P[tiles_m][N] --; a dispatch with the plain dact id (the call without a workspace) and the K slices of a two-pass form go to the dact
+// set's launcher in its own unit.
+template <class CFG, int ACT>
+void launch_nn_dbias(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi != EPI_C16_DACT_DBIAS + ACT) return launch_nn_dact<CFG, ACT>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_DACT_DBIAS + ACT>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_NN_DBIAS_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_nn_dbias<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_NN_DBIAS_INST(...) template void HGEMM_NN_DBIAS_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_NN_DBIAS_EXTERN(...) extern HGEMM_NN_DBIAS_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_RELU, CfgNNB)       // hgemm_inst_g17.hip
+HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_GELU, CfgNNB)
+HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_GELU_TANH, CfgNNB)
+
+// The dgated sets (bgemm_mi355x_nn_dgated), one per activation: the member's EPI_C16_DGATED + ACT kernel alone, handed a DgatedArgs as its
+// GemmArgs base (tr_launch, hgemm_api.hip); the K slices of a two-pass form are the bf16 16-bit set's EPI_SLAB kernels, which read the base.
+template <class CFG, int ACT>
+void launch_nn_dgated(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((hgemm_nn_dgated_kernel<CFG, EPI_C16_DGATED + ACT>), grid, CFG::THREADS, stream, ts, static_cast<const DgatedArgs&>(g));
+}
+#define HGEMM_NN_DGATED_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_nn_dgated<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_NN_DGATED_INST(...) template void HGEMM_NN_DGATED_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_NN_DGATED_EXTERN(...) extern HGEMM_NN_DGATED_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_NN_DGATED_EXTERN, ACT_RELU, CfgNNB)      // hgemm_inst_g19.hip
+HGEMM_TR_MEMBERS(HGEMM_NN_DGATED_EXTERN, ACT_GELU, CfgNNB)
+HGEMM_TR_MEMBERS(HGEMM_NN_DGATED_EXTERN, ACT_GELU_TANH, CfgNNB)
+HGEMM_TR_MEMBERS(HGEMM_NN_DGATED_EXTERN, ACT_SILU, CfgNNB)
+
+// A layout's table (hgemm_registry.hip builds both, each by one expansion of the member list: a config id is a position in `rows`; the
+// geometry table of hgemm_configs*.def does not know these families).  A row is the member's geometry and its launcher in every kernel
+// set of the layout; TrKernels is what a set has besides: the combine of the two-pass form and the reference kernel (status 0, exact:
+// answers whatever is outside the kernels' scope or reach).  All sets share the signatures; a set with a 16-bit C is handed
+// accumulate = false and ignores it.  A set the layout does not have (NN with an fp32 C, NN / TA with a fused bias) is empty: null
+// launchers, TrKernels{}.
+struct TrEntry {
+  const char* name;
+  int bm, bn, wm, wn, nbuf, threads, lds_bytes;
+};
+enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C hold: 2 bytes either way
+// The output kinds of a layout: a 16-bit C, an fp32 C (family a), a 16-bit C with a fused bias (family f: bgemm_mi355x_tn_bias).
+// TR_C16_BIAS + a (a = 1, 2, 3: hgemm_act.hpp's ACT_RELU / _GELU / _GELU_TANH): the bias followed by that activation (bgemm_mi355x_tn_bias_act).
+// TR_C16_BIAS_AUX + a: the same with the rounded pre-activation as a second output (bgemm_mi355x_tn_bias_act_aux).  TR_C16_DACT + a: a
+// 16-bit C through that activation's derivative at a saved pre-activation (family n: bgemm_mi355x_nn_dact).
+enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_C16_BIAS_GELU = 4, TR_C16_BIAS_GELU_TANH = 5,
+              TR_C16_BIAS_AUX = 5, TR_C16_DACT = 8, TR_C16_DACT_DBIAS = 11, TR_KINDS = 15,   // TR_C16_DACT_DBIAS + a: dact with the bias gradient
+              // TR_C16_GATED + a (a = 1 .. 4, ACT_SILU included): the gated product (family f: bgemm_mi355x_tn_gated).  TR_KINDS keeps counting
+              // the kinds with one sum per output; the tables hold TR_KINDS_ALL cells.
+              // TR_C16_DGATED + a (a = 1 .. 4): the gated MLP's input gradient (family n: bgemm_mi355x_nn_dgated), one sum, two outputs.
+              TR_C16_GATED = 14, TR_C16_DGATED = 18, TR_KINDS_ALL = 23 };
+struct TrRow {
+  TrEntry e;
+  TrLaunch launch[2][TR_KINDS_ALL];   // [TrElem][TrKind]
+};
+// `bias`: the bf16 bias vector of the TR_C16_BIAS sets (N elements, added last in fp32, the sum rounded once); every other set is handed
+// nullptr and ignores it.  `z` with its row stride ldz: the second matrix -- TR_C16_BIAS_AUX + a: the output z_out, TR_C16_DACT + a: the
+// input z --; every other set is handed nullptr / 0 and ignores them, as a set with a 16-bit C ignores `accumulate`.  `b2` and `bias2`: the
+// second weight and its bias vector of the TR_C16_GATED sets, whose `b` / `bias` are the gate's (either bias may be null there: +0.0); every
+// other set is handed nullptr and ignores them.  The slabs of a gated set are [splits][M][2 N] (hgemm_gated.hpp).  The TR_C16_DGATED sets
+// have two inputs and two outputs besides the operands and use the same four: `z` = g and `bias` = u (inputs, both at ldz), `c` = dg and
+// `bias2` = du (outputs, both at ldc; the set writes through that one pointer, const in the signature for every other kind's sake).
+struct TrKernels {
+  void (*combine)(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
+                  bool accumulate, hipStream_t, TimingSlot);
+  void (*reference)(const void* a, const void* b, const void* b2, void* c, const void* bias, const void* bias2, void* z, int M, int N, int K, int lda,
+                    int ldb, int ldc, int ldz, bool accumulate, hipStream_t, TimingSlot);
+  bool present() const { return reference; }
+};
+// The column sum of a bf16 matrix in fp32 (hgemm_registry.hip; hgemm_dbias.hpp has the forms): out32[n] (+)= sum over m of float(x[m][n]).
+// finish: out32[n] = (accumulate ? out32[n] : 0) + (P[0][n] + P[1][n] + .. + P[rows - 1][n]), the partials of the fused kernels or of
+// colsum_blocked, added in that order, then the one add into the old value.
+void launch_colsum_direct(const void* x, float* out32, int M, int N, int ldx, bool accumulate, hipStream_t, TimingSlot);
+void launch_colsum_blocked(const void* x, float* partial, int M, int N, int ldx, hipStream_t, TimingSlot);
+void launch_colsum_finish(const float* partial, float* out32, int rows, int N, bool accumulate, hipStream_t, TimingSlot);
+struct TrTable {
+  const TrRow* rows;
+  int count;
+  TrKernels kernels[2][TR_KINDS_ALL];   // [TrElem][TrKind]
+};
+const TrTable& tr_table_nn();
+const TrTable& tr_table_ta();
+const TrTable& tr_table_tn();   // family f (hgemm_kernel_tn.hpp): the bf16 forward product, B given as b_col_major; no transposed read
+
+}  // namespace hgemm_mi355x
+
+#endif  // HGEMM_KERNEL_NN_HPP
+
+// ---- the device text of family n's kernel: the statements of hgemm_nn_kernel<CFG, EPI>(const GemmArgs g) and of
+// hgemm_nn_dgated_kernel<CFG, EPI>(const DgatedArgs g) behind their kernarg prefetch, included by both (see the head of the file).  A text
+// and not a function for hgemm_tr_store_c16.inc's reason: the two entry points differ in the TYPE of g alone -- the dgated kernels find
+// their second input and output behind GemmArgs -- and included, every kernel of hgemm_nn_kernel compiles to the stream it had when the
+// text stood in its braces.
+#ifdef HGEMM_NN_KERNEL_TEXT
   constexpr int BM = CFG::BM, BN = CFG::BN, NBUF = CFG::NBUF;
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
   using elem = typename CFG::elem;   // f16, or __bf16 (the bgemm_ entry points)
   using ex4 = __attribute__((ext_vector_type(4))) elem;
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || ((epi_is_dact(EPI) || epi_is_dbias(EPI)) && __is_same(elem, __bf16)),
-                "plain, two-pass slab and (bf16) dact / dact + dbias epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || ((epi_is_dact(EPI) || epi_is_dbias(EPI) || epi_is_dgated(EPI)) && __is_same(elem, __bf16)),
+                "plain, two-pass slab and (bf16) dact / dact + dbias / dgated epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -354,137 +546,59 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_nn_kernel(const GemmArgs g
     }
   }
 
+  // ---- the gated MLP's input gradient (EPI_C16_DGATED + ACT, bgemm_mi355x_nn_dgated): dU = bf16(act(g) x acc), dG = bf16(acc x u x act'(g)) ---
+  // The dact epilogue's text with TWO saved bf16 matrices and two outputs: g.counters is G and nn_dgated_u(g) is U (both [M][ldz], read-only,
+  // ldz in g.tail_first), g.C is dG and nn_dgated_du(g) is dU (both [M][ldc]).  One 8-byte load per fragment from EACH matrix, each through a
+  // descriptor of its own that starts at the tile's first row and ends at ITS matrix's last valid element (dact_z_range_bytes): with a
+  // fused [M][2 N] buffer (U = G + N) a column group at or past N of G reads U's data, inside the range, and one of U the next row or zeros
+  // behind the end -- values the store text never stores.  Issued behind the K loop, as the dact loads are.  dgated_store (hgemm_dgated.hpp)
+  // is the combine's and the reference kernel's text.  Both results are held: dG replaces the sum in acc, dU goes to a second array of
+  // FM x FN x 4 registers (the 128 x 128 member: 64 + 64 accumulators); it is stored first, through the shared 16-bit store text entered
+  // with `acc` naming it, and the kernel's own store below then writes dG.
+  if constexpr (epi_is_dgated(EPI)) {
+    using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+    using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+    const uint32_t ldz = (uint32_t)g.tail_first;
+    const uint32_t z_bytes = dact_z_range_bytes(g.M, g.N, g.tail_first, tc.m0);
+    const __amdgpu_buffer_rsrc_t rsG =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)g.counters + (size_t)tc.m0 * ldz), 0, z_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc((void*)(nn_dgated_u(g) + (size_t)tc.m0 * ldz), 0, z_bytes, 0x00020000);
+    f32x4 du_acc[FM][FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const uint32_t row = (uint32_t)dbias_row(wave_m, CFG::TM, i, lane);
+      bx4 zg[FN], zu[FN];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const uint32_t n_z = (uint32_t)(tc.n0 + wave_n * CFG::TN + 16 * j + 4 * (lane >> 4));
+        zg[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsG, (row * ldz + n_z) * 2u, 0, 0));
+        zu[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsU, (row * ldz + n_z) * 2u, 0, 0));
+      }
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          DgatedPair y = dgated_store<epi_dgated(EPI)>(acc[i][j][e], (float)zg[j][e], (float)zu[j][e]);
+          asm volatile("" : "+a"(y.dg), "+a"(y.du));
+          acc[i][j][e] = y.dg;
+          du_acc[i][j][e] = y.du;
+        }
+      }
+    }
+    {
+      f32x4(&acc)[FM][FN] = du_acc;   // the store text reads `acc`
+#define HGEMM_TR_STORE_C nn_dgated_du(g)
+#define HGEMM_TR_STORE_LD g.ldc
+#include "hgemm_tr_store_c16.inc"
+#undef HGEMM_TR_STORE_C
+#undef HGEMM_TR_STORE_LD
+    }
+  }
+
   if constexpr (EPI == EPI_SLAB) {
     store_tile<16, FM, FN, CFG::TM, CFG::TN, true>(g, tc, wave_m, wave_n, lane, acc);
   } else {
 #include "hgemm_tr_store_c16.inc"   // the 16-bit C epilogue, one text for families n, a and f
   }
-#endif  // __HIP_DEVICE_COMPILE__
-}
-
-// ---- host side of both transposed-read families (family a builds on it) -----------------------------------------------------------
-// A kernel set is one (element, output) of a layout: CfgNN / CfgNNB / CfgTA / CfgTAB, with a 16-bit C or -- C32 -- the fp32 C.  Each
-// set is instantiated in a unit of its own (hgemm_inst_g5.hip .. g10.hip).
-//
-// The one launcher: member CFG's kernel of epilogue `epi`.  The 16-bit set has the EPI_C16 and EPI_SLAB kernels.  The fp32-C set has
-// the EPI_C32 kernel alone: the K slices of its two-pass form are the 16-bit set's EPI_SLAB kernels (slabs are fp32 either way), reached
-// through that set's launcher in its own unit -- the extern declarations below keep it from being instantiated a second time.
-template <class CFG, bool C32>
-void launch_tr(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  if constexpr (C32) {
-    if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
-    HGEMM_LAUNCH((CFG::template kernel<EPI_C32>()), grid, CFG::THREADS, stream, ts, g);
-  } else if (epi == EPI_SLAB) {
-    HGEMM_LAUNCH((CFG::template kernel<EPI_SLAB>()), grid, CFG::THREADS, stream, ts, g);
-  } else {
-    HGEMM_LAUNCH((CFG::template kernel<EPI_C16>()), grid, CFG::THREADS, stream, ts, g);
-  }
-}
-using TrLaunch = void (*)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-// What a launcher of the gated sets (hgemm_kernel_tn_gated.hpp) is handed through that signature: the launch's GemmArgs (A = X, Bt = Wg,
-// C, partial = the slabs, N = the OUTPUT width, tiles_n = ceil(N / (BN / 2))) and behind it the second weight and the two bias vectors
-// (either may be null).  tr_launch (hgemm_api.hip) builds one and passes it as its base; the launcher casts back.  GemmArgs itself keeps
-// its size and every kernarg offset.
-struct GatedArgs : GemmArgs {
-  const __bf16* Bu;
-  const __bf16* bias_g;
-  const __bf16* bias_u;
-};
-
-// The members of both families, smallest tile first, and what is made of them: X(args ..., BM, BN, WM, WN, NBUF) per member.
-//   HGEMM_TR_INST(CFG, C32)    a unit's one line: the explicit instantiation of a kernel set's launchers, and with them its kernels
-//   HGEMM_TR_EXTERN(CFG, C32)  everyone else's view of the set: no unit but the set's own instantiates a launcher or a kernel
-//   HGEMM_TR_ENTRY(P, CFG)     the member's geometry row, named P<BM>x<BN>_w<WM>x<WN>
-#define HGEMM_TR_MEMBERS(X, ...) \
-  X(__VA_ARGS__, 64, 64, 2, 2, 4) X(__VA_ARGS__, 128, 64, 2, 2, 3) X(__VA_ARGS__, 64, 128, 2, 2, 3) X(__VA_ARGS__, 128, 128, 2, 2, 3)
-#define HGEMM_TR_LAUNCHER(CFG, C32, BM, BN, WM, WN, NB) launch_tr<CFG<BM, BN, WM, WN, NB>, C32>
-#define HGEMM_TR_INST(...) template void HGEMM_TR_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_TR_EXTERN(...) extern HGEMM_TR_INST(__VA_ARGS__)
-#define HGEMM_TR_ENTRY(P, CFG, BM, BN, WM, WN, NB) \
-  {P #BM "x" #BN "_w" #WM "x" #WN, BM, BN, WM, WN, NB, CFG<BM, BN, WM, WN, NB>::THREADS, CFG<BM, BN, WM, WN, NB>::LDS_BYTES}
-
-HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNN, false)    // hgemm_inst_g5.hip
-HGEMM_TR_MEMBERS(HGEMM_TR_EXTERN, CfgNNB, false)   // hgemm_inst_g8.hip
-
-// The dact sets (bgemm_mi355x_nn_dact), one per activation: the member's EPI_C16_DACT + ACT kernel alone; the K slices of a two-pass
-// form are the bf16 16-bit set's EPI_SLAB kernels, reached through that set's launcher in its own unit.  g.counters of the dact dispatch
-// is Z, g.tail_first its row stride (tr_launch, hgemm_api.hip).
-template <class CFG, int ACT>
-void launch_nn_dact(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
-  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_DACT + ACT>()), grid, CFG::THREADS, stream, ts, g);
-}
-#define HGEMM_NN_DACT_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_nn_dact<CFG<BM, BN, WM, WN, NB>, ACT>
-#define HGEMM_NN_DACT_INST(...) template void HGEMM_NN_DACT_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_NN_DACT_EXTERN(...) extern HGEMM_NN_DACT_INST(__VA_ARGS__)
-HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_RELU, CfgNNB)        // hgemm_inst_g16.hip
-HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU, CfgNNB)
-HGEMM_TR_MEMBERS(HGEMM_NN_DACT_EXTERN, ACT_GELU_TANH, CfgNNB)
-
-// The dact + dbias sets (bgemm_mi355x_nn_dact_dbias): the member's EPI_C16_DACT_DBIAS + ACT kernel alone -- g.partial of its dispatch is
-// P[tiles_m][N] --; a dispatch with the plain dact id (the call without a workspace) and the K slices of a two-pass form go to the dact
-// set's launcher in its own unit.
-template <class CFG, int ACT>
-void launch_nn_dbias(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  if (epi != EPI_C16_DACT_DBIAS + ACT) return launch_nn_dact<CFG, ACT>(g, grid, stream, epi, ts);
-  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_DACT_DBIAS + ACT>()), grid, CFG::THREADS, stream, ts, g);
-}
-#define HGEMM_NN_DBIAS_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_nn_dbias<CFG<BM, BN, WM, WN, NB>, ACT>
-#define HGEMM_NN_DBIAS_INST(...) template void HGEMM_NN_DBIAS_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_NN_DBIAS_EXTERN(...) extern HGEMM_NN_DBIAS_INST(__VA_ARGS__)
-HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_RELU, CfgNNB)       // hgemm_inst_g17.hip
-HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_GELU, CfgNNB)
-HGEMM_TR_MEMBERS(HGEMM_NN_DBIAS_EXTERN, ACT_GELU_TANH, CfgNNB)
-
-// A layout's table (hgemm_registry.hip builds both, each by one expansion of the member list: a config id is a position in `rows`; the
-// geometry table of hgemm_configs*.def does not know these families).  A row is the member's geometry and its launcher in every kernel
-// set of the layout; TrKernels is what a set has besides: the combine of the two-pass form and the reference kernel (status 0, exact:
-// answers whatever is outside the kernels' scope or reach).  All sets share the signatures; a set with a 16-bit C is handed
-// accumulate = false and ignores it.  A set the layout does not have (NN with an fp32 C, NN / TA with a fused bias) is empty: null
-// launchers, TrKernels{}.
-struct TrEntry {
-  const char* name;
-  int bm, bn, wm, wn, nbuf, threads, lds_bytes;
-};
-enum TrElem { TR_F16 = 0, TR_BF16 = 1 };   // what the operands and a 16-bit C hold: 2 bytes either way
-// The output kinds of a layout: a 16-bit C, an fp32 C (family a), a 16-bit C with a fused bias (family f: bgemm_mi355x_tn_bias).
-// TR_C16_BIAS + a (a = 1, 2, 3: hgemm_act.hpp's ACT_RELU / _GELU / _GELU_TANH): the bias followed by that activation (bgemm_mi355x_tn_bias_act).
-// TR_C16_BIAS_AUX + a: the same with the rounded pre-activation as a second output (bgemm_mi355x_tn_bias_act_aux).  TR_C16_DACT + a: a
-// 16-bit C through that activation's derivative at a saved pre-activation (family n: bgemm_mi355x_nn_dact).
-enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_C16_BIAS_GELU = 4, TR_C16_BIAS_GELU_TANH = 5,
-              TR_C16_BIAS_AUX = 5, TR_C16_DACT = 8, TR_C16_DACT_DBIAS = 11, TR_KINDS = 15,   // TR_C16_DACT_DBIAS + a: dact with the bias gradient
-              // TR_C16_GATED + a (a = 1 .. 4, ACT_SILU included): the gated product (family f: bgemm_mi355x_tn_gated).  TR_KINDS keeps counting
-              // the kinds with one sum per output; the tables hold TR_KINDS_ALL cells.
-              TR_C16_GATED = 14, TR_KINDS_ALL = 19 };
-struct TrRow {
-  TrEntry e;
-  TrLaunch launch[2][TR_KINDS_ALL];   // [TrElem][TrKind]
-};
-// `bias`: the bf16 bias vector of the TR_C16_BIAS sets (N elements, added last in fp32, the sum rounded once); every other set is handed
-// nullptr and ignores it.  `z` with its row stride ldz: the second matrix -- TR_C16_BIAS_AUX + a: the output z_out, TR_C16_DACT + a: the
-// input z --; every other set is handed nullptr / 0 and ignores them, as a set with a 16-bit C ignores `accumulate`.  `b2` and `bias2`: the
-// second weight and its bias vector of the TR_C16_GATED sets, whose `b` / `bias` are the gate's (either bias may be null there: +0.0); every
-// other set is handed nullptr and ignores them.  The slabs of a gated set are [splits][M][2 N] (hgemm_gated.hpp).
-struct TrKernels {
-  void (*combine)(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
-                  bool accumulate, hipStream_t, TimingSlot);
-  void (*reference)(const void* a, const void* b, const void* b2, void* c, const void* bias, const void* bias2, void* z, int M, int N, int K, int lda,
-                    int ldb, int ldc, int ldz, bool accumulate, hipStream_t, TimingSlot);
-  bool present() const { return reference; }
-};
-// The column sum of a bf16 matrix in fp32 (hgemm_registry.hip; hgemm_dbias.hpp has the forms): out32[n] (+)= sum over m of float(x[m][n]).
-// finish: out32[n] = (accumulate ? out32[n] : 0) + (P[0][n] + P[1][n] + .. + P[rows - 1][n]), the partials of the fused kernels or of
-// colsum_blocked, added in that order, then the one add into the old value.
-void launch_colsum_direct(const void* x, float* out32, int M, int N, int ldx, bool accumulate, hipStream_t, TimingSlot);
-void launch_colsum_blocked(const void* x, float* partial, int M, int N, int ldx, hipStream_t, TimingSlot);
-void launch_colsum_finish(const float* partial, float* out32, int rows, int N, bool accumulate, hipStream_t, TimingSlot);
-struct TrTable {
-  const TrRow* rows;
-  int count;
-  TrKernels kernels[2][TR_KINDS_ALL];   // [TrElem][TrKind]
-};
-const TrTable& tr_table_nn();
-const TrTable& tr_table_ta();
-const TrTable& tr_table_tn();   // family f (hgemm_kernel_tn.hpp): the bf16 forward product, B given as b_col_major; no transposed read
-
-}  // namespace hgemm_mi355x
+#endif  // HGEMM_NN_KERNEL_TEXT

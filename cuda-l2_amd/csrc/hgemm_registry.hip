@@ -225,6 +225,34 @@ struct OutGated {
   }
 };
 
+// the gated MLP's input gradient (bgemm_mi355x_nn_dgated): ONE finished sum S = dY Wd, two saved pre-activations read early (G and U, both
+// at ldz) and two outputs (dG and dU, both at ldc): dgated_store (hgemm_dgated.hpp), each value rounded once.  U arrives in the signatures'
+// `bias` and dU in their `bias2`, two pointers this kind has no other use for (hgemm_kernel_nn.hpp: TrKernels).
+template <int V> struct DgatedSaved { vec_t<__bf16, V> g, u; };
+template <int ACT>
+struct OutDgated {
+  static constexpr int SUMS = 1;
+  __bf16* dG; __bf16* dU; const __bf16* G; const __bf16* U; int ldc, ldz;
+  static OutDgated make(const OutArgs& o) {
+    return {(__bf16*)o.c, (__bf16*)const_cast<void*>(o.bias2), (const __bf16*)o.z, (const __bf16*)o.bias, o.ldc, o.ldz};
+  }
+  template <int V, class At> __device__ DgatedSaved<V> early(At at) const {
+    const size_t at_z = (size_t)at.m() * ldz + at.n();
+    return {out_load<__bf16, V>(G + at_z), out_load<__bf16, V>(U + at_z)};
+  }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, DgatedSaved<V> z) const {
+    vec_t<float, V> du;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const DgatedPair y = dgated_store<ACT>(s[i], (float)z.g[i], (float)z.u[i]);
+      s[i] = y.dg; du[i] = y.du;
+    }
+    const size_t at_c = (size_t)at.m() * ldc + at.n();
+    out_store<V>(dU + at_c, du);
+    out_store<V>(dG + at_c, s);
+  }
+};
+
 // Split-K combine of every kind: S = p[0] + p[1] + ... + p[S-1], fp32 adds in split order and one fixed order per plan, THEN the kind's
 // store.  Nothing is ever applied to a slab; slabs are fp32 whatever the operands were.  (N % 4 == 0 on this path.)
 // (deterministic, unlike the reference's atomicAdd split-K, a100_F32F16F16F32/64_256_16384.cu:149-152).
@@ -503,6 +531,10 @@ static TrRow nn_row(TrEntry e) {
   r.launch[TR_BF16][TR_C16_DACT_DBIAS + ACT_RELU] = &launch_nn_dbias<B, ACT_RELU>;
   r.launch[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU] = &launch_nn_dbias<B, ACT_GELU>;
   r.launch[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU_TANH] = &launch_nn_dbias<B, ACT_GELU_TANH>;
+  r.launch[TR_BF16][TR_C16_DGATED + ACT_RELU] = &launch_nn_dgated<B, ACT_RELU>;
+  r.launch[TR_BF16][TR_C16_DGATED + ACT_GELU] = &launch_nn_dgated<B, ACT_GELU>;
+  r.launch[TR_BF16][TR_C16_DGATED + ACT_GELU_TANH] = &launch_nn_dgated<B, ACT_GELU_TANH>;
+  r.launch[TR_BF16][TR_C16_DGATED + ACT_SILU] = &launch_nn_dgated<B, ACT_SILU>;
   return r;
 }
 template <int... G>
@@ -550,6 +582,10 @@ const TrTable& tr_table_nn() {
     t.kernels[TR_BF16][TR_C16_DACT_DBIAS + ACT_RELU] = tr_kernels<B, OutDact<ACT_RELU>>();
     t.kernels[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU] = tr_kernels<B, OutDact<ACT_GELU>>();
     t.kernels[TR_BF16][TR_C16_DACT_DBIAS + ACT_GELU_TANH] = tr_kernels<B, OutDact<ACT_GELU_TANH>>();
+    t.kernels[TR_BF16][TR_C16_DGATED + ACT_RELU] = tr_kernels<B, OutDgated<ACT_RELU>>();
+    t.kernels[TR_BF16][TR_C16_DGATED + ACT_GELU] = tr_kernels<B, OutDgated<ACT_GELU>>();
+    t.kernels[TR_BF16][TR_C16_DGATED + ACT_GELU_TANH] = tr_kernels<B, OutDgated<ACT_GELU_TANH>>();
+    t.kernels[TR_BF16][TR_C16_DGATED + ACT_SILU] = tr_kernels<B, OutDgated<ACT_SILU>>();
     return t;
   }();
   return table;

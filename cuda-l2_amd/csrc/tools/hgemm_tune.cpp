@@ -45,6 +45,9 @@
 //                                                     dact call's, db32 against the fp64 column sum of the C read back -- ReLU bit for bit, the
 //                                                     GELUs inside gamma_(M-1) sum |C| --, accumulate = 1 one fp32 add; bench against
 //                                                     bgemm_mi355x_launch_nn_dact + bgemm_mi355x_colsum_c32 at the same member and splits
+//   hgemm_tune check|bench --layout nn --bf16 --dgated relu|gelu|gelu_tanh|silu [...]   bgemm_mi355x_launch_nn_dgated: ReLU bit for bit, the
+//                                                     others inside the two bars of hgemm_dgated.hpp, sentinel bytes behind both outputs; bench
+//                                                     against bgemm_mi355x_launch_nn + an element-wise kernel at the same member and splits
 //   hgemm_tune bench --layout tn --bf16 --bias --act A --shapes ... [--out F.jsonl]   against bgemm_mi355x_launch_tn_bias followed by an
 //                                                     element-wise activation kernel, "act_le_unfused"
 //                                                     that check first, then per shape interleaved rounds of the planned call, of
@@ -83,6 +86,7 @@
 #include "../../../include/hgemm_mi355x.h"
 #include "../hgemm_act.hpp"
 #include "../hgemm_dbias.hpp"
+#include "../hgemm_dgated.hpp"
 #include "../hgemm_gated.hpp"
 
 // Ablation switches exist only in the -DHGEMM_ABLATION build of the library (build.py: HGEMM_LIB_SUFFIX=ablation
@@ -1041,8 +1045,8 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
 }
 
 // ---- The transposed-read variants: `check --layout nn|ta|tn ...`, `bench --layout nn|ta|tn ...` ------------------------------------------
-// Twelve call kinds -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias, tn --bf16 --bias --act A,
-// ... --act A --aux, nn --bf16 --dact A, ... --dact A --dbias --, each one row of kVariants that main resolves once from the flags; the
+// Fourteen call kinds -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias, tn --bf16 --bias --act A,
+// ... --act A --aux, nn --bf16 --dact A, ... --dact A --dbias, tn --bf16 --gated A, nn --bf16 --dgated A --, each one row of kVariants that main resolves once from the flags; the
 // activation A is a run-time value of the call (TrCall::act), not of the row.  ONE check (tr_check) and ONE bench driver (tr_bench) serve
 // them all; a row names what differs: its operand scheme, its judge of one finished run, its closing sentence, its bench description.
 // The check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} (fp32 C: x {store, accumulate}) from NaN-filled outputs.
@@ -1063,11 +1067,13 @@ enum Elem { kF16, kBF16 };
 // c32: C is fp32, stored or accumulated onto (else 16-bit elements); bias: the call takes bias[N]; db32: it also writes the column sum
 // db32[N]; act: it takes an activation.
 enum ZRole { kZNone, kZRead, kZWritten };   // no z; Z is an input (dact); z_out is a second output (aux)
-struct OutKind { bool c32, bias; ZRole z; bool db32, act; bool gated = false; };   // gated: two weights, two biases (bgemm_mi355x_tn_gated)
+struct OutKind { bool c32, bias; ZRole z; bool db32, act; bool gated = false;       // gated: two weights, two biases (bgemm_mi355x_tn_gated)
+                 bool dgated = false; };   // dgated: two saved matrices in, two 16-bit matrices out (bgemm_mi355x_nn_dgated)
 static const OutKind kOutC16 = {false, false, kZNone, false, false}, kOutC32 = {true, false, kZNone, false, false},
                      kOutBias = {false, true, kZNone, false, false}, kOutBiasAct = {false, true, kZNone, false, true},
                      kOutBiasAux = {false, true, kZWritten, false, true}, kOutDact = {false, false, kZRead, false, true},
-                     kOutDactDbias = {false, false, kZRead, true, true}, kOutGated = {false, false, kZNone, false, true, true};
+                     kOutDactDbias = {false, false, kZRead, true, true}, kOutGated = {false, false, kZNone, false, true, true},
+                     kOutDgated = {false, false, kZNone, false, true, false, true};
 static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh", "silu"};   // silu: --gated alone
 // fp16 values as fp16 or as bf16 bits, ready for upload
 static std::vector<uint16_t> operand_bits(const std::vector<f16>& v, Elem elem) {
@@ -1109,7 +1115,8 @@ static const TrLayout kLayoutTN = {"tn", "the TN kernels", kShapesNN, false, tru
 // One call's operands.  Every variant's entry points sit behind the same two signatures; what a variant has no use for (bias,
 // accumulate, z, db32, act) its adapter drops.  z: z_out of --aux, Z of --dact; act: HGEMM_ACT_RELU / _GELU / _GELU_TANH
 struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; float* db32 = nullptr; int act = 0;
-                const void *b2 = nullptr, *bias2 = nullptr; };   // b2, bias2: Wu and bias_u of a gated call, whose b and bias are the gate's
+                const void *b2 = nullptr, *bias2 = nullptr;      // b2, bias2: Wu and bias_u of a gated call, whose b and bias are the gate's
+                void* c2 = nullptr; };   // a dgated call: z = g, b2 = u (both [M][N]), c = dg, c2 = du
 template <auto F> static int launch16(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: a 16-bit-C launch
   return F(cfg, splits, o.a, o.b, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
@@ -1150,6 +1157,13 @@ static int launch_gated(int cfg, int splits, const TrCall& o, const Shape& sh, i
 }
 static int planned_gated(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_gated(o.a, o.b, o.b2, o.bias, o.bias2, o.c, sh.M, sh.N, sh.K, o.act, nullptr); }
 
+// the gated MLP's input gradient (bgemm_mi355x_nn_dgated; ldz = ldc = N throughout)
+static int launch_dgated(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_nn_dgated(cfg, splits, o.a, o.b, o.z, o.b2, o.c, o.c2, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, o.act, nullptr);
+}
+static int planned_dgated(const TrCall& o, const Shape& sh) { return bgemm_mi355x_nn_dgated(o.a, o.b, o.z, o.b2, o.c, o.c2, sh.M, sh.N, sh.K, o.act, nullptr); }
+static int dgated_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_nn_dgated_runs(cfg, M, N, K, lda, ldb, N, ldc); }
+
 // What tr_bench is told about one bench (the descriptions themselves: bench_nn ... bench_nn_dact_dbias, below).
 struct TrBench;
 struct BenchDesc {
@@ -1164,12 +1178,12 @@ static void warm_hipblaslt(bool autotune) {
   if (autotune) hgemm_hipblaslt_autotune_init();
 }
 static void bench_nn(TrBench&), bench_ta(TrBench&), bench_ta_c32(TrBench&), bench_bf16(TrBench&), bench_tn_bf16(TrBench&), bench_tn_bias(TrBench&),
-    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&), bench_tn_gated(TrBench&);
+    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&), bench_tn_gated(TrBench&), bench_nn_dgated(TrBench&);
 static const BenchDesc kBenchNN = {77, warm_hipblaslt, bench_nn}, kBenchTA = {91, warm_none, bench_ta}, kBenchTAC32 = {91, warm_none, bench_ta_c32},
                        kBenchBF16 = {91, warm_rocblas, bench_bf16}, kBenchTN = {91, warm_rocblas, bench_tn_bf16}, kBenchTNBias = {91, warm_none, bench_tn_bias},
                        kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act}, kBenchTNAux = {91, warm_none, bench_tn_aux},
                        kBenchNNDact = {91, warm_none, bench_nn_dact}, kBenchNNDactDbias = {91, warm_none, bench_nn_dact_dbias},
-                       kBenchTNGated = {91, warm_none, bench_tn_gated};
+                       kBenchTNGated = {91, warm_none, bench_tn_gated}, kBenchNNDgated = {91, warm_none, bench_nn_dgated};
 
 // What tr_check is told about one kind (the functions themselves: below, above tr_check).
 struct Check;
@@ -1178,10 +1192,12 @@ struct CheckDesc {
   int (*judge)(Check&);           // per finished run: compares, reports through Check::report; 0, or the exit status that ends the check
   void (*summary)(const Check&);  // the closing line(s)
 };
-static int operands_zero_one(Check&), operands_small_int(Check&), operands_gated(Check&), judge_exact(Check&), judge_act(Check&), judge_dbias(Check&), judge_gated(Check&);
-static void summary_exact(const Check&), summary_act(const Check&), summary_gated(const Check&);
+static int operands_zero_one(Check&), operands_small_int(Check&), operands_gated(Check&), judge_exact(Check&), judge_act(Check&), judge_dbias(Check&), judge_gated(Check&),
+           operands_dgated(Check&), judge_dgated(Check&);
+static void summary_exact(const Check&), summary_act(const Check&), summary_gated(const Check&), summary_dgated(const Check&);
 static const CheckDesc kCheckExact = {operands_zero_one, judge_exact, summary_exact}, kCheckAct = {operands_small_int, judge_act, summary_act},
-                       kCheckDbias = {operands_small_int, judge_dbias, summary_act}, kCheckGated = {operands_gated, judge_gated, summary_gated};
+                       kCheckDbias = {operands_small_int, judge_dbias, summary_act}, kCheckGated = {operands_gated, judge_gated, summary_gated},
+                       kCheckDgated = {operands_dgated, judge_dgated, summary_dgated};
 
 struct Variant {
   const TrLayout* L;
@@ -1196,7 +1212,7 @@ struct Variant {
   std::string words(const char* layout, const char* sep, int act = 0) const {
     std::string w = std::string(layout) + L->label + (out->c32 ? std::string(sep) + "c32" : "") + (elem == kBF16 ? std::string(sep) + "bf16" : "") +
                     (out->bias ? std::string(sep) + "bias" : "");
-    if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : out->gated ? std::string(sep) + "gated" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
+    if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : out->gated ? std::string(sep) + "gated" : out->dgated ? std::string(sep) + "dgated" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
                   (out->db32 ? std::string(sep) + "dbias" : "");
     return w;
   }
@@ -1216,20 +1232,21 @@ static const Variant kVariants[] = {
     {&kLayoutNN, kBF16, &kOutDact, dact_runs, launch_dact, planned_dact, &kCheckAct, &kBenchNNDact},
     {&kLayoutNN, kBF16, &kOutDactDbias, dact_dbias_runs, launch_dact_dbias, planned_dact_dbias, &kCheckDbias, &kBenchNNDactDbias},
     {&kLayoutTN, kBF16, &kOutGated, bgemm_mi355x_tn_gated_runs, launch_gated, planned_gated, &kCheckGated, &kBenchTNGated},
+    {&kLayoutNN, kBF16, &kOutDgated, dgated_runs, launch_dgated, planned_dgated, &kCheckDgated, &kBenchNNDgated},
 };
 // What the command line says of the call; act, dact: 0, or the A of --act A / --dact A as HGEMM_ACT_RELU / _GELU / _GELU_TANH.
 struct TrFlags {
   std::string layout;
   bool bf16 = false, c32 = false, bias = false, aux = false, dbias = false;
-  int act = 0, dact = 0, gated = 0;
-  int activation() const { return act ? act : dact ? dact : gated; }
+  int act = 0, dact = 0, gated = 0, dgated = 0;
+  int activation() const { return act ? act : dact ? dact : gated ? gated : dgated; }
 };
 // nullptr: no such variant (--layout tn without --bf16 and no --layout at all are the fp16 b_col_major commands)
 static const Variant* resolve_variant(const TrFlags& f) {
   for (const Variant& v : kVariants)
     if (f.layout == v.L->label && (v.elem == kBF16) == f.bf16 && v.out->c32 == f.c32 && v.out->bias == f.bias && v.out->db32 == f.dbias &&
         v.out->z == (f.dact ? kZRead : f.aux ? kZWritten : kZNone) && v.out->act == (f.activation() != 0) && v.out->gated == (f.gated != 0) &&
-        !(f.gated && (f.act || f.dact)))
+        v.out->dgated == (f.dgated != 0) && !((f.gated || f.dgated) && (f.act || f.dact)) && !(f.gated && f.dgated))
       return &v;
   return nullptr;
 }
@@ -1289,6 +1306,7 @@ struct Check {
     std::vector<float> old;
     std::vector<uint16_t> relu;           // operands_small_int: ReLU's exact C,
     std::vector<double> y, eps;           //   the GELUs' fp64 target y* and the second term of their bar
+                                          // (operands_dgated: 2 M N of each, dg's and behind them du's; z = g and b2 = u, [M][N])
   } h;
   TrCall call = {};
   int cfg = 0, splits = 1;
@@ -1582,6 +1600,82 @@ static void summary_gated(const Check& K) {
               K.lay.c_str(), K.runs, K.failures, K.worst);
 }
 
+// ---- The dgated kind's check (--dgated A with --layout nn --bf16; bgemm_mi355x_nn_dgated) ------------------------------------------------------
+// dg = bf16(dact_mul(fl32(S u), g)), du = bf16(fl32(act(g) S)): A and B as in operands_small_int, so S is exact in fp32 in any order (verified
+// per element); g and u seeded matrices of multiples of 1/32 in [-4, 4] (bf16 values; both signs, zeros, some -0).  The bars: ReLU bit for bit
+// against hgemm_dgated.hpp's dgated_store on the exact S; the other three |dg - S u act'*(g)| <= 1/2 ulp_bf16(.) + 2^-19 |S u| and
+// |du - act*(g) S| <= 1/2 ulp_bf16(.) + 2^-19 |g| |S| + 2^-23 |.|, fp64 values.  Each output is followed by GATED_GUARD sentinel bytes.
+static double dact_fp64_any(double z, int act) {
+  if (act != HGEMM_ACT_SILU) return dact_fp64(z, act);
+  const double s = 1.0 / (1.0 + exp(-z));
+  return s + z * s * (1.0 - s);
+}
+static int operands_dgated(Check& K) {
+  const Shape& sh = K.sh;
+  const size_t cn = K.cn;
+  int j = 0;
+  while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
+  const double scale = ldexp(1.0, -std::max(j - 2, 0));
+  uint64_t lcg = 0xA0761D6478BD642Full + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
+  auto next = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(lcg >> 33); };
+  std::vector<int8_t> ai((size_t)sh.M * sh.K), bi((size_t)sh.K * sh.N);
+  for (auto& v : ai) v = (int8_t)((int)(next() % 5) - 2);
+  for (auto& v : bi) v = (int8_t)((int)(next() % 5) - 2);
+  for (int8_t v : ai) K.h.a.push_back(bf16_rne((float)(v * scale)));
+  for (int8_t v : bi) K.h.b.push_back(bf16_rne((float)v));
+  std::vector<double> g(cn), u(cn);
+  K.h.z.resize(cn), K.h.b2.resize(cn), K.h.relu.resize(2 * cn), K.h.y.resize(2 * cn), K.h.eps.resize(2 * cn);
+  for (size_t i = 0; i < cn; ++i) {
+    g[i] = (double)((int)(next() % 257) - 128) / 32.0;   // |q| <= 128: at most 8 significant bits, a bf16 value
+    u[i] = (double)((int)(next() % 257) - 128) / 32.0;
+    K.h.z[i] = (i % 29 == 7) ? (uint16_t)0x8000 : bf16_rne((float)g[i]);   // some -0
+    if (i % 29 == 7) g[i] = 0.0;
+    K.h.b2[i] = bf16_rne((float)u[i]);
+  }
+  const std::vector<int8_t> bt = transposed(bi, sh.K, sh.N);   // [N][K]
+  for (int m = 0; m < sh.M; ++m)
+    for (int n = 0; n < sh.N; ++n) {
+      int acc = 0;
+      const int8_t *ar = &ai[(size_t)m * sh.K], *br = &bt[(size_t)n * sh.K];
+      for (int k = 0; k < sh.K; ++k) acc += ar[k] * br[k];
+      const double s = acc * scale;
+      if ((double)(float)s != s) { fprintf(stderr, "check %s: S is not exact in fp32 at %d_%d_%d\n", K.lay.c_str(), sh.M, sh.N, sh.K); return 2; }
+      const size_t i = (size_t)m * sh.N + n;
+      const hgemm_mi355x::DgatedPair r = hgemm_mi355x::dgated_store<HGEMM_ACT_RELU>((float)s, (float)bf16_value(K.h.z[i]), (float)u[i]);
+      K.h.relu[i] = bf16_rne(r.dg), K.h.relu[cn + i] = bf16_rne(r.du);
+      K.h.y[i] = s * u[i] * dact_fp64_any(g[i], K.act), K.h.eps[i] = ldexp(fabs(s * u[i]), hgemm_mi355x::DGATED_DACT_EPS_LOG2);
+      K.h.y[cn + i] = act_fp64(g[i], K.act) * s;
+      K.h.eps[cn + i] = ldexp(fabs(g[i]) * fabs(s), hgemm_mi355x::DGATED_ACT_EPS_LOG2) + ldexp(fabs(K.h.y[cn + i]), hgemm_mi355x::DGATED_MUL_EPS_LOG2);
+    }
+  return 0;
+}
+static int judge_dgated(Check& K) {   // both outputs by judge_act's two rules, then the sentinels behind each
+  const size_t cn = K.cn;
+  std::vector<uint16_t> du(cn);
+  unsigned char guard[2][GATED_GUARD];
+  HIP_OK(hipMemcpy(du.data(), K.call.c2, cn * 2, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(guard[0], (const unsigned char*)K.call.c + cn * 2, GATED_GUARD, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(guard[1], (const unsigned char*)K.call.c2 + cn * 2, GATED_GUARD, hipMemcpyDeviceToHost));
+  const uint16_t* dg = (const uint16_t*)K.got.data();
+  size_t bad = 0, changed = 0;
+  for (size_t i = 0; i < cn; ++i) {
+    if (K.act == HGEMM_ACT_RELU) bad += (dg[i] != K.h.relu[i]) || (du[i] != K.h.relu[cn + i]);
+    else bad += !within_gelu_bar(dg[i], K.h.y[i], K.h.eps[i], K.worst) || !within_gelu_bar(du[i], K.h.y[cn + i], K.h.eps[cn + i], K.worst);
+  }
+  K.report(bad);
+  for (const auto& gd : guard) for (unsigned char b : gd) changed += b != GATED_SENTINEL;
+  if (changed) {
+    printf("FAIL %s %d_%d_%d %s s=%d: %zu sentinel bytes behind dg or du changed\n", K.lay.c_str(), K.sh.M, K.sh.N, K.sh.K, K.cname, K.splits & HGEMM_SPLITK_MASK, changed);
+    ++K.failures;
+  }
+  return 0;
+}
+static void summary_dgated(const Check& K) {
+  if (K.act == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (both outputs bit-exact against bf16(relu(g) S) and where(g <= 0, +0, bf16(S u)) of the exact S)\n", K.lay.c_str(), K.runs, K.failures);
+  else printf("check %s: %d runs, %d failures (every element of dg within 1/2 ulp_bf16 + 2^-19 |S u| and of du within 1/2 ulp_bf16 + 2^-19 |g| |S| + 2^-23 |du*| of the fp64 "
+              "values of the exact S; worst %.3f of it)\n", K.lay.c_str(), K.runs, K.failures, K.worst);
+}
+
 static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
   const TrLayout& L = *V.L;
   const OutKind& O = *V.out;
@@ -1597,12 +1691,17 @@ static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
     DevBufs dev;
     TrCall& call = K.call;
     call = {dev.upload(K.h.a.data(), K.h.a.size() * 2), dev.upload(K.h.b.data(), K.h.b.size() * 2),
-            O.bias || O.gated ? dev.upload(K.h.bias.data(), K.h.bias.size() * 2) : nullptr, dev.alloc(cn * esz + (O.gated ? GATED_GUARD : 0)), 0,
-            O.z == kZRead ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : nullptr,
+            O.bias || O.gated ? dev.upload(K.h.bias.data(), K.h.bias.size() * 2) : nullptr, dev.alloc(cn * esz + (O.gated || O.dgated ? GATED_GUARD : 0)), 0,
+            O.z == kZRead || O.dgated ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : nullptr,
             O.db32 ? (float*)dev.alloc((sh.N + DBIAS_GUARD) * sizeof(float)) : nullptr, act};
     if (O.gated) {
       call.b2 = dev.upload(K.h.b2.data(), K.h.b2.size() * 2), call.bias2 = dev.upload(K.h.bias2.data(), K.h.bias2.size() * 2);
       HIP_OK(hipMemset((unsigned char*)call.c + cn * esz, GATED_SENTINEL, GATED_GUARD));
+    }
+    if (O.dgated) {
+      call.b2 = dev.upload(K.h.b2.data(), cn * 2), call.c2 = dev.alloc(cn * 2 + GATED_GUARD);
+      HIP_OK(hipMemset((unsigned char*)call.c + cn * 2, GATED_SENTINEL, GATED_GUARD));
+      HIP_OK(hipMemset((unsigned char*)call.c2 + cn * 2, GATED_SENTINEL, GATED_GUARD));
     }
     K.got.resize(cn * esz);
     for (int c = 0; c < nc; ++c) {
@@ -1615,6 +1714,7 @@ static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
           if (call.accumulate) HIP_OK(hipMemcpy(call.c, K.h.old.data(), cn * esz, hipMemcpyHostToDevice));
           else                 HIP_OK(hipMemset(call.c, 0xff, cn * esz));   // NaN pattern: a store must not read it, unwritten outputs are caught
           if (O.z == kZWritten) HIP_OK(hipMemset(call.z, 0xff, cn * 2));
+          if (O.dgated) HIP_OK(hipMemset(call.c2, 0xff, cn * 2));
           if (O.db32) HIP_OK(hipMemcpy(call.db32, dbias_prefill(sh.N, false).data(), (sh.N + DBIAS_GUARD) * sizeof(float), hipMemcpyHostToDevice));
           const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
           const hipError_t e = hipDeviceSynchronize();
@@ -2024,6 +2124,40 @@ static void bench_nn_dact(TrBench& B) {
   B.verdict("dact_le_unfused", 0, 1, true);
 }
 
+// nn --bf16 --dgated A: bgemm_mi355x_launch_nn_dgated at the plan against the sequence it replaces at the SAME member and splits --
+// bgemm_mi355x_launch_nn writing a bf16 dH, then an element-wise kernel that reads dH, g and u and writes dg and du (10 M N bytes; its launch
+// is not checked: the contender answers with the product's status) --, and, context only, the plain NN call.  "dgated_le_unfused", within
+// the unfused path's own spread.
+template <int ACT>
+__global__ void dgated_elementwise_kernel(__bf16* __restrict__ dg, __bf16* __restrict__ du, const __bf16* __restrict__ dh, const __bf16* __restrict__ g,
+                                          const __bf16* __restrict__ u, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const hgemm_mi355x::DgatedPair y = hgemm_mi355x::dgated_store<ACT>((float)dh[i], (float)g[i], (float)u[i]);
+    dg[i] = (__bf16)y.dg, du[i] = (__bf16)y.du;
+  }
+}
+static void bench_nn_dgated(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), act = B.act, grid = elementwise_grid(cn);
+  const NnDactBufs t = nn_dact_bufs(B);
+  const TrBench::PerSet ab = t.ab, bb = t.bb, dg = t.cb, gb = t.zb, ub = B.alloc(cn * 2), du = B.alloc(cn * 2), hb = B.alloc(cn * 2);
+  for (void* p : ub) fill_z_kernel<<<grid, 256>>>((__bf16*)p, cn);
+  B.add("dgated", [=](Buffers&, size_t i) {
+    return bgemm_mi355x_launch_nn_dgated(cfg, splits, ab[i], bb[i], gb[i], ub[i], dg[i], du[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, act, nullptr);
+  });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], hb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
+    with_gated_act(act, [&](auto A) {
+      dgated_elementwise_kernel<decltype(A)::value><<<grid, 256>>>((__bf16*)dg[i], (__bf16*)du[i], (const __bf16*)hb[i], (const __bf16*)gb[i], (const __bf16*)ub[i], cn);
+    });
+    return st;
+  });
+  B.add("nn", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], hb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
+  head_act(B, "c16_dgated");
+  B.verdict("dgated_le_unfused", 0, 1, true);
+}
+
 // nn --bf16 --dact A --dbias: bgemm_mi355x_launch_nn_dact_dbias at the plan against the sequence it replaces -- bgemm_mi355x_launch_nn_dact with
 // the same member and splits, then bgemm_mi355x_colsum_c32 over the dZ just written (one more launch, 2 M N more bytes read) --, and,
 // context only, the dact call alone.  "dbias_le_unfused", within the unfused path's own spread.
@@ -2084,6 +2218,11 @@ int main(int argc, char** argv) {
       for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.gated = k;
       if (!tr.gated) { fprintf(stderr, "--gated takes relu, gelu, gelu_tanh or silu\n"); return 2; }
     }
+    else if (a == "--dgated") {
+      const std::string nm = next();
+      for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.dgated = k;
+      if (!tr.dgated) { fprintf(stderr, "--dgated takes relu, gelu, gelu_tanh or silu\n"); return 2; }
+    }
     else if (a == "--fused") g_fused_too = true;
     else if (a == "--with-shipped") g_with_shipped = true;
     else if (a == "--streamk") g_streamk_too = true;
@@ -2140,6 +2279,7 @@ int main(int argc, char** argv) {
   if (tr.aux && !tr.act) { fprintf(stderr, "--aux goes with --layout tn --bf16 --bias --act A (bgemm_mi355x_tn_bias_act_aux)\n"); return 2; }
   if (tr.dact && !(tr.bf16 && tr.layout == "nn" && !tr.act)) { fprintf(stderr, "--dact goes with --layout nn --bf16 (bgemm_mi355x_nn_dact)\n"); return 2; }
   if (tr.dbias && !tr.dact) { fprintf(stderr, "--dbias goes with --layout nn --bf16 --dact A (bgemm_mi355x_nn_dact_dbias)\n"); return 2; }
+  if (tr.dgated && !(tr.bf16 && tr.layout == "nn" && !tr.act && !tr.dact)) { fprintf(stderr, "--dgated goes with --layout nn --bf16 (bgemm_mi355x_nn_dgated)\n"); return 2; }
   const Variant* variant = resolve_variant(tr);
   if (variant && mode != "check" && mode != "bench") {
     fprintf(stderr, "--layout %s%s goes with check or bench\n", tr.layout.c_str(), variant->L->b_col_major ? " --bf16" : "");

@@ -507,7 +507,7 @@ int bgemm_mi355x_tn_bias_act_runs(int tn_config, int M, int N, int K, int lda, i
  * Scope of the kernels: K % 64 == 0, N % 8 == 0, lda / ldb / ldc multiples of 8, a, both weights, c and any non-NULL bias 16-byte
  * aligned, (BM lda + K) 2, (BN / 2 ldb + K) 2 for each weight and (BM ldc + N) 2 bytes below 2 GiB.  Everything else is answered by the
  * reference kernel (status 0, the same semantics).  NULL a, wg, wu or c, N >= 2^30: HGEMM_ERR_BAD_ARG.  No fp16 form, no other layout. */
-#define HGEMM_ACT_SILU 4   /* the gated calls only */
+#define HGEMM_ACT_SILU 4   /* the gated calls only: bgemm_mi355x_tn_gated and its input gradient, bgemm_mi355x_nn_dgated */
 /* planned, contiguous (lda = ldb = K, ldc = N) */
 int bgemm_mi355x_tn_gated(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c,
                           int M, int N, int K, int act, void* stream);
@@ -629,6 +629,48 @@ int bgemm_mi355x_nn_dact_dbias_reserve_workspace(int M, int N, int K, void* stre
  * by 2-byte loads), 2-byte loads otherwise; the same adds in the same order either way --, then the finish kernel of the call above.  Otherwise, and without a workspace: one thread per column walks the M
  * rows in order. */
 int bgemm_mi355x_colsum_c32(const void* x, float* out32, int M, int N, int ldx, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Input gradient of the gated MLP (SwiGLU, GeGLU, ReGLU): with H = act(G) (.) U the layer bgemm_mi355x_tn_gated computes and dH = dY x Wd,
+ *     dU = act(G) (.) dH          dG = dH (.) U (.) act'(G)
+ * in one call.  a = dY [M][lda] (K = the model width), b = Wd [K][ldb] row-major (N = the MLP's inner width): bgemm_mi355x_nn's operands.
+ * `g` and `u` are the saved bf16 pre-activations, each [M][ldz], read-only, one ldz for both; `dg` and `du` the bf16 outputs, each
+ * [M][ldc], one ldc for both.  The saved [g|u] is the [M][2N] output of ONE bgemm_mi355x_tn_bias (or bgemm_mi355x_tn) call on the fused
+ * [2N][K] gate_up weight: pass u = g + N with ldz >= 2N (g == u is allowed).  A fused [M][2N] gradient is du = dg + N with ldc >= 2N; the
+ * next two products are then existing calls -- dX = [dG|dU] x [Wg;Wu] is bgemm_mi355x_nn with K = 2N, dW_gate_up += X^T x [dG|dU] is
+ * bgemm_mi355x_ta_c32 with N = 2N -- and the bias gradients are bgemm_mi355x_colsum_c32 over the [M][2N] result.
+ * Replaces bgemm_mi355x_nn followed by an element-wise kernel that reads dH, g, u and writes dG, dU: one more launch, 10 M N more bytes,
+ * and dH rounded to bf16 before it meets the gate.
+ * Semantics, exactly:  gf = float( g[m][n] ), uf = float( u[m][n] )         (exact)
+ *                      du[m][n] = bf16_rne( fl32( act32(gf) x S ) )
+ *                      dg[m][n] = bf16_rne( dact_mul<act>( fl32( S x uf ), gf ) )
+ *   - S is the finished fp32 sum: the accumulator of a plain launch, or the slabs of a two-pass plan added in split order.  Nothing is
+ *     applied to a slab, each output is rounded once, no bf16 dH exists.
+ *   - act32 is bgemm_mi355x_tn_gated's activation; dact_mul is bgemm_mi355x_nn_dact's: for HGEMM_ACT_RELU the select gf <= 0 ? +0 : value,
+ *     otherwise one fp32 multiply by the derivative.  `act` is HGEMM_ACT_RELU, _GELU, _GELU_TANH or _SILU (SiLU stays refused by the dact
+ *     calls).  SiLU's derivative is s + z s (1 - s), s = 1 / (1 + exp(-z)), evaluated on |z| clamped to 128: every z >= 128, +inf
+ *     included, gives exactly 1, every z <= -128, -inf included, +0; NaN gives NaN.
+ *   - The bars, fp64 values on the given S, gf, uf, for every element with a finite S (csrc/hgemm_dgated.hpp and hgemm_act.hpp derive them):
+ *       |du - act*(gf) S|      <= 1/2 ulp_bf16(.) + 2^-19 |gf| |S| + 2^-23 |.|
+ *       |dg - S uf act'*(gf)|  <= 1/2 ulp_bf16(.) + 2^-19 |S uf|
+ *     ReLU is defined bit for bit for both outputs.
+ * Scope is bgemm_mi355x_nn_dact's with z replaced by two inputs and C by two outputs: K % 64 == 0, N % 8 == 0, every stride a multiple of
+ * 8, all six pointers 16-byte aligned, (BM ldc + N) 2 and (BM ldz + N) 2 bytes below 2 GiB, M free; anything else is answered by the
+ * reference kernel (status 0, the same semantics).  g and u are each read through a range that ends at that matrix's last valid element.
+ * Refused with HGEMM_ERR_BAD_ARG: any NULL of the six pointers, dg == du, an output equal to g or u (no in-place form), ldz < N, ldc < N, a
+ * bad id, any other act.
+ * The table, ids, names, plan (hgemm_mi355x_nn_plan(M, N, K)), workspace size and reserve call are hgemm_mi355x_nn_*'s, the splits word
+ * and HGEMM_PLAN_NT_STORE (both outputs) bgemm_mi355x_launch_nn_dact's; a captured split call without a workspace runs unsplit, status 0,
+ * and allocates nothing.
+ * Out of scope: a forward that writes H and [g|u] in one call, a bias gradient inside this call, in-place operation, fp16. */
+/* planned, contiguous (lda = K, ldb = ldz = ldc = N) */
+int bgemm_mi355x_nn_dgated(const void* a, const void* b, const void* g, const void* u, void* dg, void* du, int M, int N, int K, int act,
+                           void* stream);
+int bgemm_mi355x_launch_nn_dgated(int nn_config, int splits, const void* a, const void* b, const void* g, const void* u, void* dg, void* du,
+                                  int M, int N, int K, int lda, int ldb, int ldz, int ldc, int act, void* stream);
+/* bgemm_mi355x_nn_dact_runs(nn_config, M, N, K, lda, ldb, ldc, ldz): the second input and output change no scope (note the order of the
+ * last two arguments here) */
+int bgemm_mi355x_nn_dgated_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldz, int ldc);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
