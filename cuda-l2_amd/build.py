@@ -55,6 +55,7 @@ LIB_SOURCES = [
     "hgemm_inst_g17.hip",
     "hgemm_inst_g18.hip",
     "hgemm_inst_g19.hip",
+    "hgemm_inst_g20.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -496,6 +496,9 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // dgated (bgemm_mi355x_nn_dgated, family n only, with dact): the gated layer's input gradient -- two saved 16-bit inputs g (= z) and u at ldz,
 // two 16-bit outputs dg (= c) and du at ldc, hgemm_dgated.hpp's dgated_store on the finished sum --, the kinds TR_C16_DGATED + act
 // (HGEMM_ACT_SILU included) and the ids EPI_C16_DGATED + act.  The dact call's plan in everything but those ids.
+// gaux (bgemm_mi355x_tn_gated_aux, with gated): the gated call with the rounded pre-activations as two more 16-bit outputs g_out (= z) and
+// u_out, both at row stride ldz with z_out's rules; the kinds TR_C16_GATED_AUX + act and the ids EPI_C16_GATED_AUX + act.  The gated call's
+// plan in everything but those ids.
 struct TrOut {
   bool c32, accumulate;
   bool bias = false;
@@ -505,13 +508,14 @@ struct TrOut {
   bool dbias = false, db_acc = false;
   bool gated = false;
   bool dgated = false;   // with dact: two saved matrices in (z = g, and u) and two outputs (c = dg, and du); the dact call's plan
+  bool gaux = false;     // with gated: two more outputs (z = g_out, and u_out) at ldz; the gated call's plan
   int elem_bytes() const { return c32 ? 4 : 2; }
-  bool has_z() const { return aux || dact; }
+  bool has_z() const { return aux || dact || gaux; }
   bool has_epi() const { return bias || dact || gated; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
   TrKind kind() const {   // the kernel set's cell in TrRow / TrTable
-    return dgated ? (TrKind)(TR_C16_DGATED + act) : gated ? (TrKind)(TR_C16_GATED + act) : dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
+    return dgated ? (TrKind)(TR_C16_DGATED + act) : gaux ? (TrKind)(TR_C16_GATED_AUX + act) : gated ? (TrKind)(TR_C16_GATED + act) : dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
   }
-  int epi_bias() const { return (dgated ? EPI_C16_DGATED : gated ? EPI_C16_GATED : dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
+  int epi_bias() const { return (dgated ? EPI_C16_DGATED : gaux ? EPI_C16_GATED_AUX : gated ? EPI_C16_GATED : dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
 };
 constexpr TrOut kOutC16{false, false};
 constexpr TrOut kOutC16Bias{false, false, true};
@@ -521,10 +525,11 @@ static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIA
               "a kind per activation, four times");
 constexpr bool act_known(int act) { return act == HGEMM_ACT_RELU || act == HGEMM_ACT_GELU || act == HGEMM_ACT_GELU_TANH; }
 static_assert(HGEMM_ACT_SILU == ACT_SILU && TR_C16_GATED + 1 == TR_KINDS && TR_C16_GATED + ACT_SILU == TR_C16_DGATED &&
-              TR_C16_DGATED + ACT_SILU + 1 == TR_KINDS_ALL && !act_known(HGEMM_ACT_SILU),
-              "the gated kinds and the dgated kinds follow; SiLU is theirs alone");
+              TR_C16_DGATED + ACT_SILU == TR_C16_GATED_AUX && TR_C16_GATED_AUX + ACT_SILU + 1 == TR_KINDS_ALL && !act_known(HGEMM_ACT_SILU),
+              "the gated kinds, the dgated kinds and the gated aux kinds follow; SiLU is theirs alone");
 constexpr bool act_known_gated(int act) { return act_known(act) || act == HGEMM_ACT_SILU; }
 constexpr TrOut out_gated(int act) { return TrOut{false, false, false, act, false, false, 0, false, false, true}; }   // (act_known_gated(act) checked by the caller)
+constexpr TrOut out_gated_aux(int act, int ldz) { return TrOut{false, false, false, act, false, false, ldz, false, false, true, false, true}; }
 constexpr TrOut out_bias_act(int act) { return TrOut{false, false, true, act}; }   // (act_known(act) checked by the caller)
 constexpr TrOut out_bias_act_aux(int act, int ldz) { return TrOut{false, false, true, act, true, false, ldz}; }
 constexpr TrOut out_dact(int act, int ldz) { return TrOut{false, false, false, act, false, true, ldz}; }
@@ -706,17 +711,20 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 // (out.dgated: z = g as in a dact call; the second input u travels as `bias` and the second output du as `bias2`, both required, with z's
 // and c's rules; no output may be the other output or an input.  They reach the combine and the reference kernel under those names and the
 // member's kernel behind its GemmArgs, in a DgatedArgs (hgemm_kernel_nn.hpp).)
+// (out.gaux: a gated call with z = g_out and `z2` = u_out, both required, each distinct from c and from the other, with z_out's rules.  They
+// reach the combine and the reference kernel as a GatedAuxOut pair behind `z` and the member's kernel in a GatedAuxArgs.)
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
               int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr, float* db32 = nullptr, const void* b2 = nullptr,
-              const void* bias2 = nullptr) {
+              const void* bias2 = nullptr, void* z2 = nullptr) {
   DisarmTiming disarm_timing;
   if (!a || !b || !c || (out.bias && !bias) || (out.gated && !b2) || (out.has_z() && (!z || z == c)) || (out.dbias && !db32) || M <= 0 || N <= 0 || K <= 0)
     return HGEMM_ERR_BAD_ARG;
   if (out.dgated && (!bias || !bias2 || bias2 == c || bias2 == z || bias2 == bias || c == bias)) return HGEMM_ERR_BAD_ARG;
+  if (out.gaux && (!z2 || z2 == c || z2 == z)) return HGEMM_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   const bool aligned = L.path_ok(out, a, b, c, M, N, K, lda, ldb, ldc) && !(out.bias && ((uintptr_t)bias & 15)) && !(out.has_z() && ((uintptr_t)z & 15)) &&
                        !(out.gated && (((uintptr_t)b2 | (uintptr_t)bias | (uintptr_t)bias2) & 15)) &&   // (a null bias is aligned)
-                       !(out.dgated && (((uintptr_t)bias | (uintptr_t)bias2) & 15));
+                       !(out.dgated && (((uintptr_t)bias | (uintptr_t)bias2) & 15)) && !(out.gaux && ((uintptr_t)z2 & 15));
   unsigned ruled_out = 0;
   LaunchPlan p = tr_resolve(L, elem, out, config, splits_arg, aligned, M, N, K, lda, ldb, ldc, ruled_out);
   float* slabs = nullptr; unsigned* counters = nullptr;
@@ -732,12 +740,16 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
   if (p.status != HGEMM_OK) return p.status;
   const TrKernels& kern = L.t.kernels[elem][out.kind()];
   const TrLaunch launch = L.t.rows[config].launch[elem][out.kind()];
+  // out.gaux alone: what the combine and the reference kernel are handed in the `z` slot, a HOST address that the policy's make() reads
+  // before the launch call returns (launch_combine / launch_reference, hgemm_registry.hip); it lives to the end of this function.  Unused
+  // by every other kind, whose `z` is the device pointer itself.
+  const GatedAuxOut gaux_out{z, z2};
   for (int i = 0; i < p.n; ++i) {
     GemmArgs& g = p.d[i].g;
     g.A = (const f16*)a; g.Bt = (const f16*)b; g.C = (f16*)c;   // (bf16 travels in the same fields: the kernels of its Cfgs reinterpret)
     if (p.d[i].epi != EPI_C16) g.partial = slabs;
     if (out.bias && p.d[i].epi == out.epi_bias()) g.counters = (unsigned*)const_cast<void*>(bias);   // read-only there: the kernel's bf16 bias vector
-    if (out.has_z() && p.d[i].thunk == THUNK_ENTRY &&
+    if (out.has_z() && !out.gaux && p.d[i].thunk == THUNK_ENTRY &&
         (p.d[i].epi == out.epi_bias() || (out.dbias && p.d[i].epi == EPI_C16_DACT_DBIAS + out.act))) {   // the member's own kernel, never a slab kernel
       if (out.aux) g.partial = (float*)z; else g.counters = (unsigned*)z;              // (read-only in the dact kernels)
       g.tail_first = out.ldz;
@@ -745,7 +757,13 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
     switch (p.d[i].thunk) {
       case THUNK_ENTRY:
-        if (out.gated) {   // the gated sets' launchers are handed a GatedArgs (hgemm_kernel_tn_gated.hpp)
+        if (out.gaux) {   // the gated aux sets' launchers are handed a GatedAuxArgs (hgemm_kernel_tn_gated.hpp)
+          GatedAuxArgs ga;
+          static_cast<GemmArgs&>(ga) = g;
+          ga.Bu = (const __bf16*)b2; ga.bias_g = (const __bf16*)bias; ga.bias_u = (const __bf16*)bias2;
+          ga.G = (__bf16*)z; ga.U = (__bf16*)z2; ga.ldz = out.ldz;
+          launch(ga, p.d[i].grid, s, p.d[i].epi, ts);
+        } else if (out.gated) {   // the gated sets' launchers are handed a GatedArgs (hgemm_kernel_tn_gated.hpp)
           GatedArgs ga;
           static_cast<GemmArgs&>(ga) = g;
           ga.Bu = (const __bf16*)b2; ga.bias_g = (const __bf16*)bias; ga.bias_u = (const __bf16*)bias2;
@@ -762,8 +780,8 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
       case THUNK_COLSUM_BLOCKED: launch_colsum_blocked(c, slabs + p.colsum_off / sizeof(float), M, N, ldc, s, ts); break;
       case THUNK_COLSUM_FINISH: launch_colsum_finish(slabs + p.colsum_off / sizeof(float), db32, g.items, N, out.db_acc, s, ts); break;
       case THUNK_COLSUM_DIRECT: launch_colsum_direct(c, db32, M, N, ldc, out.db_acc, s, ts); break;
-      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, bias, bias2, z, M, N, ldc, out.ldz, g.splits, out.accumulate, s, ts); break;
-      default: kern.reference(a, b, b2, c, bias, bias2, z, M, N, K, lda, ldb, ldc, out.ldz, out.accumulate, s, ts); break;
+      case THUNK_SPLITK_REDUCE: kern.combine(g.partial, c, bias, bias2, out.gaux ? (void*)&gaux_out : z, M, N, ldc, out.ldz, g.splits, out.accumulate, s, ts); break;
+      default: kern.reference(a, b, b2, c, bias, bias2, out.gaux ? (void*)&gaux_out : z, M, N, K, lda, ldb, ldc, out.ldz, out.accumulate, s, ts); break;
     }
   }
   hipError_t err = hipGetLastError();
@@ -1273,6 +1291,42 @@ int bgemm_mi355x_tn_gated(const void* a, const void* wg_col_major, const void* w
   int cfg, splits;
   tr_model_plan(kLayoutTN, M, 2 * N, K, &cfg, &splits);
   return bgemm_mi355x_launch_tn_gated(cfg, splits, a, wg_col_major, wu_col_major, bias_g, bias_u, c, M, N, K, K, K, N, act, stream);
+}
+// ---- the gated forward product's training form (the kinds TR_C16_GATED_AUX + act): the call above with g_out = bf16(g) and u_out = bf16(u)
+// as two more outputs, both [M][ldz]; the activation and the gate read the unrounded g and u, so C is the gated call's C bit for bit.  Plan,
+// workspace and reserve call are the gated call's.
+int bgemm_mi355x_tn_gated_aux_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz) {
+  return tr_runs(kLayoutTN, TR_BF16, out_gated_aux(HGEMM_ACT_RELU, ldz), tn_config, M, N, K, lda, ldb, ldc);
+}
+int bgemm_mi355x_launch_tn_gated_aux(int tn_config, int splits_arg, const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g,
+                                     const void* bias_u, void* c, void* g_out, void* u_out, int M, int N, int K, int lda, int ldb, int ldc, int ldz, int act,
+                                     void* stream) {
+  if (!act_known_gated(act) || !g_out || !u_out) return HGEMM_ERR_BAD_ARG;
+  return tr_launch(kLayoutTN, TR_BF16, out_gated_aux(act, ldz), tn_config, splits_arg, a, wg_col_major, bias_g, c, M, N, K, lda, ldb, ldc, stream, g_out, nullptr,
+                   wu_col_major, bias_u, u_out);
+}
+int bgemm_mi355x_tn_gated_aux(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c, void* g_out,
+                              void* u_out, int M, int N, int K, int act, void* stream) {
+  if (!act_known_gated(act) || M <= 0 || N <= 0 || K <= 0 || N >= (1 << 30)) return HGEMM_ERR_BAD_ARG;   // (2 N is an int)
+  int cfg, splits;
+  tr_model_plan(kLayoutTN, M, 2 * N, K, &cfg, &splits);
+  return bgemm_mi355x_launch_tn_gated_aux(cfg, splits, a, wg_col_major, wu_col_major, bias_g, bias_u, c, g_out, u_out, M, N, K, K, K, N, N, act, stream);
+}
+// (the gated hook's output; operands & 4: g_out and u_out are 16-byte aligned too)
+int bgemm_mi355x_selfcheck_launch_tn_gated_aux(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                                               int ruled_out, int act, long long out[20]) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, out_gated_aux(act, ldz), tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_nn_gated_aux(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                                               int ruled_out, int act, long long out[20]) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_gated_aux(act, ldz), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_ta_gated_aux(int ta_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldz,
+                                               int ruled_out, int act, long long out[20]) {
+  if (!act_known_gated(act)) return HGEMM_ERR_BAD_ARG;
+  return tr_selfcheck_launch(kLayoutTA, TR_BF16, out_gated_aux(act, ldz), ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 // (bgemm_mi355x_selfcheck_launch_tn_bias_act's output; operands & 4: a, both weights, c and every non-NULL bias are 16-byte aligned.  The NN
 // and TA twins show the refusal.)

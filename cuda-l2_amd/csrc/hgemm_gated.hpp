@@ -64,4 +64,26 @@ HGEMM_GATED_HD float gated_mul(float a, float u) {
   return a * u;
 }
 
+
+// the view of a member that hgemm_tr_store_c16.inc sees in the gated kernels: the wave tile's OUTPUT columns
+template <class MEMBER>
+struct GatedOutView {
+  static constexpr int TM = MEMBER::TM, TN = MEMBER::TN / 2;
+};
+// acc[i][J0 + j] under the name acc[i][j]: what that text sees of the up half of the accumulators (V: the lane's quad type; the indices are
+// constants after unrolling, so on the device this is a renaming of registers)
+template <class V, int FM, int FN_ALL, int J0>
+struct GatedFragView {
+  V (&a)[FM][FN_ALL];
+  HGEMM_GATED_HD const V* operator[](int i) const { return &a[i][J0]; }
+};
+
+// bgemm_mi355x_tn_gated_aux: the fp32 pre-activation of one half, the finished sum plus its bias as ONE fp32 add -- the value that g_out /
+// u_out round to bf16 (round to nearest even, the conversion to __bf16, once) and that the activation and the gate read UNROUNDED.  The
+// text of the kernel's in-place add, of the combine's and the reference kernel's policy and of the CPU programs.
+HGEMM_GATED_HD float gated_pre(float sum, float bias) {
+  HGEMM_GATED_NO_CONTRACT
+  return sum + bias;
+}
+
 }  // namespace hgemm_mi355x

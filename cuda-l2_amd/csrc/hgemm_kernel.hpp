@@ -317,6 +317,10 @@ constexpr int EPI_C16_GATED = 64;
 // The gated MLP's input gradient (family n, bgemm_mi355x_nn_dgated): dU = bf16(act(g) x acc), dG = bf16(acc x u x act'(g)), g and u the saved
 // bf16 pre-activations (hgemm_dgated.hpp).  EPI_C16_DGATED + the activation's id, HGEMM_ACT_SILU included: 97 .. 100, neither flag bit set.
 constexpr int EPI_C16_DGATED = 96;
+// The gated forward product that also writes the rounded pre-activations (family f, bgemm_mi355x_tn_gated_aux): g_out = bf16(g), u_out =
+// bf16(u) and C = bf16(act(g) x u), g and u unrounded (hgemm_kernel_tn_gated.hpp).  EPI_C16_GATED_AUX + the activation's id: 129 .. 132,
+// neither flag bit set.
+constexpr int EPI_C16_GATED_AUX = 128;
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

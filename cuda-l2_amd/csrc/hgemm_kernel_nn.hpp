@@ -221,6 +221,19 @@ struct GatedArgs : GemmArgs {
   const __bf16* bias_g;
   const __bf16* bias_u;
 };
+// The same for the sets that also write the pre-activations (bgemm_mi355x_tn_gated_aux): behind the GatedArgs the two more bf16 outputs
+// and their one row stride.  GatedArgs keeps its size and every kernarg offset too; the slab launcher of those sets reads the GatedArgs in it.
+struct GatedAuxArgs : GatedArgs {
+  __bf16* G;
+  __bf16* U;
+  int ldz;
+};
+// What the combine and the reference kernel of those sets are handed as `z` (TrKernels below has no slot for a third output): the address
+// of this pair on the HOST, read by the policy's make() in front of the launch; the pointers travel to the device inside the policy.
+struct GatedAuxOut {
+  void* g_out;
+  void* u_out;
+};
 
 // The members of both families, smallest tile first, and what is made of them: X(args ..., BM, BN, WM, WN, NBUF) per member.
 //   HGEMM_TR_INST(CFG, C32)    a unit's one line: the explicit instantiation of a kernel set's launchers, and with them its kernels
@@ -302,7 +315,9 @@ enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_
               // TR_C16_GATED + a (a = 1 .. 4, ACT_SILU included): the gated product (family f: bgemm_mi355x_tn_gated).  TR_KINDS keeps counting
               // the kinds with one sum per output; the tables hold TR_KINDS_ALL cells.
               // TR_C16_DGATED + a (a = 1 .. 4): the gated MLP's input gradient (family n: bgemm_mi355x_nn_dgated), one sum, two outputs.
-              TR_C16_GATED = 14, TR_C16_DGATED = 18, TR_KINDS_ALL = 23 };
+              // TR_C16_GATED_AUX + a (a = 1 .. 4): the gated product with the rounded pre-activations as two more outputs (family f:
+              // bgemm_mi355x_tn_gated_aux), two sums, three outputs.
+              TR_C16_GATED = 14, TR_C16_DGATED = 18, TR_C16_GATED_AUX = 22, TR_KINDS_ALL = 27 };
 struct TrRow {
   TrEntry e;
   TrLaunch launch[2][TR_KINDS_ALL];   // [TrElem][TrKind]
@@ -314,6 +329,7 @@ struct TrRow {
 // other set is handed nullptr and ignores them.  The slabs of a gated set are [splits][M][2 N] (hgemm_gated.hpp).  The TR_C16_DGATED sets
 // have two inputs and two outputs besides the operands and use the same four: `z` = g and `bias` = u (inputs, both at ldz), `c` = dg and
 // `bias2` = du (outputs, both at ldc; the set writes through that one pointer, const in the signature for every other kind's sake).
+// The TR_C16_GATED_AUX sets are the gated sets with `z` = the address of a host-side GatedAuxOut (g_out and u_out, both at ldz).
 struct TrKernels {
   void (*combine)(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
                   bool accumulate, hipStream_t, TimingSlot);

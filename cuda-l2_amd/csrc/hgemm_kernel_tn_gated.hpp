@@ -19,23 +19,101 @@
 //     hgemm_tr_store_c16.inc's convert-and-swap and 16-byte stores; one (BN = 64) is stored as the lane's four columns, 8 bytes.
 //   * ACT = ACT_NONE: the K slice of a two-pass plan; the fp32 sums go to the slab as gated_slab_index has it, nothing applied.
 //   * Scope (the host sends anything else to the reference kernel): family f's, with (BN / 2 ldb + K) 2 bytes below 2 GiB per weight.
-#pragma once
+// This header includes ITSELF, as hgemm_kernel_nn.hpp does: the device text of the kernel stands at the end of the file, behind the include
+// guard, under HGEMM_TN_GATED_KERNEL_TEXT, and each of the two entry points (hgemm_tn_gated_kernel, hgemm_tn_gated_aux_kernel) includes the
+// file once more with that macro set.  Hence a guard and no `#pragma once`.
+//   * hgemm_tn_gated_aux_kernel (bgemm_mi355x_tn_gated_aux, unit g20): the same text behind a GatedAuxArgs, AUX = true.  Behind the bias
+//     loads the biases are added IN PLACE (acc[i][jo] = g, acc[i][jo + OFN] = u, the fp32 adds of the gate pass), g_out = bf16(g) and
+//     u_out = bf16(u) are stored from those through hgemm_tn_gated_store.inc (acc only read), then the gate pass runs on the unrounded
+//     values and C is stored: three outputs, each rounded once, no register beyond the gated kernel's.
+#ifndef HGEMM_KERNEL_TN_GATED_HPP
+#define HGEMM_KERNEL_TN_GATED_HPP
 
 #include "hgemm_gated.hpp"
 #include "hgemm_kernel_tn.hpp"
 
 namespace hgemm_mi355x {
 
-// the view of a member that hgemm_tr_store_c16.inc sees in the gated kernel: the wave tile's OUTPUT columns
-template <class MEMBER>
-struct GatedOutView {
-  static constexpr int TM = MEMBER::TM, TN = MEMBER::TN / 2;
-};
+
+// What the text reads the aux call's two outputs and their stride through: the GatedArgs overloads are never called (the text names them
+// where AUX holds alone) and let the one text compile for both entry points.
+__device__ __forceinline__ __bf16* tn_gated_aux_g(const GatedArgs&) { return nullptr; }
+__device__ __forceinline__ __bf16* tn_gated_aux_u(const GatedArgs&) { return nullptr; }
+__device__ __forceinline__ int tn_gated_aux_ldz(const GatedArgs&) { return 0; }
+__device__ __forceinline__ __bf16* tn_gated_aux_g(const GatedAuxArgs& g) { return g.G; }
+__device__ __forceinline__ __bf16* tn_gated_aux_u(const GatedAuxArgs& g) { return g.U; }
+__device__ __forceinline__ int tn_gated_aux_ldz(const GatedAuxArgs& g) { return g.ldz; }
 
 template <class MEMBER, int ACT>
 __global__ void __launch_bounds__(MEMBER::THREADS) hgemm_tn_gated_kernel(const GatedArgs g) {
   prefetch_kernargs<sizeof(GatedArgs)>();
 #if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool AUX = false;
+#define HGEMM_TN_GATED_KERNEL_TEXT
+#include "hgemm_kernel_tn_gated.hpp"   // the kernel text at the end of this file
+#undef HGEMM_TN_GATED_KERNEL_TEXT
+#endif  // __HIP_DEVICE_COMPILE__
+}
+// the same text behind a GatedAuxArgs: the kernels that also write g_out and u_out (hgemm_inst_g20.hip)
+template <class MEMBER, int ACT>
+__global__ void __launch_bounds__(MEMBER::THREADS) hgemm_tn_gated_aux_kernel(const GatedAuxArgs g) {
+  static_assert(ACT >= ACT_RELU && ACT <= ACT_SILU, "the four activations; the K slices of a two-pass form are hgemm_tn_gated_kernel<., ACT_NONE>");
+  prefetch_kernargs<sizeof(GatedAuxArgs)>();
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool AUX = true;
+#define HGEMM_TN_GATED_KERNEL_TEXT
+#include "hgemm_kernel_tn_gated.hpp"   // the kernel text at the end of this file
+#undef HGEMM_TN_GATED_KERNEL_TEXT
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
+// ---- host side: the gated sets, one per activation.  TrLaunch's signature; `g` is the base of a GatedArgs (see there).  The K slices of a
+// two-pass form are the gated slab kernel (ACT_NONE), instantiated with the ReLU set alone and reached from the others through it.
+template <class CFG>
+void launch_tn_gated_slab(const GemmArgs& g, int grid, hipStream_t stream, TimingSlot ts) {
+  HGEMM_LAUNCH((hgemm_tn_gated_kernel<CFG, ACT_NONE>), grid, CFG::THREADS, stream, ts, static_cast<const GatedArgs&>(g));
+}
+template <class CFG, int ACT>
+void launch_tn_gated(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tn_gated_slab<CFG>(g, grid, stream, ts);
+  HGEMM_LAUNCH((hgemm_tn_gated_kernel<CFG, ACT>), grid, CFG::THREADS, stream, ts, static_cast<const GatedArgs&>(g));
+}
+#define HGEMM_TN_GATED_SLAB_LAUNCHER(CFG, BM, BN, WM, WN, NB) launch_tn_gated_slab<CFG<BM, BN, WM, WN, NB>>
+#define HGEMM_TN_GATED_SLAB_INST(...) template void HGEMM_TN_GATED_SLAB_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, TimingSlot);
+#define HGEMM_TN_GATED_SLAB_EXTERN(...) extern HGEMM_TN_GATED_SLAB_INST(__VA_ARGS__)
+#define HGEMM_TN_GATED_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_tn_gated<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_TN_GATED_INST(...) template void HGEMM_TN_GATED_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TN_GATED_EXTERN(...) extern HGEMM_TN_GATED_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_SLAB_EXTERN, CfgTNB)             // hgemm_inst_g18.hip
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_RELU, CfgTNB)
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_GELU, CfgTNB)
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_GELU_TANH, CfgTNB)
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_SILU, CfgTNB)
+
+// The sets that also write the pre-activations (bgemm_mi355x_tn_gated_aux), one per activation: `g` is the base of a GatedAuxArgs; the K
+// slices of a two-pass form are unit g18's slab kernels, which read the GatedArgs in it.
+template <class CFG, int ACT>
+void launch_tn_gated_aux(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tn_gated_slab<CFG>(g, grid, stream, ts);
+  HGEMM_LAUNCH((hgemm_tn_gated_aux_kernel<CFG, ACT>), grid, CFG::THREADS, stream, ts, static_cast<const GatedAuxArgs&>(g));
+}
+#define HGEMM_TN_GATED_AUX_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_tn_gated_aux<CFG<BM, BN, WM, WN, NB>, ACT>
+#define HGEMM_TN_GATED_AUX_INST(...) template void HGEMM_TN_GATED_AUX_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TN_GATED_AUX_EXTERN(...) extern HGEMM_TN_GATED_AUX_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_AUX_EXTERN, ACT_RELU, CfgTNB)    // hgemm_inst_g20.hip
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_AUX_EXTERN, ACT_GELU, CfgTNB)
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_AUX_EXTERN, ACT_GELU_TANH, CfgTNB)
+HGEMM_TR_MEMBERS(HGEMM_TN_GATED_AUX_EXTERN, ACT_SILU, CfgTNB)
+
+}  // namespace hgemm_mi355x
+
+#endif  // HGEMM_KERNEL_TN_GATED_HPP
+
+// ---- the device text of family f's gated kernel: the statements of hgemm_tn_gated_kernel<MEMBER, ACT>(const GatedArgs g) and of
+// hgemm_tn_gated_aux_kernel<MEMBER, ACT>(const GatedAuxArgs g) behind their kernarg prefetch and their `constexpr bool AUX`, included by
+// both (see the head of the file).  A text and not a function for hgemm_tr_store_c16.inc's reason: included, every kernel of
+// hgemm_tn_gated_kernel compiles to the stream it had when the text stood in its braces.
+#ifdef HGEMM_TN_GATED_KERNEL_TEXT
   constexpr int BM = MEMBER::BM, BN = MEMBER::BN, NBUF = MEMBER::NBUF, TN = MEMBER::TN;
   constexpr int FM = MEMBER::FM, NW = MEMBER::NW, NJ = MEMBER::NJ, NJ_A = MEMBER::NJ_A;
   constexpr int FN_ALL = MEMBER::FN, OFN = FN_ALL / 2;   // column fragments of the image; output fragments of a wave
@@ -163,6 +241,26 @@ __global__ void __launch_bounds__(MEMBER::THREADS) hgemm_tn_gated_kernel(const G
       bg[jo] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsBiasG, n_b * 2u, 0, 0));
       bu[jo] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsBiasU, n_b * 2u, 0, 0));
     }
+    if constexpr (AUX) {
+      // ---- the pre-activations as two more outputs (bgemm_mi355x_tn_gated_aux): the gate pass's two fp32 adds made in place, then
+      // g_out = bf16(g) from acc[i][jo] and u_out = bf16(u) from acc[i][jo + OFN], each at stride ldz; acc is only read by the stores,
+      // so the gate pass below works on the unrounded values
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int jo = 0; jo < OFN; ++jo)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            acc[i][jo][e] = gated_pre(acc[i][jo][e], (float)bg[jo][e]);
+            acc[i][jo + OFN][e] = gated_pre(acc[i][jo + OFN][e], (float)bu[jo][e]);
+          }
+#define HGEMM_GATED_STORE_OUTPUT 0
+#include "hgemm_tn_gated_store.inc"
+#undef HGEMM_GATED_STORE_OUTPUT
+#define HGEMM_GATED_STORE_OUTPUT 1
+#include "hgemm_tn_gated_store.inc"
+#undef HGEMM_GATED_STORE_OUTPUT
+    }
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -170,61 +268,20 @@ __global__ void __launch_bounds__(MEMBER::THREADS) hgemm_tn_gated_kernel(const G
         __builtin_amdgcn_sched_barrier(0);   // hgemm_kernel_tn.hpp's register steering: a quad's temporaries at a time
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float gv = acc[i][jo][e] + (float)bg[jo][e];
-          const float uv = acc[i][jo + OFN][e] + (float)bu[jo][e];
+          float gv, uv;
+          if constexpr (AUX) {
+            gv = acc[i][jo][e];
+            uv = acc[i][jo + OFN][e];
+          } else {
+            gv = acc[i][jo][e] + (float)bg[jo][e];
+            uv = acc[i][jo + OFN][e] + (float)bu[jo][e];
+          }
           float y = gated_mul(act_apply<ACT>(gv), uv);
           asm volatile("" : "+a"(y));   // the finished value waits in an accumulation register for the stores
           acc[i][jo][e] = y;
         }
       }
 
-    if constexpr (OFN >= 2) {
-      // two output fragments per wave: the family's 16-bit C epilogue over acc[i][0 .. OFN - 1]
-      constexpr int FN = OFN;
-      using CFG = GatedOutView<MEMBER>;
-#include "hgemm_tr_store_c16.inc"
-    } else {
-      // one output fragment per wave: the lane's four columns, one 8-byte buffer store; the NT hint an instruction of its own
-      using h2 = __attribute__((ext_vector_type(2))) elem;
-      const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(g.C + (size_t)tc.m0 * g.ldc), 0, 0xFFFFFFFFu, 0x00020000);
-      const int n = tc.n0 + gated_lane_col(wave_n, TN, 0, lane, 0);
-#pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        const int row = dbias_row(wave_m, MEMBER::TM, i, lane);
-        const h2 y01 = {(elem)acc[i][0][0], (elem)acc[i][0][1]}, y23 = {(elem)acc[i][0][2], (elem)acc[i][0][3]};
-        if (tc.m0 + row < g.M && n < g.N) {
-          const u32x2 o = {__builtin_bit_cast(unsigned, y01), __builtin_bit_cast(unsigned, y23)};
-          const uint32_t off = ((uint32_t)row * (uint32_t)g.ldc + (uint32_t)n) * 2u;
-          if (g.flags & ARG_NT_STORE) __builtin_amdgcn_raw_buffer_store_b64(o, rsC, off, 0, 2);
-          else                        __builtin_amdgcn_raw_buffer_store_b64(o, rsC, off, 0, 0);
-        }
-      }
-    }
+#include "hgemm_tn_gated_store.inc"   // C: the bf16 store of the gated kernels, one text for the three outputs
   }
-#endif  // __HIP_DEVICE_COMPILE__
-}
-
-// ---- host side: the gated sets, one per activation.  TrLaunch's signature; `g` is the base of a GatedArgs (see there).  The K slices of a
-// two-pass form are the gated slab kernel (ACT_NONE), instantiated with the ReLU set alone and reached from the others through it.
-template <class CFG>
-void launch_tn_gated_slab(const GemmArgs& g, int grid, hipStream_t stream, TimingSlot ts) {
-  HGEMM_LAUNCH((hgemm_tn_gated_kernel<CFG, ACT_NONE>), grid, CFG::THREADS, stream, ts, static_cast<const GatedArgs&>(g));
-}
-template <class CFG, int ACT>
-void launch_tn_gated(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
-  if (epi == EPI_SLAB) return launch_tn_gated_slab<CFG>(g, grid, stream, ts);
-  HGEMM_LAUNCH((hgemm_tn_gated_kernel<CFG, ACT>), grid, CFG::THREADS, stream, ts, static_cast<const GatedArgs&>(g));
-}
-#define HGEMM_TN_GATED_SLAB_LAUNCHER(CFG, BM, BN, WM, WN, NB) launch_tn_gated_slab<CFG<BM, BN, WM, WN, NB>>
-#define HGEMM_TN_GATED_SLAB_INST(...) template void HGEMM_TN_GATED_SLAB_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, TimingSlot);
-#define HGEMM_TN_GATED_SLAB_EXTERN(...) extern HGEMM_TN_GATED_SLAB_INST(__VA_ARGS__)
-#define HGEMM_TN_GATED_LAUNCHER(ACT, CFG, BM, BN, WM, WN, NB) launch_tn_gated<CFG<BM, BN, WM, WN, NB>, ACT>
-#define HGEMM_TN_GATED_INST(...) template void HGEMM_TN_GATED_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
-#define HGEMM_TN_GATED_EXTERN(...) extern HGEMM_TN_GATED_INST(__VA_ARGS__)
-HGEMM_TR_MEMBERS(HGEMM_TN_GATED_SLAB_EXTERN, CfgTNB)             // hgemm_inst_g18.hip
-HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_RELU, CfgTNB)
-HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_GELU, CfgTNB)
-HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_GELU_TANH, CfgTNB)
-HGEMM_TR_MEMBERS(HGEMM_TN_GATED_EXTERN, ACT_SILU, CfgTNB)
-
-}  // namespace hgemm_mi355x
+#endif  // HGEMM_TN_GATED_KERNEL_TEXT

@@ -225,6 +225,37 @@ struct OutGated {
   }
 };
 
+// the same with the rounded pre-activations as two more outputs (bgemm_mi355x_tn_gated_aux): g_out = bf16(g) and u_out = bf16(u), both at
+// stride ldz, and C = bf16(act_apply<ACT>(g) * u) of the UNROUNDED g and u (gated_pre, hgemm_gated.hpp) -- three stores, each value rounded
+// once.  TrKernels' signatures have no slot for a third output: `z` is the address of a host-side GatedAuxOut, which make() reads on the
+// host; the two pointers travel in the policy, as Wu does.
+template <int ACT>
+struct OutGatedAux {
+  static constexpr int SUMS = 2;
+  __bf16* C; const __bf16* Wu; const __bf16* bias_g; const __bf16* bias_u; __bf16* G; __bf16* U; int ldc, ldz;
+  static OutGatedAux make(const OutArgs& o) {
+    const GatedAuxOut* z = (const GatedAuxOut*)o.z;
+    return {(__bf16*)o.c, (const __bf16*)o.b2, (const __bf16*)o.bias, (const __bf16*)o.bias2, (__bf16*)z->g_out, (__bf16*)z->u_out, o.ldc, o.ldz};
+  }
+  template <int V, class At> __device__ GatedBias<V> early(At at) const {
+    GatedBias<V> b;
+    b.g = (__bf16)0.0f; b.u = (__bf16)0.0f;
+    if (bias_g) b.g = out_load<__bf16, V>(bias_g + at.n());
+    if (bias_u) b.u = out_load<__bf16, V>(bias_u + at.n());
+    return b;
+  }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> sg, vec_t<float, V> su, GatedBias<V> b) const {
+#pragma unroll
+    for (int i = 0; i < V; ++i) { sg[i] = gated_pre(sg[i], (float)b.g[i]); su[i] = gated_pre(su[i], (float)b.u[i]); }
+    const size_t at_z = (size_t)at.m() * ldz + at.n();
+    out_store<V>(G + at_z, sg);
+    out_store<V>(U + at_z, su);
+#pragma unroll
+    for (int i = 0; i < V; ++i) sg[i] = gated_mul(act_apply<ACT>(sg[i]), su[i]);
+    out_store<V>(C + (size_t)at.m() * ldc + at.n(), sg);
+  }
+};
+
 // the gated MLP's input gradient (bgemm_mi355x_nn_dgated): ONE finished sum S = dY Wd, two saved pre-activations read early (G and U, both
 // at ldz) and two outputs (dG and dU, both at ldc): dgated_store (hgemm_dgated.hpp), each value rounded once.  U arrives in the signatures'
 // `bias` and dU in their `bias2`, two pointers this kind has no other use for (hgemm_kernel_nn.hpp: TrKernels).
@@ -472,6 +503,9 @@ static CombineGrid combine_grid(int M, int N) {
   return {grid, threads};
 }
 
+// (Out::make() runs HERE, on the host, in front of the launch, and may READ THROUGH `z`: the gated aux kinds are handed the address of a
+// host-side GatedAuxOut there -- hgemm_kernel_nn.hpp -- and OutGatedAux::make copies the two device pointers out of it.  Every other kind
+// treats `z` as the device pointer it is and only stores it.  The same holds for launch_reference below.)
 template <class Out>
 static void launch_combine(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
                            bool accumulate, hipStream_t stream, TimingSlot ts) {
@@ -563,6 +597,10 @@ static TrRow tn_row(TrEntry e) {
   r.launch[TR_BF16][TR_C16_GATED + ACT_GELU] = &launch_tn_gated<B, ACT_GELU>;
   r.launch[TR_BF16][TR_C16_GATED + ACT_GELU_TANH] = &launch_tn_gated<B, ACT_GELU_TANH>;
   r.launch[TR_BF16][TR_C16_GATED + ACT_SILU] = &launch_tn_gated<B, ACT_SILU>;
+  r.launch[TR_BF16][TR_C16_GATED_AUX + ACT_RELU] = &launch_tn_gated_aux<B, ACT_RELU>;
+  r.launch[TR_BF16][TR_C16_GATED_AUX + ACT_GELU] = &launch_tn_gated_aux<B, ACT_GELU>;
+  r.launch[TR_BF16][TR_C16_GATED_AUX + ACT_GELU_TANH] = &launch_tn_gated_aux<B, ACT_GELU_TANH>;
+  r.launch[TR_BF16][TR_C16_GATED_AUX + ACT_SILU] = &launch_tn_gated_aux<B, ACT_SILU>;
   return r;
 }
 #define HGEMM_TR_ROW(ROW, P, CFG, ...) ROW<__VA_ARGS__>(HGEMM_TR_ENTRY(P, CFG, __VA_ARGS__)),
@@ -621,6 +659,10 @@ const TrTable& tr_table_tn() {
     t.kernels[TR_BF16][TR_C16_GATED + ACT_GELU] = tr_kernels<B, OutGated<ACT_GELU>>();
     t.kernels[TR_BF16][TR_C16_GATED + ACT_GELU_TANH] = tr_kernels<B, OutGated<ACT_GELU_TANH>>();
     t.kernels[TR_BF16][TR_C16_GATED + ACT_SILU] = tr_kernels<B, OutGated<ACT_SILU>>();
+    t.kernels[TR_BF16][TR_C16_GATED_AUX + ACT_RELU] = tr_kernels<B, OutGatedAux<ACT_RELU>>();
+    t.kernels[TR_BF16][TR_C16_GATED_AUX + ACT_GELU] = tr_kernels<B, OutGatedAux<ACT_GELU>>();
+    t.kernels[TR_BF16][TR_C16_GATED_AUX + ACT_GELU_TANH] = tr_kernels<B, OutGatedAux<ACT_GELU_TANH>>();
+    t.kernels[TR_BF16][TR_C16_GATED_AUX + ACT_SILU] = tr_kernels<B, OutGatedAux<ACT_SILU>>();
     return t;
   }();
   return table;

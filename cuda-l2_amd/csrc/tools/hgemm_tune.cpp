@@ -45,6 +45,9 @@
 //                                                     dact call's, db32 against the fp64 column sum of the C read back -- ReLU bit for bit, the
 //                                                     GELUs inside gamma_(M-1) sum |C| --, accumulate = 1 one fp32 add; bench against
 //                                                     bgemm_mi355x_launch_nn_dact + bgemm_mi355x_colsum_c32 at the same member and splits
+//   hgemm_tune check|bench --layout tn --bf16 --gated-aux relu|gelu|gelu_tanh|silu [...]   bgemm_mi355x_launch_tn_gated_aux: C as --gated judges it,
+//                                                     g_out and u_out bit for bit, sentinel bytes behind each of the three; bench against
+//                                                     bgemm_mi355x_launch_tn_bias on the stacked weight at 2N + the element-wise gate kernel
 //   hgemm_tune check|bench --layout nn --bf16 --dgated relu|gelu|gelu_tanh|silu [...]   bgemm_mi355x_launch_nn_dgated: ReLU bit for bit, the
 //                                                     others inside the two bars of hgemm_dgated.hpp, sentinel bytes behind both outputs; bench
 //                                                     against bgemm_mi355x_launch_nn + an element-wise kernel at the same member and splits
@@ -1045,8 +1048,8 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
 }
 
 // ---- The transposed-read variants: `check --layout nn|ta|tn ...`, `bench --layout nn|ta|tn ...` ------------------------------------------
-// Fourteen call kinds -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias, tn --bf16 --bias --act A,
-// ... --act A --aux, nn --bf16 --dact A, ... --dact A --dbias, tn --bf16 --gated A, nn --bf16 --dgated A --, each one row of kVariants that main resolves once from the flags; the
+// Fifteen call kinds -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias, tn --bf16 --bias --act A,
+// ... --act A --aux, nn --bf16 --dact A, ... --dact A --dbias, tn --bf16 --gated A, nn --bf16 --dgated A, tn --bf16 --gated-aux A --, each one row of kVariants that main resolves once from the flags; the
 // activation A is a run-time value of the call (TrCall::act), not of the row.  ONE check (tr_check) and ONE bench driver (tr_bench) serve
 // them all; a row names what differs: its operand scheme, its judge of one finished run, its closing sentence, its bench description.
 // The check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} (fp32 C: x {store, accumulate}) from NaN-filled outputs.
@@ -1068,12 +1071,13 @@ enum Elem { kF16, kBF16 };
 // db32[N]; act: it takes an activation.
 enum ZRole { kZNone, kZRead, kZWritten };   // no z; Z is an input (dact); z_out is a second output (aux)
 struct OutKind { bool c32, bias; ZRole z; bool db32, act; bool gated = false;       // gated: two weights, two biases (bgemm_mi355x_tn_gated)
-                 bool dgated = false; };   // dgated: two saved matrices in, two 16-bit matrices out (bgemm_mi355x_nn_dgated)
+                 bool dgated = false;      // dgated: two saved matrices in, two 16-bit matrices out (bgemm_mi355x_nn_dgated)
+                 bool gaux = false; };     // gaux (with gated): g_out and u_out as two more 16-bit outputs (bgemm_mi355x_tn_gated_aux)
 static const OutKind kOutC16 = {false, false, kZNone, false, false}, kOutC32 = {true, false, kZNone, false, false},
                      kOutBias = {false, true, kZNone, false, false}, kOutBiasAct = {false, true, kZNone, false, true},
                      kOutBiasAux = {false, true, kZWritten, false, true}, kOutDact = {false, false, kZRead, false, true},
                      kOutDactDbias = {false, false, kZRead, true, true}, kOutGated = {false, false, kZNone, false, true, true},
-                     kOutDgated = {false, false, kZNone, false, true, false, true};
+                     kOutDgated = {false, false, kZNone, false, true, false, true}, kOutGatedAux = {false, false, kZNone, false, true, true, false, true};
 static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh", "silu"};   // silu: --gated alone
 // fp16 values as fp16 or as bf16 bits, ready for upload
 static std::vector<uint16_t> operand_bits(const std::vector<f16>& v, Elem elem) {
@@ -1116,7 +1120,7 @@ static const TrLayout kLayoutTN = {"tn", "the TN kernels", kShapesNN, false, tru
 // accumulate, z, db32, act) its adapter drops.  z: z_out of --aux, Z of --dact; act: HGEMM_ACT_RELU / _GELU / _GELU_TANH
 struct TrCall { const void *a, *b, *bias; void* c; int accumulate; void* z = nullptr; float* db32 = nullptr; int act = 0;
                 const void *b2 = nullptr, *bias2 = nullptr;      // b2, bias2: Wu and bias_u of a gated call, whose b and bias are the gate's
-                void* c2 = nullptr; };   // a dgated call: z = g, b2 = u (both [M][N]), c = dg, c2 = du
+                void* c2 = nullptr; };   // a dgated call: z = g, b2 = u (both [M][N]), c = dg, c2 = du; a gated aux call: z = g_out, c2 = u_out
 template <auto F> static int launch16(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {   // F: a 16-bit-C launch
   return F(cfg, splits, o.a, o.b, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
 }
@@ -1157,6 +1161,15 @@ static int launch_gated(int cfg, int splits, const TrCall& o, const Shape& sh, i
 }
 static int planned_gated(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_gated(o.a, o.b, o.b2, o.bias, o.bias2, o.c, sh.M, sh.N, sh.K, o.act, nullptr); }
 
+// its training form (bgemm_mi355x_tn_gated_aux; separate g_out and u_out, ldz = N)
+static int launch_gated_aux(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_gated_aux(cfg, splits, o.a, o.b, o.b2, o.bias, o.bias2, o.c, o.z, o.c2, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, o.act, nullptr);
+}
+static int planned_gated_aux(const TrCall& o, const Shape& sh) {
+  return bgemm_mi355x_tn_gated_aux(o.a, o.b, o.b2, o.bias, o.bias2, o.c, o.z, o.c2, sh.M, sh.N, sh.K, o.act, nullptr);
+}
+static int gated_aux_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_tn_gated_aux_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+
 // the gated MLP's input gradient (bgemm_mi355x_nn_dgated; ldz = ldc = N throughout)
 static int launch_dgated(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
   return bgemm_mi355x_launch_nn_dgated(cfg, splits, o.a, o.b, o.z, o.b2, o.c, o.c2, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, o.act, nullptr);
@@ -1178,12 +1191,13 @@ static void warm_hipblaslt(bool autotune) {
   if (autotune) hgemm_hipblaslt_autotune_init();
 }
 static void bench_nn(TrBench&), bench_ta(TrBench&), bench_ta_c32(TrBench&), bench_bf16(TrBench&), bench_tn_bf16(TrBench&), bench_tn_bias(TrBench&),
-    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&), bench_tn_gated(TrBench&), bench_nn_dgated(TrBench&);
+    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&), bench_tn_gated(TrBench&), bench_nn_dgated(TrBench&), bench_tn_gated_aux(TrBench&);
 static const BenchDesc kBenchNN = {77, warm_hipblaslt, bench_nn}, kBenchTA = {91, warm_none, bench_ta}, kBenchTAC32 = {91, warm_none, bench_ta_c32},
                        kBenchBF16 = {91, warm_rocblas, bench_bf16}, kBenchTN = {91, warm_rocblas, bench_tn_bf16}, kBenchTNBias = {91, warm_none, bench_tn_bias},
                        kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act}, kBenchTNAux = {91, warm_none, bench_tn_aux},
                        kBenchNNDact = {91, warm_none, bench_nn_dact}, kBenchNNDactDbias = {91, warm_none, bench_nn_dact_dbias},
-                       kBenchTNGated = {91, warm_none, bench_tn_gated}, kBenchNNDgated = {91, warm_none, bench_nn_dgated};
+                       kBenchTNGated = {91, warm_none, bench_tn_gated}, kBenchNNDgated = {91, warm_none, bench_nn_dgated},
+                       kBenchTNGatedAux = {91, warm_none, bench_tn_gated_aux};
 
 // What tr_check is told about one kind (the functions themselves: below, above tr_check).
 struct Check;
@@ -1193,11 +1207,11 @@ struct CheckDesc {
   void (*summary)(const Check&);  // the closing line(s)
 };
 static int operands_zero_one(Check&), operands_small_int(Check&), operands_gated(Check&), judge_exact(Check&), judge_act(Check&), judge_dbias(Check&), judge_gated(Check&),
-           operands_dgated(Check&), judge_dgated(Check&);
-static void summary_exact(const Check&), summary_act(const Check&), summary_gated(const Check&), summary_dgated(const Check&);
+           operands_dgated(Check&), judge_dgated(Check&), judge_gated_aux(Check&);
+static void summary_exact(const Check&), summary_act(const Check&), summary_gated(const Check&), summary_dgated(const Check&), summary_gated_aux(const Check&);
 static const CheckDesc kCheckExact = {operands_zero_one, judge_exact, summary_exact}, kCheckAct = {operands_small_int, judge_act, summary_act},
                        kCheckDbias = {operands_small_int, judge_dbias, summary_act}, kCheckGated = {operands_gated, judge_gated, summary_gated},
-                       kCheckDgated = {operands_dgated, judge_dgated, summary_dgated};
+                       kCheckDgated = {operands_dgated, judge_dgated, summary_dgated}, kCheckGatedAux = {operands_gated, judge_gated_aux, summary_gated_aux};
 
 struct Variant {
   const TrLayout* L;
@@ -1212,7 +1226,7 @@ struct Variant {
   std::string words(const char* layout, const char* sep, int act = 0) const {
     std::string w = std::string(layout) + L->label + (out->c32 ? std::string(sep) + "c32" : "") + (elem == kBF16 ? std::string(sep) + "bf16" : "") +
                     (out->bias ? std::string(sep) + "bias" : "");
-    if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : out->gated ? std::string(sep) + "gated" : out->dgated ? std::string(sep) + "dgated" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
+    if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : out->gaux ? std::string(sep) + "gated-aux" : out->gated ? std::string(sep) + "gated" : out->dgated ? std::string(sep) + "dgated" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
                   (out->db32 ? std::string(sep) + "dbias" : "");
     return w;
   }
@@ -1233,20 +1247,22 @@ static const Variant kVariants[] = {
     {&kLayoutNN, kBF16, &kOutDactDbias, dact_dbias_runs, launch_dact_dbias, planned_dact_dbias, &kCheckDbias, &kBenchNNDactDbias},
     {&kLayoutTN, kBF16, &kOutGated, bgemm_mi355x_tn_gated_runs, launch_gated, planned_gated, &kCheckGated, &kBenchTNGated},
     {&kLayoutNN, kBF16, &kOutDgated, dgated_runs, launch_dgated, planned_dgated, &kCheckDgated, &kBenchNNDgated},
+    {&kLayoutTN, kBF16, &kOutGatedAux, gated_aux_runs, launch_gated_aux, planned_gated_aux, &kCheckGatedAux, &kBenchTNGatedAux},
 };
 // What the command line says of the call; act, dact: 0, or the A of --act A / --dact A as HGEMM_ACT_RELU / _GELU / _GELU_TANH.
 struct TrFlags {
   std::string layout;
   bool bf16 = false, c32 = false, bias = false, aux = false, dbias = false;
-  int act = 0, dact = 0, gated = 0, dgated = 0;
-  int activation() const { return act ? act : dact ? dact : gated ? gated : dgated; }
+  int act = 0, dact = 0, gated = 0, dgated = 0, gated_aux = 0;
+  int activation() const { return act ? act : dact ? dact : gated ? gated : dgated ? dgated : gated_aux; }
 };
 // nullptr: no such variant (--layout tn without --bf16 and no --layout at all are the fp16 b_col_major commands)
 static const Variant* resolve_variant(const TrFlags& f) {
   for (const Variant& v : kVariants)
     if (f.layout == v.L->label && (v.elem == kBF16) == f.bf16 && v.out->c32 == f.c32 && v.out->bias == f.bias && v.out->db32 == f.dbias &&
-        v.out->z == (f.dact ? kZRead : f.aux ? kZWritten : kZNone) && v.out->act == (f.activation() != 0) && v.out->gated == (f.gated != 0) &&
-        v.out->dgated == (f.dgated != 0) && !((f.gated || f.dgated) && (f.act || f.dact)) && !(f.gated && f.dgated))
+        v.out->z == (f.dact ? kZRead : f.aux ? kZWritten : kZNone) && v.out->act == (f.activation() != 0) && v.out->gated == (f.gated != 0 || f.gated_aux != 0) &&
+        v.out->dgated == (f.dgated != 0) && v.out->gaux == (f.gated_aux != 0) && !((f.gated || f.dgated || f.gated_aux) && (f.act || f.dact)) &&
+        (f.gated != 0) + (f.dgated != 0) + (f.gated_aux != 0) <= 1)
       return &v;
   return nullptr;
 }
@@ -1564,6 +1580,7 @@ static int operands_gated(Check& K) {
     K.h.bias2.push_back(bf16_rne((float)bu[n]));
   }
   K.h.relu.resize(K.cn), K.h.y.resize(K.cn), K.h.eps.resize(K.cn);
+  if (K.V.out->gaux) K.h.z.resize(2 * K.cn);   // what g_out and behind it u_out must hold: bf16(g), bf16(u) of gated_pre's value
   for (int m = 0; m < sh.M; ++m)
     for (int n = 0; n < sh.N; ++n) {
       int sg = 0, su = 0;
@@ -1576,6 +1593,10 @@ static int operands_gated(Check& K) {
       }
       const size_t i = (size_t)m * sh.N + n;
       const float gf = (float)g, uf = (float)u;
+      if (K.V.out->gaux) {
+        K.h.z[i] = bf16_rne(hgemm_mi355x::gated_pre((float)(sg * scale), (float)bg[n]));
+        K.h.z[K.cn + i] = bf16_rne(hgemm_mi355x::gated_pre((float)(su * scale), (float)bu[n]));
+      }
       K.h.relu[i] = bf16_rne(hgemm_mi355x::gated_mul(gf > 0 ? gf : 0.0f, uf));
       K.h.y[i] = act_fp64(g, K.act) * u;
       K.h.eps[i] = hgemm_mi355x::GATED_ACT_EPS * fabs(g) * fabs(u) + hgemm_mi355x::GATED_MUL_EPS * fabs(K.h.y[i]);
@@ -1598,6 +1619,37 @@ static void summary_gated(const Check& K) {
   if (K.act == HGEMM_ACT_RELU) printf("check %s: %d runs, %d failures (bit-exact against bf16(relu(g) u) of the exact g and u)\n", K.lay.c_str(), K.runs, K.failures);
   else printf("check %s: %d runs, %d failures (every element within 1/2 ulp_bf16(y*) + 2^-19 |g| |u| + 2^-23 |y*| of the fp64 value of the exact g and u; worst %.3f of it)\n",
               K.lay.c_str(), K.runs, K.failures, K.worst);
+}
+
+// ---- The gated aux kind's check (--gated-aux A with --layout tn --bf16; bgemm_mi355x_tn_gated_aux): operands_gated's operands, C judged as
+// --gated judges it, g_out and u_out bit for bit against bf16(g) and bf16(u) for every activation; each of the three outputs is followed by
+// GATED_GUARD sentinel bytes.
+static int judge_gated_aux(Check& K) {
+  judge_gated(K);
+  const size_t cn = K.cn;
+  std::vector<uint16_t> go(cn), uo(cn);
+  unsigned char guard[2][GATED_GUARD];
+  HIP_OK(hipMemcpy(go.data(), K.call.z, cn * 2, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(uo.data(), K.call.c2, cn * 2, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(guard[0], (const unsigned char*)K.call.z + cn * 2, GATED_GUARD, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(guard[1], (const unsigned char*)K.call.c2 + cn * 2, GATED_GUARD, hipMemcpyDeviceToHost));
+  size_t bad = 0, changed = 0;
+  for (size_t i = 0; i < cn; ++i) bad += (go[i] != K.h.z[i]) + (uo[i] != K.h.z[cn + i]);
+  if (bad) {
+    printf("FAIL %s %d_%d_%d %s s=%d%s: %zu elements of g_out / u_out differ from bf16(g) / bf16(u)\n", K.lay.c_str(), K.sh.M, K.sh.N, K.sh.K, K.cname,
+           K.splits & HGEMM_SPLITK_MASK, (K.splits & HGEMM_PLAN_NT_STORE) ? "|nt" : "", bad);
+    ++K.failures;
+  }
+  for (const auto& gd : guard) for (unsigned char b : gd) changed += b != GATED_SENTINEL;
+  if (changed) {
+    printf("FAIL %s %d_%d_%d %s s=%d: %zu sentinel bytes behind g_out or u_out changed\n", K.lay.c_str(), K.sh.M, K.sh.N, K.sh.K, K.cname, K.splits & HGEMM_SPLITK_MASK, changed);
+    ++K.failures;
+  }
+  return 0;
+}
+static void summary_gated_aux(const Check& K) {
+  summary_gated(K);
+  printf("check %s: g_out and u_out bit-exact against bf16(g) and bf16(u) in every run\n", K.lay.c_str());
 }
 
 // ---- The dgated kind's check (--dgated A with --layout nn --bf16; bgemm_mi355x_nn_dgated) ------------------------------------------------------
@@ -1692,11 +1744,16 @@ static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
     TrCall& call = K.call;
     call = {dev.upload(K.h.a.data(), K.h.a.size() * 2), dev.upload(K.h.b.data(), K.h.b.size() * 2),
             O.bias || O.gated ? dev.upload(K.h.bias.data(), K.h.bias.size() * 2) : nullptr, dev.alloc(cn * esz + (O.gated || O.dgated ? GATED_GUARD : 0)), 0,
-            O.z == kZRead || O.dgated ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : nullptr,
+            O.z == kZRead || O.dgated ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : O.gaux ? dev.alloc(cn * 2 + GATED_GUARD) : nullptr,
             O.db32 ? (float*)dev.alloc((sh.N + DBIAS_GUARD) * sizeof(float)) : nullptr, act};
     if (O.gated) {
       call.b2 = dev.upload(K.h.b2.data(), K.h.b2.size() * 2), call.bias2 = dev.upload(K.h.bias2.data(), K.h.bias2.size() * 2);
       HIP_OK(hipMemset((unsigned char*)call.c + cn * esz, GATED_SENTINEL, GATED_GUARD));
+    }
+    if (O.gaux) {
+      call.c2 = dev.alloc(cn * 2 + GATED_GUARD);
+      HIP_OK(hipMemset((unsigned char*)call.z + cn * 2, GATED_SENTINEL, GATED_GUARD));
+      HIP_OK(hipMemset((unsigned char*)call.c2 + cn * 2, GATED_SENTINEL, GATED_GUARD));
     }
     if (O.dgated) {
       call.b2 = dev.upload(K.h.b2.data(), cn * 2), call.c2 = dev.alloc(cn * 2 + GATED_GUARD);
@@ -1714,7 +1771,8 @@ static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
           if (call.accumulate) HIP_OK(hipMemcpy(call.c, K.h.old.data(), cn * esz, hipMemcpyHostToDevice));
           else                 HIP_OK(hipMemset(call.c, 0xff, cn * esz));   // NaN pattern: a store must not read it, unwritten outputs are caught
           if (O.z == kZWritten) HIP_OK(hipMemset(call.z, 0xff, cn * 2));
-          if (O.dgated) HIP_OK(hipMemset(call.c2, 0xff, cn * 2));
+          if (O.dgated || O.gaux) HIP_OK(hipMemset(call.c2, 0xff, cn * 2));
+          if (O.gaux) HIP_OK(hipMemset(call.z, 0xff, cn * 2));
           if (O.db32) HIP_OK(hipMemcpy(call.db32, dbias_prefill(sh.N, false).data(), (sh.N + DBIAS_GUARD) * sizeof(float), hipMemcpyHostToDevice));
           const int st = V.launch(c, splits, call, sh, L.lda(sh), L.ldb(sh));
           const hipError_t e = hipDeviceSynchronize();
@@ -2041,6 +2099,42 @@ static void bench_tn_gated(TrBench& B) {
   B.verdict("gated_le_unfused", 0, 1, true);
 }
 
+// tn --bf16 --gated-aux A: bgemm_mi355x_launch_tn_gated_aux (H and a fused [M][2 N] g|u buffer) at the plan of the product of width 2 N against
+// the route a training caller has without it, at the SAME member and splits -- bgemm_mi355x_launch_tn_bias on the stacked [2 N][K] weight
+// with the stacked bias, which writes g|u, then the element-wise gate kernel above over it (its launch is not checked) --, and, context
+// only, bgemm_mi355x_launch_tn_gated alone: the price of the two extra stores.  "gated_aux_le_unfused", within the unfused route's spread.
+static void bench_tn_gated_aux(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  int cfg = 0, splits = 1;
+  bgemm_mi355x_tn_plan(sh.M, 2 * sh.N, sh.K, &cfg, &splits);
+  B.cfg = cfg, B.splits = splits;
+  const int lda = sh.K, ldb = sh.K, act = B.act, gate_grid = elementwise_grid(cn);
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), half = B.to_bf16(B.of(&Buffers::bt), B.b_elems), w = B.alloc(2 * B.b_elems * 2),
+                        gu = B.alloc(2 * cn * 2), cb = B.alloc(cn * 2), bias = B.alloc((size_t)2 * sh.N * 2);
+  for (size_t i = 0; i < w.size(); ++i) {
+    HIP_OK(hipMemcpy(w[i], half[i], B.b_elems * 2, hipMemcpyDeviceToDevice));
+    HIP_OK(hipMemcpy((char*)w[i] + B.b_elems * 2, half[i], B.b_elems * 2, hipMemcpyDeviceToDevice));
+    fill_bias_kernel<<<64, 256>>>((__bf16*)bias[i], 2 * sh.N);
+  }
+  B.add("gated_aux", [=](Buffers&, size_t i) {
+    return bgemm_mi355x_launch_tn_gated_aux(cfg, splits, ab[i], w[i], (const char*)w[i] + (size_t)sh.N * sh.K * 2, bias[i], (const char*)bias[i] + (size_t)sh.N * 2, cb[i],
+                                            gu[i], (char*)gu[i] + (size_t)sh.N * 2, sh.M, sh.N, sh.K, lda, ldb, sh.N, 2 * sh.N, act, nullptr);
+  });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], w[i], bias[i], gu[i], sh.M, 2 * sh.N, sh.K, lda, ldb, 2 * sh.N, nullptr);
+    with_gated_act(act, [&](auto A) { gate_bf16_kernel<decltype(A)::value><<<gate_grid, 256>>>((const __bf16*)gu[i], (__bf16*)cb[i], cn, sh.N); });
+    return st;
+  });
+  B.add("gated", [=](Buffers&, size_t i) {
+    return bgemm_mi355x_launch_tn_gated(cfg, splits, ab[i], w[i], (const char*)w[i] + (size_t)sh.N * sh.K * 2, bias[i], (const char*)bias[i] + (size_t)sh.N * 2, cb[i],
+                                        sh.M, sh.N, sh.K, lda, ldb, sh.N, act, nullptr);
+  });
+  B.head("\"output\": \"c16_gated_aux\", \"act\": \"%s\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", kActNames[act],
+         B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("gated_aux_le_unfused", 0, 1, true);
+}
+
 // tn --bf16 --bias --act A: the planned bgemm_mi355x_tn_bias_act call against the path it replaces -- bgemm_mi355x_launch_tn_bias with the
 // same member and splits followed by the element-wise activation kernel above (its launch is not checked: the contender answers with the
 // product's status) --, and, context only, the plain bias call.  The one condition: fused <= unfused within the unfused path's own
@@ -2218,6 +2312,11 @@ int main(int argc, char** argv) {
       for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.gated = k;
       if (!tr.gated) { fprintf(stderr, "--gated takes relu, gelu, gelu_tanh or silu\n"); return 2; }
     }
+    else if (a == "--gated-aux") {
+      const std::string nm = next();
+      for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.gated_aux = k;
+      if (!tr.gated_aux) { fprintf(stderr, "--gated-aux takes relu, gelu, gelu_tanh or silu\n"); return 2; }
+    }
     else if (a == "--dgated") {
       const std::string nm = next();
       for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.dgated = k;
@@ -2280,6 +2379,10 @@ int main(int argc, char** argv) {
   if (tr.dact && !(tr.bf16 && tr.layout == "nn" && !tr.act)) { fprintf(stderr, "--dact goes with --layout nn --bf16 (bgemm_mi355x_nn_dact)\n"); return 2; }
   if (tr.dbias && !tr.dact) { fprintf(stderr, "--dbias goes with --layout nn --bf16 --dact A (bgemm_mi355x_nn_dact_dbias)\n"); return 2; }
   if (tr.dgated && !(tr.bf16 && tr.layout == "nn" && !tr.act && !tr.dact)) { fprintf(stderr, "--dgated goes with --layout nn --bf16 (bgemm_mi355x_nn_dgated)\n"); return 2; }
+  if (tr.gated_aux && !(tr.bf16 && tr.layout == "tn" && !tr.act && !tr.dact && !tr.gated && !tr.dgated)) {
+    fprintf(stderr, "--gated-aux goes with --layout tn --bf16 (bgemm_mi355x_tn_gated_aux)\n");
+    return 2;
+  }
   const Variant* variant = resolve_variant(tr);
   if (variant && mode != "check" && mode != "bench") {
     fprintf(stderr, "--layout %s%s goes with check or bench\n", tr.layout.c_str(), variant->L->b_col_major ? " --bf16" : "");

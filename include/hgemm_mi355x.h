@@ -662,7 +662,8 @@ int bgemm_mi355x_colsum_c32(const void* x, float* out32, int M, int N, int ldx, 
  * The table, ids, names, plan (hgemm_mi355x_nn_plan(M, N, K)), workspace size and reserve call are hgemm_mi355x_nn_*'s, the splits word
  * and HGEMM_PLAN_NT_STORE (both outputs) bgemm_mi355x_launch_nn_dact's; a captured split call without a workspace runs unsplit, status 0,
  * and allocates nothing.
- * Out of scope: a forward that writes H and [g|u] in one call, a bias gradient inside this call, in-place operation, fp16. */
+ * The forward that writes H and [g|u] in one call is bgemm_mi355x_tn_gated_aux, below.
+ * Out of scope: a bias gradient inside this call, in-place operation, fp16. */
 /* planned, contiguous (lda = K, ldb = ldz = ldc = N) */
 int bgemm_mi355x_nn_dgated(const void* a, const void* b, const void* g, const void* u, void* dg, void* du, int M, int N, int K, int act,
                            void* stream);
@@ -671,6 +672,40 @@ int bgemm_mi355x_launch_nn_dgated(int nn_config, int splits, const void* a, cons
 /* bgemm_mi355x_nn_dact_runs(nn_config, M, N, K, lda, ldb, ldc, ldz): the second input and output change no scope (note the order of the
  * last two arguments here) */
 int bgemm_mi355x_nn_dgated_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldz, int ldc);
+
+/* ------------------------------------------------------------------------------------------
+ * Training form of the gated forward product: bgemm_mi355x_tn_gated that also saves the bf16 pre-activations g and u, the two matrices
+ * bgemm_mi355x_nn_dgated reads.  Operands, `act`, the NULL-bias rule, layout, strides, table, ids, names, plan (bgemm_mi355x_tn_plan(M, 2N, K)),
+ * workspace size, reserve call, splits word and capture behaviour are bgemm_mi355x_tn_gated's.  `g_out` and `u_out` are two more bf16
+ * outputs, each [M][ldz], one ldz for both.
+ * Fused buffer: u_out = g_out + N with ldz >= 2N is the [M][2N] matrix g|u that bgemm_mi355x_nn_dgated takes as it is (u = g + N, its ldz =
+ * this call's).  One gated MLP layer's forward and backward are then this library's calls on their fused buffers: this call writes H and
+ * g|u, bgemm_mi355x_nn_dgated writes dg|du, bgemm_mi355x_nn at K = 2N gives dX, bgemm_mi355x_ta_c32 at N = 2N gives dW and
+ * bgemm_mi355x_colsum_c32 gives db.
+ * Semantics, exactly, with g and u the fp32 values of bgemm_mi355x_tn_gated (finished sum + float(bias), one fp32 add each):
+ *     g_out[m][n] = bf16_rne( g[m][n] )     u_out[m][n] = bf16_rne( u[m][n] )     C[m][n] = bf16_rne( fl32( act32(g[m][n]) x u[m][n] ) )
+ *   - The activation and the gate see the UNROUNDED g and u.  Each of the three outputs is rounded once.  Nothing is applied to a slab: in
+ *     a two-pass plan the combine writes all three outputs.  HGEMM_PLAN_NT_STORE applies to all three outputs.
+ *   - C keeps bgemm_mi355x_tn_gated's bar (ReLU bit for bit); g_out and u_out are defined bit for bit for every activation.
+ * Identities, for the same tn_config, splits word and arguments:
+ *   - C is the C of bgemm_mi355x_launch_tn_gated, bit for bit.
+ *   - g_out is the C of bgemm_mi355x_launch_tn_bias(tn_config, splits, a, wg, bias_g, ...) at (M, N, K), bit for bit on arbitrary operands,
+ *     and u_out the same with wu and bias_u (a NULL bias: a zero-filled vector): each accumulator walks K in the same order whatever the
+ *     tile's width.  This holds for every unsplit launch (plain and NT), and for a split launch wherever both calls resolve to the same K
+ *     cuts -- they do whenever both run their kernels, the cuts depend on K and the splits word alone.
+ * Scope: bgemm_mi355x_tn_gated's, and g_out and u_out have C's rules: 16-byte aligned, ldz % 8 == 0, (BM ldz + N) 2 bytes below 2 GiB;
+ * anything else is answered by the reference kernel (status 0, the same semantics).
+ * Refused with HGEMM_ERR_BAD_ARG: everything bgemm_mi355x_tn_gated refuses, a NULL g_out or u_out, g_out == u_out, either of them equal
+ * to c, ldz < N.  Overlap of the three outputs with each other or with an input is the caller's error.
+ * Out of scope: fp16, a bias gradient, more than two saved matrices. */
+/* planned, contiguous (lda = ldb = K, ldc = ldz = N) */
+int bgemm_mi355x_tn_gated_aux(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c,
+                              void* g_out, void* u_out, int M, int N, int K, int act, void* stream);
+int bgemm_mi355x_launch_tn_gated_aux(int tn_config, int splits, const void* a, const void* wg_col_major, const void* wu_col_major,
+                                     const void* bias_g, const void* bias_u, void* c, void* g_out, void* u_out, int M, int N, int K, int lda,
+                                     int ldb, int ldc, int ldz, int act, void* stream);
+/* bgemm_mi355x_tn_gated_runs with g_out's and u_out's conditions added; 0 for ldz < N */
+int bgemm_mi355x_tn_gated_aux_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
