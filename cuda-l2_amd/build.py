@@ -56,6 +56,8 @@ LIB_SOURCES = [
     "hgemm_inst_g18.hip",
     "hgemm_inst_g19.hip",
     "hgemm_inst_g20.hip",
+    "hgemm_inst_g21.hip",
+    "hgemm_inst_g22.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -499,6 +499,11 @@ int run(int acc, const void* a, const void* b, const void* bt, void* c, int M, i
 // gaux (bgemm_mi355x_tn_gated_aux, with gated): the gated call with the rounded pre-activations as two more 16-bit outputs g_out (= z) and
 // u_out, both at row stride ldz with z_out's rules; the kinds TR_C16_GATED_AUX + act and the ids EPI_C16_GATED_AUX + act.  The gated call's
 // plan in everything but those ids.
+// add (bgemm_mi355x_tn_bias_add: family f, with bias, which may then be NULL; bgemm_mi355x_nn_add: family n, without): a read-only 16-bit
+// residual matrix r (= z) at row stride ldr (= ldz), added to the finished sum in fp32 behind the bias and in front of the one rounding
+// (hgemm_residual.hpp); the kinds TR_C16_BIAS_ADD / TR_C16_ADD and the ids EPI_C16_BIAS_ADD / EPI_C16_ADD, no activation.  r has dact's rules
+// for z with one difference: r == c is allowed where ldr == ldc (in place) and refused otherwise.  The parent call's plan in everything but
+// those ids.
 struct TrOut {
   bool c32, accumulate;
   bool bias = false;
@@ -509,13 +514,14 @@ struct TrOut {
   bool gated = false;
   bool dgated = false;   // with dact: two saved matrices in (z = g, and u) and two outputs (c = dg, and du); the dact call's plan
   bool gaux = false;     // with gated: two more outputs (z = g_out, and u_out) at ldz; the gated call's plan
+  bool add = false;      // the residual matrix r (z = r, ldz = ldr), with bias (family f; the vector may be NULL) or without (family n)
   int elem_bytes() const { return c32 ? 4 : 2; }
-  bool has_z() const { return aux || dact || gaux; }
-  bool has_epi() const { return bias || dact || gated; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
+  bool has_z() const { return aux || dact || gaux || add; }
+  bool has_epi() const { return bias || dact || gated || add; }   // the plain dispatch and the combine dispatch carry an id of their own, epi_bias()
   TrKind kind() const {   // the kernel set's cell in TrRow / TrTable
-    return dgated ? (TrKind)(TR_C16_DGATED + act) : gaux ? (TrKind)(TR_C16_GATED_AUX + act) : gated ? (TrKind)(TR_C16_GATED + act) : dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
+    return add ? (bias ? TR_C16_BIAS_ADD : TR_C16_ADD) : dgated ? (TrKind)(TR_C16_DGATED + act) : gaux ? (TrKind)(TR_C16_GATED_AUX + act) : gated ? (TrKind)(TR_C16_GATED + act) : dact ? (TrKind)((dbias ? TR_C16_DACT_DBIAS : TR_C16_DACT) + act) : bias ? (TrKind)((aux ? TR_C16_BIAS_AUX : TR_C16_BIAS) + act) : c32 ? TR_C32 : TR_C16;
   }
-  int epi_bias() const { return (dgated ? EPI_C16_DGATED : gaux ? EPI_C16_GATED_AUX : gated ? EPI_C16_GATED : dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
+  int epi_bias() const { return add ? (bias ? EPI_C16_BIAS_ADD : EPI_C16_ADD) : (dgated ? EPI_C16_DGATED : gaux ? EPI_C16_GATED_AUX : gated ? EPI_C16_GATED : dact ? EPI_C16_DACT : aux ? EPI_C16_BIAS_AUX : EPI_C16_BIAS) + act; }
 };
 constexpr TrOut kOutC16{false, false};
 constexpr TrOut kOutC16Bias{false, false, true};
@@ -525,7 +531,8 @@ static_assert(TR_C16_BIAS + ACT_GELU_TANH == TR_C16_BIAS_GELU_TANH && TR_C16_BIA
               "a kind per activation, four times");
 constexpr bool act_known(int act) { return act == HGEMM_ACT_RELU || act == HGEMM_ACT_GELU || act == HGEMM_ACT_GELU_TANH; }
 static_assert(HGEMM_ACT_SILU == ACT_SILU && TR_C16_GATED + 1 == TR_KINDS && TR_C16_GATED + ACT_SILU == TR_C16_DGATED &&
-              TR_C16_DGATED + ACT_SILU == TR_C16_GATED_AUX && TR_C16_GATED_AUX + ACT_SILU + 1 == TR_KINDS_ALL && !act_known(HGEMM_ACT_SILU),
+              TR_C16_DGATED + ACT_SILU == TR_C16_GATED_AUX && TR_C16_GATED_AUX + ACT_SILU + 1 == TR_C16_BIAS_ADD && TR_C16_ADD + 1 == TR_KINDS_ALL &&
+              !act_known(HGEMM_ACT_SILU),
               "the gated kinds, the dgated kinds and the gated aux kinds follow; SiLU is theirs alone");
 constexpr bool act_known_gated(int act) { return act_known(act) || act == HGEMM_ACT_SILU; }
 constexpr TrOut out_gated(int act) { return TrOut{false, false, false, act, false, false, 0, false, false, true}; }   // (act_known_gated(act) checked by the caller)
@@ -536,6 +543,8 @@ constexpr TrOut out_dact(int act, int ldz) { return TrOut{false, false, false, a
 constexpr TrOut out_dact_dbias(int act, int ldz, bool db_acc) { return TrOut{false, false, false, act, false, true, ldz, true, db_acc}; }
 // (act_known_gated(act) checked by the caller.)  A dact call in every rule and in its plan: z is g, ldz the stride of g and of u alike
 constexpr TrOut out_dgated(int act, int ldz) { return TrOut{false, false, false, act, false, true, ldz, false, false, false, true}; }
+constexpr TrOut out_bias_add(int ldr) { return TrOut{false, false, true, 0, false, false, ldr, false, false, false, false, false, true}; }
+constexpr TrOut out_add(int ldr) { return TrOut{false, false, false, 0, false, false, ldr, false, false, false, false, false, true}; }
 
 // What the operands and a 16-bit C hold (TrElem): fp16 (every hgemm_mi355x_nn_ / _ta_ entry point) or bfloat16 (bgemm_mi355x_).  Elements
 // are 2 bytes either way: scope, reach, strides, tables, plans and workspaces do not ask.  (TrElem, c32) selects a kernel set and nothing
@@ -713,11 +722,14 @@ void tr_model_plan(const TrLayout& L, int M, int N, int K, int* cfg, int* splits
 // member's kernel behind its GemmArgs, in a DgatedArgs (hgemm_kernel_nn.hpp).)
 // (out.gaux: a gated call with z = g_out and `z2` = u_out, both required, each distinct from c and from the other, with z_out's rules.  They
 // reach the combine and the reference kernel as a GatedAuxOut pair behind `z` and the member's kernel in a GatedAuxArgs.)
+// (out.add: z = r, required, read-only; r == c is the in-place call and needs ldr == ldc -- with another stride the rows of r and c would
+// overlap out of step.  With out.bias the vector may be NULL (+0.0).  r reaches the combine and the reference kernel as `z` and the member's
+// kernel in g.partial (family f, beside the bias in g.counters) or g.counters (family n), its stride in g.tail_first.)
 int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_arg, const void* a, const void* b, const void* bias, void* c, int M,
               int N, int K, int lda, int ldb, int ldc, void* stream, void* z = nullptr, float* db32 = nullptr, const void* b2 = nullptr,
               const void* bias2 = nullptr, void* z2 = nullptr) {
   DisarmTiming disarm_timing;
-  if (!a || !b || !c || (out.bias && !bias) || (out.gated && !b2) || (out.has_z() && (!z || z == c)) || (out.dbias && !db32) || M <= 0 || N <= 0 || K <= 0)
+  if (!a || !b || !c || (out.bias && !out.add && !bias) || (out.gated && !b2) || (out.has_z() && (!z || (z == c && !(out.add && out.ldz == ldc)))) || (out.dbias && !db32) || M <= 0 || N <= 0 || K <= 0)
     return HGEMM_ERR_BAD_ARG;
   if (out.dgated && (!bias || !bias2 || bias2 == c || bias2 == z || bias2 == bias || c == bias)) return HGEMM_ERR_BAD_ARG;
   if (out.gaux && (!z2 || z2 == c || z2 == z)) return HGEMM_ERR_BAD_ARG;
@@ -751,7 +763,7 @@ int tr_launch(const TrLayout& L, TrElem elem, TrOut out, int config, int splits_
     if (out.bias && p.d[i].epi == out.epi_bias()) g.counters = (unsigned*)const_cast<void*>(bias);   // read-only there: the kernel's bf16 bias vector
     if (out.has_z() && !out.gaux && p.d[i].thunk == THUNK_ENTRY &&
         (p.d[i].epi == out.epi_bias() || (out.dbias && p.d[i].epi == EPI_C16_DACT_DBIAS + out.act))) {   // the member's own kernel, never a slab kernel
-      if (out.aux) g.partial = (float*)z; else g.counters = (unsigned*)z;              // (read-only in the dact kernels)
+      if (out.aux || (out.add && out.bias)) g.partial = (float*)z; else g.counters = (unsigned*)z;   // (read-only in the dact and add kernels)
       g.tail_first = out.ldz;
     }
     const TimingSlot ts = timing_slot(p.d[i].start, p.d[i].stop);
@@ -1273,6 +1285,33 @@ int bgemm_mi355x_selfcheck_launch_ta_bias(int ta_config, int splits, int operand
   return tr_selfcheck_launch(kLayoutTA, TR_BF16, kOutC16Bias, ta_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 
+// ---- the forward product with a fused bias and residual add, X_out = X_in + (H W^T + b) (the kind TR_C16_BIAS_ADD): C = bf16((S +
+// float(bias[n])) + float(r[m][n])), hgemm_residual.hpp's two fp32 adds in this order and one rounding, in the kernel's epilogue, in the
+// combine and in the reference kernel.  A call resolves to the plan of the bgemm_mi355x_launch_tn_bias call with the same arguments; only
+// the epi id of the plain dispatch and of the combine dispatch differs.  bias may be NULL (+0.0); r is read-only, has dact's rules for z and
+// may be c where ldr == ldc.
+int bgemm_mi355x_tn_bias_add_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldr) {
+  return tr_runs(kLayoutTN, TR_BF16, out_bias_add(ldr), tn_config, M, N, K, lda, ldb, ldc);
+}
+int bgemm_mi355x_launch_tn_bias_add(int tn_config, int splits_arg, const void* a, const void* b_col_major, const void* bias, const void* r, void* c,
+                                    int M, int N, int K, int lda, int ldb, int ldc, int ldr, void* stream) {
+  return tr_launch(kLayoutTN, TR_BF16, out_bias_add(ldr), tn_config, splits_arg, a, b_col_major, bias, c, M, N, K, lda, ldb, ldc, stream, const_cast<void*>(r));
+}
+int bgemm_mi355x_tn_bias_add(const void* a, const void* b_col_major, const void* bias, const void* r, void* c, int M, int N, int K, void* stream) {
+  if (!r) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutTN, TR_BF16, out_bias_add(N), a, b_col_major, bias, c, M, N, K, stream, const_cast<void*>(r));
+}
+// (bgemm_mi355x_selfcheck_launch_tn_bias_act_aux's output; operands & 4: a, b, c, r and a non-NULL bias are 16-byte aligned.  The NN twin shows
+// the refusal: family n has no bias.)
+int bgemm_mi355x_selfcheck_launch_tn_bias_add(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldr,
+                                              int ruled_out, long long out[20]) {
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, out_bias_add(ldr), tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_nn_bias_add(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldr,
+                                              int ruled_out, long long out[20]) {
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_bias_add(ldr), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
 // ---- the gated forward product, H = act(X Wg^T + bg) (.) (X Wu^T + bu) (the kinds TR_C16_GATED + act): the work of the TN product of width
 // 2 N, so the planned call asks bgemm_mi355x_tn_plan(M, 2 N, K) and the workspace is that product's; N is the output width everywhere else.
 // act: HGEMM_ACT_RELU / _GELU / _GELU_TANH / _SILU, anything else HGEMM_ERR_BAD_ARG.  Either bias may be NULL: +0.0.
@@ -1418,6 +1457,29 @@ int bgemm_mi355x_launch_nn_dact(int nn_config, int splits_arg, const void* a, co
 int bgemm_mi355x_nn_dact(const void* a, const void* b, const void* z, void* c, int M, int N, int K, int act, void* stream) {
   if (!act_known(act) || !z) return HGEMM_ERR_BAD_ARG;
   return tr_run(kLayoutNN, TR_BF16, out_dact(act, N), a, b, nullptr, c, M, N, K, stream, const_cast<void*>(z));
+}
+// ---- the input gradient with a fused residual add, dX = dZ W + dX_out (the kind TR_C16_ADD, family n, bf16): C = bf16(S + float(r[m][n])),
+// hgemm_residual.hpp's one fp32 add on the finished sum and one rounding.  A call resolves to the plan of the bgemm_mi355x_launch_nn call with
+// the same arguments; only the epi id of the plain dispatch and of the combine dispatch differs.  r as in bgemm_mi355x_launch_tn_bias_add.
+int bgemm_mi355x_nn_add_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldr) {
+  return tr_runs(kLayoutNN, TR_BF16, out_add(ldr), nn_config, M, N, K, lda, ldb, ldc);
+}
+int bgemm_mi355x_launch_nn_add(int nn_config, int splits_arg, const void* a, const void* b, const void* r, void* c, int M, int N, int K, int lda,
+                               int ldb, int ldc, int ldr, void* stream) {
+  return tr_launch(kLayoutNN, TR_BF16, out_add(ldr), nn_config, splits_arg, a, b, nullptr, c, M, N, K, lda, ldb, ldc, stream, const_cast<void*>(r));
+}
+int bgemm_mi355x_nn_add(const void* a, const void* b, const void* r, void* c, int M, int N, int K, void* stream) {
+  if (!r) return HGEMM_ERR_BAD_ARG;
+  return tr_run(kLayoutNN, TR_BF16, out_add(N), a, b, nullptr, c, M, N, K, stream, const_cast<void*>(r));
+}
+// (not part of the public header; the TN twin shows the refusal: family f's residual call is the bias form)
+int bgemm_mi355x_selfcheck_launch_nn_add(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldr,
+                                         int ruled_out, long long out[20]) {
+  return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_add(ldr), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+int bgemm_mi355x_selfcheck_launch_tn_add(int tn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldr,
+                                         int ruled_out, long long out[20]) {
+  return tr_selfcheck_launch(kLayoutTN, TR_BF16, out_add(ldr), tn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
 }
 // ---- the gated MLP's input gradient, dG = (dY Wd) (.) U (.) act'(G) and dU = act(G) (.) (dY Wd) (the kinds TR_C16_DGATED + act, family n,
 // bf16, HGEMM_ACT_SILU included): hgemm_dgated.hpp's dgated_store on the finished sum in the kernel's epilogue, in the combine and in the

@@ -321,6 +321,12 @@ constexpr int EPI_C16_DGATED = 96;
 // bf16(u) and C = bf16(act(g) x u), g and u unrounded (hgemm_kernel_tn_gated.hpp).  EPI_C16_GATED_AUX + the activation's id: 129 .. 132,
 // neither flag bit set.
 constexpr int EPI_C16_GATED_AUX = 128;
+// The fused residual add (hgemm_residual.hpp), the two ids without an activation behind them and with neither flag bit set.
+// EPI_C16_BIAS_ADD (family f, bgemm_mi355x_tn_bias_add): C = bf16((acc + float(bias[n])) + float(r[m][n])), two fp32 adds in this order and
+// one rounding; g.counters holds the bias pointer (null: +0.0), g.partial the read-only bf16 r and g.tail_first its row stride ldr.
+// EPI_C16_ADD (family n, bgemm_mi355x_nn_add): C = bf16(acc + float(r[m][n])); g.counters holds r and g.tail_first ldr, as a dact launch
+// carries its z.  r may be C itself (ldr == ldc): every r of a wave's tile is consumed before the wave's first store.
+constexpr int EPI_C16_BIAS_ADD = 160, EPI_C16_ADD = 161;
 // Kernel-template flag on top of an epilogue id (families q and r): the "ktail" variant of the kernel, for a K that is not a
 // multiple of the geometry's stage depth -- whole stages through the pipeline, the rest by direct_k_tail.  A variant of its own,
 // so the kernels every K % stage == 0 launch runs keep their instruction streams.

@@ -40,6 +40,7 @@
 #include "hgemm_dbias.hpp"
 #include "hgemm_dgated.hpp"
 #include "hgemm_launch.hpp"
+#include "hgemm_residual.hpp"
 
 namespace hgemm_mi355x {
 
@@ -295,6 +296,18 @@ HGEMM_TR_MEMBERS(HGEMM_NN_DGATED_EXTERN, ACT_GELU, CfgNNB)
 HGEMM_TR_MEMBERS(HGEMM_NN_DGATED_EXTERN, ACT_GELU_TANH, CfgNNB)
 HGEMM_TR_MEMBERS(HGEMM_NN_DGATED_EXTERN, ACT_SILU, CfgNNB)
 
+// The residual set (bgemm_mi355x_nn_add): the member's EPI_C16_ADD kernel alone; the K slices of a two-pass form are the bf16 16-bit set's
+// EPI_SLAB kernels.  g.counters of the dispatch is r, g.tail_first its row stride, as a dact dispatch carries z (tr_launch, hgemm_api.hip).
+template <class CFG>
+void launch_nn_add(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_ADD>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_NN_ADD_LAUNCHER(CFG, BM, BN, WM, WN, NB) launch_nn_add<CFG<BM, BN, WM, WN, NB>>
+#define HGEMM_NN_ADD_INST(...) template void HGEMM_NN_ADD_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_NN_ADD_EXTERN(...) extern HGEMM_NN_ADD_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_NN_ADD_EXTERN, CfgNNB)                   // hgemm_inst_g22.hip
+
 // A layout's table (hgemm_registry.hip builds both, each by one expansion of the member list: a config id is a position in `rows`; the
 // geometry table of hgemm_configs*.def does not know these families).  A row is the member's geometry and its launcher in every kernel
 // set of the layout; TrKernels is what a set has besides: the combine of the two-pass form and the reference kernel (status 0, exact:
@@ -317,7 +330,9 @@ enum TrKind { TR_C16 = 0, TR_C32 = 1, TR_C16_BIAS = 2, TR_C16_BIAS_RELU = 3, TR_
               // TR_C16_DGATED + a (a = 1 .. 4): the gated MLP's input gradient (family n: bgemm_mi355x_nn_dgated), one sum, two outputs.
               // TR_C16_GATED_AUX + a (a = 1 .. 4): the gated product with the rounded pre-activations as two more outputs (family f:
               // bgemm_mi355x_tn_gated_aux), two sums, three outputs.
-              TR_C16_GATED = 14, TR_C16_DGATED = 18, TR_C16_GATED_AUX = 22, TR_KINDS_ALL = 27 };
+              // TR_C16_BIAS_ADD: the fused bias (may be null) and residual matrix (family f: bgemm_mi355x_tn_bias_add).  TR_C16_ADD: the fused
+              // residual matrix (family n: bgemm_mi355x_nn_add).  One sum, one output, no activation; `z` is the read-only r, which may be c.
+              TR_C16_GATED = 14, TR_C16_DGATED = 18, TR_C16_GATED_AUX = 22, TR_C16_BIAS_ADD = 27, TR_C16_ADD = 28, TR_KINDS_ALL = 29 };
 struct TrRow {
   TrEntry e;
   TrLaunch launch[2][TR_KINDS_ALL];   // [TrElem][TrKind]
@@ -330,6 +345,8 @@ struct TrRow {
 // have two inputs and two outputs besides the operands and use the same four: `z` = g and `bias` = u (inputs, both at ldz), `c` = dg and
 // `bias2` = du (outputs, both at ldc; the set writes through that one pointer, const in the signature for every other kind's sake).
 // The TR_C16_GATED_AUX sets are the gated sets with `z` = the address of a host-side GatedAuxOut (g_out and u_out, both at ldz).
+// TR_C16_BIAS_ADD and TR_C16_ADD: `z` = the read-only residual matrix r and ldz = its row stride ldr (non-const in the signature for the
+// output kinds' sake); `bias` of TR_C16_BIAS_ADD may be null: +0.0.  r may be c (ldz == ldc): the thread that stores an element read its r first.
 struct TrKernels {
   void (*combine)(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
                   bool accumulate, hipStream_t, TimingSlot);
@@ -367,8 +384,8 @@ const TrTable& tr_table_tn();   // family f (hgemm_kernel_tn.hpp): the bf16 forw
   using elem = typename CFG::elem;   // f16, or __bf16 (the bgemm_ entry points)
   using ex4 = __attribute__((ext_vector_type(4))) elem;
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || ((epi_is_dact(EPI) || epi_is_dbias(EPI) || epi_is_dgated(EPI)) && __is_same(elem, __bf16)),
-                "plain, two-pass slab and (bf16) dact / dact + dbias / dgated epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || ((epi_is_dact(EPI) || epi_is_dbias(EPI) || epi_is_dgated(EPI) || EPI == EPI_C16_ADD) && __is_same(elem, __bf16)),
+                "plain, two-pass slab and (bf16) dact / dact + dbias / dgated / residual epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -609,6 +626,37 @@ const TrTable& tr_table_tn();   // family f (hgemm_kernel_tn.hpp): the bf16 forw
 #include "hgemm_tr_store_c16.inc"
 #undef HGEMM_TR_STORE_C
 #undef HGEMM_TR_STORE_LD
+    }
+  }
+
+  // ---- the fused residual add (EPI_C16_ADD, bgemm_mi355x_nn_add): C = bf16(acc + float(r[m][n])) ----------------------------------------------
+  // The dact epilogue's loads with residual_add (hgemm_residual.hpp: one fp32 add on the finished sum, the combine's and the reference
+  // kernel's text) in place of dact_mul: g.counters is the bf16 residual matrix r ([M][ldr], read-only, ldr in g.tail_first), one 8-byte load
+  // per fragment through a descriptor from the tile's first row to r's last valid element (dact_z_range_bytes), issued behind the K loop.
+  // r may be C itself (ldr == ldc).  Every load of the wave's tile is issued and consumed in this block, in front of the store text below;
+  // the element a lane stores there -- its own or, behind the permlane swap, one of another lane of the SAME wave -- is computed from that
+  // element's r, so its store depends on its load; wave tiles are disjoint, and what a load reads outside its tile's M x N elements is never
+  // stored by this wave.
+  if constexpr (EPI == EPI_C16_ADD) {
+    using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
+    using bx4 = __attribute__((ext_vector_type(4))) __bf16;
+    const uint32_t ldr = (uint32_t)g.tail_first;
+    const uint32_t r_bytes = dact_z_range_bytes(g.M, g.N, g.tail_first, tc.m0);
+    const __amdgpu_buffer_rsrc_t rsR =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)g.counters + (size_t)tc.m0 * ldr), 0, r_bytes, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const uint32_t row = (uint32_t)dbias_row(wave_m, CFG::TM, i, lane);
+      bx4 r[FN];
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const uint32_t n_r = (uint32_t)(tc.n0 + wave_n * CFG::TN + 16 * j + 4 * (lane >> 4));
+        r[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsR, (row * ldr + n_r) * 2u, 0, 0));
+      }
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][j][e] = residual_add(acc[i][j][e], (float)r[j][e]);
     }
   }
 

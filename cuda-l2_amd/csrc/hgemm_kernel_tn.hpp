@@ -28,14 +28,18 @@
 
 #include "hgemm_act.hpp"
 #include "hgemm_kernel_nn.hpp"
+#include "hgemm_residual.hpp"
 
 namespace hgemm_mi355x {
 
 // The epilogues with a bias vector: EPI_C16_BIAS and, with an activation behind the add, EPI_C16_BIAS + ACT_* (hgemm_act.hpp).
 // EPI_C16_BIAS_AUX + ACT_*: the activation forms that also write the rounded pre-activation (bgemm_mi355x_tn_bias_act_aux).
 constexpr bool epi_has_aux(int epi) { return epi > EPI_C16_BIAS_AUX && epi <= EPI_C16_BIAS_AUX + ACT_GELU_TANH; }
-constexpr bool epi_has_bias(int epi) { return (epi >= EPI_C16_BIAS && epi <= EPI_C16_BIAS_GELU_TANH) || epi_has_aux(epi); }
-constexpr int epi_act(int epi) { return epi_has_aux(epi) ? epi - EPI_C16_BIAS_AUX : epi_has_bias(epi) ? epi - EPI_C16_BIAS : ACT_NONE; }
+// EPI_C16_BIAS_ADD: the bias (which may be null: +0.0) and then a residual matrix r, two fp32 adds and one rounding (bgemm_mi355x_tn_bias_add).
+constexpr bool epi_has_bias(int epi) { return (epi >= EPI_C16_BIAS && epi <= EPI_C16_BIAS_GELU_TANH) || epi_has_aux(epi) || epi == EPI_C16_BIAS_ADD; }
+constexpr int epi_act(int epi) { return epi_has_aux(epi) ? epi - EPI_C16_BIAS_AUX : epi == EPI_C16_BIAS_ADD ? ACT_NONE : epi_has_bias(epi) ? epi - EPI_C16_BIAS : ACT_NONE; }
+static_assert(epi_has_bias(EPI_C16_BIAS_ADD) && epi_act(EPI_C16_BIAS_ADD) == ACT_NONE && !epi_has_aux(EPI_C16_BIAS_ADD) && !epi_has_bias(EPI_C16_ADD),
+              "the residual form has a bias and no activation; family n's add id is not family f's");
 static_assert(epi_act(EPI_C16_BIAS_AUX + ACT_RELU) == ACT_RELU && epi_act(EPI_C16_BIAS_AUX + ACT_GELU_TANH) == ACT_GELU_TANH &&
               !epi_has_aux(EPI_C16_BIAS_GELU_TANH) && !epi_has_bias(EPI_C16_DACT + ACT_RELU), "the aux ids follow the activation ids");
 static_assert(epi_act(EPI_C16_BIAS_RELU) == ACT_RELU && epi_act(EPI_C16_BIAS_GELU) == ACT_GELU && epi_act(EPI_C16_BIAS_GELU_TANH) == ACT_GELU_TANH &&
@@ -55,7 +59,7 @@ struct CfgTNB : CfgTR<BM_, BN_, WM_, WN_, NBUF_, BM_ * ROW_BYTES> {
 
 // GemmArgs as the kernel reads it: A = [M][lda], Bt = b_col_major ([N][ldb], ldb >= K its row stride); tail_tiles = 0, counters = nullptr
 // -- except EPI_C16_BIAS and its activation forms, where counters is the bias vector (const __bf16*, N elements, 16-byte aligned), reinterpreted below as the fp32-C
-// kernels reinterpret g.C.
+// kernels reinterpret g.C.  EPI_C16_BIAS_ADD: counters is the bias vector or null, partial the residual matrix r and tail_first its row stride.
 template <class CFG, int EPI>
 __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmArgs g) {
   prefetch_kernargs<sizeof(GemmArgs)>();
@@ -64,7 +68,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
   constexpr int FM = CFG::FM, FN = CFG::FN, NW = CFG::NW, NJ = CFG::NJ, NJ_A = CFG::NJ_A;
   using elem = typename CFG::elem;   // __bf16
   using ex8 = __attribute__((ext_vector_type(8))) elem;
-  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || epi_has_bias(EPI), "plain, two-pass slab, fused-bias, fused-bias-activation and pre-activation-output epilogues");
+  static_assert(EPI == EPI_C16 || EPI == EPI_SLAB || epi_has_bias(EPI), "plain, two-pass slab, fused-bias, fused-bias-activation, pre-activation-output and bias + residual epilogues");
 
   __shared__ __attribute__((aligned(1024))) char smem[CFG::LDS_BYTES];
 
@@ -169,17 +173,60 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_bf16_kernel(const GemmA
     using bx4 = __attribute__((ext_vector_type(4))) __bf16;
     const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc((void*)g.counters, 0, (uint32_t)g.N * 2u, 0x00020000);
     bx4 bias[FN];
+    if constexpr (EPI == EPI_C16_BIAS_ADD) {
+      // This epilogue alone takes a NULL bias: the same loads through a descriptor whose range is then 0 bytes, so every load is out of range
+      // and returns zeros without touching memory -- four bf16 +0.0, the bits of a zero-filled vector --, added below like any other bias.
+      // One kernel set, one scalar select.
+      const __amdgpu_buffer_rsrc_t rsBiasOrNone = __builtin_amdgcn_make_buffer_rsrc((void*)g.counters, 0, g.counters ? (uint32_t)g.N * 2u : 0u, 0x00020000);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) {
+        const uint32_t n_b = (uint32_t)(tc.n0 + wave_n * CFG::TN + 16 * j + 4 * (lane >> 4));
+        bias[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsBiasOrNone, n_b * 2u, 0, 0));
+      }
+    } else {
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const int n_b = tc.n0 + wave_n * CFG::TN + 16 * j + 4 * (lane >> 4);
       bias[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsBias, (uint32_t)n_b * 2u, 0, 0));
     }
+    }
+    if constexpr (EPI != EPI_C16_BIAS_ADD) {
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
       for (int j = 0; j < FN; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[i][j][e] += (float)bias[j][e];
+    } else {
+      // ---- fused bias and residual (EPI_C16_BIAS_ADD, bgemm_mi355x_tn_bias_add): C = bf16((acc + float(bias[n])) + float(r[m][n])) ------------
+      // g.partial is the bf16 residual matrix r ([M][ldr], read-only, reinterpreted; ldr in g.tail_first -- the fields the aux kernels' z_out
+      // travels in).  The loads are family n's dact loads (hgemm_kernel_nn.hpp): the lane's four r of a fragment are one 8-byte load through a
+      // descriptor that starts at the tile's first row and ENDS AT r's LAST VALID ELEMENT (dact_z_range_bytes): a row at or past M reads zeros,
+      // a column group at or past N pad, the next row or zeros -- values the store text never stores.  Issued here, behind the K loop and the
+      // bias loads.  bias_residual_add (hgemm_residual.hpp) is the combine's and the reference kernel's text: two fp32 adds in this order.
+      // r may be C itself (ldr == ldc).  Every load of the wave's tile is issued and consumed in this block, in front of the store text below;
+      // the element a lane stores there -- its own or, behind the permlane swap, one of another lane of the SAME wave -- is computed from that
+      // element's r, so its store depends on its load; wave tiles are disjoint, and what a load reads outside its tile's M x N elements is
+      // never stored by this wave.
+      const uint32_t ldr = (uint32_t)g.tail_first;
+      const uint32_t r_bytes = dact_z_range_bytes(g.M, g.N, g.tail_first, tc.m0);
+      const __amdgpu_buffer_rsrc_t rsR =
+          __builtin_amdgcn_make_buffer_rsrc((void*)((const __bf16*)g.partial + (size_t)tc.m0 * ldr), 0, r_bytes, 0x00020000);
+#pragma unroll
+      for (int i = 0; i < FM; ++i) {
+        const uint32_t row = (uint32_t)dbias_row(wave_m, CFG::TM, i, lane);
+        bx4 r[FN];
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          const uint32_t n_r = (uint32_t)(tc.n0 + wave_n * CFG::TN + 16 * j + 4 * (lane >> 4));
+          r[j] = __builtin_bit_cast(bx4, (u32x2)__builtin_amdgcn_raw_buffer_load_b64(rsR, (row * ldr + n_r) * 2u, 0, 0));
+        }
+#pragma unroll
+        for (int j = 0; j < FN; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[i][j][e] = bias_residual_add(acc[i][j][e], (float)bias[j][e], (float)r[j][e]);
+      }
+    }
   }
 
   // ---- the rounded pre-activation as a second output (EPI_C16_BIAS_AUX + ACT, bgemm_mi355x_tn_bias_act_aux): z_out = bf16(z) ----------------
@@ -268,5 +315,17 @@ void launch_tn_bias_act_aux(const GemmArgs& g, int grid, hipStream_t stream, int
 HGEMM_TR_MEMBERS(HGEMM_TN_AUX_EXTERN, ACT_RELU, CfgTNB)        // hgemm_inst_g15.hip
 HGEMM_TR_MEMBERS(HGEMM_TN_AUX_EXTERN, ACT_GELU, CfgTNB)
 HGEMM_TR_MEMBERS(HGEMM_TN_AUX_EXTERN, ACT_GELU_TANH, CfgTNB)
+
+// The fused bias + residual set (bgemm_mi355x_tn_bias_add): the member's EPI_C16_BIAS_ADD kernel alone, the K slices again the 16-bit
+// set's EPI_SLAB kernels.  g.counters of the dispatch is the bias pointer or null, g.partial r, g.tail_first ldr (tr_launch, hgemm_api.hip).
+template <class CFG>
+void launch_tn_bias_add(const GemmArgs& g, int grid, hipStream_t stream, int epi, TimingSlot ts) {
+  if (epi == EPI_SLAB) return launch_tr<CFG, false>(g, grid, stream, epi, ts);
+  HGEMM_LAUNCH((CFG::template kernel<EPI_C16_BIAS_ADD>()), grid, CFG::THREADS, stream, ts, g);
+}
+#define HGEMM_TN_ADD_LAUNCHER(CFG, BM, BN, WM, WN, NB) launch_tn_bias_add<CFG<BM, BN, WM, WN, NB>>
+#define HGEMM_TN_ADD_INST(...) template void HGEMM_TN_ADD_LAUNCHER(__VA_ARGS__)(const GemmArgs&, int, hipStream_t, int, TimingSlot);
+#define HGEMM_TN_ADD_EXTERN(...) extern HGEMM_TN_ADD_INST(__VA_ARGS__)
+HGEMM_TR_MEMBERS(HGEMM_TN_ADD_EXTERN, CfgTNB)      // hgemm_inst_g21.hip
 
 }  // namespace hgemm_mi355x

@@ -116,7 +116,9 @@ struct ElemPos { int row, col; __device__ int m() const { return row; } __device
 struct QuadPos { size_t e; int N; __device__ int m() const { return (int)(e / N); } __device__ int n() const { return (int)(e % N); } };
 template <class T, int V>
 using vec_t = T __attribute__((ext_vector_type(V)));
-struct OutArgs { void* c; const void* bias; void* z; int ldc, ldz; bool accumulate; const void* b2; const void* bias2; };   // what TrKernels' launchers are handed (host)
+// what TrKernels' launchers are handed (host).  r / ldr: the read-only residual matrix of the add kinds and its row stride -- TrKernels' `z` /
+// ldz under the name the kinds use.  r may be c (ldr == ldc): early() loads r[m][n] and store() writes C[m][n] in the same thread, the load first.
+struct OutArgs { void* c; const void* bias; void* z; int ldc, ldz; bool accumulate; const void* b2; const void* bias2; const void* r; int ldr; };
 
 template <class T, int V>
 __device__ __forceinline__ vec_t<T, V> out_load(const T* p) { return *(const vec_t<T, V>*)p; }
@@ -198,6 +200,41 @@ struct OutDact {
   template <int V, class At> __device__ void store(At at, vec_t<float, V> s, vec_t<__bf16, V> z) const {
 #pragma unroll
     for (int i = 0; i < V; ++i) s[i] = dact_mul<ACT>(s[i], (float)z[i]);
+    out_store<V>(C + (size_t)at.m() * ldc + at.n(), s);
+  }
+};
+// the fused residual add (bgemm_mi355x_nn_add): C = bf16(residual_add(S, float(R[m][n]))), hgemm_residual.hpp's one fp32 add on the finished sum;
+// R is read-only at stride ldr and MAY BE C (ldr == ldc): the thread that stores C[m][n .. n + V) is the one that loaded R[m][n .. n + V) in
+// early(), in front of the sum -- the combine's quad and the reference kernel's element alike --, and no other thread touches those elements.
+// No __restrict__ on either pointer.
+struct OutAdd {
+  static constexpr int SUMS = 1;
+  __bf16* C; const __bf16* R; int ldc, ldr;
+  static OutAdd make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.r, o.ldc, o.ldr}; }
+  template <int V, class At> __device__ vec_t<__bf16, V> early(At at) const { return out_load<__bf16, V>(R + (size_t)at.m() * ldr + at.n()); }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, vec_t<__bf16, V> r) const {
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] = residual_add(s[i], (float)r[i]);
+    out_store<V>(C + (size_t)at.m() * ldc + at.n(), s);
+  }
+};
+// the same behind a bias (bgemm_mi355x_tn_bias_add): C = bf16(bias_residual_add(S, float(bias[n]), float(R[m][n]))), two fp32 adds in that order
+// and one rounding.  A null bias vector counts as +0.0, added like any other: the bits of a zero-filled vector (the gated kinds' rule).
+template <int V> struct BiasAddEarly { vec_t<__bf16, V> b, r; };
+struct OutBiasAdd {
+  static constexpr int SUMS = 1;
+  __bf16* C; const __bf16* bias; const __bf16* R; int ldc, ldr;
+  static OutBiasAdd make(const OutArgs& o) { return {(__bf16*)o.c, (const __bf16*)o.bias, (const __bf16*)o.r, o.ldc, o.ldr}; }
+  template <int V, class At> __device__ BiasAddEarly<V> early(At at) const {
+    BiasAddEarly<V> e;
+    e.b = (__bf16)0.0f;
+    if (bias) e.b = out_load<__bf16, V>(bias + at.n());
+    e.r = out_load<__bf16, V>(R + (size_t)at.m() * ldr + at.n());
+    return e;
+  }
+  template <int V, class At> __device__ void store(At at, vec_t<float, V> s, BiasAddEarly<V> e) const {
+#pragma unroll
+    for (int i = 0; i < V; ++i) s[i] = bias_residual_add(s[i], (float)e.b[i], (float)e.r[i]);
     out_store<V>(C + (size_t)at.m() * ldc + at.n(), s);
   }
 };
@@ -510,7 +547,7 @@ template <class Out>
 static void launch_combine(const float* partial, void* c, const void* bias, const void* bias2, void* z, int M, int N, int ldc, int ldz, int splits,
                            bool accumulate, hipStream_t stream, TimingSlot ts) {
   const CombineGrid cg = combine_grid(M, N);
-  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate, nullptr, bias2});
+  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate, nullptr, bias2, z, ldz});
   HGEMM_LAUNCH((hgemm_splitk_reduce_kernel<Out>), cg.grid, cg.threads, stream, ts, partial, out, M, N, splits);
 }
 // the fp32-C kind's combine is the kernel that kept its text (see there)
@@ -526,7 +563,7 @@ static void launch_reference(const void* A, const void* B, const void* B2, void*
                              int lda, int ldb, int ldc, int ldz, bool accumulate, hipStream_t stream, TimingSlot ts) {
   using T = typename Ops::T;
   dim3 grid((N + 63) / 64, (unsigned)std::min<long>(((long)M + 3) / 4, 65535));
-  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate, B2, bias2});
+  const Out out = Out::make({c, bias, z, ldc, ldz, accumulate, B2, bias2, z, ldz});
   HGEMM_LAUNCH((hgemm_generic_kernel<Ops, Out>), grid, 256, stream, ts, (const T*)A, (const T*)B, out, M, N, K, lda, ldb);
 }
 
@@ -569,6 +606,7 @@ static TrRow nn_row(TrEntry e) {
   r.launch[TR_BF16][TR_C16_DGATED + ACT_GELU] = &launch_nn_dgated<B, ACT_GELU>;
   r.launch[TR_BF16][TR_C16_DGATED + ACT_GELU_TANH] = &launch_nn_dgated<B, ACT_GELU_TANH>;
   r.launch[TR_BF16][TR_C16_DGATED + ACT_SILU] = &launch_nn_dgated<B, ACT_SILU>;
+  r.launch[TR_BF16][TR_C16_ADD] = &launch_nn_add<B>;
   return r;
 }
 template <int... G>
@@ -601,6 +639,7 @@ static TrRow tn_row(TrEntry e) {
   r.launch[TR_BF16][TR_C16_GATED_AUX + ACT_GELU] = &launch_tn_gated_aux<B, ACT_GELU>;
   r.launch[TR_BF16][TR_C16_GATED_AUX + ACT_GELU_TANH] = &launch_tn_gated_aux<B, ACT_GELU_TANH>;
   r.launch[TR_BF16][TR_C16_GATED_AUX + ACT_SILU] = &launch_tn_gated_aux<B, ACT_SILU>;
+  r.launch[TR_BF16][TR_C16_BIAS_ADD] = &launch_tn_bias_add<B>;
   return r;
 }
 #define HGEMM_TR_ROW(ROW, P, CFG, ...) ROW<__VA_ARGS__>(HGEMM_TR_ENTRY(P, CFG, __VA_ARGS__)),
@@ -624,6 +663,7 @@ const TrTable& tr_table_nn() {
     t.kernels[TR_BF16][TR_C16_DGATED + ACT_GELU] = tr_kernels<B, OutDgated<ACT_GELU>>();
     t.kernels[TR_BF16][TR_C16_DGATED + ACT_GELU_TANH] = tr_kernels<B, OutDgated<ACT_GELU_TANH>>();
     t.kernels[TR_BF16][TR_C16_DGATED + ACT_SILU] = tr_kernels<B, OutDgated<ACT_SILU>>();
+    t.kernels[TR_BF16][TR_C16_ADD] = tr_kernels<B, OutAdd>();
     return t;
   }();
   return table;
@@ -663,6 +703,7 @@ const TrTable& tr_table_tn() {
     t.kernels[TR_BF16][TR_C16_GATED_AUX + ACT_GELU] = tr_kernels<B, OutGatedAux<ACT_GELU>>();
     t.kernels[TR_BF16][TR_C16_GATED_AUX + ACT_GELU_TANH] = tr_kernels<B, OutGatedAux<ACT_GELU_TANH>>();
     t.kernels[TR_BF16][TR_C16_GATED_AUX + ACT_SILU] = tr_kernels<B, OutGatedAux<ACT_SILU>>();
+    t.kernels[TR_BF16][TR_C16_BIAS_ADD] = tr_kernels<B, OutBiasAdd>();
     return t;
   }();
   return table;

@@ -48,6 +48,11 @@
 //   hgemm_tune check|bench --layout tn --bf16 --gated-aux relu|gelu|gelu_tanh|silu [...]   bgemm_mi355x_launch_tn_gated_aux: C as --gated judges it,
 //                                                     g_out and u_out bit for bit, sentinel bytes behind each of the three; bench against
 //                                                     bgemm_mi355x_launch_tn_bias on the stacked weight at 2N + the element-wise gate kernel
+//   hgemm_tune check|bench --layout tn --bf16 --bias-add [...]   bgemm_mi355x_launch_tn_bias_add: C = bf16((S + bias) + r) bit for bit, every run
+//                                                     once out of place and once in place (r == c); bench against bgemm_mi355x_launch_tn_bias +
+//                                                     an element-wise add at the same member and splits
+//   hgemm_tune check|bench --layout nn --bf16 --nn-add [...]     bgemm_mi355x_launch_nn_add: C = bf16(S + r), the same check; bench against
+//                                                     bgemm_mi355x_launch_nn + an element-wise add
 //   hgemm_tune check|bench --layout nn --bf16 --dgated relu|gelu|gelu_tanh|silu [...]   bgemm_mi355x_launch_nn_dgated: ReLU bit for bit, the
 //                                                     others inside the two bars of hgemm_dgated.hpp, sentinel bytes behind both outputs; bench
 //                                                     against bgemm_mi355x_launch_nn + an element-wise kernel at the same member and splits
@@ -91,6 +96,7 @@
 #include "../hgemm_dbias.hpp"
 #include "../hgemm_dgated.hpp"
 #include "../hgemm_gated.hpp"
+#include "../hgemm_residual.hpp"
 
 // Ablation switches exist only in the -DHGEMM_ABLATION build of the library (build.py: HGEMM_LIB_SUFFIX=ablation
 // HGEMM_EXTRA_HIPFLAGS=-DHGEMM_ABLATION); against the shipping library the symbol is absent and --debug refuses.
@@ -1049,7 +1055,7 @@ static int cmd_bench(const Shape& sh, const char* cfg_name, int splits, int grou
 
 // ---- The transposed-read variants: `check --layout nn|ta|tn ...`, `bench --layout nn|ta|tn ...` ------------------------------------------
 // Fifteen call kinds -- nn, ta, ta --c32, nn --bf16, ta --bf16, ta --c32 --bf16, tn --bf16, tn --bf16 --bias, tn --bf16 --bias --act A,
-// ... --act A --aux, nn --bf16 --dact A, ... --dact A --dbias, tn --bf16 --gated A, nn --bf16 --dgated A, tn --bf16 --gated-aux A --, each one row of kVariants that main resolves once from the flags; the
+// ... --act A --aux, nn --bf16 --dact A, ... --dact A --dbias, tn --bf16 --gated A, nn --bf16 --dgated A, tn --bf16 --gated-aux A, tn --bf16 --bias-add, nn --bf16 --nn-add (seventeen) --, each one row of kVariants that main resolves once from the flags; the
 // activation A is a run-time value of the call (TrCall::act), not of the row.  ONE check (tr_check) and ONE bench driver (tr_bench) serve
 // them all; a row names what differs: its operand scheme, its judge of one finished run, its closing sentence, its bench description.
 // The check: every member x {plain, non-temporal stores, two-pass splits 2 / 5} (fp32 C: x {store, accumulate}) from NaN-filled outputs.
@@ -1072,12 +1078,14 @@ enum Elem { kF16, kBF16 };
 enum ZRole { kZNone, kZRead, kZWritten };   // no z; Z is an input (dact); z_out is a second output (aux)
 struct OutKind { bool c32, bias; ZRole z; bool db32, act; bool gated = false;       // gated: two weights, two biases (bgemm_mi355x_tn_gated)
                  bool dgated = false;      // dgated: two saved matrices in, two 16-bit matrices out (bgemm_mi355x_nn_dgated)
-                 bool gaux = false; };     // gaux (with gated): g_out and u_out as two more 16-bit outputs (bgemm_mi355x_tn_gated_aux)
+                 bool gaux = false;        // gaux (with gated): g_out and u_out as two more 16-bit outputs (bgemm_mi355x_tn_gated_aux)
+                 bool add = false; };      // add: a read-only residual matrix r [M][N] (TrCall::z), with a bias (tn) or without (nn); no activation
 static const OutKind kOutC16 = {false, false, kZNone, false, false}, kOutC32 = {true, false, kZNone, false, false},
                      kOutBias = {false, true, kZNone, false, false}, kOutBiasAct = {false, true, kZNone, false, true},
                      kOutBiasAux = {false, true, kZWritten, false, true}, kOutDact = {false, false, kZRead, false, true},
                      kOutDactDbias = {false, false, kZRead, true, true}, kOutGated = {false, false, kZNone, false, true, true},
-                     kOutDgated = {false, false, kZNone, false, true, false, true}, kOutGatedAux = {false, false, kZNone, false, true, true, false, true};
+                     kOutDgated = {false, false, kZNone, false, true, false, true}, kOutGatedAux = {false, false, kZNone, false, true, true, false, true},
+                     kOutBiasAdd = {false, true, kZNone, false, false, false, false, false, true}, kOutAdd = {false, false, kZNone, false, false, false, false, false, true};
 static const char* const kActNames[] = {"", "relu", "gelu", "gelu_tanh", "silu"};   // silu: --gated alone
 // fp16 values as fp16 or as bf16 bits, ready for upload
 static std::vector<uint16_t> operand_bits(const std::vector<f16>& v, Elem elem) {
@@ -1170,6 +1178,18 @@ static int planned_gated_aux(const TrCall& o, const Shape& sh) {
 }
 static int gated_aux_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_tn_gated_aux_runs(cfg, M, N, K, lda, ldb, ldc, N); }
 
+// the fused residual add (bgemm_mi355x_tn_bias_add, bgemm_mi355x_nn_add; z = r, ldr = N; r == c is the in-place call)
+static int launch_bias_add(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_tn_bias_add(cfg, splits, o.a, o.b, o.bias, o.z, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, nullptr);
+}
+static int planned_bias_add(const TrCall& o, const Shape& sh) { return bgemm_mi355x_tn_bias_add(o.a, o.b, o.bias, o.z, o.c, sh.M, sh.N, sh.K, nullptr); }
+static int bias_add_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_tn_bias_add_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+static int launch_nn_add(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
+  return bgemm_mi355x_launch_nn_add(cfg, splits, o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, nullptr);
+}
+static int planned_nn_add(const TrCall& o, const Shape& sh) { return bgemm_mi355x_nn_add(o.a, o.b, o.z, o.c, sh.M, sh.N, sh.K, nullptr); }
+static int nn_add_runs(int cfg, int M, int N, int K, int lda, int ldb, int ldc) { return bgemm_mi355x_nn_add_runs(cfg, M, N, K, lda, ldb, ldc, N); }
+
 // the gated MLP's input gradient (bgemm_mi355x_nn_dgated; ldz = ldc = N throughout)
 static int launch_dgated(int cfg, int splits, const TrCall& o, const Shape& sh, int lda, int ldb) {
   return bgemm_mi355x_launch_nn_dgated(cfg, splits, o.a, o.b, o.z, o.b2, o.c, o.c2, sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, o.act, nullptr);
@@ -1191,13 +1211,14 @@ static void warm_hipblaslt(bool autotune) {
   if (autotune) hgemm_hipblaslt_autotune_init();
 }
 static void bench_nn(TrBench&), bench_ta(TrBench&), bench_ta_c32(TrBench&), bench_bf16(TrBench&), bench_tn_bf16(TrBench&), bench_tn_bias(TrBench&),
-    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&), bench_tn_gated(TrBench&), bench_nn_dgated(TrBench&), bench_tn_gated_aux(TrBench&);
+    bench_tn_bias_act(TrBench&), bench_tn_aux(TrBench&), bench_nn_dact(TrBench&), bench_nn_dact_dbias(TrBench&), bench_tn_gated(TrBench&), bench_nn_dgated(TrBench&), bench_tn_gated_aux(TrBench&), bench_tn_bias_add(TrBench&), bench_nn_add(TrBench&);
 static const BenchDesc kBenchNN = {77, warm_hipblaslt, bench_nn}, kBenchTA = {91, warm_none, bench_ta}, kBenchTAC32 = {91, warm_none, bench_ta_c32},
                        kBenchBF16 = {91, warm_rocblas, bench_bf16}, kBenchTN = {91, warm_rocblas, bench_tn_bf16}, kBenchTNBias = {91, warm_none, bench_tn_bias},
                        kBenchTNBiasAct = {91, warm_none, bench_tn_bias_act}, kBenchTNAux = {91, warm_none, bench_tn_aux},
                        kBenchNNDact = {91, warm_none, bench_nn_dact}, kBenchNNDactDbias = {91, warm_none, bench_nn_dact_dbias},
                        kBenchTNGated = {91, warm_none, bench_tn_gated}, kBenchNNDgated = {91, warm_none, bench_nn_dgated},
-                       kBenchTNGatedAux = {91, warm_none, bench_tn_gated_aux};
+                       kBenchTNGatedAux = {91, warm_none, bench_tn_gated_aux}, kBenchTNBiasAdd = {91, warm_none, bench_tn_bias_add},
+                       kBenchNNAdd = {91, warm_none, bench_nn_add};
 
 // What tr_check is told about one kind (the functions themselves: below, above tr_check).
 struct Check;
@@ -1207,11 +1228,12 @@ struct CheckDesc {
   void (*summary)(const Check&);  // the closing line(s)
 };
 static int operands_zero_one(Check&), operands_small_int(Check&), operands_gated(Check&), judge_exact(Check&), judge_act(Check&), judge_dbias(Check&), judge_gated(Check&),
-           operands_dgated(Check&), judge_dgated(Check&), judge_gated_aux(Check&);
-static void summary_exact(const Check&), summary_act(const Check&), summary_gated(const Check&), summary_dgated(const Check&), summary_gated_aux(const Check&);
+           operands_dgated(Check&), judge_dgated(Check&), judge_gated_aux(Check&), operands_add(Check&), judge_add(Check&);
+static void summary_exact(const Check&), summary_act(const Check&), summary_gated(const Check&), summary_dgated(const Check&), summary_gated_aux(const Check&), summary_add(const Check&);
 static const CheckDesc kCheckExact = {operands_zero_one, judge_exact, summary_exact}, kCheckAct = {operands_small_int, judge_act, summary_act},
                        kCheckDbias = {operands_small_int, judge_dbias, summary_act}, kCheckGated = {operands_gated, judge_gated, summary_gated},
-                       kCheckDgated = {operands_dgated, judge_dgated, summary_dgated}, kCheckGatedAux = {operands_gated, judge_gated_aux, summary_gated_aux};
+                       kCheckDgated = {operands_dgated, judge_dgated, summary_dgated}, kCheckGatedAux = {operands_gated, judge_gated_aux, summary_gated_aux},
+                       kCheckAdd = {operands_add, judge_add, summary_add};
 
 struct Variant {
   const TrLayout* L;
@@ -1225,7 +1247,7 @@ struct Variant {
   // "ta-c32-bf16" / "--layout ta --c32 --bf16"; with an activation the check's label, "tn-bf16-bias-gelu-aux" / "nn-bf16-dact-relu-dbias"
   std::string words(const char* layout, const char* sep, int act = 0) const {
     std::string w = std::string(layout) + L->label + (out->c32 ? std::string(sep) + "c32" : "") + (elem == kBF16 ? std::string(sep) + "bf16" : "") +
-                    (out->bias ? std::string(sep) + "bias" : "");
+                    (out->bias ? std::string(sep) + "bias" : "") + (out->add ? std::string(sep) + "add" : "");
     if (act) w += (out->z == kZRead ? std::string(sep) + "dact" : out->gaux ? std::string(sep) + "gated-aux" : out->gated ? std::string(sep) + "gated" : out->dgated ? std::string(sep) + "dgated" : "") + sep + kActNames[act] + (out->z == kZWritten ? std::string(sep) + "aux" : "") +
                   (out->db32 ? std::string(sep) + "dbias" : "");
     return w;
@@ -1248,11 +1270,14 @@ static const Variant kVariants[] = {
     {&kLayoutTN, kBF16, &kOutGated, bgemm_mi355x_tn_gated_runs, launch_gated, planned_gated, &kCheckGated, &kBenchTNGated},
     {&kLayoutNN, kBF16, &kOutDgated, dgated_runs, launch_dgated, planned_dgated, &kCheckDgated, &kBenchNNDgated},
     {&kLayoutTN, kBF16, &kOutGatedAux, gated_aux_runs, launch_gated_aux, planned_gated_aux, &kCheckGatedAux, &kBenchTNGatedAux},
+    {&kLayoutTN, kBF16, &kOutBiasAdd, bias_add_runs, launch_bias_add, planned_bias_add, &kCheckAdd, &kBenchTNBiasAdd},
+    {&kLayoutNN, kBF16, &kOutAdd, nn_add_runs, launch_nn_add, planned_nn_add, &kCheckAdd, &kBenchNNAdd},
 };
 // What the command line says of the call; act, dact: 0, or the A of --act A / --dact A as HGEMM_ACT_RELU / _GELU / _GELU_TANH.
 struct TrFlags {
   std::string layout;
   bool bf16 = false, c32 = false, bias = false, aux = false, dbias = false;
+  bool bias_add = false, nn_add = false;   // --bias-add (a bias kind: sets `bias` too), --nn-add
   int act = 0, dact = 0, gated = 0, dgated = 0, gated_aux = 0;
   int activation() const { return act ? act : dact ? dact : gated ? gated : dgated ? dgated : gated_aux; }
 };
@@ -1262,7 +1287,7 @@ static const Variant* resolve_variant(const TrFlags& f) {
     if (f.layout == v.L->label && (v.elem == kBF16) == f.bf16 && v.out->c32 == f.c32 && v.out->bias == f.bias && v.out->db32 == f.dbias &&
         v.out->z == (f.dact ? kZRead : f.aux ? kZWritten : kZNone) && v.out->act == (f.activation() != 0) && v.out->gated == (f.gated != 0 || f.gated_aux != 0) &&
         v.out->dgated == (f.dgated != 0) && v.out->gaux == (f.gated_aux != 0) && !((f.gated || f.dgated || f.gated_aux) && (f.act || f.dact)) &&
-        (f.gated != 0) + (f.dgated != 0) + (f.gated_aux != 0) <= 1)
+        (f.gated != 0) + (f.dgated != 0) + (f.gated_aux != 0) <= 1 && v.out->add == (f.bias_add || f.nn_add))
       return &v;
   return nullptr;
 }
@@ -1652,6 +1677,70 @@ static void summary_gated_aux(const Check& K) {
   printf("check %s: g_out and u_out bit-exact against bf16(g) and bf16(u) in every run\n", K.lay.c_str());
 }
 
+// ---- The residual kinds' check (--bias-add with --layout tn --bf16, --nn-add with --layout nn --bf16) ------------------------------------------
+// C = bf16((S + bias[n]) + r[m][n]) / bf16(S + r[m][n]), hgemm_residual.hpp's text on the host.  A, B and the bias as in operands_small_int: S
+// is exact in fp32 in any order (verified per element); r a seeded matrix of multiples of 1/32 in [-4, 4] (bf16 values, some -0).  Every run
+// is judged bit for bit and then made once more IN PLACE -- C refilled with r and passed as r too -- and judged again.
+static int operands_add(Check& K) {
+  const Shape& sh = K.sh;
+  const size_t cn = K.cn;
+  int j = 0;
+  while ((2 << j) <= sh.K) ++j;   // floor(log2 K)
+  const double scale = ldexp(1.0, -std::max(j - 2, 0));
+  uint64_t lcg = 0x9E3779B97F4A7C15ull + (uint64_t)sh.M * 1315423911u + (uint64_t)sh.N * 2654435761u + (uint64_t)sh.K;
+  auto next = [&]() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(lcg >> 33); };
+  std::vector<int8_t> ai((size_t)sh.M * sh.K), bi((size_t)sh.K * sh.N);
+  for (auto& v : ai) v = (int8_t)((int)(next() % 5) - 2);
+  for (auto& v : bi) v = (int8_t)((int)(next() % 5) - 2);
+  for (int8_t v : ai) K.h.a.push_back(bf16_rne((float)(v * scale)));
+  for (int8_t v : bi) K.h.b.push_back(bf16_rne((float)v));
+  std::vector<float> bias(sh.N, 0.0f);
+  for (int n = 0; n < sh.N && K.V.out->bias; ++n) {
+    bias[n] = (float)(((n * 37 + 11) % 513) - 256) / 256.0f;
+    K.h.bias.push_back(bf16_rne(bias[n]));
+  }
+  K.h.z.resize(cn), K.h.want[0].resize(cn * 2);
+  const std::vector<int8_t> bt = K.V.L->b_col_major ? bi : transposed(bi, sh.K, sh.N);   // [N][K]
+  for (int m = 0; m < sh.M; ++m)
+    for (int n = 0; n < sh.N; ++n) {
+      int acc = 0;
+      const int8_t *ar = &ai[(size_t)m * sh.K], *br = &bt[(size_t)n * sh.K];
+      for (int k = 0; k < sh.K; ++k) acc += ar[k] * br[k];
+      const double s = acc * scale;
+      if ((double)(float)s != s) { fprintf(stderr, "check %s: S is not exact in fp32 at %d_%d_%d\n", K.lay.c_str(), sh.M, sh.N, sh.K); return 2; }
+      const size_t i = (size_t)m * sh.N + n;
+      K.h.z[i] = (i % 29 == 7) ? (uint16_t)0x8000 : bf16_rne((float)((int)(next() % 257) - 128) / 32.0f);
+      const float r = (float)bf16_value(K.h.z[i]);
+      const uint16_t w = bf16_rne(K.V.out->bias ? hgemm_mi355x::bias_residual_add((float)s, bias[n], r) : hgemm_mi355x::residual_add((float)s, r));
+      memcpy(&K.h.want[0][i * 2], &w, 2);
+    }
+  return 0;
+}
+static int judge_add(Check& K) {
+  judge_exact(K);   // the out-of-place run
+  const Shape& sh = K.sh;
+  const void* r = K.call.z;
+  HIP_OK(hipMemcpy(K.call.c, r, K.cn * 2, hipMemcpyDeviceToDevice));
+  K.call.z = K.call.c;
+  const int st = K.V.launch(K.cfg, K.splits, K.call, sh, K.V.L->lda(sh), K.V.L->ldb(sh));
+  K.call.z = const_cast<void*>(r);
+  const hipError_t e = hipDeviceSynchronize();
+  if (st != HGEMM_OK || e != hipSuccess) {
+    printf("FAIL %s %d_%d_%d %s s=%d in place: status %d hip %d\n", K.lay.c_str(), sh.M, sh.N, sh.K, K.cname, K.splits & HGEMM_SPLITK_MASK, st, (int)e);
+    ++K.failures;
+    return e != hipSuccess ? 3 : 0;
+  }
+  HIP_OK(hipMemcpy(K.got.data(), K.call.c, K.cn * 2, hipMemcpyDeviceToHost));
+  const int before = K.failures;
+  judge_exact(K);
+  if (K.failures != before) printf("     (the in-place run, r == c)\n");
+  return 0;
+}
+static void summary_add(const Check& K) {
+  printf("check %s: %d runs, %d failures (each run out of place and in place, bit-exact against bf16(%s) of the exact S)\n", K.lay.c_str(), K.runs, K.failures,
+         K.V.out->bias ? "(S + bias) + r" : "S + r");
+}
+
 // ---- The dgated kind's check (--dgated A with --layout nn --bf16; bgemm_mi355x_nn_dgated) ------------------------------------------------------
 // dg = bf16(dact_mul(fl32(S u), g)), du = bf16(fl32(act(g) S)): A and B as in operands_small_int, so S is exact in fp32 in any order (verified
 // per element); g and u seeded matrices of multiples of 1/32 in [-4, 4] (bf16 values; both signs, zeros, some -0).  The bars: ReLU bit for bit
@@ -1744,7 +1833,7 @@ static int tr_check(const Variant& V, int act, std::vector<Shape> shapes) {
     TrCall& call = K.call;
     call = {dev.upload(K.h.a.data(), K.h.a.size() * 2), dev.upload(K.h.b.data(), K.h.b.size() * 2),
             O.bias || O.gated ? dev.upload(K.h.bias.data(), K.h.bias.size() * 2) : nullptr, dev.alloc(cn * esz + (O.gated || O.dgated ? GATED_GUARD : 0)), 0,
-            O.z == kZRead || O.dgated ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : O.gaux ? dev.alloc(cn * 2 + GATED_GUARD) : nullptr,
+            O.z == kZRead || O.dgated || O.add ? dev.upload(K.h.z.data(), cn * 2) : O.z == kZWritten ? dev.alloc(cn * 2) : O.gaux ? dev.alloc(cn * 2 + GATED_GUARD) : nullptr,
             O.db32 ? (float*)dev.alloc((sh.N + DBIAS_GUARD) * sizeof(float)) : nullptr, act};
     if (O.gated) {
       call.b2 = dev.upload(K.h.b2.data(), K.h.b2.size() * 2), call.bias2 = dev.upload(K.h.bias2.data(), K.h.bias2.size() * 2);
@@ -2135,6 +2224,52 @@ static void bench_tn_gated_aux(TrBench& B) {
   B.verdict("gated_aux_le_unfused", 0, 1, true);
 }
 
+// tn --bf16 --bias-add: bgemm_mi355x_launch_tn_bias_add, in place on r, against the route it replaces at the SAME member and splits --
+// bgemm_mi355x_launch_tn_bias into a scratch C, then an element-wise x += c over the residual stream (6 M N bytes; its launch is not
+// checked) --, and, context only, bgemm_mi355x_launch_tn_bias alone: the price of the loads.  "bias_add_le_unfused", within the unfused
+// route's spread.  nn --bf16 --nn-add: the same with bgemm_mi355x_launch_nn_add and bgemm_mi355x_launch_nn, "nn_add_le_unfused".
+__global__ void residual_elementwise_kernel(__bf16* __restrict__ x, const __bf16* __restrict__ c, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+    x[i] = (__bf16)hgemm_mi355x::residual_add((float)c[i], (float)x[i]);
+}
+static void bench_tn_bias_add(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), grid = elementwise_grid(cn);
+  const TnBiasBufs t = tn_bias_bufs(B);
+  const TrBench::PerSet ab = t.ab, btb = t.btb, cb = t.cb, bias = t.bias, xb = B.alloc(cn * 2);
+  for (void* p : xb) HIP_OK(hipMemset(p, 0, cn * 2));
+  B.add("bias_add", [=](Buffers&, size_t i) {
+    return bgemm_mi355x_launch_tn_bias_add(cfg, splits, ab[i], btb[i], bias[i], xb[i], xb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, nullptr);
+  });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
+    residual_elementwise_kernel<<<grid, 256>>>((__bf16*)xb[i], (const __bf16*)cb[i], cn);
+    return st;
+  });
+  B.add("bias", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_tn_bias(cfg, splits, ab[i], btb[i], bias[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
+  B.head("\"output\": \"c16_bias_add\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("bias_add_le_unfused", 0, 1, true);
+}
+static void bench_nn_add(TrBench& B) {
+  const Shape sh = B.sh;
+  const size_t cn = B.cn;
+  const int cfg = B.cfg, splits = B.splits, lda = B.V.L->lda(sh), ldb = B.V.L->ldb(sh), grid = elementwise_grid(cn);
+  const TrBench::PerSet ab = B.to_bf16(B.of(&Buffers::a), B.a_elems), bb = B.to_bf16(B.of(&Buffers::b), B.b_elems), cb = B.alloc(cn * 2), xb = B.alloc(cn * 2);
+  for (void* p : xb) HIP_OK(hipMemset(p, 0, cn * 2));
+  B.add("nn_add", [=](Buffers&, size_t i) {
+    return bgemm_mi355x_launch_nn_add(cfg, splits, ab[i], bb[i], xb[i], xb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, sh.N, nullptr);
+  });
+  B.add("unfused", [=](Buffers&, size_t i) {
+    const int st = bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr);
+    residual_elementwise_kernel<<<grid, 256>>>((__bf16*)xb[i], (const __bf16*)cb[i], cn);
+    return st;
+  });
+  B.add("nn", [=](Buffers&, size_t i) { return bgemm_mi355x_launch_nn(cfg, splits, ab[i], bb[i], cb[i], sh.M, sh.N, sh.K, lda, ldb, sh.N, nullptr); });
+  B.head("\"output\": \"c16_add\", \"elem\": \"bf16\", \"config\": \"%s\", \"splits\": %d, \"runs\": %d", B.V.L->config_name(cfg), splits, B.V.runs_at(cfg, sh));
+  B.verdict("nn_add_le_unfused", 0, 1, true);
+}
+
 // tn --bf16 --bias --act A: the planned bgemm_mi355x_tn_bias_act call against the path it replaces -- bgemm_mi355x_launch_tn_bias with the
 // same member and splits followed by the element-wise activation kernel above (its launch is not checked: the contender answers with the
 // product's status) --, and, context only, the plain bias call.  The one condition: fused <= unfused within the unfused path's own
@@ -2317,6 +2452,8 @@ int main(int argc, char** argv) {
       for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.gated_aux = k;
       if (!tr.gated_aux) { fprintf(stderr, "--gated-aux takes relu, gelu, gelu_tanh or silu\n"); return 2; }
     }
+    else if (a == "--bias-add") tr.bias_add = tr.bias = true;
+    else if (a == "--nn-add") tr.nn_add = true;
     else if (a == "--dgated") {
       const std::string nm = next();
       for (int k = 1; k <= 4; ++k) if (nm == kActNames[k]) tr.dgated = k;
@@ -2383,6 +2520,8 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--gated-aux goes with --layout tn --bf16 (bgemm_mi355x_tn_gated_aux)\n");
     return 2;
   }
+  if (tr.bias_add && !(tr.bf16 && tr.layout == "tn" && !tr.activation() && !tr.aux)) { fprintf(stderr, "--bias-add goes with --layout tn --bf16 (bgemm_mi355x_tn_bias_add)\n"); return 2; }
+  if (tr.nn_add && !(tr.bf16 && tr.layout == "nn" && !tr.activation() && !tr.bias)) { fprintf(stderr, "--nn-add goes with --layout nn --bf16 (bgemm_mi355x_nn_add)\n"); return 2; }
   const Variant* variant = resolve_variant(tr);
   if (variant && mode != "check" && mode != "bench") {
     fprintf(stderr, "--layout %s%s goes with check or bench\n", tr.layout.c_str(), variant->L->b_col_major ? " --bf16" : "");

@@ -4,6 +4,9 @@
  *
  *     C[M,N] (fp16) = A[M,K] (fp16) x B[K,N] (fp16),  fp32 accumulate, alpha = 1, beta = 0
  *
+ * Two calls add an existing bf16 matrix to the product (beta = 1, in place if wished): bgemm_mi355x_tn_bias_add and bgemm_mi355x_nn_add,
+ * the two ends of a residual block; the fp32 C of the _ta_c32 calls accumulates.  Every other entry point computes beta = 0.
+ *
  * Everything here is `extern "C"`, plain pointers and ints; no torch types.  The torch
  * extension `hgemm_lib` (cuda-l2_amd/pybind/hgemm_mi355x_{fp16,fp32}.cc) is a thin shim over
  * these entry points and exports the 15 Python names the reference harness binds
@@ -697,6 +700,8 @@ int bgemm_mi355x_nn_dgated_runs(int nn_config, int M, int N, int K, int lda, int
  * anything else is answered by the reference kernel (status 0, the same semantics).
  * Refused with HGEMM_ERR_BAD_ARG: everything bgemm_mi355x_tn_gated refuses, a NULL g_out or u_out, g_out == u_out, either of them equal
  * to c, ldz < N.  Overlap of the three outputs with each other or with an input is the caller's error.
+ * The two ends of the chain that meet the residual stream are bgemm_mi355x_tn_bias_add (X_out = X_in + H x Wd^T + b) and
+ * bgemm_mi355x_nn_add at K = 2N (dX = [dG|dU] x [Wg;Wu] + dX_out), below.
  * Out of scope: fp16, a bias gradient, more than two saved matrices. */
 /* planned, contiguous (lda = ldb = K, ldc = ldz = N) */
 int bgemm_mi355x_tn_gated_aux(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c,
@@ -706,6 +711,59 @@ int bgemm_mi355x_launch_tn_gated_aux(int tn_config, int splits, const void* a, c
                                      int ldb, int ldc, int ldz, int act, void* stream);
 /* bgemm_mi355x_tn_gated_runs with g_out's and u_out's conditions added; 0 for ldz < N */
 int bgemm_mi355x_tn_gated_aux_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldz);
+
+/* ------------------------------------------------------------------------------------------
+ * Forward product with a fused bias and residual add: X_out = X_in + (H x Wd^T + b), a down projection (or an attention output
+ * projection) written straight into the residual stream.  Operands, layout, strides and scope are bgemm_mi355x_tn_bias's; `r` = X_in is a
+ * bf16 matrix [M][ldr], read-only.  The vendor libraries' beta = 1.
+ * Replaces bgemm_mi355x_tn_bias followed by an element-wise add: a second launch, 6 M N more bytes and a second bf16 rounding.
+ * Semantics, exactly:  z       = fl32( S[m][n] + float(bias[n]) )        (bgemm_mi355x_tn_bias's value before its rounding)
+ *                      C[m][n] = bf16_rne( fl32( z + float(r[m][n]) ) )
+ *   - S is the finished fp32 sum: the accumulator of a plain launch, or the slabs of a two-pass plan added in split order.
+ *   - Two fp32 adds IN THIS ORDER, then one rounding.  Nothing is added to a slab.
+ *   - bias == NULL means a vector of +0.0, bit for bit (the gated calls' rule): a layer without a bias has no other call to fall back on.
+ *   - Identity with bgemm_mi355x_launch_tn_bias (same tn_config, splits word and arguments): for an r of +0.0, C equals that call's C
+ *     wherever z is not -0; for z = -0 this call gives +0 (-0 + +0 = +0) where that call gives -0.
+ * In place: r == c with ldr == ldc is allowed and defined -- each C[m][n] is computed from the OLD r[m][n] (x += f(h)), in the kernels, in
+ * the two-pass combine and in the reference kernel alike; pad columns of c stay untouched.  r == c with ldr != ldc: HGEMM_ERR_BAD_ARG.  Any
+ * other overlap of r and c, and an overlap of c with a, b_col_major or bias, is the caller's error, as in bgemm_mi355x_tn_bias.
+ * r has bgemm_mi355x_nn_dact's rules for z: ldr >= N (less: HGEMM_ERR_BAD_ARG); 16-byte aligned, ldr % 8 == 0 and (BM ldr + N) 2 bytes below
+ * 2 GiB, or the reference kernel answers (status 0, the same semantics).  The kernels read r through a range that ends at its last valid
+ * element (M - 1, N - 1): no byte behind it is touched and pad columns do not matter.
+ * Refused with HGEMM_ERR_BAD_ARG: a NULL a, b_col_major, r or c, bad strides, an id outside the table.
+ * The table, ids, names, plan, workspace size and reserve call are bgemm_mi355x_tn_*'s: the tiles, cuts and slabs of a call are those of the
+ * bgemm_mi355x_launch_tn_bias call with the same arguments, and so are the splits word, HGEMM_PLAN_NT_STORE, the statuses and the capture
+ * behaviour (a captured split call without a workspace runs unsplit, status 0, and allocates nothing).
+ * Out of scope: beta other than 1, an fp32 or fp16 r, an activation behind the add, fp16, the TA layout (its fp32 form accumulates), the
+ * gated calls. */
+/* planned, contiguous (lda = ldb = K, ldc = ldr = N) */
+int bgemm_mi355x_tn_bias_add(const void* a, const void* b_col_major, const void* bias, const void* r, void* c, int M, int N, int K, void* stream);
+int bgemm_mi355x_launch_tn_bias_add(int tn_config, int splits, const void* a, const void* b_col_major, const void* bias, const void* r, void* c,
+                                    int M, int N, int K, int lda, int ldb, int ldc, int ldr, void* stream);
+/* 1 when the call (with aligned pointers) runs one of the family's kernels: bgemm_mi355x_tn_bias_runs with r's conditions added; 0 for
+ * ldr < N */
+int bgemm_mi355x_tn_bias_add_runs(int tn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldr);
+
+/* ------------------------------------------------------------------------------------------
+ * Input gradient with a fused residual add: dX = dZ x W + dX_out, the gradient that reaches a residual block's input -- the skip
+ * connection carries dX_out straight through.  Operands are bgemm_mi355x_nn's (a = dZ [M][lda], b = W [K][ldb] row-major; for the gated
+ * layer a = [dG|dU] and b = [Wg;Wu] with K = 2N of that layer); `r` = dX_out is a bf16 matrix [M][ldr], read-only.  There is no bias: a
+ * gradient has none.
+ * Replaces bgemm_mi355x_nn followed by an element-wise add: a second launch, 6 M N more bytes and a second bf16 rounding.
+ * Semantics, exactly:  C[m][n] = bf16_rne( fl32( S[m][n] + float(r[m][n]) ) )
+ *   - S is the finished fp32 sum: the accumulator of a plain launch, or the slabs of a two-pass plan added in split order.  ONE fp32 add on
+ *     the finished sum, then one rounding.  Nothing is added to a slab.
+ * In place, r's rules, the refusals and what is out of scope are bgemm_mi355x_tn_bias_add's: r == c needs ldr == ldc, each C[m][n] is
+ * computed from the old r[m][n]; r is 16-byte aligned with ldr % 8 == 0 and (BM ldr + N) 2 bytes below 2 GiB, or the reference kernel answers.
+ * The table, ids, names, plan, workspace size and reserve call are hgemm_mi355x_nn_*'s: the tiles, cuts and slabs of a call are those of the
+ * bgemm_mi355x_launch_nn call with the same arguments, and so are the splits word, HGEMM_PLAN_NT_STORE, the statuses and the capture
+ * behaviour. */
+/* planned, contiguous (lda = K, ldb = ldc = ldr = N) */
+int bgemm_mi355x_nn_add(const void* a, const void* b, const void* r, void* c, int M, int N, int K, void* stream);
+int bgemm_mi355x_launch_nn_add(int nn_config, int splits, const void* a, const void* b, const void* r, void* c, int M, int N, int K,
+                               int lda, int ldb, int ldc, int ldr, void* stream);
+/* bgemm_mi355x_nn_dact_runs(nn_config, M, N, K, lda, ldb, ldc, ldr): r has z's conditions; 0 for ldr < N */
+int bgemm_mi355x_nn_add_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldr);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
