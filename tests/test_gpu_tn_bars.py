@@ -403,6 +403,17 @@ def test_the_other_bf16_calls_round_the_same_operands_to_nearest_even(g, L, side
 
 
 # ---- 4. the reach rule, both sides executed ----------------------------------------------------------------------------------------------
+def largest_stride(runs, least):
+    """The largest stride (a multiple of 8, from `least` on) at which runs(stride) still holds -- by bisection; runs is monotone in the
+    stride (a call's _runs function with every other argument fixed)."""
+    lo, hi = least // 8, 1 << 27                       # 8 x 2^27 = 2^30 elements: beyond the reach of every member and K >= 64
+    assert runs(8 * lo) and not runs(8 * hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if runs(8 * mid) else (lo, mid)
+    return 8 * lo
+
+
 def largest_tn_stride(L, biased, cid, m, n, k, side):
     """The largest stride (a multiple of 8) of operand `side` at which the member's kernel still runs, the other two contiguous -- by
     bisection over bgemm_mi355x_tn_runs (_tn_bias_runs), which is monotone in the stride."""
@@ -411,12 +422,7 @@ def largest_tn_stride(L, biased, cid, m, n, k, side):
         lds[side] = s
         return kernel_runs(L, biased, cid, m, n, k, lds) == 1
 
-    lo, hi = (k, k, n)[side] // 8, 1 << 27             # 8 x 2^27 = 2^30 elements: beyond the reach of every member and K >= 64
-    assert runs(8 * lo) and not runs(8 * hi)
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if runs(8 * mid) else (lo, mid)
-    return 8 * lo
+    return largest_stride(runs, (k, k, n)[side])
 
 
 def reach_rule(bm, bn, n, k, side):
