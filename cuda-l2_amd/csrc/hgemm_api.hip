@@ -4,6 +4,7 @@
 // (benchmarking_utils.py:23-31), so a lean host path is part of the hot path.
 #include "hgemm_plan.hpp"
 #include "hgemm_kernel_nn.hpp"
+#include "hgemm_kernel_tn_grouped.hpp"
 #include "hgemm_act.hpp"
 #include "../../include/hgemm_mi355x.h"
 
@@ -1310,6 +1311,84 @@ int bgemm_mi355x_selfcheck_launch_tn_bias_add(int tn_config, int splits, int ope
 int bgemm_mi355x_selfcheck_launch_nn_bias_add(int nn_config, int splits, int operands, int M, int N, int K, int lda, int ldb, int ldc, int ldr,
                                               int ruled_out, long long out[20]) {
   return tr_selfcheck_launch(kLayoutNN, TR_BF16, out_bias_add(ldr), nn_config, splits, operands, M, N, K, lda, ldb, ldc, ruled_out, out);
+}
+
+// ---- the grouped forward product (bgemm_mi355x_tn_grouped, hgemm_kernel_tn_grouped.hpp): group g owns rows [offsets[g], offsets[g + 1]) and
+// weight g.  `offsets` is a device pointer the host never reads: no plan over its contents, no workspace, no copy, no synchronisation --
+// one dispatch whose grid is the bound grouped_tiles_m_max x tiles_n, or the grouped reference kernel for what is outside the kernels' scope.
+static_assert(HGEMM_GROUPED_MAX_GROUPS == GROUPED_MAX_GROUPS, "the public cap is the map's one wave pass");
+namespace {
+struct GroupedPlan { int status, form; long long grid; };
+// host logic only (bgemm_mi355x_selfcheck_launch_tn_grouped shows it to the tests); `aligned`: a, b_col_major, c and a non-NULL bias are
+// 16-byte aligned
+GroupedPlan grouped_resolve(int config, int word, bool aligned, bool has_bias, int G, int M, int N, int K, int lda, int ldb, long long gsb, int ldbias,
+                            int ldc) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || config < 0 || config >= kLayoutTN.t.count || lda < K || ldb < K || ldc < N || (has_bias && ldbias < N) ||
+      gsb < (long long)(N - 1) * ldb + K || (word & HGEMM_SPLITK_MASK) > 1)
+    return {HGEMM_ERR_BAD_ARG, FORM_REFERENCE, 0};
+  const TrEntry& e = kLayoutTN.t.rows[config].e;
+  const long long grid = grouped_tiles_m_max(M, G, e.bm) * ((N + e.bn - 1) / e.bn);
+  const bool kernel = aligned && G <= GROUPED_MAX_GROUPS && K % BK == 0 && (N & 7) == 0 && !((lda | ldb | ldc) & 7) && !(has_bias && (ldbias & 7)) &&
+                      (gsb & 7) == 0 && kLayoutTN.reach_ok(kOutC16Bias, e, M, N, K, lda, ldb, ldc) && grid <= 0x7fffffffLL;
+  return {HGEMM_OK, kernel ? FORM_PLAIN : FORM_REFERENCE, kernel ? grid : 0};
+}
+// The planned call's member, from (rows per group r = ceil(M / G), N, K); a stated rule, UNTUNED: BM = 128 when r > 64 (a 64-row group in a
+// 128-row tile computes as many clamped rows as real ones), BN = 128 when the estimate G ceil(r / BM) ceil(N / 128) still fills the CUs;
+// a 128 x 64 choice that does not fill them falls to 64 x 64.  K does not enter.
+int grouped_model_plan(int G, int M, int N) {
+  const long r = ((long)M + G - 1) / G;
+  int bm = r > 64 ? 128 : 64;
+  const auto tiles = [&](int m, int n) { return (long)G * ((r + m - 1) / m) * ((N + n - 1) / n); };
+  const int bn = tiles(bm, 128) >= kCUs ? 128 : 64;
+  if (bm == 128 && bn == 64 && tiles(128, 64) < kCUs) bm = 64;
+  for (int i = 0; i < kLayoutTN.t.count; ++i)
+    if (kLayoutTN.t.rows[i].e.bm == bm && kLayoutTN.t.rows[i].e.bn == bn) return i;
+  return 0;
+}
+}  // namespace
+int bgemm_mi355x_tn_grouped_runs(int tn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldbias, int ldc) {
+  const GroupedPlan p = grouped_resolve(tn_config, 1, true, true, G, M, N, K, lda, ldb, group_stride_b, ldbias, ldc);
+  return p.status == HGEMM_OK && p.form == FORM_PLAIN ? 1 : 0;
+}
+int bgemm_mi355x_launch_tn_grouped(int tn_config, int word, const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets,
+                                   int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldbias, int ldc, void* stream) {
+  DisarmTiming disarm_timing;
+  if (!a || !b_col_major || !c || !offsets) return HGEMM_ERR_BAD_ARG;
+  const bool aligned = !(((uintptr_t)a | (uintptr_t)b_col_major | (uintptr_t)c | (uintptr_t)bias) & 15);
+  const GroupedPlan p = grouped_resolve(tn_config, word, aligned, bias != nullptr, G, M, N, K, lda, ldb, group_stride_b, ldbias, ldc);
+  if (p.status != HGEMM_OK) return p.status;
+  GroupedArgs g{};
+  g.A = (const __bf16*)a; g.B = (const __bf16*)b_col_major; g.bias = (const __bf16*)bias; g.C = (__bf16*)c; g.offsets = offsets;
+  g.group_stride_b = group_stride_b;
+  g.G = G; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldbias = ldbias; g.ldc = ldc;
+  g.tiles_n = (N + kLayoutTN.t.rows[tn_config].e.bn - 1) / kLayoutTN.t.rows[tn_config].e.bn;
+  g.flags = (word & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
+  const TimingSlot ts = timing_slot(true, true);
+  if (p.form == FORM_PLAIN) tn_grouped_launcher(tn_config)(g, (int)p.grid, (hipStream_t)stream, ts);
+  else launch_tn_grouped_reference(g, (hipStream_t)stream, ts);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
+}
+int bgemm_mi355x_tn_grouped_plan(int G, int M, int N, int K, int* tn_config) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || !tn_config) return HGEMM_ERR_BAD_ARG;
+  *tn_config = grouped_model_plan(G, M, N);
+  return HGEMM_OK;
+}
+int bgemm_mi355x_tn_grouped(const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets, int G, int M, int N, int K,
+                            void* stream) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  return bgemm_mi355x_launch_tn_grouped(grouped_model_plan(G, M, N), 1, a, b_col_major, bias, c, offsets, G, M, N, K, K, K, (long long)N * K, N, N, stream);
+}
+// what bgemm_mi355x_launch_tn_grouped decides, nothing launched (not part of the public header): operands & 4: the pointers are 16-byte aligned,
+// operands & 8: a bias is given.  Returns the call's status; out = {form, dispatches (1), 0, 0, thunk, grid (0: the reference kernel's own)}.
+int bgemm_mi355x_selfcheck_launch_tn_grouped(int tn_config, int word, int operands, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b,
+                                             int ldbias, int ldc, long long out[20]) {
+  if (!out) return HGEMM_ERR_BAD_ARG;
+  const GroupedPlan p = grouped_resolve(tn_config, word, (operands & 4) != 0, (operands & 8) != 0, G, M, N, K, lda, ldb, group_stride_b, ldbias, ldc);
+  out[0] = p.form; out[1] = p.status == HGEMM_OK ? 1 : 0; out[2] = out[3] = 0;
+  out[4] = p.form == FORM_PLAIN ? THUNK_ENTRY : THUNK_GENERIC; out[5] = p.grid;
+  return p.status;
 }
 
 // ---- the gated forward product, H = act(X Wg^T + bg) (.) (X Wu^T + bu) (the kinds TR_C16_GATED + act): the work of the TN product of width

@@ -4,6 +4,7 @@
 #include "hgemm_kernel_ta.hpp"
 #include "hgemm_kernel_tn.hpp"
 #include "hgemm_kernel_tn_gated.hpp"
+#include "hgemm_kernel_tn_grouped.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -707,6 +708,35 @@ const TrTable& tr_table_tn() {
     return t;
   }();
   return table;
+}
+
+// ---- the grouped forward product (bgemm_mi355x_tn_grouped, hgemm_kernel_tn_grouped.hpp): the members' launchers by config id -- the order
+// of tr_table_tn()'s rows, one expansion of the same member list -- and the reference kernel of everything outside the kernels' scope.
+#define HGEMM_TN_GROUPED_CELL(...) HGEMM_TN_GROUPED_LAUNCHER(__VA_ARGS__),
+GroupedLaunch tn_grouped_launcher(int config) {
+  static const GroupedLaunch launchers[] = {HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_CELL, CfgTNB)};
+  return config >= 0 && config < (int)(sizeof(launchers) / sizeof(launchers[0])) ? launchers[config] : nullptr;
+}
+// A thread per element, hgemm_generic_kernel's grid: the row's group by binary search over the clamped offsets (a row no group owns is not
+// written), the sum by fmaf in k order, the group's bias (NULL: +0.0) added last, one rounding -- the member kernels' bits wherever the
+// sum is exact in any order.
+__global__ void __launch_bounds__(256) hgemm_tn_grouped_reference_kernel(const GroupedArgs a) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= a.N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < a.M; m += gridDim.y * 4) {
+    const int grp = grouped_find_row(a.offsets, a.G, a.M, m);
+    if (grp < 0) continue;
+    const __bf16* x = a.A + (size_t)m * a.lda;
+    const __bf16* w = a.B + (long long)grp * a.group_stride_b + (long long)n * a.ldb;
+    float s = 0.f;
+    for (int k = 0; k < a.K; ++k) s = fmaf((float)x[k], (float)w[k], s);
+    const float b = a.bias ? (float)a.bias[(size_t)grp * a.ldbias + n] : 0.0f;
+    a.C[(size_t)m * a.ldc + n] = (__bf16)(s + b);
+  }
+}
+void launch_tn_grouped_reference(const GroupedArgs& g, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((g.N + 63) / 64, (unsigned)std::min<long>(((long)g.M + 3) / 4, 65535));
+  HGEMM_LAUNCH(hgemm_tn_grouped_reference_kernel, grid, 256, stream, ts, g);
 }
 
 void launch_tail_reduce(const GemmArgs& g, int BM, int BN, hipStream_t stream, TimingSlot ts) {

@@ -53,6 +53,10 @@
 //                                                     an element-wise add at the same member and splits
 //   hgemm_tune check|bench --layout nn --bf16 --nn-add [...]     bgemm_mi355x_launch_nn_add: C = bf16(S + r), the same check; bench against
 //                                                     bgemm_mi355x_launch_nn + an element-wise add
+//   hgemm_tune check --grouped                        bgemm_mi355x_launch_tn_grouped: every member against the grouped reference kernel over
+//                                                     offset patterns, byte for byte
+//   hgemm_tune bench --grouped --groups G --rows R --n N --k K [--config name]   the grouped call against the loop of G
+//                                                     bgemm_mi355x_launch_tn_bias calls on the same member, and the price of its empty workgroups
 //   hgemm_tune check|bench --layout nn --bf16 --dgated relu|gelu|gelu_tanh|silu [...]   bgemm_mi355x_launch_nn_dgated: ReLU bit for bit, the
 //                                                     others inside the two bars of hgemm_dgated.hpp, sentinel bytes behind both outputs; bench
 //                                                     against bgemm_mi355x_launch_nn + an element-wise kernel at the same member and splits
@@ -2407,12 +2411,150 @@ static void bench_nn_dact_dbias(TrBench& B) {
   B.verdict("dbias_le_unfused", 0, 1, true);
 }
 
+// ---- check|bench --grouped: bgemm_mi355x_launch_tn_grouped (the tile map read from device offsets) -------------------------------------------
+// A row of its own, not one of kVariants: the call has a group count, an offsets vector and G weights where those have one shape.
+//   check: four members x {plain, NT store} x offset patterns at two small shapes, the member's kernel against the grouped REFERENCE kernel
+//          (the same call with C moved 8 bytes: misaligned, so the reference kernel answers) on integer operands whose sums are exact in any
+//          order: the whole C buffers, sentinel rows included, byte for byte.
+//   bench: --groups G --rows R (mean rows per group) --n N --k K [--config name] [--rounds n]: per routing (uniform; skewed: half the rows on
+//          two groups) the tuner's interleaved rounds of (1) the grouped call, (2) the loop it replaces -- one bgemm_mi355x_launch_tn_bias per
+//          non-empty group on the SAME member, the offsets known to the host: the loop's sync-free best case --, (3) the grouped call with all
+//          rows on group 0 and (4) the grouped call at G = 1 on the same rows: (3) against (4) is the price of the bound's empty workgroups.
+struct GroupedBufs { uint16_t *a, *w, *bias, *c; int* off; };
+static std::vector<int> grouped_routing(int G, int M, const char* kind) {
+  std::vector<int> rows(G, 0), off(G + 1, 0);
+  if (!strcmp(kind, "one_hot")) rows[0] = M;
+  else if (!strcmp(kind, "skewed") && G > 2) {
+    rows[0] = rows[1] = M / 4;
+    for (int g = 2; g < G; ++g) rows[g] = (M - 2 * (M / 4)) / (G - 2);
+    rows[G - 1] += M - 2 * (M / 4) - (G - 2) * ((M - 2 * (M / 4)) / (G - 2));
+  } else {
+    for (int g = 0; g < G; ++g) rows[g] = M / G + (g < M % G ? 1 : 0);
+  }
+  for (int g = 0; g < G; ++g) off[g + 1] = off[g] + rows[g];
+  return off;
+}
+static void grouped_fill_small_int(uint16_t* dev, size_t n, uint64_t seed, float scale) {
+  std::vector<uint16_t> h(n);
+  for (size_t i = 0; i < n; ++i) { seed = seed * 6364136223846793005ull + 1442695040888963407ull; h[i] = bf16_rne((float)((int)((seed >> 33) % 5) - 2) * scale); }
+  HIP_OK(hipMemcpy(dev, h.data(), n * 2, hipMemcpyHostToDevice));
+}
+static int grouped_check() {
+  struct Case { int M, N, K; std::vector<int> off; const char* what; };
+  std::vector<Case> cases = {{300, 72, 320, {3, 3, 4, 68, 68, 197, 290, 290}, "boundaries"}};
+  for (const char* kind : {"uniform", "skewed", "one_hot"}) cases.push_back({777, 136, 192, grouped_routing(6, 777, kind), kind});
+  cases.push_back({777, 136, 192, {5, 5, 5, 5, 5, 5, 5}, "all empty"});
+  cases.push_back({777, 136, 192, {9, 140, 141, 141, 500, 700, 770}, "dropped ends"});
+  int runs = 0, failures = 0;
+  for (const Case& cs : cases) {
+    const int G = (int)cs.off.size() - 1;
+    const size_t cn = (size_t)cs.M * cs.N;
+    GroupedBufs b;
+    HIP_OK(hipMalloc(&b.a, (size_t)cs.M * cs.K * 2)); HIP_OK(hipMalloc(&b.w, (size_t)G * cs.N * cs.K * 2)); HIP_OK(hipMalloc(&b.bias, (size_t)G * cs.N * 2));
+    HIP_OK(hipMalloc(&b.c, cn * 2 + 16)); HIP_OK(hipMalloc(&b.off, (G + 1) * 4));
+    grouped_fill_small_int(b.a, (size_t)cs.M * cs.K, 11, 1.0f / 64); grouped_fill_small_int(b.w, (size_t)G * cs.N * cs.K, 12, 1.0f);
+    grouped_fill_small_int(b.bias, (size_t)G * cs.N, 13, 1.0f / 256);
+    HIP_OK(hipMemcpy(b.off, cs.off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+    std::vector<uint16_t> want(cn), got(cn);
+    auto call = [&](int cfg, int word, uint16_t* c, std::vector<uint16_t>& out) {
+      HIP_OK(hipMemset(b.c, 0x7f, cn * 2 + 16));   // bf16 0x7f7f: a finite sentinel
+      const int st = bgemm_mi355x_launch_tn_grouped(cfg, word, b.a, b.w, b.bias, c, b.off, G, cs.M, cs.N, cs.K, cs.K, cs.K, (long long)cs.N * cs.K, cs.N, cs.N, nullptr);
+      const hipError_t e = hipDeviceSynchronize();
+      if (e != hipSuccess) { printf("FAIL grouped %s: hip error %d\n", cs.what, (int)e); exit(3); }
+      HIP_OK(hipMemcpy(out.data(), c, cn * 2, hipMemcpyDeviceToHost));
+      return st;
+    };
+    if (call(0, 1, b.c + 4, want) != HGEMM_OK) { printf("FAIL grouped %s: the reference form's status\n", cs.what); ++failures; }
+    for (int cfg = 0; cfg < bgemm_mi355x_tn_num_configs(); ++cfg)
+      for (int word : {1, 1 | HGEMM_PLAN_NT_STORE}) {
+        ++runs;
+        const bool runs_kernel = bgemm_mi355x_tn_grouped_runs(cfg, G, cs.M, cs.N, cs.K, cs.K, cs.K, (long long)cs.N * cs.K, cs.N, cs.N) == 1;
+        if (call(cfg, word, b.c, got) != HGEMM_OK || !runs_kernel || memcmp(got.data(), want.data(), cn * 2) != 0) {
+          size_t bad = 0;
+          for (size_t i = 0; i < cn; ++i) bad += got[i] != want[i];
+          printf("FAIL grouped %s %d_%d_%d %s word %#x: %zu elements differ from the reference kernel%s\n", cs.what, cs.M, cs.N, cs.K,
+                 bgemm_mi355x_tn_config_name(cfg), word, bad, runs_kernel ? "" : " (not run by the member's kernel)");
+          ++failures;
+        }
+      }
+    HIP_OK(hipFree(b.a)); HIP_OK(hipFree(b.w)); HIP_OK(hipFree(b.bias)); HIP_OK(hipFree(b.c)); HIP_OK(hipFree(b.off));
+  }
+  printf("check tn grouped: %d runs, %d failures (the whole C buffer byte for byte against the grouped reference kernel, exact sums)\n", runs, failures);
+  return failures ? 1 : 0;
+}
+static int grouped_bench(int G, int rows, int N, int K, const char* cfg_name, int rounds) {
+  const long long M64 = (long long)G * rows;
+  if (G < 1 || rows < 1 || N < 1 || K < 1 || M64 > 0x7fffffffLL) { fprintf(stderr, "bench --grouped: --groups G --rows R --n N --k K\n"); return 2; }
+  const int M = (int)M64;
+  int cfg = 0;
+  if (cfg_name) cfg = bgemm_mi355x_tn_config_by_name(cfg_name); else bgemm_mi355x_tn_grouped_plan(G, M, N, K, &cfg);
+  if (cfg < 0 || bgemm_mi355x_tn_grouped_runs(cfg, G, M, N, K, K, K, (long long)N * K, N, N) != 1) { fprintf(stderr, "bench --grouped: no member kernel runs this call\n"); return 2; }
+  GroupedBufs b;
+  int* off_alt[2];
+  HIP_OK(hipMalloc(&b.a, (size_t)M * K * 2)); HIP_OK(hipMalloc(&b.w, (size_t)G * N * K * 2)); HIP_OK(hipMalloc(&b.bias, (size_t)G * N * 2));
+  HIP_OK(hipMalloc(&b.c, (size_t)M * N * 2)); HIP_OK(hipMalloc(&b.off, (G + 1) * 4)); HIP_OK(hipMalloc(&off_alt[0], (G + 1) * 4)); HIP_OK(hipMalloc(&off_alt[1], 8));
+  // (fp16 normal bit patterns read as bf16: finite values of mixed magnitude; the timed work does not depend on them)
+  hgemm_fill_normal_f16(b.a, (size_t)M * K, 1, nullptr); hgemm_fill_normal_f16(b.w, (size_t)G * N * K, 2, nullptr); hgemm_fill_normal_f16(b.bias, (size_t)G * N, 3, nullptr);
+  const std::vector<int> one_hot = grouped_routing(G, M, "one_hot"), single = {0, M};
+  HIP_OK(hipMemcpy(off_alt[0], one_hot.data(), (G + 1) * 4, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(off_alt[1], single.data(), 8, hipMemcpyHostToDevice));
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+  std::vector<Buffers> sets(1);   // one operand set: the weights alone (G N K 2 bytes) are what the caches see
+  for (const char* kind : {"uniform", "skewed"}) {
+    const std::vector<int> off = grouped_routing(G, M, kind);
+    HIP_OK(hipMemcpy(b.off, off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+    auto grouped = [=](const int* o, int groups) {
+      return bgemm_mi355x_launch_tn_grouped(cfg, 1, b.a, b.w, b.bias, b.c, o, groups, M, N, K, K, K, (long long)N * K, N, N, nullptr);
+    };
+    std::vector<Contender> cs;
+    cs.push_back({"grouped", [=](Buffers&) { return grouped(b.off, G); }});
+    cs.push_back({"loop", [=](Buffers&) {
+      for (int g = 0; g < G; ++g) {
+        if (off[g + 1] == off[g]) continue;
+        const int st = bgemm_mi355x_launch_tn_bias(cfg, 1, b.a + (size_t)off[g] * K, b.w + (size_t)g * N * K, b.bias + (size_t)g * N, b.c + (size_t)off[g] * N,
+                                                   off[g + 1] - off[g], N, K, K, K, N, nullptr);
+        if (st != HGEMM_OK) return st;
+      }
+      return (int)HGEMM_OK;
+    }});
+    cs.push_back({"grouped_one_hot", [=](Buffers&) { return grouped(off_alt[0], G); }});
+    cs.push_back({"grouped_g1", [=](Buffers&) { return grouped(off_alt[1], 1); }});
+    const double est_us = std::max(20.0, 2.0 * M * (double)N * K / 1.0e9);   // (at 1 PFLOP/s; sizes the back-to-back boxes)
+    time_interleaved(cs, sets, rounds, 3, 0.05, est_us, e0, e1);
+    int max_rows = 0;
+    for (int g = 0; g < G; ++g) max_rows = std::max(max_rows, off[g + 1] - off[g]);
+    printf("{\"bench\": \"tn_grouped\", \"G\": %d, \"rows_per_group\": %d, \"M\": %d, \"N\": %d, \"K\": %d, \"routing\": \"%s\", \"max_rows\": %d, \"config\": \"%s\", "
+           "\"rounds\": %d, \"protocol\": \"interleaved\"", G, rows, M, N, K, kind, max_rows, bgemm_mi355x_tn_config_name(cfg), rounds);
+    for (const Contender& c : cs) printf(", \"%s_us\": %.2f, \"%s_stream_us\": %.2f", c.key, c.iso_us(), c.key, c.box_us());
+    printf(", \"loop_over_grouped\": %.3f, \"loop_over_grouped_stream\": %.3f, \"one_hot_over_g1\": %.3f}\n", cs[1].iso_us() / cs[0].iso_us(),
+           cs[1].box_us() / cs[0].box_us(), cs[2].iso_us() / cs[3].iso_us());
+    fflush(stdout);
+  }
+  HIP_OK(hipFree(b.a)); HIP_OK(hipFree(b.w)); HIP_OK(hipFree(b.bias)); HIP_OK(hipFree(b.c)); HIP_OK(hipFree(b.off)); HIP_OK(hipFree(off_alt[0])); HIP_OK(hipFree(off_alt[1]));
+  return 0;
+}
+static int cmd_grouped(const std::string& mode, int argc, char** argv) {
+  int G = 8, rows = 64, N = 4096, K = 4096, rounds = 30;
+  const char* cfg_name = nullptr;
+  for (int i = 2; i + 1 < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--groups") G = atoi(argv[++i]); else if (a == "--rows") rows = atoi(argv[++i]); else if (a == "--n") N = atoi(argv[++i]);
+    else if (a == "--k") K = atoi(argv[++i]); else if (a == "--rounds") rounds = atoi(argv[++i]); else if (a == "--config") cfg_name = argv[++i];
+  }
+  if (mode == "check") return grouped_check();
+  if (mode == "bench") return grouped_bench(G, rows, N, K, cfg_name, rounds);
+  fprintf(stderr, "--grouped goes with check or bench\n");
+  return 2;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
     return 2;
   }
   std::string mode = argv[1];
+  for (int i = 2; i < argc; ++i)
+    if (!strcmp(argv[i], "--grouped")) return cmd_grouped(mode, argc, argv);
   TrFlags tr;   // --layout, --bf16, --c32, --bias, --act, --aux, --dact, --dbias
   std::vector<Shape> shapes;
   const char* out_path = nullptr;

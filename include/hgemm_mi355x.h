@@ -765,6 +765,39 @@ int bgemm_mi355x_launch_nn_add(int nn_config, int splits, const void* a, const v
 /* bgemm_mi355x_nn_dact_runs(nn_config, M, N, K, lda, ldb, ldc, ldr): r has z's conditions; 0 for ldr < N */
 int bgemm_mi355x_nn_add_runs(int nn_config, int M, int N, int K, int lda, int ldb, int ldc, int ldr);
 
+/* ------------------------------------------------------------------------------------------
+ * Grouped forward product, the expert layer of a mixture-of-experts model in ONE launch: the rows of a and c are sorted by group (expert),
+ * group g of G owns rows [offsets[g], offsets[g + 1]) and has its own weight W_g and bias row.
+ * Semantics, exactly, for every g and every row m of it:
+ *     C[m][n] = bf16_rne( fl32( S + float(bias[g][n]) ) ),   S = sum_k a[m][k] W_g[n][k]   (fp32 accumulation)
+ *   - a is [M][lda] bf16; b_col_major holds the G weights [N][ldb], group_stride_b elements apart (the planned call: ldb = K,
+ *     group_stride_b = N K); bias is [G][ldbias] bf16 or NULL (+0.0, bit for bit); c is [M][ldc] bf16.
+ *   - offsets is a DEVICE pointer to G + 1 int32, non-decreasing, within [0, M].  The host never reads it: no copy, no synchronisation, no
+ *     workspace.  The call can be captured in a graph on a fresh stream with nothing reserved, and a replay follows whatever the buffer
+ *     holds then.  M, the row count of the buffers, is the bound the grid is sized from.
+ *   - Rows of c outside [offsets[0], offsets[G]) (dropped tokens) and pad columns are not written.
+ *   - Malformed offsets are defined, not checked: each is clamped to [0, M] and a group whose clamped end lies below its start is empty, so
+ *     no row outside [0, M) is ever read or written; which tiles of overlapping groups are computed is unspecified.
+ *   - G = 1 with offsets {0, M} gives bgemm_mi355x_launch_tn_bias's C bit for bit (same tn_config).
+ * tn_config is one of bgemm_mi355x_tn_*'s four members.  word: HGEMM_PLAN_NT_STORE is honoured; its split count must be 1 (or 0) -- there
+ * is no split-K form, a larger count is refused.  The planned call picks the member by a stated rule from (ceil(M / G), N, K); untuned.
+ * The members' kernels serve K % 64 == 0, N % 8 == 0, lda / ldb / ldc / ldbias / group_stride_b multiples of 8, 16-byte aligned pointers,
+ * (BM lda + K) 2, (BN ldb + K) 2 and (BM ldc + N) 2 bytes below 2 GiB, G <= HGEMM_GROUPED_MAX_GROUPS and a grid bound that fits an int;
+ * anything else is answered by the grouped reference kernel (status 0, the same semantics, slow: bgemm_mi355x_tn_grouped_runs tells).
+ * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL a, b_col_major, c or offsets; G < 1; M, N or K < 1; lda < K, ldb < K, ldc < N,
+ * ldbias < N (with a bias); group_stride_b < (N - 1) ldb + K; an id outside the table; more than one split in the word.
+ * Out of scope: the grouped gated forward, the grouped input and weight gradients, fp16, int64 offsets. */
+#define HGEMM_GROUPED_MAX_GROUPS 256
+/* planned, contiguous (lda = ldb = K, group_stride_b = N K, ldbias = ldc = N) */
+int bgemm_mi355x_tn_grouped(const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets, int G, int M, int N, int K,
+                            void* stream);
+int bgemm_mi355x_launch_tn_grouped(int tn_config, int word, const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets,
+                                   int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldbias, int ldc, void* stream);
+/* 1 when the call (with aligned pointers) runs the member's kernel, 0 when the reference kernel answers or the call is refused */
+int bgemm_mi355x_tn_grouped_runs(int tn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldbias, int ldc);
+/* the member the planned call takes */
+int bgemm_mi355x_tn_grouped_plan(int G, int M, int N, int K, int* tn_config);
+
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
 const char* hgemm_mi355x_version(void);
