@@ -59,6 +59,7 @@ LIB_SOURCES = [
     "hgemm_inst_g21.hip",
     "hgemm_inst_g22.hip",
     "hgemm_inst_g23.hip",
+    "hgemm_inst_g24.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -4,6 +4,7 @@
 // (benchmarking_utils.py:23-31), so a lean host path is part of the hot path.
 #include "hgemm_plan.hpp"
 #include "hgemm_kernel_nn.hpp"
+#include "hgemm_kernel_ta_grouped.hpp"
 #include "hgemm_kernel_tn_grouped.hpp"
 #include "hgemm_act.hpp"
 #include "../../include/hgemm_mi355x.h"
@@ -1389,6 +1390,113 @@ int bgemm_mi355x_selfcheck_launch_tn_grouped(int tn_config, int word, int operan
   out[0] = p.form; out[1] = p.status == HGEMM_OK ? 1 : 0; out[2] = out[3] = 0;
   out[4] = p.form == FORM_PLAIN ? THUNK_ENTRY : THUNK_GENERIC; out[5] = p.grid;
   return p.status;
+}
+
+// ---- the grouped weight gradient (bgemm_mi355x_ta_grouped / _ta_grouped_c32, hgemm_kernel_ta_grouped.hpp): group g owns k-rows [offsets[g],
+// offsets[g + 1]) of both operands and the matrix c + g group_stride_c.  `offsets` is a device pointer the host never reads; the tile count
+// does not depend on it, so the grid G tiles_m tiles_n is exact: one dispatch, no workspace, no copy, no synchronisation -- or the grouped
+// TA reference kernel for what is outside the kernels' scope.
+namespace {
+// host logic only (bgemm_mi355x_selfcheck_launch_ta_grouped shows it to the tests); `aligned`: a_col_major, b and c are 16-byte aligned
+GroupedPlan ta_grouped_resolve(bool c32, int config, int word, bool aligned, int G, int M, int N, int K, int lda, int ldb, int ldc, long long gsc,
+                               int accumulate) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || config < 0 || config >= kLayoutTA.t.count || lda < M || ldb < N || ldc < N ||
+      gsc < (long long)(M - 1) * ldc + N || (accumulate != 0 && accumulate != 1) || (accumulate && !c32) || (word & HGEMM_SPLITK_MASK) > 1)
+    return {HGEMM_ERR_BAD_ARG, FORM_REFERENCE, 0};
+  const TrEntry& e = kLayoutTA.t.rows[config].e;
+  const long long grid = ta_grouped_grid(G, (M + e.bm - 1) / e.bm, (N + e.bn - 1) / e.bn);
+  const int cmask = c32 ? 3 : 7;
+  // family a's reach with K rounded up to a stage: a group may end at row K in a partial stage, whose lane offsets run up to that bound
+  const long long kr = ((long long)K + BK - 1) / BK * BK;
+  const bool kernel = aligned && !((M | N | lda | ldb) & 7) && !(ldc & cmask) && !(gsc & cmask) && kr <= 0x7fffffffLL &&
+                      kLayoutTA.reach_ok(TrOut{c32, false}, e, M, N, (int)kr, lda, ldb, ldc) && grid <= 0x7fffffffLL;
+  return {HGEMM_OK, kernel ? FORM_PLAIN : FORM_REFERENCE, kernel ? grid : 0};
+}
+// The planned call's member: tr_model_plan's fill rule (hgemm_mi355x_ta_plan) with G tiles in the place of tiles -- the largest member whose
+// G tiles_m tiles_n fills the CUs (ties: fewer padded elements, then the taller tile), otherwise 64 x 64; there are no splits.  UNTUNED.
+int ta_grouped_model_plan(int G, int M, int N) {
+  const TrRow* table = kLayoutTA.t.rows;
+  int best = -1, small = 0;
+  long best_area = 0, best_pad = 0;
+  for (int i = 0; i < kLayoutTA.t.count; ++i) {
+    const TrEntry& e = table[i].e;
+    const long tm = (M + e.bm - 1) / e.bm, tn = (N + e.bn - 1) / e.bn, area = (long)e.bm * e.bn, pad = tm * e.bm * tn * e.bn;
+    if (area < (long)table[small].e.bm * table[small].e.bn) small = i;
+    if ((long long)G * tm * tn < kCUs) continue;
+    if (best < 0 || area > best_area || (area == best_area && (pad < best_pad || (pad == best_pad && e.bm > table[best].e.bm)))) {
+      best = i; best_area = area; best_pad = pad;
+    }
+  }
+  return best >= 0 ? best : small;
+}
+int ta_grouped_launch(bool c32, int config, int word, const void* a, const void* b, void* c, const int* offsets, int G, int M, int N, int K, int lda,
+                      int ldb, int ldc, long long gsc, int accumulate, void* stream) {
+  DisarmTiming disarm_timing;
+  if (!a || !b || !c || !offsets) return HGEMM_ERR_BAD_ARG;
+  const bool aligned = !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15);
+  const GroupedPlan p = ta_grouped_resolve(c32, config, word, aligned, G, M, N, K, lda, ldb, ldc, gsc, accumulate);
+  if (p.status != HGEMM_OK) return p.status;
+  const TrEntry& e = kLayoutTA.t.rows[config].e;
+  TaGroupedArgs g{};
+  g.A = (const __bf16*)a; g.B = (const __bf16*)b; g.C = c; g.offsets = offsets; g.group_stride_c = gsc;
+  g.G = G; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.tiles_m = (M + e.bm - 1) / e.bm; g.tiles_n = (N + e.bn - 1) / e.bn;
+  g.flags = ((word & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0) | (accumulate ? ARG_ACCUMULATE : 0);
+  const TimingSlot ts = timing_slot(true, true);
+  if (p.form == FORM_PLAIN) ta_grouped_launcher(config)(g, (int)p.grid, (hipStream_t)stream, c32, ts);
+  else launch_ta_grouped_reference(g, c32, (hipStream_t)stream, ts);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
+}
+}  // namespace
+int bgemm_mi355x_ta_grouped_c32_runs(int ta_config, int G, int M, int N, int K, int lda, int ldb, int ldc, long long group_stride_c) {
+  const GroupedPlan p = ta_grouped_resolve(true, ta_config, 1, true, G, M, N, K, lda, ldb, ldc, group_stride_c, 0);
+  return p.status == HGEMM_OK && p.form == FORM_PLAIN ? 1 : 0;
+}
+int bgemm_mi355x_ta_grouped_runs(int ta_config, int G, int M, int N, int K, int lda, int ldb, int ldc, long long group_stride_c) {
+  const GroupedPlan p = ta_grouped_resolve(false, ta_config, 1, true, G, M, N, K, lda, ldb, ldc, group_stride_c, 0);
+  return p.status == HGEMM_OK && p.form == FORM_PLAIN ? 1 : 0;
+}
+int bgemm_mi355x_launch_ta_grouped_c32(int ta_config, int word, const void* a_col_major, const void* b, float* c32, const int* offsets, int G, int M,
+                                       int N, int K, int lda, int ldb, int ldc, long long group_stride_c, int accumulate, void* stream) {
+  return ta_grouped_launch(true, ta_config, word, a_col_major, b, c32, offsets, G, M, N, K, lda, ldb, ldc, group_stride_c, accumulate, stream);
+}
+int bgemm_mi355x_launch_ta_grouped(int ta_config, int word, const void* a_col_major, const void* b, void* c, const int* offsets, int G, int M, int N,
+                                   int K, int lda, int ldb, int ldc, long long group_stride_c, void* stream) {
+  return ta_grouped_launch(false, ta_config, word, a_col_major, b, c, offsets, G, M, N, K, lda, ldb, ldc, group_stride_c, 0, stream);
+}
+int bgemm_mi355x_ta_grouped_plan(int G, int M, int N, int K, int* ta_config) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || !ta_config) return HGEMM_ERR_BAD_ARG;
+  *ta_config = ta_grouped_model_plan(G, M, N);
+  return HGEMM_OK;
+}
+int bgemm_mi355x_ta_grouped_c32(const void* a_col_major, const void* b, float* c32, const int* offsets, int G, int M, int N, int K, int accumulate,
+                                void* stream) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  return ta_grouped_launch(true, ta_grouped_model_plan(G, M, N), 1, a_col_major, b, c32, offsets, G, M, N, K, M, N, N, (long long)M * N, accumulate, stream);
+}
+int bgemm_mi355x_ta_grouped(const void* a_col_major, const void* b, void* c, const int* offsets, int G, int M, int N, int K, void* stream) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  return ta_grouped_launch(false, ta_grouped_model_plan(G, M, N), 1, a_col_major, b, c, offsets, G, M, N, K, M, N, N, (long long)M * N, 0, stream);
+}
+// what the two launch calls decide, nothing launched (not part of the public header): c32: the fp32-C form; operands & 4: the pointers are
+// 16-byte aligned.  Returns the call's status; out = {form, dispatches (1), 0, 0, thunk, grid (0: the reference kernel's own)}.
+int bgemm_mi355x_selfcheck_launch_ta_grouped(int ta_config, int word, int operands, int c32, int G, int M, int N, int K, int lda, int ldb, int ldc,
+                                             long long group_stride_c, int accumulate, long long out[20]) {
+  if (!out) return HGEMM_ERR_BAD_ARG;
+  const GroupedPlan p = ta_grouped_resolve(c32 != 0, ta_config, word, (operands & 4) != 0, G, M, N, K, lda, ldb, ldc, group_stride_c, accumulate);
+  out[0] = p.form; out[1] = p.status == HGEMM_OK ? 1 : 0; out[2] = out[3] = 0;
+  out[4] = p.form == FORM_PLAIN ? THUNK_ENTRY : THUNK_GENERIC; out[5] = p.grid;
+  return p.status;
+}
+// the kernels' map as the host computes it (hgemm_grouped.hpp; not part of the public header): workgroup `bid` of `grid` -> out = {group, tile
+// row, tile column}, and the stages of a group with the offsets (off_g, off_g1) under the bound K in out[3]
+int bgemm_mi355x_selfcheck_ta_grouped_tile(int bid, int grid, int tiles_m, int tiles_n, int off_g, int off_g1, int K, int out[4]) {
+  if (!out || grid < 1 || bid < 0 || bid >= grid || tiles_m < 1 || tiles_n < 1) return HGEMM_ERR_BAD_ARG;
+  const TaGroupedTile t = ta_grouped_tile(grouped_remap(bid, grid), tiles_m, tiles_n);
+  out[0] = t.g; out[1] = t.tile_m; out[2] = t.tile_n; out[3] = ta_grouped_stages(grouped_rows(off_g, off_g1, K), BK);
+  return HGEMM_OK;
 }
 
 // ---- the gated forward product, H = act(X Wg^T + bg) (.) (X Wu^T + bu) (the kinds TR_C16_GATED + act): the work of the TN product of width

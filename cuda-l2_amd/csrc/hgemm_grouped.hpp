@@ -93,4 +93,22 @@ HGEMM_HD inline int grouped_find_row(const int* off, int G, int M, int m) {
   return (m >= r.start && m < r.end) ? lo : -1;
 }
 
+// ---- the grouped weight gradient (bgemm_mi355x_ta_grouped, hgemm_kernel_ta_grouped.hpp): group g owns k-rows [off[g], off[g + 1]) of BOTH
+// operands and a whole M x N matrix C_g.  The group boundary cuts the K walk, not the rows of C, so the tile count does not depend on the
+// offsets: the grid is EXACT and host-known, G tiles_m tiles_n, every id has a tile and nothing is searched.
+//   * Workgroup id -> logical id L: grouped_remap over the grid (the family's XCD remap).
+//   * Group g's tiles are one contiguous run of logical ids, g = L / (tiles_m tiles_n): the ids an XCD owns walk one expert's rows of dY and
+//     X at a time.  Inside the group: grouped_raster, which with GROUPED_BAND = 8 is the dense family's raster (group_m = min(tiles_m, 8)).
+//   * A group's k-rows are grouped_rows with K as the bound; its walk has ceil(rows / 64) stages, the last one partial.
+struct TaGroupedTile { int g, tile_m, tile_n; };
+HGEMM_HD inline long long ta_grouped_grid(int G, int tiles_m, int tiles_n) { return (long long)G * tiles_m * tiles_n; }
+HGEMM_HD inline TaGroupedTile ta_grouped_tile(int L, int tiles_m, int tiles_n) {
+  const int per = tiles_m * tiles_n;
+  TaGroupedTile t;
+  t.g = L / per;
+  grouped_raster(L - t.g * per, tiles_m, tiles_n, t.tile_m, t.tile_n);
+  return t;
+}
+HGEMM_HD inline int ta_grouped_stages(GroupRows r, int BK) { return (r.end - r.start + BK - 1) / BK; }
+
 }  // namespace hgemm_mi355x

@@ -4,6 +4,7 @@
 #include "hgemm_kernel_ta.hpp"
 #include "hgemm_kernel_tn.hpp"
 #include "hgemm_kernel_tn_gated.hpp"
+#include "hgemm_kernel_ta_grouped.hpp"
 #include "hgemm_kernel_tn_grouped.hpp"
 
 #include <algorithm>
@@ -737,6 +738,41 @@ __global__ void __launch_bounds__(256) hgemm_tn_grouped_reference_kernel(const G
 void launch_tn_grouped_reference(const GroupedArgs& g, hipStream_t stream, TimingSlot ts) {
   dim3 grid((g.N + 63) / 64, (unsigned)std::min<long>(((long)g.M + 3) / 4, 65535));
   HGEMM_LAUNCH(hgemm_tn_grouped_reference_kernel, grid, 256, stream, ts, g);
+}
+
+// ---- the grouped weight gradient (bgemm_mi355x_ta_grouped, hgemm_kernel_ta_grouped.hpp): the members' launchers by config id -- the order of
+// tr_table_ta()'s rows -- and the reference kernel of everything outside the kernels' scope.
+#define HGEMM_TA_GROUPED_CELL(...) HGEMM_TA_GROUPED_LAUNCHER(__VA_ARGS__),
+TaGroupedLaunch ta_grouped_launcher(int config) {
+  static const TaGroupedLaunch launchers[] = {HGEMM_TR_MEMBERS(HGEMM_TA_GROUPED_CELL, CfgTAB)};
+  return config >= 0 && config < (int)(sizeof(launchers) / sizeof(launchers[0])) ? launchers[config] : nullptr;
+}
+// hgemm_generic_kernel with a third grid dimension, the group, and the group's k-rows as the range of the sum: a thread per element of C_g,
+// fmaf over t ascending, then the kind's store (OutC32 / OutC16<__bf16>) on the group's matrix.  The same grouped_rows as the member
+// kernels; an empty group under `accumulate` is neither read nor written, otherwise its sum is +0.0.
+template <class Out>
+__global__ void __launch_bounds__(256) hgemm_ta_grouped_reference_kernel(const TaGroupedArgs a, const Out out0) {
+  using Ops = Operands<__bf16, true, false>;
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= a.N) return;
+  for (int grp = blockIdx.z; grp < a.G; grp += gridDim.z) {
+    const GroupRows r = grouped_rows(a.offsets[grp], a.offsets[grp + 1], a.K);
+    if (r.end == r.start && (a.flags & ARG_ACCUMULATE)) continue;
+    Out out = out0;
+    out.C += (long long)grp * a.group_stride_c;
+    for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < a.M; m += gridDim.y * 4) {
+      const auto early = out.template early<1>(ElemPos{m, n});
+      float s = 0.f;
+      for (int t = r.start; t < r.end; ++t) s = fmaf((float)a.A[Ops::a(m, t, a.lda)], (float)a.B[Ops::b(t, n, a.ldb)], s);
+      out.template store<1>(ElemPos{m, n}, vec_t<float, 1>(s), early);
+    }
+  }
+}
+void launch_ta_grouped_reference(const TaGroupedArgs& g, bool c32, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((g.N + 63) / 64, (unsigned)std::min<long>(((long)g.M + 3) / 4, 65535), (unsigned)std::min(g.G, 65535));
+  const OutArgs o{g.C, nullptr, nullptr, g.ldc, 0, (g.flags & ARG_ACCUMULATE) != 0, nullptr, nullptr, nullptr, 0};
+  if (c32) HGEMM_LAUNCH((hgemm_ta_grouped_reference_kernel<OutC32>), grid, 256, stream, ts, g, OutC32::make(o));
+  else     HGEMM_LAUNCH((hgemm_ta_grouped_reference_kernel<OutC16<__bf16>>), grid, 256, stream, ts, g, OutC16<__bf16>::make(o));
 }
 
 void launch_tail_reduce(const GemmArgs& g, int BM, int BN, hipStream_t stream, TimingSlot ts) {

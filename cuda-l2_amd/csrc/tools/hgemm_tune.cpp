@@ -57,6 +57,11 @@
 //                                                     offset patterns, byte for byte
 //   hgemm_tune bench --grouped --groups G --rows R --n N --k K [--config name]   the grouped call against the loop of G
 //                                                     bgemm_mi355x_launch_tn_bias calls on the same member, and the price of its empty workgroups
+//   hgemm_tune check --ta-grouped                     bgemm_mi355x_launch_ta_grouped / _c32: members x forms x routings against the grouped TA
+//                                                     reference kernel, byte for byte
+//   hgemm_tune bench --ta-grouped --groups G --rows R [--m M --n N --config name --rounds n]   the grouped c32 accumulate call against the loop
+//                                                     of G bgemm_mi355x_launch_ta_c32 calls on the same member, uniform and skewed routing, with
+//                                                     the HBM floor G M N 8 bytes over each measured time
 //   hgemm_tune check|bench --layout nn --bf16 --dgated relu|gelu|gelu_tanh|silu [...]   bgemm_mi355x_launch_nn_dgated: ReLU bit for bit, the
 //                                                     others inside the two bars of hgemm_dgated.hpp, sentinel bytes behind both outputs; bench
 //                                                     against bgemm_mi355x_launch_nn + an element-wise kernel at the same member and splits
@@ -2547,6 +2552,153 @@ static int cmd_grouped(const std::string& mode, int argc, char** argv) {
   return 2;
 }
 
+// ---- check|bench --ta-grouped: bgemm_mi355x_launch_ta_grouped / _ta_grouped_c32 (each group's K walk read from device offsets) --------------------
+//   check: four members x {c32 store, c32 accumulate, bf16} x {plain, NT store} x a handful of routings, the member's kernel against the grouped
+//          TA REFERENCE kernel (the same call with C moved 8 bytes: misaligned, so the reference kernel answers) on integer operands whose sums
+//          are exact in any order: the whole C buffers byte for byte.  C starts as small integers, so an accumulate that did not add shows.
+//   bench: per routing (uniform; skewed: half the rows on two groups, in units of 64 rows where --rows is a multiple of 64) the tuner's
+//          interleaved rounds of (1) the grouped c32 accumulate call and (2) the loop it replaces, one bgemm_mi355x_launch_ta_c32 (accumulate)
+//          per non-empty group on the SAME member, the offsets known to the host and no sync: the loop's best case.  Where a group's rows are
+//          no multiple of 64 the loop runs the dense family's reference kernel ("loop_runs_kernels": 0; fewer rounds, they take seconds).
+//          floor_bytes = G M N 4 (1 + accumulate): the call is store-bound at these walk lengths, 2 rows / 8 flop per byte.
+static std::vector<int> ta_grouped_skewed(int G, int K, int unit) {
+  const int U = K / unit;
+  std::vector<int> units(G, 0), off(G + 1, 0);
+  if (G > 2) {
+    units[0] = units[1] = U / 4;
+    const int rest = U - 2 * (U / 4);
+    for (int g = 2; g < G; ++g) units[g] = rest / (G - 2) + (g - 2 < rest % (G - 2) ? 1 : 0);
+  } else {
+    for (int g = 0; g < G; ++g) units[g] = U / G + (g < U % G ? 1 : 0);
+  }
+  for (int g = 0; g < G; ++g) off[g + 1] = off[g] + units[g] * unit;
+  off[G] = K;   // (K % unit rows, if any, to the last group)
+  return off;
+}
+static int ta_grouped_check() {
+  struct Case { int K, M, N; std::vector<int> off; const char* what; };
+  std::vector<Case> cases = {{700, 72, 136, {3, 3, 4, 68, 68, 197, 524, 690}, "boundaries"}};
+  for (const char* kind : {"uniform", "skewed", "one_hot"}) cases.push_back({777, 136, 72, grouped_routing(6, 777, kind), kind});
+  cases.push_back({777, 136, 72, {5, 5, 5, 5, 5, 5, 5}, "all empty"});
+  cases.push_back({777, 136, 72, {9, 140, 141, 141, 500, 700, 770}, "dropped ends"});
+  int runs = 0, failures = 0;
+  for (const Case& cs : cases) {
+    const int G = (int)cs.off.size() - 1;
+    const size_t cn = (size_t)G * cs.M * cs.N;
+    uint16_t *a, *b;
+    char* c;
+    int* off;
+    HIP_OK(hipMalloc(&a, (size_t)cs.K * cs.M * 2)); HIP_OK(hipMalloc(&b, (size_t)cs.K * cs.N * 2)); HIP_OK(hipMalloc(&c, cn * 4 + 16)); HIP_OK(hipMalloc(&off, (G + 1) * 4));
+    grouped_fill_small_int(a, (size_t)cs.K * cs.M, 21, 1.0f / 64); grouped_fill_small_int(b, (size_t)cs.K * cs.N, 22, 1.0f);
+    HIP_OK(hipMemcpy(off, cs.off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+    for (int form = 0; form < 3; ++form) {   // 0: c32 store, 1: c32 accumulate, 2: bf16
+      const size_t bytes = cn * (form == 2 ? 2 : 4);
+      std::vector<char> init(bytes + 16), want(bytes), got(bytes);
+      for (size_t i = 0; i < (bytes + 16) / 4; ++i) { const float v = (float)((int)(i % 17) - 8); memcpy(&init[4 * i], &v, 4); }
+      auto call = [&](int cfg, int word, char* cp, std::vector<char>& out) {
+        HIP_OK(hipMemcpy(c, init.data(), bytes + 16, hipMemcpyHostToDevice));
+        const int st = form == 2 ? bgemm_mi355x_launch_ta_grouped(cfg, word, a, b, cp, off, G, cs.M, cs.N, cs.K, cs.M, cs.N, cs.N, (long long)cs.M * cs.N, nullptr)
+                                 : bgemm_mi355x_launch_ta_grouped_c32(cfg, word, a, b, (float*)cp, off, G, cs.M, cs.N, cs.K, cs.M, cs.N, cs.N, (long long)cs.M * cs.N, form, nullptr);
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) { printf("FAIL ta grouped %s: hip error %d\n", cs.what, (int)e); exit(3); }
+        HIP_OK(hipMemcpy(out.data(), cp, bytes, hipMemcpyDeviceToHost));
+        return st;
+      };
+      if (call(0, 1, c + 8, want) != HGEMM_OK) { printf("FAIL ta grouped %s: the reference form's status\n", cs.what); ++failures; }
+      for (int cfg = 0; cfg < hgemm_mi355x_ta_num_configs(); ++cfg)
+        for (int word : {1, 1 | HGEMM_PLAN_NT_STORE}) {
+          ++runs;
+          const bool runs_kernel = (form == 2 ? bgemm_mi355x_ta_grouped_runs : bgemm_mi355x_ta_grouped_c32_runs)(cfg, G, cs.M, cs.N, cs.K, cs.M, cs.N, cs.N, (long long)cs.M * cs.N) == 1;
+          // (the reference run saw the initial pattern 8 bytes later: compare what each ADDED where the form reads C, the bytes otherwise)
+          bool same = call(cfg, word, c, got) == HGEMM_OK && runs_kernel;
+          if (same && form == 1) {
+            for (size_t i = 0; i < cn && same; ++i) {
+              float g32, w32, gi, wi;
+              memcpy(&g32, &got[4 * i], 4); memcpy(&w32, &want[4 * i], 4); memcpy(&gi, &init[4 * i], 4); memcpy(&wi, &init[4 * i + 8], 4);
+              same = g32 - gi == w32 - wi;   // small integers and exact sums: exact differences
+            }
+          } else if (same) {
+            same = memcmp(got.data(), want.data(), bytes) == 0;
+          }
+          if (!same) {
+            printf("FAIL ta grouped %s %d_%d_%d %s form %d word %#x differs from the reference kernel%s\n", cs.what, cs.M, cs.N, cs.K, hgemm_mi355x_ta_config_name(cfg),
+                   form, word, runs_kernel ? "" : " (not run by the member's kernel)");
+            ++failures;
+          }
+        }
+    }
+    HIP_OK(hipFree(a)); HIP_OK(hipFree(b)); HIP_OK(hipFree(c)); HIP_OK(hipFree(off));
+  }
+  printf("check ta grouped: %d runs, %d failures (every C_g against the grouped TA reference kernel, exact sums)\n", runs, failures);
+  return failures ? 1 : 0;
+}
+static int ta_grouped_bench(int G, int rows, int M, int N, const char* cfg_name, int rounds) {
+  const long long K64 = (long long)G * rows;
+  if (G < 1 || rows < 1 || M < 1 || N < 1 || K64 > 0x7fffffffLL) { fprintf(stderr, "bench --ta-grouped: --groups G --rows R --m M --n N\n"); return 2; }
+  const int K = (int)K64;
+  int cfg = 0;
+  if (cfg_name) cfg = hgemm_mi355x_ta_config_by_name(cfg_name); else bgemm_mi355x_ta_grouped_plan(G, M, N, K, &cfg);
+  if (cfg < 0 || bgemm_mi355x_ta_grouped_c32_runs(cfg, G, M, N, K, M, N, N, (long long)M * N) != 1) { fprintf(stderr, "bench --ta-grouped: no member kernel runs this call\n"); return 2; }
+  uint16_t *a, *b;
+  float* c;
+  int* off_d;
+  const size_t cn = (size_t)G * M * N;
+  HIP_OK(hipMalloc(&a, (size_t)K * M * 2)); HIP_OK(hipMalloc(&b, (size_t)K * N * 2)); HIP_OK(hipMalloc(&c, cn * 4)); HIP_OK(hipMalloc(&off_d, (G + 1) * 4));
+  // (fp16 normal bit patterns read as bf16: finite values of mixed magnitude; the timed work does not depend on them)
+  hgemm_fill_normal_f16(a, (size_t)K * M, 1, nullptr); hgemm_fill_normal_f16(b, (size_t)K * N, 2, nullptr);
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+  std::vector<Buffers> sets(1);
+  const double floor_bytes = (double)cn * 4.0 * 2.0;
+  for (const char* kind : {"uniform", "skewed"}) {
+    const std::vector<int> off = !strcmp(kind, "skewed") ? ta_grouped_skewed(G, K, rows % 64 == 0 ? 64 : 1) : grouped_routing(G, K, kind);
+    HIP_OK(hipMemcpy(off_d, off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(c, 0, cn * 4));
+    int max_rows = 0, loop_kernels = 1;
+    for (int g = 0; g < G; ++g) {
+      const int r = off[g + 1] - off[g];
+      max_rows = std::max(max_rows, r);
+      if (r > 0 && bgemm_mi355x_ta_c32_runs(cfg, M, N, r, M, N, N) != 1) loop_kernels = 0;
+    }
+    std::vector<Contender> cs;
+    cs.push_back({"grouped", [=](Buffers&) { return bgemm_mi355x_launch_ta_grouped_c32(cfg, 1, a, b, c, off_d, G, M, N, K, M, N, N, (long long)M * N, 1, nullptr); }});
+    cs.push_back({"loop", [=](Buffers&) {
+      for (int g = 0; g < G; ++g) {
+        if (off[g + 1] == off[g]) continue;
+        const int st = bgemm_mi355x_launch_ta_c32(cfg, 1, a + (size_t)off[g] * M, b + (size_t)off[g] * N, c + (size_t)g * M * N, M, N, off[g + 1] - off[g], M, N, N, 1, nullptr);
+        if (st != HGEMM_OK) return st;
+      }
+      return (int)HGEMM_OK;
+    }});
+    const int n_rounds = loop_kernels ? rounds : std::min(rounds, 6);
+    const double est_us = loop_kernels ? std::max(20.0, floor_bytes / 4.0e6) : 1.0e6;   // (at 4 TB/s; a reference-kernel loop: the least box)
+    time_interleaved(cs, sets, n_rounds, loop_kernels ? 3 : 1, 0.05, est_us, e0, e1);
+    printf("{\"bench\": \"ta_grouped_c32\", \"G\": %d, \"rows_per_group\": %d, \"M\": %d, \"N\": %d, \"K\": %d, \"accumulate\": 1, \"routing\": \"%s\", \"max_rows\": %d, "
+           "\"config\": \"%s\", \"rounds\": %d, \"protocol\": \"interleaved\", \"loop_runs_kernels\": %d, \"floor_bytes\": %.0f", G, rows, M, N, K, kind, max_rows,
+           hgemm_mi355x_ta_config_name(cfg), n_rounds, loop_kernels, floor_bytes);
+    for (const Contender& ct : cs)
+      printf(", \"%s_us\": %.2f, \"%s_stream_us\": %.2f, \"%s_floor_gbps\": %.1f, \"%s_stream_floor_gbps\": %.1f", ct.key, ct.iso_us(), ct.key, ct.box_us(), ct.key,
+             floor_bytes / ct.iso_us() / 1.0e3, ct.key, floor_bytes / ct.box_us() / 1.0e3);
+    printf(", \"loop_over_grouped\": %.3f, \"loop_over_grouped_stream\": %.3f}\n", cs[1].iso_us() / cs[0].iso_us(), cs[1].box_us() / cs[0].box_us());
+    fflush(stdout);
+  }
+  HIP_OK(hipFree(a)); HIP_OK(hipFree(b)); HIP_OK(hipFree(c)); HIP_OK(hipFree(off_d));
+  return 0;
+}
+static int cmd_ta_grouped(const std::string& mode, int argc, char** argv) {
+  int G = 8, rows = 64, M = 4096, N = 2048, rounds = 30;
+  const char* cfg_name = nullptr;
+  for (int i = 2; i + 1 < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--groups") G = atoi(argv[++i]); else if (a == "--rows") rows = atoi(argv[++i]); else if (a == "--m") M = atoi(argv[++i]);
+    else if (a == "--n") N = atoi(argv[++i]); else if (a == "--rounds") rounds = atoi(argv[++i]); else if (a == "--config") cfg_name = argv[++i];
+  }
+  if (mode == "check") return ta_grouped_check();
+  if (mode == "bench") return ta_grouped_bench(G, rows, M, N, cfg_name, rounds);
+  fprintf(stderr, "--ta-grouped goes with check or bench\n");
+  return 2;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: hgemm_tune check|tune|bench [options]\n");
@@ -2555,6 +2707,8 @@ int main(int argc, char** argv) {
   std::string mode = argv[1];
   for (int i = 2; i < argc; ++i)
     if (!strcmp(argv[i], "--grouped")) return cmd_grouped(mode, argc, argv);
+  for (int i = 2; i < argc; ++i)
+    if (!strcmp(argv[i], "--ta-grouped")) return cmd_ta_grouped(mode, argc, argv);
   TrFlags tr;   // --layout, --bf16, --c32, --bias, --act, --aux, --dact, --dbias
   std::vector<Shape> shapes;
   const char* out_path = nullptr;

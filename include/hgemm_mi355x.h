@@ -786,7 +786,7 @@ int bgemm_mi355x_nn_add_runs(int nn_config, int M, int N, int K, int lda, int ld
  * anything else is answered by the grouped reference kernel (status 0, the same semantics, slow: bgemm_mi355x_tn_grouped_runs tells).
  * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL a, b_col_major, c or offsets; G < 1; M, N or K < 1; lda < K, ldb < K, ldc < N,
  * ldbias < N (with a bias); group_stride_b < (N - 1) ldb + K; an id outside the table; more than one split in the word.
- * Out of scope: the grouped gated forward, the grouped input and weight gradients, fp16, int64 offsets. */
+ * Out of scope: the grouped gated forward, the grouped input gradient, fp16, int64 offsets (the weight gradient: bgemm_mi355x_ta_grouped). */
 #define HGEMM_GROUPED_MAX_GROUPS 256
 /* planned, contiguous (lda = ldb = K, group_stride_b = N K, ldbias = ldc = N) */
 int bgemm_mi355x_tn_grouped(const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets, int G, int M, int N, int K,
@@ -797,6 +797,53 @@ int bgemm_mi355x_launch_tn_grouped(int tn_config, int word, const void* a, const
 int bgemm_mi355x_tn_grouped_runs(int tn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldbias, int ldc);
 /* the member the planned call takes */
 int bgemm_mi355x_tn_grouped_plan(int G, int M, int N, int K, int* tn_config);
+
+/* ------------------------------------------------------------------------------------------
+ * Grouped weight gradient, dW_g = dY_g^T X_g for every expert of a mixture-of-experts layer in ONE launch, from the forward call's offsets.
+ * The k-rows (tokens) of both operands are sorted by group; group g of G owns rows [s_g, e_g) and a whole M x N matrix C_g.
+ * Semantics, exactly, for every g and every m < M, n < N:
+ *     S_g[m][n] = sum over t in [s_g, e_g) of a_col_major[t][m] b[t][n]     (fp32 accumulation, t ascending in the dense TA kernel's order)
+ *     (s_g, e_g) = offsets[g], offsets[g + 1], each clamped to [0, K]; an end below the start is an empty group
+ *     c32 form:  C_g[m][n] = S_g              (accumulate = 0; the old contents are never read and may be NaN)
+ *                C_g[m][n] = C_g[m][n] + S_g  (accumulate = 1; one fp32 add per element)
+ *     bf16 form: C_g[m][n] = bf16_rne(S_g)
+ *     C_g = c + g group_stride_c, [M][ldc]
+ *   - a_col_major is [K][lda] bf16 with M contiguous, b is [K][ldb] bf16 with N contiguous; K is the row count of both buffers and the bound
+ *     the offsets are clamped to.  For the forward Y = X W_g^T with W stacked [G][Nout][Kin]: a_col_major = dY, b = X, M = Nout, N = Kin,
+ *     K = tokens, c32 = the stacked fp32 gradient, group_stride_c = Nout Kin.
+ *   - offsets is a DEVICE pointer to G + 1 int32, the forward call's vector.  The host never reads it: no workspace, no copy, no
+ *     synchronisation.  The call can be captured in a graph on a fresh stream, and a replay follows whatever the buffer holds then.
+ *   - Rows of a_col_major and b outside [s_g, e_g) contribute NOTHING to C_g, whatever they hold, NaN and Inf included: rows no group owns
+ *     and the neighbouring groups' rows alike.
+ *   - An empty group: accumulate = 0 and the bf16 form store +0.0; accumulate = 1 leaves C_g untouched, neither read nor written.
+ *   - Deterministic: no atomics and no split-K (a word with more than one split is refused); one workgroup owns a C tile and walks the whole
+ *     group.  G = 1 with offsets {0, K} and K % 64 == 0 gives bgemm_mi355x_launch_ta_c32 / _launch_ta (unsplit, same ta_config) bit for bit.
+ *   - Malformed offsets are defined by the clamp, not checked: no row outside [0, K) is read; overlapping groups each get their own sum.
+ * ta_config is one of the four a... members (hgemm_mi355x_ta_config_*).  word: HGEMM_PLAN_NT_STORE is honoured; its split count must be 1 (or 0).
+ * The planned calls pick the member by hgemm_mi355x_ta_plan's fill rule with G tiles in the place of tiles: the largest member whose
+ * G tiles_m tiles_n fills the 256 CUs, otherwise 64 x 64; UNTUNED.
+ * The members' kernels serve M % 8 == 0, N % 8 == 0, lda / ldb multiples of 8, ldc and group_stride_c multiples of 4 (c32) / 8 (bf16),
+ * 16-byte aligned pointers, the TA family's reach rules with K (rounded up to a multiple of 64) as the bound on a group's rows --
+ * ((K' - 1) lda + M) 2 and ((K' - 1) ldb + N) 2 bytes and a C tile's (BM ldc + N) elements below 2 GiB -- and G tiles_m tiles_n that fits an
+ * int.  K and the offsets are unrestricted, and there is no cap on G.  Anything else is answered by the grouped TA reference kernel
+ * (status 0, the same semantics, slow: bgemm_mi355x_ta_grouped_runs / _c32_runs tell).
+ * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL pointer; G, M, N or K < 1; lda < M, ldb < N or ldc < N;
+ * group_stride_c < (M - 1) ldc + N; an id outside the table; accumulate outside {0, 1}; more than one split in the word.
+ * Out of scope: the grouped input gradient, the grouped gated forward, a grouped bias gradient, fp16, int64 offsets, splitting a heavy
+ * group's walk. */
+/* planned, contiguous (lda = M, ldb = ldc = N, group_stride_c = M N) */
+int bgemm_mi355x_ta_grouped_c32(const void* a_col_major, const void* b, float* c32, const int* offsets, int G, int M, int N, int K, int accumulate,
+                                void* stream);
+int bgemm_mi355x_ta_grouped(const void* a_col_major, const void* b, void* c, const int* offsets, int G, int M, int N, int K, void* stream);
+int bgemm_mi355x_launch_ta_grouped_c32(int ta_config, int word, const void* a_col_major, const void* b, float* c32, const int* offsets, int G, int M,
+                                       int N, int K, int lda, int ldb, int ldc, long long group_stride_c, int accumulate, void* stream);
+int bgemm_mi355x_launch_ta_grouped(int ta_config, int word, const void* a_col_major, const void* b, void* c, const int* offsets, int G, int M, int N,
+                                   int K, int lda, int ldb, int ldc, long long group_stride_c, void* stream);
+/* 1 when the call (with aligned pointers) runs the member's kernel, 0 when the reference kernel answers or the call is refused */
+int bgemm_mi355x_ta_grouped_runs(int ta_config, int G, int M, int N, int K, int lda, int ldb, int ldc, long long group_stride_c);
+int bgemm_mi355x_ta_grouped_c32_runs(int ta_config, int G, int M, int N, int K, int lda, int ldb, int ldc, long long group_stride_c);
+/* the member the planned calls take */
+int bgemm_mi355x_ta_grouped_plan(int G, int M, int N, int K, int* ta_config);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
