@@ -60,6 +60,7 @@ LIB_SOURCES = [
     "hgemm_inst_g22.hip",
     "hgemm_inst_g23.hip",
     "hgemm_inst_g24.hip",
+    "hgemm_inst_g25.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

@@ -4,6 +4,7 @@
 // (benchmarking_utils.py:23-31), so a lean host path is part of the hot path.
 #include "hgemm_plan.hpp"
 #include "hgemm_kernel_nn.hpp"
+#include "hgemm_kernel_nn_grouped.hpp"
 #include "hgemm_kernel_ta_grouped.hpp"
 #include "hgemm_kernel_tn_grouped.hpp"
 #include "hgemm_act.hpp"
@@ -1335,15 +1336,16 @@ GroupedPlan grouped_resolve(int config, int word, bool aligned, bool has_bias, i
 }
 // The planned call's member, from (rows per group r = ceil(M / G), N, K); a stated rule, UNTUNED: BM = 128 when r > 64 (a 64-row group in a
 // 128-row tile computes as many clamped rows as real ones), BN = 128 when the estimate G ceil(r / BM) ceil(N / 128) still fills the CUs;
-// a 128 x 64 choice that does not fill them falls to 64 x 64.  K does not enter.
-int grouped_model_plan(int G, int M, int N) {
+// a 128 x 64 choice that does not fill them falls to 64 x 64.  K does not enter.  L: the layout whose table the id indexes (TN: the forward
+// call, NN: bgemm_mi355x_nn_grouped); the four members have the same tiles in both.
+int grouped_model_plan(const TrLayout& L, int G, int M, int N) {
   const long r = ((long)M + G - 1) / G;
   int bm = r > 64 ? 128 : 64;
   const auto tiles = [&](int m, int n) { return (long)G * ((r + m - 1) / m) * ((N + n - 1) / n); };
   const int bn = tiles(bm, 128) >= kCUs ? 128 : 64;
   if (bm == 128 && bn == 64 && tiles(128, 64) < kCUs) bm = 64;
-  for (int i = 0; i < kLayoutTN.t.count; ++i)
-    if (kLayoutTN.t.rows[i].e.bm == bm && kLayoutTN.t.rows[i].e.bn == bn) return i;
+  for (int i = 0; i < L.t.count; ++i)
+    if (L.t.rows[i].e.bm == bm && L.t.rows[i].e.bn == bn) return i;
   return 0;
 }
 }  // namespace
@@ -1373,13 +1375,13 @@ int bgemm_mi355x_launch_tn_grouped(int tn_config, int word, const void* a, const
 }
 int bgemm_mi355x_tn_grouped_plan(int G, int M, int N, int K, int* tn_config) {
   if (G < 1 || M <= 0 || N <= 0 || K <= 0 || !tn_config) return HGEMM_ERR_BAD_ARG;
-  *tn_config = grouped_model_plan(G, M, N);
+  *tn_config = grouped_model_plan(kLayoutTN, G, M, N);
   return HGEMM_OK;
 }
 int bgemm_mi355x_tn_grouped(const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets, int G, int M, int N, int K,
                             void* stream) {
   if (G < 1 || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
-  return bgemm_mi355x_launch_tn_grouped(grouped_model_plan(G, M, N), 1, a, b_col_major, bias, c, offsets, G, M, N, K, K, K, (long long)N * K, N, N, stream);
+  return bgemm_mi355x_launch_tn_grouped(grouped_model_plan(kLayoutTN, G, M, N), 1, a, b_col_major, bias, c, offsets, G, M, N, K, K, K, (long long)N * K, N, N, stream);
 }
 // what bgemm_mi355x_launch_tn_grouped decides, nothing launched (not part of the public header): operands & 4: the pointers are 16-byte aligned,
 // operands & 8: a bias is given.  Returns the call's status; out = {form, dispatches (1), 0, 0, thunk, grid (0: the reference kernel's own)}.
@@ -1389,6 +1391,71 @@ int bgemm_mi355x_selfcheck_launch_tn_grouped(int tn_config, int word, int operan
   const GroupedPlan p = grouped_resolve(tn_config, word, (operands & 4) != 0, (operands & 8) != 0, G, M, N, K, lda, ldb, group_stride_b, ldbias, ldc);
   out[0] = p.form; out[1] = p.status == HGEMM_OK ? 1 : 0; out[2] = out[3] = 0;
   out[4] = p.form == FORM_PLAIN ? THUNK_ENTRY : THUNK_GENERIC; out[5] = p.grid;
+  return p.status;
+}
+
+// ---- the grouped input gradient (bgemm_mi355x_nn_grouped, hgemm_kernel_nn_grouped.hpp): group g owns rows [offsets[g], offsets[g + 1]) of a, r and
+// c and the row-major matrix b + g group_stride_b.  The forward call's host side once more: a device offsets pointer the host never reads, one
+// dispatch whose grid is the bound grouped_tiles_m_max x tiles_n, or the grouped NN reference kernel for what is outside the kernels' scope.
+namespace {
+// host logic only (bgemm_mi355x_selfcheck_launch_nn_grouped shows it to the tests); `aligned`: a, b, c and a non-NULL r are 16-byte aligned;
+// r_is_c: the in-place call, which needs ldr == ldc.  form: FORM_PLAIN (the member's kernel of either epilogue) or FORM_REFERENCE
+GroupedPlan nn_grouped_resolve(int config, int word, bool aligned, bool has_r, bool r_is_c, int G, int M, int N, int K, int lda, int ldb, long long gsb,
+                               int ldr, int ldc) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || config < 0 || config >= kLayoutNN.t.count || lda < K || ldb < N || ldc < N || (has_r && ldr < N) ||
+      (has_r && r_is_c && ldr != ldc) || gsb < (long long)(K - 1) * ldb + N || (word & HGEMM_SPLITK_MASK) > 1)
+    return {HGEMM_ERR_BAD_ARG, FORM_REFERENCE, 0};
+  const TrEntry& e = kLayoutNN.t.rows[config].e;
+  const long long grid = grouped_tiles_m_max(M, G, e.bm) * ((N + e.bn - 1) / e.bn);
+  const bool r_ok = !has_r || ((ldr & 7) == 0 && ((double)e.bm * ldr + N) * 2.0 < 2147483648.0);   // r: C's rules
+  const bool kernel = aligned && r_ok && G <= GROUPED_MAX_GROUPS && K % BK == 0 && (N & 7) == 0 && !((lda | ldb | ldc) & 7) && (gsb & 7) == 0 &&
+                      kLayoutNN.reach_ok(kOutC16, e, M, N, K, lda, ldb, ldc) && grid <= 0x7fffffffLL;
+  return {HGEMM_OK, kernel ? FORM_PLAIN : FORM_REFERENCE, kernel ? grid : 0};
+}
+}  // namespace
+int bgemm_mi355x_nn_grouped_runs(int nn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldr, int ldc) {
+  const GroupedPlan p = nn_grouped_resolve(nn_config, 1, true, ldr != 0, false, G, M, N, K, lda, ldb, group_stride_b, ldr, ldc);
+  return p.status == HGEMM_OK && p.form == FORM_PLAIN ? 1 : 0;
+}
+int bgemm_mi355x_launch_nn_grouped(int nn_config, int word, const void* a, const void* b, const void* r, void* c, const int* offsets, int G, int M, int N,
+                                   int K, int lda, int ldb, long long group_stride_b, int ldr, int ldc, void* stream) {
+  DisarmTiming disarm_timing;
+  if (!a || !b || !c || !offsets) return HGEMM_ERR_BAD_ARG;
+  const bool aligned = !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)r) & 15);
+  const GroupedPlan p = nn_grouped_resolve(nn_config, word, aligned, r != nullptr, r == c, G, M, N, K, lda, ldb, group_stride_b, ldr, ldc);
+  if (p.status != HGEMM_OK) return p.status;
+  NnGroupedArgs g{};
+  g.A = (const __bf16*)a; g.B = (const __bf16*)b; g.R = (const __bf16*)r; g.C = (__bf16*)c; g.offsets = offsets;
+  g.group_stride_b = group_stride_b;
+  g.G = G; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldr = r ? ldr : 0; g.ldc = ldc;
+  g.tiles_n = (N + kLayoutNN.t.rows[nn_config].e.bn - 1) / kLayoutNN.t.rows[nn_config].e.bn;
+  g.flags = (word & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
+  const TimingSlot ts = timing_slot(true, true);
+  if (p.form == FORM_PLAIN) nn_grouped_launcher(nn_config)(g, (int)p.grid, (hipStream_t)stream, ts);
+  else launch_nn_grouped_reference(g, (hipStream_t)stream, ts);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
+}
+int bgemm_mi355x_nn_grouped_plan(int G, int M, int N, int K, int* nn_config) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || !nn_config) return HGEMM_ERR_BAD_ARG;
+  *nn_config = grouped_model_plan(kLayoutNN, G, M, N);
+  return HGEMM_OK;
+}
+int bgemm_mi355x_nn_grouped(const void* a, const void* b, const void* r, void* c, const int* offsets, int G, int M, int N, int K, void* stream) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0) return HGEMM_ERR_BAD_ARG;
+  return bgemm_mi355x_launch_nn_grouped(grouped_model_plan(kLayoutNN, G, M, N), 1, a, b, r, c, offsets, G, M, N, K, K, N, (long long)K * N, N, N, stream);
+}
+// what bgemm_mi355x_launch_nn_grouped decides, nothing launched (not part of the public header): operands & 4: the pointers are 16-byte aligned,
+// operands & 8: an r is given, operands & 16: it is c itself.  Returns the call's status; out = {form, dispatches (1), 0, 0, thunk, grid (0: the
+// reference kernel's own), the epilogue (EPI_C16 / EPI_C16_ADD)}.
+int bgemm_mi355x_selfcheck_launch_nn_grouped(int nn_config, int word, int operands, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b,
+                                             int ldr, int ldc, long long out[20]) {
+  if (!out) return HGEMM_ERR_BAD_ARG;
+  const GroupedPlan p = nn_grouped_resolve(nn_config, word, (operands & 4) != 0, (operands & 8) != 0, (operands & 16) != 0, G, M, N, K, lda, ldb,
+                                           group_stride_b, ldr, ldc);
+  out[0] = p.form; out[1] = p.status == HGEMM_OK ? 1 : 0; out[2] = out[3] = 0;
+  out[4] = p.form == FORM_PLAIN ? THUNK_ENTRY : THUNK_GENERIC; out[5] = p.grid; out[6] = (operands & 8) ? EPI_C16_ADD : EPI_C16;
   return p.status;
 }
 

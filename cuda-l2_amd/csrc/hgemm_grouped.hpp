@@ -13,6 +13,10 @@
 //     the grid size in that place the empty ids would all fall on the last XCDs.
 //   * Inside a group (grouped_raster): bands of GROUPED_BAND row tiles; inside a band the row tile runs fastest, then the column tile.
 // grouped_find_tile walks all of it serially; the kernels do the prefix sum and the search across a wave's lanes and use the rest as it is.
+// The grouped input gradient (bgemm_mi355x_nn_grouped, hgemm_kernel_nn_grouped.hpp) cuts the rows of ITS A and C by the same offsets, so the
+// whole map is its map too: the two kernels share the front's text (hgemm_grouped_front.inc, with grouped_wave_scan below), the two reference
+// kernels grouped_find_row, the two host sides grouped_tiles_m_max.  Only the device pass sees grouped_wave_scan; everything else in this
+// file stays plain C++.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -92,6 +96,21 @@ HGEMM_HD inline int grouped_find_row(const int* off, int G, int M, int m) {
   const GroupRows r = grouped_rows(off[lo], off[lo + 1], M);
   return (m >= r.start && m < r.end) ? lo : -1;
 }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// (the device pass alone: what hgemm_grouped_front.inc, the front of the two kernels that search the map, sums the lanes' tile counts with)
+// inclusive sum over the 64 lanes (EXEC all ones): Hillis-Steele inside each row of 16 by DPP row shifts -- a lane whose source lies outside
+// its row adds the `old` operand, 0 --, then lane 15 of rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3
+__device__ inline __attribute__((always_inline)) int grouped_wave_scan(int v) {   // (no HIP header in front of this file: __forceinline__ spelled out)
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
+  return v;
+}
+#endif
 
 // ---- the grouped weight gradient (bgemm_mi355x_ta_grouped, hgemm_kernel_ta_grouped.hpp): group g owns k-rows [off[g], off[g + 1]) of BOTH
 // operands and a whole M x N matrix C_g.  The group boundary cuts the K walk, not the rows of C, so the tile count does not depend on the

@@ -5,7 +5,7 @@
 // its tile, or that it has none, from the offsets alone.  A kernel of its own, not an epilogue of hgemm_tn_bf16_kernel: that kernel's
 // tile is a function of the launch, this one's of data.
 //
-// The front, which is what is new:
+// The front, which is what is new (its text is hgemm_grouped_front.inc, shared with hgemm_nn_grouped_kernel):
 //   * Every wave runs the map redundantly -- no LDS, no barrier, the result is wave-uniform and ends in scalar registers.  Lane l holds
 //     the GROUPED_LANE_GROUPS = 4 consecutive groups 4 l .. 4 l + 3: five dword loads of off[4 l .. 4 l + 4] through a descriptor that ends
 //     behind off[G] (a load past it returns 0 and touches nothing), all issued at once: ONE round trip, whatever G is, up to 256 groups.
@@ -45,20 +45,6 @@ struct GroupedArgs {
   int flags;              // ARG_NT_STORE
 };
 
-#if defined(__HIP_DEVICE_COMPILE__)
-// inclusive sum over the 64 lanes (EXEC all ones): Hillis-Steele inside each row of 16 by DPP row shifts -- a lane whose source lies outside
-// its row adds the `old` operand, 0 --, then lane 15 of rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3
-__device__ __forceinline__ int grouped_wave_scan(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-  return v;
-}
-#endif
-
 template <class CFG>
 __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_grouped_kernel(const GroupedArgs ka) {
   prefetch_kernargs<sizeof(GroupedArgs)>();
@@ -80,43 +66,7 @@ __global__ void __launch_bounds__(CFG::THREADS) hgemm_tn_grouped_kernel(const Gr
   // ---- the tile map: offsets -> (group, first row, first column, the group's end row), or no tile --------------------------------
   struct { int m0, n0; } tc;
   int group, row_end;
-  {
-    const __amdgpu_buffer_rsrc_t rsOff = __builtin_amdgcn_make_buffer_rsrc((void*)ka.offsets, 0, ((uint32_t)ka.G + 1u) * 4u, 0x00020000);
-    int o[LG + 1];
-#pragma unroll
-    for (int j = 0; j <= LG; ++j) o[j] = (int)__builtin_amdgcn_raw_buffer_load_b32(rsOff, (uint32_t)(LG * lane + j) * 4u, 0, 0);
-    int t[LG], mine = 0;
-#pragma unroll
-    for (int j = 0; j < LG; ++j) {
-      t[j] = LG * lane + j < ka.G ? grouped_tiles_m(grouped_rows(o[j], o[j + 1], ka.M), BM) : 0;
-      mine += t[j];
-    }
-    const int incl = grouped_wave_scan(mine);
-    const int T = __builtin_amdgcn_readlane(incl, 63) * ka.tiles_n;
-    const int bid = blockIdx.x;
-    if (bid >= T) return;   // beyond the real tile count: nothing loaded but the offsets, no barrier met
-    const int L = grouped_remap(bid, T), q = L / ka.tiles_n;
-    const int owner = __builtin_ctzll(__builtin_amdgcn_ballot_w64(incl > q));   // q < total: some lane's sum passes it
-    // every lane walks its own four groups; the owner's walk stops inside them
-    int before = incl - mine, js = 0, os = o[0], oe = o[1];
-    bool go = true;
-#pragma unroll
-    for (int j = 0; j + 1 < LG; ++j) {
-      go = go && q >= before + t[j];
-      if (go) { before += t[j]; js = j + 1; os = o[j + 1]; oe = o[j + 2]; }
-    }
-    group = LG * owner + __builtin_amdgcn_readlane(js, owner);
-    const int tiles_before = __builtin_amdgcn_readlane(before, owner);
-    const GroupRows gr = grouped_rows(__builtin_amdgcn_readlane(os, owner), __builtin_amdgcn_readlane(oe, owner), ka.M);
-    const int tg = grouped_tiles_m(gr, BM);
-    int tm, tn;
-    grouped_raster(L - tiles_before * ka.tiles_n, tg, ka.tiles_n, tm, tn);
-    // (never taken for offsets the host's bound covers; for others it keeps every row inside the group, whatever the sums wrapped to)
-    if ((unsigned)tm >= (unsigned)tg || (unsigned)tn >= (unsigned)ka.tiles_n || group >= ka.G) return;
-    tc.m0 = gr.start + tm * BM;
-    tc.n0 = tn * BN;
-    row_end = gr.end;
-  }
+#include "hgemm_grouped_front.inc"   // the tile map, one text with hgemm_nn_grouped_kernel
   // what the shared store text reads as `g`: M is the GROUP's end row (its predicate and A's clamp below)
   const struct { elem* C; int ldc, M, N, flags; } g = {ka.C, ka.ldc, row_end, ka.N, ka.flags};
 

@@ -4,6 +4,7 @@
 #include "hgemm_kernel_ta.hpp"
 #include "hgemm_kernel_tn.hpp"
 #include "hgemm_kernel_tn_gated.hpp"
+#include "hgemm_kernel_nn_grouped.hpp"
 #include "hgemm_kernel_ta_grouped.hpp"
 #include "hgemm_kernel_tn_grouped.hpp"
 
@@ -773,6 +774,38 @@ void launch_ta_grouped_reference(const TaGroupedArgs& g, bool c32, hipStream_t s
   const OutArgs o{g.C, nullptr, nullptr, g.ldc, 0, (g.flags & ARG_ACCUMULATE) != 0, nullptr, nullptr, nullptr, 0};
   if (c32) HGEMM_LAUNCH((hgemm_ta_grouped_reference_kernel<OutC32>), grid, 256, stream, ts, g, OutC32::make(o));
   else     HGEMM_LAUNCH((hgemm_ta_grouped_reference_kernel<OutC16<__bf16>>), grid, 256, stream, ts, g, OutC16<__bf16>::make(o));
+}
+
+// ---- the grouped input gradient (bgemm_mi355x_nn_grouped, hgemm_kernel_nn_grouped.hpp): the members' launchers by config id -- the order of
+// tr_table_nn()'s rows -- and the reference kernel of everything outside the kernels' scope.
+#define HGEMM_NN_GROUPED_CELL(...) HGEMM_NN_GROUPED_LAUNCHER(__VA_ARGS__),
+NnGroupedLaunch nn_grouped_launcher(int config) {
+  static const NnGroupedLaunch launchers[] = {HGEMM_TR_MEMBERS(HGEMM_NN_GROUPED_CELL, CfgNNB)};
+  return config >= 0 && config < (int)(sizeof(launchers) / sizeof(launchers[0])) ? launchers[config] : nullptr;
+}
+// hgemm_generic_kernel with the row's group found by grouped_find_row (a row no group owns is neither read nor written) and B the group's
+// matrix: a thread per element, fmaf over k ascending, then the dense kinds' stores -- OutC16<__bf16>, or OutAdd, whose early() loads
+// r[m][n] in the thread that stores C[m][n] (r may be C).
+template <class Out>
+__global__ void __launch_bounds__(256) hgemm_nn_grouped_reference_kernel(const NnGroupedArgs a, const Out out) {
+  using Ops = Operands<__bf16, false, false>;
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= a.N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < a.M; m += gridDim.y * 4) {
+    const int grp = grouped_find_row(a.offsets, a.G, a.M, m);
+    if (grp < 0) continue;
+    const __bf16* w = a.B + (long long)grp * a.group_stride_b;
+    const auto early = out.template early<1>(ElemPos{m, n});
+    float s = 0.f;
+    for (int k = 0; k < a.K; ++k) s = fmaf((float)a.A[Ops::a(m, k, a.lda)], (float)w[Ops::b(k, n, a.ldb)], s);
+    out.template store<1>(ElemPos{m, n}, vec_t<float, 1>(s), early);
+  }
+}
+void launch_nn_grouped_reference(const NnGroupedArgs& g, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((g.N + 63) / 64, (unsigned)std::min<long>(((long)g.M + 3) / 4, 65535));
+  const OutArgs o{g.C, nullptr, nullptr, g.ldc, 0, false, nullptr, nullptr, g.R, g.ldr};
+  if (g.R) HGEMM_LAUNCH((hgemm_nn_grouped_reference_kernel<OutAdd>), grid, 256, stream, ts, g, OutAdd::make(o));
+  else     HGEMM_LAUNCH((hgemm_nn_grouped_reference_kernel<OutC16<__bf16>>), grid, 256, stream, ts, g, OutC16<__bf16>::make(o));
 }
 
 void launch_tail_reduce(const GemmArgs& g, int BM, int BN, hipStream_t stream, TimingSlot ts) {

@@ -57,6 +57,9 @@
 //                                                     offset patterns, byte for byte
 //   hgemm_tune bench --grouped --groups G --rows R --n N --k K [--config name]   the grouped call against the loop of G
 //                                                     bgemm_mi355x_launch_tn_bias calls on the same member, and the price of its empty workgroups
+//   hgemm_tune check|bench --nn-grouped [...]         the same two for bgemm_mi355x_launch_nn_grouped: check over members x {no r, r, r == c} x
+//                                                     {contiguous, padded} x {plain, NT}; bench against the loop of bgemm_mi355x_launch_nn calls,
+//                                                     uniform, skewed and ragged routing (--k defaults to 2048)
 //   hgemm_tune check --ta-grouped                     bgemm_mi355x_launch_ta_grouped / _c32: members x forms x routings against the grouped TA
 //                                                     reference kernel, byte for byte
 //   hgemm_tune bench --ta-grouped --groups G --rows R [--m M --n N --config name --rounds n]   the grouped c32 accumulate call against the loop
@@ -2425,7 +2428,19 @@ static void bench_nn_dact_dbias(TrBench& B) {
 //          two groups) the tuner's interleaved rounds of (1) the grouped call, (2) the loop it replaces -- one bgemm_mi355x_launch_tn_bias per
 //          non-empty group on the SAME member, the offsets known to the host: the loop's sync-free best case --, (3) the grouped call with all
 //          rows on group 0 and (4) the grouped call at G = 1 on the same rows: (3) against (4) is the price of the bound's empty workgroups.
-struct GroupedBufs { uint16_t *a, *w, *bias, *c; int* off; };
+// --nn-grouped: the same two paths for bgemm_mi355x_launch_nn_grouped (`nn` below): the weights are G row-major [K][N] matrices, the third
+// operand is the residual r ([M][ldr]) in place of the bias rows.
+//   check: the GPU tests' routing (M = 300, N = 72, K = 128 and 320) x four members x {no r, r, r == c} x {contiguous, padded strides} x
+//          {plain, NT store} against the grouped NN reference kernel, the same way.
+//   bench: a third routing, "ragged" (no group's row count a multiple of 64); the loop is one bgemm_mi355x_launch_nn per non-empty group; every
+//          row carries the share of the grid bound's workgroups that find no tile.
+struct GroupedBufs { uint16_t *a, *w, *x, *c; int* off; };   // x: the bias rows (tn) / r (nn)
+struct GroupedStrides { int lda, ldb; long long gsb; int ldx, ldc; };
+static int grouped_launch(bool nn, int cfg, int word, const GroupedBufs& b, const uint16_t* x, uint16_t* c, const int* off, int G, int M, int N, int K,
+                          const GroupedStrides& s) {
+  return nn ? bgemm_mi355x_launch_nn_grouped(cfg, word, b.a, b.w, x, c, off, G, M, N, K, s.lda, s.ldb, s.gsb, s.ldx, s.ldc, nullptr)
+            : bgemm_mi355x_launch_tn_grouped(cfg, word, b.a, b.w, x, c, off, G, M, N, K, s.lda, s.ldb, s.gsb, s.ldx, s.ldc, nullptr);
+}
 static std::vector<int> grouped_routing(int G, int M, const char* kind) {
   std::vector<int> rows(G, 0), off(G + 1, 0);
   if (!strcmp(kind, "one_hot")) rows[0] = M;
@@ -2435,6 +2450,8 @@ static std::vector<int> grouped_routing(int G, int M, const char* kind) {
     rows[G - 1] += M - 2 * (M / 4) - (G - 2) * ((M - 2 * (M / 4)) / (G - 2));
   } else {
     for (int g = 0; g < G; ++g) rows[g] = M / G + (g < M % G ? 1 : 0);
+    if (!strcmp(kind, "ragged"))   // pairs of groups trade 21 rows: M / G - 21 and M / G + 21
+      for (int g = 0; g + 1 < G; g += 2) if (rows[g] > 21) { rows[g] -= 21; rows[g + 1] += 21; }
   }
   for (int g = 0; g < G; ++g) off[g + 1] = off[g] + rows[g];
   return off;
@@ -2444,80 +2461,103 @@ static void grouped_fill_small_int(uint16_t* dev, size_t n, uint64_t seed, float
   for (size_t i = 0; i < n; ++i) { seed = seed * 6364136223846793005ull + 1442695040888963407ull; h[i] = bf16_rne((float)((int)((seed >> 33) % 5) - 2) * scale); }
   HIP_OK(hipMemcpy(dev, h.data(), n * 2, hipMemcpyHostToDevice));
 }
-static int grouped_check() {
+static int grouped_check(bool nn) {
   struct Case { int M, N, K; std::vector<int> off; const char* what; };
   std::vector<Case> cases = {{300, 72, 320, {3, 3, 4, 68, 68, 197, 290, 290}, "boundaries"}};
-  for (const char* kind : {"uniform", "skewed", "one_hot"}) cases.push_back({777, 136, 192, grouped_routing(6, 777, kind), kind});
-  cases.push_back({777, 136, 192, {5, 5, 5, 5, 5, 5, 5}, "all empty"});
-  cases.push_back({777, 136, 192, {9, 140, 141, 141, 500, 700, 770}, "dropped ends"});
-  int runs = 0, failures = 0;
-  for (const Case& cs : cases) {
-    const int G = (int)cs.off.size() - 1;
-    const size_t cn = (size_t)cs.M * cs.N;
-    GroupedBufs b;
-    HIP_OK(hipMalloc(&b.a, (size_t)cs.M * cs.K * 2)); HIP_OK(hipMalloc(&b.w, (size_t)G * cs.N * cs.K * 2)); HIP_OK(hipMalloc(&b.bias, (size_t)G * cs.N * 2));
-    HIP_OK(hipMalloc(&b.c, cn * 2 + 16)); HIP_OK(hipMalloc(&b.off, (G + 1) * 4));
-    grouped_fill_small_int(b.a, (size_t)cs.M * cs.K, 11, 1.0f / 64); grouped_fill_small_int(b.w, (size_t)G * cs.N * cs.K, 12, 1.0f);
-    grouped_fill_small_int(b.bias, (size_t)G * cs.N, 13, 1.0f / 256);
-    HIP_OK(hipMemcpy(b.off, cs.off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
-    std::vector<uint16_t> want(cn), got(cn);
-    auto call = [&](int cfg, int word, uint16_t* c, std::vector<uint16_t>& out) {
-      HIP_OK(hipMemset(b.c, 0x7f, cn * 2 + 16));   // bf16 0x7f7f: a finite sentinel
-      const int st = bgemm_mi355x_launch_tn_grouped(cfg, word, b.a, b.w, b.bias, c, b.off, G, cs.M, cs.N, cs.K, cs.K, cs.K, (long long)cs.N * cs.K, cs.N, cs.N, nullptr);
-      const hipError_t e = hipDeviceSynchronize();
-      if (e != hipSuccess) { printf("FAIL grouped %s: hip error %d\n", cs.what, (int)e); exit(3); }
-      HIP_OK(hipMemcpy(out.data(), c, cn * 2, hipMemcpyDeviceToHost));
-      return st;
-    };
-    if (call(0, 1, b.c + 4, want) != HGEMM_OK) { printf("FAIL grouped %s: the reference form's status\n", cs.what); ++failures; }
-    for (int cfg = 0; cfg < bgemm_mi355x_tn_num_configs(); ++cfg)
-      for (int word : {1, 1 | HGEMM_PLAN_NT_STORE}) {
-        ++runs;
-        const bool runs_kernel = bgemm_mi355x_tn_grouped_runs(cfg, G, cs.M, cs.N, cs.K, cs.K, cs.K, (long long)cs.N * cs.K, cs.N, cs.N) == 1;
-        if (call(cfg, word, b.c, got) != HGEMM_OK || !runs_kernel || memcmp(got.data(), want.data(), cn * 2) != 0) {
-          size_t bad = 0;
-          for (size_t i = 0; i < cn; ++i) bad += got[i] != want[i];
-          printf("FAIL grouped %s %d_%d_%d %s word %#x: %zu elements differ from the reference kernel%s\n", cs.what, cs.M, cs.N, cs.K,
-                 bgemm_mi355x_tn_config_name(cfg), word, bad, runs_kernel ? "" : " (not run by the member's kernel)");
-          ++failures;
-        }
-      }
-    HIP_OK(hipFree(b.a)); HIP_OK(hipFree(b.w)); HIP_OK(hipFree(b.bias)); HIP_OK(hipFree(b.c)); HIP_OK(hipFree(b.off));
+  if (nn) {
+    cases.push_back({300, 72, 128, {3, 3, 4, 68, 68, 197, 290, 290}, "boundaries"});
+  } else {
+    for (const char* kind : {"uniform", "skewed", "one_hot"}) cases.push_back({777, 136, 192, grouped_routing(6, 777, kind), kind});
+    cases.push_back({777, 136, 192, {5, 5, 5, 5, 5, 5, 5}, "all empty"});
+    cases.push_back({777, 136, 192, {9, 140, 141, 141, 500, 700, 770}, "dropped ends"});
   }
-  printf("check tn grouped: %d runs, %d failures (the whole C buffer byte for byte against the grouped reference kernel, exact sums)\n", runs, failures);
+  const char* name = nn ? "nn grouped" : "grouped";
+  int runs = 0, failures = 0;
+  for (const Case& cs : cases)
+    for (int padded = 0; padded <= (nn ? 1 : 0); ++padded)
+      for (int form = 0; form < (nn ? 3 : 1); ++form) {   // nn: 0 no r, 1 r, 2 r == c; tn: the bias rows
+        const int G = (int)cs.off.size() - 1;
+        const int wrows = nn ? cs.K : cs.N, wcols = nn ? cs.N : cs.K;   // a weight as it lies
+        GroupedStrides s{cs.K, wcols, (long long)wrows * wcols, cs.N, cs.N};
+        if (padded) s = GroupedStrides{cs.K + 8, wcols + 16, (long long)wrows * (wcols + 16) + 24, cs.N + 8, cs.N + 24};
+        if (form == 2) s.ldx = s.ldc;
+        const size_t cn = (size_t)cs.M * s.ldc, xn = nn ? (size_t)cs.M * s.ldx : (size_t)G * s.ldx;
+        GroupedBufs b;
+        HIP_OK(hipMalloc(&b.a, (size_t)cs.M * s.lda * 2)); HIP_OK(hipMalloc(&b.w, (size_t)G * s.gsb * 2)); HIP_OK(hipMalloc(&b.x, xn * 2));
+        HIP_OK(hipMalloc(&b.c, cn * 2 + 16)); HIP_OK(hipMalloc(&b.off, (G + 1) * 4));
+        grouped_fill_small_int(b.a, (size_t)cs.M * s.lda, 11, 1.0f / 64); grouped_fill_small_int(b.w, (size_t)G * s.gsb, 12, 1.0f);
+        grouped_fill_small_int(b.x, xn, 13, 1.0f / 256);
+        HIP_OK(hipMemcpy(b.off, cs.off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+        std::vector<uint16_t> want(cn), got(cn), init(cn);
+        for (size_t i = 0; i < cn; ++i) init[i] = bf16_rne((float)((int)(i % 7) - 3) / 256);   // what an in-place call reads as r
+        auto call = [&](int cfg, int word, uint16_t* c, std::vector<uint16_t>& out) {
+          HIP_OK(hipMemset(b.c, 0x7f, cn * 2 + 16));   // bf16 0x7f7f: a finite sentinel
+          if (form == 2) HIP_OK(hipMemcpy(c, init.data(), cn * 2, hipMemcpyHostToDevice));
+          const int st = grouped_launch(nn, cfg, word, b, nn && form == 0 ? nullptr : form == 2 ? c : b.x, c, b.off, G, cs.M, cs.N, cs.K, s);
+          const hipError_t e = hipDeviceSynchronize();
+          if (e != hipSuccess) { printf("FAIL %s %s: hip error %d\n", name, cs.what, (int)e); exit(3); }
+          HIP_OK(hipMemcpy(out.data(), c, cn * 2, hipMemcpyDeviceToHost));
+          return st;
+        };
+        if (call(0, 1, b.c + 4, want) != HGEMM_OK) { printf("FAIL %s %s: the reference form's status\n", name, cs.what); ++failures; }
+        for (int cfg = 0; cfg < (nn ? hgemm_mi355x_nn_num_configs() : bgemm_mi355x_tn_num_configs()); ++cfg)
+          for (int word : {1, 1 | HGEMM_PLAN_NT_STORE}) {
+            ++runs;
+            const bool runs_kernel = (nn ? bgemm_mi355x_nn_grouped_runs(cfg, G, cs.M, cs.N, cs.K, s.lda, s.ldb, s.gsb, form ? s.ldx : 0, s.ldc)
+                                         : bgemm_mi355x_tn_grouped_runs(cfg, G, cs.M, cs.N, cs.K, s.lda, s.ldb, s.gsb, s.ldx, s.ldc)) == 1;
+            if (call(cfg, word, b.c, got) != HGEMM_OK || !runs_kernel || memcmp(got.data(), want.data(), cn * 2) != 0) {
+              size_t bad = 0;
+              for (size_t i = 0; i < cn; ++i) bad += got[i] != want[i];
+              printf("FAIL %s %s %d_%d_%d %s form %d padded %d word %#x: %zu elements differ from the reference kernel%s\n", name, cs.what, cs.M, cs.N, cs.K,
+                     nn ? hgemm_mi355x_nn_config_name(cfg) : bgemm_mi355x_tn_config_name(cfg), form, padded, word, bad, runs_kernel ? "" : " (not run by the member's kernel)");
+              ++failures;
+            }
+          }
+        HIP_OK(hipFree(b.a)); HIP_OK(hipFree(b.w)); HIP_OK(hipFree(b.x)); HIP_OK(hipFree(b.c)); HIP_OK(hipFree(b.off));
+      }
+  printf("check %s: %d runs, %d failures (the whole C buffer byte for byte against the grouped reference kernel, exact sums)\n", nn ? "nn grouped" : "tn grouped",
+         runs, failures);
   return failures ? 1 : 0;
 }
-static int grouped_bench(int G, int rows, int N, int K, const char* cfg_name, int rounds) {
+static int grouped_bench(bool nn, int G, int rows, int N, int K, const char* cfg_name, int rounds) {
   const long long M64 = (long long)G * rows;
   if (G < 1 || rows < 1 || N < 1 || K < 1 || M64 > 0x7fffffffLL) { fprintf(stderr, "bench --grouped: --groups G --rows R --n N --k K\n"); return 2; }
   const int M = (int)M64;
-  int cfg = 0;
-  if (cfg_name) cfg = bgemm_mi355x_tn_config_by_name(cfg_name); else bgemm_mi355x_tn_grouped_plan(G, M, N, K, &cfg);
-  if (cfg < 0 || bgemm_mi355x_tn_grouped_runs(cfg, G, M, N, K, K, K, (long long)N * K, N, N) != 1) { fprintf(stderr, "bench --grouped: no member kernel runs this call\n"); return 2; }
+  const GroupedStrides s{K, nn ? N : K, (long long)N * K, N, N};
+  int cfg = 0, info[8] = {0};
+  if (cfg_name) cfg = nn ? hgemm_mi355x_nn_config_by_name(cfg_name) : bgemm_mi355x_tn_config_by_name(cfg_name);
+  else if (nn) bgemm_mi355x_nn_grouped_plan(G, M, N, K, &cfg); else bgemm_mi355x_tn_grouped_plan(G, M, N, K, &cfg);
+  if (cfg < 0 || (nn ? bgemm_mi355x_nn_grouped_runs(cfg, G, M, N, K, s.lda, s.ldb, s.gsb, 0, s.ldc)
+                     : bgemm_mi355x_tn_grouped_runs(cfg, G, M, N, K, s.lda, s.ldb, s.gsb, s.ldx, s.ldc)) != 1) {
+    fprintf(stderr, "bench --grouped: no member kernel runs this call\n"); return 2;
+  }
+  if (nn) hgemm_mi355x_nn_config_info(cfg, info); else bgemm_mi355x_tn_config_info(cfg, info);
   GroupedBufs b;
   int* off_alt[2];
-  HIP_OK(hipMalloc(&b.a, (size_t)M * K * 2)); HIP_OK(hipMalloc(&b.w, (size_t)G * N * K * 2)); HIP_OK(hipMalloc(&b.bias, (size_t)G * N * 2));
+  HIP_OK(hipMalloc(&b.a, (size_t)M * K * 2)); HIP_OK(hipMalloc(&b.w, (size_t)G * N * K * 2)); HIP_OK(hipMalloc(&b.x, (size_t)G * N * 2));
   HIP_OK(hipMalloc(&b.c, (size_t)M * N * 2)); HIP_OK(hipMalloc(&b.off, (G + 1) * 4)); HIP_OK(hipMalloc(&off_alt[0], (G + 1) * 4)); HIP_OK(hipMalloc(&off_alt[1], 8));
   // (fp16 normal bit patterns read as bf16: finite values of mixed magnitude; the timed work does not depend on them)
-  hgemm_fill_normal_f16(b.a, (size_t)M * K, 1, nullptr); hgemm_fill_normal_f16(b.w, (size_t)G * N * K, 2, nullptr); hgemm_fill_normal_f16(b.bias, (size_t)G * N, 3, nullptr);
+  hgemm_fill_normal_f16(b.a, (size_t)M * K, 1, nullptr); hgemm_fill_normal_f16(b.w, (size_t)G * N * K, 2, nullptr); hgemm_fill_normal_f16(b.x, (size_t)G * N, 3, nullptr);
   const std::vector<int> one_hot = grouped_routing(G, M, "one_hot"), single = {0, M};
   HIP_OK(hipMemcpy(off_alt[0], one_hot.data(), (G + 1) * 4, hipMemcpyHostToDevice)); HIP_OK(hipMemcpy(off_alt[1], single.data(), 8, hipMemcpyHostToDevice));
   hipEvent_t e0, e1;
   HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
   std::vector<Buffers> sets(1);   // one operand set: the weights alone (G N K 2 bytes) are what the caches see
-  for (const char* kind : {"uniform", "skewed"}) {
+  for (const char* kind : {"uniform", "skewed", "ragged"}) {
+    if (!nn && !strcmp(kind, "ragged")) continue;
     const std::vector<int> off = grouped_routing(G, M, kind);
     HIP_OK(hipMemcpy(b.off, off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
-    auto grouped = [=](const int* o, int groups) {
-      return bgemm_mi355x_launch_tn_grouped(cfg, 1, b.a, b.w, b.bias, b.c, o, groups, M, N, K, K, K, (long long)N * K, N, N, nullptr);
-    };
+    const uint16_t* x = nn ? nullptr : b.x;   // nn: the plain form, what the loop of bgemm_mi355x_launch_nn computes
+    auto grouped = [=](const int* o, int groups) { return grouped_launch(nn, cfg, 1, b, x, b.c, o, groups, M, N, K, s); };
     std::vector<Contender> cs;
     cs.push_back({"grouped", [=](Buffers&) { return grouped(b.off, G); }});
     cs.push_back({"loop", [=](Buffers&) {
       for (int g = 0; g < G; ++g) {
         if (off[g + 1] == off[g]) continue;
-        const int st = bgemm_mi355x_launch_tn_bias(cfg, 1, b.a + (size_t)off[g] * K, b.w + (size_t)g * N * K, b.bias + (size_t)g * N, b.c + (size_t)off[g] * N,
-                                                   off[g + 1] - off[g], N, K, K, K, N, nullptr);
+        const uint16_t *ag = b.a + (size_t)off[g] * K, *wg = b.w + (size_t)g * N * K;
+        uint16_t* cg = b.c + (size_t)off[g] * N;
+        const int st = nn ? bgemm_mi355x_launch_nn(cfg, 1, ag, wg, cg, off[g + 1] - off[g], N, K, K, N, N, nullptr)
+                          : bgemm_mi355x_launch_tn_bias(cfg, 1, ag, wg, b.x + (size_t)g * N, cg, off[g + 1] - off[g], N, K, K, K, N, nullptr);
         if (st != HGEMM_OK) return st;
       }
       return (int)HGEMM_OK;
@@ -2527,28 +2567,31 @@ static int grouped_bench(int G, int rows, int N, int K, const char* cfg_name, in
     const double est_us = std::max(20.0, 2.0 * M * (double)N * K / 1.0e9);   // (at 1 PFLOP/s; sizes the back-to-back boxes)
     time_interleaved(cs, sets, rounds, 3, 0.05, est_us, e0, e1);
     int max_rows = 0;
-    for (int g = 0; g < G; ++g) max_rows = std::max(max_rows, off[g + 1] - off[g]);
-    printf("{\"bench\": \"tn_grouped\", \"G\": %d, \"rows_per_group\": %d, \"M\": %d, \"N\": %d, \"K\": %d, \"routing\": \"%s\", \"max_rows\": %d, \"config\": \"%s\", "
-           "\"rounds\": %d, \"protocol\": \"interleaved\"", G, rows, M, N, K, kind, max_rows, bgemm_mi355x_tn_config_name(cfg), rounds);
+    long tiles = 0;
+    for (int g = 0; g < G; ++g) { max_rows = std::max(max_rows, off[g + 1] - off[g]); tiles += (off[g + 1] - off[g] + info[0] - 1) / info[0]; }
+    printf("{\"bench\": \"%s\", \"G\": %d, \"rows_per_group\": %d, \"M\": %d, \"N\": %d, \"K\": %d, \"routing\": \"%s\", \"max_rows\": %d, \"config\": \"%s\", "
+           "\"rounds\": %d, \"protocol\": \"interleaved\"", nn ? "nn_grouped" : "tn_grouped", G, rows, M, N, K, kind, max_rows,
+           nn ? hgemm_mi355x_nn_config_name(cfg) : bgemm_mi355x_tn_config_name(cfg), rounds);
+    if (nn) printf(", \"empty_wg_share\": %.3f", 1.0 - (double)tiles / (double)(((long long)M + (long long)G * (info[0] - 1)) / info[0]));
     for (const Contender& c : cs) printf(", \"%s_us\": %.2f, \"%s_stream_us\": %.2f", c.key, c.iso_us(), c.key, c.box_us());
     printf(", \"loop_over_grouped\": %.3f, \"loop_over_grouped_stream\": %.3f, \"one_hot_over_g1\": %.3f}\n", cs[1].iso_us() / cs[0].iso_us(),
            cs[1].box_us() / cs[0].box_us(), cs[2].iso_us() / cs[3].iso_us());
     fflush(stdout);
   }
-  HIP_OK(hipFree(b.a)); HIP_OK(hipFree(b.w)); HIP_OK(hipFree(b.bias)); HIP_OK(hipFree(b.c)); HIP_OK(hipFree(b.off)); HIP_OK(hipFree(off_alt[0])); HIP_OK(hipFree(off_alt[1]));
+  HIP_OK(hipFree(b.a)); HIP_OK(hipFree(b.w)); HIP_OK(hipFree(b.x)); HIP_OK(hipFree(b.c)); HIP_OK(hipFree(b.off)); HIP_OK(hipFree(off_alt[0])); HIP_OK(hipFree(off_alt[1]));
   return 0;
 }
-static int cmd_grouped(const std::string& mode, int argc, char** argv) {
-  int G = 8, rows = 64, N = 4096, K = 4096, rounds = 30;
+static int cmd_grouped(const std::string& mode, bool nn, int argc, char** argv) {
+  int G = 8, rows = 64, N = 4096, K = nn ? 2048 : 4096, rounds = 30;
   const char* cfg_name = nullptr;
   for (int i = 2; i + 1 < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--groups") G = atoi(argv[++i]); else if (a == "--rows") rows = atoi(argv[++i]); else if (a == "--n") N = atoi(argv[++i]);
     else if (a == "--k") K = atoi(argv[++i]); else if (a == "--rounds") rounds = atoi(argv[++i]); else if (a == "--config") cfg_name = argv[++i];
   }
-  if (mode == "check") return grouped_check();
-  if (mode == "bench") return grouped_bench(G, rows, N, K, cfg_name, rounds);
-  fprintf(stderr, "--grouped goes with check or bench\n");
+  if (mode == "check") return grouped_check(nn);
+  if (mode == "bench") return grouped_bench(nn, G, rows, N, K, cfg_name, rounds);
+  fprintf(stderr, "--grouped / --nn-grouped go with check or bench\n");
   return 2;
 }
 
@@ -2706,7 +2749,7 @@ int main(int argc, char** argv) {
   }
   std::string mode = argv[1];
   for (int i = 2; i < argc; ++i)
-    if (!strcmp(argv[i], "--grouped")) return cmd_grouped(mode, argc, argv);
+    if (!strcmp(argv[i], "--grouped") || !strcmp(argv[i], "--nn-grouped")) return cmd_grouped(mode, argv[i][2] == 'n', argc, argv);
   for (int i = 2; i < argc; ++i)
     if (!strcmp(argv[i], "--ta-grouped")) return cmd_ta_grouped(mode, argc, argv);
   TrFlags tr;   // --layout, --bf16, --c32, --bias, --act, --aux, --dact, --dbias

@@ -786,7 +786,8 @@ int bgemm_mi355x_nn_add_runs(int nn_config, int M, int N, int K, int lda, int ld
  * anything else is answered by the grouped reference kernel (status 0, the same semantics, slow: bgemm_mi355x_tn_grouped_runs tells).
  * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL a, b_col_major, c or offsets; G < 1; M, N or K < 1; lda < K, ldb < K, ldc < N,
  * ldbias < N (with a bias); group_stride_b < (N - 1) ldb + K; an id outside the table; more than one split in the word.
- * Out of scope: the grouped gated forward, the grouped input gradient, fp16, int64 offsets (the weight gradient: bgemm_mi355x_ta_grouped). */
+ * Out of scope: the grouped gated forward, fp16, int64 offsets (the weight gradient: bgemm_mi355x_ta_grouped, the input gradient:
+ * bgemm_mi355x_nn_grouped). */
 #define HGEMM_GROUPED_MAX_GROUPS 256
 /* planned, contiguous (lda = ldb = K, group_stride_b = N K, ldbias = ldc = N) */
 int bgemm_mi355x_tn_grouped(const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets, int G, int M, int N, int K,
@@ -829,8 +830,8 @@ int bgemm_mi355x_tn_grouped_plan(int G, int M, int N, int K, int* tn_config);
  * (status 0, the same semantics, slow: bgemm_mi355x_ta_grouped_runs / _c32_runs tell).
  * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL pointer; G, M, N or K < 1; lda < M, ldb < N or ldc < N;
  * group_stride_c < (M - 1) ldc + N; an id outside the table; accumulate outside {0, 1}; more than one split in the word.
- * Out of scope: the grouped input gradient, the grouped gated forward, a grouped bias gradient, fp16, int64 offsets, splitting a heavy
- * group's walk. */
+ * Out of scope: the grouped gated forward, a grouped bias gradient, fp16, int64 offsets, splitting a heavy group's walk (the input
+ * gradient: bgemm_mi355x_nn_grouped). */
 /* planned, contiguous (lda = M, ldb = ldc = N, group_stride_c = M N) */
 int bgemm_mi355x_ta_grouped_c32(const void* a_col_major, const void* b, float* c32, const int* offsets, int G, int M, int N, int K, int accumulate,
                                 void* stream);
@@ -844,6 +845,45 @@ int bgemm_mi355x_ta_grouped_runs(int ta_config, int G, int M, int N, int K, int 
 int bgemm_mi355x_ta_grouped_c32_runs(int ta_config, int G, int M, int N, int K, int lda, int ldb, int ldc, long long group_stride_c);
 /* the member the planned calls take */
 int bgemm_mi355x_ta_grouped_plan(int G, int M, int N, int K, int* ta_config);
+
+/* ------------------------------------------------------------------------------------------
+ * Grouped input gradient, dX_g = dY_g W_g for every expert of a mixture-of-experts layer in ONE launch, from the forward call's offsets: with
+ * bgemm_mi355x_tn_grouped and bgemm_mi355x_ta_grouped the three products of an expert layer, none of which reads the offsets on the host.
+ * The rows of a, r and c are sorted by group; group g of G owns rows [offsets[g], offsets[g + 1]) and its own row-major matrix
+ * B_g = b + g group_stride_b, [K][ldb] with N contiguous.
+ * Semantics, exactly, for every g and every row m of it:
+ *     S = sum_k a[m][k] B_g[k][n]                                   (fp32 accumulation, the dense NN kernel's order)
+ *     r == NULL:  C[m][n] = bf16_rne( S )                           (S = -0.0 stays -0.0: not the r form with zeros)
+ *     r != NULL:  C[m][n] = bf16_rne( fl32( S + float(r[m][n]) ) )  (one fp32 add, one rounding, as bgemm_mi355x_nn_add)
+ *   - a is [M][lda] bf16, r is [M][ldr] bf16 or NULL, c is [M][ldc] bf16.  For the forward Y = X W_g^T with W stacked [G][Nout][Kin]: a = dY,
+ *     b = the SAME weight buffer as the forward call's b_col_major, M = tokens, K = Nout, N = Kin, group_stride_b = Nout Kin.  No
+ *     transposed copy of the weights exists anywhere.  The gated backward's dX = dG Wg + dU Wu is two calls, the second with r = c.
+ *   - offsets is a DEVICE pointer to G + 1 int32, the forward call's vector.  The host never reads it: no copy, no synchronisation, no
+ *     workspace.  The call can be captured in a graph on a fresh stream with nothing reserved, and a replay follows whatever the buffer
+ *     holds then.  Malformed offsets are defined by the forward call's clamp, not checked.
+ *   - Rows of c outside [offsets[0], offsets[G]) and pad columns are not written; rows of a and r that no group owns are not read for any
+ *     stored value.
+ *   - r may be c itself (ldr == ldc required then): each element is computed from the old r.
+ *   - G = 1 with offsets {0, M} gives bgemm_mi355x_launch_nn's C (r == NULL) and bgemm_mi355x_launch_nn_add's (with r), unsplit, same
+ *     nn_config, bit for bit.
+ * nn_config is one of the four n... members (hgemm_mi355x_nn_config_*).  word: HGEMM_PLAN_NT_STORE is honoured; its split count must be 1 (or
+ * 0) -- there is no split-K form, a larger count is refused.  The planned call picks the member by the forward call's stated rule from
+ * (ceil(M / G), N, K) over the NN table; untuned.
+ * The members' kernels serve K % 64 == 0, N % 8 == 0, lda / ldb / ldc / ldr / group_stride_b multiples of 8, 16-byte aligned pointers,
+ * (BM lda + K) 2, ((K - 1) ldb + N) 2, (BM ldc + N) 2 and (BM ldr + N) 2 bytes below 2 GiB, G <= HGEMM_GROUPED_MAX_GROUPS and a grid bound that
+ * fits an int; anything else is answered by the grouped NN reference kernel (status 0, the same semantics, slow:
+ * bgemm_mi355x_nn_grouped_runs tells).
+ * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL a, b, c or offsets; G, M, N or K < 1; lda < K, ldb < N, ldc < N; ldr < N (with an
+ * r); r == c with ldr != ldc; group_stride_b < (K - 1) ldb + N; an id outside the table; more than one split in the word.
+ * Out of scope: the grouped gated forward, a dact / dgated epilogue, fp16, int64 offsets. */
+/* planned, contiguous (lda = K, ldb = N, group_stride_b = K N, ldr = ldc = N) */
+int bgemm_mi355x_nn_grouped(const void* a, const void* b, const void* r, void* c, const int* offsets, int G, int M, int N, int K, void* stream);
+int bgemm_mi355x_launch_nn_grouped(int nn_config, int word, const void* a, const void* b, const void* r, void* c, const int* offsets, int G, int M, int N,
+                                   int K, int lda, int ldb, long long group_stride_b, int ldr, int ldc, void* stream);
+/* 1 when the call (with aligned pointers) runs the member's kernel, 0 when the reference kernel answers or the call is refused; ldr = 0: no r */
+int bgemm_mi355x_nn_grouped_runs(int nn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldr, int ldc);
+/* the member the planned call takes */
+int bgemm_mi355x_nn_grouped_plan(int G, int M, int N, int K, int* nn_config);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
