@@ -61,6 +61,8 @@ LIB_SOURCES = [
     "hgemm_inst_g23.hip",
     "hgemm_inst_g24.hip",
     "hgemm_inst_g25.hip",
+    "hgemm_inst_g26.hip",
+    "hgemm_inst_g27.hip",
     "hgemm_registry.hip",
     "hgemm_plan.hip",
     "hgemm_api.hip",

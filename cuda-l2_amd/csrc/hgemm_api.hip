@@ -7,6 +7,7 @@
 #include "hgemm_kernel_nn_grouped.hpp"
 #include "hgemm_kernel_ta_grouped.hpp"
 #include "hgemm_kernel_tn_grouped.hpp"
+#include "hgemm_kernel_tn_grouped_gated.hpp"
 #include "hgemm_act.hpp"
 #include "../../include/hgemm_mi355x.h"
 
@@ -1389,6 +1390,77 @@ int bgemm_mi355x_selfcheck_launch_tn_grouped(int tn_config, int word, int operan
                                              int ldbias, int ldc, long long out[20]) {
   if (!out) return HGEMM_ERR_BAD_ARG;
   const GroupedPlan p = grouped_resolve(tn_config, word, (operands & 4) != 0, (operands & 8) != 0, G, M, N, K, lda, ldb, group_stride_b, ldbias, ldc);
+  out[0] = p.form; out[1] = p.status == HGEMM_OK ? 1 : 0; out[2] = out[3] = 0;
+  out[4] = p.form == FORM_PLAIN ? THUNK_ENTRY : THUNK_GENERIC; out[5] = p.grid;
+  return p.status;
+}
+
+// ---- the grouped gated forward (bgemm_mi355x_tn_grouped_gated, hgemm_kernel_tn_grouped_gated.hpp): group g owns rows [offsets[g], offsets[g + 1])
+// of a, c, g_out and u_out, the two weights wg + g group_stride_b and wu + g group_stride_b and its two bias rows.  The forward grouped call's
+// host side with the gated call's tile: a device offsets pointer the host never reads, one dispatch whose grid is the bound
+// grouped_tiles_m_max x ceil(N / (BN / 2)), or the grouped gated reference kernel for what is outside the kernels' scope.  No plan, table or
+// workspace of its own: the members are family f's, the planned call takes grouped_model_plan at width 2 N.
+namespace {
+// host logic only (bgemm_mi355x_selfcheck_launch_tn_grouped_gated shows it to the tests); `aligned`: every given pointer is 16-byte aligned;
+// has_bias: either bias is given (ldbias is read); aux: g_out and u_out are given (ldz is read)
+GroupedPlan grouped_gated_resolve(int config, int word, bool aligned, bool has_bias, bool aux, int G, int M, int N, int K, int lda, int ldb, long long gsb,
+                                  int ldbias, int ldc, int ldz, int act) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || config < 0 || config >= kLayoutTN.t.count || !act_known_gated(act) || lda < K || ldb < K ||
+      ldc < N || (aux && ldz < N) || (has_bias && ldbias < N) || gsb < (long long)(N - 1) * ldb + K || (word & HGEMM_SPLITK_MASK) > 1)
+    return {HGEMM_ERR_BAD_ARG, FORM_REFERENCE, 0};
+  const TrEntry& e = kLayoutTN.t.rows[config].e;
+  const int wn = e.bn / 2;   // a tile's OUTPUT width
+  const long long grid = grouped_tiles_m_max(M, G, e.bm) * ((N + wn - 1) / wn);
+  const bool z_ok = !aux || ((ldz & 7) == 0 && ((double)e.bm * ldz + N) * 2.0 < 2147483648.0);   // g_out / u_out: C's rules
+  const bool kernel = aligned && z_ok && G <= GROUPED_MAX_GROUPS && K % BK == 0 && (N & 7) == 0 && !((lda | ldb | ldc) & 7) && !(has_bias && (ldbias & 7)) &&
+                      (gsb & 7) == 0 && kLayoutTN.reach_ok(out_gated(act), e, M, N, K, lda, ldb, ldc) && grid <= 0x7fffffffLL;
+  return {HGEMM_OK, kernel ? FORM_PLAIN : FORM_REFERENCE, kernel ? grid : 0};
+}
+}  // namespace
+int bgemm_mi355x_tn_grouped_gated_runs(int tn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldbias, int ldc, int ldz) {
+  const GroupedPlan p = grouped_gated_resolve(tn_config, 1, true, true, ldz != 0, G, M, N, K, lda, ldb, group_stride_b, ldbias, ldc, ldz, HGEMM_ACT_RELU);
+  return p.status == HGEMM_OK && p.form == FORM_PLAIN ? 1 : 0;
+}
+int bgemm_mi355x_launch_tn_grouped_gated(int tn_config, int word, const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g,
+                                         const void* bias_u, void* c, void* g_out, void* u_out, const int* offsets, int G, int M, int N, int K, int lda,
+                                         int ldb, long long group_stride_b, int ldbias, int ldc, int ldz, int act, void* stream) {
+  DisarmTiming disarm_timing;
+  if (!a || !wg_col_major || !wu_col_major || !c || !offsets || !g_out != !u_out || (g_out && (g_out == u_out || g_out == c || u_out == c)))
+    return HGEMM_ERR_BAD_ARG;
+  const bool aligned = !(((uintptr_t)a | (uintptr_t)wg_col_major | (uintptr_t)wu_col_major | (uintptr_t)c | (uintptr_t)bias_g | (uintptr_t)bias_u |
+                          (uintptr_t)g_out | (uintptr_t)u_out) & 15);
+  const GroupedPlan p = grouped_gated_resolve(tn_config, word, aligned, bias_g || bias_u, g_out != nullptr, G, M, N, K, lda, ldb, group_stride_b, ldbias,
+                                              ldc, ldz, act);
+  if (p.status != HGEMM_OK) return p.status;
+  GroupedGatedArgs g{};
+  g.A = (const __bf16*)a; g.B = (const __bf16*)wg_col_major; g.Bu = (const __bf16*)wu_col_major; g.bias = (const __bf16*)bias_g;
+  g.bias_u = (const __bf16*)bias_u; g.C = (__bf16*)c; g.G_out = (__bf16*)g_out; g.U_out = (__bf16*)u_out; g.offsets = offsets;
+  g.group_stride_b = group_stride_b;
+  g.G = G; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldbias = ldbias; g.ldc = ldc; g.ldz = g_out ? ldz : 0;
+  const int wn = kLayoutTN.t.rows[tn_config].e.bn / 2;
+  g.tiles_n = (N + wn - 1) / wn;
+  g.flags = (word & HGEMM_PLAN_NT_STORE) ? ARG_NT_STORE : 0;
+  const TimingSlot ts = timing_slot(true, true);
+  if (p.form == FORM_PLAIN) tn_grouped_gated_launcher(tn_config, act, g_out != nullptr)(g, (int)p.grid, (hipStream_t)stream, ts);
+  else launch_tn_grouped_gated_reference(g, act, (hipStream_t)stream, ts);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) { g_last_hip_error = (int)err; return HGEMM_ERR_HIP; }
+  return HGEMM_OK;
+}
+int bgemm_mi355x_tn_grouped_gated(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c,
+                                  void* g_out, void* u_out, const int* offsets, int G, int M, int N, int K, int act, void* stream) {
+  if (G < 1 || M <= 0 || N <= 0 || K <= 0 || N >= (1 << 30)) return HGEMM_ERR_BAD_ARG;   // (2 N is an int)
+  return bgemm_mi355x_launch_tn_grouped_gated(grouped_model_plan(kLayoutTN, G, M, 2 * N), 1, a, wg_col_major, wu_col_major, bias_g, bias_u, c, g_out, u_out,
+                                              offsets, G, M, N, K, K, K, (long long)N * K, N, N, N, act, stream);
+}
+// what bgemm_mi355x_launch_tn_grouped_gated decides, nothing launched (not part of the public header): operands & 4: the pointers are 16-byte
+// aligned, operands & 8: a bias is given, operands & 16: g_out and u_out are given.  Returns the call's status; out = {form, dispatches (1), 0, 0,
+// thunk, grid (0: the reference kernel's own)}.
+int bgemm_mi355x_selfcheck_launch_tn_grouped_gated(int tn_config, int word, int operands, int G, int M, int N, int K, int lda, int ldb,
+                                                   long long group_stride_b, int ldbias, int ldc, int ldz, int act, long long out[20]) {
+  if (!out) return HGEMM_ERR_BAD_ARG;
+  const GroupedPlan p = grouped_gated_resolve(tn_config, word, (operands & 4) != 0, (operands & 8) != 0, (operands & 16) != 0, G, M, N, K, lda, ldb,
+                                              group_stride_b, ldbias, ldc, ldz, act);
   out[0] = p.form; out[1] = p.status == HGEMM_OK ? 1 : 0; out[2] = out[3] = 0;
   out[4] = p.form == FORM_PLAIN ? THUNK_ENTRY : THUNK_GENERIC; out[5] = p.grid;
   return p.status;

@@ -7,6 +7,7 @@
 #include "hgemm_kernel_nn_grouped.hpp"
 #include "hgemm_kernel_ta_grouped.hpp"
 #include "hgemm_kernel_tn_grouped.hpp"
+#include "hgemm_kernel_tn_grouped_gated.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -739,6 +740,56 @@ __global__ void __launch_bounds__(256) hgemm_tn_grouped_reference_kernel(const G
 void launch_tn_grouped_reference(const GroupedArgs& g, hipStream_t stream, TimingSlot ts) {
   dim3 grid((g.N + 63) / 64, (unsigned)std::min<long>(((long)g.M + 3) / 4, 65535));
   HGEMM_LAUNCH(hgemm_tn_grouped_reference_kernel, grid, 256, stream, ts, g);
+}
+
+// ---- the grouped gated forward (bgemm_mi355x_tn_grouped_gated, hgemm_kernel_tn_grouped_gated.hpp): the members' launchers by (aux, activation,
+// config id) -- each row one expansion of the member list -- and the reference kernel of everything outside the kernels' scope.
+#define HGEMM_TN_GROUPED_GATED_CELL(...) HGEMM_TN_GROUPED_GATED_LAUNCHER(__VA_ARGS__),
+GroupedGatedLaunch tn_grouped_gated_launcher(int config, int act, bool aux) {
+  constexpr int MEMBERS = 4;
+  static const GroupedGatedLaunch launchers[2][ACT_SILU][MEMBERS] = {
+      {{HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_RELU, false, CfgTNB)}, {HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_GELU, false, CfgTNB)},
+       {HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_GELU_TANH, false, CfgTNB)}, {HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_SILU, false, CfgTNB)}},
+      {{HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_RELU, true, CfgTNB)}, {HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_GELU, true, CfgTNB)},
+       {HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_GELU_TANH, true, CfgTNB)}, {HGEMM_TR_MEMBERS(HGEMM_TN_GROUPED_GATED_CELL, ACT_SILU, true, CfgTNB)}}};
+  return config >= 0 && config < MEMBERS && act >= ACT_RELU && act <= ACT_SILU ? launchers[aux][act - ACT_RELU][config] : nullptr;
+}
+// hgemm_tn_grouped_reference_kernel with two sums: the row's group by grouped_find_row (a row no group owns is written in none of the outputs),
+// both sums by fmaf in k order, each group bias (NULL: +0.0) one fp32 add (gated_pre), g_out / u_out rounded from those when given, C from the
+// UNROUNDED values -- the member kernels' bits wherever the sums are exact in any order and the activation is ReLU.
+template <int ACT>
+__global__ void __launch_bounds__(256) hgemm_tn_grouped_gated_reference_kernel(const GroupedGatedArgs a) {
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (n >= a.N) return;
+  for (int m = blockIdx.y * 4 + (threadIdx.x >> 6); m < a.M; m += gridDim.y * 4) {
+    const int grp = grouped_find_row(a.offsets, a.G, a.M, m);
+    if (grp < 0) continue;
+    const __bf16* x = a.A + (size_t)m * a.lda;
+    const long long w = (long long)grp * a.group_stride_b + (long long)n * a.ldb;
+    const __bf16* wg = a.B + w;
+    const __bf16* wu = a.Bu + w;
+    float sg = 0.f, su = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+      sg = fmaf((float)x[k], (float)wg[k], sg);
+      su = fmaf((float)x[k], (float)wu[k], su);
+    }
+    const float gv = gated_pre(sg, a.bias ? (float)a.bias[(size_t)grp * a.ldbias + n] : 0.0f);
+    const float uv = gated_pre(su, a.bias_u ? (float)a.bias_u[(size_t)grp * a.ldbias + n] : 0.0f);
+    if (a.G_out) {
+      a.G_out[(size_t)m * a.ldz + n] = (__bf16)gv;
+      a.U_out[(size_t)m * a.ldz + n] = (__bf16)uv;
+    }
+    a.C[(size_t)m * a.ldc + n] = (__bf16)gated_mul(act_apply<ACT>(gv), uv);
+  }
+}
+void launch_tn_grouped_gated_reference(const GroupedGatedArgs& g, int act, hipStream_t stream, TimingSlot ts) {
+  dim3 grid((g.N + 63) / 64, (unsigned)std::min<long>(((long)g.M + 3) / 4, 65535));
+  switch (act) {
+    case ACT_RELU:      HGEMM_LAUNCH((hgemm_tn_grouped_gated_reference_kernel<ACT_RELU>), grid, 256, stream, ts, g); break;
+    case ACT_GELU:      HGEMM_LAUNCH((hgemm_tn_grouped_gated_reference_kernel<ACT_GELU>), grid, 256, stream, ts, g); break;
+    case ACT_GELU_TANH: HGEMM_LAUNCH((hgemm_tn_grouped_gated_reference_kernel<ACT_GELU_TANH>), grid, 256, stream, ts, g); break;
+    default:            HGEMM_LAUNCH((hgemm_tn_grouped_gated_reference_kernel<ACT_SILU>), grid, 256, stream, ts, g); break;
+  }
 }
 
 // ---- the grouped weight gradient (bgemm_mi355x_ta_grouped, hgemm_kernel_ta_grouped.hpp): the members' launchers by config id -- the order of

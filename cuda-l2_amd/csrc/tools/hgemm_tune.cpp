@@ -60,6 +60,11 @@
 //   hgemm_tune check|bench --nn-grouped [...]         the same two for bgemm_mi355x_launch_nn_grouped: check over members x {no r, r, r == c} x
 //                                                     {contiguous, padded} x {plain, NT}; bench against the loop of bgemm_mi355x_launch_nn calls,
 //                                                     uniform, skewed and ragged routing (--k defaults to 2048)
+//   hgemm_tune check --tn-grouped-gated               bgemm_mi355x_launch_tn_grouped_gated: members x {no aux, aux} x {plain, NT} x routings against
+//                                                     the grouped gated reference kernel, ReLU, all three outputs byte for byte
+//   hgemm_tune bench --tn-grouped-gated --groups G --rows R --n N --k K [--act silu --aux --config name]   the new call against the loop of G
+//                                                     bgemm_mi355x_launch_tn_gated(_aux) calls, against bgemm_mi355x_launch_tn_grouped at width 2 N
+//                                                     (the unfused path without its element-wise kernel) and against itself at G = 1
 //   hgemm_tune check --ta-grouped                     bgemm_mi355x_launch_ta_grouped / _c32: members x forms x routings against the grouped TA
 //                                                     reference kernel, byte for byte
 //   hgemm_tune bench --ta-grouped --groups G --rows R [--m M --n N --config name --rounds n]   the grouped c32 accumulate call against the loop
@@ -2595,6 +2600,147 @@ static int cmd_grouped(const std::string& mode, bool nn, int argc, char** argv) 
   return 2;
 }
 
+// ---- check|bench --tn-grouped-gated: bgemm_mi355x_launch_tn_grouped_gated (the gated forward of every expert from device offsets) ---------------
+//   check: four members x {no aux, aux} x {plain, NT store} x the forward check's routings, ReLU, each expert's weight one fused [2 N][K] matrix
+//          (wu = wg + N ldb), the member's kernel against the grouped gated REFERENCE kernel (the same call with C moved 8 bytes: misaligned, so
+//          the reference kernel answers) on small-integer operands whose sums are exact in fp32 in any order: all three output buffers byte for
+//          byte, which covers the rows no group owns and the sentinel behind them.
+//   bench: G groups of R rows (uniform and skewed routing), the tuner's interleaved rounds of (1) the new call, (2) the loop it replaces -- one
+//          bgemm_mi355x_launch_tn_gated(_aux) per non-empty group on the SAME member, the offsets known to the host --, (3)
+//          bgemm_mi355x_launch_tn_grouped at width 2 N on the fused weight: the unfused path WITHOUT its element-wise kernel, a lower bound of
+//          it, and (4) the new call at G = 1 on the same rows.  grouped2n_spread is max / min over case (3)'s own rounds: the noise floor of
+//          (1) against (3).
+static int grouped_gated_check() {
+  struct Case { int M, N, K; std::vector<int> off; const char* what; };
+  std::vector<Case> cases = {{300, 72, 320, {3, 3, 4, 68, 68, 197, 290, 290}, "boundaries"}};
+  for (const char* kind : {"uniform", "skewed", "one_hot"}) cases.push_back({777, 136, 192, grouped_routing(6, 777, kind), kind});
+  cases.push_back({777, 136, 192, {5, 5, 5, 5, 5, 5, 5}, "all empty"});
+  cases.push_back({777, 136, 192, {9, 140, 141, 141, 500, 700, 770}, "dropped ends"});
+  int runs = 0, failures = 0;
+  for (const Case& cs : cases)
+    for (int aux = 0; aux <= 1; ++aux) {
+      const int G = (int)cs.off.size() - 1, M = cs.M, N = cs.N, K = cs.K;
+      const long long gsb = 2LL * N * K;
+      const size_t cn = (size_t)M * N;
+      uint16_t *a, *w, *x, *out;   // out: C, g_out, u_out, one after the other with 16 elements of slack each
+      int* off;
+      HIP_OK(hipMalloc(&a, (size_t)M * K * 2)); HIP_OK(hipMalloc(&w, (size_t)G * gsb * 2)); HIP_OK(hipMalloc(&x, (size_t)G * 2 * N * 2));
+      HIP_OK(hipMalloc(&out, 3 * (cn + 16) * 2)); HIP_OK(hipMalloc(&off, (G + 1) * 4));
+      grouped_fill_small_int(a, (size_t)M * K, 11, 1.0f / 64); grouped_fill_small_int(w, (size_t)G * gsb, 12, 1.0f); grouped_fill_small_int(x, (size_t)G * 2 * N, 13, 1.0f / 256);
+      HIP_OK(hipMemcpy(off, cs.off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+      std::vector<uint16_t> want(3 * (cn + 16)), got(3 * (cn + 16));
+      auto call = [&](int cfg, int word, int shift, std::vector<uint16_t>& res) {   // shift: elements C is moved by (4: misaligned)
+        HIP_OK(hipMemset(out, 0x7f, 3 * (cn + 16) * 2));   // bf16 0x7f7f: a finite sentinel
+        const int st = bgemm_mi355x_launch_tn_grouped_gated(cfg, word, a, w, w + (size_t)N * K, x, x + N, out + shift, aux ? out + cn + 16 : nullptr,
+                                                            aux ? out + 2 * (cn + 16) : nullptr, off, G, M, N, K, K, K, gsb, 2 * N, N, N, HGEMM_ACT_RELU, nullptr);
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) { printf("FAIL tn grouped gated %s: hip error %d\n", cs.what, (int)e); exit(3); }
+        HIP_OK(hipMemcpy(res.data(), out, 3 * (cn + 16) * 2, hipMemcpyDeviceToHost));
+        return st;
+      };
+      if (call(0, 1, 4, want) != HGEMM_OK) { printf("FAIL tn grouped gated %s: the reference form's status\n", cs.what); ++failures; }
+      std::memmove(want.data(), want.data() + 4, cn * 2);   // C as the aligned call lays it; the 4 elements behind it are sentinel in both
+      for (int i = 0; i < 4; ++i) want[cn + i] = 0x7f7f;
+      for (int cfg = 0; cfg < bgemm_mi355x_tn_num_configs(); ++cfg)
+        for (int word : {1, 1 | HGEMM_PLAN_NT_STORE}) {
+          ++runs;
+          const bool runs_kernel = bgemm_mi355x_tn_grouped_gated_runs(cfg, G, M, N, K, K, K, gsb, 2 * N, N, aux ? N : 0) == 1;
+          if (call(cfg, word, 0, got) != HGEMM_OK || !runs_kernel || memcmp(got.data(), want.data(), got.size() * 2) != 0) {
+            size_t bad = 0;
+            for (size_t i = 0; i < got.size(); ++i) bad += got[i] != want[i];
+            printf("FAIL tn grouped gated %s %d_%d_%d %s aux %d word %#x: %zu elements differ from the reference kernel%s\n", cs.what, M, N, K,
+                   bgemm_mi355x_tn_config_name(cfg), aux, word, bad, runs_kernel ? "" : " (not run by the member's kernel)");
+            ++failures;
+          }
+        }
+      HIP_OK(hipFree(a)); HIP_OK(hipFree(w)); HIP_OK(hipFree(x)); HIP_OK(hipFree(out)); HIP_OK(hipFree(off));
+    }
+  printf("check tn grouped gated: %d runs, %d failures (C, g_out and u_out byte for byte against the grouped gated reference kernel, exact sums, ReLU)\n", runs, failures);
+  return failures ? 1 : 0;
+}
+static int grouped_gated_bench(int G, int rows, int N, int K, int act, bool aux, const char* cfg_name, int rounds) {
+  const long long M64 = (long long)G * rows;
+  if (G < 1 || rows < 1 || N < 1 || K < 1 || M64 > 0x7fffffffLL || N >= (1 << 30)) { fprintf(stderr, "bench --tn-grouped-gated: --groups G --rows R --n N --k K\n"); return 2; }
+  const int M = (int)M64;
+  const long long gsb = 2LL * N * K;   // each expert's weight one fused [2 N][K] matrix
+  int cfg = 0;
+  if (cfg_name) cfg = bgemm_mi355x_tn_config_by_name(cfg_name); else bgemm_mi355x_tn_grouped_plan(G, M, 2 * N, K, &cfg);
+  if (cfg < 0 || bgemm_mi355x_tn_grouped_gated_runs(cfg, G, M, N, K, K, K, gsb, 2 * N, N, aux ? 2 * N : 0) != 1 ||
+      bgemm_mi355x_tn_grouped_runs(cfg, G, M, 2 * N, K, K, K, gsb, 2 * N, 2 * N) != 1) {
+    fprintf(stderr, "bench --tn-grouped-gated: no member kernel runs this call\n"); return 2;
+  }
+  uint16_t *a, *w, *x, *c, *gu;   // gu: [M][2 N], g_out | u_out of the aux form and the C of case (3)
+  int *off_d, *off_g1;
+  HIP_OK(hipMalloc(&a, (size_t)M * K * 2)); HIP_OK(hipMalloc(&w, (size_t)G * gsb * 2)); HIP_OK(hipMalloc(&x, (size_t)G * 2 * N * 2));
+  HIP_OK(hipMalloc(&c, (size_t)M * N * 2)); HIP_OK(hipMalloc(&gu, (size_t)M * 2 * N * 2)); HIP_OK(hipMalloc(&off_d, (G + 1) * 4)); HIP_OK(hipMalloc(&off_g1, 8));
+  // (fp16 normal bit patterns read as bf16: finite values of mixed magnitude; the timed work does not depend on them)
+  hgemm_fill_normal_f16(a, (size_t)M * K, 1, nullptr); hgemm_fill_normal_f16(w, (size_t)G * gsb, 2, nullptr); hgemm_fill_normal_f16(x, (size_t)G * 2 * N, 3, nullptr);
+  const std::vector<int> single = {0, M};
+  HIP_OK(hipMemcpy(off_g1, single.data(), 8, hipMemcpyHostToDevice));
+  hipEvent_t e0, e1;
+  HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+  std::vector<Buffers> sets(1);
+  uint16_t *go = aux ? gu : nullptr, *uo = aux ? gu + N : nullptr;
+  for (const char* kind : {"uniform", "skewed"}) {
+    const std::vector<int> off = grouped_routing(G, M, kind);
+    HIP_OK(hipMemcpy(off_d, off.data(), (G + 1) * 4, hipMemcpyHostToDevice));
+    auto gated = [=](const int* o, int groups) {
+      return bgemm_mi355x_launch_tn_grouped_gated(cfg, 1, a, w, w + (size_t)N * K, x, x + N, c, go, uo, o, groups, M, N, K, K, K, gsb, 2 * N, N, 2 * N, act, nullptr);
+    };
+    std::vector<Contender> cs;
+    cs.push_back({"gated", [=](Buffers&) { return gated(off_d, G); }});
+    cs.push_back({"loop", [=](Buffers&) {
+      for (int g = 0; g < G; ++g) {
+        if (off[g + 1] == off[g]) continue;
+        const int mg = off[g + 1] - off[g];
+        const uint16_t *ag = a + (size_t)off[g] * K, *wg = w + (size_t)g * gsb, *xg = x + (size_t)g * 2 * N;
+        uint16_t* cg = c + (size_t)off[g] * N;
+        const int st = aux ? bgemm_mi355x_launch_tn_gated_aux(cfg, 1, ag, wg, wg + (size_t)N * K, xg, xg + N, cg, go + (size_t)off[g] * 2 * N, uo + (size_t)off[g] * 2 * N, mg,
+                                                              N, K, K, K, N, 2 * N, act, nullptr)
+                           : bgemm_mi355x_launch_tn_gated(cfg, 1, ag, wg, wg + (size_t)N * K, xg, xg + N, cg, mg, N, K, K, K, N, act, nullptr);
+        if (st != HGEMM_OK) return st;
+      }
+      return (int)HGEMM_OK;
+    }});
+    cs.push_back({"grouped2n", [=](Buffers&) { return bgemm_mi355x_launch_tn_grouped(cfg, 1, a, w, x, gu, off_d, G, M, 2 * N, K, K, K, gsb, 2 * N, 2 * N, nullptr); }});
+    cs.push_back({"gated_g1", [=](Buffers&) { return gated(off_g1, 1); }});
+    const double est_us = std::max(20.0, 4.0 * M * (double)N * K / 1.0e9);   // (at 1 PFLOP/s; sizes the back-to-back boxes)
+    time_interleaved(cs, sets, rounds, 3, 0.05, est_us, e0, e1);
+    int max_rows = 0;
+    for (int g = 0; g < G; ++g) max_rows = std::max(max_rows, off[g + 1] - off[g]);
+    printf("{\"bench\": \"tn_grouped_gated\", \"G\": %d, \"rows_per_group\": %d, \"M\": %d, \"N\": %d, \"K\": %d, \"act\": %d, \"aux\": %d, \"routing\": \"%s\", \"max_rows\": %d, "
+           "\"config\": \"%s\", \"rounds\": %d, \"protocol\": \"interleaved\"", G, rows, M, N, K, act, aux ? 1 : 0, kind, max_rows, bgemm_mi355x_tn_config_name(cfg), rounds);
+    for (const Contender& ct : cs) printf(", \"%s_us\": %.2f, \"%s_stream_us\": %.2f", ct.key, ct.iso_us(), ct.key, ct.box_us());
+    const std::vector<float>& r3 = cs[2].iso;
+    const double spread = r3.empty() ? -1.0 : (double)*std::max_element(r3.begin(), r3.end()) / (double)*std::min_element(r3.begin(), r3.end());
+    printf(", \"gated_over_grouped2n\": %.3f, \"grouped2n_spread\": %.3f, \"loop_over_gated\": %.3f, \"loop_over_gated_stream\": %.3f, \"gated_over_g1\": %.3f}\n",
+           cs[0].iso_us() / cs[2].iso_us(), spread, cs[1].iso_us() / cs[0].iso_us(), cs[1].box_us() / cs[0].box_us(), cs[0].iso_us() / cs[3].iso_us());
+    fflush(stdout);
+  }
+  HIP_OK(hipFree(a)); HIP_OK(hipFree(w)); HIP_OK(hipFree(x)); HIP_OK(hipFree(c)); HIP_OK(hipFree(gu)); HIP_OK(hipFree(off_d)); HIP_OK(hipFree(off_g1));
+  return 0;
+}
+static int cmd_grouped_gated(const std::string& mode, int argc, char** argv) {
+  int G = 8, rows = 64, N = 4096, K = 4096, rounds = 30, act = HGEMM_ACT_SILU;
+  bool aux = false;
+  const char* cfg_name = nullptr;
+  for (int i = 2; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--aux") { aux = true; continue; }
+    if (i + 1 >= argc) break;
+    if (a == "--groups") G = atoi(argv[++i]); else if (a == "--rows") rows = atoi(argv[++i]); else if (a == "--n") N = atoi(argv[++i]);
+    else if (a == "--k") K = atoi(argv[++i]); else if (a == "--rounds") rounds = atoi(argv[++i]); else if (a == "--config") cfg_name = argv[++i];
+    else if (a == "--act") {
+      const std::string v = argv[++i];
+      act = v == "relu" ? HGEMM_ACT_RELU : v == "gelu" ? HGEMM_ACT_GELU : v == "gelu_tanh" ? HGEMM_ACT_GELU_TANH : HGEMM_ACT_SILU;
+    }
+  }
+  if (mode == "check") return grouped_gated_check();
+  if (mode == "bench") return grouped_gated_bench(G, rows, N, K, act, aux, cfg_name, rounds);
+  fprintf(stderr, "--tn-grouped-gated goes with check or bench\n");
+  return 2;
+}
+
 // ---- check|bench --ta-grouped: bgemm_mi355x_launch_ta_grouped / _ta_grouped_c32 (each group's K walk read from device offsets) --------------------
 //   check: four members x {c32 store, c32 accumulate, bf16} x {plain, NT store} x a handful of routings, the member's kernel against the grouped
 //          TA REFERENCE kernel (the same call with C moved 8 bytes: misaligned, so the reference kernel answers) on integer operands whose sums
@@ -2752,6 +2898,8 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "--grouped") || !strcmp(argv[i], "--nn-grouped")) return cmd_grouped(mode, argv[i][2] == 'n', argc, argv);
   for (int i = 2; i < argc; ++i)
     if (!strcmp(argv[i], "--ta-grouped")) return cmd_ta_grouped(mode, argc, argv);
+  for (int i = 2; i < argc; ++i)
+    if (!strcmp(argv[i], "--tn-grouped-gated")) return cmd_grouped_gated(mode, argc, argv);
   TrFlags tr;   // --layout, --bf16, --c32, --bias, --act, --aux, --dact, --dbias
   std::vector<Shape> shapes;
   const char* out_path = nullptr;

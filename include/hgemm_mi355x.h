@@ -786,8 +786,8 @@ int bgemm_mi355x_nn_add_runs(int nn_config, int M, int N, int K, int lda, int ld
  * anything else is answered by the grouped reference kernel (status 0, the same semantics, slow: bgemm_mi355x_tn_grouped_runs tells).
  * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL a, b_col_major, c or offsets; G < 1; M, N or K < 1; lda < K, ldb < K, ldc < N,
  * ldbias < N (with a bias); group_stride_b < (N - 1) ldb + K; an id outside the table; more than one split in the word.
- * Out of scope: the grouped gated forward, fp16, int64 offsets (the weight gradient: bgemm_mi355x_ta_grouped, the input gradient:
- * bgemm_mi355x_nn_grouped). */
+ * Out of scope: fp16, int64 offsets (the gated forward: bgemm_mi355x_tn_grouped_gated, the weight gradient: bgemm_mi355x_ta_grouped, the
+ * input gradient: bgemm_mi355x_nn_grouped). */
 #define HGEMM_GROUPED_MAX_GROUPS 256
 /* planned, contiguous (lda = ldb = K, group_stride_b = N K, ldbias = ldc = N) */
 int bgemm_mi355x_tn_grouped(const void* a, const void* b_col_major, const void* bias, void* c, const int* offsets, int G, int M, int N, int K,
@@ -830,8 +830,8 @@ int bgemm_mi355x_tn_grouped_plan(int G, int M, int N, int K, int* tn_config);
  * (status 0, the same semantics, slow: bgemm_mi355x_ta_grouped_runs / _c32_runs tell).
  * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL pointer; G, M, N or K < 1; lda < M, ldb < N or ldc < N;
  * group_stride_c < (M - 1) ldc + N; an id outside the table; accumulate outside {0, 1}; more than one split in the word.
- * Out of scope: the grouped gated forward, a grouped bias gradient, fp16, int64 offsets, splitting a heavy group's walk (the input
- * gradient: bgemm_mi355x_nn_grouped). */
+ * Out of scope: a grouped bias gradient, fp16, int64 offsets, splitting a heavy group's walk (the gated forward:
+ * bgemm_mi355x_tn_grouped_gated, the input gradient: bgemm_mi355x_nn_grouped). */
 /* planned, contiguous (lda = M, ldb = ldc = N, group_stride_c = M N) */
 int bgemm_mi355x_ta_grouped_c32(const void* a_col_major, const void* b, float* c32, const int* offsets, int G, int M, int N, int K, int accumulate,
                                 void* stream);
@@ -875,7 +875,7 @@ int bgemm_mi355x_ta_grouped_plan(int G, int M, int N, int K, int* ta_config);
  * bgemm_mi355x_nn_grouped_runs tells).
  * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL a, b, c or offsets; G, M, N or K < 1; lda < K, ldb < N, ldc < N; ldr < N (with an
  * r); r == c with ldr != ldc; group_stride_b < (K - 1) ldb + N; an id outside the table; more than one split in the word.
- * Out of scope: the grouped gated forward, a dact / dgated epilogue, fp16, int64 offsets. */
+ * Out of scope: a dact / dgated epilogue, fp16, int64 offsets (the gated forward: bgemm_mi355x_tn_grouped_gated). */
 /* planned, contiguous (lda = K, ldb = N, group_stride_b = K N, ldr = ldc = N) */
 int bgemm_mi355x_nn_grouped(const void* a, const void* b, const void* r, void* c, const int* offsets, int G, int M, int N, int K, void* stream);
 int bgemm_mi355x_launch_nn_grouped(int nn_config, int word, const void* a, const void* b, const void* r, void* c, const int* offsets, int G, int M, int N,
@@ -884,6 +884,52 @@ int bgemm_mi355x_launch_nn_grouped(int nn_config, int word, const void* a, const
 int bgemm_mi355x_nn_grouped_runs(int nn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldr, int ldc);
 /* the member the planned call takes */
 int bgemm_mi355x_nn_grouped_plan(int G, int M, int N, int K, int* nn_config);
+
+/* ------------------------------------------------------------------------------------------
+ * Grouped gated forward, H_g = act(X_g Wg_g^T + bg_g) (.) (X_g Wu_g^T + bu_g) for every expert of a mixture-of-experts layer in ONE launch
+ * (SwiGLU / GeGLU expert MLPs), from the forward call's offsets; optionally the two pre-activations are saved for the backward pass.
+ * The rows of a, c, g_out and u_out are sorted by group; group g of G owns rows [offsets[g], offsets[g + 1]).
+ * Semantics, exactly, for every g, every row m of it and every n < N:
+ *     gv = fl32( sum_k a[m][k] Wg_g[n][k] + float(bias_g[g][n]) )     (fp32 accumulation, the bias as ONE fp32 add)
+ *     uv = fl32( sum_k a[m][k] Wu_g[n][k] + float(bias_u[g][n]) )
+ *     C[m][n]     = bf16_rne( fl32( act32(gv) x uv ) )                (act32: bgemm_mi355x_tn_gated's activation, one fp32 product)
+ *     g_out[m][n] = bf16_rne(gv),  u_out[m][n] = bf16_rne(uv)         (only when given; the activation and the gate see the UNROUNDED values)
+ *   - Wg_g = wg_col_major + g group_stride_b and Wu_g = wu_col_major + g group_stride_b, each [N][ldb] with K contiguous; one ldb and one
+ *     group_stride_b serve both.  A fused per-expert [2N][K] gate_up weight is wu = wg + N ldb with group_stride_b = 2N ldb.  wg == wu is
+ *     allowed.
+ *   - bias_g and bias_u are [G][ldbias] bf16; each may be NULL on its own (+0.0, bit for bit).
+ *   - `act` is HGEMM_ACT_RELU, _GELU, _GELU_TANH or _SILU, as in bgemm_mi355x_tn_gated.
+ *   - g_out and u_out are both NULL (the inference form) or both given (the training form), distinct from each other and from c, each
+ *     [M][ldz].  u_out = g_out + N with ldz >= 2N is the fused [M][2N] buffer bgemm_mi355x_nn_dgated reads.
+ *   - offsets is a DEVICE pointer to G + 1 int32, bgemm_mi355x_tn_grouped's vector under its contract: the host never reads it (no copy, no
+ *     synchronisation, no workspace), the call can be captured in a graph on a fresh stream with nothing reserved and a replay follows
+ *     whatever the buffer holds then; each offset is clamped to [0, M].  Rows that no group owns, and pad columns, are not written in any
+ *     of the three outputs.
+ *   - Bit for bit, same tn_config: G = 1 with offsets {0, M} gives bgemm_mi355x_launch_tn_gated's C (without g_out / u_out) and
+ *     bgemm_mi355x_launch_tn_gated_aux's three outputs (with them), unsplit, for every activation; for any G, g_out is the C of
+ *     bgemm_mi355x_launch_tn_grouped on (wg, bias_g) and u_out the same on (wu, bias_u).
+ *   - The bar on C is bgemm_mi355x_tn_gated's: |C - y*| <= 1/2 ulp_bf16(y*) + 2^-19 |g| |u| + 2^-23 |y*|; ReLU bit for bit.
+ * tn_config is one of bgemm_mi355x_tn_*'s four members; a member's tile is BM rows by BN / 2 output columns.  word: HGEMM_PLAN_NT_STORE is
+ * honoured for all outputs; its split count must be 1 (or 0) -- there is no split-K form.  The planned call takes the member
+ * bgemm_mi355x_tn_grouped_plan(G, M, 2N, K) names; there is no plan, table or workspace of this call's own.
+ * The members' kernels serve K % 64 == 0, N % 8 == 0, lda / ldb / ldc / ldz / ldbias / group_stride_b multiples of 8, 16-byte aligned
+ * pointers, (BM lda + K) 2, (BN / 2 ldb + K) 2 per weight, (BM ldc + N) 2 and (BM ldz + N) 2 bytes below 2 GiB, G <= HGEMM_GROUPED_MAX_GROUPS
+ * and a grid bound that fits an int; anything else is answered by the grouped gated reference kernel (status 0, the same semantics, slow:
+ * bgemm_mi355x_tn_grouped_gated_runs tells).
+ * Refused with HGEMM_ERR_BAD_ARG, nothing launched: a NULL a, wg, wu, c or offsets; exactly one of g_out / u_out; g_out == u_out or either
+ * equal to c; G, M, N or K < 1; lda < K, ldb < K, ldc < N, ldz < N (with g_out / u_out), ldbias < N (with a bias);
+ * group_stride_b < (N - 1) ldb + K; an id outside the table; an unknown act; more than one split in the word.
+ * Out of scope: a grouped dgated (the backward through the gate), fp16, int64 offsets, split-K. */
+/* planned, contiguous: lda = ldb = K, group_stride_b = N K (two separate [G][N][K] stacks), ldbias = ldc = ldz = N */
+int bgemm_mi355x_tn_grouped_gated(const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g, const void* bias_u, void* c,
+                                  void* g_out, void* u_out, const int* offsets, int G, int M, int N, int K, int act, void* stream);
+int bgemm_mi355x_launch_tn_grouped_gated(int tn_config, int word, const void* a, const void* wg_col_major, const void* wu_col_major, const void* bias_g,
+                                         const void* bias_u, void* c, void* g_out, void* u_out, const int* offsets, int G, int M, int N, int K, int lda,
+                                         int ldb, long long group_stride_b, int ldbias, int ldc, int ldz, int act, void* stream);
+/* 1 when the call (with aligned pointers) runs the member's kernel, 0 when the reference kernel answers or the call is refused; ldz = 0: no
+ * g_out / u_out */
+int bgemm_mi355x_tn_grouped_gated_runs(int tn_config, int G, int M, int N, int K, int lda, int ldb, long long group_stride_b, int ldbias, int ldc,
+                                       int ldz);
 
 const char* hgemm_mi355x_strerror(int status);
 int hgemm_mi355x_last_hip_error(void);   /* hipError_t behind the calling thread's last HGEMM_ERR_HIP */
